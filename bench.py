@@ -15,8 +15,23 @@ launcher WORLD_SIZE must equal N -- anything else is an error, not a 1-GPU run.
 
 Prints ONE JSON line (rank 0) following the driver's contract, extended with
   roofline      achieved algorithmic GB/s of the validity kernel vs the HBM roof
+                (from the HIP events of the timed steps themselves)
+
+A plain run does only what that line needs: set-up, warm-up, the timed steps,
+the line.  Everything else the benchmark measures or checks runs only with
+`--full`:
   cpu_baseline  the CPU oracle (this repo's C restatement -- NOT MuJoCo/OMPL)
-                timed on this box's host cores on the same states
+                timed on this box's host cores on the same states, + parity
+  sections      motion validation, RRT-Connect planner, per-scene validity,
+                env.step (kinematic / dynamics / contacts), IK, rollouts
+and the full record (every section, all prose) is written to
+bench_out/bench_full_n<N>.json.
+
+`--dump-outputs DIR` writes, after the timed steps, what the last timed step
+computed -- the verdict mask a caller of the path receives (all ranks' masks
+after the all-gather) -- as DIR/valid.npy (float32; a fixed, seeded sample with
+its indices in DIR/valid_index.npy when the mask is larger than 64 MB as float32).
+Inputs are seeded: the same arguments give the same inputs in every run.
 """
 from __future__ import annotations
 
@@ -605,6 +620,26 @@ def unsettle():
     gc.enable()
 
 
+DUMP_MAX_BYTES = 64 << 20
+DUMP_SAMPLE = 1 << 22
+
+
+def dump_outputs(d, valid):
+    """--dump-outputs: the verdict mask of the last timed step as d/valid.npy (float32, one value per state in batch order; with
+    several ranks the all-gathered mask every rank receives).  A mask over DUMP_MAX_BYTES as float32 is sampled: DUMP_SAMPLE states
+    drawn with a fixed seed, their indices in d/valid_index.npy (float64)."""
+    os.makedirs(d, exist_ok=True)
+    v = valid.cpu().numpy().astype(np.float32)
+    index = os.path.join(d, "valid_index.npy")
+    if v.nbytes > DUMP_MAX_BYTES:
+        idx = np.sort(np.random.default_rng(0).choice(v.size, size=DUMP_SAMPLE, replace=False))
+        np.save(index, idx.astype(np.float64))
+        v = v[idx]
+    elif os.path.exists(index):
+        os.remove(index)          # (left by an earlier, larger run into the same directory)
+    np.save(os.path.join(d, "valid.npy"), v)
+
+
 def lib_sha256():
     import hashlib
     from mopa_rl_amd import _lib
@@ -712,8 +747,8 @@ def exchange_preflight(torch, dist, world, rank, device):
 
 def headline(out):
     """The ONE line the driver parses: the contract's keys, `roofline`, `cpu_baseline`, the parity count and a numeric summary of
-    every section -- no prose (the per-section blocks are in gpurun_out/bench_full_n<N>.json and on stderr).  Pure function of
-    the full record: tests/test_bench_headline.py holds it under HEADLINE_MAX_BYTES on a canned record."""
+    every section -- no prose (with --full the per-section blocks are in the full record file, `full_record`).  Pure function of
+    the record: tests/test_bench_headline.py holds it under HEADLINE_MAX_BYTES on a canned record."""
     rf = out.get("roofline") or {}
     cb = out.get("cpu_baseline")
     ro_keys = [k for k in out if k.startswith("rollout")]
@@ -755,7 +790,8 @@ def headline(out):
         "rollout_envs_stepping_per_call": {k[8:] or "lockstep": _g(out[k], "envs_stepping_per_call") for k in ro_keys},
         "parity_mismatches": parity,
     }
-    h["full_record"] = f"gpurun_out/bench_full_n{out.get('n_gpus')}.json"
+    h["full"] = out.get("full")
+    h["full_record"] = out.get("full_record")           # path of the full record (--full runs), else None
     h = _r(h)
     if len(json.dumps(h, separators=(",", ":"))) > HEADLINE_MAX_BYTES:       # never again a line the driver cannot keep: drop the summary first
         h["summary"] = {"dropped": "headline over the byte budget; see the full record"}
@@ -769,6 +805,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--envs", type=int, default=4096, help="envs per GPU")
     ap.add_argument("--samples", type=int, default=256, help="states per env per step")
+    ap.add_argument("--full", action="store_true", help="also run everything beyond the headline: CPU baselines + parity, the motion / "
+                    "planner / scenes / env.step / IK / rollout sections, and write the full record to bench_out/bench_full_n<N>.json (the --no-* flags "
+                    "below select among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one computed "
+                    "(the verdict mask) as DIR/valid.npy, float32")
     ap.add_argument("--cpu-states", type=int, default=1 << 20, help="states timed on the CPU oracle (rank 0, N=1)")
     ap.add_argument("--mode", default="mixed", choices=["mixed", "near", "uniform"],
                     help="state distribution: the headline workload is `mixed` (50%% uniform joint-box, 50%% near-init)")
@@ -785,6 +826,8 @@ def main():
 
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # launch the ranks ourselves: one process per GPU under torch.distributed.run (reference rank set-up: rl/main.py:24-35)
         import socket
@@ -904,6 +947,8 @@ def main():
         dist.all_gather(km, torch.tensor([kern_ms], dtype=torch.float64, device=cdev))
         kern_ms_ranks = [round(float(x.item()), 6) for x in km]      # a slow rank shows here (the headline's roofline is rank 0's kernel)
     valid = og.local[(args.steps - 1) % og.depth] if args.steps > 0 else og.local[0]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, og.result(args.steps - 1))
 
     n_valid = int(valid.sum().item())
     if rank == 0:
@@ -914,7 +959,7 @@ def main():
         out = {
             "metric": "valid-state collision checks/sec", "value": value, "unit": "checks/s", "n_gpus": world,
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3,
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic", "full": args.full,
             "config": {"workload": f"{ENV} state validity (FK + collision), {E} envs/GPU x {S} states/env per step, "
                                    + {"mixed": "states 50% uniform joint-box samples + 50% near-init N(0,0.3)", "near": "states near-init N(0,0.3)",
                                       "uniform": "states uniform in the joint box"}[args.mode],
@@ -946,14 +991,15 @@ def main():
                 out["roofline"]["valu"] = {"achieved": ach, "peak": peak, "unit": "wave-instr/s", "frac": ach / peak,
                                            "insts_per_check": t["valu_insts_per_launch"] / t["states_per_launch"],
                                            "note": "SQ_INSTS_VALU from the committed PMC pass / live kernel time"}
-        if not args.no_plan and world == 1:
+        # everything below the headline runs with --full only
+        if args.full and not args.no_plan and world == 1:
             out["motion"] = motion_section(torch, bp, pi, qa, rows, S, device)
             out["planner"] = plan_section(torch, bp, pi, args.plan_envs, device, not args.no_cpu)
-        if not args.no_env and world == 1:
+        if args.full and not args.no_env and world == 1:
             out["scenes"] = scenes_section(torch, device, E, S)
             out["env_step"] = env_step_section(torch, args.envs, device, 50, not args.no_cpu)
             out["ik"] = ik_section(torch, device)
-        if not args.no_cpu and world == 1:
+        if args.full and not args.no_cpu and world == 1:
             cb = cpu_baseline(pi, qa.cpu().numpy(), rows.cpu().numpy(), S, args.cpu_states)
             mism = int((cb["verdicts"] != valid[: cb["n"]].cpu().numpy()).sum())
             out["cpu_baseline"] = {
@@ -964,7 +1010,7 @@ def main():
     # the rollout sections run on EVERY rank (their exchanges are collectives): config 3 (Push) at one GPU, config 4
     # (Lift: env shard + all-gather of the rollout transitions + gradient all-reduce) at any rank count
     ro = {}
-    if not args.no_rollout:
+    if args.full and not args.no_rollout:
         if world == 1:
             ro["rollout"] = rollout_section(torch, ENV, args.envs, device, 3)
             ro["rollout_async"] = rollout_section(torch, ENV, args.envs, device, 300, async_planner=True)     # (a retry launch lives ~25 calls: 300 calls = 12 of its cycles)
@@ -983,17 +1029,21 @@ def main():
                                                     use_ik=True)
     if rank == 0:
         out.update(ro)
-        # the full record (every section, all prose) goes to a file + stderr; stdout ends with ONE compact line (< 4 KB)
-        full = json.dumps(out)
-        try:
-            os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
-            with open(os.path.join(ROOT, "gpurun_out", f"bench_full_n{world}.json"), "w") as f:
-                f.write(full + "\n")
-        except OSError:
-            pass
-        if os.environ.get("MOPA_BENCH_FULL_STDERR"):
-            print("[bench full record] " + full, file=sys.stderr)
-            sys.stderr.flush()
+        out["full_record"] = None
+        if args.full:
+            # the full record (every section, all prose) goes to a file + stderr; stdout ends with ONE compact line (< 4 KB)
+            path = os.path.join("bench_out", f"bench_full_n{world}.json")
+            try:
+                os.makedirs(os.path.join(ROOT, "bench_out"), exist_ok=True)
+                out["full_record"] = path
+                with open(os.path.join(ROOT, path), "w") as f:
+                    f.write(json.dumps(out) + "\n")
+            except OSError as e:
+                out["full_record"] = None
+                print(f"[bench] full record not written: {e}", file=sys.stderr)
+            if os.environ.get("MOPA_BENCH_FULL_STDERR"):
+                print("[bench full record] " + json.dumps(out), file=sys.stderr)
+                sys.stderr.flush()
         print(json.dumps(headline(out), separators=(",", ":")))
         sys.stdout.flush()
     if world > 1:

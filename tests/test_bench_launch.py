@@ -43,7 +43,7 @@ def test_world_size_mismatch_is_an_error():
 def test_gpus_2_full_bench_on_one_device():
     """Two ranks pinned to the same GPU over gloo (test knobs): the whole multi-rank bench path incl. the collectives."""
     r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--steps", "2", "--warmup", "1", "--envs", "256", "--samples", "64",
-                        "--no-rollout"], env=_env(MOPA_BENCH_DEVICE="0"), capture_output=True, text=True, timeout=600)
+                        "--full", "--no-rollout"], env=_env(MOPA_BENCH_DEVICE="0"), capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert out["n_gpus"] == 2 and out["exchange"]["ranks"] == 2 and out["value"] > 0

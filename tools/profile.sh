@@ -24,7 +24,7 @@ run() {  # name, rocprof args...
 run trace --kernel-trace --stats
 if [ "$MODE" = all ]; then
 # all kernels of the default bench (planner K3, env step K4, IK K5, rollout) in one kernel-trace pass
-BENCH_SAVE=$BENCH; BENCH="python $R/bench.py --no-cpu --steps 5 --warmup 2"
+BENCH_SAVE=$BENCH; BENCH="python $R/bench.py --full --no-cpu --steps 5 --warmup 2"
 run full --kernel-trace --stats
 BENCH=$BENCH_SAVE
 fi
@@ -33,7 +33,7 @@ run pmc_sq2 --kernel-trace --pmc SQ_ACTIVE_INST_ANY SQ_WAIT_ANY SQ_LDS_BANK_CONF
 run pmc_fetch --kernel-trace --pmc FETCH_SIZE
 if [ "$MODE" = all ]; then
 # the planner kernel's counters (bench with the planner section only)
-BENCH_SAVE=$BENCH; BENCH="python $R/bench.py --no-cpu --no-env --no-rollout --steps 2 --warmup 1"
+BENCH_SAVE=$BENCH; BENCH="python $R/bench.py --full --no-cpu --no-env --no-rollout --steps 2 --warmup 1"
 run pmc_plan --kernel-trace --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAIT_INST_ANY
 BENCH=$BENCH_SAVE
 fi

@@ -26,6 +26,6 @@ tools/ubench/bin/lone_wave > $O/lone_wave.txt 2>&1
 bash tools/k7_icache.sh ${TAG}_k7ic > $O/k7_icache.txt 2>&1
 python tools/k3_build_ab.py 2>&1 | grep -v amdgpu.ids > $O/k3_build_ab.txt
 python tools/ct_tail.py 2>&1 | grep -v amdgpu.ids > $O/ct_tail.txt
-python bench.py > $O/bench_line.json 2> $O/bench.err
-cp gpurun_out/bench_full_n1.json $O/bench_line_full.json
+python bench.py --full > $O/bench_line.json 2> $O/bench.err
+cp bench_out/bench_full_n1.json $O/bench_line_full.json
 tail -3 $O/*.txt | cut -c1-200
