@@ -171,6 +171,14 @@ int mopa_scene_lds_bytes(const MopaScene *scene);
 /* name of the validity kernel mopa_is_valid_batch dispatches for a batch of N states on this scene ("k_is_valid_v5",
  * "k_is_valid_v2" or "k_is_valid"); the benchmark labels its roofline line and selects profiler rows with it */
 int mopa_scene_valid_kernel(const MopaScene *scene, int64_t N, char *out, int32_t cap /* >= 24 */);
+/* k_is_valid_v5 on this scene: 0 = the generic instantiation, i > 0 = the i-th baked scene (mopa_valid_v5_baked.inc) */
+int mopa_scene_k1_baked(const MopaScene *scene);
+/* host-only export of what k_is_valid_v5 reads from a scene (no device needed; tools/bake_k1_scenes.py):
+ * sizes[8] = n_dbl, n_int, n_tab, sizeof(SceneHdr), use_v5, centre table in LDS, mesh pairs, moving geoms;
+ * dbl / ints / tab / hdr (nullable) receive the two blobs, the FP32 pair table and the header, *fingerprint (nullable)
+ * the 64-bit FNV-1a hash over those bytes that selects a baked instantiation */
+int mopa_scene_k1_export(const MopaSceneDesc *desc, int64_t *sizes /*[8]*/, double *dbl, int32_t *ints, int32_t *tab, void *hdr,
+                         uint64_t *fingerprint);
 
 /* N states: state i = qpos_env[i / samples_per_env] with its active entries replaced by q_active[i].
  * valid[i] = 1 iff no non-ignored pair has dist <= contact_threshold.

@@ -25,6 +25,7 @@ _ip = C.POINTER(C.c_int32)
 EXPORTED_SYMBOLS = [
     "mopa_last_error", "mopa_version", "mopa_device_count", "mopa_scene_create", "mopa_scene_destroy",
     "mopa_scene_num_active", "mopa_scene_active_idx", "mopa_scene_num_pairs", "mopa_scene_lds_bytes", "mopa_scene_valid_kernel",
+    "mopa_scene_k1_baked", "mopa_scene_k1_export",
     "mopa_is_valid_batch", "mopa_check_motion_batch", "mopa_plan_batch", "mopa_pullback_batch", "mopa_is_valid_state", "mopa_plan",
     "mopa_planner_status", "mopa_debug_fk", "mopa_debug_pair_dist",
     "mopa_env_create", "mopa_env_destroy", "mopa_env_obs_dim", "mopa_env_action_dim", "mopa_env_step_batch", "mopa_env_exec_batch", "mopa_env_desired_batch",
@@ -205,6 +206,8 @@ def lib() -> C.CDLL:
     L.mopa_ik_site_pose_batch.argtypes = [vp, C.c_int64, vp, vp, vp, vp]
     L.mopa_ik_targets_batch.argtypes = [vp, C.c_int64, vp, vp, vp, C.c_int64, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double), vp, vp, vp]
     L.mopa_scene_valid_kernel.argtypes = [vp, C.c_int64, C.c_char_p, C.c_int32]
+    L.mopa_scene_k1_baked.argtypes = [vp]
+    L.mopa_scene_k1_export.argtypes = [vp, vp, vp, vp, vp, vp, vp]
     i32, i64, f64 = C.c_int32, C.c_int64, C.c_double
     L.mopa_paths_unwrap_batch.argtypes = [C.c_int, i64, i32, i32, vp, i32, vp, vp, vp, f64, i32, vp, vp, vp, vp, vp, vp, vp, vp]
     L.mopa_paths_unwrap_seam_batch.argtypes = [C.c_int, i64, i32, i32, vp, i32, vp, vp, vp, f64, i32, vp, vp, vp, vp, vp, vp, vp, C.c_uint64, vp]
@@ -248,6 +251,78 @@ def model_struct(m, keep: list, pair_geom=None) -> MopaModel:
         len(m.mesh_vertnum), len(m.mesh_vert), i(m.mesh_vertadr), i(m.mesh_vertnum), d(m.mesh_vert), i(m.geom_dataid))
 
 
+def scene_desc(model, passive_joint_idx, ignored_contacts, contact_threshold: float, range_: float = 0.1, resolution: float = 0.005,
+               seed: int = 0, device: int = -1, prune_pairs: Optional[bool] = None):
+    """The MopaSceneDesc that Scene hands to mopa_scene_create (pair pruning and per-pair cull radii applied as described
+    there) + the numpy buffers it points at + (pairs pruned, pairs with a tightened cull radius)."""
+    m = model
+    keep = []
+    if prune_pairs is None:
+        prune_pairs = os.environ.get("MOPA_PRUNE_PAIRS", "1") != "0"
+    pairs = np.asarray(m.pair_geom, dtype=np.int32).reshape(-1, 2)
+    meta = getattr(m, "meta", {})
+    never = list(meta.get("never_violating_pairs") or [])
+    at = meta.get("never_violating_pairs_thr") or {}
+    if at and float(contact_threshold) <= float(at.get("threshold", -np.inf)):
+        never += list(at.get("pairs") or [])      # may touch, never reach a threshold this negative
+    npair_pruned = 0
+    if prune_pairs and len(never) and float(contact_threshold) <= 0.0:
+        drop = {(int(a), int(b)) for a, b in never} | {(int(b), int(a)) for a, b in never}
+        keep_row = np.array([(int(a), int(b)) not in drop for a, b in pairs], dtype=bool)
+        npair_pruned = int((~keep_row).sum())
+        pairs = np.ascontiguousarray(pairs[keep_row])
+
+    def d(a):
+        a, p = _d(a); keep.append(a); return p
+
+    def i(a):
+        a, p = _i(a); keep.append(a); return p
+
+    ign = np.asarray(list(ignored_contacts), dtype=np.int32).reshape(-1, 2)
+    pas = np.asarray(list(passive_joint_idx), dtype=np.int32)
+    desc = MopaSceneDesc()
+    desc.model = model_struct(m, keep, pair_geom=pairs)
+    # per-pair bound on the centre distance at which the pair can reach the threshold (same proof machinery): the FP32
+    # broad phase culls with it instead of the bounding-sphere sum (closed gripper fingers: 9 mm instead of 10 cm)
+    cr = meta.get("pair_cull_radius") or {}
+    npair_tightened = 0
+    if prune_pairs and cr and float(contact_threshold) <= float(cr.get("threshold", -np.inf)):
+        rad = {(int(a), int(b)): float(r) for a, b, r in cr.get("pairs") or []}
+        arr = np.array([rad.get((int(a), int(b)), rad.get((int(b), int(a)), 0.0)) for a, b in pairs], dtype=np.float64)
+        if (arr > 0).any():
+            npair_tightened = int((arr > 0).sum())
+            desc.pair_cull_radius = d(arr)
+    desc.n_passive = len(pas)
+    desc.passive_qpos_idx = i(pas)
+    desc.n_ignored = len(ign)
+    desc.ignored_pairs = i(ign)
+    desc.contact_threshold = float(contact_threshold)
+    desc.range = float(range_)
+    desc.resolution = float(resolution)
+    desc.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    desc.device = int(device)
+    return desc, keep, npair_pruned, npair_tightened
+
+
+def k1_export(*args, **kw) -> dict:
+    """Host-only export of what k_is_valid_v5 reads from a scene (mopa_scene_k1_export: no device needed); the arguments are
+    those of Scene.  Returns the two blobs, the FP32 pair table, the header bytes, the fingerprint and the launch facts."""
+    L = lib()
+    desc, keep, _, _ = scene_desc(*args, **kw)
+    sizes = np.zeros(8, dtype=np.int64)
+    check(L.mopa_scene_k1_export(C.byref(desc), sizes.ctypes.data_as(C.c_void_p), None, None, None, None, None))
+    dbl = np.zeros(int(sizes[0]), dtype=np.float64)
+    ints = np.zeros(int(sizes[1]), dtype=np.int32)
+    tab = np.zeros(int(sizes[2]), dtype=np.int32)
+    hdr = np.zeros(int(sizes[3]), dtype=np.uint8)
+    fp = C.c_uint64()
+    check(L.mopa_scene_k1_export(C.byref(desc), sizes.ctypes.data_as(C.c_void_p), dbl.ctypes.data_as(C.c_void_p), ints.ctypes.data_as(C.c_void_p),
+                                 tab.ctypes.data_as(C.c_void_p), hdr.ctypes.data_as(C.c_void_p), C.byref(fp)))
+    del keep
+    return {"dbl": dbl, "ints": ints, "tab": tab, "hdr": hdr, "fingerprint": int(fp.value), "use_v5": bool(sizes[4]),
+            "cen_lds": bool(sizes[5]), "n_mesh_pairs": int(sizes[6]), "nmg": int(sizes[7])}
+
+
 class Scene:
     """Owns one MopaScene* (== one KinematicPlanner instance of the reference)."""
 
@@ -262,61 +337,18 @@ class Scene:
         is_valid(guard=True)`, send a state with a joint beyond range + band through a sibling scene with the full pair list."""
         L = lib()
         m = model
-        keep = []
-        if prune_pairs is None:
-            prune_pairs = os.environ.get("MOPA_PRUNE_PAIRS", "1") != "0"
-        pairs = np.asarray(m.pair_geom, dtype=np.int32).reshape(-1, 2)
-        meta = getattr(m, "meta", {})
-        never = list(meta.get("never_violating_pairs") or [])
-        at = meta.get("never_violating_pairs_thr") or {}
-        if at and float(contact_threshold) <= float(at.get("threshold", -np.inf)):
-            never += list(at.get("pairs") or [])      # may touch, never reach a threshold this negative
-        self.npair_pruned = 0
-        self._full = None
         self._ctor = (model, list(passive_joint_idx), list(ignored_contacts), float(contact_threshold), float(range_), float(resolution), int(seed),
                       int(device))
+        self._full = None
         # the box inside which the pruning is proven: range + guard band of every limited joint (scenes proven without a band: the range)
-        band = meta.get("prune_guard_band") or {}
+        band = getattr(m, "meta", {}).get("prune_guard_band") or {}
         lim = np.asarray(m.jnt_limited).astype(bool) & (np.asarray(m.jnt_type) != 0)
         bw = np.where(np.asarray(m.jnt_type) == 2, float(band.get("slide", 0.0)), float(band.get("hinge", 0.0)))
         self.guard_adr = np.asarray(m.jnt_qposadr, dtype=np.int64)[lim]
         self.guard_lo = (np.asarray(m.jnt_range, dtype=np.float64)[:, 0] - bw)[lim]
         self.guard_hi = (np.asarray(m.jnt_range, dtype=np.float64)[:, 1] + bw)[lim]
-        if prune_pairs and len(never) and float(contact_threshold) <= 0.0:
-            drop = {(int(a), int(b)) for a, b in never} | {(int(b), int(a)) for a, b in never}
-            keep_row = np.array([(int(a), int(b)) not in drop for a, b in pairs], dtype=bool)
-            self.npair_pruned = int((~keep_row).sum())
-            pairs = np.ascontiguousarray(pairs[keep_row])
-
-        def d(a):
-            a, p = _d(a); keep.append(a); return p
-
-        def i(a):
-            a, p = _i(a); keep.append(a); return p
-
-        ign = np.asarray(list(ignored_contacts), dtype=np.int32).reshape(-1, 2)
-        pas = np.asarray(list(passive_joint_idx), dtype=np.int32)
-        desc = MopaSceneDesc()
-        desc.model = model_struct(m, keep, pair_geom=pairs)
-        # per-pair bound on the centre distance at which the pair can reach the threshold (same proof machinery): the FP32
-        # broad phase culls with it instead of the bounding-sphere sum (closed gripper fingers: 9 mm instead of 10 cm)
-        cr = meta.get("pair_cull_radius") or {}
-        self.npair_tightened = 0
-        if prune_pairs and cr and float(contact_threshold) <= float(cr.get("threshold", -np.inf)):
-            rad = {(int(a), int(b)): float(r) for a, b, r in cr.get("pairs") or []}
-            arr = np.array([rad.get((int(a), int(b)), rad.get((int(b), int(a)), 0.0)) for a, b in pairs], dtype=np.float64)
-            if (arr > 0).any():
-                self.npair_tightened = int((arr > 0).sum())
-                desc.pair_cull_radius = d(arr)
-        desc.n_passive = len(pas)
-        desc.passive_qpos_idx = i(pas)
-        desc.n_ignored = len(ign)
-        desc.ignored_pairs = i(ign)
-        desc.contact_threshold = float(contact_threshold)
-        desc.range = float(range_)
-        desc.resolution = float(resolution)
-        desc.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
-        desc.device = int(device)
+        desc, keep, self.npair_pruned, self.npair_tightened = scene_desc(model, passive_joint_idx, ignored_contacts, contact_threshold, range_,
+                                                                         resolution, seed, device, prune_pairs)
         h = C.c_void_p()
         check(L.mopa_scene_create(C.byref(desc), C.byref(h)))
         self._h = h

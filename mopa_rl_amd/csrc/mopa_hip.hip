@@ -17,8 +17,10 @@
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <cstddef>
 #include <cstring>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include <map>
@@ -134,6 +136,7 @@ struct MopaScene {
     int v5_lds_bytes = 0;        // verdict-only instantiations of k_is_valid_v5 (hdr.v5_ent_cap entries per wave)
     int v5_lds_bytes_md = 0, v5_ent_cap_md = 0;   // depth-reporting instantiations
     int use_v5 = 0;
+    int k1_baked = 0;         // k_is_valid_v5 on a baked scene: its index in MOPA_K1_BAKED_SCENES (0: the generic instantiation)
     bool v5_cen_lds = true;   // FP32 centre table of a tile in LDS (false: read back from the pose slab; scenes with many moving geoms)
     bool v2_forced = false;   // MOPA_VALID_KERNEL=v2: lane-per-state kernel for every N >= 64 (tests, A/B runs)
     // Launch scratch, one set PER STREAM: a scene may be driven from several streams at once (validity on one stream while
@@ -549,8 +552,9 @@ struct Builder {
 
 }  // namespace
 
-extern "C" int mopa_scene_create(const MopaSceneDesc *desc, MopaScene **out) {
-    if (!desc || !out) return fail(MOPA_ERR_INVALID_ARG, "null argument");
+// Host half of scene creation: every table the kernels read (blobs, header, FP32 pair table) from the description,
+// no device needed (mopa_scene_k1_export runs it on its own; tools/bake_k1_scenes.py bakes scenes from it).
+static int scene_build_host(const MopaSceneDesc *desc, MopaScene *S) {
     const MopaModel &m = desc->model;
     if (m.nq <= 0 || m.nbody <= 0 || m.ngeom < 0) return fail(MOPA_ERR_INVALID_ARG, "empty model");
     if (m.ngeom > 255) return fail(MOPA_ERR_LIMIT, "more than 255 collidable geoms");
@@ -579,7 +583,6 @@ extern "C" int mopa_scene_create(const MopaSceneDesc *desc, MopaScene **out) {
         }
     }
 
-    MopaScene *S = new MopaScene();
     S->nq = m.nq;
     S->seed = desc->seed;
     S->ngeom_model = m.ngeom;
@@ -589,7 +592,7 @@ extern "C" int mopa_scene_create(const MopaSceneDesc *desc, MopaScene **out) {
     std::vector<char> is_passive(m.nq, 0);
     for (int i = 0; i < desc->n_passive; i++) {
         int a = desc->passive_qpos_idx[i];
-        if (a < 0 || a >= m.nq) { delete S; return fail(MOPA_ERR_INVALID_ARG, "passive_qpos_idx out of range"); }
+        if (a < 0 || a >= m.nq) { return fail(MOPA_ERR_INVALID_ARG, "passive_qpos_idx out of range"); }
         is_passive[a] = 1;
     }
     std::vector<int> qpos_jnt(m.nq, -1);
@@ -604,9 +607,8 @@ extern "C" int mopa_scene_create(const MopaSceneDesc *desc, MopaScene **out) {
     for (int i = 0; i < m.nq; i++) {
         if (is_passive[i]) continue;
         int j = qpos_jnt[i];
-        if (j < 0) { delete S; return fail(MOPA_ERR_INVALID_ARG, "active qpos address without a joint"); }
+        if (j < 0) { return fail(MOPA_ERR_INVALID_ARG, "active qpos address without a joint"); }
         if (m.jnt_type[j] == J_FREE || m.jnt_type[j] == J_BALL) {
-            delete S;
             return fail(MOPA_ERR_UNSUPPORTED, "free/ball joints cannot be planned over (only hinge/slide are active in the reference scenes)");
         }
         active_slot[i] = (int)act_adr.size();
@@ -632,11 +634,9 @@ extern "C" int mopa_scene_create(const MopaSceneDesc *desc, MopaScene **out) {
             const int id = (m.nmesh > 0 && m.geom_dataid) ? m.geom_dataid[g] : -1;
             if (id < 0 || id >= m.nmesh || !m.mesh_vert || m.mesh_vertnum[id] <= 0 ||
                 m.mesh_vertadr[id] < 0 || m.mesh_vertadr[id] + m.mesh_vertnum[id] > m.nmeshvert) {
-                delete S;
                 return fail(MOPA_ERR_INVALID_ARG, "mesh geom " + std::to_string(g) + " without a convex hull (MopaModel.geom_dataid / mesh_vert)");
             }
         } else if (!(t == G_PLANE || t == G_SPHERE || t == G_CAPSULE || t == G_CYLINDER || t == G_BOX)) {
-            delete S;
             return fail(MOPA_ERR_UNSUPPORTED, "collidable geom type " + std::to_string(t) + " (ellipsoid/hfield) is not supported");
         }
     }
@@ -700,8 +700,8 @@ extern "C" int mopa_scene_create(const MopaSceneDesc *desc, MopaScene **out) {
         mb_jntnum.push_back(m.body_jntnum[b]);
         for (int j = m.body_jntadr[b]; j < m.body_jntadr[b] + m.body_jntnum[b]; j++) {
             int t = m.jnt_type[j];
-            if (t == J_BALL) { delete S; return fail(MOPA_ERR_UNSUPPORTED, "ball joints are not supported (the reference throws as well: mujoco_ompl_interface.cpp:217-229)"); }
-            if (t == J_FREE && m.body_jntnum[b] != 1) { delete S; return fail(MOPA_ERR_UNSUPPORTED, "free joint combined with other joints"); }
+            if (t == J_BALL) { return fail(MOPA_ERR_UNSUPPORTED, "ball joints are not supported (the reference throws as well: mujoco_ompl_interface.cpp:217-229)"); }
+            if (t == J_FREE && m.body_jntnum[b] != 1) { return fail(MOPA_ERR_UNSUPPORTED, "free joint combined with other joints"); }
             mj_type.push_back(t);
             mj_axis.insert(mj_axis.end(), m.jnt_axis + 3 * j, m.jnt_axis + 3 * j + 3);
             mj_pos.insert(mj_pos.end(), m.jnt_pos + 3 * j, m.jnt_pos + 3 * j + 3);
@@ -711,7 +711,7 @@ extern "C" int mopa_scene_create(const MopaSceneDesc *desc, MopaScene **out) {
                 int first = passive_slot(adr);
                 for (int c = 1; c < 7; c++) {
                     int sl = passive_slot(adr + c);
-                    if (sl != first + c) { delete S; return fail(MOPA_ERR_UNSUPPORTED, "free joint qpos not contiguous in the passive list"); }
+                    if (sl != first + c) { return fail(MOPA_ERR_UNSUPPORTED, "free joint qpos not contiguous in the passive list"); }
                 }
                 mj_qsrc.push_back(first);
             } else {
@@ -763,14 +763,14 @@ extern "C" int mopa_scene_create(const MopaSceneDesc *desc, MopaScene **out) {
         }
     }
     const int nmg = (int)mg_geom.size();
-    if (nmg > 64) { delete S; return fail(MOPA_ERR_LIMIT, "more than 64 moving collidable geoms"); }
+    if (nmg > 64) { return fail(MOPA_ERR_LIMIT, "more than 64 moving collidable geoms"); }
 
     // pairs: drop ignored (mujoco_ompl_interface.cpp:950-960), sort by narrow-phase cost class
     struct PairE { int code, g1, g2, model_idx; };
     std::vector<PairE> pairs;
     for (int p = 0; p < m.npair; p++) {
         int g1 = m.pair_geom[2 * p], g2 = m.pair_geom[2 * p + 1];
-        if (g1 < 0 || g1 >= m.ngeom || g2 < 0 || g2 >= m.ngeom) { delete S; return fail(MOPA_ERR_INVALID_ARG, "pair_geom out of range"); }
+        if (g1 < 0 || g1 >= m.ngeom || g2 < 0 || g2 >= m.ngeom) { return fail(MOPA_ERR_INVALID_ARG, "pair_geom out of range"); }
         int a = m.geom_mjid[g1], b = m.geom_mjid[g2];
         int lo = std::min(a, b), hi = std::max(a, b);
         bool ignored = false;
@@ -778,7 +778,7 @@ extern "C" int mopa_scene_create(const MopaSceneDesc *desc, MopaScene **out) {
             if (desc->ignored_pairs[2 * i] == lo && desc->ignored_pairs[2 * i + 1] == hi) ignored = true;
         if (ignored) continue;
         int code = pair_code(m.geom_type[g1], m.geom_type[g2]);
-        if (code < 0) { delete S; return fail(MOPA_ERR_UNSUPPORTED, "unsupported geom type pair (must be ordered type1<=type2)"); }
+        if (code < 0) { return fail(MOPA_ERR_UNSUPPORTED, "unsupported geom type pair (must be ordered type1<=type2)"); }
         pairs.push_back(PairE{code, g1, g2, p});
     }
     std::stable_sort(pairs.begin(), pairs.end(), [](const PairE &a, const PairE &b) { return a.code < b.code; });
@@ -812,11 +812,11 @@ extern "C" int mopa_scene_create(const MopaSceneDesc *desc, MopaScene **out) {
     for (int mslot = 0; mslot < nmg; mslot++) {
         int k = g_mb[mg_geom[mslot]];
         if (mb_mgnum[k] == 0) mb_mgadr[k] = mslot;
-        else if (mb_mgadr[k] + mb_mgnum[k] != mslot) { delete S; return fail(MOPA_ERR_UNSUPPORTED, "moving geoms of a body are not contiguous"); }
+        else if (mb_mgadr[k] + mb_mgnum[k] != mslot) { return fail(MOPA_ERR_UNSUPPORTED, "moving geoms of a body are not contiguous"); }
         mb_mgnum[k]++;
     }
     for (int k = 1; k < nmb; k++)   // slots must follow body order for the "earlier partner" rule
-        if (mb_mgnum[k] && mb_mgnum[k - 1] && mb_mgadr[k] < mb_mgadr[k - 1]) { delete S; return fail(MOPA_ERR_UNSUPPORTED, "geom order does not follow body order"); }
+        if (mb_mgnum[k] && mb_mgnum[k - 1] && mb_mgadr[k] < mb_mgadr[k - 1]) { return fail(MOPA_ERR_UNSUPPORTED, "geom order does not follow body order"); }
     // Per-owner-geom pair lists for the lane-per-state kernels.  Pairs whose class involves a mesh are kept in a list
     // of their own: the main pass (k_is_valid_v5 / v2) then carries no mesh code at all, and a second, light pass of
     // the MESH instantiation handles the handful of mesh pairs and folds its verdict into the first one's.
@@ -1106,7 +1106,7 @@ extern "C" int mopa_scene_create(const MopaSceneDesc *desc, MopaScene **out) {
     S->h_dbl = B.dbl;
     S->h_int = B.ints;
     S->lds_bytes = h.n_dbl * 8 + ((h.n_int + 1) & ~1) * 4 + kWavesPerBlock * h.wave_bytes;
-    if (S->lds_bytes > kMaxLdsBytes) { delete S; return fail(MOPA_ERR_LIMIT, "scene does not fit the 160 KiB LDS"); }
+    if (S->lds_bytes > kMaxLdsBytes) { return fail(MOPA_ERR_LIMIT, "scene does not fit the 160 KiB LDS"); }
     {
         S->v2_lds_bytes = h.n_dbl * 8 + ((h.n_int + 1) & ~1) * 4 + kWavesPerBlock * kV2LdsPerWave;
         const char *ev = std::getenv("MOPA_VALID_KERNEL");
@@ -1159,6 +1159,75 @@ extern "C" int mopa_scene_create(const MopaSceneDesc *desc, MopaScene **out) {
     S->hdr_mesh = h;
     S->hdr_mesh.o_mgr = o_mgr_mesh; S->hdr_mesh.o_gp_word = o_gp_word_mesh; S->hdr_mesh.n_gp = (int)gp_word_mesh.size();
     S->n_mesh_gp = (int)gp_word_mesh.size();
+    return MOPA_OK;
+}
+
+// The bytes k_is_valid_v5 reads from a scene -- both blobs, the FP32 pair table, the header (no padding: asserted) -- hashed
+// (FNV-1a, 64 bit).  A baked instantiation is launched only for a scene whose fingerprint equals the baked one.  The
+// planner's fields of the header (range, resolution, nn_eps: never read by K1) are hashed as zeros, so the planner
+// settings of a Scene do not decide which K1 it gets.
+static_assert(offsetof(SceneHdr, thr) == offsetof(SceneHdr, wave_bytes) + sizeof(int) && sizeof(SceneHdr) == offsetof(SceneHdr, nn_eps) + sizeof(double),
+              "SceneHdr has padding: k1_fingerprint would hash indeterminate bytes");
+static uint64_t k1_fingerprint(const MopaScene *S) {
+    uint64_t f = 0xcbf29ce484222325ull;
+    auto add = [&f](const void *p, size_t n) {
+        const unsigned char *b = static_cast<const unsigned char *>(p);
+        for (size_t i = 0; i < n; i++) f = (f ^ b[i]) * 0x100000001b3ull;
+    };
+    add(S->h_dbl.data(), S->h_dbl.size() * sizeof(double));
+    add(S->h_int.data(), S->h_int.size() * sizeof(int32_t));
+    add(S->h_gp_tab.data(), S->h_gp_tab.size() * sizeof(int32_t));
+    SceneHdr h = S->hdr;
+    h.range = 0.0; h.resolution = 0.0; h.nn_eps = 0.0;
+    add(&h, sizeof(SceneHdr));
+    return f;
+}
+// baked scene of this fingerprint (its index in MOPA_K1_BAKED_SCENES, from 1), 0 = none
+static int k1_baked_index(uint64_t fp) {
+#define MOPA_K1_MATCH(i_, T_) if (fp == T_::kFingerprint) return i_;
+    MOPA_K1_BAKED_SCENES(MOPA_K1_MATCH)
+#undef MOPA_K1_MATCH
+    return 0;
+}
+
+// Host export of what K1 reads from a scene (no device needed): sizes[8] = n_dbl, n_int, n_tab (int32 words of the FP32 pair
+// table + its per-geom tail), sizeof(SceneHdr), use_v5, centres in LDS, mesh pairs, nmg.  The buffers may be null (sizes only).
+extern "C" int mopa_scene_k1_export(const MopaSceneDesc *desc, int64_t *sizes, double *dbl, int32_t *ints, int32_t *tab, void *hdr,
+                                    uint64_t *fingerprint) {
+    if (!desc || !sizes) return fail(MOPA_ERR_INVALID_ARG, "null argument");
+    MopaScene *S = new MopaScene();
+    const int rc = scene_build_host(desc, S);
+    if (rc != MOPA_OK) { delete S; return rc; }
+    sizes[0] = (int64_t)S->h_dbl.size(); sizes[1] = (int64_t)S->h_int.size(); sizes[2] = (int64_t)S->h_gp_tab.size();
+    sizes[3] = (int64_t)sizeof(SceneHdr); sizes[4] = S->use_v5; sizes[5] = S->v5_cen_lds ? 1 : 0; sizes[6] = S->n_mesh_gp; sizes[7] = S->hdr.nmg;
+    if (dbl) std::memcpy(dbl, S->h_dbl.data(), S->h_dbl.size() * sizeof(double));
+    if (ints) std::memcpy(ints, S->h_int.data(), S->h_int.size() * sizeof(int32_t));
+    if (tab) std::memcpy(tab, S->h_gp_tab.data(), S->h_gp_tab.size() * sizeof(int32_t));
+    if (hdr) std::memcpy(hdr, &S->hdr, sizeof(SceneHdr));
+    if (fingerprint) *fingerprint = k1_fingerprint(S);
+    delete S;
+    return MOPA_OK;
+}
+
+extern "C" int mopa_scene_create(const MopaSceneDesc *desc, MopaScene **out) {
+    if (!desc || !out) return fail(MOPA_ERR_INVALID_ARG, "null argument");
+    MopaScene *S = new MopaScene();
+    {
+        const int rc = scene_build_host(desc, S);
+        if (rc != MOPA_OK) { delete S; return rc; }
+    }
+    {
+        // K1 on a baked scene (mopa_valid_v5_baked.inc) when the fingerprint matches; MOPA_K1_BAKED=0: always the generic kernel (A/B runs)
+        const char *eb = std::getenv("MOPA_K1_BAKED");
+        const uint64_t fp = k1_fingerprint(S);
+        const bool allowed = !(eb && std::string(eb) == "0") && S->use_v5 && S->v5_cen_lds && S->n_mesh_gp == 0;
+        S->k1_baked = allowed ? k1_baked_index(fp) : 0;
+        if (std::getenv("MOPA_DEBUG"))
+            fprintf(stderr, "[mopa] scene fingerprint %016llx: k_is_valid_v5 %s%s\n", (unsigned long long)fp, S->k1_baked ? "baked #" : "generic",
+                    S->k1_baked ? std::to_string(S->k1_baked).c_str() : (eb && std::string(eb) == "0" ? " (MOPA_K1_BAKED=0)" : ""));
+    }
+    const MopaModel &m = desc->model;
+    const SceneHdr &h = S->hdr;
 
     // --- device upload ---
     int ndev = mopa_device_count();
@@ -1179,8 +1248,8 @@ extern "C" int mopa_scene_create(const MopaSceneDesc *desc, MopaScene **out) {
     hipError_t e1 = up((void **)&S->d_dbl, S->h_dbl.data(), S->h_dbl.size() * 8);
     hipError_t e2 = up((void **)&S->d_int, S->h_int.data(), S->h_int.size() * 4);
     if (e2 == hipSuccess) e2 = up((void **)&S->d_gp_tab, S->h_gp_tab.data(), S->h_gp_tab.size() * 4);
-    S->dbg_doubles = (size_t)kGeomStride * m.ngeom + pairs.size() + 8;
-    hipError_t e3 = hipMalloc((void **)&S->d_q, sizeof(double) * (size_t)(m.nq + na + 8));
+    S->dbg_doubles = (size_t)kGeomStride * m.ngeom + (size_t)h.npair + 8;
+    hipError_t e3 = hipMalloc((void **)&S->d_q, sizeof(double) * (size_t)(m.nq + S->na + 8));
     hipError_t e4 = hipMalloc((void **)&S->d_valid, 8);
     hipError_t e5 = hipMalloc((void **)&S->d_md, 8);
     hipError_t e6 = hipMalloc((void **)&S->d_dbg, sizeof(double) * S->dbg_doubles);
@@ -1197,6 +1266,11 @@ extern "C" int mopa_scene_create(const MopaSceneDesc *desc, MopaScene **out) {
                           (const void *)k_is_valid_v5<false, false, false>, (const void *)k_is_valid_v5<true, false, false>,
                           (const void *)k_is_valid_v5<false, false, true>, (const void *)k_is_valid_v5<true, false, true>})
         (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLdsBytes);
+#define MOPA_K1_ATTR(i_, T_)                                                                                                  \
+    for (const void *k : {(const void *)k_is_valid_v5<false, true, false, T_>, (const void *)k_is_valid_v5<true, true, false, T_>}) \
+        (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLdsBytes);
+    MOPA_K1_BAKED_SCENES(MOPA_K1_ATTR)
+#undef MOPA_K1_ATTR
     plan_register_lds();
     *out = S;
     return MOPA_OK;
@@ -1226,6 +1300,8 @@ extern "C" int mopa_scene_active_idx(const MopaScene *S, int32_t *out) {
 }
 extern "C" int mopa_scene_num_pairs(const MopaScene *S) { return S ? S->hdr.npair : -1; }
 extern "C" int mopa_scene_lds_bytes(const MopaScene *S) { return S ? S->lds_bytes : -1; }
+
+extern "C" int mopa_scene_k1_baked(const MopaScene *S) { return S ? S->k1_baked : -1; }
 
 extern "C" int mopa_scene_valid_kernel(const MopaScene *S, int64_t N, char *out, int32_t cap) {
     if (!S || !out || cap < 24) return fail(MOPA_ERR_INVALID_ARG, "null argument / buffer under 24 bytes");
@@ -1324,6 +1400,12 @@ static int launch_is_valid(MopaScene *S, const double *q_active, const double *q
             auto k5 = S->v5_cen_lds ? (min_dist ? k_is_valid_v5<true, true, false> : k_is_valid_v5<false, true, false>)
                       : mesh_list   ? (min_dist ? k_is_valid_v5<true, false, true> : k_is_valid_v5<false, false, true>)
                                     : (min_dist ? k_is_valid_v5<true, false, false> : k_is_valid_v5<false, false, false>);
+            switch (S->k1_baked) {     // (set only for scenes with the centre table in LDS and no mesh pairs)
+#define MOPA_K1_CASE(i_, T_) case i_: k5 = min_dist ? k_is_valid_v5<true, true, false, T_> : k_is_valid_v5<false, true, false, T_>; break;
+                MOPA_K1_BAKED_SCENES(MOPA_K1_CASE)
+#undef MOPA_K1_CASE
+                default: break;
+            }
             SceneHdr hk = S->hdr;
             if (min_dist) hk.v5_ent_cap = S->v5_ent_cap_md;
             hipLaunchKernelGGL(k5, grid, block, min_dist ? S->v5_lds_bytes_md : S->v5_lds_bytes, st, hk, S->d_dbl, S->d_int, S->d_gp_tab, q_active, qpos_env,

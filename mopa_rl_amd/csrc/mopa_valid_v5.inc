@@ -24,6 +24,60 @@ constexpr int kMprCapV5 = 128;     // per-wave ring of cylinder pairs waiting fo
 constexpr int kMprRow = 32;        // doubles per row: geom 1 record[15], geom 2 record[15], state index, types
 constexpr float kCullEps = 2.0e-5f;
 
+// Scene traits of k_is_valid_v5.  K1Generic: every scene table is read at run time (LDS / scalar loads + v_readlane
+// broadcasts).  A baked scene (mopa_valid_v5_baked.inc, written by tools/bake_k1_scenes.py from the host export of a
+// committed scene) carries its FP32 pair table as compile-time constants: pass A becomes straight-line compares against
+// literals (no table fetch, no broadcasts, no count-driven loops) and pass B visits only the pairs some lane kept.
+// mopa_scene_create launches a baked instantiation only when the scene's fingerprint (k1_fingerprint: blobs, pair table,
+// header) equals the baked one -- the same bytes the constants were taken from.
+struct K1Generic {
+    static constexpr bool kBaked = false;
+};
+#include "mopa_valid_v5_baked.inc"
+
+// pass A of a baked scene, one candidate pair (entry padr[M] + K of the table): the same FP32 arithmetic and compares as
+// the generic loops of k_is_valid_v5, with the table values as literals.  An inscribed-ball bound of 0 (no bound) is
+// never exceeded (d2 >= 0 or NaN), so its test is left out.
+template <class TR, int M, bool WANT_MD, int K>
+MOPA_D void v5_cull_baked(float cx, float cy, float cz, const float *cen_lane, unsigned &surv_lo, unsigned &surv_hi,
+                          unsigned long long &deep_mask, unsigned long long &any_kept) {
+    constexpr int e = TR::padr[M] + K;
+    constexpr float c0 = __builtin_bit_cast(float, TR::tab[8 * e + 0]), c1 = __builtin_bit_cast(float, TR::tab[8 * e + 1]);
+    constexpr float c2 = __builtin_bit_cast(float, TR::tab[8 * e + 2]), c3 = __builtin_bit_cast(float, TR::tab[8 * e + 3]);
+    constexpr float c4 = __builtin_bit_cast(float, TR::tab[8 * e + 4]), c5 = __builtin_bit_cast(float, TR::tab[8 * e + 5]);
+    constexpr float c6 = __builtin_bit_cast(float, TR::tab[8 * e + 6]);
+    bool keep;
+    if constexpr (K < TR::nmov[M]) {          // moving partner: its centre from the tile's table
+        const float *pc = cen_lane + ((TR::tab[8 * e + 7] >> 14) & 0xff) * 3 * 64;
+        const float dx = cx - pc[0], dy = cy - pc[64], dz = cz - pc[128];
+        const float d2 = fmaf(dz, dz, fmaf(dy, dy, dx * dx));
+        if constexpr (!WANT_MD && TR::tab[8 * e + 0] != 0u) deep_mask |= __ballot(d2 < c0);
+        keep = !(d2 > c3);
+    } else if constexpr (K < TR::nmov[M] + TR::nstat[M]) {   // static partner: sphere, then world AABB
+        const float dx = cx - c0, dy = cy - c1, dz = cz - c2;
+        keep = !((fmaf(dz, dz, fmaf(dy, dy, dx * dx)) > c3) | (fabsf(dx) > c4) | (fabsf(dy) > c5) | (fabsf(dz) > c6));
+    } else {                                  // plane: (c4, c5, c6) is the normal
+        const float dx = cx - c0, dy = cy - c1, dz = cz - c2;
+        keep = !(fmaf(dz, c6, fmaf(dy, c5, dx * c4)) > c3);
+    }
+    if constexpr (K < 32) surv_lo |= keep ? (1u << K) : 0u;
+    else surv_hi |= keep ? (1u << (K - 32)) : 0u;
+    any_kept |= __ballot(keep) ? (1ull << K) : 0ull;
+}
+template <class TR, int M, bool WANT_MD, int... K>
+MOPA_D void v5_pass_a_baked(float cx, float cy, float cz, const float *cen_lane, unsigned &surv_lo, unsigned &surv_hi,
+                            unsigned long long &deep_mask, unsigned long long &any_kept, std::integer_sequence<int, K...>) {
+    (v5_cull_baked<TR, M, WANT_MD, K>(cx, cy, cz, cen_lane, surv_lo, surv_hi, deep_mask, any_kept), ...);
+}
+// geom slot m (wave-uniform) -> its straight-line pass A
+template <class TR, bool WANT_MD, int... M>
+MOPA_D void v5_pass_a_dispatch(int m, float cx, float cy, float cz, const float *cen_lane, unsigned &surv_lo, unsigned &surv_hi,
+                               unsigned long long &deep_mask, unsigned long long &any_kept, std::integer_sequence<int, M...>) {
+    (void)((m == M ? (v5_pass_a_baked<TR, M, WANT_MD>(cx, cy, cz, cen_lane, surv_lo, surv_hi, deep_mask, any_kept,
+                                                     std::make_integer_sequence<int, TR::pnum[M]>{}), true)
+                   : false) || ...);
+}
+
 struct V5Lds {
     float *cen;                 // [nmg][3][64]   geom centres of this tile, FP32
     unsigned *ent;              // [h.v5_ent_cap]    lane | owner slot << 6 | pair class << 12 | table index << 16
@@ -221,8 +275,11 @@ MOPA_D void v5_drain(const SceneHdr &h, const LdsView &v, const V5Lds &q, const 
 // cull issues its loads four partners ahead) and two workgroups fit again.
 // GATE: the scene has mesh pairs; they take part in the FP32 broad phase only, and the states in which one survives are
 // appended to the work list of the second (mesh) pass.
-template <bool WANT_MD, bool CEN_LDS, bool GATE>
-__global__ __launch_bounds__(kBlock) void k_is_valid_v5(SceneHdr h, const double *__restrict__ g_dbl, const int32_t *__restrict__ g_int,
+// TR: scene traits (K1Generic, or a baked scene of mopa_valid_v5_baked.inc: CEN_LDS, no GATE).  A baked instantiation asks for
+// two workgroups per CU: left to itself the allocator spends the straight-line pass A's freedom on 256 VGPRs + AGPRs (one
+// wave per SIMD); held to 256 it needs 245 and spills no VGPR.  (The generic ones keep the default: measured slower with it.)
+template <bool WANT_MD, bool CEN_LDS, bool GATE, class TR = K1Generic>
+__global__ __launch_bounds__(kBlock, TR::kBaked ? 2 : 1) void k_is_valid_v5(SceneHdr h, const double *__restrict__ g_dbl, const int32_t *__restrict__ g_int,
                                                          const int32_t *__restrict__ g_tab, const double *__restrict__ q_active,
                                                          const double *__restrict__ qpos_env, long long N, long long samples_per_env,
                                                          unsigned char *__restrict__ valid, double *__restrict__ min_dist,
@@ -521,7 +578,18 @@ __global__ __launch_bounds__(kBlock) void k_is_valid_v5(SceneHdr h, const double
             unsigned surv_lo = 0u, surv_hi = 0u;
             unsigned long long deep_mask = 0ull;   // lanes whose state this geom's moving partners prove invalid
             int t7 = 0;        // flags word of table entry p0 + lane (pass B broadcasts it again)
-            {
+            unsigned long long any_kept = 0ull;   // baked scenes: the pairs some lane kept (pass B visits only these)
+            if constexpr (TR::kBaked) {
+                static_assert(CEN_LDS && !GATE, "baked scenes: centre table in LDS, no mesh gate");
+                if (lane < pn) t7 = s_tab[8 * (p0 + lane) + 7];
+#ifdef MOPA_V5_CULL_REPS
+                for (int cull_rep = 1; cull_rep < MOPA_V5_CULL_REPS; cull_rep++) {
+                    v5_pass_a_dispatch<TR, WANT_MD>(m, cx, cy, cz, q.cen + lane, surv_lo, surv_hi, deep_mask, any_kept, std::make_integer_sequence<int, TR::nmg>{});
+                    asm volatile("" : "+v"(surv_lo), "+v"(surv_hi));
+                }
+#endif
+                v5_pass_a_dispatch<TR, WANT_MD>(m, cx, cy, cz, q.cen + lane, surv_lo, surv_hi, deep_mask, any_kept, std::make_integer_sequence<int, TR::nmg>{});
+            } else {
                 const int cnt = g_tab[8 * h.n_gp + m];
                 const int n_mov = cnt & 0xff, n_stat = (cnt >> 8) & 0xff, n_pl = (cnt >> 16) & 0xff;
                 int t0 = 0, t1 = 0, t2 = 0, t3 = 0, t4 = 0, t5 = 0, t6 = 0;
@@ -609,10 +677,10 @@ __global__ __launch_bounds__(kBlock) void k_is_valid_v5(SceneHdr h, const double
             continue;
 #endif
             if (!__any((surv_lo | surv_hi) != 0u)) continue;
-            for (int k = 0; k < pn; k++) {
+            auto pass_b_pair = [&](const int k) {
                 const bool sv = (((k < 32) ? surv_lo : surv_hi) >> (k & 31)) & 1u;
                 const unsigned long long mask = __ballot(sv);
-                if (!mask) continue;
+                if (!mask) return;
                 const unsigned pcode = ((unsigned)__builtin_amdgcn_readlane(t7, k) >> 8) & 0xfu;
                 if (GATE && pcode >= (unsigned)PC_PLANE_MESH) {     // mesh pair within reach: evaluated after this kernel
                     // Its two posed records go to the launch's row list as they stand in the slab: k_mesh_rows runs the pair routine on them, a
@@ -641,7 +709,7 @@ __global__ __launch_bounds__(kBlock) void k_is_valid_v5(SceneHdr h, const double
                         }
                     }
                     need_mesh |= listed;
-                    continue;
+                    return;
                 }
                 if (sv) q.ent[n_ent + __builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u))] =
                             (unsigned)lane | ((unsigned)m << 6) | (pcode << 12) | ((unsigned)(p0 + k) << 16);
@@ -655,6 +723,11 @@ __global__ __launch_bounds__(kBlock) void k_is_valid_v5(SceneHdr h, const double
                     n_ent = 0;
                     present = 0u;
                 }
+            };
+            if constexpr (TR::kBaked) {
+                for (unsigned long long bits = any_kept; bits; bits &= bits - 1ull) pass_b_pair((int)__builtin_ctzll(bits));
+            } else {
+                for (int k = 0; k < pn; k++) pass_b_pair(k);
             }
         }
 #ifndef MOPA_V5_KO_DRAIN
