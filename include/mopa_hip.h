@@ -179,6 +179,13 @@ int mopa_scene_k1_baked(const MopaScene *scene);
  * the 64-bit FNV-1a hash over those bytes that selects a baked instantiation */
 int mopa_scene_k1_export(const MopaSceneDesc *desc, int64_t *sizes /*[8]*/, double *dbl, int32_t *ints, int32_t *tab, void *hdr,
                          uint64_t *fingerprint);
+/* byte offset of a field of the exported header (mopa_scene_k1_export's hdr) by name, -1 for an unknown name: the layout
+ * tools/bake_k1_scenes.py reads the header with, taken from the compiler rather than restated */
+int mopa_scene_hdr_offset(const char *field);
+/* host run of the forward kinematics compiled into the i-th baked scene (no device needed; tests): n states, state s =
+ * q_active[s] (na values) over the env row qpos_env[s] (nq values); out[s][nmg][12] = each moving geom's world position
+ * and row-major rotation matrix.  Returns MOPA_ERR_INVALID_ARG for an index that names no baked scene */
+int mopa_k1_baked_fk_host(int index, int64_t n, const double *q_active, const double *qpos_env, double *out);
 
 /* N states: state i = qpos_env[i / samples_per_env] with its active entries replaced by q_active[i].
  * valid[i] = 1 iff no non-ignored pair has dist <= contact_threshold.

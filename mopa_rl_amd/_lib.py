@@ -25,7 +25,7 @@ _ip = C.POINTER(C.c_int32)
 EXPORTED_SYMBOLS = [
     "mopa_last_error", "mopa_version", "mopa_device_count", "mopa_scene_create", "mopa_scene_destroy",
     "mopa_scene_num_active", "mopa_scene_active_idx", "mopa_scene_num_pairs", "mopa_scene_lds_bytes", "mopa_scene_valid_kernel",
-    "mopa_scene_k1_baked", "mopa_scene_k1_export",
+    "mopa_scene_k1_baked", "mopa_scene_k1_export", "mopa_scene_hdr_offset", "mopa_k1_baked_fk_host",
     "mopa_is_valid_batch", "mopa_check_motion_batch", "mopa_plan_batch", "mopa_pullback_batch", "mopa_is_valid_state", "mopa_plan",
     "mopa_planner_status", "mopa_debug_fk", "mopa_debug_pair_dist",
     "mopa_env_create", "mopa_env_destroy", "mopa_env_obs_dim", "mopa_env_action_dim", "mopa_env_step_batch", "mopa_env_exec_batch", "mopa_env_desired_batch",
@@ -208,6 +208,8 @@ def lib() -> C.CDLL:
     L.mopa_scene_valid_kernel.argtypes = [vp, C.c_int64, C.c_char_p, C.c_int32]
     L.mopa_scene_k1_baked.argtypes = [vp]
     L.mopa_scene_k1_export.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+    L.mopa_scene_hdr_offset.argtypes = [C.c_char_p]
+    L.mopa_k1_baked_fk_host.argtypes = [C.c_int, C.c_int64, vp, vp, vp]
     i32, i64, f64 = C.c_int32, C.c_int64, C.c_double
     L.mopa_paths_unwrap_batch.argtypes = [C.c_int, i64, i32, i32, vp, i32, vp, vp, vp, f64, i32, vp, vp, vp, vp, vp, vp, vp, vp]
     L.mopa_paths_unwrap_seam_batch.argtypes = [C.c_int, i64, i32, i32, vp, i32, vp, vp, vp, f64, i32, vp, vp, vp, vp, vp, vp, vp, C.c_uint64, vp]

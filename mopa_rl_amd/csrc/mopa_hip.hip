@@ -1209,6 +1209,44 @@ extern "C" int mopa_scene_k1_export(const MopaSceneDesc *desc, int64_t *sizes, d
     return MOPA_OK;
 }
 
+// Offsets of the header fields tools/bake_k1_scenes.py reads from an exported header (the compiler's layout, by name).
+extern "C" int mopa_scene_hdr_offset(const char *field) {
+    if (!field) return -1;
+#define MOPA_HDR_FIELD(f_) if (!std::strcmp(field, #f_)) return (int)offsetof(SceneHdr, f_);
+    MOPA_HDR_FIELD(na) MOPA_HDR_FIELD(nq) MOPA_HDR_FIELD(n_pq) MOPA_HDR_FIELD(nmb) MOPA_HDR_FIELD(nmg) MOPA_HDR_FIELD(nsf)
+    MOPA_HDR_FIELD(n_save) MOPA_HDR_FIELD(n_pas_b) MOPA_HDR_FIELD(n_dbl) MOPA_HDR_FIELD(n_int) MOPA_HDR_FIELD(o_mbr) MOPA_HDR_FIELD(o_mbd)
+    MOPA_HDR_FIELD(o_mgd) MOPA_HDR_FIELD(o_sf_pos) MOPA_HDR_FIELD(o_sf_quat) MOPA_HDR_FIELD(o_sf_mat) MOPA_HDR_FIELD(o_act_ref)
+    MOPA_HDR_FIELD(o_pq_adr) MOPA_HDR_FIELD(o_mg_geom) MOPA_HDR_FIELD(thr)
+#undef MOPA_HDR_FIELD
+    return -1;
+}
+
+// The baked walk of k_is_valid_v5 (k1_fk_baked) run on the host: each moving geom's world position and rotation matrix
+namespace {
+struct K1HostSink {
+    double *out;   // [nmg][12]
+    void operator()(int m, V3 gp, Q4 gq) {
+        double *o = out + 12 * m;
+        o[0] = gp.x; o[1] = gp.y; o[2] = gp.z;
+        quat2mat(o + 3, gq);
+    }
+};
+template <class TR>
+void k1_fk_host(int64_t n, const double *q_active, const double *qpos_env, double *out) {
+    for (int64_t s = 0; s < n; s++) {
+        K1HostSink sink{out + (size_t)s * 12 * TR::nmg};
+        k1_fk_baked<TR>(q_active + (size_t)s * TR::na, qpos_env + (size_t)s * TR::nq, sink, std::make_integer_sequence<int, TR::nmb>{});
+    }
+}
+}  // namespace
+extern "C" int mopa_k1_baked_fk_host(int index, int64_t n, const double *q_active, const double *qpos_env, double *out) {
+    if (n < 0 || (n > 0 && (!q_active || !qpos_env || !out))) return fail(MOPA_ERR_INVALID_ARG, "null argument / negative count");
+#define MOPA_K1_FK_HOST(i_, T_) if (index == i_) { k1_fk_host<T_>(n, q_active, qpos_env, out); return MOPA_OK; }
+    MOPA_K1_BAKED_SCENES(MOPA_K1_FK_HOST)
+#undef MOPA_K1_FK_HOST
+    return fail(MOPA_ERR_INVALID_ARG, "no baked scene #" + std::to_string(index));
+}
+
 extern "C" int mopa_scene_create(const MopaSceneDesc *desc, MopaScene **out) {
     if (!desc || !out) return fail(MOPA_ERR_INVALID_ARG, "null argument");
     MopaScene *S = new MopaScene();

@@ -78,6 +78,104 @@ MOPA_D void v5_pass_a_dispatch(int m, float cx, float cy, float cz, const float 
                    : false) || ...);
 }
 
+// Phase 1 of a baked scene: the moving-body program of the generic walk (k_is_valid_v5, phase 1) expanded body by body at
+// compile time.  Every body runs the generic walk's FP64 operations on the same operands in the same order -- only the scene
+// values are literals (bit patterns of the exported blobs), the branches on joint type / load slot / anchor are resolved by
+// the compiler, each joint takes its own sine / cosine (no select chain) and the DFS save slots stay in registers.  All
+// inputs (active values, passive coordinates) are read before the first pose leaves, so the pose stores drain under the
+// rest of the walk and pass A.  `sink(m, pos, quat)` receives moving geom m's world pose.
+MOPA_HD constexpr double k1_bits(unsigned long long b) { return __builtin_bit_cast(double, b); }
+template <class TR>
+struct K1FkRegs {
+    V3 pos;
+    Q4 quat;
+    double mat[9];
+    V3 save_pos[TR::n_save];
+    Q4 save_quat[TR::n_save];
+};
+template <class TR, int M, class Sink>
+MOPA_HD void k1_fk_geom(const K1FkRegs<TR> &r, Sink &sink) {
+    constexpr const unsigned long long *gd = TR::fk_gd[M];   // lpos[3] lquat[4]
+    const V3 gp = add3(r.pos, mat_vec(r.mat, V3{k1_bits(gd[0]), k1_bits(gd[1]), k1_bits(gd[2])}));
+    const Q4 gq = quat_mul(r.quat, Q4{k1_bits(gd[3]), k1_bits(gd[4]), k1_bits(gd[5]), k1_bits(gd[6])});
+    sink(M, gp, gq);
+}
+template <class TR, int B, class Sink, int... G>
+MOPA_HD void k1_fk_body(K1FkRegs<TR> &r, const double *qact, const double *sn, const double *cs, const double *pv, Sink &sink,
+                        std::integer_sequence<int, G...>) {
+    constexpr const int *bi = TR::fk_body[B];                // load, static frame, save, first geom, geoms, joints, type, anchor 0, value slot
+    constexpr int load = bi[0], sf = bi[1], save = bi[2], mgadr = bi[3], jn = bi[5], jt = bi[6], src = bi[8];
+    constexpr bool jp0 = bi[7] != 0;
+    constexpr const unsigned long long *bd = TR::fk_bd[B];   // pos[3] quat[4] axis[3] jpos[3] ref
+    static_assert(jn <= 1 && sizeof...(G) == bi[4], "baked walk: one joint per body at most");
+    if constexpr (jn == 1 && jt == J_FREE) {
+        const double *qp = pv + (src - TR::na);
+        r.pos = V3{qp[0], qp[1], qp[2]};
+        r.quat = quat_normalize(Q4{qp[3], qp[4], qp[5], qp[6]});
+    } else {
+        V3 ppos;
+        Q4 pquat;
+        if constexpr (load == -2) {
+            constexpr const unsigned long long *f = TR::fk_sf[sf];   // pos[3] quat[4] mat[9]
+            ppos = V3{k1_bits(f[0]), k1_bits(f[1]), k1_bits(f[2])};
+            pquat = Q4{k1_bits(f[3]), k1_bits(f[4]), k1_bits(f[5]), k1_bits(f[6])};
+#pragma unroll
+            for (int i = 0; i < 9; i++) r.mat[i] = k1_bits(f[7 + i]);
+        } else if constexpr (load >= 0) {
+            ppos = r.save_pos[load];
+            pquat = r.save_quat[load];
+            quat2mat(r.mat, pquat);
+        } else {
+            ppos = r.pos;
+            pquat = r.quat;
+        }
+        r.pos = add3(ppos, mat_vec(r.mat, V3{k1_bits(bd[0]), k1_bits(bd[1]), k1_bits(bd[2])}));
+        r.quat = quat_mul(pquat, Q4{k1_bits(bd[3]), k1_bits(bd[4]), k1_bits(bd[5]), k1_bits(bd[6])});
+        if constexpr (jn == 1) {
+            const V3 ax{k1_bits(bd[7]), k1_bits(bd[8]), k1_bits(bd[9])}, jp{k1_bits(bd[10]), k1_bits(bd[11]), k1_bits(bd[12])};
+            constexpr double ref = k1_bits(bd[13]);
+            if constexpr (src < TR::na) apply_joint_sc(jt, ax, jp, jp0, qact[src] - ref, sn[src], cs[src], r.pos, r.quat);
+            else apply_joint(jt, ax, jp, jp0, pv[src - TR::na] - ref, r.pos, r.quat);
+        }
+        r.quat = quat_normalize(r.quat);
+    }
+    quat2mat(r.mat, r.quat);
+    if constexpr (save >= 0) {
+        r.save_pos[save] = r.pos;
+        r.save_quat[save] = r.quat;
+    }
+    (k1_fk_geom<TR, mgadr + G>(r, sink), ...);
+}
+template <class TR, class Sink, int... B>
+MOPA_HD void k1_fk_baked(const double *qa_row, const double *env_row, Sink &sink, std::integer_sequence<int, B...>) {
+    static_assert(TR::na <= 8 && TR::n_pq >= 1 && TR::n_save >= 1, "baked walk: at most 8 active values; array sizes padded to 1");
+    double qact[TR::na], pv[TR::n_pq], sn[TR::na], cs[TR::na];
+#pragma unroll
+    for (int a = 0; a < TR::na; a++) qact[a] = qa_row[a];
+#pragma unroll
+    for (int k = 0; k < TR::n_pq; k++) pv[k] = env_row[TR::fk_pq_adr[k]];
+    // half-angle sine / cosine of every active value up front, as in the generic walk (same function, same argument)
+#pragma unroll
+    for (int a = 0; a < TR::na; a++) mopa_sincos(0.5 * (qact[a] - k1_bits(TR::fk_act_ref[a])), sn[a], cs[a]);
+    K1FkRegs<TR> r;
+    r.pos = V3{0.0, 0.0, 0.0};
+    r.quat = Q4{1.0, 0.0, 0.0, 0.0};
+    (k1_fk_body<TR, B>(r, qact, sn, cs, pv, sink, std::make_integer_sequence<int, TR::fk_body[B][4]>{}), ...);
+}
+// the kernel's sink: pose -> the geom's slab row, FP32 centre -> the tile's centre table in LDS (what pass A, v5_flush and the
+// MPR ring read, exactly as the generic walk writes them)
+struct V5FkSink {
+    double *slab;   // this lane's place in the wave's slab
+    float *cen;     // this lane's place in the centre table
+    MOPA_D void operator()(int m, V3 gp, Q4 gq) {
+        double *sp = slab + (size_t)m * kSlabStride;
+        sp[0] = gp.x; sp[64] = gp.y; sp[128] = gp.z;
+        sp[192] = gq.w; sp[256] = gq.x; sp[320] = gq.y; sp[384] = gq.z;
+        float *cp = cen + (size_t)m * 3 * 64;
+        cp[0] = (float)gp.x; cp[64] = (float)gp.y; cp[128] = (float)gp.z;
+    }
+};
+
 struct V5Lds {
     float *cen;                 // [nmg][3][64]   geom centres of this tile, FP32
     unsigned *ent;              // [h.v5_ent_cap]    lane | owner slot << 6 | pair class << 12 | table index << 16
@@ -348,7 +446,17 @@ __global__ __launch_bounds__(kBlock, TR::kBaked ? 2 : 1) void k_is_valid_v5(Scen
 #ifdef MOPA_V5_FK_REPS
         for (int fk_rep = 0; fk_rep < MOPA_V5_FK_REPS; fk_rep++)
 #endif
-        {
+        if constexpr (TR::kBaked) {       // (the baked scenes have no tile-posed bodies: q.tp stays false)
+            // (the slab pointer passes through an empty asm once per tile: otherwise the 98 loop-invariant store addresses of the
+            //  straight-line walk are hoisted out of the tile loop and held in VGPR pairs for the whole kernel)
+            double *fk_slab = slab;
+            asm volatile("" : "+v"(fk_slab));
+            V5FkSink sink{fk_slab, q.cen + lane};
+            k1_fk_baked<TR>(qa_row, env_row, sink, std::make_integer_sequence<int, TR::nmb>{});
+#ifdef MOPA_V5_FK_REPS
+            asm volatile("" ::: "memory");   // each repetition loads, computes and stores again
+#endif
+        } else {
             // ---- phase 0 (tiles whose states share ONE env row): the bodies no active coordinate reaches, one body per lane, level by level
             // (same arithmetic per body as the walk below); poses -> `ps` (over the entry buffer, idle until phase 2): [body | geom][7]
             double *ps = reinterpret_cast<double *>(q.ent);

@@ -3,9 +3,9 @@
 
 Each scene is loaded the way the library's callers load it (scene.planner_inputs + _lib.Scene's pair pruning and cull
 radii), the host half of mopa_scene_create runs on it (mopa_scene_k1_export: no device), and what k_is_valid_v5 reads
-of the FP32 pair table goes into a traits struct as compile-time constants, with the scene's fingerprint (FNV-1a over
-both blobs, the pair table and the header).  mopa_scene_create launches the baked instantiation only for a scene whose
-fingerprint matches; every other scene -- the full-pair-list sibling (Scene.full), other thresholds, custom scenes --
+of the FP32 pair table and of the moving-body program (forward kinematics) goes into a traits struct as compile-time
+constants, with the scene's fingerprint (FNV-1a over both blobs, the pair table and the header).  mopa_scene_create
+launches the baked instantiation only for a scene whose fingerprint matches; every other scene -- the full-pair-list sibling (Scene.full), other thresholds, custom scenes --
 keeps the generic kernel.  The output depends on nothing but the inputs: two runs give the same bytes.
 
     python tools/bake_k1_scenes.py [--out PATH]      (then rebuild: make -C mopa_rl_amd/csrc)
@@ -55,14 +55,83 @@ def scene_args(env: str):
     return pi, (pi.model, pi.passive_joint_idx, pi.ignored_contacts, pi.spec.contact_threshold)
 
 
+class Unsupported(Exception):
+    """The scene is outside what the baked kernel supports: it keeps the generic one."""
+
+
+J_FREE, J_SLIDE, J_HINGE = 0, 2, 3
+
+
+def hdr_int(ex: dict, field: str) -> int:
+    """An int field of the exported header, at the offset the library reports for it (offsetof, not restated here)."""
+    off = _lib.lib().mopa_scene_hdr_offset(field.encode())
+    if off < 0:
+        raise KeyError(f"SceneHdr has no field {field!r}")
+    return int(ex["hdr"][off: off + 4].view("<i4")[0])
+
+
+def hdr_double(ex: dict, field: str) -> float:
+    off = _lib.lib().mopa_scene_hdr_offset(field.encode())
+    if off < 0:
+        raise KeyError(f"SceneHdr has no field {field!r}")
+    return float(ex["hdr"][off: off + 8].view("<f8")[0])
+
+
+def fk_program(ex: dict) -> dict:
+    """The moving-body program of k_is_valid_v5's phase 1, read from the exported blobs (the bytes the fingerprint covers):
+    per body its record of the packed int blob and its 14 doubles (as 64-bit patterns), per moving geom its local pose, the
+    static frames, the active values' references and the passive coordinates' qpos addresses.  Raises Unsupported for a
+    scene the baked walk does not cover."""
+    if not (ex["use_v5"] and ex["cen_lds"]):
+        raise Unsupported("not a scene of the baked instantiation (third-generation kernel, centres in LDS)")
+    if ex["n_mesh_pairs"] != 0:
+        raise Unsupported(f"{ex['n_mesh_pairs']} mesh pairs (the baked instantiation has no mesh gate)")
+    H = {f: hdr_int(ex, f) for f in ("na", "nq", "n_pq", "nmb", "nmg", "nsf", "n_save", "n_pas_b", "n_dbl", "n_int", "o_mbr", "o_mbd",
+                                     "o_mgd", "o_sf_pos", "o_sf_quat", "o_sf_mat", "o_act_ref", "o_pq_adr")}
+    ints, bits = ex["ints"].astype("<i4"), ex["dbl"].astype("<f8").view("<u8")
+    if H["n_dbl"] != len(bits) or H["n_int"] != len(ints) or H["nmg"] != ex["nmg"]:
+        raise Unsupported("header does not describe the exported blobs")
+    na, nmb, nmg, n_pq, n_save = H["na"], H["nmb"], H["nmg"], H["n_pq"], H["n_save"]
+    if na > 8:
+        raise Unsupported(f"{na} active values (the walk's hoisted sines cover 8)")
+    if H["n_pas_b"] > 0:
+        raise Unsupported(f"{H['n_pas_b']} tile-posed bodies (phase 0 is not baked)")
+    pq_adr = [int(x) for x in ints[H["o_pq_adr"]: H["o_pq_adr"] + n_pq]]
+    bodies, bd = [], []
+    for k in range(nmb):
+        jn, _jntadr, load, sf, save, mgadr, mgnum, w = (int(x) for x in ints[H["o_mbr"] + 8 * k: H["o_mbr"] + 8 * k + 8])
+        jt, jp0, src = w & 0x7F, (w >> 7) & 1, w >> 8
+        if jn > 1:
+            raise Unsupported(f"moving body {k} has {jn} joints (the baked walk takes one at most)")
+        if jn == 1 and jt not in (J_FREE, J_SLIDE, J_HINGE):
+            raise Unsupported(f"moving body {k}: joint type {jt}")
+        if jn == 1 and jt == J_FREE and not (src >= na and src - na + 7 <= n_pq
+                                             and pq_adr[src - na: src - na + 7] == list(range(pq_adr[src - na], pq_adr[src - na] + 7))):
+            raise Unsupported(f"moving body {k}: free joint coordinates not contiguous")
+        if jn == 1 and not 0 <= src < na + n_pq:
+            raise Unsupported(f"moving body {k}: value slot {src}")
+        if not (load >= -2 and load < n_save and save < n_save and (load != -2 or 0 <= sf < H["nsf"]) and (k > 0 or load == -2 or jt == J_FREE)
+                and 0 <= mgadr and mgadr + mgnum <= nmg):
+            raise Unsupported(f"moving body {k}: record {[jn, load, sf, save, mgadr, mgnum]} out of range")
+        bodies.append([load, sf, save, mgadr, mgnum, jn, jt, jp0, src])
+        bd.append([int(x) for x in bits[H["o_mbd"] + 16 * k: H["o_mbd"] + 16 * k + 14]])
+    gd = [[int(x) for x in bits[H["o_mgd"] + 8 * m: H["o_mgd"] + 8 * m + 7]] for m in range(nmg)]
+    sf = [[int(x) for x in bits[H["o_sf_pos"] + 3 * i: H["o_sf_pos"] + 3 * i + 3]] + [int(x) for x in bits[H["o_sf_quat"] + 4 * i: H["o_sf_quat"] + 4 * i + 4]]
+          + [int(x) for x in bits[H["o_sf_mat"] + 9 * i: H["o_sf_mat"] + 9 * i + 9]] for i in range(H["nsf"])]
+    act_ref = [int(x) for x in bits[H["o_act_ref"]: H["o_act_ref"] + na]]
+    return {"na": na, "nq": H["nq"], "nmb": nmb, "n_pq": n_pq, "n_save": n_save, "bodies": bodies, "bd": bd, "gd": gd, "sf": sf, "act_ref": act_ref, "pq_adr": pq_adr}
+
+
 def bake(env: str, name: str) -> str:
     pi, args = scene_args(env)
     ex = _lib.k1_export(*args)
     fp = fingerprint(ex)
     if fp != ex["fingerprint"]:
         raise SystemExit(f"{env}: fingerprint {fp:016x} != the library's {ex['fingerprint']:016x}")
-    if not (ex["use_v5"] and ex["cen_lds"] and ex["n_mesh_pairs"] == 0):
-        raise SystemExit(f"{env}: not a scene of the baked instantiation (third-generation kernel, centres in LDS, no mesh pairs)")
+    try:
+        fk = fk_program(ex)
+    except Unsupported as e:
+        raise SystemExit(f"{env}: cannot be baked: {e}")
     nmg = ex["nmg"]
     tab = ex["tab"].astype("<i4").view("<u4")
     n5 = (len(tab) - 3 * nmg) // 8
@@ -75,10 +144,13 @@ def bake(env: str, name: str) -> str:
     assert all(a + b + c == p for a, b, c, p in zip(nmov, nstat, npl, pnum)) and max(pnum) <= 64
     path = os.path.join(SCENE_DIR, ENV_SPECS[env].scene + ".json")
     sha = hashlib.sha256(open(path, "rb").read()).hexdigest()
-    thr = struct.unpack("<d", ex["hdr"].tobytes()[-32:-24])[0]
+    thr = hdr_double(ex, "thr")
 
     def ints(v):
         return "{" + ", ".join(str(x) for x in v) + "}"
+
+    def u64(v):
+        return "{" + ", ".join(f"0x{x:016x}ull" for x in v) + "}"
 
     L = [f"// {env}: mopa_rl_amd/scenes/{os.path.basename(path)} (sha256 {sha}),",
          f"// contact threshold {thr!r}, pair pruning and cull radii from the scene's meta; {nmg} moving geoms, {n5} table entries",
@@ -99,7 +171,23 @@ def bake(env: str, name: str) -> str:
         for e in range(padr[m], padr[m] + pnum[m]):
             L.append("        " + ", ".join(f"0x{int(w):08x}u" for w in tab[8 * e: 8 * e + 8]) + ",")
     L.append("    };")
-    L.append("};")
+    n_save, n_pq = max(fk["n_save"], 1), max(fk["n_pq"], 1)      # (array sizes: at least 1)
+    L += ["    // forward kinematics (phase 1): the moving-body program of the generic walk, doubles as 64-bit patterns",
+          f"    static constexpr int nmb = {fk['nmb']}, na = {fk['na']}, nq = {fk['nq']}, n_pq = {n_pq}, n_save = {n_save}, nsf = {len(fk['sf'])};",
+          "    // per moving body: load (-2 static frame, -1 the body before, >= 0 save slot), static frame, save slot, first moving geom,",
+          "    // moving geoms, joints, joint type, anchor at the body origin, value slot (< na active, else passive na + k)",
+          "    static constexpr int fk_body[nmb][9] = {"]
+    L += [f"        {ints(b)}," for b in fk["bodies"]]
+    L += ["    };", "    // per moving body: pos[3] quat[4] joint axis[3] joint pos[3] joint ref", "    static constexpr unsigned long long fk_bd[nmb][14] = {"]
+    L += [f"        {u64(b)}," for b in fk["bd"]]
+    L += ["    };", "    // per moving geom: local pos[3] quat[4]", "    static constexpr unsigned long long fk_gd[nmg][7] = {"]
+    L += [f"        {u64(g)}," for g in fk["gd"]]
+    L += ["    };", "    // static frames: pos[3] quat[4] mat[9]", "    static constexpr unsigned long long fk_sf[nsf][16] = {"]
+    L += [f"        {u64(f)}," for f in fk["sf"]]
+    L += ["    };",
+          f"    static constexpr unsigned long long fk_act_ref[na] = {u64(fk['act_ref'])};",
+          f"    static constexpr int fk_pq_adr[n_pq] = {ints(fk['pq_adr'] + [0] * (n_pq - fk['n_pq']))};",
+          "};"]
     return "\n".join(L)
 
 
