@@ -477,6 +477,51 @@ int mopa_env_step_dyn_batch(MopaEnv *env, int64_t E, double *qpos_dev, double *q
                             const uint8_t *move_mask_dev, double *obs_dev, double *reward_dev, uint8_t *done_dev,
                             uint8_t *success_dev, void *stream);
 
+/* ---- K8: PusherObstacle-v0 dynamics (mopa_pusher_dyn.inc) ----------------------------------------------------------------
+ * `PusherObstacleEnv._step` (env/pusher/pusher_obstacle.py:245-279): the env's PID loop (env/base.py:200-209) sets the four
+ * velocity actuators (pusher_gripper.xml:123-126) before each of nsub = int(frame_dt / timestep) sub-steps of MuJoCo 2.0's RK4
+ * integrator (pusher_gripper.xml:7), restated in the plane: dofs joint0..3 (hinges about z) and box_x / box_y (slides); contacts
+ * (planar capsule-box, capsule-capsule, box-box) and joint limits as soft-constraint rows solved by Newton with pyramidal cones.
+ * PARITY UNPINNED.  qvel rows are [6] in dof order; i_term [E,4] is the PID's integral term, owned by
+ * the caller (zeroed at reset).
+ * Pair records: [npair, 20] doubles = class (0 capsule-box, 1 capsule-capsule, 2 box-box), body A, body B (-1 world, 0..3 arm
+ * bodies, 4 the box), geom A [5], geom B [5] (capsule: end 0 xy, end 1 xy, radius; box: centre xy, half sizes xy, 0; in the
+ * body's frame), mu, margin, K, B, d0, dmax, width. */
+#define MOPA_PUSHER_MAXCON 16   /* contacts kept per env and forward pass at most */
+typedef struct MopaPusherDynDesc {
+    int32_t qadr[6];                  /* qpos addresses of joint0..3, box_x, box_y */
+    int32_t limited[6];
+    double lo[6], hi[6];
+    double armature[6], damping[6];
+    double base[2];                   /* joint0's anchor in the world (xy) */
+    double rel[8];                    /* [4,2] anchor of arm body k in the frame of body k - 1 (entry 0 unused) */
+    double mass[4], com[8], izz[4];   /* lumped arm bodies: mass, centre of mass [4,2] in the body frame, inertia about z at the COM */
+    double box_mass, box_org[2], box_ref[2];
+    double gear[4], kv[4], ctrl_lo[4], ctrl_hi[4];
+    double kp, kd, ki, alpha;         /* PID gains (config/pusher.py:40-46) and the integral's decay 0.95 */
+    double frame_dt, timestep;
+    int32_t nsub;                     /* int(frame_dt / timestep) = 100 */
+    int32_t iterations;               /* Newton iterations (MuJoCo's default 100) */
+    double tolerance, inv_scale;      /* stop when (cost decrease) * inv_scale < tolerance (1e-8) */
+    double lim_par[8];                /* joint-limit rows: -, margin, K, B, d0, dmax, width, - */
+    int32_t maxcon;                   /* <= MOPA_PUSHER_MAXCON */
+    int32_t npair;                    /* 0: no contact stage (the arm alone) */
+    const double *pairs;              /* [npair, 20] */
+} MopaPusherDynDesc;
+int mopa_pusher_dyn_desc_size(void);  /* sizeof(MopaPusherDynDesc) as the library was built (binding self-check) */
+int mopa_env_attach_pusher_dynamics(MopaEnv *env, const MopaPusherDynDesc *desc);
+/* per-env counter of the stepping / sub-step launches that follow: [E] int32 = contacts dropped by the cap (NULL: off) */
+int mopa_env_set_pusher_stats(MopaEnv *env, int32_t *stats_dev);
+/* n raw sub-steps (PID + RK4) towards desired [E,4] with prev_state [E,4] as the PID's prev; qpos, qvel [E,6], i_term in/out */
+int mopa_env_pusher_substeps_batch(MopaEnv *env, int64_t E, double *qpos_dev, double *qvel_dev, double *i_term_dev,
+                                   const double *desired_dev, const double *prev_state_dev, int32_t n, void *stream);
+/* mopa_env_step_batch with the Pusher dynamics as `_do_simulation`: same arguments and bookkeeping, plus qvel [E,6] and i_term
+ * [E,4]; move_mask bit 0 clear -> the command is recorded, no sub-step runs.  action == NULL: obs refresh only. */
+int mopa_env_step_pusher_batch(MopaEnv *env, int64_t E, double *qpos_dev, double *qvel_dev, double *i_term_dev, double *prev_state_dev,
+                               uint8_t *has_prev_dev, int32_t *ep_len_dev, const double *action_dev, int32_t is_planner,
+                               const uint8_t *move_mask_dev, double *obs_dev, double *reward_dev, uint8_t *done_dev,
+                               uint8_t *success_dev, void *stream);
+
 /* ---- bookkeeping of one batched rollout call (rl/mopa_rollouts.py:70-375 + rl/sac_agent.py:148-318 for E envs at once) -------------
  * The elementwise work of mopa_rl_amd/rollout.py::BatchMoPARollout.agent_step between the library's launches, as six
  * one-wave-per-env kernels (mopa_rollstep.inc names the stages).  All pointers are device buffers; bool buffers are bytes. */

@@ -30,6 +30,8 @@ EXPORTED_SYMBOLS = [
     "mopa_planner_status", "mopa_debug_fk", "mopa_debug_pair_dist",
     "mopa_env_create", "mopa_env_destroy", "mopa_env_obs_dim", "mopa_env_action_dim", "mopa_env_step_batch", "mopa_env_exec_batch", "mopa_env_desired_batch",
     "mopa_env_attach_dynamics", "mopa_env_attach_contacts", "mopa_env_set_contact_stats", "mopa_rollout_stage", "mopa_rollout_pool_pick", "mopa_rollout_step_size", "mopa_ct_desc_size", "mopa_env_contact_arena", "mopa_env_dyn_dofs", "mopa_env_dyn_qvel_width", "mopa_env_dyn_forward_batch", "mopa_env_dyn_substeps_batch", "mopa_env_step_dyn_batch",
+    "mopa_pusher_dyn_desc_size", "mopa_env_attach_pusher_dynamics", "mopa_env_set_pusher_stats", "mopa_env_pusher_substeps_batch",
+    "mopa_env_step_pusher_batch",
     "mopa_ik_create", "mopa_ik_destroy", "mopa_ik_solve_batch", "mopa_ik_site_pose_batch", "mopa_ik_targets_batch",
     "mopa_paths_unwrap_batch", "mopa_paths_unwrap_seam_batch", "mopa_paths_walk_batch", "mopa_paths_assemble_batch", "mopa_interpolate_batch",
 ]
@@ -123,6 +125,20 @@ class MopaCtDesc(C.Structure):
     ]
 
 
+class MopaPusherDynDesc(C.Structure):
+    _fields_ = [
+        ("qadr", C.c_int32 * 6), ("limited", C.c_int32 * 6), ("lo", C.c_double * 6), ("hi", C.c_double * 6),
+        ("armature", C.c_double * 6), ("damping", C.c_double * 6), ("base", C.c_double * 2), ("rel", C.c_double * 8),
+        ("mass", C.c_double * 4), ("com", C.c_double * 8), ("izz", C.c_double * 4),
+        ("box_mass", C.c_double), ("box_org", C.c_double * 2), ("box_ref", C.c_double * 2),
+        ("gear", C.c_double * 4), ("kv", C.c_double * 4), ("ctrl_lo", C.c_double * 4), ("ctrl_hi", C.c_double * 4),
+        ("kp", C.c_double), ("kd", C.c_double), ("ki", C.c_double), ("alpha", C.c_double),
+        ("frame_dt", C.c_double), ("timestep", C.c_double), ("nsub", C.c_int32), ("iterations", C.c_int32),
+        ("tolerance", C.c_double), ("inv_scale", C.c_double), ("lim_par", C.c_double * 8),
+        ("maxcon", C.c_int32), ("npair", C.c_int32), ("pairs", _dp),
+    ]
+
+
 class MopaIkDesc(C.Structure):
     _fields_ = [("model", MopaModel), ("n_joints", C.c_int32), ("joint_ids", _ip), ("site_body", C.c_int32),
                 ("site_off", C.c_double * 3), ("site_quat", C.c_double * 4), ("device", C.c_int32)]
@@ -198,6 +214,11 @@ def lib() -> C.CDLL:
     L.mopa_env_dyn_forward_batch.argtypes = [vp, C.c_int64, vp, vp, vp, vp, vp, vp]
     L.mopa_env_dyn_substeps_batch.argtypes = [vp, C.c_int64, vp, vp, vp, vp, C.c_int32, vp]
     L.mopa_env_step_dyn_batch.argtypes = [vp, C.c_int64, vp, vp, vp, vp, vp, vp, vp, C.c_int32, vp, vp, vp, vp, vp, vp]
+    L.mopa_pusher_dyn_desc_size.argtypes = []
+    L.mopa_env_attach_pusher_dynamics.argtypes = [vp, C.POINTER(MopaPusherDynDesc)]
+    L.mopa_env_set_pusher_stats.argtypes = [vp, vp]
+    L.mopa_env_pusher_substeps_batch.argtypes = [vp, C.c_int64, vp, vp, vp, vp, vp, C.c_int32, vp]
+    L.mopa_env_step_pusher_batch.argtypes = [vp, C.c_int64, vp, vp, vp, vp, vp, vp, vp, C.c_int32, vp, vp, vp, vp, vp, vp]
     L.mopa_ik_create.argtypes = [C.POINTER(MopaIkDesc), C.POINTER(vp)]
     L.mopa_ik_destroy.argtypes = [vp]
     L.mopa_ik_destroy.restype = None

@@ -63,6 +63,9 @@ struct MopaEnv {
     int ct_solver = 0;      // 0: projected Gauss-Seidel, 1: Newton (pyramidal cones), 2: Newton (elliptic cones)
     int ct_arena = 0;       // solver 2: LDS slots (doubles) the contact records of an env share
     int32_t *ct_stats = nullptr;
+    // K8 (mopa_pusher_dyn.inc): the Pusher dynamics attached to this env, freed with it
+    void *pusher = nullptr;
+    void (*pusher_free)(void *) = nullptr;
     // waypoint execution scratch (one slot per env and waypoint), per stream, grow-only; outgrown buffers are retired and
     // freed with the handle (a kernel in flight may still read them)
     std::mutex mu;
@@ -79,6 +82,7 @@ struct MopaEnv {
         for (auto &kv : exec_scratch)
             if (kv.second.p) (void)hipFree(kv.second.p);
         for (void *q : retired) (void)hipFree(q);
+        if (pusher_free) pusher_free(pusher);
     }
 };
 
@@ -252,7 +256,8 @@ __device__ __forceinline__ void env_step_lane(const EnvHdr &h, const double *__r
         }
         k = 2 * h.n_arm;
         o[k++] = row[h.nq - 2]; o[k++] = row[h.nq - 1];
-        for (int j = 0; j < h.n_arm + 2; j++) o[k++] = 0.0;          // joint and box velocities: the kinematic limit
+        // joint and box velocities: 0 in the kinematic limit; with the dynamics (K8) qvel rows are joint0..3, box_x, box_y
+        for (int j = 0; j < h.n_arm + 2; j++) o[k++] = dyn ? qvel[e * dob->nv + j] : 0.0;
         o[k++] = tip.x; o[k++] = tip.y;
         o[k++] = row[h.nq - 4]; o[k++] = row[h.nq - 3];
         const double dist_box_to_gripper = norm3(sub3(box, tip_site));

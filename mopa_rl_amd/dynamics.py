@@ -385,6 +385,27 @@ def _spread_order(n: int):
     return [i for i in order if i < n]
 
 
+def _pair_solver_params(m, a: int, b: int, h: float):
+    """MuJoCo's per-pair mix of two collidable geoms' margin / solref / solimp ([3P] max margin, mean solref and solimp, the
+    time constant kept >= 2 timesteps) -> (margin, K, B, d0, dmax, width): the impedance parameters of a contact row."""
+    margin = max(float(m.geom_margin[a]), float(m.geom_margin[b]))
+    tc = max(0.5 * (float(m.geom_solref[a][0]) + float(m.geom_solref[b][0])), 2.0 * h)
+    dr = 0.5 * (float(m.geom_solref[a][1]) + float(m.geom_solref[b][1]))
+    d0, dmax, width = (0.5 * (float(m.geom_solimp[a][k]) + float(m.geom_solimp[b][k])) for k in range(3))
+    if not (m.geom_solref[a][0] > 0 and m.geom_solref[b][0] > 0 and dr > 0 and 0 < d0 <= dmax < 1 and width > 0):
+        raise ValueError("unsupported solref / solimp")
+    K, B = 1.0 / (dmax * dmax * tc * tc * dr * dr), 2.0 / (dmax * tc)
+    return margin, K, B, d0, dmax, width
+
+
+def _limit_solver_params(h: float, limit_solref=(0.02, 1.0), limit_solimp=(0.9, 0.95, 0.001)):
+    """joint limits as solver rows: MuJoCo's joint defaults (solreflimit 0.02 1, solimplimit 0.9 0.95 0.001, margin 0), the time
+    constant kept >= 2 timesteps as for contacts -> a pair record's layout: -, margin, K, B, d0, dmax, width, -"""
+    l_tc, l_dr = max(float(limit_solref[0]), 2.0 * h), float(limit_solref[1])
+    l_d0, l_dmax, l_w = (float(x) for x in limit_solimp)
+    return (0.0, 0.0, 1.0 / (l_dmax ** 2 * l_tc ** 2 * l_dr ** 2), 2.0 / (l_dmax * l_tc), l_d0, l_dmax, l_w, 0.0)
+
+
 def contact_facts(model, dyn: DynFacts, object_body: str, maxcon: int = None, maxpair: int = None, iterations: int = 50,
                   tolerance: float = 1e-10, precull_every: int = 15, precull_margin: float = 0.15, near_every: int = 3, near_margin: float = 0.03, warmstart: bool = True,
                   noslip_iterations: int = 5, noslip_tolerance: float = 1e-6, solver: str = "newton", cone: str = None, limit_rows=None,
@@ -571,13 +592,7 @@ def contact_facts(model, dyn: DynFacts, object_body: str, maxcon: int = None, ma
             f_roll = max(float(m.geom_friction3[a][2]), float(m.geom_friction3[b][2]))
         elif cdim > 3:
             raise ValueError("compiled scene carries no torsional / rolling friction (recompile with tools/compile_scenes.py)")
-        margin = max(float(m.geom_margin[a]), float(m.geom_margin[b]))
-        tc = max(0.5 * (float(m.geom_solref[a][0]) + float(m.geom_solref[b][0])), 2.0 * h)
-        dr = 0.5 * (float(m.geom_solref[a][1]) + float(m.geom_solref[b][1]))
-        d0, dmax, width = (0.5 * (float(m.geom_solimp[a][k]) + float(m.geom_solimp[b][k])) for k in range(3))
-        if not (m.geom_solref[a][0] > 0 and m.geom_solref[b][0] > 0 and dr > 0 and 0 < d0 <= dmax < 1 and width > 0):
-            raise ValueError("unsupported solref / solimp")
-        K, B = 1.0 / (dmax * dmax * tc * tc * dr * dr), 2.0 / (dmax * tc)
+        margin, K, B, d0, dmax, width = _pair_solver_params(m, a, b, h)
         for f_, s_ in dirs:
             if sh[f_][2] == GEOM_PLANE:
                 continue
@@ -606,9 +621,7 @@ def contact_facts(model, dyn: DynFacts, object_body: str, maxcon: int = None, ma
         limit_rows = solver == "newton"
     if limit_rows and solver != "newton":
         raise ValueError("joint limits as solver rows need the Newton solver")
-    l_tc, l_dr = max(float(limit_solref[0]), 2.0 * float(dyn.timestep)), float(limit_solref[1])
-    l_d0, l_dmax, l_w = (float(x) for x in limit_solimp)
-    lim_par = (0.0, 0.0, 1.0 / (l_dmax ** 2 * l_tc ** 2 * l_dr ** 2), 2.0 / (l_dmax * l_tc), l_d0, l_dmax, l_w, 0.0)
+    lim_par = _limit_solver_params(float(dyn.timestep), limit_solref, limit_solimp)
     return CtFacts(
         sh_geom=np.array([s[0] for s in sh], dtype=np.int32), sh_body=np.array([s[1] for s in sh], dtype=np.int32),
         sh_type=np.array([s[2] for s in sh], dtype=np.int32), sh_size=np.array([s[3] for s in sh]), sh_pos=np.array([s[4] for s in sh]),
@@ -623,3 +636,218 @@ def contact_facts(model, dyn: DynFacts, object_body: str, maxcon: int = None, ma
         warmstart=int(bool(warmstart)), near_every=int(near_every), near_margin=float(near_margin), noslip_iterations=int(noslip_iterations), noslip_tolerance=float(noslip_tolerance),
         solver={("pgs", "pyramidal"): 0, ("newton", "pyramidal"): 1, ("newton", "elliptic"): 2}[(solver, cone)], limit_rows=int(limit_rows), lim_par=lim_par,
         condim_downgraded=n_downgraded, arena=int(arena or 0))
+
+
+# ---- K8: PusherObstacle-v0 (csrc/mopa_pusher_dyn.inc) ------------------------------------------------------------------------
+PUSHER_DOFS = ("joint0", "joint1", "joint2", "joint3", "box_x", "box_y")
+PUSHER_BODIES = ("body0", "body1", "body2", "body3")     # the arm's jointed bodies; `fingertip` is welded to body3
+PUSHER_MAXCON = 16          # contacts kept per env and forward pass (include/mopa_hip.h MOPA_PUSHER_MAXCON)
+PUSHER_PAIR_REC = 20
+PAIR_CAPSULE_BOX, PAIR_CAPSULE_CAPSULE, PAIR_BOX_BOX = 0, 1, 2
+
+
+@dataclass
+class PusherDynFacts:
+    """What `k_pusher_dyn` (K8) and tests/pusher_dyn_ref.py take: the planar 6-dof tree of PusherObstacle-v0, its velocity
+    actuators, the env's PID loop and the contact pairs.  Everything moves in the plane z = const and turns about z only.
+    Bodies: 0..3 the arm's (body3 with the fingertip welded to it, lumped), 4 the box, -1 the world."""
+    dof_names: tuple
+    qadr: np.ndarray          # [6] i32
+    limited: np.ndarray       # [6] i32
+    lo: np.ndarray
+    hi: np.ndarray
+    armature: np.ndarray      # [6]
+    damping: np.ndarray       # [6]
+    base: np.ndarray          # [2] joint0's anchor in the world
+    rel: np.ndarray           # [4,2] anchor of arm body k in the frame of body k - 1 (row 0 unused)
+    mass: np.ndarray          # [4]
+    com: np.ndarray           # [4,2] centre of mass in the body frame
+    izz: np.ndarray           # [4] inertia about z at the centre of mass
+    box_mass: float
+    box_org: np.ndarray       # [2] box body position at qpos = ref
+    box_ref: np.ndarray       # [2]
+    act_kind: np.ndarray      # [4] 2 = velocity actuator
+    kv: np.ndarray            # [4]
+    gear: np.ndarray          # [4]
+    ctrl_lo: np.ndarray
+    ctrl_hi: np.ndarray
+    kp: float
+    kd: float
+    ki: float
+    alpha: float
+    integrator: str
+    timestep: float
+    frame_dt: float
+    nsub: int
+    iterations: int
+    tolerance: float
+    inv_scale: float
+    lim_par: tuple
+    maxcon: int
+    pairs: np.ndarray         # [npair, 20] (include/mopa_hip.h: MopaPusherDynDesc)
+    pair_names: list          # [(geom A, geom B)] in record order
+    dropped_pairs: list       # [(geom, geom, reason)] compiled candidates left out
+
+
+def _pusher_mass_diag(f: PusherDynFacts, q) -> np.ndarray:
+    """diag(M) of the planar tree at arm angles q[:4] (for MuJoCo's meaninertia)"""
+    th, px, py, pc, ps = 0.0, f.base[0], f.base[1], 1.0, 0.0
+    org, cs = [], []
+    for k in range(4):
+        if k > 0:
+            px, py = px + (pc * f.rel[k][0] - ps * f.rel[k][1]), py + (ps * f.rel[k][0] + pc * f.rel[k][1])
+        th += float(q[k])
+        pc, ps = np.cos(th), np.sin(th)
+        org.append((px, py))
+        cs.append((pc, ps))
+    com = [(org[b][0] + cs[b][0] * f.com[b][0] - cs[b][1] * f.com[b][1], org[b][1] + cs[b][1] * f.com[b][0] + cs[b][0] * f.com[b][1]) for b in range(4)]
+    diag = [sum(f.mass[b] * ((com[b][0] - org[j][0]) ** 2 + (com[b][1] - org[j][1]) ** 2) + f.izz[b] for b in range(j, 4)) + f.armature[j]
+            for j in range(4)]
+    return np.array(diag + [f.box_mass + f.armature[4], f.box_mass + f.armature[5]])
+
+
+def pusher_dyn_facts(model, facts=None, frame_dt: float = 1.0, contacts: bool = True, maxcon: int = PUSHER_MAXCON,
+                     iterations: int = 100, tolerance: float = 1e-8) -> PusherDynFacts:
+    """From the compiled scene (mopa_rl_amd/scenes/pusher_obstacle.json).  Integrator RK4, timestep 0.01
+    (env/assets/xml/common/pusher_gripper.xml:7); velocity actuators kv 1, gear 10, ctrlrange +-1 (:123-126); joint damping 1,
+    armature 1 (:9), box slides damping 1, armature 0, range +-0.4 (:109-110); PID kp 150, kd 20, ki 0.1 (config/pusher.py:40-46),
+    integral decay 0.95 (env/base.py:201); frame_dt 1.0 (config/pusher.py:49).  The XML names no solver, cone, iterations or
+    tolerance: MuJoCo 2.0's defaults (Newton, pyramidal, 100, 1e-8).  `facts` is unused (kept for dyn_facts' call shape)."""
+    from .mjcf import GEOM_BOX, GEOM_CAPSULE
+    m = model
+    names = list(m.body_names)
+    jn = list(m.jnt_names)
+    jid = [jn.index(n) for n in PUSHER_DOFS]
+    for n, j in zip(PUSHER_DOFS, jid):
+        want = JNT_HINGE if n.startswith("joint") else JNT_SLIDE
+        if int(m.jnt_type[j]) != want or float(m.jnt_stiffness[j]) != 0.0 or np.abs(m.jnt_pos[j]).max() != 0.0:
+            raise ValueError(f"{n}: the planar tree takes stiffness-free joints anchored at their body's origin")
+    ax = np.asarray(m.jnt_axis, dtype=np.float64)
+    if any(list(ax[j]) != [0.0, 0.0, 1.0] for j in jid[:4]) or list(ax[jid[4]]) != [1.0, 0.0, 0.0] or list(ax[jid[5]]) != [0.0, 1.0, 0.0]:
+        raise ValueError("the planar tree takes hinges about z and box slides along x / y")
+    arm_b = [names.index(n) for n in PUSHER_BODIES]
+    tip = names.index("fingertip")
+    box_b = names.index("box")
+    for b in arm_b + [tip, box_b]:
+        if list(np.asarray(m.body_quat[b], dtype=np.float64)) != [1.0, 0.0, 0.0, 0.0]:
+            raise ValueError(f"body {names[b]!r}: the planar tree takes unrotated body frames")
+    for k in range(1, 4):
+        if int(m.body_parent[arm_b[k]]) != arm_b[k - 1]:
+            raise ValueError("the arm must be the chain body0 .. body3")
+    if int(m.body_parent[tip]) != arm_b[3] or int(m.body_jntnum[tip]) != 0:
+        raise ValueError("fingertip must be welded to body3")
+    base = np.asarray(m.body_pos[arm_b[0]], dtype=np.float64)[:2].copy()
+    rel = np.zeros((4, 2))
+    for k in range(1, 4):
+        rel[k] = np.asarray(m.body_pos[arm_b[k]], dtype=np.float64)[:2]
+    mass, com, izz = np.zeros(4), np.zeros((4, 2)), np.zeros(4)
+    tip_off = np.asarray(m.body_pos[tip], dtype=np.float64)[:2]
+    for k, b in enumerate(arm_b):
+        parts = [(float(m.body_mass[b]), np.asarray(m.body_ipos[b], dtype=np.float64)[:2], float(m.body_inertia[b][2]))]
+        if k == 3:
+            parts.append((float(m.body_mass[tip]), tip_off + np.asarray(m.body_ipos[tip], dtype=np.float64)[:2], float(m.body_inertia[tip][2])))
+        mt = sum(p[0] for p in parts)
+        c = sum(p[0] * p[1] for p in parts) / mt
+        mass[k], com[k] = mt, c
+        izz[k] = sum(p[2] + p[0] * float((p[1] - c) @ (p[1] - c)) for p in parts)
+    qadr = np.array([int(m.jnt_qposadr[j]) for j in jid], dtype=np.int32)
+    limited = np.array([int(m.jnt_limited[j]) for j in jid], dtype=np.int32)
+    rng = np.asarray(m.jnt_range, dtype=np.float64)
+    lo = np.where(limited == 1, rng[jid, 0], -np.inf)
+    hi = np.where(limited == 1, rng[jid, 1], np.inf)
+    act_j = [int(j) for j in m.act_joint]
+    if act_j != jid[:4] or any(int(k) != 2 for k in m.act_kind) or not all(int(c) for c in m.act_ctrllimited):
+        raise ValueError("the Pusher's actuators: ctrl-limited velocity actuators on joint0 .. joint3, in that order")
+    h = float(m.opt[3])
+    f = PusherDynFacts(
+        dof_names=PUSHER_DOFS, qadr=qadr, limited=limited, lo=lo, hi=hi,
+        armature=np.array([float(m.jnt_armature[j]) for j in jid]), damping=np.array([float(m.jnt_damping[j]) for j in jid]),
+        base=base, rel=rel, mass=mass, com=com, izz=izz, box_mass=float(m.body_mass[box_b]),
+        box_org=np.asarray(m.body_pos[box_b], dtype=np.float64)[:2].copy(), box_ref=np.array([float(m.jnt_ref[jid[4]]), float(m.jnt_ref[jid[5]])]),
+        act_kind=np.asarray(m.act_kind, dtype=np.int32).copy(), kv=np.asarray(m.act_gain, dtype=np.float64).copy(),
+        gear=np.asarray(m.act_gear, dtype=np.float64).copy(), ctrl_lo=np.asarray(m.act_ctrlrange, dtype=np.float64)[:, 0].copy(),
+        ctrl_hi=np.asarray(m.act_ctrlrange, dtype=np.float64)[:, 1].copy(), kp=150.0, kd=20.0, ki=0.1, alpha=0.95,
+        integrator="RK4", timestep=h, frame_dt=float(frame_dt), nsub=int(frame_dt / h), iterations=int(iterations), tolerance=float(tolerance),
+        inv_scale=0.0, lim_par=_limit_solver_params(h), maxcon=int(maxcon), pairs=np.zeros((0, PUSHER_PAIR_REC)), pair_names=[], dropped_pairs=[])
+    if not 0 <= f.maxcon <= PUSHER_MAXCON:
+        raise ValueError(f"maxcon <= {PUSHER_MAXCON}")
+    # meaninertia: mean of diag(M) over the six dofs at qpos0
+    f.inv_scale = 1.0 / (float(_pusher_mass_diag(f, np.asarray(m.qpos0)[qadr[:4]]).mean()) * 6)
+
+    # ---- contact pairs: the compiled candidate list (contype / conaffinity and the parent filter already applied)
+    sim_body = {b: k for k, b in enumerate(arm_b)}
+    sim_body[tip] = 3
+    sim_body[box_b] = 4
+
+    def body_of(b):          # -> simulated body index, -1 world-welded, None: moves but is not simulated
+        c = b
+        while c > 0:
+            if c in sim_body:
+                return sim_body[c]
+            if int(m.body_jntnum[c]) > 0:
+                return None
+            c = int(m.body_parent[c])
+        return -1
+
+    def world_z(b):
+        z = 0.0
+        while b > 0:
+            z += float(m.body_pos[b][2])
+            b = int(m.body_parent[b])
+        return z
+
+    def gname(g):
+        return m.all_geom_names[int(m.geom_mjid[g])]
+
+    def geom_rec(g):
+        """(type, body index, 5 numbers in the body frame, z range)"""
+        gb = int(m.geom_body[g])
+        own = body_of(gb)
+        off = tip_off if gb == tip else np.zeros(2)
+        org = np.zeros(2) if own is not None and own >= 0 else np.asarray(m.body_pos[gb], dtype=np.float64)[:2]
+        p = np.asarray(m.geom_pos[g], dtype=np.float64)
+        R = _quat_to_mat(np.asarray(m.geom_quat[g], dtype=np.float64))
+        s = np.asarray(m.geom_size[g], dtype=np.float64)
+        z = world_z(gb) + p[2]
+        t = int(m.geom_type[g])
+        if t == GEOM_CAPSULE:
+            a = R @ np.array([0.0, 0.0, s[1]])
+            if abs(a[2]) > 1e-12:
+                raise ValueError(f"{gname(g)}: capsules must lie in the plane")
+            e0, e1 = p[:2] - a[:2] + off + org, p[:2] + a[:2] + off + org
+            return t, own, [e0[0], e0[1], e1[0], e1[1], s[0]], (z - s[0], z + s[0])
+        if t == GEOM_BOX:
+            if np.abs(R - np.eye(3)).max() > 0.0:
+                raise ValueError(f"{gname(g)}: boxes must be axis-aligned")
+            c = p[:2] + off + org
+            return t, own, [c[0], c[1], s[0], s[1], 0.0], (z - s[2], z + s[2])
+        zh = s[1] if t == 5 else (s[2] if len(s) > 2 else 0.0)     # cylinder: half-height
+        return t, own, None, (z - zh, z + zh)
+
+    recs, pnames, dropped = [], [], []
+    for a, b in m.pair_geom:
+        a, b = int(a), int(b)
+        ta, oa, ga, za = geom_rec(a)
+        tb, ob, gb_, zb = geom_rec(b)
+        if not ((oa is not None and oa >= 0) or (ob is not None and ob >= 0)):
+            dropped.append((gname(a), gname(b), "no simulated body"))
+            continue
+        if za[1] <= zb[0] or zb[1] <= za[0]:
+            dropped.append((gname(a), gname(b), "z-extents never overlap"))
+            continue
+        if oa is None or ob is None or ga is None or gb_ is None:
+            raise ValueError(f"pair {gname(a)} / {gname(b)}: not a planar capsule / box pair of simulated or static bodies")
+        if ta == GEOM_BOX and tb == GEOM_CAPSULE:
+            (ta, oa, ga, a), (tb, ob, gb_, b) = (tb, ob, gb_, b), (ta, oa, ga, a)
+        if ta == GEOM_BOX and tb == GEOM_BOX and oa < 0:
+            (ta, oa, ga, a), (tb, ob, gb_, b) = (tb, ob, gb_, b), (ta, oa, ga, a)
+        cls = {(GEOM_CAPSULE, GEOM_BOX): PAIR_CAPSULE_BOX, (GEOM_CAPSULE, GEOM_CAPSULE): PAIR_CAPSULE_CAPSULE, (GEOM_BOX, GEOM_BOX): PAIR_BOX_BOX}[(ta, tb)]
+        mu = max(float(m.geom_friction[a]), float(m.geom_friction[b]))
+        margin, K, B, d0, dmx, width = _pair_solver_params(m, a, b, h)
+        recs.append([float(cls), float(oa), float(ob)] + [float(x) for x in ga] + [float(x) for x in gb_] + [mu, margin, K, B, d0, dmx, width])
+        pnames.append((gname(a), gname(b)))
+    if contacts:
+        f.pairs = np.array(recs, dtype=np.float64).reshape(-1, PUSHER_PAIR_REC)
+        f.pair_names = pnames
+    f.dropped_pairs = dropped
+    return f

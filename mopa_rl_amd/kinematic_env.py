@@ -28,6 +28,11 @@ functions.  The cube can be pushed, the can pinched and lifted by friction.  `co
 `contacts="penalty"` (stage B of round 3, Push only) keeps the earlier stand-in: the cube under penalty springs, one-way
 coupled (spring-damper normal force, capped regularised Coulomb friction) -- NOT a constraint solver, labelled as such.
 
+PusherObstacle-v0 with `dynamics=True` (K8, `csrc/mopa_pusher_dyn.inc`, `dynamics.pusher_dyn_facts`): the env's PID loop over 100
+RK4 sub-steps per env.step (frame_dt 1.0), the four hinges and the box slides in the plane; `contacts=True` adds capsule / box
+contacts and the box is pushed, `contacts=False` leaves the arm alone (joint limits stay).  `qvel` [E,6] and the PID's `i_term`
+[E,4] are carried per env.  PARITY UNPINNED.
+
 `block_invalid=True` adds the one piece of contact behaviour a kinematic arm can have: a step whose desired state is
 in collision (K1 validity kernel, same rule as the planner) is not executed -- the arm stays where it is.
 
@@ -187,15 +192,15 @@ class BatchKinematicEnv:
 
     def __init__(self, env_name: str, num_envs: int, device=None, seed: int = 0, max_episode_steps: Optional[int] = None,
                  distance_threshold: Optional[float] = None, success_reward: float = 150.0, ac_scale: Optional[float] = None,
-                 block_invalid: bool = False, model=None, dynamics: bool = False, frame_dt: float = 0.15, contacts=False,
+                 block_invalid: bool = False, model=None, dynamics: bool = False, frame_dt: Optional[float] = None, contacts=False,
                  contact_options: dict = None, dyn_lanes: int = 1):
         torch = _torch()
         if env_name not in ENV_KIND:
             raise _lib.MopaError(f"no batched kinematic env for {env_name!r}")
         if distance_threshold is None:        # config/sawyer.py: 0.06, config/pusher.py:16-20: 0.05
             distance_threshold = 0.05 if ENV_KIND[env_name] == KIND_PUSHER else 0.06
-        if dynamics and ENV_KIND[env_name] == KIND_PUSHER:
-            raise _lib.MopaError("PusherObstacle-v0: kinematic env only (the dynamics / contact kernels restate the Sawyer envs' servo model)")
+        if frame_dt is None:                  # config/pusher.py:49: 1.0; the Sawyer envs' 0.15
+            frame_dt = 1.0 if ENV_KIND[env_name] == KIND_PUSHER else 0.15
         if not torch.cuda.is_available():
             raise _lib.MopaError("BatchKinematicEnv needs a HIP device (there is no CPU fallback)")
         self.env_name = env_name
@@ -264,9 +269,13 @@ class BatchKinematicEnv:
         self._planner = None
         self._scene = None
         self.dynamics = bool(dynamics)
+        self.distance_threshold = float(distance_threshold)
         self.dyn = None
         self.obj = None
-        if self.dynamics:
+        self.pdyn = None
+        if self.dynamics and f.kind == KIND_PUSHER:
+            self._attach_pusher_dynamics(frame_dt, contacts, contact_options, dyn_lanes, keep)
+        elif self.dynamics:
             from .dynamics import dyn_facts
             self.dyn = df = dyn_facts(self.model, f, frame_dt=frame_dt)
             dd = _lib.MopaDynDesc()
@@ -365,6 +374,63 @@ class BatchKinematicEnv:
                                      range_=self.spec.range, device=desc.device)
             self._planner = BatchPlanner(self._scene)
 
+    def _attach_pusher_dynamics(self, frame_dt, contacts, contact_options, dyn_lanes, keep):
+        """K8 (csrc/mopa_pusher_dyn.inc): the PID loop + RK4 physics of PusherObstacle-v0 (dynamics.pusher_dyn_facts).
+        contacts=True: contacts and joint limits behind Newton with pyramidal cones; False: the arm and box without contacts
+        (joint limits stay).  contact_options: maxcon, iterations, tolerance -- and solver / cone / noslip_iterations only at the
+        values the kernel implements ('newton', 'pyramidal', 0)."""
+        torch = _torch()
+        if contacts == "penalty":
+            raise _lib.MopaError("contacts='penalty': the penalty-contact object model is built for the Push cube only")
+        if dyn_lanes != 1:
+            raise _lib.MopaError("PusherObstacle-v0 dynamics: one lane per env (dyn_lanes=1)")
+        opts = dict(contact_options or {})
+        if opts.pop("solver", "newton") != "newton" or opts.pop("cone", "pyramidal") != "pyramidal" or int(opts.pop("noslip_iterations", 0)) != 0:
+            raise _lib.MopaError("PusherObstacle-v0 dynamics: Newton with pyramidal cones and no noslip pass only")
+        unknown = set(opts) - {"maxcon", "iterations", "tolerance"}
+        if unknown:
+            raise _lib.MopaError(f"PusherObstacle-v0 dynamics: contact options not implemented: {sorted(unknown)}")
+        from .dynamics import pusher_dyn_facts
+        try:
+            self.pdyn = pf = pusher_dyn_facts(self.model, self.facts, frame_dt=frame_dt, contacts=bool(contacts), **opts)
+        except ValueError as e:
+            raise _lib.MopaError(str(e)) from None
+        d = _lib.MopaPusherDynDesc()
+        arr = lambda ty, n, a: (ty * n)(*[float(x) if ty is C.c_double else int(x) for x in np.asarray(a).ravel()])
+        d.qadr, d.limited = arr(C.c_int32, 6, pf.qadr), arr(C.c_int32, 6, pf.limited)
+        d.lo, d.hi = arr(C.c_double, 6, pf.lo), arr(C.c_double, 6, pf.hi)
+        d.armature, d.damping = arr(C.c_double, 6, pf.armature), arr(C.c_double, 6, pf.damping)
+        d.base, d.rel = arr(C.c_double, 2, pf.base), arr(C.c_double, 8, pf.rel)
+        d.mass, d.com, d.izz = arr(C.c_double, 4, pf.mass), arr(C.c_double, 8, pf.com), arr(C.c_double, 4, pf.izz)
+        d.box_mass, d.box_org, d.box_ref = float(pf.box_mass), arr(C.c_double, 2, pf.box_org), arr(C.c_double, 2, pf.box_ref)
+        d.gear, d.kv = arr(C.c_double, 4, pf.gear), arr(C.c_double, 4, pf.kv)
+        d.ctrl_lo, d.ctrl_hi = arr(C.c_double, 4, pf.ctrl_lo), arr(C.c_double, 4, pf.ctrl_hi)
+        d.kp, d.kd, d.ki, d.alpha = float(pf.kp), float(pf.kd), float(pf.ki), float(pf.alpha)
+        d.frame_dt, d.timestep, d.nsub = float(pf.frame_dt), float(pf.timestep), int(pf.nsub)
+        d.iterations, d.tolerance, d.inv_scale = int(pf.iterations), float(pf.tolerance), float(pf.inv_scale)
+        d.lim_par = arr(C.c_double, 8, pf.lim_par)
+        d.maxcon, d.npair = int(pf.maxcon), len(pf.pairs)
+        pairs = np.ascontiguousarray(pf.pairs, dtype=np.float64)
+        keep.append(pairs)
+        d.pairs = pairs.ctypes.data_as(C.POINTER(C.c_double)) if len(pairs) else None
+        _lib.check(_lib.lib().mopa_env_attach_pusher_dynamics(self._h, C.byref(d)))
+        dev, f64 = self.device, torch.float64
+        self.nv = 6
+        self.qvel = torch.zeros(self.E, 6, dtype=f64, device=dev)       # joint0..3, box_x, box_y
+        self.i_term = torch.zeros(self.E, 4, dtype=f64, device=dev)     # the PID's integral term (env/base.py:204), per episode
+        self.ct = None
+
+    def set_pusher_stats(self, stats):
+        """stats [E] int32 on the device: contacts dropped by the cap in the launches that follow (None: off)"""
+        _lib.check(_lib.lib().mopa_env_set_pusher_stats(self._h, _ptr(stats) if stats is not None else None))
+
+    def pusher_substeps(self, desired, prev_state, n: int = 1, stream=None):
+        """n raw sub-steps (PID + RK4) towards desired [E,4] with prev_state [E,4] as the PID's prev (tests / parity)"""
+        if self.pdyn is None:
+            raise _lib.MopaError("pusher_substeps: a PusherObstacle env with dynamics=True")
+        _lib.check(_lib.lib().mopa_env_pusher_substeps_batch(self._h, self.E, _ptr(self.qpos), _ptr(self.qvel), _ptr(self.i_term),
+                                                             _ptr(desired), _ptr(prev_state), int(n), _stream_handle(stream)))
+
     # ------------------------------------------------------------------
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
@@ -380,6 +446,13 @@ class BatchKinematicEnv:
             pass
 
     def _launch(self, action, is_planner: bool, move_mask, stream=None):
+        if self.pdyn is not None:
+            _lib.check(_lib.lib().mopa_env_step_pusher_batch(
+                self._h, self.E, _ptr(self.qpos), _ptr(self.qvel), _ptr(self.i_term), _ptr(self.prev_state), _ptr(self.has_prev),
+                _ptr(self.ep_len), _ptr(action) if action is not None else None, int(bool(is_planner)),
+                _ptr(move_mask) if move_mask is not None else None, _ptr(self.obs), _ptr(self.reward), _ptr(self.done),
+                _ptr(self.success), _stream_handle(stream)))
+            return
         if self.dynamics:
             _lib.check(_lib.lib().mopa_env_step_dyn_batch(
                 self._h, self.E, _ptr(self.qpos), _ptr(self.qvel), _ptr(self.bias_lag), _ptr(self.prev_state), _ptr(self.has_prev),
@@ -500,7 +573,7 @@ class BatchKinematicEnv:
             self.qpos.copy_(torch.where(mk[:, None], q, self.qpos))
             self.has_prev.copy_(torch.where(mk, torch.zeros_like(self.has_prev), self.has_prev))
             self.ep_len.copy_(torch.where(mk, torch.zeros_like(self.ep_len), self.ep_len))
-        self._rest(mask)
+        self._rest(mask, noise=True)
         self._launch(None, False, None)
         return self.obs
 
@@ -571,11 +644,30 @@ class BatchKinematicEnv:
         self._launch(None, False, None)
         return self.obs
 
-    def _rest(self, mask):
+    def _rest_pusher(self, mask, noise):
+        """Pusher dynamics: `_reset` (env/pusher/pusher_obstacle.py:51-57) draws qvel += U(-0.005, 0.005) for every dof and zeroes the
+        target's and the box's -- of the simulated dofs that leaves the arm's four; `_after_reset` zeroes the PID's i_term
+        (env/base.py:226).  set_state (noise=False): at rest."""
+        torch = _torch()
+        v = torch.zeros(self.E, 6, dtype=torch.float64, device=self.device)
+        if noise:
+            v[:, :4] = torch.rand(self.E, 4, dtype=torch.float64, device=self.device, generator=self._gen) * 0.01 - 0.005
+        if mask is None:
+            self.qvel.copy_(v)
+            self.i_term.zero_()
+        else:
+            mk = mask.to(torch.bool)
+            self.qvel.copy_(torch.where(mk[:, None], v, self.qvel))
+            self.i_term.copy_(torch.where(mk[:, None], torch.zeros_like(self.i_term), self.i_term))
+
+    def _rest(self, mask, noise: bool = False):
         """dynamics: the (re)set envs are at rest; bias_lag <- qfrc_bias of the `sim.forward()` that follows a reset."""
         if not self.dynamics:
             return
         torch = _torch()
+        if self.pdyn is not None:
+            self._rest_pusher(mask, noise)
+            return
         skip = None
         if mask is None:
             self.qvel.zero_()

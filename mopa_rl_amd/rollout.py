@@ -39,6 +39,7 @@ from .agent_planning import (JointLimits, action_to_displacement, displacement_t
                              is_planner_action, simple_interpolate_batch)
 from .batch import BatchPlanner, _torch
 from .planner import ITERS_PER_SECOND
+from .kinematic_env import KIND_PUSHER
 from .scene import ENV_SPECS, planner_inputs
 
 COUNTERS = ("mp", "rl", "interpolation", "mp_fail", "approximate", "invalid")
@@ -1414,9 +1415,11 @@ class BatchMoPARollout:
         disc = self._disc_pow(Lw)
         ext = W["extra"] if last_extra is not None else None
         # the launch runs with planner-step semantics (the action IS the displacement): a direct action's arm entries are
-        # multiplied by ac_scale here instead of in the kernel -- the same one multiplication
+        # multiplied by ac_scale here instead of in the kernel -- the same one multiplication.  (Pusher: `desired_state = prev +
+        # action` in both step forms, env/pusher/pusher_obstacle.py:262-266 -- nothing to multiply.)
         other = act0.clone()
-        other[:, :n] = act0[:, :n] * torch.full_like(act0[:, :n], cfg.ac_scale)
+        if env.kind != KIND_PUSHER:
+            other[:, :n] = act0[:, :n] * torch.full_like(act0[:, :n], cfg.ac_scale)
         walked = env.walk_round(W["traj"], W["len"], W["pos"], disc, W["rew"], W["done"], W["intra"], rec, ext, other_action=other, other_flags=flags0)
         rew1, done1 = env.reward.clone(), env.done.clone()           # of the envs that took their direct / failed-plan step
         if cfg.walk_chunk > 1:

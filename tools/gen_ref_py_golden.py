@@ -787,6 +787,54 @@ def gen_env_pusher():
          reward=rew, done=done, success=succ, qpos_after=q_after, max_episode_steps=np.array(MAXS))
 
 
+def gen_pusher_pid():
+    """K8's Python around the physics: the reference's own `PusherObstacleEnv._step` with its real PID loop (`_get_control`,
+    env/base.py:200-209; kp 150, kd 20, ki 0.1, frame_dt 1.0: config/pusher.py:40-49) over refshim.FakeSim, whose `sim.step()` is a
+    scripted state update unrelated to the physics (qvel[:4] = 0.02 ctrl, qpos[:4] += 0.01 qvel[:4]).  Records data.ctrl at every
+    sub-step, `_prev_state` and `_i_term` after every step, for direct and planner steps within one episode and across a
+    `_reset_prev_state`.  (tests/test_pusher_dyn_host.py replays it through tests/pusher_dyn_ref.py's PID.)"""
+    env = make_ref_env_pusher(seed=3)
+    del env._get_control                     # the reference's own PID loop
+    env._kp, env._kd, env._ki = 150.0, 20.0, 0.1
+    env._frame_dt = 1.0
+    env._i_term = np.zeros(4)                # `_after_reset` (env/base.py:226)
+    sim = env.sim
+    adr = np.array(env.ref_joint_pos_indexes)
+    log = []
+
+    def scripted_step(a=None):
+        sim.data.ctrl[:] = a[:]
+        log.append(np.array(sim.data.ctrl, dtype=np.float64).copy())
+        sim.data.qvel[adr] = 0.02 * sim.data.ctrl
+        sim.data.qpos[adr] = sim.data.qpos[adr] + 0.01 * sim.data.qvel[adr]
+        sim.forward()
+
+    env._do_simulation = scripted_step
+    rng = np.random.RandomState(7)
+    sim.data.qpos[adr] = rng.uniform(-0.3, 0.3, size=4)
+    sim.forward()
+    plan = [(False, False), (True, False), (True, False), (True, True), (False, False), (True, False)]   # (is_planner, reset prev first)
+    q0, v0, act, isp, rst, ctrl, prev, iterm = [], [], [], [], [], [], [], []
+    for is_planner, reset_prev in plan:
+        if reset_prev:
+            env._reset_prev_state()
+        a = rng.uniform(-0.15, 0.15, size=4) if is_planner else rng.uniform(-1, 1, size=4)
+        q0.append(np.array(sim.data.qpos, dtype=np.float64).copy())
+        v0.append(np.array(sim.data.qvel, dtype=np.float64).copy())
+        log.clear()
+        env._step(a, is_planner=is_planner)
+        act.append(a)
+        isp.append(is_planner)
+        rst.append(reset_prev)
+        ctrl.append(np.array(log))
+        prev.append(np.array(env._prev_state, dtype=np.float64).copy())
+        iterm.append(np.array(env._i_term, dtype=np.float64).copy())
+    save("ref_py_pusher_pid.npz", qpos0=np.array(q0), qvel0=np.array(v0), action=np.array(act), is_planner=np.array(isp),
+         reset_prev=np.array(rst), ctrl=np.array(ctrl), prev_state=np.array(prev), i_term=np.array(iterm), arm_qpos_idx=adr,
+         arm_qvel_idx=np.array(env.ref_joint_vel_indexes))
+    print(f"  pusher_pid: {len(plan)} steps x {np.array(ctrl).shape[1]} sub-steps")
+
+
 def gen_rollouts():
     gen_rollout()
     gen_rollout(E=12, T=4, reuse=True)
@@ -801,7 +849,7 @@ def gen_rollout_pusher():
     gen_rollout("PusherObstacle-v0", "pusher", E=24, T=5)
 
 
-SECTIONS = OrderedDict(host=gen_host, agent=gen_agent, rollout=gen_rollouts, ik=gen_ik, env=gen_env, env_pusher=gen_env_pusher, rollout_pusher=gen_rollout_pusher, episode=gen_episodes)
+SECTIONS = OrderedDict(host=gen_host, agent=gen_agent, rollout=gen_rollouts, ik=gen_ik, env=gen_env, env_pusher=gen_env_pusher, rollout_pusher=gen_rollout_pusher, pusher_pid=gen_pusher_pid, episode=gen_episodes)
 
 
 def main():
