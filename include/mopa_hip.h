@@ -235,6 +235,23 @@ int mopa_debug_fk(MopaScene *scene, const double *qpos_host /*[nq]*/, double *ge
 /* per-candidate-pair distances (MOPA_FAR for culled / ignored pairs), in MopaModel.pair_geom order */
 int mopa_debug_pair_dist(MopaScene *scene, const double *qpos_host /*[nq]*/, double *dist_host /*[npair]*/);
 
+/* Contact report: WHICH pairs are in contact -- what a user of the reference reads off d->contact[i].geom1 / geom2 / dist
+ * (mujoco_ompl_interface.cpp:917-978).  State i as in mopa_is_valid_batch.  One record per non-ignored candidate pair p with
+ * dist_p <= cutoff: p = index into the pair list of the MopaSceneDesc the scene was created from, dist_p = the bits
+ * mopa_debug_pair_dist reports.  The records of a state are sorted by ascending p; count[i] is their true number, even above
+ * max_contacts (K) -- then the K records with the lowest p are kept.  Unused slots hold pair = -1, dist = MOPA_FAR.
+ * cutoff must be finite and < 0 and K >= 1 (MOPA_ERR_INVALID_ARG): the broad phase culls at zero margin, so every pair at or
+ * below a negative cutoff survives it and the report is exact.  A scene created with pair_cull_radius is proven down to its
+ * contact_threshold only: cutoff > contact_threshold returns MOPA_ERR_UNSUPPORTED there.  cutoff = contact_threshold lists the
+ * pairs that make a state invalid.  Two launches (the min-depth form of mopa_is_valid_batch, then one wave per state that has a
+ * record), asynchronous on `stream`, deterministic: no atomics decide order or content. */
+int mopa_contacts_batch(MopaScene *scene, const double *q_active_dev /*[N,na]*/, const double *qpos_env_dev /*[E,nq]*/,
+                        int64_t N, int64_t samples_per_env, double cutoff, int32_t max_contacts /*K*/,
+                        int32_t *count_dev /*[N]*/, int32_t *pair_dev /*[N,K]*/, double *dist_dev /*[N,K]*/, void *stream);
+/* the same for one state (host pointers, synchronous) */
+int mopa_contacts_state(MopaScene *scene, const double *qpos_host /*[nq]*/, double cutoff, int32_t max_contacts /*K*/,
+                        int32_t *count /*[1]*/, int32_t *pair /*[K]*/, double *dist /*[K]*/);
+
 /* ======================================================================================================
  * (BASELINE configs 3-5) batched KINEMATIC env.step for the three Sawyer obstacle envs --
  * the "env-steps/sec" half of the metric.  Restates what the reference envs compute around the physics:

@@ -27,7 +27,7 @@ EXPORTED_SYMBOLS = [
     "mopa_scene_num_active", "mopa_scene_active_idx", "mopa_scene_num_pairs", "mopa_scene_lds_bytes", "mopa_scene_valid_kernel",
     "mopa_scene_k1_baked", "mopa_scene_k1_export", "mopa_scene_hdr_offset", "mopa_k1_baked_fk_host",
     "mopa_is_valid_batch", "mopa_check_motion_batch", "mopa_plan_batch", "mopa_pullback_batch", "mopa_is_valid_state", "mopa_plan",
-    "mopa_planner_status", "mopa_debug_fk", "mopa_debug_pair_dist",
+    "mopa_planner_status", "mopa_debug_fk", "mopa_debug_pair_dist", "mopa_contacts_batch", "mopa_contacts_state",
     "mopa_env_create", "mopa_env_destroy", "mopa_env_obs_dim", "mopa_env_action_dim", "mopa_env_step_batch", "mopa_env_exec_batch", "mopa_env_desired_batch",
     "mopa_env_attach_dynamics", "mopa_env_attach_contacts", "mopa_env_set_contact_stats", "mopa_rollout_stage", "mopa_rollout_pool_pick", "mopa_rollout_step_size", "mopa_ct_desc_size", "mopa_env_contact_arena", "mopa_env_dyn_dofs", "mopa_env_dyn_qvel_width", "mopa_env_dyn_forward_batch", "mopa_env_dyn_substeps_batch", "mopa_env_step_dyn_batch",
     "mopa_pusher_dyn_desc_size", "mopa_env_attach_pusher_dynamics", "mopa_env_set_pusher_stats", "mopa_env_pusher_substeps_batch",
@@ -192,6 +192,8 @@ def lib() -> C.CDLL:
     L.mopa_planner_status.restype = C.c_char_p
     L.mopa_debug_fk.argtypes = [vp, _dp, _dp, _dp]
     L.mopa_debug_pair_dist.argtypes = [vp, _dp, _dp]
+    L.mopa_contacts_batch.argtypes = [vp, vp, vp, C.c_int64, C.c_int64, C.c_double, C.c_int32, vp, vp, vp, vp]
+    L.mopa_contacts_state.argtypes = [vp, _dp, C.c_double, C.c_int32, _ip, _ip, _dp]
     L.mopa_env_create.argtypes = [C.POINTER(MopaEnvDesc), C.POINTER(vp)]
     L.mopa_env_destroy.argtypes = [vp]
     L.mopa_env_destroy.restype = None
@@ -386,6 +388,7 @@ class Scene:
         self.ngeom = len(m.geom_type)
         self.npair = len(m.pair_geom)
         self.seed = int(seed)
+        self.contact_threshold = float(contact_threshold)
 
     def close(self):
         if getattr(self, "_full", None) is not None:
@@ -409,6 +412,16 @@ class Scene:
         """the sibling scene with the FULL candidate-pair list (created on first use): where states outside the pruning proof's
         box -- a joint beyond its range + guard band -- are evaluated"""
         if not self.npair_pruned:
+            return self
+        if self._full is None:
+            mdl, pas, ign, thr, rng, res, seed, dev = self._ctor
+            self._full = Scene(mdl, pas, ign, thr, range_=rng, resolution=res, seed=seed, device=dev, prune_pairs=False)
+        return self._full
+
+    def contact_scene(self) -> "Scene":
+        """the scene the contact reports run on: this one when it holds the model's whole pair list with no tightened cull
+        radius, else the sibling created without pruning (pair indices are then indices into `model.pair_geom`)"""
+        if not (self.npair_pruned or self.npair_tightened):
             return self
         if self._full is None:
             mdl, pas, ign, thr, rng, res, seed, dev = self._ctor
@@ -458,6 +471,31 @@ class Scene:
         gpos = np.zeros((self.ngeom, 3)); gmat = np.zeros((self.ngeom, 9))
         check(lib().mopa_debug_fk(self._h, qp, gpos.ctypes.data_as(_dp), gmat.ctypes.data_as(_dp)))
         return gpos, gmat.reshape(-1, 3, 3)
+
+    def contacts_state_raw(self, qpos, cutoff: Optional[float] = None, max_contacts: int = 64):
+        """(count, pair [K] int32, dist [K]) of one state: the single-state form of `BatchPlanner.contacts`"""
+        sc = self.contact_scene()
+        q, qp = _d(qpos)
+        if q.shape != (self.nq,):
+            raise MopaError(f"state has dimension {q.shape}, expected nq={self.nq}")
+        K = int(max_contacts)
+        cnt = C.c_int32(0)
+        pair = np.full(max(K, 1), -1, dtype=np.int32)
+        dist = np.full(max(K, 1), MOPA_FAR)
+        check(lib().mopa_contacts_state(sc._h, qp, float(self.contact_threshold if cutoff is None else cutoff), K, C.byref(cnt),
+                                        pair.ctypes.data_as(_ip), dist.ctypes.data_as(_dp)))
+        return int(cnt.value), pair, dist
+
+    def contacts_state(self, qpos, cutoff: Optional[float] = None):
+        """The pairs in contact in one state, as the reference's checker sees them in `d->contact[i]`: a list of
+        (geom1_name, geom2_name, dist) over the non-ignored candidate pairs with dist <= cutoff, in `model.pair_geom` order.
+        cutoff=None: the scene's contact_threshold -- the pairs that make the state invalid.  cutoff must be < 0."""
+        m = self.model
+        K = max(1, len(m.pair_geom))
+        n, pair, dist = self.contacts_state_raw(qpos, cutoff, K)
+        g = np.asarray(m.pair_geom).reshape(-1, 2)
+        name = lambda k: m.all_geom_names[int(m.geom_mjid[int(k)])]
+        return [(name(g[p, 0]), name(g[p, 1]), float(d)) for p, d in zip(pair[:n], dist[:n])]
 
     def debug_pair_dist(self, qpos):
         q, qp = _d(qpos)

@@ -87,6 +87,40 @@ class PlanState:
         return PlanState(tq, torch.cat([p.tree_p for p in parts]), torch.cat([p.state for p in parts]), p0.max_nodes, p0.na)
 
 
+class ContactReport:
+    """`BatchPlanner.contacts`: per state the number of pairs at or below the cutoff (`count` [N] int32, not capped), their
+    indices into `model.pair_geom` in ascending order (`pair` [N, K] int32, -1 in unused slots) and their signed distances
+    (`dist` [N, K] float64, MOPA_FAR in unused slots)."""
+
+    def __init__(self, count, pair, dist, model):
+        self.count, self.pair, self.dist, self.model = count, pair, dist, model
+
+    def __iter__(self):
+        return iter((self.count, self.pair, self.dist))
+
+    def geoms(self):
+        """[N, K, 2] int64 numpy array: ids of the two geoms of every record among ALL geoms of the model (MuJoCo's geom ids,
+        `model.geom_mjid`), -1 in unused slots"""
+        return pair_geom_ids(self.model, self.pair.cpu().numpy())
+
+    def names(self, i: int):
+        """the records of state i as (geom1_name, geom2_name, dist)"""
+        m = self.model
+        n = min(int(self.count[i]), self.pair.shape[1])
+        ids = pair_geom_ids(m, self.pair[i, :n].cpu().numpy())
+        d = self.dist[i, :n].cpu().numpy()
+        return [(m.all_geom_names[int(a)], m.all_geom_names[int(b)], float(x)) for (a, b), x in zip(ids, d)]
+
+
+def pair_geom_ids(model, pair) -> np.ndarray:
+    """pair indices (any shape, -1 = unused) -> [..., 2] MuJoCo geom ids of the pairs' geoms, -1 where unused"""
+    pair = np.asarray(pair, dtype=np.int64)
+    g = np.asarray(model.geom_mjid, dtype=np.int64)[np.asarray(model.pair_geom, dtype=np.int64).reshape(-1, 2)]
+    out = g[np.clip(pair, 0, max(len(g) - 1, 0))] if len(g) else np.zeros(pair.shape + (2,), dtype=np.int64)
+    out[pair < 0] = -1
+    return out
+
+
 class BatchPlanner:
     """N-state validity / motion checks and E-env RRT-Connect on one GPU."""
 
@@ -140,6 +174,30 @@ class BatchPlanner:
                 else:
                     valid[rows] = r
         return (valid, md) if want_min_dist else valid
+
+    def contacts(self, q_active, qpos_env, samples_per_env: Optional[int] = None, cutoff: Optional[float] = None,
+                 max_contacts: int = 16, stream=None) -> ContactReport:
+        """Which pairs are in contact, for every state of a batch (states as in `is_valid`): one record per non-ignored
+        candidate pair with dist <= cutoff, ascending index into `model.pair_geom`; `count` is not capped by `max_contacts`,
+        the records with the lowest indices are kept.  cutoff=None: the scene's contact_threshold, i.e. the pairs that make a
+        state invalid; any other cutoff must be < 0.  Runs on the scene with the full pair list (`Scene.contact_scene`)."""
+        torch = _torch()
+        _check_f64(q_active, "q_active", self.na)
+        _check_f64(qpos_env, "qpos_env", self.nq)
+        N = q_active.shape[0]
+        K = int(max_contacts)
+        spe = int(samples_per_env) if samples_per_env is not None else max(1, N // max(1, qpos_env.shape[0]))
+        if N and (N + spe - 1) // spe > qpos_env.shape[0]:
+            raise _lib.MopaError("qpos_env has fewer rows than ceil(N / samples_per_env)")
+        sc = self.scene.contact_scene()
+        dev = q_active.device
+        count = torch.empty(N, dtype=torch.int32, device=dev)
+        pair = torch.empty(N, max(K, 1), dtype=torch.int32, device=dev)
+        dist = torch.empty(N, max(K, 1), dtype=torch.float64, device=dev)
+        _lib.check(_lib.lib().mopa_contacts_batch(sc.handle, _ptr(q_active), _ptr(qpos_env), N, spe,
+                                                  float(self.scene.contact_threshold if cutoff is None else cutoff), K,
+                                                  _ptr(count), _ptr(pair), _ptr(dist), _stream_handle(stream)))
+        return ContactReport(count, pair, dist, self.scene.model)
 
     def check_motion(self, qa, qb, qpos_env, samples_per_env: Optional[int] = None, stream=None):
         torch = _torch()

@@ -1,0 +1,170 @@
+// mopa_contacts.inc -- batched contact report: which candidate pairs of a state lie at or below a (negative) cutoff, and how deep.
+// What the reference reads off d->contact[i].geom1 / geom2 / dist (mujoco_ompl_interface.cpp:917-978), for N states at once.
+//
+// Two stages (DESIGN.md section 4, "Contact report"):
+//   1. the min-depth launch of mopa_is_valid_batch: a state has a record iff its deepest penetration is <= cutoff.  Exact for
+//      cutoff < 0 (the broad phase culls at zero margin: it only ever drops separated pairs).
+//   2. k_contact_rows (here): persistent waves pull chunks of states from a counter; rows of states without a record are filled with
+//      the "unused" pattern, every other state gets one wave: the FK and pair sweep of the wave-per-state validity routine
+//      (wave_load_state / wave_fk / pair_culled / geom_dist -- what k_is_valid, k_debug_state and plan_state_valid_impl are made of)
+//      with NO verdict early-out and NO deep-overlap shortcut, so a distance carries the bits mopa_debug_pair_dist reports.
+// Order: every distance lands in a per-wave LDS array indexed by the pair's position in the MopaSceneDesc pair list; the wave then
+// emits records in that order with a ballot and a prefix popcount -- ascending pair index and "the lowest K are kept" without atomics,
+// so two runs write the same bytes.
+
+template <bool MESH>
+__global__ __launch_bounds__(kBlock) void k_contact_rows(SceneHdr h, const double *__restrict__ g_dbl, const int32_t *__restrict__ g_int,
+                                                         const int32_t *__restrict__ pair_model /*[h.npair] device pair -> index in the desc's pair list*/,
+                                                         int npair_model, const double *__restrict__ q_active, const double *__restrict__ qpos_env,
+                                                         long long N, long long samples_per_env, const double *__restrict__ min_dist /*[N] stage 1*/,
+                                                         double cutoff, int K, int chunk /*1..64 states per pull*/, unsigned long long *__restrict__ ctr,
+                                                         int32_t *__restrict__ count, int32_t *__restrict__ pair, double *__restrict__ dist,
+                                                         int pd_off /*byte offset of the per-wave distance arrays in LDS*/) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    LdsView v = make_view(h, smem);
+    stage_scene(h, g_dbl, g_int, const_cast<double *>(v.dbl), const_cast<int *>(v.ints));
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    double *pd = reinterpret_cast<double *>(smem + pd_off) + wave * npair_model;   // [npair_model] distance by pair index, kFar = no record
+    const int *I = v.ints;
+    const unsigned long long lt = (1ull << lane) - 1ull;
+    for (;;) {
+        unsigned long long t = 0ull;
+        if (lane == 0) t = atomicAdd(ctr, 1ull);
+        // (the chunk index is wave-uniform: through readfirstlane it and every address formed from it stay in scalar registers)
+        const unsigned t_lo = __builtin_amdgcn_readfirstlane((unsigned)t), t_hi = __builtin_amdgcn_readfirstlane((unsigned)(t >> 32));
+        const long long s0 = (long long)(((unsigned long long)t_hi << 32) | t_lo) * chunk;
+        if (s0 >= N) break;
+        const int n = (int)((N - s0 < (long long)chunk) ? (N - s0) : (long long)chunk);
+        const bool kept = lane < n && min_dist[s0 + lane] <= cutoff;
+        unsigned long long km = __ballot(kept);
+        // states without a record: count 0, the whole row unused
+        for (long long e = lane; e < (long long)n * K; e += 64) {
+            const int ls = (int)(e / K);
+            if (!((km >> ls) & 1ull)) {
+                pair[s0 * K + e] = -1;
+                dist[s0 * K + e] = kFar;
+            }
+        }
+        if (lane < n && !kept) count[s0 + lane] = 0;
+        while (km) {
+            const int ls = __ffsll((long long)km) - 1;
+            km &= km - 1ull;
+            const long long s = s0 + ls;
+            wave_load_state(h, v, lane, q_active + s * h.na, qpos_env + (s / samples_per_env) * h.nq);
+            wave_fk(h, v, lane);
+            for (int i = lane; i < npair_model; i += 64) pd[i] = kFar;
+            // broad phase + ballot compaction (order-preserving: the worklist stays sorted by narrow-phase class)
+            int wl_count = 0;
+            for (int base = 0; base < h.npair; base += 64) {
+                const int p = base + lane;
+                bool surv = false;
+                if (p < h.npair) {
+                    const int pk = I[h.o_pairs + p];
+                    const int g1 = pk & 0xff, g2 = (pk >> 8) & 0xff;
+                    surv = !pair_culled(h, v, g1, g2, geom_rec(h, v, g1), geom_rec(h, v, g2));
+                }
+                const unsigned long long mask = __ballot(surv);
+                if (surv) v.wl[wl_count + __popcll(mask & lt)] = (unsigned short)p;
+                wl_count += __popcll(mask);
+            }
+            wave_sync();
+            // narrow phase over every survivor, full refinement
+            for (int base = 0; base < wl_count; base += 64) {
+                const int i = base + lane;
+                if (i < wl_count) {
+                    const int p = v.wl[i];
+                    const int pk = I[h.o_pairs + p];
+                    const int g1 = pk & 0xff, g2 = (pk >> 8) & 0xff, code = (pk >> 16) & 0xff;
+                    pd[pair_model[p]] = geom_dist<MESH>(code, geom_rec(h, v, g1), I[h.o_g_type + g1], geom_rec(h, v, g2), I[h.o_g_type + g2], v.dbl);
+                }
+            }
+            wave_sync();
+            // records in pair-index order; the count runs on past K
+            int cnt = 0;
+            for (int base = 0; base < npair_model; base += 64) {
+                const int p = base + lane;
+                const double d = (p < npair_model) ? pd[p] : kFar;
+                const bool hit = d <= cutoff;
+                const unsigned long long mask = __ballot(hit);
+                const int idx = cnt + __popcll(mask & lt);
+                if (hit && idx < K) {
+                    pair[s * K + idx] = p;
+                    dist[s * K + idx] = d;
+                }
+                cnt += __popcll(mask);
+            }
+            for (int i = cnt + lane; i < K; i += 64) {
+                pair[s * K + i] = -1;
+                dist[s * K + i] = kFar;
+            }
+            if (lane == 0) count[s] = cnt;
+            wave_sync();   // pd / worklist / geom slab are about to be reused
+        }
+    }
+    tile_ctr_release(ctr, lane);
+}
+
+static void contacts_register_lds() {
+    for (const void *k : {(const void *)k_contact_rows<false>, (const void *)k_contact_rows<true>})
+        (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLdsBytes);
+}
+
+extern "C" int mopa_contacts_batch(MopaScene *S, const double *q_active, const double *qpos_env, int64_t N, int64_t samples_per_env,
+                                   double cutoff, int32_t K, int32_t *count, int32_t *pair, double *dist, void *stream) {
+    if (!S || !count || !pair || !dist || (N > 0 && (!q_active || !qpos_env))) return fail(MOPA_ERR_INVALID_ARG, "null argument");
+    if (N < 0 || samples_per_env <= 0) return fail(MOPA_ERR_INVALID_ARG, "N < 0 or samples_per_env <= 0");
+    if (!std::isfinite(cutoff) || !(cutoff < 0.0)) return fail(MOPA_ERR_INVALID_ARG, "cutoff must be finite and < 0 (the broad phase culls at zero margin)");
+    if (K < 1) return fail(MOPA_ERR_INVALID_ARG, "max_contacts must be >= 1");
+    if (S->pruned && cutoff > S->hdr.thr)
+        return fail(MOPA_ERR_UNSUPPORTED, "a scene with pair_cull_radius is proven down to its contact_threshold only: cutoff > contact_threshold needs the full scene");
+    if (N == 0) return MOPA_OK;
+    ON_DEVICE(S->device);
+    hipStream_t st = (hipStream_t)stream;
+    const int pd_off = (S->lds_bytes + 15) & ~15;
+    const size_t lds = (size_t)pd_off + (size_t)kWavesPerBlock * S->npair_model * sizeof(double);
+    if (lds > (size_t)kMaxLdsBytes) return fail(MOPA_ERR_LIMIT, "contact report: the per-wave distance arrays do not fit LDS");
+    StreamScratch &sc = scratch_for(S, st);
+    HIP_TRY(grow(S, sc.ct_valid, (size_t)N));
+    HIP_TRY(grow(S, sc.ct_md, (size_t)N * sizeof(double)));
+    if (!sc.ct_ctr.p) {      // zeroed once, synchronously; the kernel puts it back to zero (tile_ctr_release)
+        HIP_TRY(grow(S, sc.ct_ctr, 64));
+        HIP_TRY(hipMemset(sc.ct_ctr.p, 0, 64));
+    }
+    // stage 1: deepest penetration of every state
+    const int rc = launch_is_valid(S, q_active, qpos_env, N, samples_per_env, nullptr, sc.ct_valid.as<uint8_t>(), sc.ct_md.as<double>(), stream);
+    if (rc != MOPA_OK) return rc;
+    // stage 2: persistent waves (189 / 191 VGPRs: two waves per SIMD, i.e. two workgroups per CU are resident); small batches are
+    // handed out state by state, large ones in chunks of up to 64
+    const int64_t max_blocks = (int64_t)S->n_cu * 2;
+    const int64_t blocks = std::max<int64_t>(1, std::min<int64_t>((N + kWavesPerBlock - 1) / kWavesPerBlock, max_blocks));
+    const int chunk = (int)std::max<int64_t>(1, std::min<int64_t>(64, N / (blocks * kWavesPerBlock * 8)));
+    hipLaunchKernelGGL(S->hdr.has_mesh ? k_contact_rows<true> : k_contact_rows<false>, dim3((unsigned)blocks), dim3(kBlock), lds, st, S->hdr, S->d_dbl, S->d_int,
+                       (const int32_t *)S->d_pair_model, S->npair_model, q_active, qpos_env, (long long)N, (long long)samples_per_env,
+                       (const double *)sc.ct_md.as<double>(), cutoff, (int)K, chunk, sc.ct_ctr.as<unsigned long long>(), count, pair, dist, pd_off);
+    HIP_TRY(hipGetLastError());
+    return MOPA_OK;
+}
+
+extern "C" int mopa_contacts_state(MopaScene *S, const double *qpos_host, double cutoff, int32_t K, int32_t *count, int32_t *pair, double *dist) {
+    if (!S || !qpos_host || !count || !pair || !dist) return fail(MOPA_ERR_INVALID_ARG, "null argument");
+    if (K < 1) return fail(MOPA_ERR_INVALID_ARG, "max_contacts must be >= 1");
+    ON_DEVICE(S->device);
+    int rc = upload_state(S, qpos_host);
+    if (rc) return rc;
+    void *buf = nullptr;
+    const size_t off_dist = 0, off_pair = (size_t)K * sizeof(double), off_count = off_pair + (size_t)K * sizeof(int32_t);
+    HIP_TRY(hipMalloc(&buf, off_count + sizeof(int32_t)));
+    unsigned char *b = static_cast<unsigned char *>(buf);
+    rc = mopa_contacts_batch(S, S->d_q + S->nq, S->d_q, 1, 1, cutoff, K, reinterpret_cast<int32_t *>(b + off_count), reinterpret_cast<int32_t *>(b + off_pair),
+                             reinterpret_cast<double *>(b + off_dist), nullptr);
+    hipError_t e = hipSuccess;
+    if (rc == MOPA_OK) {
+        e = hipMemcpy(dist, b + off_dist, (size_t)K * sizeof(double), hipMemcpyDeviceToHost);
+        if (e == hipSuccess) e = hipMemcpy(pair, b + off_pair, (size_t)K * sizeof(int32_t), hipMemcpyDeviceToHost);
+        if (e == hipSuccess) e = hipMemcpy(count, b + off_count, sizeof(int32_t), hipMemcpyDeviceToHost);
+    }
+    (void)hipFree(buf);
+    if (rc != MOPA_OK) return rc;
+    HIP_TRY(e);
+    return MOPA_OK;
+}

@@ -41,6 +41,7 @@ int mopa_fail(int code, const std::string &msg) {
 }
 constexpr double kV5MaxReach = 32.0;        // metres: beyond this the FP32 broad phase is not used (see mopa_scene_create)
 static void plan_register_lds();            // defined with K3 (mopa_planner.inc)
+static void contacts_register_lds();        // defined with the contact report (mopa_contacts.inc)
 
 extern "C" const char *mopa_last_error(void) { return g_err.c_str(); }
 extern "C" const char *mopa_version(void) { return "mopa_hip 0.1.0 (gfx950)"; }
@@ -102,6 +103,7 @@ struct StreamScratch {
     DevBuf plan_q, plan_p, plan_ctr;                          // planner: both trees of every env, env counter (mopa_planner.inc)
     DevBuf ip_walk;                                           // straight-line pre-check: walk states + verdicts (mopa_paths.inc)
     DevBuf pb_small, pb_rows, pb_act;                         // batched pull-back: verdicts / slots, candidate rows, their active coordinates + verdicts
+    DevBuf ct_valid, ct_md, ct_ctr;                           // contact report (mopa_contacts.inc): stage 1's verdicts and depths, stage 2's chunk counter
 };
 
 struct MopaScene {
@@ -120,6 +122,9 @@ struct MopaScene {
     int nq = 0, na = 0, ngeom_model = 0, npair_model = 0;
     std::vector<int32_t> active_idx;
     std::vector<int32_t> pair_slot;   // model pair index -> device pair index or -1
+    std::vector<int32_t> pair_model;  // device pair index -> model pair index (contact report)
+    int32_t *d_pair_model = nullptr;
+    bool pruned = false;              // created with pair_cull_radius: the pair list is proven down to the contact threshold only
     std::vector<int32_t> geom_model_of_dev;  // (identity; device geoms == model collidable geoms)
     uint64_t seed = 0;
     std::string status = "none";
@@ -784,9 +789,12 @@ static int scene_build_host(const MopaSceneDesc *desc, MopaScene *S) {
     std::stable_sort(pairs.begin(), pairs.end(), [](const PairE &a, const PairE &b) { return a.code < b.code; });
     std::vector<int32_t> pk(pairs.size());
     S->pair_slot.assign(m.npair, -1);
+    S->pair_model.assign(pairs.size(), 0);
+    S->pruned = desc->pair_cull_radius != nullptr;
     for (size_t i = 0; i < pairs.size(); i++) {
         pk[i] = pairs[i].g1 | (pairs[i].g2 << 8) | (pairs[i].code << 16);
         S->pair_slot[pairs[i].model_idx] = (int)i;
+        S->pair_model[i] = pairs[i].model_idx;
     }
 
     // --- second-generation kernel: DFS program over the moving bodies + per-geom pair lists ---
@@ -1286,6 +1294,7 @@ extern "C" int mopa_scene_create(const MopaSceneDesc *desc, MopaScene **out) {
     hipError_t e1 = up((void **)&S->d_dbl, S->h_dbl.data(), S->h_dbl.size() * 8);
     hipError_t e2 = up((void **)&S->d_int, S->h_int.data(), S->h_int.size() * 4);
     if (e2 == hipSuccess) e2 = up((void **)&S->d_gp_tab, S->h_gp_tab.data(), S->h_gp_tab.size() * 4);
+    if (e2 == hipSuccess) e2 = up((void **)&S->d_pair_model, S->pair_model.data(), S->pair_model.size() * 4);
     S->dbg_doubles = (size_t)kGeomStride * m.ngeom + (size_t)h.npair + 8;
     hipError_t e3 = hipMalloc((void **)&S->d_q, sizeof(double) * (size_t)(m.nq + S->na + 8));
     hipError_t e4 = hipMalloc((void **)&S->d_valid, 8);
@@ -1310,6 +1319,7 @@ extern "C" int mopa_scene_create(const MopaSceneDesc *desc, MopaScene **out) {
     MOPA_K1_BAKED_SCENES(MOPA_K1_ATTR)
 #undef MOPA_K1_ATTR
     plan_register_lds();
+    contacts_register_lds();
     *out = S;
     return MOPA_OK;
 }
@@ -1318,12 +1328,12 @@ extern "C" void mopa_scene_destroy(MopaScene *S) {
     if (!S) return;
     DeviceGuard guard(S->device);
     (void)hipDeviceSynchronize();      // nothing of this scene may still be running when its tables go away
-    for (void *q : {(void *)S->d_dbl, (void *)S->d_int, (void *)S->d_q, (void *)S->d_valid, (void *)S->d_md, (void *)S->d_dbg, (void *)S->d_gp_tab})
+    for (void *q : {(void *)S->d_dbl, (void *)S->d_int, (void *)S->d_q, (void *)S->d_valid, (void *)S->d_md, (void *)S->d_dbg, (void *)S->d_gp_tab, (void *)S->d_pair_model})
         if (q) (void)hipFree(q);
     for (auto &kv : S->scratch) {
         StreamScratch &sc = kv.second;
         for (DevBuf *b : {&sc.slab, &sc.mpr, &sc.cen, &sc.mesh_list, &sc.mesh_rows, &sc.mv_cnt, &sc.mv_off, &sc.mv_env, &sc.mv_q, &sc.mv_valid, &sc.mv_scan, &sc.plan_q,
-                          &sc.plan_p, &sc.plan_ctr, &sc.pb_small, &sc.pb_rows, &sc.pb_act, &sc.ip_walk})
+                          &sc.plan_p, &sc.plan_ctr, &sc.pb_small, &sc.pb_rows, &sc.pb_act, &sc.ip_walk, &sc.ct_valid, &sc.ct_md, &sc.ct_ctr})
             if (b->p) (void)hipFree(b->p);
     }
     for (void *q : S->retired) (void)hipFree(q);
@@ -1582,6 +1592,9 @@ extern "C" int mopa_debug_pair_dist(MopaScene *S, const double *qpos_host, doubl
 }
 
 extern "C" const char *mopa_planner_status(const MopaScene *S) { return S ? S->status.c_str() : "none"; }
+
+// batched contact report: mopa_contacts_batch / mopa_contacts_state
+#include "mopa_contacts.inc"
 
 // The planner entry points are defined in mopa_planner.inc (K3).
 #include "mopa_planner.inc"

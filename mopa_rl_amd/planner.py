@@ -96,3 +96,8 @@ class PyKinematicPlanner:
     @property
     def model(self):
         return self._model
+
+    def contacts(self, state_vec) -> List[Tuple[str, str, float]]:
+        """the pairs that make `state_vec` invalid -- (geom1_name, geom2_name, dist) with dist <= contact_threshold, what the
+        reference's checker finds in d->contact[i] (mujoco_ompl_interface.cpp:917-978); empty for a valid state"""
+        return self._scene.contacts_state(np.asarray(state_vec, dtype=np.float64))

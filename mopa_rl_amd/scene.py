@@ -167,3 +167,33 @@ def qpos_joint_arrays(model: CompiledModel, float32_limits: bool = False):
     if float32_limits:
         lo, hi = lo.astype(np.float32), hi.astype(np.float32)
     return np.array(idx, dtype=np.int64), lo, hi, lim
+
+
+# ---- pair classes -------------------------------------------------------------------------------
+_GEOM_TYPE_NAMES = {0: "plane", 2: "sphere", 3: "capsule", 5: "cylinder", 6: "box", 7: "mesh"}
+#: pair classes whose distance function is MuJoCo 2.0's own ("same"); every other class is a documented deviation
+EXACT_PAIR_CLASSES = frozenset(["plane-sphere", "plane-capsule", "plane-cylinder", "plane-box", "plane-mesh", "sphere-sphere", "sphere-capsule",
+                                "capsule-capsule", "sphere-box"])
+
+
+def pair_classes(model: CompiledModel) -> List[str]:
+    """One class label per candidate pair of `model.pair_geom`: "<type1>-<type2>" with the geom types in MuJoCo's order
+    (plane < sphere < capsule < cylinder < box < mesh), e.g. "sphere-cylinder" -- the rows of DESIGN.md section 3's table."""
+    t = np.asarray(model.geom_type)[np.asarray(model.pair_geom, dtype=np.int64).reshape(-1, 2)]
+    t = np.sort(t, axis=1)
+    return [f"{_GEOM_TYPE_NAMES[int(a)]}-{_GEOM_TYPE_NAMES[int(b)]}" for a, b in t]
+
+
+def ignored_pair_mask(model: CompiledModel, ignored_contacts=()) -> np.ndarray:
+    """bool per candidate pair: the scene drops it (its ordered MuJoCo geom ids are in `ignored_contacts`)"""
+    ign = {make_ordered_pair(int(a), int(b)) for a, b in ignored_contacts}
+    mj = np.asarray(model.geom_mjid)
+    return np.array([make_ordered_pair(int(mj[a]), int(mj[b])) in ign for a, b in np.asarray(model.pair_geom).reshape(-1, 2)], dtype=bool)
+
+
+def deviating_pair_mask(model: CompiledModel, ignored_contacts=()) -> np.ndarray:
+    """bool per candidate pair: its class is one DESIGN.md section 3 lists as a deviation from MuJoCo 2.0 -- any pair with a
+    cylinder other than plane-cylinder, capsule-box, box-box, and the non-plane mesh pairs -- and the scene does not drop the
+    pair as ignored.  (Exact classes: plane-*, sphere-sphere, sphere-capsule, capsule-capsule, sphere-box.)"""
+    dev = np.array([c not in EXACT_PAIR_CLASSES for c in pair_classes(model)], dtype=bool)
+    return dev & ~ignored_pair_mask(model, ignored_contacts)
