@@ -16,7 +16,9 @@ obstacle envs (7 arm entries per action, Lift adds the gripper entry, which a pl
 the last waypoint of its path, :163-167) and PusherObstacle-v0 (4 joints, joint0 UNLIMITED: query endpoints are wrapped into
 (-3.14, 3.14) before planning and the returned steps un-wrapped across the seam, as `SamplingBasedPlanner.plan` does --
 `wrap_unlimited`, `seam_steps_np`, `mopa_paths_unwrap_seam_batch`; `RolloutConfig.for_env` carries config/pusher.py).  The `reuse_data` relabelling (:204-300) -- extra transitions between random
-pairs of waypoints of an executed path -- is `reuse_transitions()` below, fed by `agent_step(..., record=True)`.
+pairs of waypoints of an executed path -- is fed by `agent_step(..., record=True)`: `reuse_transitions_device()` relabels all envs
+in three launches and leaves the transitions on the device (a `ReuseBatch`), `reuse_transitions()` is the same rule as a host loop
+over envs and draws (the checker of the device form; tests/test_reuse_gpu.py compares the two bit for bit).
 The env is the KINEMATIC one (kinematic_env.py) -- not dynamics parity.
 
 Where the work runs: every validity check (targets, pull-back, interpolated states, densification) and every
@@ -191,6 +193,147 @@ def reuse_transitions(out, cfg, n_arm: int, rng, max_reuse_data: int = 30, grip_
     return extra
 
 
+def draw_reuse_pairs(n_exec, max_reuse_data: int, rng):
+    """The (start, goal) draws of `reuse_transitions` as a table [E, max_reuse_data, 2] int32 (numpy) for
+    `BatchMoPARollout.reuse_transitions_device(..., pairs=...)`: `rng` (one object, or a callable env -> object) is consumed
+    exactly as the host loop consumes it -- the same `randint` calls in the same order, envs with more than 3 executed
+    waypoints only, min(n_exec, max_reuse_data) draws per env -- so the draws of a numpy RandomState (the reference's) reach
+    the device.  A draw the host loop skips (no room for a goal; a pair its env drew before) is (-1, -1)."""
+    nexec = n_exec.cpu().numpy() if hasattr(n_exec, "cpu") else np.asarray(n_exec)
+    table = np.full((len(nexec), int(max_reuse_data), 2), -1, dtype=np.int32)
+    for e in np.where(nexec > 3)[0]:
+        draw = rng(int(e)) if callable(rng) else rng
+        L = int(nexec[e])
+        seen = set()
+        for i in range(min(L, max_reuse_data)):
+            start = draw.randint(low=0, high=L - 1)
+            if start + 1 > L - 1:
+                continue
+            goal = draw.randint(low=start + 1, high=L)
+            if (start, goal) in seen:
+                continue
+            seen.add((start, goal))
+            table[e, i] = (start, goal)
+    return table
+
+
+@dataclass
+class ReuseBatch:
+    """What `BatchMoPARollout.reuse_transitions_device` returns: the relabelled transitions as device tensors.  `count` [1] int64
+    is the number kept (the true number, also when it exceeds the capacity `cap` = rows of the other tensors); rows
+    0 .. min(count, cap) - 1 are the transitions, ordered by env, then draw, as the host function lists them; rows behind them
+    hold whatever the buffers held before.  `ac_type` is None unless the rollout has the discrete head."""
+    count: "object"
+    env: "object"
+    start: "object"
+    goal: "object"
+    ob: "object"
+    ac: "object"
+    rew: "object"
+    done: "object"
+    intra_steps: "object"
+    ob_next: "object"
+    ac_type: "object" = None
+
+    @property
+    def cap(self) -> int:
+        return int(self.env.shape[0])
+
+    def to_list(self):
+        """the host function's list of dicts of numpy values (the one place that reads back, and so waits for the device)"""
+        n = min(int(self.count.cpu()[0]), self.cap)
+        col = {k: getattr(self, k)[:n].cpu().numpy() for k in ("env", "start", "goal", "ob", "ac", "rew", "done", "intra_steps", "ob_next")}
+        ac_type = self.ac_type[:n].cpu().numpy() if self.ac_type is not None else None
+        out = []
+        for r in range(n):
+            out.append({"env": int(col["env"][r]), "start": int(col["start"][r]), "goal": int(col["goal"][r]), "ob": col["ob"][r],
+                        "ac": col["ac"][r], "rew": float(col["rew"][r]), "done": int(col["done"][r]),
+                        "intra_steps": int(col["intra_steps"][r]), "ob_next": col["ob_next"][r]})
+            if ac_type is not None:
+                out[-1]["ac_type"] = int(ac_type[r])
+        return out
+
+
+_INV_DISC = {}
+
+
+def reuse_transitions_device(out, cfg, n_arm: int, max_reuse_data: int = 30, grip_qpos_idx=None, pairs=None, cap=None, env_mask=None,
+                             into=None, t: int = 0):
+    """`reuse_transitions` on the device (library call mopa_reuse_batch: three launches on the current stream, no read-back
+    and no synchronisation): the record of `agent_step(..., record=True)` -> a `ReuseBatch` of device tensors whose rows are the
+    host function's list, bit for bit and in its order (tests/test_reuse_gpu.py).
+    pairs     [E, max_reuse_data, 2] int32 (numpy or device tensor; `draw_reuse_pairs` builds it from a RandomState-like
+              object): draw i of env e; (-1, -1) and out-of-range entries emit nothing.  None: the draws come from the
+              library's counter RNG on the device, key (cfg.seed + t, stream 3 * env_id_total + global env id) -- behind the
+              planners' streams e, E + e, 2E + e --, counters 2i and 2i + 1 through randint(low, high) = low + min(int(u * (high -
+              low)), high - low - 1): a sharded rollout draws what the unsharded one draws.
+    cap       rows of the result (default E * max_reuse_data, which always suffices); `count` holds the true number either way
+    env_mask  [E] bool / uint8: envs with a zero entry emit nothing (a `walk_chunk` rollout: the record of an env is complete
+              only in the call in which it `stepped`)
+    into      a ReuseBatch of the same shapes whose tensors are written (no allocation); rows beyond the count stay as they are
+    The IK action space raises NotImplementedError (see `reuse_transitions`: the reference cannot reach that branch)."""
+    torch = _torch()
+    rec = out["record"]
+    if cfg.use_ik_target:
+        raise NotImplementedError("reuse_data relabelling for the IK action space (cart_list / quat_list, rl/mopa_rollouts.py:247-262)")
+    if grip_qpos_idx is None and int(out["ac"].shape[1]) > n_arm:
+        raise ValueError("the env's action has a gripper entry: pass grip_qpos_idx (BatchMoPARollout.reuse_transitions_device does)")
+    normal = cfg.ac_space_type == "normal"
+    if not normal and cfg.ac_space_type != "piecewise":
+        raise NotImplementedError(cfg.ac_space_type)
+    R = int(max_reuse_data)
+    grip = -1 if grip_qpos_idx is None else int(grip_qpos_idx)
+    dof = int(n_arm) + (1 if grip >= 0 else 0)
+    ob, mr, dn, nexec = rec["ob"].contiguous(), rec["meta_rew"].contiguous(), rec["done"].contiguous(), rec["n_exec"].contiguous()
+    wp = rec["waypoint"].contiguous()
+    if not ob.is_cuda:
+        raise _lib.MopaError("reuse_transitions_device: the record is not on a GPU (there is no CPU fallback; reuse_transitions is the host form)")
+    E, L, D = (int(x) for x in ob.shape)
+    f64 = torch.float64
+    if (tuple(wp.shape[:2]) != (E, L) or tuple(mr.shape) != (E, L) or tuple(dn.shape) != (E, L) or tuple(nexec.shape) != (E,) or dn.dtype != torch.uint8
+            or nexec.dtype != torch.int64 or ob.dtype != f64 or mr.dtype != f64 or wp.dtype != f64):
+        raise _lib.MopaError("reuse_transitions_device: not a record of agent_step(..., record=True)")
+    dev = ob.device
+    ac_type = out["ac_type"].reshape(-1).to(torch.int32).contiguous() if (cfg.discrete_action and "ac_type" in out) else None
+    if env_mask is not None:
+        env_mask = env_mask.to(torch.uint8).contiguous()
+        if tuple(env_mask.shape) != (E,):
+            raise _lib.MopaError("reuse_transitions_device: env_mask is not [E]")
+    if pairs is not None:
+        pairs = torch.as_tensor(pairs, dtype=torch.int32).to(dev).contiguous()
+        if tuple(pairs.shape) != (E, R, 2):
+            raise _lib.MopaError(f"reuse_transitions_device: pairs is not [E, max_reuse_data, 2] = {(E, R, 2)}")
+    cap = E * R if cap is None else int(cap)
+    if into is None:
+        rows = max(cap, 0)
+        mk = lambda *sh, dt=f64: torch.empty(*sh, dtype=dt, device=dev)
+        into = ReuseBatch(count=mk(1, dt=torch.int64), env=mk(rows, dt=torch.int32), start=mk(rows, dt=torch.int32), goal=mk(rows, dt=torch.int32),
+                          ob=mk(rows, D), ac=mk(rows, dof), rew=mk(rows), done=mk(rows, dt=torch.uint8), intra_steps=mk(rows, dt=torch.int32),
+                          ob_next=mk(rows, D), ac_type=mk(rows, dt=torch.int32) if ac_type is not None else None)
+    elif into.cap != cap or tuple(into.ob.shape) != (cap, D) or tuple(into.ac.shape) != (cap, dof) or (into.ac_type is None) != (ac_type is None):
+        raise _lib.MopaError("reuse_transitions_device: `into` has other shapes than this call")
+    key = (str(dev), L, float(cfg.discount_factor))
+    inv = _INV_DISC.get(key)
+    if inv is None:      # gamma^-(start + 1) as the host function forms it, once per record length
+        inv = _INV_DISC[key] = torch.tensor([cfg.discount_factor ** (-(k + 1)) for k in range(L)], dtype=f64, device=dev)
+    work = torch.empty(2 * max(E, 1), dtype=torch.int64, device=dev)
+    ptr = lambda x: x.data_ptr() if x is not None else None
+    # the constants of agent_planning.displacement_to_action, formed as its expressions form them (Python doubles)
+    c1 = 1.0 if normal else (cfg.action_range - cfg.ac_scale) / (1.0 - cfg.ac_scale)
+    c2 = 1.0 if normal else (1.0 - cfg.ac_scale) / (1.0 - cfg.omega)
+    stream = torch.cuda.current_stream(dev)
+    _lib.check(_lib.lib().mopa_reuse_batch(
+        E, L, D, int(wp.shape[2]), int(n_arm), dof, grip, ptr(ob), ptr(mr), ptr(dn), ptr(wp), ptr(nexec), ptr(ac_type), ptr(env_mask),
+        cfg.ac_scale, cfg.omega, cfg.omega / cfg.ac_scale, c1, c2, cfg.action_range, int(normal), ptr(inv), R, ptr(pairs),
+        (int(cfg.seed) + int(t)) & 0xFFFFFFFFFFFFFFFF, int(cfg.env_id_base), int(cfg.env_id_total) or E, cap, ptr(work), ptr(into.count),
+        ptr(into.env), ptr(into.start), ptr(into.goal), ptr(into.ac), ptr(into.rew), ptr(into.done), ptr(into.intra_steps), ptr(into.ob),
+        ptr(into.ob_next), ptr(into.ac_type), stream.cuda_stream))
+    for x in (ob, mr, dn, wp, nexec, ac_type, env_mask, pairs, inv, work):      # (tensors of another stream's allocator pool)
+        if x is not None:
+            x.record_stream(stream)
+    return into
+
+
 _SIDE_STREAMS = {}
 
 
@@ -275,6 +418,15 @@ class BatchMoPARollout:
         f = self.env.facts
         grip = int(f.grip_qpos_idx[0]) if self.ac_dim > self.n and len(f.grip_qpos_idx) else None
         return reuse_transitions(out, self.cfg, self.n, rng, max_reuse_data=max_reuse_data, grip_qpos_idx=grip)
+
+    def reuse_transitions_device(self, out, max_reuse_data: int = 30, pairs=None, cap=None, env_mask=None, into=None):
+        """`reuse_transitions_device` on a recorded step of this rollout: the gripper joint is supplied as in
+        `reuse_transitions`; without `pairs` the draws are keyed by (cfg.seed + self.t, cfg.env_id_base, cfg.env_id_total or E)
+        -- `self.t` as it stands when this is called.  Runs on the current stream; returns a `ReuseBatch`."""
+        f = self.env.facts
+        grip = int(f.grip_qpos_idx[0]) if self.ac_dim > self.n and len(f.grip_qpos_idx) else None
+        return reuse_transitions_device(out, self.cfg, self.n, max_reuse_data=max_reuse_data, grip_qpos_idx=grip, pairs=pairs, cap=cap,
+                                        env_mask=env_mask, into=into, t=self.t)
 
     def __init__(self, env, cfg: Optional[RolloutConfig] = None):
         torch = _torch()
