@@ -619,6 +619,36 @@ int mopa_reuse_batch(int64_t E, int32_t L, int32_t D, int32_t nq, int32_t n_arm,
                      double *out_ac_dev, double *out_rew_dev, uint8_t *out_done_dev, int32_t *out_intra_dev, double *out_ob_dev,
                      double *out_ob_next_dev, int32_t *out_ac_type_dev, void *stream);
 
+/* The replay sink (the reference's rl/dataset.py as its trainer uses it: runner.run(every_steps=1), rl/trainer.py:280, so every stored rollout
+ * holds ONE transition, the ring overwrites the oldest and RandomSampler, rl/dataset.py:51-84, draws uniformly over the stored transitions;
+ * mopa_rl_amd/replay.py::DeviceReplayBuffer is the Python form).  All buffers on the device, nothing is read back.
+ *   ring        [capacity, W] float32, W = 2 * D + A + 4; a row is  ob[D] | ac[A] | rew | done | intra_steps | ac_type | ob_next[D]  -- the width of a
+ *               TransitionExchange record, with ac_type where that record has `stepped`.  Doubles are narrowed with (float)x (round to nearest
+ *               even), integers and bytes converted exactly.
+ *   state       [2] int64: state[0] = rows appended since creation, state[1] = min(state[0], capacity) = rows a sampler may draw.
+ * mopa_replay_append selects rows of a source of n rows and writes them behind the ring's head, at most two launches on `stream` (n = 0: none):
+ *   selection   mask [n] bytes: the rows with a non-zero byte, ascending; count [1] int64: rows 0 .. min(count, n) - 1 (a negative count keeps
+ *               none); neither: all n rows; both: MOPA_ERR_INVALID_ARG.
+ *   destination the k-th kept row goes to ring row (state[0] + k) % capacity; of m > capacity kept rows the first m - capacity are skipped, so no
+ *               ring row is written twice in one call; then state[0] += m.  The order is computed (scan over the keep flags, 1024 at a time
+ *               with a running carry), not raced for: every run writes the same bytes.
+ *   source (a)  columns: ob [n,D], ac [n,ac_ld] (the first A entries of a row are taken; ac_ld >= A), rew [n] doubles, done [n] bytes, intra [n]
+ *               int64 (intra_is_int64 != 0) or int32, ob_next [n,D], ac_type [n] int32 or NULL (stored as 0); packed = NULL
+ *   source (b)  packed [n,W] float32 exchange records; column D + A + 3 (`stepped`) is the mask -- non-zero keeps the row --, the stored ac_type
+ *               is 0; mask, count and every column pointer NULL
+ *   work        [n + 2] int64 scratch.
+ * mopa_replay_sample draws B * n_batches rows, one launch on `stream`: draw i takes u = uniform(key(seed, stream_id), counter draw_base + i) of the
+ * counter RNG and the ring row min(int(u * size), size - 1) with size = state[1] read on the device -> out [B * n_batches, W], out_idx
+ * [B * n_batches] int64.  size = 0: the rows are zero-filled and the indices are -1.  (draw_base by value: the caller keeps the counter.)
+ * Argument errors (a NULL required buffer, capacity < 1, D < 1, A < 1, ac_ld < A, n < 0, B < 1, n_batches < 1, both a mask and a count, a
+ * packed source next to a mask, a count or columns) return MOPA_ERR_INVALID_ARG before any launch. */
+int mopa_replay_append(int64_t capacity, int32_t D, int32_t A, float *ring_dev, int64_t *state_dev, int64_t n,
+                       const uint8_t *mask_dev, const int64_t *count_dev, const double *ob_dev, const double *ac_dev, int32_t ac_ld,
+                       const double *rew_dev, const uint8_t *done_dev, const void *intra_dev, int32_t intra_is_int64,
+                       const double *ob_next_dev, const int32_t *ac_type_dev, const float *packed_dev, int64_t *work_dev, void *stream);
+int mopa_replay_sample(int64_t capacity, int32_t D, int32_t A, const float *ring_dev, const int64_t *state_dev, int64_t B, int64_t n_batches,
+                       uint64_t seed, uint64_t stream_id, uint64_t draw_base, float *out_dev, int64_t *out_idx_dev, void *stream);
+
 /* The arm state the NEXT mopa_env_step_batch call with the same arguments would reach (desired_state clamped to ctrlrange
  * and joint limits), without stepping: input of a collision gate (mopa_is_valid_batch with samples_per_env = 1 -> move_mask). */
 int mopa_env_desired_batch(MopaEnv *env, int64_t E, const double *qpos_dev /*[E,nq]*/, const double *prev_state_dev /*[E,n_arm]*/,

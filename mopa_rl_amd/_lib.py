@@ -29,7 +29,7 @@ EXPORTED_SYMBOLS = [
     "mopa_is_valid_batch", "mopa_check_motion_batch", "mopa_plan_batch", "mopa_pullback_batch", "mopa_is_valid_state", "mopa_plan",
     "mopa_planner_status", "mopa_debug_fk", "mopa_debug_pair_dist", "mopa_contacts_batch", "mopa_contacts_state",
     "mopa_env_create", "mopa_env_destroy", "mopa_env_obs_dim", "mopa_env_action_dim", "mopa_env_step_batch", "mopa_env_exec_batch", "mopa_env_desired_batch",
-    "mopa_env_attach_dynamics", "mopa_env_attach_contacts", "mopa_env_set_contact_stats", "mopa_rollout_stage", "mopa_rollout_pool_pick", "mopa_rollout_step_size", "mopa_reuse_batch", "mopa_ct_desc_size", "mopa_env_contact_arena", "mopa_env_dyn_dofs", "mopa_env_dyn_qvel_width", "mopa_env_dyn_forward_batch", "mopa_env_dyn_substeps_batch", "mopa_env_step_dyn_batch",
+    "mopa_env_attach_dynamics", "mopa_env_attach_contacts", "mopa_env_set_contact_stats", "mopa_rollout_stage", "mopa_rollout_pool_pick", "mopa_rollout_step_size", "mopa_reuse_batch", "mopa_replay_append", "mopa_replay_sample", "mopa_ct_desc_size", "mopa_env_contact_arena", "mopa_env_dyn_dofs", "mopa_env_dyn_qvel_width", "mopa_env_dyn_forward_batch", "mopa_env_dyn_substeps_batch", "mopa_env_step_dyn_batch",
     "mopa_pusher_dyn_desc_size", "mopa_env_attach_pusher_dynamics", "mopa_env_set_pusher_stats", "mopa_env_pusher_substeps_batch",
     "mopa_env_step_pusher_batch",
     "mopa_ik_create", "mopa_ik_destroy", "mopa_ik_solve_batch", "mopa_ik_site_pose_batch", "mopa_ik_targets_batch",
@@ -210,6 +210,8 @@ def lib() -> C.CDLL:
     L.mopa_rollout_step_size.argtypes = []
     L.mopa_reuse_batch.argtypes = ([C.c_int64] + [C.c_int32] * 6 + [vp] * 7 + [C.c_double] * 6 + [C.c_int32, vp, C.c_int32, vp, C.c_uint64, C.c_int64, C.c_int64,
                                                                                                    C.c_int64] + [vp] * 13)
+    L.mopa_replay_append.argtypes = [C.c_int64, C.c_int32, C.c_int32, vp, vp, C.c_int64, vp, vp, vp, vp, C.c_int32, vp, vp, vp, C.c_int32, vp, vp, vp, vp, vp]
+    L.mopa_replay_sample.argtypes = [C.c_int64, C.c_int32, C.c_int32, vp, vp, C.c_int64, C.c_int64, C.c_uint64, C.c_uint64, C.c_uint64, vp, vp, vp]
     L.mopa_ct_desc_size.argtypes = []
     L.mopa_env_contact_arena.argtypes = [vp]
     L.mopa_env_contact_arena.restype = C.c_int
