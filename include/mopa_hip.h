@@ -539,6 +539,24 @@ int mopa_env_step_pusher_batch(MopaEnv *env, int64_t E, double *qpos_dev, double
                                const uint8_t *move_mask_dev, double *obs_dev, double *reward_dev, uint8_t *done_dev,
                                uint8_t *success_dev, void *stream);
 
+/* ---- contact-force readout of the solver-backed contact stages (K7: mopa_env_attach_contacts, K8: mopa_env_attach_pusher_dynamics) ----
+ * `env.get_contact_force()` (env/base.py:568-581: sum over the contacts of sum_k |mj_contactForce(i)[k]|, read from the constraint forces
+ * the last sub-step of `_do_simulation` left), for the launches that follow -- env.step and the raw sub-step entry points alike.  After the
+ * last sub-step of a launch, for every env that ran a sub-step in it (the others keep their values):
+ *   rows [E,K,8]  per contact of the launch's last constraint solve (K7: the solve of the last sub-step; K8: the 4th RK4 stage of the last
+ *                 sub-step): pair (index into pr_f / pr_s resp. the Pusher pair records), key (K7: feature index, K8: signed distance),
+ *                 f0 .. f5 = mj_contactForce in the contact frame (elliptic cones: the contact's dim solver forces, zero-padded; pyramidal
+ *                 cones with edge forces p: f0 = (p0 + p1) + (p2 + p3), f1 = mu (p0 - p1), f2 = mu (p2 - p3)); joint-limit rows are no contacts
+ *   force [E]     sum over the contacts, in contact order, of ((((|f0| + |f1|) + |f2|) + |f3|) + |f4|) + |f5| -- plain adds: the host
+ *                 reproduces it from the rows bit for bit
+ *   total [E]     += force (the caller's accumulator: a rollout's per-episode sum)
+ *   count [E]     contacts
+ * All pointers NULL: off.  MOPA_ERR_INVALID_ARG: rows with K below the stage's maxcon; an env without such a stage (kinematic, servo
+ * dynamics alone, the penalty-contact object); force NULL with another pointer set.  The contact-free 16-lane form reports zeros.
+ * PARITY UNPINNED against MuJoCo, like the solves it reads. */
+int mopa_env_set_contact_force(MopaEnv *env, double *force_dev /*[E]*/, double *total_dev /*[E] in/out, or NULL*/,
+                               double *rows_dev /*[E,K,8] or NULL*/, int32_t *count_dev /*[E] or NULL*/, int32_t K);
+
 /* ---- bookkeeping of one batched rollout call (rl/mopa_rollouts.py:70-375 + rl/sac_agent.py:148-318 for E envs at once) -------------
  * The elementwise work of mopa_rl_amd/rollout.py::BatchMoPARollout.agent_step between the library's launches, as six
  * one-wave-per-env kernels (mopa_rollstep.inc names the stages).  All pointers are device buffers; bool buffers are bytes. */

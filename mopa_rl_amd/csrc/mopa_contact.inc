@@ -54,6 +54,7 @@ struct CtHdr {
     double o_mass, o_in0, o_in1, o_in2, o_ipx, o_ipy, o_ipz, o_iqw, o_iqx, o_iqy, o_iqz, o_damp;
     double o_imass, o_iin0, o_iin1, o_iin2, o_imass_d, o_iin0_d, o_iin1_d, o_iin2_d;
     double tol, inv_scale, margin_pre, noslip_tol, lim_par[8], margin_near;
+    CfOut cf;                                       // contact-force readout (mopa_env_set_contact_force rewrites it in place); cf.force == nullptr: off
 };
 
 #define DLW(slot) W[(size_t)(slot) * ST]
@@ -1133,8 +1134,59 @@ __device__ __forceinline__ void ct_substep(const DynHdr &dh, const CtHdr &ch, co
     CT_TICK(6);
 }
 
+// Contact-force readout (mopa_env_set_contact_force), after the sub-step loop: what mj_contactForce would return for the `ncon` contacts of
+// the launch's LAST constraint solve (the solve of the last sub-step, at the state that sub-step started from), read from the records that
+// solve left in LDS -- the post-noslip forces, the ones that acted.  Elliptic cones (SOLVER 2): the contact's dim solver forces; pyramidal
+// cones: normal and tangential sums of the four edge forces, the expression order of ct_substep's J^T f.  Lane c holds contact c and
+// writes its row (pair, feature, f0 .. f5); s_c = |f0| + .. + |f5| and the sum over the contacts in contact order are plain adds, so the
+// host reproduces `force` from the rows bit for bit; lane 0 writes the scalars.  PARITY UNPINNED like the solve it reads.
+template <int ST, int SOLVER>
+__device__ __forceinline__ void ct_force_readout(const CtHdr &ch, const double *W, int l, int grp, int nd, int ncon, bool write, long long e,
+                                                 const CfOut &cf) {
+    double f[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    long long ids = 0;
+    if (l < ncon) {
+        if constexpr (SOLVER == 2) {
+            const CtRecRef r = ct_rec_w<6>(ch, (int)__double_as_longlong(DLW(ch.tab_slot + l)), l, nd);
+            ids = __double_as_longlong(DLW(r.s + CT_IDS));
+#pragma unroll
+            for (int a = 0; a < kCtMaxDim; a++)
+                if (a < r.dim) f[a] = DLW(r.row_s + 2 * r.dim + a);
+        } else {
+            const int s = ch.con_slot + kCtRec * l;
+            ids = __double_as_longlong(DLW(s + CT_KEY));
+            const double f0 = DLW(s + CT_FS), f1 = DLW(s + CT_FS + 1), f2 = DLW(s + CT_FS + 2), f3 = DLW(s + CT_FS + 3), mu = DLW(s + CT_MU);
+            f[0] = (f0 + f1) + (f2 + f3);
+            f[1] = mu * (f0 - f1);
+            f[2] = mu * (f2 - f3);
+        }
+    }
+    const double s_l = ((((fabs(f[0]) + fabs(f[1])) + fabs(f[2])) + fabs(f[3])) + fabs(f[4])) + fabs(f[5]);
+    double force = 0.0;
+#pragma unroll
+    for (int c = 0; c < 16; c++) {
+        const double s_c = __shfl(s_l, 16 * grp + c, 64);
+        if (c < ncon) force = force + s_c;
+    }
+    if (!write) return;
+    if (cf.rows && l < ncon) {
+        double *row = cf.rows + ((size_t)e * (size_t)cf.K + (size_t)l) * 8;
+        row[0] = (double)(int)(ids & 0xffff);
+        row[1] = (double)(int)((ids >> 16) & 0xffff);
+#pragma unroll
+        for (int a = 0; a < 6; a++) row[2 + a] = f[a];
+    }
+    if (l == 0) {
+        cf.force[e] = force;
+        if (cf.total) cf.total[e] = cf.total[e] + force;
+        if (cf.count) cf.count[e] = ncon;
+    }
+}
+
 // mode 0: env.step's physics (ctrl from the action, prev_state / has_prev updated, dh.nsub sub-steps when the move flag is set);
 // mode 1: n_steps sub-steps towards the given ctrl rows [E, nd].  qvel rows are [nd + 6].
+// ch.cf (optional, cf.force != nullptr): the contact-force readout of the last sub-step, for the envs that ran one -- in the header the
+// kernel reads through scalar loads anyway, so the kernel's arguments (and what it keeps in registers over the sub-step loop) stay as they were.
 template <int KIND, int SOLVER>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void k_env_dyn_ct(
     EnvHdr h, const DynHdr *__restrict__ dhp, const CtHdr *__restrict__ chp, const double *__restrict__ GD, const int32_t *__restrict__ GI,
@@ -1219,6 +1271,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void
 #ifdef MOPA_CT_PROF
     cnt.maxc = (int)(wall_clock64() - tw0_);       // prof builds: the wave's time in the sub-step loop (100 MHz ticks) in the max-contacts word
 #endif
+    if (ch.cf.force) ct_force_readout<ST, SOLVER>(ch, W, l, grp, dh.nd, nwarm, live && n_steps > 0, e, ch.cf);
     if (live && l == 0) {
         for (int i = 0; i < dh.nd; i++) {
             row[dh.qadr[i]] = DLW(DL_Q + i);
@@ -1351,6 +1404,8 @@ extern "C" int mopa_env_attach_contacts(MopaEnv *env, const MopaCtDesc *d) {
     env->ct_on = true;
     env->ct_solver = d->solver;
     env->ct_arena = ch.arena;
+    env->ct_maxcon = d->maxcon;
+    env->cf = CfOut{nullptr, nullptr, nullptr, nullptr, 0};
     env->dyn.nv = nd + (smooth_only ? 0 : 6);
     HIP_TRY(hipMemcpy(env->d_dynhdr, &env->dyn, sizeof(DynHdr), hipMemcpyHostToDevice));
     for (const void *k : {(const void *)k_env_dyn_ct<0, 0>, (const void *)k_env_dyn_ct<1, 0>, (const void *)k_env_dyn_ct<2, 0>,

@@ -43,6 +43,15 @@ struct DynHdr {
 };
 struct DynObs { int nd, nv; int arm_dof[8], grip_dof[4]; };   // what the obs needs of it
 
+// Contact-force readout of the solver-backed contact stages (K7, K8; mopa_env_set_contact_force): after the last sub-step of a launch the
+// kernel writes, per env that ran a sub-step, force [E] (sum over the contacts of the last constraint solve of |f0| + .. + |f5| of what
+// mj_contactForce returns), total [E] += force, rows [E, K, 8] = (pair, key, f0 .. f5) per contact, count [E].  force == nullptr: off.
+struct CfOut {
+    double *force, *total, *rows;
+    int32_t *count;
+    int K;
+};
+
 struct MopaEnv {
     int device = 0;
     EnvHdr hdr{};
@@ -62,10 +71,13 @@ struct MopaEnv {
     bool ct_on = false;
     int ct_solver = 0;      // 0: projected Gauss-Seidel, 1: Newton (pyramidal cones), 2: Newton (elliptic cones)
     int ct_arena = 0;       // solver 2: LDS slots (doubles) the contact records of an env share
+    int ct_maxcon = 0;      // contacts an env keeps per sub-step (rows of a contact-force readout)
     int32_t *ct_stats = nullptr;
     // K8 (mopa_pusher_dyn.inc): the Pusher dynamics attached to this env, freed with it
     void *pusher = nullptr;
     void (*pusher_free)(void *) = nullptr;
+    int pusher_maxcon = 0;
+    CfOut cf{nullptr, nullptr, nullptr, nullptr, 0};      // contact-force readout of K7 / K8, off by default
     // waypoint execution scratch (one slot per env and waypoint), per stream, grow-only; outgrown buffers are retired and
     // freed with the handle (a kernel in flight may still read them)
     std::mutex mu;

@@ -91,6 +91,7 @@ struct PdCon {
     double Jn[kPdMaxCon][kPdNv], Jt[kPdMaxCon][kPdNv];
     double dist[kPdMaxCon];
     int pair[kPdMaxCon];
+    double mu[kPdMaxCon], D[kPdMaxCon][4], aref[kPdMaxCon][4];      // the rows' friction, weight and reference acceleration (kept for the readout)
 };
 
 // kinematics of the planar tree: poses of the arm bodies (0..3) and of the box (4)
@@ -392,7 +393,6 @@ __device__ __forceinline__ void pd_forward(const PdHdr &ph, const double *__rest
     // rows of the contacts: edge i = Jn + s mu Jt (i = 0, 1: s = +1, -1 along the in-plane tangent), Jn (i = 2, 3: the tangent
     // along z moves no dof); weight D = 1 / R, R = (1 - imp) / imp * A_ii with A_ii = J_i M^-1 J_i^T; reference acceleration
     // aref = -B J_i v - K imp (dist - margin)
-    double cmu[kPdMaxCon], cD[kPdMaxCon][4], cA[kPdMaxCon][4];
 #pragma unroll 1
     for (int c = 0; c < C.n; c++) {
         const double *par = PR + (size_t)kPdPairRec * C.pair[c] + 13;
@@ -413,7 +413,7 @@ __device__ __forceinline__ void pd_forward(const PdHdr &ph, const double *__rest
         const double mu = par[0];
         const double imp = pd_impedance(par, C.dist[c]);
         const double kpos = (par[2] * imp) * (C.dist[c] - par[1]);
-        cmu[c] = mu;
+        C.mu[c] = mu;
 #pragma unroll
         for (int i = 0; i < 4; i++) {
             const double sm = i == 0 ? mu : (i == 1 ? -mu : 0.0);
@@ -421,8 +421,8 @@ __device__ __forceinline__ void pd_forward(const PdHdr &ph, const double *__rest
             double Ri = ((1.0 - imp) / imp) * Aii;
             if (Ri < kPdMinVal) Ri = kPdMinVal;
             const double jv = jvn + sm * jvt;
-            cD[c][i] = 1.0 / Ri;
-            cA[c][i] = -(par[3] * jv) - kpos;
+            C.D[c][i] = 1.0 / Ri;
+            C.aref[c][i] = -(par[3] * jv) - kpos;
         }
     }
     // ---- primal Newton: minimise 1/2 (a - a0)' M (a - a0) + sum_rows 1/2 D min(0, J a - aref)^2
@@ -454,10 +454,10 @@ __device__ __forceinline__ void pd_forward(const PdHdr &ph, const double *__rest
             for (int i = 0; i < kPdNv; i++) { un = un + C.Jn[c][i] * qacc[i]; ut = ut + C.Jt[c][i] * qacc[i]; }
 #pragma unroll
             for (int r = 0; r < 4; r++) {
-                const double sm = r == 0 ? cmu[c] : (r == 1 ? -cmu[c] : 0.0);
-                const double x = (un + sm * ut) - cA[c][r];
+                const double sm = r == 0 ? C.mu[c] : (r == 1 ? -C.mu[c] : 0.0);
+                const double x = (un + sm * ut) - C.aref[c][r];
                 if (!(x < 0.0)) continue;
-                const double D = cD[c][r];
+                const double D = C.D[c][r];
                 p0 = p0 + (0.5 * D * x) * x;
                 double J[kPdNv];
 #pragma unroll
@@ -514,12 +514,12 @@ __device__ __forceinline__ void pd_forward(const PdHdr &ph, const double *__rest
                 }
 #pragma unroll
                 for (int r = 0; r < 4; r++) {
-                    const double sm = r == 0 ? cmu[c] : (r == 1 ? -cmu[c] : 0.0);
-                    const double x = (un + sm * ut) - cA[c][r], jd = dn + sm * dt;
+                    const double sm = r == 0 ? C.mu[c] : (r == 1 ? -C.mu[c] : 0.0);
+                    const double x = (un + sm * ut) - C.aref[c][r], jd = dn + sm * dt;
                     const double xr = x + alpha * jd;
                     if ((x < 0.0) != (xr < 0.0)) chg = true;
                     if (xr < 0.0) {
-                        const double D = cD[c][r];
+                        const double D = C.D[c][r];
                         d1 = d1 + (D * xr) * jd;
                         d2 = d2 + (D * jd) * jd;
                         pa = pa + (0.5 * D * xr) * xr;
@@ -558,7 +558,7 @@ __device__ __forceinline__ void pd_forward(const PdHdr &ph, const double *__rest
 // in j order), X_i = (q0 + h dX_v, v0 + h dX_a), F_i = (v_i, qacc(X_i)); finally dX = sum_j B[j] F[j], q = q0 + h dX_v,
 // v = v0 + h dX_a.  A = {1/2; 0 1/2; 0 0 1}, B = {1/6, 1/3, 1/3, 1/6}.
 __device__ __forceinline__ void pd_substep(const PdHdr &ph, const double *__restrict__ PR, double *q, double *v, double *iterm,
-                                           const double *desired, const double *prev, const double *tv0, PdCon &C, int &drop) {
+                                           const double *desired, const double *prev, const double *tv0, PdCon &C, int &drop, double *qacc4) {
     double ctrl[kPdArm];
 #pragma unroll
     for (int j = 0; j < kPdArm; j++) {
@@ -595,7 +595,40 @@ __device__ __forceinline__ void pd_substep(const PdHdr &ph, const double *__rest
         for (int j = 1; j < 4; j++) { dv = dv + Fv[j][i] * Bcoef[j]; da = da + Fa[j][i] * Bcoef[j]; }
         q[i] = q[i] + ph.h * dv;
         v[i] = v[i] + ph.h * da;
+        qacc4[i] = Fa[3][i];
     }
+}
+
+// Contact-force readout (mopa_env_set_contact_force), after the sub-step loop: the contacts of the 4th RK4 stage of the last sub-step -- what the
+// constraint forces hold when the reference's `_do_simulation` returns -- with the edge forces recomputed from that stage's qacc
+// (p_r = -D_r x_r where x_r = J_r qacc - aref_r < 0, as tests/pusher_dyn_ref.py's forward(want=True)), decoded as mj_contactForce decodes
+// a pyramid: f0 = (p0 + p1) + (p2 + p3), f1 = mu (p0 - p1), f2 = mu (p2 - p3).  Row: (pair, dist, f0, f1, f2, 0, 0, 0); force = the sum
+// of |f0| + |f1| + |f2| over the contacts in contact order, plain adds.  PARITY UNPINNED like the solve it reads.
+__device__ __forceinline__ void pd_force_readout(const PdCon &C, const double *qacc, long long e, const CfOut &cf) {
+    double force = 0.0;
+#pragma unroll 1
+    for (int c = 0; c < C.n; c++) {
+        double un = 0.0, ut = 0.0;
+#pragma unroll
+        for (int i = 0; i < kPdNv; i++) { un = un + C.Jn[c][i] * qacc[i]; ut = ut + C.Jt[c][i] * qacc[i]; }
+        double p[4];
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+            const double sm = r == 0 ? C.mu[c] : (r == 1 ? -C.mu[c] : 0.0);
+            const double x = (un + sm * ut) - C.aref[c][r];
+            p[r] = x < 0.0 ? -(C.D[c][r] * x) : 0.0;
+        }
+        const double f0 = (p[0] + p[1]) + (p[2] + p[3]);
+        const double f1 = C.mu[c] * (p[0] - p[1]), f2 = C.mu[c] * (p[2] - p[3]);
+        force = force + ((fabs(f0) + fabs(f1)) + fabs(f2));       // (f3 .. f5 = 0: adding them changes no bit)
+        if (cf.rows) {
+            double *row = cf.rows + ((size_t)e * (size_t)cf.K + (size_t)c) * 8;
+            row[0] = (double)C.pair[c]; row[1] = C.dist[c]; row[2] = f0; row[3] = f1; row[4] = f2; row[5] = 0.0; row[6] = 0.0; row[7] = 0.0;
+        }
+    }
+    cf.force[e] = force;
+    if (cf.total) cf.total[e] = cf.total[e] + force;
+    if (cf.count) cf.count[e] = C.n;
 }
 
 // mode 0: env.step physics (desired state by K4's rule, nsub sub-steps, prev_state <- desired); the reward / obs half follows in
@@ -603,12 +636,13 @@ __device__ __forceinline__ void pd_substep(const PdHdr &ph, const double *__rest
 //         env sits the launch out.
 // mode 1: n raw sub-steps towards desired_in [E,4] with prev_state [E,4] as the PID's prev (tests).
 // stats (optional, [E] int32): contacts dropped by the cap over the launch.
+// cf (optional, cf.force != nullptr): the contact-force readout of the last sub-step, for the envs that ran one.
 __global__ __launch_bounds__(64) void k_pusher_dyn(EnvHdr h, const PdHdr *__restrict__ php, const double *__restrict__ GD,
                                                    const int32_t *__restrict__ GI, const double *__restrict__ PR, long long E, int mode, int n_steps,
                                                    double *__restrict__ qpos, double *__restrict__ qvel, double *__restrict__ i_term,
                                                    double *__restrict__ prev_state, unsigned char *__restrict__ has_prev,
                                                    const double *__restrict__ action, int is_planner, const unsigned char *__restrict__ move_mask,
-                                                   const double *__restrict__ desired_in, int32_t *__restrict__ stats) {
+                                                   const double *__restrict__ desired_in, int32_t *__restrict__ stats, CfOut cf) {
     const PdHdr &ph = *php;
     const long long e = (long long)blockIdx.x * 64 + threadIdx.x;
     if (e >= E) return;
@@ -644,9 +678,12 @@ __global__ __launch_bounds__(64) void k_pusher_dyn(EnvHdr h, const PdHdr *__rest
 #pragma unroll
     for (int j = 0; j < kPdArm; j++) it[j] = i_term[e * kPdArm + j];
     PdCon C;
+    C.n = 0;
     int drop = 0;
+    double qacc4[kPdNv] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};      // qacc of the last sub-step's 4th stage (the readout's)
 #pragma unroll 1
-    for (int s = 0; s < n_steps; s++) pd_substep(ph, PR, q, v, it, des, pv, tv0, C, drop);
+    for (int s = 0; s < n_steps; s++) pd_substep(ph, PR, q, v, it, des, pv, tv0, C, drop, qacc4);
+    if (cf.force && n_steps > 0) pd_force_readout(C, qacc4, e, cf);
 #pragma unroll
     for (int i = 0; i < kPdNv; i++) { row[ph.qadr[i]] = q[i]; qvel[e * kPdNv + i] = v[i]; }
 #pragma unroll
@@ -718,6 +755,8 @@ extern "C" int mopa_env_attach_pusher_dynamics(MopaEnv *env, const MopaPusherDyn
     if (env->pusher_free) env->pusher_free(env->pusher);
     env->pusher = pd;
     env->pusher_free = pd_free;
+    env->pusher_maxcon = d->maxcon;
+    env->cf = CfOut{nullptr, nullptr, nullptr, nullptr, 0};
     return MOPA_OK;
 }
 
@@ -732,7 +771,7 @@ static int pd_launch(MopaEnv *env, MopaPusherDyn *pd, int64_t E, int mode, int n
                      uint8_t *has_prev, const double *action, int is_planner, const uint8_t *move_mask, const double *desired, hipStream_t st) {
     const unsigned blocks = (unsigned)((E + 63) / 64);
     hipLaunchKernelGGL(k_pusher_dyn, dim3(blocks), dim3(64), 0, st, env->hdr, pd->d_hdr, env->d_dbl, env->d_int, pd->d_pairs, (long long)E, mode, n,
-                       qpos, qvel, i_term, prev_state, has_prev, action, is_planner, move_mask, desired, pd->stats);
+                       qpos, qvel, i_term, prev_state, has_prev, action, is_planner, move_mask, desired, pd->stats, env->cf);
     HIP_TRY(hipGetLastError());
     return MOPA_OK;
 }
@@ -769,4 +808,24 @@ extern "C" int mopa_env_step_pusher_batch(MopaEnv *env, int64_t E, double *qpos_
     }
     return env_step_launch(env, E, qpos_dev, prev_state_dev, has_prev_dev, ep_len_dev, action_dev, (int)is_planner, move_mask_dev, obs_dev,
                            reward_dev, done_dev, success_dev, qvel_dev, st);
+}
+
+// One entry for both solver-backed contact stages (K7: mopa_env_attach_contacts, K8: mopa_env_attach_pusher_dynamics); the kernels read the
+// pointers at every launch that follows (K7 from its header in device memory, K8 as a kernel argument).  All pointers null: off.  Call it
+// between launches: a launch in flight on another stream may see either setting.
+extern "C" int mopa_env_set_contact_force(MopaEnv *env, double *force_dev, double *total_dev, double *rows_dev, int32_t *count_dev, int32_t K) {
+    if (!env) return fail(MOPA_ERR_INVALID_ARG, "null env");
+    const bool k8 = pd_of(env) != nullptr;
+    if (!k8 && !env->ct_on)
+        return fail(MOPA_ERR_INVALID_ARG, "contact forces need a contact stage behind a constraint solver (K7 contacts or the Pusher dynamics)");
+    if (!force_dev && (total_dev || rows_dev || count_dev)) return fail(MOPA_ERR_INVALID_ARG, "force_dev is null but another output is set");
+    const int maxcon = k8 ? env->pusher_maxcon : env->ct_maxcon;
+    if (rows_dev && K < maxcon) return fail(MOPA_ERR_INVALID_ARG, "rows_dev needs K >= the stage's maxcon rows per env");
+    const CfOut cf{force_dev, total_dev, rows_dev, count_dev, rows_dev ? (int)K : 0};
+    if (!k8) {       // K7 reads it from its device-side header (a blocking copy: ordered behind the launches already on the default stream)
+        ON_DEVICE(env->device);
+        HIP_TRY(hipMemcpy(reinterpret_cast<char *>(env->d_cthdr) + offsetof(CtHdr, cf), &cf, sizeof(CfOut), hipMemcpyHostToDevice));
+    }
+    env->cf = cf;
+    return MOPA_OK;
 }

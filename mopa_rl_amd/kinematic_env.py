@@ -33,6 +33,10 @@ RK4 sub-steps per env.step (frame_dt 1.0), the four hinges and the box slides in
 contacts and the box is pushed, `contacts=False` leaves the arm alone (joint limits stay).  `qvel` [E,6] and the PID's `i_term`
 [E,4] are carried per env.  PARITY UNPINNED.
 
+`enable_contact_force()` (the K7 / K8 envs above) has every stepping launch report the reference's `env.get_contact_force()`
+(env/base.py:568-581) from its last constraint solve: `contact_force`, `contact_force_total`, `contact_count` [E] and, with
+`rows=True`, the per-contact rows.  PARITY UNPINNED like the solves it reads.
+
 `block_invalid=True` adds the one piece of contact behaviour a kinematic arm can have: a step whose desired state is
 in collision (K1 validity kernel, same rule as the planner) is not executed -- the arm stays where it is.
 
@@ -368,6 +372,7 @@ class BatchKinematicEnv:
             self.bias_lag = torch.zeros(self.E, df.nd, dtype=f64, device=dev)    # qfrc_bias of the last mj_forward
         self._desired = torch.zeros(self.E, self.n_arm, dtype=f64, device=dev)
         self._move = torch.zeros(self.E, dtype=torch.uint8, device=dev)
+        self.contact_force = self.contact_force_total = self.contact_count = self.contact_rows = None      # enable_contact_force
         if block_invalid:
             pi = planner_inputs(self.env_name, self.model)
             self._scene = _lib.Scene(pi.model, pi.passive_joint_idx, pi.ignored_contacts, self.spec.contact_threshold,
@@ -430,6 +435,65 @@ class BatchKinematicEnv:
             raise _lib.MopaError("pusher_substeps: a PusherObstacle env with dynamics=True")
         _lib.check(_lib.lib().mopa_env_pusher_substeps_batch(self._h, self.E, _ptr(self.qpos), _ptr(self.qvel), _ptr(self.i_term),
                                                              _ptr(desired), _ptr(prev_state), int(n), _stream_handle(stream)))
+
+    # ---- contact-force readout (`env.get_contact_force()`, env/base.py:568-581) ----------------------------------------------
+    @property
+    def contact_maxcon(self) -> int:
+        """contacts an env of the solver-backed contact stage keeps per constraint solve (0: no such stage)"""
+        if self.pdyn is not None:
+            return int(self.pdyn.maxcon)
+        ct = getattr(self, "ct", None)
+        if ct is not None:
+            return int(ct.maxcon)
+        return 0
+
+    def has_contact_solver(self) -> bool:
+        """True for the envs whose contacts run behind a constraint solver (K7: contacts=True, dyn_lanes=16; K8: the Pusher dynamics) --
+        the ones `enable_contact_force` serves"""
+        return self.pdyn is not None or (self.dynamics and getattr(self, "dyn_lanes", 1) == 16)
+
+    def enable_contact_force(self, rows: bool = False):
+        """Have every stepping launch that follows (`step`, `dyn_substeps`, `pusher_substeps`, waypoint walks) report the reference's
+        `env.get_contact_force()`: sum over the contacts of sum_k |mj_contactForce(i)[k]|, read from the constraint forces of the launch's
+        last sub-step (K7: its one solve; K8: its 4th RK4 stage).  Binds, per env,
+          contact_force [E] f64        of the last launch in which the env ran a sub-step
+          contact_force_total [E] f64  += contact_force at every such launch (zeroed by `reset`)
+          contact_count [E] int32      contacts of that solve
+          contact_rows [E, maxcon, 8]  with rows=True: (pair, key, f0 .. f5) per contact -- pair: index into the stage's directed pairs
+                                       (`ct.pr_f / pr_s`, `pdyn.pair_names`), key: feature index (K7) / signed distance (K8), f: the
+                                       contact-frame force (elliptic cones: the contact's dim solver forces; pyramidal: normal and the two
+                                       tangential sums of the edge forces)
+        `contact_force` is the plain left-to-right sum of ((((|f0| + |f1|) + |f2|) + |f3|) + |f4|) + |f5| over the rows.  PARITY
+        UNPINNED against MuJoCo like the solves it reads.  Raises MopaError on an env without a solver-backed contact stage
+        (kinematic, servo dynamics alone, contacts='penalty')."""
+        torch = _torch()
+        if not self.has_contact_solver():
+            raise _lib.MopaError("enable_contact_force: contact forces need contacts behind a constraint solver "
+                                 "(dynamics=True with contacts=True, or PusherObstacle-v0 with dynamics=True)")
+        dev, f64 = self.device, torch.float64
+        K = self.contact_maxcon
+        force, total = torch.zeros(self.E, dtype=f64, device=dev), torch.zeros(self.E, dtype=f64, device=dev)
+        count = torch.zeros(self.E, dtype=torch.int32, device=dev)
+        crow = torch.zeros(self.E, K, 8, dtype=f64, device=dev) if rows else None
+        _lib.check(_lib.lib().mopa_env_set_contact_force(self._h, _ptr(force), _ptr(total), _ptr(crow) if rows and K > 0 else None, _ptr(count), K))
+        self.contact_force, self.contact_force_total, self.contact_count, self.contact_rows = force, total, count, crow
+        return self
+
+    def disable_contact_force(self):
+        """turn the readout off (the buffers are released)"""
+        if self.contact_force is not None:
+            _lib.check(_lib.lib().mopa_env_set_contact_force(self._h, None, None, None, None, 0))
+        self.contact_force = self.contact_force_total = self.contact_count = self.contact_rows = None
+
+    def _zero_contact_force(self, mask):
+        if self.contact_force is None:
+            return
+        torch = _torch()
+        for t in (self.contact_force, self.contact_force_total, self.contact_count):
+            if mask is None:
+                t.zero_()
+            else:
+                t.copy_(torch.where(mask.to(torch.bool), torch.zeros_like(t), t))
 
     # ------------------------------------------------------------------
     def close(self):
@@ -574,6 +638,7 @@ class BatchKinematicEnv:
             self.has_prev.copy_(torch.where(mk, torch.zeros_like(self.has_prev), self.has_prev))
             self.ep_len.copy_(torch.where(mk, torch.zeros_like(self.ep_len), self.ep_len))
         self._rest(mask, noise=True)
+        self._zero_contact_force(mask)
         self._launch(None, False, None)
         return self.obs
 
@@ -641,6 +706,7 @@ class BatchKinematicEnv:
         self.has_prev.zero_()
         self.ep_len.zero_()
         self._rest(None)
+        self._zero_contact_force(None)
         self._launch(None, False, None)
         return self.obs
 

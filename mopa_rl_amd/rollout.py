@@ -493,6 +493,14 @@ class BatchMoPARollout:
         self._pend_ac = torch.zeros(self.E, self.ac_dim, dtype=f64, device=dev)
         self._ac_type_in = torch.zeros(self.E, dtype=torch.int64, device=dev)      # discrete_action: this call's ac_type / that of a pending step
         self._pend_type = torch.zeros(self.E, dtype=torch.int64, device=dev)
+        # contact force (`env.get_contact_force()` after every env.step, rl/mopa_rollouts.py:538-539, :636-637): on the envs whose contacts run
+        # behind a constraint solver (K7 / K8) the env accumulates it per launch on the device; `_cf_mark` = the accumulator when an
+        # env's agent step began, so a step's force is total - mark however its env.steps were spread over launches and calls
+        self._cf_mark = None
+        if getattr(env, "has_contact_solver", None) is not None and env.has_contact_solver():
+            if env.contact_force is None:
+                env.enable_contact_force()
+            self._cf_mark = env.contact_force_total.clone()
 
     # ------------------------------------------------------------------
     def close(self):
@@ -919,6 +927,8 @@ class BatchMoPARollout:
         Returns a dict of GPU tensors: ob [E,obs_dim] (before), ac (the action each transition belongs to), ob_next
         [E,obs_dim], rew [E] (SMDP return of the step), done [E] uint8, intra_steps [E] int64, is_planner [E] bool, success [E]
         (env success flag), `path_len`, `plan_ok`, and `stepped` [E] bool: the envs that completed an agent step in this call.
+        On an env with contacts behind a constraint solver (K7 / K8) also `contact_force` [E]: `env.get_contact_force()` summed over
+        every env.step of the agent step (all waypoints of a planner path, rl/mopa_rollouts.py:538-539) -- parity unpinned.
         record=True adds `record`: per executed waypoint k the obs after it, the running SMDP return, the done flag and
         the waypoint itself ([E, L, ...]; `n_exec` [E] = waypoints actually executed) -- the `ob_list / meta_rew_list /
         done_list / traj` of the reference, input of `reuse_transitions`.
@@ -935,6 +945,8 @@ class BatchMoPARollout:
             self._ac_type_in.copy_(ac_type.reshape(-1))
         if self.cfg.use_graphs and not record and getattr(self, "timing", None) is None:
             return self._agent_step_graphs(ac)
+        if self._cf_mark is not None:      # envs that begin an agent step in this call (a reset since the last one has zeroed their total)
+            self._cf_mark.copy_(_torch().where(self.busy, self._cf_mark, self.env.contact_force_total))
         bag = self._seg_pre(ac)
         self._seg_plan(bag)
         res = self._seg_exec(bag, record)
@@ -1324,7 +1336,7 @@ class BatchMoPARollout:
             res["ac_type"] = bag["ac_type"]
         if rec is not None:
             res["record"] = rec
-        return res
+        return self._cf_out(res)
 
     # ---- the same two parts with the elementwise work in the library's bookkeeping kernels (cfg.fused) ----
     def _fused_struct(self):
@@ -1507,6 +1519,16 @@ class BatchMoPARollout:
             res["ac_type"] = bag["ac_type"]
         if rec is not None:
             res["record"] = rec
+        return self._cf_out(res)
+
+    def _cf_out(self, res):
+        """`contact_force` of the envs that completed their agent step: the env's accumulator minus its value when the step began"""
+        if self._cf_mark is None:
+            return res
+        torch = _torch()
+        tot, st = self.env.contact_force_total, res["stepped"].bool()
+        res["contact_force"] = torch.where(st, tot - self._cf_mark, torch.zeros_like(tot))
+        self._cf_mark.copy_(torch.where(st, tot, self._cf_mark))
         return res
 
     def _disc_pow(self, L):
@@ -1619,7 +1641,10 @@ class BatchMoPARollout:
                    (env e took an agent step in call t), n_steps [E], qpos_final [E, nq] (the state each episode ended in) -- the reference's
                    evaluation rollout holds ob / ac of planner steps only (:577-585 against :648-653), this one of every step;
           ep_info  len, rew (:663-670), success (the env's `episode_success`), and the six counters (:671), one entry per env.
-        `contact_force` (:538, MuJoCo's contact solver forces) has no kinematic counterpart and is not reported.  `max_step` below the
+        On an env with contacts behind a constraint solver (K7 / K8) ep_info also holds `contact_force` (:538-539, :636-637: the sum of
+        `env.get_contact_force()` over every env.step of the episode) and `avg_conntact_force` (the reference's key, :669-675: that sum
+        / len) -- from the restated solver, PARITY UNPINNED against MuJoCo; a kinematic env has no contact forces and reports neither
+        key.  `max_step` below the
         env's own episode cap would cut a path between two waypoints (:575): build the env with that cap instead."""
         torch = _torch()
         env, cfg, E = self.env, self.cfg, self.E
@@ -1638,6 +1663,7 @@ class BatchMoPARollout:
             ep_rew = torch.zeros(E, dtype=torch.float64, device=dev)
             cnt = {k: torch.zeros(E, dtype=torch.int64, device=dev) for k in COUNTERS}
             success = torch.zeros(E, dtype=torch.bool, device=dev)
+            ep_cf = torch.zeros(E, dtype=torch.float64, device=dev) if self._cf_mark is not None else None
             obs, acs, rews, dones, valids = [], [], [], [], []
             last_ob, last_q = env.obs.clone(), env.qpos.clone()
             while True:
@@ -1650,6 +1676,8 @@ class BatchMoPARollout:
                 out = self.agent_step(ac, ac_type=ac_type)
                 ep_len += torch.where(alive, out["intra_steps"] + 1, torch.zeros_like(ep_len))
                 ep_rew += torch.where(alive, out["rew"], torch.zeros_like(ep_rew))
+                if ep_cf is not None:
+                    ep_cf += torch.where(alive, out["contact_force"], torch.zeros_like(ep_cf))
                 for k in COUNTERS:
                     cnt[k] += torch.where(alive, self.counters[k] - before[k], torch.zeros_like(cnt[k]))
                 success |= alive & out["success"].bool()
@@ -1672,4 +1700,7 @@ class BatchMoPARollout:
         rollout = {"ob": ob_t, "ac": torch.stack(acs), "rew": torch.stack(rews), "done": torch.stack(dones), "valid": valid,
                    "n_steps": valid.sum(0), "qpos_final": last_q}
         ep_info = {"len": ep_len, "rew": ep_rew, "success": success, **cnt}
+        if ep_cf is not None:
+            ep_info["contact_force"] = ep_cf
+            ep_info["avg_conntact_force"] = ep_cf / ep_len.to(torch.float64)
         return rollout, ep_info
