@@ -249,7 +249,7 @@ extern "C" int mopa_pullback_batch(MopaScene *S, const double *cur, double *targ
     // few envs: the wave-per-env walk (no read-back); MOPA_PULLBACK=wave|batch pins the form for A/B runs and tests
     const char *force = getenv("MOPA_PULLBACK");
     const bool batch = force ? std::strcmp(force, "batch") == 0 : E >= 256;
-    if (!batch || !S->use_v2 || S->nq > 64) return pullback_wave_per_env(S, cur, target, E, step_size, num_trials, n_trials, valid, stream);
+    if (!batch || !S->k1.use_v2 || S->nq > 64) return pullback_wave_per_env(S, cur, target, E, step_size, num_trials, n_trials, valid, stream);
     StreamScratch &sc = scratch_for(S, st);
     const int nq = S->nq, na = S->na;
     // 1. verdicts of the targets as they come
@@ -271,7 +271,7 @@ extern "C" int mopa_pullback_batch(MopaScene *S, const double *cur, double *targ
     if (num_trials == 0) return MOPA_OK;
     int64_t n_inv_max = E;
     const size_t row_bytes = (size_t)num_trials * (nq + na) * sizeof(double) + num_trials;
-    if ((size_t)E * row_bytes > ((size_t)1 << 30) || !S->use_v5) {
+    if ((size_t)E * row_bytes > ((size_t)1 << 30) || !S->k1.use_v5) {
         unsigned int n_inv = 0;
         HIP_TRY(hipMemcpyAsync(&n_inv, ctr, 4, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
@@ -291,7 +291,7 @@ extern "C" int mopa_pullback_batch(MopaScene *S, const double *cur, double *targ
     unsigned char *cand_valid = reinterpret_cast<unsigned char *>(qa + (size_t)n_rows * na);
     hipLaunchKernelGGL(k_pb_active, dim3((unsigned)((n_rows * na + 255) / 256)), dim3(256), 0, st, S->hdr, S->d_int, cand, (long long)n_rows, qa,
                        (const long long *)n_rows_dev, (unsigned int *)nullptr);
-    rc = launch_is_valid(S, qa, cand, n_rows, 1, nullptr, cand_valid, nullptr, stream, S->use_v5 ? n_rows_dev : nullptr);
+    rc = launch_is_valid(S, qa, cand, n_rows, 1, nullptr, cand_valid, nullptr, stream, S->k1.use_v5 ? n_rows_dev : nullptr);
     if (rc != MOPA_OK) return rc;
     hipLaunchKernelGGL(k_pb_pick, dim3((unsigned)((n_inv_max + kWavesPerBlock - 1) / kWavesPerBlock)), dim3(kBlock), 0, st, nq, target, num_trials, ctr, slot_env, cand, cand_valid,
                        n_trials, valid);

@@ -998,3 +998,45 @@ def test_planner_builds_agree(env, oracle_mod, monkeypatch):
     for e in (0, 3, 7, 19, 33):
         ost, opath, ochk, _ = orc.plan(starts[e], goals[e], pi.spec.range, 0.005, max_iters=700, max_nodes=1024, seed=23, env_id=e, max_path=256)
         assert ost == ref[2][e] and ochk == ref[3][e], e
+
+
+_BOUNDARY_SEED = 29      # "near" sample whose first 63 states hold both classes on Push and on Lift (asserted below)
+
+
+@pytest.mark.parametrize("env", ["SawyerPushObstacle-v0", "SawyerLiftObstacle-v0"])    # no mesh pairs + baked / mesh gate, row list, fallback pass
+def test_batches_at_the_kernel_choice_thresholds(env, oracle_mod):
+    """Batches right at the sizes where the launch plan changes kernels (k1_plan): the wave-per-state kernel below
+    T = max(64, 36 CUs) states and the lane-per-state kernel from T on (from 64 on for a scene pinned with MOPA_VALID_KERNEL=v5), one
+    tile / two tiles around 64, and motion validation around its own 16-per-CU threshold.  Prefixes of ONE sample, so one oracle
+    run serves them all: verdicts and depths equal the oracle's bit for bit on either side of every threshold, with and without
+    depths, and valid_kernel() names the kernel the plan picks."""
+    import torch
+    from mopa_rl_amd.batch import BatchPlanner
+    n_cu = torch.cuda.get_device_properties(0).multi_processor_count
+    T = max(64, 36 * n_cu)
+    pi, sc, orc = _mk(env, oracle_mod)
+    _, sc5, _ = _mk(env, oracle_mod, "v5")
+    qa, row = sample_states(pi, T + 1, _BOUNDARY_SEED, "near")
+    ov, omd = orc.is_valid_batch(qa, row, samples_per_env=len(qa), nthreads=0)
+    sizes = [1, 63, 64, 65, T - 1, T, T + 1]
+    for n in sizes:
+        if n >= 63:
+            assert 0 < ov[:n].sum() < n, f"prefix {n} holds one class only"
+    tq, tr = torch.from_numpy(qa).cuda(), torch.from_numpy(row).cuda()
+    for scene, thr in ((sc, T), (sc5, 64)):
+        bp = BatchPlanner(scene)
+        for n in sizes:
+            assert scene.valid_kernel(n) == ("k_is_valid" if n < thr else "k_is_valid_v5"), (thr, n)
+            q = tq[:n].contiguous()
+            v, md = bp.is_valid(q, tr, samples_per_env=n, want_min_dist=True)
+            v2 = bp.is_valid(q, tr, samples_per_env=n)
+            torch.cuda.synchronize()
+            assert np.array_equal(v.cpu().numpy(), ov[:n]), (thr, n, "kernel with depths")
+            assert np.array_equal(v2.cpu().numpy(), ov[:n]), (thr, n, "verdict-only kernel")
+            assert np.array_equal(_bits(md.cpu().numpy()), _bits(omd[:n])), (thr, n)
+        # zero-length segments: the verdict of a motion is the verdict of its state
+        for n in (16 * n_cu - 1, 16 * n_cu, 16 * n_cu + 1):
+            q = tq[:n].contiguous()
+            mv = bp.check_motion(q, q, tr, samples_per_env=n)
+            torch.cuda.synchronize()
+            assert np.array_equal(mv.cpu().numpy(), ov[:n]), (thr, n, "motion")

@@ -193,7 +193,7 @@ def bake(env: str, name: str) -> str:
 
 def generate() -> str:
     parts = ["// mopa_valid_v5_baked.inc -- GENERATED by tools/bake_k1_scenes.py: do not edit.  Inputs: the scene files named below,",
-             "// the host half of mopa_scene_create (mopa_hip.hip) that builds the tables.  Included by mopa_valid_v5.inc.",
+             "// the scene compiler (mopa_scene_build.inc) that builds the tables.  Included by mopa_valid_v5.inc.",
              "// Regenerate after changing either; tests/test_k1_baked_host.py checks that this file is current.",
              ""]
     for env, name in SCENES:
