@@ -211,6 +211,27 @@ int mopa_plan_batch(MopaScene *scene, const double *start_dev /*[E,nq]*/, const 
                     const MopaPlanParams *params, double *path_dev /*[E,max_path,nq]*/, int32_t *path_len_dev /*[E]*/,
                     int32_t *status_dev /*[E]*/, int64_t *n_checks_dev /*[E] or NULL*/, void *stream);
 
+/* K9: the two vertex-removing passes of OMPL's PathSimplifier (reduceVertices, collapseCloseVertices) over the rows
+ * mopa_plan_batch wrote, in place, one wave per path, asynchronous on `stream` with no read-back.  Every surviving row is one of
+ * the input rows (both endpoints are kept); the survivors are compacted to the front in order and path_len[e] is rewritten; rows
+ * at and beyond the new length are unspecified.  The routines, their integer draws and the schedule are defined in DESIGN.md
+ * ("K9 path simplification"); shortcutPath, the B-spline smoothing and checkAndRepair are NOT built.
+ *   motion checks: mopa_check_motion_batch's rule between the rows' active entries, with the passive entries of row 0.
+ *   draws:         the k-th draw of path e is the uniform of counter 2^63 + k of the stream (seed, id) that query e of
+ *                  mopa_plan_batch samples from -- seed, env_id_base, env_ids_dev and seeds_dev as in MopaPlanParams.
+ *   passes:        bit 0 = reduceVertices, bit 1 = collapseCloseVertices (a routine that is masked out returns false).
+ *   skipped:       paths with status[e] != 0 (status_dev may be NULL: none) or path_len[e] < 3 (the unwritten rows of a
+ *                  continuation launch among them) -- not one of their bytes is touched, info_dev's included.
+ *   info_dev:      nullable, [E,2]: motion checks made, draws consumed.
+ * Argument errors return before any launch: NULL scene / buffers, E < 0, max_path < 2, passes outside 1..3
+ * (MOPA_ERR_INVALID_ARG); max_path beyond mopa_simplify_paths_max_path(scene), what the per-wave LDS lists hold -- at least 512
+ * for the scenes of this project -- (MOPA_ERR_UNSUPPORTED). */
+int mopa_simplify_paths_batch(MopaScene *scene, int64_t E, int32_t max_path, double *path_dev /*[E,max_path,nq] in/out*/,
+                              int32_t *path_len_dev /*[E] in/out*/, const int32_t *status_dev /*[E] nullable*/, uint64_t seed,
+                              uint64_t env_id_base, const uint64_t *env_ids_dev /*nullable*/, const uint64_t *seeds_dev /*nullable*/,
+                              int32_t passes, int64_t *info_dev /*[E,2] nullable*/, void *stream);
+int mopa_simplify_paths_max_path(const MopaScene *scene);
+
 /* The rollout's invalid-target back-off (rl/mopa_rollouts.py:133-143) for E envs, asynchronous (no read-back unless E * num_trials
  * rows would exceed 1 GiB of scratch; E < 256: one wave per env walks its trials, otherwise all candidate rows of all
  * invalid targets go through one validity launch -- same results): while target[e] (a full

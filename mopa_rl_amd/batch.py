@@ -213,7 +213,8 @@ class BatchPlanner:
 
     def plan(self, start, goal, max_iters: int = 2000, max_nodes: int = 1024, max_path: int = 256, seed: int = 0,
              env_id_base: int = 0, stream=None, env_ids=None, seeds=None, max_workgroups: int = 0, exclusive: bool = False,
-             keep_state: bool = False, resume=None) -> Tuple["object", "object", "object", "object"]:
+             keep_state: bool = False, resume=None, vertex_simplify: bool = False,
+             simplify_passes: int = 3) -> Tuple["object", "object", "object", "object"]:
         """E independent RRT-Connect queries.  Returns (path[E,max_path,nq], path_len[E], status[E], n_checks[E]).
         env_ids (int64 [E] GPU tensor, optional): the sample-stream id of every query (default env_id_base + index).
         seeds (int64 [E] GPU tensor, optional): a seed per query instead of `seed`.
@@ -223,7 +224,11 @@ class BatchPlanner:
         keep_state: the launch keeps its trees in tensors of its own and returns a fifth element, a `PlanState` (tree_q, tree_p,
         state, max_nodes), from which a later launch with a larger `max_iters` continues the unsolved queries: `resume=` a
         PlanState whose rows are in this launch's query order (`PlanState.rows(idx)` gathers; same max_nodes, same seeds / ids).
-        The continued run gives what one launch with the larger budget gives, without retracing the first iterations."""
+        The continued run gives what one launch with the larger budget gives, without retracing the first iterations.
+        vertex_simplify: the launch of `simplify_paths` (K9: OMPL's two vertex-removing passes, `simplify_passes` selects them) goes
+        directly behind the planner's on the same stream with the same seed / ids / seeds, so the rows and `path_len` that come
+        back are the simplified ones; `n_checks` stays the planner's own count.  A continuation leaves `path_len` 0 for the
+        queries an earlier launch settled, so every query's final rows are simplified exactly once."""
         torch = _torch()
         _check_f64(start, "start", self.nq)
         _check_f64(goal, "goal", self.nq)
@@ -257,11 +262,46 @@ class BatchPlanner:
         if resume is not None and stream is not None:
             for t in (resume.tree_q, resume.tree_p, resume.state):
                 t.record_stream(stream)
+        if vertex_simplify:
+            self.simplify_paths(path, plen, status, seed=seed, env_id_base=env_id_base, env_ids=env_ids, seeds=seeds,
+                                passes=simplify_passes, stream=stream)
         return (path, plen, status, nchk, ps) if keep_state else (path, plen, status, nchk)
+
+    def simplify_paths(self, path, plen, status=None, seed: int = 0, env_id_base: int = 0, env_ids=None, seeds=None, passes: int = 3,
+                       stream=None, want_info: bool = False):
+        """K9, in place: OMPL's reduceVertices (passes bit 0) and collapseCloseVertices (bit 1) over the planner's rows -- `path`
+        [E, max_path, nq] float64, `plen` [E] int32, `status` [E] int32 or None -- one wave per path, asynchronous, no read-back.
+        Every surviving row is one of the input rows; they are compacted to the front and `plen` is rewritten (rows behind it are
+        unspecified).  Paths with a non-zero status or fewer than 3 rows are not touched.  seed / env_id_base / env_ids / seeds: what
+        `plan` was given (the draws come from the planner's sample stream of the query, at counters from 2^63 on).  shortcutPath,
+        B-spline smoothing and checkAndRepair of OMPL's simplify() are not built.  Returns None, or with `want_info` an int64
+        [E, 2] tensor: motion checks made, draws consumed (0 for untouched paths)."""
+        torch = _torch()
+        if path.dtype != torch.float64 or not path.is_cuda or not path.is_contiguous() or path.dim() != 3 or path.shape[2] != self.nq:
+            raise _lib.MopaError(f"path must be a contiguous float64 GPU tensor of shape [E, max_path, {self.nq}]")
+        E, max_path = int(path.shape[0]), int(path.shape[1])
+        for t, name in ((plen, "plen"), (status, "status")):
+            if t is not None and (t.dtype != torch.int32 or not t.is_cuda or not t.is_contiguous() or tuple(t.shape) != (E,)):
+                raise _lib.MopaError(f"{name} must be a contiguous int32 GPU tensor of shape [E]")
+        for t, name in ((env_ids, "env_ids"), (seeds, "seeds")):
+            if t is not None and (t.dtype != torch.int64 or not t.is_cuda or not t.is_contiguous() or tuple(t.shape) != (E,)):
+                raise _lib.MopaError(f"{name} must be a contiguous int64 GPU tensor of shape [E]")
+        info = None
+        if want_info:
+            if stream is not None:
+                with torch.cuda.stream(stream):
+                    info = torch.zeros(E, 2, dtype=torch.int64, device=path.device)
+            else:
+                info = torch.zeros(E, 2, dtype=torch.int64, device=path.device)
+        _lib.check(_lib.lib().mopa_simplify_paths_batch(
+            self.scene.handle, E, max_path, _ptr(path), _ptr(plen), _ptr(status) if status is not None else None,
+            int(seed) & 0xFFFFFFFFFFFFFFFF, int(env_id_base), _ptr(env_ids) if env_ids is not None else None,
+            _ptr(seeds) if seeds is not None else None, int(passes), _ptr(info) if info is not None else None, _stream_handle(stream)))
+        return info
 
     def plan_laddered(self, batches, max_iters: int = 2000, first_iters: int = 100, max_nodes: int = 1024, max_path: int = 256,
                       retry_streams=None, first_stream=None, max_workgroups_first: int = -1, retry_min: int = 1024, resume: bool = True,
-                      retry_exclusive: bool = False):
+                      retry_exclusive: bool = False, vertex_simplify: bool = False, simplify_passes: int = 3):
         """A stream of query batches through RRT-Connect with an iteration ladder.  `batches`: list of dicts with `start`,
         `goal` ([E, nq] tensors), `seed` and optionally `env_ids` / `seeds` as for `plan`.  Every batch first runs with
         `first_iters`; the queries that come back "no exact solution" (a few %: the ones that would have kept the whole
@@ -272,11 +312,13 @@ class BatchPlanner:
         are those of `plan(..., max_iters=max_iters)`, bit for bit.  Returns the list of those tuples (after all launches
         have finished).  One host read-back per batch (which queries go again).  The defaults of `first_iters` / `retry_min` are
         the ones that measured best over long streams of 4096-query batches on Push (tools/ladder_grid.py: 100 / 1024; they only
-        schedule the work)."""
+        schedule the work).  vertex_simplify / simplify_passes: as for `plan`, passed to every launch -- a query is solved by
+        exactly one of them, which simplifies its rows."""
+        vs = dict(vertex_simplify=vertex_simplify, simplify_passes=simplify_passes)
         torch = _torch()
         if first_iters <= 0 or first_iters >= max_iters:
             return [self.plan(b["start"], b["goal"], max_iters=max_iters, max_nodes=max_nodes, max_path=max_path, seed=b.get("seed", 0),
-                              env_ids=b.get("env_ids"), seeds=b.get("seeds")) for b in batches]
+                              env_ids=b.get("env_ids"), seeds=b.get("seeds"), **vs) for b in batches]
         dev = batches[0]["start"].device
         main = torch.cuda.current_stream(dev)
         sa = first_stream if first_stream is not None else torch.cuda.Stream(device=dev)
@@ -296,7 +338,7 @@ class BatchPlanner:
                 cat = lambda k: torch.cat([w[k] for w in wait]).contiguous()
                 r2 = self.plan(cat("start"), cat("goal"), max_iters=max_iters, max_nodes=max_nodes, max_path=max_path, seed=0,
                                env_ids=cat("ids"), seeds=cat("seeds"), stream=sb, max_workgroups=0 if retry_exclusive else -1,
-                               exclusive=retry_exclusive, resume=PlanState.cat([w["state"] for w in wait]) if resume else None)
+                               exclusive=retry_exclusive, resume=PlanState.cat([w["state"] for w in wait]) if resume else None, **vs)
             # the pooled slices were allocated on `sa` and are read by the cat on `sb`: tell the caching allocator, or the
             # next first launch on `sa` may be handed their blocks while `sb` still waits behind an earlier retry
             for w in wait:
@@ -315,7 +357,7 @@ class BatchPlanner:
                 ids = torch.arange(E, device=dev, dtype=torch.int64)
             with torch.cuda.stream(sa):
                 res = self.plan(b["start"], b["goal"], max_iters=first_iters, max_nodes=max_nodes, max_path=max_path, seed=b.get("seed", 0),
-                                env_ids=ids, seeds=b.get("seeds"), stream=sa, max_workgroups=max_workgroups_first, keep_state=resume)
+                                env_ids=ids, seeds=b.get("seeds"), stream=sa, max_workgroups=max_workgroups_first, keep_state=resume, **vs)
                 kept = res[4] if resume else None
                 res = res[:4]
                 again = torch.nonzero(res[2] == _lib.PLAN_NO_EXACT).flatten()       # (waits for this launch: the one read-back)

@@ -16,7 +16,12 @@ Differences that cannot be hidden (DESIGN.md "Semantics"):
   * ``opt``, ``num_actions``, ``goal_bias``, ``simplified_duration`` are
     accepted and ignored exactly as the reference ignores them
     (KinematicPlanner.cpp:42-61); ``is_simplified=True`` is rejected
-    (PathSimplifier is randomised and time-bounded);
+    (PathSimplifier is randomised and time-bounded).  The part of it that can
+    be stated exactly -- the two vertex-removing passes reduceVertices and
+    collapseCloseVertices (K9) -- runs behind the attribute
+    ``vertex_simplify`` (default False; not a constructor argument, the
+    reference's 14 stay as they are); shortcutPath, the B-spline smoothing
+    and checkAndRepair are not built;
   * ``glue_bodies`` must be empty (the reference never passes any).
 """
 from __future__ import annotations
@@ -60,7 +65,11 @@ class PyKinematicPlanner:
         if self.algo != "rrt_connect":
             raise NotImplementedError(f"algo={self.algo!r}: only 'rrt_connect' is implemented")
         if self.isSimplified:
-            raise NotImplementedError("is_simplified=True (OMPL PathSimplifier) is not implemented")
+            raise NotImplementedError("is_simplified=True (OMPL PathSimplifier) is not implemented; its two vertex-removing passes "
+                                      "(reduceVertices, collapseCloseVertices) are: set the attribute vertex_simplify = True")
+        #: K9: plan() runs reduceVertices + collapseCloseVertices over the solved path (`vertex_simplify_passes`: 1 / 2 / 3)
+        self.vertex_simplify = False
+        self.vertex_simplify_passes = 3
         self._model = load_scene(self.xml_filename)
         self._scene = _lib.Scene(self._model, self.passive_joint_idx, self.ignored_contacts, self.contact_threshold,
                                  range_=self._range, resolution=0.005, seed=self.seed)
@@ -77,6 +86,8 @@ class PyKinematicPlanner:
         # every plan() call of one planner object draws a fresh sample stream
         status, path, _ = self._scene.plan(start, goal, max_iters=max_iters, max_nodes=MAX_NODES, max_path=MAX_PATH,
                                            seed=self.seed, env_id=self._plan_count)
+        if self.vertex_simplify and status == _lib.PLAN_OK and len(path) >= 3:
+            path = self._simplify(path, self._plan_count)
         self._plan_count += 1
         nq = self._scene.nq
         if status == _lib.PLAN_INVALID_GOAL:
@@ -84,6 +95,18 @@ class PyKinematicPlanner:
         if status != _lib.PLAN_OK:
             return [[-4.0] * nq]
         return path.tolist()
+
+    def _simplify(self, path: np.ndarray, stream_id: int) -> np.ndarray:
+        """K9 over one solved path: the draws come from the sample stream (seed, stream_id) the plan itself used"""
+        import torch
+        from .batch import BatchPlanner
+        ordinal = self._scene._ctor[7]          # the scene's device (-1: the current one, where it was created)
+        dev = torch.device("cuda", ordinal if ordinal >= 0 else torch.cuda.current_device())
+        rows = torch.from_numpy(np.ascontiguousarray(path[None])).to(dev)
+        plen = torch.tensor([len(path)], dtype=torch.int32, device=dev)
+        BatchPlanner(self._scene).simplify_paths(rows, plen, None, seed=self.seed, env_id_base=stream_id,
+                                                 passes=self.vertex_simplify_passes)
+        return rows[0, :int(plen[0])].cpu().numpy()
 
     def getPlannerStatus(self) -> bytes:
         return self._scene.planner_status()

@@ -19,14 +19,16 @@ def action_size(ac_space) -> int:
 
 class PlannerAgent:
     def __init__(self, config, ac_space, non_limited_idx=None, passive_joint_idx=[], ignored_contacts=[],
-                 planner_type=None, goal_bias=0.05, is_simplified=False, simplified_duration=0.1, range_=None):
+                 planner_type=None, goal_bias=0.05, is_simplified=False, simplified_duration=0.1, range_=None,
+                 vertex_simplify=False):
         self._config = config
         self._is_simplified, self._simplified_duration = is_simplified, simplified_duration
         self.planner = SamplingBasedPlanner(config, config._xml_path, action_size(ac_space), non_limited_idx,
                                             planner_type=planner_type, passive_joint_idx=passive_joint_idx,
                                             ignored_contacts=ignored_contacts, contact_threshold=config.contact_threshold,
                                             goal_bias=goal_bias, is_simplified=is_simplified,
-                                            simplified_duration=simplified_duration, range_=range_)
+                                            simplified_duration=simplified_duration, range_=range_,
+                                            vertex_simplify=vertex_simplify)
 
     def isValidState(self, state):
         return self.planner.isValidState(state)

@@ -69,6 +69,11 @@ class RolloutConfig:
     max_nodes: int = 1024
     max_path: int = 256
     seed: int = 1234
+    # K9: OMPL's two vertex-removing simplifier passes (reduceVertices, collapseCloseVertices) directly behind every launch of the
+    # main / the simple planner (`BatchPlanner.plan(vertex_simplify=True)`); un-wrap and densification then work on the shorter
+    # rows.  Not the reference's is_simplified (shortcutPath, B-spline smoothing and checkAndRepair are not built).
+    vertex_simplify: bool = False
+    simple_planner_vertex_simplify: bool = False
     # data-parallel runs (sample streams keyed by (seed, GLOBAL env id, iteration), so results do not depend on how
     # the envs are sharded): this rank's envs are rows env_id_base .. env_id_base + E - 1 of env_id_total envs in all
     # (rank * E and world * E; 0 total = this rank alone)
@@ -570,13 +575,14 @@ class BatchMoPARollout:
             cur_f, target_f = self._wrap_q(cur_f).contiguous(), self._wrap_q(target_f).contiguous()
         if stream is None:
             job["path"], job["plen"], job["status"], _ = self.bp.plan(cur_f, target_f, max_iters=iters, max_nodes=cfg.max_nodes,
-                                                                      max_path=cfg.max_path, seed=cfg.seed, env_ids=gids, seeds=seeds)
+                                                                      max_path=cfg.max_path, seed=cfg.seed, env_ids=gids, seeds=seeds,
+                                                                      vertex_simplify=cfg.vertex_simplify)
         else:
             stream.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(stream):
                 res = self.bp.plan(cur_f, target_f, max_iters=iters, max_nodes=cfg.max_nodes, max_path=cfg.max_path, seed=cfg.seed,
                                    env_ids=gids, seeds=seeds, stream=stream, max_workgroups=cfg.planner_workgroups,
-                                   keep_state=keep, resume=resume,
+                                   keep_state=keep, resume=resume, vertex_simplify=cfg.vertex_simplify,
                                    exclusive=cfg.planner_exclusive >= 2 or (cfg.planner_exclusive == 1 and (resume is not None or not keep) and iters == self.main_iters))
                 job["path"], job["plen"], job["status"] = res[0], res[1], res[2]
                 if keep:
@@ -588,7 +594,7 @@ class BatchMoPARollout:
                     rb = self.bp.plan(cur_f, target_f, max_iters=self.main_iters, max_nodes=cfg.max_nodes, max_path=cfg.max_path,
                                       seed=cfg.seed, env_ids=gids, seeds=seeds, stream=stream,
                                       max_workgroups=cfg.planner_chain_workgroups or cfg.planner_workgroups,
-                                      resume=res[4], exclusive=cfg.planner_exclusive >= 1)
+                                      resume=res[4], exclusive=cfg.planner_exclusive >= 1, vertex_simplify=cfg.vertex_simplify)
                     ev_b = torch.cuda.Event()
                     ev_b.record(stream)
                     job["chain"] = {"path": rb[0], "plen": rb[1], "status": rb[2], "event": ev_b}
@@ -801,15 +807,18 @@ class BatchMoPARollout:
         seeds = torch.tensor(cfg.seed + job["steps_h"][rows], dtype=torch.int64, device=dev)
         stream = job["stream"]
         job["stage"] = stage
+        simplify = cfg.simple_planner_vertex_simplify if stage == "simple" else cfg.vertex_simplify
         if stream is None:
             job["path"], job["plen"], job["status"], _ = scene_bp.plan(starts, ends, max_iters=iters, max_nodes=cfg.max_nodes,
-                                                                       max_path=cfg.max_path, seed=cfg.seed, env_ids=ids, seeds=seeds)
+                                                                       max_path=cfg.max_path, seed=cfg.seed, env_ids=ids, seeds=seeds,
+                                                                       vertex_simplify=simplify)
         else:
             stream.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(stream):
                 job["path"], job["plen"], job["status"], _ = scene_bp.plan(starts, ends, max_iters=iters, max_nodes=cfg.max_nodes,
                                                                            max_path=cfg.max_path, seed=cfg.seed, env_ids=ids, seeds=seeds,
-                                                                           stream=stream, max_workgroups=cfg.planner_workgroups)
+                                                                           stream=stream, max_workgroups=cfg.planner_workgroups,
+                                                                           vertex_simplify=simplify)
                 job["keep"] = (starts, ends, ids, seeds)
                 job["event"] = torch.cuda.Event()
                 job["event"].record(stream)

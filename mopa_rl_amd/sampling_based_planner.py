@@ -29,7 +29,7 @@ def joint_convert(angle):
 class SamplingBasedPlanner:
     def __init__(self, config, xml_path, num_actions, non_limited_idx, planner_type=None, passive_joint_idx=[],
                  glue_bodies=[], ignored_contacts=[], contact_threshold=0.0, goal_bias=0.05, is_simplified=False,
-                 simplified_duration=0.1, range_=None):
+                 simplified_duration=0.1, range_=None, vertex_simplify=False):
         self.config = config
         self.non_limited_idx = non_limited_idx
         algo = config.planner_type if planner_type is None else planner_type
@@ -38,6 +38,9 @@ class SamplingBasedPlanner:
         self.planner = PyKinematicPlanner(enc(xml_path), enc(algo), num_actions, enc(config.planner_objective), config.threshold,
                                           step, passive_joint_idx, glue_bodies, ignored_contacts, contact_threshold, goal_bias,
                                           is_simplified, simplified_duration, config.seed)
+        # K9 (not in the reference's argument list): the planner's rows lose the vertices reduceVertices / collapseCloseVertices
+        # remove before they are un-wrapped below; `is_simplified` is passed through unchanged and still raises when set
+        self.planner.vertex_simplify = bool(vertex_simplify)
 
     # ------------------------------------------------------------------
     def convert_nonlimited(self, state):
