@@ -215,7 +215,8 @@ int mopa_plan_batch(MopaScene *scene, const double *start_dev /*[E,nq]*/, const 
  * mopa_plan_batch wrote, in place, one wave per path, asynchronous on `stream` with no read-back.  Every surviving row is one of
  * the input rows (both endpoints are kept); the survivors are compacted to the front in order and path_len[e] is rewritten; rows
  * at and beyond the new length are unspecified.  The routines, their integer draws and the schedule are defined in DESIGN.md
- * ("K9 path simplification"); shortcutPath, the B-spline smoothing and checkAndRepair are NOT built.
+ * ("K9 path simplification"); shortcutPath is mopa_shortcut_paths_batch below, the B-spline smoothing and checkAndRepair are NOT
+ * built.
  *   motion checks: mopa_check_motion_batch's rule between the rows' active entries, with the passive entries of row 0.
  *   draws:         the k-th draw of path e is the uniform of counter 2^63 + k of the stream (seed, id) that query e of
  *                  mopa_plan_batch samples from -- seed, env_id_base, env_ids_dev and seeds_dev as in MopaPlanParams.
@@ -231,6 +232,29 @@ int mopa_simplify_paths_batch(MopaScene *scene, int64_t E, int32_t max_path, dou
                               uint64_t env_id_base, const uint64_t *env_ids_dev /*nullable*/, const uint64_t *seeds_dev /*nullable*/,
                               int32_t passes, int64_t *info_dev /*[E,2] nullable*/, void *stream);
 int mopa_simplify_paths_max_path(const MopaScene *scene);
+
+/* K9 with shortcutPath: OMPL's PathSimplifier::shortcutPath (passes bit 2) in front of the two vertex-removing passes (bits 0 and
+ * 1, as above), in place, one wave per path, asynchronous on `stream` with no read-back.  shortcutPath connects points in the
+ * interior of segments, so the result holds rows that are no input rows: a new row has the interpolated active entries and row
+ * 0's passive entries.  Both endpoints are kept; the rows are put in order at the front and path_len[e] is rewritten (it can
+ * grow, never beyond max_path); rows at and beyond the new length are unspecified.  The routine, every floating-point operation
+ * of it, its two deviations from OMPL (a splice is accepted only if the stubs between a new interior point and its old
+ * neighbours pass the motion check too; a splice that would need row max_path + 1 is skipped) and the schedule are defined in
+ * DESIGN.md ("K9 path simplification: shortcutPath"); smoothBSpline and checkAndRepair are NOT built.
+ *   motion checks, draws, skipped paths: as for mopa_simplify_paths_batch (one draw counter runs through the whole call); a path
+ *                  with path_len[e] > max_path is skipped too.
+ *   passes:        1..7; with bit 2 clear the result is mopa_simplify_paths_batch's.
+ *   max_rounds:    >= 1, bound on the rounds of the schedule (it stands in for OMPL's wall clock: a shortcut can add a vertex).
+ *   info_dev:      nullable, [E,6]: motion checks, draws, rounds, accepted shortcut splices, capacity skips, largest vertex
+ *                  count reached.
+ * Argument errors return before any launch: NULL scene / buffers, E < 0, max_path < 2, passes outside 1..7, max_rounds < 1
+ * (MOPA_ERR_INVALID_ARG); max_path beyond mopa_shortcut_paths_max_path(scene), what the per-wave LDS lists hold
+ * (MOPA_ERR_UNSUPPORTED). */
+int mopa_shortcut_paths_batch(MopaScene *scene, int64_t E, int32_t max_path, double *path_dev /*[E,max_path,nq] in/out*/,
+                              int32_t *path_len_dev /*[E] in/out*/, const int32_t *status_dev /*[E] nullable*/, uint64_t seed,
+                              uint64_t env_id_base, const uint64_t *env_ids_dev /*nullable*/, const uint64_t *seeds_dev /*nullable*/,
+                              int32_t passes, int32_t max_rounds, int64_t *info_dev /*[E,6] nullable*/, void *stream);
+int mopa_shortcut_paths_max_path(const MopaScene *scene);
 
 /* The rollout's invalid-target back-off (rl/mopa_rollouts.py:133-143) for E envs, asynchronous (no read-back unless E * num_trials
  * rows would exceed 1 GiB of scratch; E < 256: one wave per env walks its trials, otherwise all candidate rows of all

@@ -45,6 +45,7 @@ constexpr double kV5MaxReach = 32.0;        // metres: beyond this the FP32 broa
 static void plan_register_lds();            // defined with K3 (mopa_planner.inc)
 static void contacts_register_lds();        // defined with the contact report (mopa_contacts.inc)
 static void simplify_register_lds();        // defined with K9 (mopa_simplify.inc)
+static void shortcut_register_lds();        // defined with K9 shortcutPath (mopa_shortcut.inc)
 static void k1_register_lds();              // defined with the K1 kernel table (mopa_valid_launch.inc)
 
 extern "C" const char *mopa_last_error(void) { return g_err.c_str(); }
@@ -671,6 +672,7 @@ extern "C" int mopa_scene_create(const MopaSceneDesc *desc, MopaScene **out) {
     plan_register_lds();
     contacts_register_lds();
     simplify_register_lds();
+    shortcut_register_lds();
     *out = S;
     return MOPA_OK;
 }
@@ -733,6 +735,8 @@ extern "C" int mopa_check_motion_batch(MopaScene *S, const double *qa, const dou
 
 // K9: vertex-reducing path simplification, one wave per path (k_simplify_paths, mopa_simplify_paths_batch)
 #include "mopa_simplify.inc"
+// K9: shortcutPath in front of those passes, new states included (k_shortcut_paths, mopa_shortcut_paths_batch)
+#include "mopa_shortcut.inc"
 
 // split a full qpos into (active vector, env row) on the scene's scratch
 static int upload_state(MopaScene *S, const double *qpos_host) {

@@ -1,0 +1,413 @@
+// mopa_shortcut.inc -- K9: shortcutPath in front of the vertex-reducing passes, one wave per path.
+// (included by mopa_hip.hip behind mopa_simplify.inc: the kernel keeps the shape of k_simplify_paths, which stays as it is)
+//
+// OMPL's PathSimplifier::shortcutPath restated (DESIGN.md "K9 path simplification: shortcutPath"): two points are drawn by arc
+// length, located on the path, connected when K2's rule allows it -- and, a deviation, when the stubs between a new interior
+// point and its old neighbours pass too -- so the result has corners that are no planner rows.  The result is required identical
+// to the sequential form of tests/shortcut_ref.py, new states included, hence every floating-point operation is the one named
+// there: adds, one product / one division where stated, interp_dim's fma.  The rows stay where they are: a 16-bit list maps
+// vertex position to a row slot among the path's own max_path rows, new points take free slots (a stack), erased ones return
+// theirs, the cumulative distances live in LDS, and one in-place gather puts the rows into order at the end.  Every decision is
+// taken from wave-uniform values, the counters are scalars.  No atomics.  reduceVertices / collapseCloseVertices are the ones of
+// k_simplify_paths over the slot list.  smoothBSpline and checkAndRepair are not built.
+
+struct ShortcutArgs {
+    double *path;                       // [E, max_path, nq] in/out
+    int32_t *path_len;                  // [E] in/out
+    const int32_t *status;              // [E] nullable
+    long long E;
+    int max_path, passes, max_rounds;
+    unsigned long long seed, env_id_base;
+    const unsigned long long *env_ids, *seeds;      // nullable, as in MopaPlanParams
+    long long *info;                    // [E, 6] nullable: motion checks, draws, rounds, accepted splices, capacity skips, largest vertex count
+    int hdr_lds_off, list_lds_off, list_bytes;      // LDS: SceneHdr copy, the waves' lists, bytes of one wave's lists
+};
+
+constexpr int kShortcutInfoCols = 6;
+
+// per wave behind the header copy: [4 * na doubles: the endpoints of the check, the points A and B][nq doubles: a new row]
+// [max_path doubles: cumulative distances][max_path words: blocked pairs][max_path halves: slot of vertex k][max_path halves: free slots]
+static int shortcut_list_bytes(int na, int nq, int max_path) { return (8 * (4 * na + nq) + 16 * max_path + 15) & ~15; }
+static int shortcut_lds_bytes(const MopaScene *S, int max_path) {
+    return ((S->lds_bytes + 15) & ~15) + (((int)sizeof(SceneHdr) + 15) & ~15) + kWavesPerBlock * shortcut_list_bytes(S->na, S->nq, max_path);
+}
+
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_shortcut_paths(SceneHdr h, const double *__restrict__ g_dbl,
+                                                                                                     const int32_t *__restrict__ g_int, ShortcutArgs a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    LdsView v = make_view(h, smem);
+    SceneHdr *lh = reinterpret_cast<SceneHdr *>(smem + a.hdr_lds_off);
+    for (int i = threadIdx.x; i < (int)(sizeof(SceneHdr) / 4); i += blockDim.x)
+        reinterpret_cast<int *>(lh)[i] = reinterpret_cast<const int *>(&h)[i];
+    stage_scene(h, g_dbl, g_int, const_cast<double *>(v.dbl), const_cast<int *>(v.ints));
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int na = h.na, nq = h.nq, max_path = a.max_path;
+    unsigned char *lbase = smem + a.list_lds_off + wave * a.list_bytes;
+    double *ends = reinterpret_cast<double *>(lbase);                                   // [2][na]
+    double *ptA = ends + 2 * na, *ptB = ptA + na;                                       // [na] each: the two points of a shortcut
+    double *rowbuf = ptB + na;                                                          // [nq]: row 0, active entries overwritten per new row
+    double *D = rowbuf + nq;                                                            // [max_path]: cumulative distance at vertex k
+    unsigned *blocked = reinterpret_cast<unsigned *>(D + max_path);                     // [max_path]: slot i << 16 | slot j
+    unsigned short *idx = reinterpret_cast<unsigned short *>(blocked + max_path);       // [max_path]: row slot of vertex k
+    unsigned short *freel = idx + max_path;                                             // [max_path]: stack of the max_path - cnt free slots
+    double *tst = v.qbuf + na + h.n_pq;                                                 // spare [na] doubles behind the joint-value buffer
+    const int *adr = v.ints + h.o_act_adr;
+    const long long stride = (long long)gridDim.x * kWavesPerBlock;
+    for (long long e = (long long)blockIdx.x * kWavesPerBlock + wave; e < a.E; e += stride) {
+        const int n_in = a.path_len[e];
+        if ((a.status && a.status[e] != 0) || n_in < 3 || n_in > max_path) continue;         // skipped: nothing of it is touched
+        double *pe = a.path + (size_t)e * max_path * nq;
+        const unsigned long long key = rng_key(a.seeds ? a.seeds[e] : a.seed, a.env_ids ? a.env_ids[e] : a.env_id_base + (unsigned long long)e);
+        for (int i = lane; i < n_in; i += 64) idx[i] = (unsigned short)i;
+        for (int i = lane; i < max_path - n_in; i += 64) freel[i] = (unsigned short)(n_in + i);
+        for (int i = lane; i < nq; i += 64) rowbuf[i] = pe[i];
+        wave_sync();
+        int cnt = n_in, max_cnt = n_in, rounds = 0;
+        long long n_checks = 0, n_draws = 0, n_splices = 0, n_cap = 0;
+
+        auto slot = [&](int k) -> int { return __builtin_amdgcn_readfirstlane((int)idx[k]); };
+        auto uni = [&](bool b) -> bool { return __builtin_amdgcn_readfirstlane((int)b) != 0; };
+        auto load_vertex = [&](double *dst, int k) {
+            const double *r = pe + (size_t)slot(k) * nq;
+            for (int i = lane; i < na; i += 64) dst[i] = r[adr[i]];
+        };
+        auto load_point = [&](double *dst, const double *src) {
+            for (int i = lane; i < na; i += 64) dst[i] = src[i];
+        };
+        // K2's rule from ends[0..na) to ends[na..2 na)
+        auto check_ends = [&]() -> bool {
+            wave_sync();
+            n_checks++;
+            const int nd = __builtin_amdgcn_readfirstlane(valid_segment_count(h, v, ends, ends + na));
+            bool ok = true;
+            for (int k = nd; k >= (nd > 0 ? 1 : 0) && ok; k--) {
+                const double t = (nd > 0) ? (double)k / (double)nd : 1.0;
+                for (int i = lane; i < na; i += 64) tst[i] = (k == nd) ? ends[na + i] : interp_dim(h, v, i, ends[i], ends[na + i], t);
+                wave_sync();
+                ok = plan_state_valid_impl(lh, v.dbl, v.ints, v.grec, v.qbuf, v.wl, lane, tst, pe);
+            }
+            ok = uni(ok);
+            wave_sync();
+            return ok;
+        };
+        auto check = [&](int ia, int ib) -> bool {
+            load_vertex(ends, ia);
+            load_vertex(ends + na, ib);
+            return check_ends();
+        };
+        // the vertices strictly between ia and ib leave: their slots go onto the free stack, the tail moves by `delta` (< 0: up,
+        // 64 entries at a time ascending, a chunk's targets lie below the next chunk's sources; 1: down, descending), and `ins`
+        // entries behind ia are left to the caller
+        auto replace = [&](int ia, int ib, int ins) {
+            const int gap = ib - ia - 1, delta = ins - gap, top = max_path - cnt;
+            for (int j = lane; j < gap; j += 64) freel[top + j] = idx[ia + 1 + j];
+            wave_sync();
+            if (delta < 0) {
+                for (int base = ib; base < cnt; base += 64) {
+                    const int s = base + lane;
+                    const unsigned short val = s < cnt ? idx[s] : (unsigned short)0;
+                    wave_sync();
+                    if (s < cnt) idx[s + delta] = val;
+                    wave_sync();
+                }
+            } else if (delta > 0) {
+                for (int hi = cnt; hi > ib; hi -= 64) {
+                    const int s = hi - 1 - lane;
+                    const unsigned short val = s >= ib ? idx[s] : (unsigned short)0;
+                    wave_sync();
+                    if (s >= ib) idx[s + delta] = val;
+                    wave_sync();
+                }
+            }
+            cnt += delta;
+        };
+        auto erase = [&](int ia, int ib) { replace(ia, ib, 0); };
+        auto next_uniform = [&]() -> double {
+            const double u = rng_uniform_k(key, 0x8000000000000000ull + (unsigned long long)n_draws);
+            n_draws++;
+            return u;
+        };
+        auto uniform_int = [&](int lo, int hi) -> int {
+            const int m = hi - lo + 1;
+            const int r = (int)(next_uniform() * (double)m);
+            return lo + (r < m - 1 ? r : m - 1);
+        };
+        auto uniform_real = [&](double lo, double hi) -> double {
+            const double w = hi - lo, pr = next_uniform() * w;
+            return lo + pr;
+        };
+        auto reduce = [&]() -> bool {
+            const int n = cnt;
+            if (!(a.passes & 1) || n < 3) return false;
+            if (check(0, cnt - 1)) {
+                erase(0, cnt - 1);
+                return true;
+            }
+            bool result = false;
+            int nochange = 0;
+            for (int i = 0; i < n && nochange < n; i++, nochange++) {
+                const int count = cnt, max_n = count - 1;
+                const int range = 1 + (33 * count + 50) / 100;
+                int p1 = uniform_int(0, max_n);
+                int p2 = uniform_int(p1 - range > 0 ? p1 - range : 0, max_n < p1 + range ? max_n : p1 + range);
+                if ((p1 > p2 ? p1 - p2 : p2 - p1) < 2) {
+                    if (p1 < max_n - 1) p2 = p1 + 2;
+                    else if (p1 > 1) p2 = p1 - 2;
+                    else continue;
+                }
+                if (p1 > p2) { const int t = p1; p1 = p2; p2 = t; }
+                p1 = __builtin_amdgcn_readfirstlane(p1);
+                p2 = __builtin_amdgcn_readfirstlane(p2);
+                if (check(p1, p2)) {
+                    erase(p1, p2);
+                    nochange = 0;
+                    result = true;
+                }
+            }
+            return result;
+        };
+        auto collapse = [&]() {
+            const int n = cnt;
+            if (!(a.passes & 2) || n < 3) return;
+            int n_blocked = 0, nochange = 0;
+            for (int s = 0; s < n && nochange < n; s++, nochange++) {
+                // as in k_simplify_paths; a blocked pair is keyed by its two slots, which no vertex changes during this call
+                double best = __builtin_inf();
+                unsigned best_ij = 0xffffffffu;
+                for (int i = 0; i + 2 < cnt; i++) {
+                    const unsigned oi = (unsigned)slot(i);
+                    const double *ri = pe + (size_t)oi * nq;
+                    for (int j = i + 2 + lane; j < cnt; j += 64) {
+                        const unsigned oj = idx[j];
+                        const double *rj = pe + (size_t)oj * nq;
+                        double d = 0.0;
+                        for (int c = 0; c < na; c++) d += dist_dim(h, v, c, ri[adr[c]], rj[adr[c]]);
+                        if (d < best) {
+                            const unsigned keyij = (oi << 16) | oj;
+                            bool is_blocked = false;
+                            for (int b = 0; b < n_blocked; b++) is_blocked |= blocked[b] == keyij;
+                            if (!is_blocked) { best = d; best_ij = ((unsigned)i << 16) | (unsigned)j; }
+                        }
+                    }
+                }
+#pragma unroll
+                for (int off = 32; off > 0; off >>= 1) {
+                    const double od = __shfl_xor(best, off, 64);
+                    const unsigned oij = (unsigned)__shfl_xor((int)best_ij, off, 64);
+                    if (od < best || (od == best && oij < best_ij)) { best = od; best_ij = oij; }
+                }
+                best_ij = (unsigned)__builtin_amdgcn_readfirstlane((int)best_ij);
+                if (best_ij == 0xffffffffu) break;
+                const int bi = (int)(best_ij >> 16), bj = (int)(best_ij & 0xffffu);
+                if (check(bi, bj)) {
+                    erase(bi, bj);
+                    nochange = 0;
+                } else {
+                    if (lane == 0) blocked[n_blocked] = ((unsigned)idx[bi] << 16) | (unsigned)idx[bj];
+                    n_blocked++;       // (at most one per iteration, at most n <= max_path iterations)
+                    wave_sync();
+                }
+            }
+        };
+
+        // D[k] for k >= from (>= 1) as the ascending cumulative sum; the entries below `from` are those sums already
+        auto cumulative = [&](int from) {
+            for (int k = from + lane; k < cnt; k += 64) {
+                const double *ra = pe + (size_t)idx[k - 1] * nq, *rb = pe + (size_t)idx[k] * nq;
+                double d = 0.0;
+                for (int c = 0; c < na; c++) d += dist_dim(h, v, c, ra[adr[c]], rb[adr[c]]);
+                D[k] = d;
+            }
+            wave_sync();
+            if (lane == 0) {
+                double acc = D[from - 1];
+                for (int k = from; k < cnt; k++) { acc = acc + D[k]; D[k] = acc; }
+            }
+            wave_sync();
+        };
+        // (p, x) of arc length d: x the vertex the point snaps to, or -1 for a point inside segment (p, p + 1)
+        auto locate = [&](double d, double thr, int &p_out, int &x_out) {
+            int p = cnt - 1;
+            for (int base = 0; base < cnt; base += 64) {
+                const int k = base + lane;
+                const unsigned long long m = __ballot(k < cnt && D[k] >= d);
+                if (m) { p = base + __ffsll((long long)m) - 1; break; }
+            }
+            p = __builtin_amdgcn_readfirstlane(p);
+            int x = -1;
+            if (p == 0 || uni(D[p] - d < thr)) x = p;
+            else {
+                while (p > 0 && uni(d < D[p])) p--;
+                if (uni(d - D[p] < thr)) x = p;
+            }
+            if (x < 0 && p >= cnt - 1) x = p;       // (only a NaN among the rows gets here: no segment behind the last vertex)
+            p_out = p;
+            x_out = x;
+        };
+        // a new row: row 0's passive entries, the point's active ones
+        auto write_row = [&](int s, const double *pt) {
+            for (int i = lane; i < na; i += 64) rowbuf[adr[i]] = pt[i];
+            wave_sync();
+            for (int i = lane; i < nq; i += 64) pe[(size_t)s * nq + i] = rowbuf[i];
+            wave_sync();
+        };
+        auto shortcut = [&]() -> bool {
+            const int n = cnt;
+            if (!(a.passes & 4) || n < 3) return false;
+            if (lane == 0) D[0] = 0.0;
+            cumulative(1);
+            double total = D[cnt - 1];
+            if (uni(total == 0.0)) return false;
+            double thr = total * 0.005, rd = 0.33 * total;
+            bool result = false;
+            int nochange = 0;
+            for (int i = 0; i < n && nochange < n; i++, nochange++) {
+                double d0 = uniform_real(0.0, total);
+                int p0, x0, p1, x1;
+                locate(d0, thr, p0, x0);
+                const double lo = d0 - rd, hi = d0 + rd;
+                double d1 = uniform_real(lo > 0.0 ? lo : 0.0, total < hi ? total : hi);
+                locate(d1, thr, p1, x1);
+                if (p0 == p1 || x0 == p1 || x1 == p0 || p0 + 1 == x1 || p1 + 1 == x0 ||
+                    (x0 >= 0 && x1 >= 0 && (x0 > x1 ? x0 - x1 : x1 - x0) < 2))
+                    continue;
+                if (p0 > p1) {
+                    const double td = d0; d0 = d1; d1 = td;
+                    int t = p0; p0 = p1; p1 = t;
+                    t = x0; x0 = x1; x1 = t;
+                }
+                const int ia = x0 < 0 ? 1 : 0, ib = x1 < 0 ? 1 : 0;
+                if (ia && ib && p0 + 1 == p1 && cnt == max_path) { n_cap++; continue; }      // one vertex would become two: no slot
+                if (ia) {
+                    const double t0 = (d0 - D[p0]) / (D[p0 + 1] - D[p0]);
+                    const double *ra = pe + (size_t)slot(p0) * nq, *rb = pe + (size_t)slot(p0 + 1) * nq;
+                    for (int c = lane; c < na; c += 64) ptA[c] = interp_dim(h, v, c, ra[adr[c]], rb[adr[c]], t0);
+                } else load_vertex(ptA, x0);
+                if (ib) {
+                    const double t1 = (d1 - D[p1]) / (D[p1 + 1] - D[p1]);
+                    const double *ra = pe + (size_t)slot(p1) * nq, *rb = pe + (size_t)slot(p1 + 1) * nq;
+                    for (int c = lane; c < na; c += 64) ptB[c] = interp_dim(h, v, c, ra[adr[c]], rb[adr[c]], t1);
+                } else load_vertex(ptB, x1);
+                wave_sync();
+                // A-B, then the stub in front of an interior A, then the stub behind an interior B
+                load_point(ends, ptA);
+                load_point(ends + na, ptB);
+                bool ok = check_ends();
+                if (ok && ia) {
+                    load_vertex(ends, p0);
+                    load_point(ends + na, ptA);
+                    ok = check_ends();
+                }
+                if (ok && ib) {
+                    load_point(ends, ptB);
+                    load_vertex(ends + na, p1 + 1);
+                    ok = check_ends();
+                }
+                if (!ok) continue;
+                const int a_end = ia ? p0 : x0, s_start = ib ? p1 + 1 : x1;
+                replace(a_end, s_start, ia + ib);              // (cnt is the new count from here on)
+                // the erased vertices' slots are on the stack by now: the new rows may take them, A and B are in LDS
+                const int top = max_path - cnt;               // free slots left once the new ones are taken
+                const int sA = ia ? __builtin_amdgcn_readfirstlane((int)freel[top + ia + ib - 1]) : 0;
+                const int sB = ib ? __builtin_amdgcn_readfirstlane((int)freel[top]) : 0;
+                if (lane == 0) {
+                    if (ia) idx[a_end + 1] = (unsigned short)sA;
+                    if (ib) idx[a_end + 1 + ia] = (unsigned short)sB;
+                }
+                wave_sync();
+                if (ia) write_row(sA, ptA);
+                if (ib) write_row(sB, ptB);
+                if (cnt > max_cnt) max_cnt = cnt;
+                n_splices++;
+                cumulative(a_end + 1);
+                total = D[cnt - 1];
+                thr = total * 0.005;
+                rd = 0.33 * total;
+                nochange = 0;
+                result = true;
+            }
+            return result;
+        };
+
+        // PathSimplifier::simplify's loop; max_rounds stands in for its wall-clock condition
+        bool try_more = true;
+        while (try_more && rounds < a.max_rounds) {
+            rounds++;
+            if (a.passes & 4) {
+                int times = 0;
+                bool m;
+                do { m = shortcut(); } while (++times <= 5 && m);
+            }
+            try_more = reduce();
+            collapse();
+            for (int times = 0; try_more && times < 5; times++) try_more = reduce();
+        }
+
+        // the rows into order, in place: vertex k's row comes to row k; the row that lay there goes to the slot this frees when a
+        // later vertex still needs it (row 0 never moves)
+        for (int k = 1; k < cnt; k++) {
+            const int src = slot(k);
+            if (src == k) continue;
+            int user = -1;                    // the later vertex whose row lies in slot k
+            for (int base = k + 1; base < cnt; base += 64) {
+                const int j = base + lane;
+                const unsigned long long m = __ballot(j < cnt && (int)idx[j] == k);
+                if (m) { user = base + __ffsll((long long)m) - 1; break; }
+            }
+            user = __builtin_amdgcn_readfirstlane(user);
+            for (int i = lane; i < nq; i += 64) {
+                const double mine = pe[(size_t)src * nq + i];
+                if (user >= 0) pe[(size_t)src * nq + i] = pe[(size_t)k * nq + i];
+                pe[(size_t)k * nq + i] = mine;
+            }
+            if (lane == 0) {
+                if (user >= 0) idx[user] = (unsigned short)src;
+                idx[k] = (unsigned short)k;
+            }
+            wave_sync();
+        }
+        if (lane == 0) {
+            a.path_len[e] = cnt;
+            if (a.info) {
+                long long *o = a.info + kShortcutInfoCols * e;
+                o[0] = n_checks; o[1] = n_draws; o[2] = rounds; o[3] = n_splices; o[4] = n_cap; o[5] = max_cnt;
+            }
+        }
+        wave_sync();
+    }
+}
+
+static void shortcut_register_lds() {
+    (void)hipFuncSetAttribute((const void *)k_shortcut_paths, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLdsBytes);
+}
+
+extern "C" int mopa_shortcut_paths_max_path(const MopaScene *S) {
+    if (!S) return -1;
+    int mp = (kMaxLdsBytes - shortcut_lds_bytes(S, 0)) / (16 * kWavesPerBlock) - 4;
+    return std::max(0, std::min(mp, 65535));        // (16-bit slots)
+}
+
+extern "C" int mopa_shortcut_paths_batch(MopaScene *S, int64_t E, int32_t max_path, double *path_dev, int32_t *path_len_dev,
+                                         const int32_t *status_dev, uint64_t seed, uint64_t env_id_base, const uint64_t *env_ids_dev,
+                                         const uint64_t *seeds_dev, int32_t passes, int32_t max_rounds, int64_t *info_dev, void *stream) {
+    if (!S || (E > 0 && (!path_dev || !path_len_dev))) return fail(MOPA_ERR_INVALID_ARG, "null argument");
+    if (E < 0 || max_path < 2 || passes < 1 || passes > 7 || max_rounds < 1)
+        return fail(MOPA_ERR_INVALID_ARG, "E < 0, max_path < 2, passes outside 1..7 or max_rounds < 1");
+    if (max_path > mopa_shortcut_paths_max_path(S))
+        return fail(MOPA_ERR_UNSUPPORTED, "path shortcutting: max_path beyond what the per-wave LDS lists hold (" +
+                                              std::to_string(mopa_shortcut_paths_max_path(S)) + ")");
+    if (E == 0) return MOPA_OK;
+    ON_DEVICE(S->device);
+    ShortcutArgs a;
+    a.path = path_dev; a.path_len = path_len_dev; a.status = status_dev; a.E = (long long)E; a.max_path = max_path; a.passes = passes;
+    a.max_rounds = max_rounds; a.seed = seed; a.env_id_base = env_id_base;
+    a.env_ids = reinterpret_cast<const unsigned long long *>(env_ids_dev); a.seeds = reinterpret_cast<const unsigned long long *>(seeds_dev);
+    a.info = reinterpret_cast<long long *>(info_dev);
+    a.hdr_lds_off = (S->lds_bytes + 15) & ~15;
+    a.list_lds_off = a.hdr_lds_off + (((int)sizeof(SceneHdr) + 15) & ~15);
+    a.list_bytes = shortcut_list_bytes(S->na, S->nq, max_path);
+    hipLaunchKernelGGL(k_shortcut_paths, dim3(grid_for(S, E)), dim3(kBlock), shortcut_lds_bytes(S, max_path), (hipStream_t)stream, S->hdr, S->d_dbl,
+                       S->d_int, a);
+    HIP_TRY(hipGetLastError());
+    return MOPA_OK;
+}

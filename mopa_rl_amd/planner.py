@@ -20,8 +20,9 @@ Differences that cannot be hidden (DESIGN.md "Semantics"):
     be stated exactly -- the two vertex-removing passes reduceVertices and
     collapseCloseVertices (K9) -- runs behind the attribute
     ``vertex_simplify`` (default False; not a constructor argument, the
-    reference's 14 stay as they are); shortcutPath, the B-spline smoothing
-    and checkAndRepair are not built;
+    reference's 14 stay as they are), and shortcutPath, with the stub
+    checks of DESIGN.md, behind the attribute ``path_shortcut``; the
+    B-spline smoothing and checkAndRepair are not built;
   * ``glue_bodies`` must be empty (the reference never passes any).
 """
 from __future__ import annotations
@@ -66,10 +67,13 @@ class PyKinematicPlanner:
             raise NotImplementedError(f"algo={self.algo!r}: only 'rrt_connect' is implemented")
         if self.isSimplified:
             raise NotImplementedError("is_simplified=True (OMPL PathSimplifier) is not implemented; its two vertex-removing passes "
-                                      "(reduceVertices, collapseCloseVertices) are: set the attribute vertex_simplify = True")
+                                      "(reduceVertices, collapseCloseVertices) and its shortcutPath are: set the attributes "
+                                      "vertex_simplify = True and / or path_shortcut = True")
         #: K9: plan() runs reduceVertices + collapseCloseVertices over the solved path (`vertex_simplify_passes`: 1 / 2 / 3)
         self.vertex_simplify = False
         self.vertex_simplify_passes = 3
+        #: K9: plan() runs shortcutPath over the solved path, in front of the vertex passes when `vertex_simplify` is set too
+        self.path_shortcut = False
         self._model = load_scene(self.xml_filename)
         self._scene = _lib.Scene(self._model, self.passive_joint_idx, self.ignored_contacts, self.contact_threshold,
                                  range_=self._range, resolution=0.005, seed=self.seed)
@@ -86,7 +90,7 @@ class PyKinematicPlanner:
         # every plan() call of one planner object draws a fresh sample stream
         status, path, _ = self._scene.plan(start, goal, max_iters=max_iters, max_nodes=MAX_NODES, max_path=MAX_PATH,
                                            seed=self.seed, env_id=self._plan_count)
-        if self.vertex_simplify and status == _lib.PLAN_OK and len(path) >= 3:
+        if (self.vertex_simplify or self.path_shortcut) and status == _lib.PLAN_OK and len(path) >= 3:
             path = self._simplify(path, self._plan_count)
         self._plan_count += 1
         nq = self._scene.nq
@@ -102,8 +106,14 @@ class PyKinematicPlanner:
         from .batch import BatchPlanner
         ordinal = self._scene._ctor[7]          # the scene's device (-1: the current one, where it was created)
         dev = torch.device("cuda", ordinal if ordinal >= 0 else torch.cuda.current_device())
-        rows = torch.from_numpy(np.ascontiguousarray(path[None])).to(dev)
         plen = torch.tensor([len(path)], dtype=torch.int32, device=dev)
+        if self.path_shortcut:          # a shortcut can add a vertex: the rows get the planner's own capacity
+            rows = torch.zeros(1, MAX_PATH, path.shape[1], dtype=torch.float64, device=dev)
+            rows[0, :len(path)] = torch.from_numpy(np.ascontiguousarray(path)).to(dev)
+            BatchPlanner(self._scene).shortcut_paths(rows, plen, None, seed=self.seed, env_id_base=stream_id,
+                                                     passes=4 | (self.vertex_simplify_passes if self.vertex_simplify else 0))
+            return rows[0, :int(plen[0])].cpu().numpy()
+        rows = torch.from_numpy(np.ascontiguousarray(path[None])).to(dev)
         BatchPlanner(self._scene).simplify_paths(rows, plen, None, seed=self.seed, env_id_base=stream_id,
                                                  passes=self.vertex_simplify_passes)
         return rows[0, :int(plen[0])].cpu().numpy()

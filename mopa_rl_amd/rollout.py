@@ -74,6 +74,10 @@ class RolloutConfig:
     # rows.  Not the reference's is_simplified (shortcutPath, B-spline smoothing and checkAndRepair are not built).
     vertex_simplify: bool = False
     simple_planner_vertex_simplify: bool = False
+    # K9 shortcutPath in front of those passes (`BatchPlanner.plan(path_shortcut=True)`): the launch behind the planner's cuts
+    # corners through the interior of segments, so the executed rows include states that are no planner rows
+    path_shortcut: bool = False
+    simple_planner_path_shortcut: bool = False
     # data-parallel runs (sample streams keyed by (seed, GLOBAL env id, iteration), so results do not depend on how
     # the envs are sharded): this rank's envs are rows env_id_base .. env_id_base + E - 1 of env_id_total envs in all
     # (rank * E and world * E; 0 total = this rank alone)
@@ -576,13 +580,13 @@ class BatchMoPARollout:
         if stream is None:
             job["path"], job["plen"], job["status"], _ = self.bp.plan(cur_f, target_f, max_iters=iters, max_nodes=cfg.max_nodes,
                                                                       max_path=cfg.max_path, seed=cfg.seed, env_ids=gids, seeds=seeds,
-                                                                      vertex_simplify=cfg.vertex_simplify)
+                                                                      vertex_simplify=cfg.vertex_simplify, path_shortcut=cfg.path_shortcut)
         else:
             stream.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(stream):
                 res = self.bp.plan(cur_f, target_f, max_iters=iters, max_nodes=cfg.max_nodes, max_path=cfg.max_path, seed=cfg.seed,
                                    env_ids=gids, seeds=seeds, stream=stream, max_workgroups=cfg.planner_workgroups,
-                                   keep_state=keep, resume=resume, vertex_simplify=cfg.vertex_simplify,
+                                   keep_state=keep, resume=resume, vertex_simplify=cfg.vertex_simplify, path_shortcut=cfg.path_shortcut,
                                    exclusive=cfg.planner_exclusive >= 2 or (cfg.planner_exclusive == 1 and (resume is not None or not keep) and iters == self.main_iters))
                 job["path"], job["plen"], job["status"] = res[0], res[1], res[2]
                 if keep:
@@ -594,7 +598,7 @@ class BatchMoPARollout:
                     rb = self.bp.plan(cur_f, target_f, max_iters=self.main_iters, max_nodes=cfg.max_nodes, max_path=cfg.max_path,
                                       seed=cfg.seed, env_ids=gids, seeds=seeds, stream=stream,
                                       max_workgroups=cfg.planner_chain_workgroups or cfg.planner_workgroups,
-                                      resume=res[4], exclusive=cfg.planner_exclusive >= 1, vertex_simplify=cfg.vertex_simplify)
+                                      resume=res[4], exclusive=cfg.planner_exclusive >= 1, vertex_simplify=cfg.vertex_simplify, path_shortcut=cfg.path_shortcut)
                     ev_b = torch.cuda.Event()
                     ev_b.record(stream)
                     job["chain"] = {"path": rb[0], "plen": rb[1], "status": rb[2], "event": ev_b}
@@ -808,17 +812,18 @@ class BatchMoPARollout:
         stream = job["stream"]
         job["stage"] = stage
         simplify = cfg.simple_planner_vertex_simplify if stage == "simple" else cfg.vertex_simplify
+        shortcut = cfg.simple_planner_path_shortcut if stage == "simple" else cfg.path_shortcut
         if stream is None:
             job["path"], job["plen"], job["status"], _ = scene_bp.plan(starts, ends, max_iters=iters, max_nodes=cfg.max_nodes,
                                                                        max_path=cfg.max_path, seed=cfg.seed, env_ids=ids, seeds=seeds,
-                                                                       vertex_simplify=simplify)
+                                                                       vertex_simplify=simplify, path_shortcut=shortcut)
         else:
             stream.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(stream):
                 job["path"], job["plen"], job["status"], _ = scene_bp.plan(starts, ends, max_iters=iters, max_nodes=cfg.max_nodes,
                                                                            max_path=cfg.max_path, seed=cfg.seed, env_ids=ids, seeds=seeds,
                                                                            stream=stream, max_workgroups=cfg.planner_workgroups,
-                                                                           vertex_simplify=simplify)
+                                                                           vertex_simplify=simplify, path_shortcut=shortcut)
                 job["keep"] = (starts, ends, ids, seeds)
                 job["event"] = torch.cuda.Event()
                 job["event"].record(stream)
