@@ -215,8 +215,8 @@ int mopa_plan_batch(MopaScene *scene, const double *start_dev /*[E,nq]*/, const 
  * mopa_plan_batch wrote, in place, one wave per path, asynchronous on `stream` with no read-back.  Every surviving row is one of
  * the input rows (both endpoints are kept); the survivors are compacted to the front in order and path_len[e] is rewritten; rows
  * at and beyond the new length are unspecified.  The routines, their integer draws and the schedule are defined in DESIGN.md
- * ("K9 path simplification"); shortcutPath is mopa_shortcut_paths_batch below, the B-spline smoothing and checkAndRepair are NOT
- * built.
+ * ("K9 path simplification"); shortcutPath is mopa_shortcut_paths_batch below, the B-spline smoothing mopa_smooth_paths_batch;
+ * checkAndRepair is NOT built.
  *   motion checks: mopa_check_motion_batch's rule between the rows' active entries, with the passive entries of row 0.
  *   draws:         the k-th draw of path e is the uniform of counter 2^63 + k of the stream (seed, id) that query e of
  *                  mopa_plan_batch samples from -- seed, env_id_base, env_ids_dev and seeds_dev as in MopaPlanParams.
@@ -240,7 +240,7 @@ int mopa_simplify_paths_max_path(const MopaScene *scene);
  * grow, never beyond max_path); rows at and beyond the new length are unspecified.  The routine, every floating-point operation
  * of it, its two deviations from OMPL (a splice is accepted only if the stubs between a new interior point and its old
  * neighbours pass the motion check too; a splice that would need row max_path + 1 is skipped) and the schedule are defined in
- * DESIGN.md ("K9 path simplification: shortcutPath"); smoothBSpline and checkAndRepair are NOT built.
+ * DESIGN.md ("K9 path simplification: shortcutPath"); smoothBSpline is mopa_smooth_paths_batch below, checkAndRepair is NOT built.
  *   motion checks, draws, skipped paths: as for mopa_simplify_paths_batch (one draw counter runs through the whole call); a path
  *                  with path_len[e] > max_path is skipped too.
  *   passes:        1..7; with bit 2 clear the result is mopa_simplify_paths_batch's.
@@ -255,6 +255,31 @@ int mopa_shortcut_paths_batch(MopaScene *scene, int64_t E, int32_t max_path, dou
                               uint64_t env_id_base, const uint64_t *env_ids_dev /*nullable*/, const uint64_t *seeds_dev /*nullable*/,
                               int32_t passes, int32_t max_rounds, int64_t *info_dev /*[E,6] nullable*/, void *stream);
 int mopa_shortcut_paths_max_path(const MopaScene *scene);
+
+/* K9 with smoothBSpline: per round of the schedule shortcutPath (passes bit 2), then OMPL's PathSimplifier::smoothBSpline (bit 3),
+ * then the two vertex-removing passes (bits 0 and 1) -- PathSimplifier::simplify's schedule without its wall clock -- in place, one
+ * wave per path, asynchronous on `stream` with no read-back.  A smoothing step (at most 3 per call of the routine) puts a vertex
+ * into the middle of every segment and moves every old interior vertex to the middle of the middles towards its two new
+ * neighbours when both motions pass and the vertex moves by more than 1/100 of the path's length at entry; so new rows appear
+ * (interpolated active entries, row 0's passive ones) and input rows change their active entries.  Both endpoints are kept;
+ * path_len[e] can grow, never beyond max_path; rows at and beyond the new length are unspecified.  The routine, every
+ * floating-point operation of it and its three deviations from OMPL (a vertex moves only if the outer halves of its two old
+ * segments pass the motion check too; a step in which nothing moves is undone; a midpoint between two vertices that stayed is
+ * kept only if both its halves pass -- so every segment of a result has itself passed the motion check) are defined in DESIGN.md
+ * ("K9 path simplification: smoothBSpline"); a step that would need more than max_path rows ends the smoothing and counts as a
+ * capacity skip.  The routine draws nothing.  checkAndRepair is NOT built.
+ *   motion checks, draws, skipped paths, max_rounds: as for mopa_shortcut_paths_batch.
+ *   passes:        1..15; with bit 3 clear the result is mopa_shortcut_paths_batch's.
+ *   info_dev:      nullable, [E,10]: columns 0-5 as for mopa_shortcut_paths_batch (the smoothing's capacity stops are added into
+ *                  column 4), then smoothing steps subdivided, vertices moved, idle midpoints dropped, state checks.
+ * Argument errors return before any launch: NULL scene / buffers, E < 0, max_path < 2, passes outside 1..15, max_rounds < 1
+ * (MOPA_ERR_INVALID_ARG); max_path beyond mopa_smooth_paths_max_path(scene), what the per-wave LDS lists hold next to the slabs of
+ * the four-state validity pass (MOPA_ERR_UNSUPPORTED). */
+int mopa_smooth_paths_batch(MopaScene *scene, int64_t E, int32_t max_path, double *path_dev /*[E,max_path,nq] in/out*/,
+                            int32_t *path_len_dev /*[E] in/out*/, const int32_t *status_dev /*[E] nullable*/, uint64_t seed,
+                            uint64_t env_id_base, const uint64_t *env_ids_dev /*nullable*/, const uint64_t *seeds_dev /*nullable*/,
+                            int32_t passes, int32_t max_rounds, int64_t *info_dev /*[E,10] nullable*/, void *stream);
+int mopa_smooth_paths_max_path(const MopaScene *scene);
 
 /* The rollout's invalid-target back-off (rl/mopa_rollouts.py:133-143) for E envs, asynchronous (no read-back unless E * num_trials
  * rows would exceed 1 GiB of scratch; E < 256: one wave per env walks its trials, otherwise all candidate rows of all

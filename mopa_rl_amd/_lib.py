@@ -26,7 +26,7 @@ EXPORTED_SYMBOLS = [
     "mopa_last_error", "mopa_version", "mopa_device_count", "mopa_scene_create", "mopa_scene_destroy",
     "mopa_scene_num_active", "mopa_scene_active_idx", "mopa_scene_num_pairs", "mopa_scene_lds_bytes", "mopa_scene_valid_kernel",
     "mopa_scene_k1_baked", "mopa_scene_k1_export", "mopa_scene_hdr_offset", "mopa_k1_baked_fk_host",
-    "mopa_is_valid_batch", "mopa_check_motion_batch", "mopa_plan_batch", "mopa_simplify_paths_batch", "mopa_simplify_paths_max_path", "mopa_shortcut_paths_batch", "mopa_shortcut_paths_max_path", "mopa_pullback_batch", "mopa_is_valid_state", "mopa_plan",
+    "mopa_is_valid_batch", "mopa_check_motion_batch", "mopa_plan_batch", "mopa_simplify_paths_batch", "mopa_simplify_paths_max_path", "mopa_shortcut_paths_batch", "mopa_shortcut_paths_max_path", "mopa_smooth_paths_batch", "mopa_smooth_paths_max_path", "mopa_pullback_batch", "mopa_is_valid_state", "mopa_plan",
     "mopa_planner_status", "mopa_debug_fk", "mopa_debug_pair_dist", "mopa_contacts_batch", "mopa_contacts_state",
     "mopa_env_create", "mopa_env_destroy", "mopa_env_obs_dim", "mopa_env_action_dim", "mopa_env_step_batch", "mopa_env_exec_batch", "mopa_env_desired_batch",
     "mopa_env_attach_dynamics", "mopa_env_attach_contacts", "mopa_env_set_contact_stats", "mopa_rollout_stage", "mopa_rollout_pool_pick", "mopa_rollout_step_size", "mopa_reuse_batch", "mopa_replay_append", "mopa_replay_sample", "mopa_ct_desc_size", "mopa_env_contact_arena", "mopa_env_dyn_dofs", "mopa_env_dyn_qvel_width", "mopa_env_dyn_forward_batch", "mopa_env_dyn_substeps_batch", "mopa_env_step_dyn_batch",
@@ -188,6 +188,8 @@ def lib() -> C.CDLL:
     L.mopa_simplify_paths_max_path.argtypes = [vp]
     L.mopa_shortcut_paths_batch.argtypes = [vp, C.c_int64, C.c_int32, vp, vp, vp, C.c_uint64, C.c_uint64, vp, vp, C.c_int32, C.c_int32, vp, vp]
     L.mopa_shortcut_paths_max_path.argtypes = [vp]
+    L.mopa_smooth_paths_batch.argtypes = [vp, C.c_int64, C.c_int32, vp, vp, vp, C.c_uint64, C.c_uint64, vp, vp, C.c_int32, C.c_int32, vp, vp]
+    L.mopa_smooth_paths_max_path.argtypes = [vp]
     L.mopa_pullback_batch.argtypes = [vp, vp, vp, C.c_int64, C.c_double, C.c_int32, vp, vp, vp]
     L.mopa_is_valid_state.argtypes = [vp, _dp, C.POINTER(C.c_int32), _dp]
     L.mopa_plan.argtypes = [vp, _dp, _dp, C.POINTER(MopaPlanParams), _dp, C.POINTER(C.c_int32), C.POINTER(C.c_int32),

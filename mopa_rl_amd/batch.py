@@ -214,7 +214,8 @@ class BatchPlanner:
     def plan(self, start, goal, max_iters: int = 2000, max_nodes: int = 1024, max_path: int = 256, seed: int = 0,
              env_id_base: int = 0, stream=None, env_ids=None, seeds=None, max_workgroups: int = 0, exclusive: bool = False,
              keep_state: bool = False, resume=None, vertex_simplify: bool = False,
-             simplify_passes: int = 3, path_shortcut: bool = False) -> Tuple["object", "object", "object", "object"]:
+             simplify_passes: int = 3, path_shortcut: bool = False,
+             path_smooth: bool = False) -> Tuple["object", "object", "object", "object"]:
         """E independent RRT-Connect queries.  Returns (path[E,max_path,nq], path_len[E], status[E], n_checks[E]).
         env_ids (int64 [E] GPU tensor, optional): the sample-stream id of every query (default env_id_base + index).
         seeds (int64 [E] GPU tensor, optional): a seed per query instead of `seed`.
@@ -231,7 +232,10 @@ class BatchPlanner:
         queries an earlier launch settled, so every query's final rows are simplified exactly once.
         path_shortcut: the launch of `shortcut_paths` (K9 with OMPL's shortcutPath in front) takes that place instead, with
         passes = 4 | (simplify_passes if vertex_simplify else 0): the rows that come back include states that are no planner
-        rows, and `path_len` may have grown (never beyond max_path)."""
+        rows, and `path_len` may have grown (never beyond max_path).
+        path_smooth: the launch of `smooth_paths` (K9 with OMPL's smoothBSpline between shortcutPath and the vertex passes) takes
+        that place instead, with passes = 8 | (4 if path_shortcut else 0) | (simplify_passes if vertex_simplify else 0); the three
+        flags together are PathSimplifier::simplify's schedule without its wall clock."""
         torch = _torch()
         _check_f64(start, "start", self.nq)
         _check_f64(goal, "goal", self.nq)
@@ -265,7 +269,10 @@ class BatchPlanner:
         if resume is not None and stream is not None:
             for t in (resume.tree_q, resume.tree_p, resume.state):
                 t.record_stream(stream)
-        if path_shortcut:
+        if path_smooth:
+            self.smooth_paths(path, plen, status, seed=seed, env_id_base=env_id_base, env_ids=env_ids, seeds=seeds,
+                              passes=8 | (4 if path_shortcut else 0) | (int(simplify_passes) if vertex_simplify else 0), stream=stream)
+        elif path_shortcut:
             self.shortcut_paths(path, plen, status, seed=seed, env_id_base=env_id_base, env_ids=env_ids, seeds=seeds,
                                 passes=4 | (int(simplify_passes) if vertex_simplify else 0), stream=stream)
         elif vertex_simplify:
@@ -313,9 +320,30 @@ class BatchPlanner:
         passive ones) and `plen` can grow, never beyond max_path; a splice is accepted only when the stubs next to a new interior
         point pass the motion check as well, so every segment of the result has passed it (DESIGN.md "K9 path simplification:
         shortcutPath").  Paths with a non-zero status, fewer than 3 rows or more than max_path are not touched.  `max_rounds`
-        bounds the rounds of OMPL's schedule.  With bit 2 clear the result is `simplify_paths`'s.  smoothBSpline and
-        checkAndRepair are not built.  Returns None, or with `want_info` an int64 [E, 6] tensor: motion checks, draws, rounds,
+        bounds the rounds of OMPL's schedule.  With bit 2 clear the result is `simplify_paths`'s.  smoothBSpline is
+        `smooth_paths`; checkAndRepair is not built.  Returns None, or with `want_info` an int64 [E, 6] tensor: motion checks, draws, rounds,
         accepted shortcut splices, capacity skips, largest vertex count reached (0 for untouched paths)."""
+        return self._k9_rows_launch(_lib.lib().mopa_shortcut_paths_batch, 6, path, plen, status, seed, env_id_base, env_ids, seeds, passes, max_rounds,
+                                    stream, want_info)
+
+    def smooth_paths(self, path, plen, status=None, seed: int = 0, env_id_base: int = 0, env_ids=None, seeds=None, passes: int = 15,
+                     max_rounds: int = 16, stream=None, want_info: bool = False):
+        """K9 with smoothBSpline, in place: per round OMPL's shortcutPath (passes bit 2), then smoothBSpline (bit 3), then
+        reduceVertices (bit 0) and collapseCloseVertices (bit 1) -- arguments as for `shortcut_paths`, one wave per path,
+        asynchronous, no read-back.  A smoothing step puts a vertex into the middle of every segment and pulls the old interior
+        vertices towards their new neighbours, so rows that are no input rows appear and input rows change their active entries;
+        `plen` can grow, never beyond max_path (a step that would need more rows ends the smoothing and counts as a capacity
+        skip).  A vertex moves only if every segment that results has itself passed the motion check (DESIGN.md "K9 path
+        simplification: smoothBSpline").  Paths with a non-zero status, fewer than 3 rows or more than max_path are not touched.
+        With bit 3 clear the result is `shortcut_paths`'s.  checkAndRepair is not built (nothing is left for it to repair).
+        Returns None, or with `want_info` an int64 [E, 10] tensor: motion checks, draws, rounds, accepted shortcut splices,
+        capacity skips, largest vertex count reached, smoothing steps subdivided, vertices moved, idle midpoints dropped, state
+        checks (0 for untouched paths)."""
+        return self._k9_rows_launch(_lib.lib().mopa_smooth_paths_batch, 10, path, plen, status, seed, env_id_base, env_ids, seeds, passes, max_rounds,
+                                    stream, want_info)
+
+    def _k9_rows_launch(self, entry, info_cols, path, plen, status, seed, env_id_base, env_ids, seeds, passes, max_rounds, stream, want_info):
+        """argument checks and launch shared by `shortcut_paths` and `smooth_paths` (the two entry points take the same arguments)"""
         torch = _torch()
         if path.dtype != torch.float64 or not path.is_cuda or not path.is_contiguous() or path.dim() != 3 or path.shape[2] != self.nq:
             raise _lib.MopaError(f"path must be a contiguous float64 GPU tensor of shape [E, max_path, {self.nq}]")
@@ -330,10 +358,10 @@ class BatchPlanner:
         if want_info:
             if stream is not None:
                 with torch.cuda.stream(stream):
-                    info = torch.zeros(E, 6, dtype=torch.int64, device=path.device)
+                    info = torch.zeros(E, info_cols, dtype=torch.int64, device=path.device)
             else:
-                info = torch.zeros(E, 6, dtype=torch.int64, device=path.device)
-        _lib.check(_lib.lib().mopa_shortcut_paths_batch(
+                info = torch.zeros(E, info_cols, dtype=torch.int64, device=path.device)
+        _lib.check(entry(
             self.scene.handle, E, max_path, _ptr(path), _ptr(plen), _ptr(status) if status is not None else None,
             int(seed) & 0xFFFFFFFFFFFFFFFF, int(env_id_base), _ptr(env_ids) if env_ids is not None else None,
             _ptr(seeds) if seeds is not None else None, int(passes), int(max_rounds), _ptr(info) if info is not None else None,
@@ -343,7 +371,7 @@ class BatchPlanner:
     def plan_laddered(self, batches, max_iters: int = 2000, first_iters: int = 100, max_nodes: int = 1024, max_path: int = 256,
                       retry_streams=None, first_stream=None, max_workgroups_first: int = -1, retry_min: int = 1024, resume: bool = True,
                       retry_exclusive: bool = False, vertex_simplify: bool = False, simplify_passes: int = 3,
-                      path_shortcut: bool = False):
+                      path_shortcut: bool = False, path_smooth: bool = False):
         """A stream of query batches through RRT-Connect with an iteration ladder.  `batches`: list of dicts with `start`,
         `goal` ([E, nq] tensors), `seed` and optionally `env_ids` / `seeds` as for `plan`.  Every batch first runs with
         `first_iters`; the queries that come back "no exact solution" (a few %: the ones that would have kept the whole
@@ -355,8 +383,10 @@ class BatchPlanner:
         have finished).  One host read-back per batch (which queries go again).  The defaults of `first_iters` / `retry_min` are
         the ones that measured best over long streams of 4096-query batches on Push (tools/ladder_grid.py: 100 / 1024; they only
         schedule the work).  vertex_simplify / simplify_passes: as for `plan`, passed to every launch -- a query is solved by
-        exactly one of them, which simplifies its rows.  path_shortcut: as for `plan`, likewise."""
+        exactly one of them, which simplifies its rows.  path_shortcut, path_smooth: as for `plan`, likewise."""
         vs = dict(vertex_simplify=vertex_simplify, simplify_passes=simplify_passes, path_shortcut=path_shortcut)
+        if path_smooth:          # (flag off: the launches get exactly the keywords they got before)
+            vs["path_smooth"] = True
         torch = _torch()
         if first_iters <= 0 or first_iters >= max_iters:
             return [self.plan(b["start"], b["goal"], max_iters=max_iters, max_nodes=max_nodes, max_path=max_path, seed=b.get("seed", 0),

@@ -46,6 +46,7 @@ static void plan_register_lds();            // defined with K3 (mopa_planner.inc
 static void contacts_register_lds();        // defined with the contact report (mopa_contacts.inc)
 static void simplify_register_lds();        // defined with K9 (mopa_simplify.inc)
 static void shortcut_register_lds();        // defined with K9 shortcutPath (mopa_shortcut.inc)
+static void smooth_register_lds();          // defined with K9 smoothBSpline (mopa_smooth.inc)
 static void k1_register_lds();              // defined with the K1 kernel table (mopa_valid_launch.inc)
 
 extern "C" const char *mopa_last_error(void) { return g_err.c_str(); }
@@ -673,6 +674,7 @@ extern "C" int mopa_scene_create(const MopaSceneDesc *desc, MopaScene **out) {
     contacts_register_lds();
     simplify_register_lds();
     shortcut_register_lds();
+    smooth_register_lds();
     *out = S;
     return MOPA_OK;
 }
@@ -735,8 +737,6 @@ extern "C" int mopa_check_motion_batch(MopaScene *S, const double *qa, const dou
 
 // K9: vertex-reducing path simplification, one wave per path (k_simplify_paths, mopa_simplify_paths_batch)
 #include "mopa_simplify.inc"
-// K9: shortcutPath in front of those passes, new states included (k_shortcut_paths, mopa_shortcut_paths_batch)
-#include "mopa_shortcut.inc"
 
 // split a full qpos into (active vector, env row) on the scene's scratch
 static int upload_state(MopaScene *S, const double *qpos_host) {
@@ -805,5 +805,10 @@ extern "C" const char *mopa_planner_status(const MopaScene *S) { return S ? S->s
 // The planner entry points are defined in mopa_planner.inc (K3).
 #include "mopa_planner.inc"
 #include "mopa_pullback.inc"
+// K9: shortcutPath in front of the vertex passes, new states included (k_shortcut_paths, mopa_shortcut_paths_batch), and the same
+// body with smoothBSpline behind it (k_smooth_paths, mopa_smooth_paths_batch); behind the planner, whose multi-state validity
+// pass the smoothing uses
+#include "mopa_shortcut.inc"
+#include "mopa_smooth.inc"
 #include "mopa_ik.inc"
 #include "mopa_paths.inc"

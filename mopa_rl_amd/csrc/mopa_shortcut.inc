@@ -1,5 +1,6 @@
 // mopa_shortcut.inc -- K9: shortcutPath in front of the vertex-reducing passes, one wave per path.
-// (included by mopa_hip.hip behind mopa_simplify.inc: the kernel keeps the shape of k_simplify_paths, which stays as it is)
+// (included by mopa_hip.hip behind the planner, whose multi-state validity pass the SMOOTH form calls: the kernel keeps the shape of
+// k_simplify_paths, which stays as it is)
 //
 // OMPL's PathSimplifier::shortcutPath restated (DESIGN.md "K9 path simplification: shortcutPath"): two points are drawn by arc
 // length, located on the path, connected when K2's rule allows it -- and, a deviation, when the stubs between a new interior
@@ -9,7 +10,9 @@
 // vertex position to a row slot among the path's own max_path rows, new points take free slots (a stack), erased ones return
 // theirs, the cumulative distances live in LDS, and one in-place gather puts the rows into order at the end.  Every decision is
 // taken from wave-uniform values, the counters are scalars.  No atomics.  reduceVertices / collapseCloseVertices are the ones of
-// k_simplify_paths over the slot list.  smoothBSpline and checkAndRepair are not built.
+// k_simplify_paths over the slot list.  The body is a template: SMOOTH = false is k_shortcut_paths as it was, SMOOTH = true adds
+// smoothBSpline between the shortcut loop and the vertex passes of a round (k_smooth_paths, mopa_smooth.inc; DESIGN.md "K9 path
+// simplification: smoothBSpline").  checkAndRepair is not built.
 
 struct ShortcutArgs {
     double *path;                       // [E, max_path, nq] in/out
@@ -20,20 +23,27 @@ struct ShortcutArgs {
     unsigned long long seed, env_id_base;
     const unsigned long long *env_ids, *seeds;      // nullable, as in MopaPlanParams
     long long *info;                    // [E, 6] nullable: motion checks, draws, rounds, accepted splices, capacity skips, largest vertex count
+                                        // (k_smooth_paths: [E, 10], then smoothing steps, vertices moved, midpoints dropped, state checks)
     int hdr_lds_off, list_lds_off, list_bytes;      // LDS: SceneHdr copy, the waves' lists, bytes of one wave's lists
 };
 
-constexpr int kShortcutInfoCols = 6;
+constexpr int kShortcutInfoCols = 6, kSmoothInfoCols = 10;
 
 // per wave behind the header copy: [4 * na doubles: the endpoints of the check, the points A and B][nq doubles: a new row]
 // [max_path doubles: cumulative distances][max_path words: blocked pairs][max_path halves: slot of vertex k][max_path halves: free slots]
-static int shortcut_list_bytes(int na, int nq, int max_path) { return (8 * (4 * na + nq) + 16 * max_path + 15) & ~15; }
+MOPA_HD int shortcut_list_bytes(int na, int nq, int max_path) { return (8 * (4 * na + nq) + 16 * max_path + 15) & ~15; }
+// k_smooth_paths, behind a wave's lists, every part padded to 16 bytes: [max_path bytes: verdict of segment k in bits 0-1 (0 not
+// checked yet, 1 passed, 2 failed), bit 2 the midpoint in front of candidate k is valid, bit 3 midpoint k leaves][max_path bits:
+// vertex k moved in this step]; the slabs of the four-state validity pass (ms_bytes_per_wave) follow
+MOPA_HD int smooth_verdict_bytes(int max_path) { return (max_path + 15) & ~15; }
+MOPA_HD int smooth_flag_bytes(int max_path) { return smooth_verdict_bytes(max_path) + ((((max_path + 31) >> 5) * 4 + 15) & ~15); }
 static int shortcut_lds_bytes(const MopaScene *S, int max_path) {
     return ((S->lds_bytes + 15) & ~15) + (((int)sizeof(SceneHdr) + 15) & ~15) + kWavesPerBlock * shortcut_list_bytes(S->na, S->nq, max_path);
 }
 
-__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_shortcut_paths(SceneHdr h, const double *__restrict__ g_dbl,
-                                                                                                     const int32_t *__restrict__ g_int, ShortcutArgs a) {
+template <bool SMOOTH>
+__device__ __forceinline__ void shortcut_paths_body(const SceneHdr &h, const double *__restrict__ g_dbl, const int32_t *__restrict__ g_int,
+                                                    const ShortcutArgs &a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     LdsView v = make_view(h, smem);
     SceneHdr *lh = reinterpret_cast<SceneHdr *>(smem + a.hdr_lds_off);
@@ -51,6 +61,13 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(2, 2))) 
     unsigned short *idx = reinterpret_cast<unsigned short *>(blocked + max_path);       // [max_path]: row slot of vertex k
     unsigned short *freel = idx + max_path;                                             // [max_path]: stack of the max_path - cnt free slots
     double *tst = v.qbuf + na + h.n_pq;                                                 // spare [na] doubles behind the joint-value buffer
+    unsigned char *vd = SMOOTH ? lbase + shortcut_list_bytes(na, nq, max_path) : nullptr;               // [max_path]: flags of position k
+    unsigned *mvw = reinterpret_cast<unsigned *>(SMOOTH ? vd + smooth_verdict_bytes(max_path) : nullptr);    // [max_path bits]: vertex k moved
+    MsLds ms;
+    ms.grec = reinterpret_cast<double *>(SMOOTH ? vd + smooth_flag_bytes(max_path) : nullptr);
+    ms.qbuf = ms.grec + kMS * h.nmg * kGeomStride;
+    ms.qs = ms.qbuf + kMS * (na + h.n_pq + ms_sc_doubles(h.nmj, h.nmb));
+    ms.wl = reinterpret_cast<unsigned *>(ms.qs + kMS * na);
     const int *adr = v.ints + h.o_act_adr;
     const long long stride = (long long)gridDim.x * kWavesPerBlock;
     for (long long e = (long long)blockIdx.x * kWavesPerBlock + wave; e < a.E; e += stride) {
@@ -64,6 +81,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(2, 2))) 
         wave_sync();
         int cnt = n_in, max_cnt = n_in, rounds = 0;
         long long n_checks = 0, n_draws = 0, n_splices = 0, n_cap = 0;
+        long long n_steps = 0, n_moved = 0, n_dropped = 0, n_state = 0;           // (SMOOTH)
 
         auto slot = [&](int k) -> int { return __builtin_amdgcn_readfirstlane((int)idx[k]); };
         auto uni = [&](bool b) -> bool { return __builtin_amdgcn_readfirstlane((int)b) != 0; };
@@ -329,6 +347,145 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(2, 2))) 
             return result;
         };
 
+        // ---- smoothBSpline (SMOOTH; tests/smooth_ref.py) ----
+        // the verdict of segment (k, k + 1) as the vertices stand: checked at most once per step
+        auto seg = [&](int k) -> bool {
+            int vk = 1;
+            if constexpr (SMOOTH) {
+                vk = __builtin_amdgcn_readfirstlane((int)vd[k]) & 3;
+                if (vk == 0) {
+                    vk = check(k, k + 1) ? 1 : 2;
+                    if (lane == 0) vd[k] = (unsigned char)(vd[k] | vk);
+                    wave_sync();
+                }
+            }
+            return vk == 1;
+        };
+        auto smooth = [&]() {
+            if constexpr (SMOOTH) {
+                if (cnt < 3) return;
+                if (lane == 0) D[0] = 0.0;
+                cumulative(1);
+                const double min_change = D[cnt - 1] / 100.0;          // of the path as it came in: not recomputed between steps
+                for (int step = 0; step < 3; step++) {
+                    const int n0 = cnt, n = 2 * n0 - 1, top = max_path - n0;
+                    if (n > max_path) { n_cap++; return; }              // no slots for the midpoints: the smoothing ends here
+                    // subdivide: vertex k goes to position 2k (from the top down, 64 entries at a time: a chunk's targets lie
+                    // above every source still to be read), the midpoint behind it takes a free slot
+                    for (int hi = n0; hi > 1; hi -= 64) {
+                        const int s = hi - 1 - lane;
+                        const unsigned short val = s >= 1 ? idx[s] : (unsigned short)0;
+                        wave_sync();
+                        if (s >= 1) idx[2 * s] = val;
+                        wave_sync();
+                    }
+                    for (int k = lane; k < n0 - 1; k += 64) idx[2 * k + 1] = freel[top - 1 - k];
+                    for (int k = lane; k < n; k += 64) vd[k] = 0;
+                    for (int k = lane; k < ((n + 31) >> 5); k += 64) mvw[k] = 0u;
+                    wave_sync();
+                    cnt = n;
+                    if (cnt > max_cnt) max_cnt = cnt;
+                    n_steps++;
+                    // the midpoints' rows: row 0's passive entries, then the interpolated active ones
+                    for (int j = lane; j < (n0 - 1) * nq; j += 64) {
+                        const int k = j / nq, i = j - k * nq;
+                        pe[(size_t)idx[2 * k + 1] * nq + i] = rowbuf[i];
+                    }
+                    wave_sync();
+                    for (int j = lane; j < (n0 - 1) * na; j += 64) {
+                        const int k = j / na, c = j - k * na;
+                        const double *ra = pe + (size_t)idx[2 * k] * nq, *rb = pe + (size_t)idx[2 * k + 2] * nq;
+                        pe[(size_t)idx[2 * k + 1] * nq + adr[c]] = interp_dim(h, v, c, ra[adr[c]], rb[adr[c]], 0.5);
+                    }
+                    wave_sync();
+                    // the state check of the midpoint in front of every candidate i = 2, 4, ... < n - 1, kMS states per validity
+                    // pass: the candidates read odd positions and their own vertex only, so none depends on another
+                    const int nc = n0 - 2;
+                    for (int c0 = 0; c0 < nc; c0 += kMS) {
+                        const int ns = nc - c0 < kMS ? nc - c0 : kMS;
+                        for (int j = lane; j < ns * na; j += 64) {
+                            const int s = j / na, c = j - s * na;
+                            ms.qs[j] = pe[(size_t)idx[2 * (c0 + s) + 1] * nq + adr[c]];
+                        }
+                        wave_sync();
+                        const unsigned okm = (unsigned)__builtin_amdgcn_readfirstlane(
+                            (int)plan_states_valid_ms(lh, v.dbl, v.ints, ms.grec, ms.qbuf, ms.wl, ms.qs, lane, ns, pe));
+                        if (lane < ns && ((okm >> lane) & 1u)) vd[2 * (c0 + lane) + 2] = 4;
+                        n_state += ns;
+                        wave_sync();
+                    }
+                    // the candidates in order: OMPL's two checks and the change, then -- a deviation -- the outer halves of the
+                    // two segments next to the vertex, whose verdicts depend on what moved before
+                    int u = 0;
+                    for (int i = 2; i < n - 1; i += 2) {
+                        if (!(__builtin_amdgcn_readfirstlane((int)vd[i]) & 4)) continue;
+                        const double *rm = pe + (size_t)slot(i - 1) * nq, *ri = pe + (size_t)slot(i) * nq, *rp = pe + (size_t)slot(i + 1) * nq;
+                        for (int c = lane; c < na; c += 64) {
+                            const double t1 = interp_dim(h, v, c, rm[adr[c]], ri[adr[c]], 0.5);
+                            const double t2 = interp_dim(h, v, c, ri[adr[c]], rp[adr[c]], 0.5);
+                            ptA[c] = interp_dim(h, v, c, t1, t2, 0.5);
+                        }
+                        wave_sync();
+                        load_vertex(ends, i - 1);
+                        load_point(ends + na, ptA);
+                        if (!check_ends()) continue;
+                        load_point(ends, ptA);
+                        load_vertex(ends + na, i + 1);
+                        if (!check_ends()) continue;
+                        double d = 0.0;
+                        for (int c = 0; c < na; c++) d += dist_dim(h, v, c, ri[adr[c]], ptA[c]);
+                        if (!uni(d > min_change)) continue;
+                        if (!seg(i - 2) || !seg(i + 1)) continue;
+                        for (int c = lane; c < na; c += 64) pe[(size_t)slot(i) * nq + adr[c]] = ptA[c];
+                        if (lane == 0) {        // the two segments at the vertex are exactly the two checks just made
+                            vd[i - 1] = (unsigned char)((vd[i - 1] & ~3) | 1);
+                            vd[i] = (unsigned char)((vd[i] & ~3) | 1);
+                            mvw[i >> 5] |= 1u << (i & 31);
+                        }
+                        wave_sync();
+                        u++;
+                    }
+                    if (u == 0) {           // (a deviation) nothing moved: the path as before the step, the popped slots are on the stack still
+                        for (int base = 1; base < n0; base += 64) {
+                            const int s = base + lane;
+                            const unsigned short val = s < n0 ? idx[2 * s] : (unsigned short)0;
+                            wave_sync();
+                            if (s < n0) idx[s] = val;
+                            wave_sync();
+                        }
+                        cnt = n0;
+                        return;
+                    }
+                    n_moved += u;
+                    // (a deviation) a midpoint between two vertices that stayed is kept only if both its halves pass
+                    for (int k = 0; k < n0 - 1; k++) {
+                        const unsigned w0 = mvw[(2 * k) >> 5], w1 = mvw[(2 * k + 2) >> 5];
+                        if (uni((((w0 >> ((2 * k) & 31)) | (w1 >> ((2 * k + 2) & 31))) & 1u) != 0u)) continue;
+                        if (seg(2 * k) && seg(2 * k + 1)) continue;
+                        if (lane == 0) vd[2 * k + 1] |= 8;
+                        n_dropped++;
+                    }
+                    wave_sync();
+                    // the kept positions to the front in order, the slots of the dropped midpoints back onto the stack
+                    int out = 0, n_out = 0;
+                    const int top2 = max_path - n;
+                    for (int base = 0; base < n; base += 64) {
+                        const int k = base + lane;
+                        const bool in = k < n, keep = in && !(vd[k] & 8);
+                        const unsigned short val = in ? idx[k] : (unsigned short)0;
+                        const unsigned long long mk = __ballot(keep), md = __ballot(in && !keep), lt = (1ull << lane) - 1ull;
+                        wave_sync();
+                        if (keep) idx[out + __popcll(mk & lt)] = val;
+                        else if (in) freel[top2 + n_out + __popcll(md & lt)] = val;
+                        out += __popcll(mk);
+                        n_out += __popcll(md);
+                        wave_sync();
+                    }
+                    cnt = out;
+                }
+            }
+        };
+
         // PathSimplifier::simplify's loop; max_rounds stands in for its wall-clock condition
         bool try_more = true;
         while (try_more && rounds < a.max_rounds) {
@@ -338,6 +495,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(2, 2))) 
                 bool m;
                 do { m = shortcut(); } while (++times <= 5 && m);
             }
+            if (SMOOTH && (a.passes & 8)) smooth();
             try_more = reduce();
             collapse();
             for (int times = 0; try_more && times < 5; times++) try_more = reduce();
@@ -369,12 +527,18 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(2, 2))) 
         if (lane == 0) {
             a.path_len[e] = cnt;
             if (a.info) {
-                long long *o = a.info + kShortcutInfoCols * e;
+                long long *o = a.info + (SMOOTH ? kSmoothInfoCols : kShortcutInfoCols) * e;
                 o[0] = n_checks; o[1] = n_draws; o[2] = rounds; o[3] = n_splices; o[4] = n_cap; o[5] = max_cnt;
+                if (SMOOTH) { o[6] = n_steps; o[7] = n_moved; o[8] = n_dropped; o[9] = n_state; }
             }
         }
         wave_sync();
     }
+}
+
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_shortcut_paths(SceneHdr h, const double *__restrict__ g_dbl,
+                                                                                                     const int32_t *__restrict__ g_int, ShortcutArgs a) {
+    shortcut_paths_body<false>(h, g_dbl, g_int, a);
 }
 
 static void shortcut_register_lds() {

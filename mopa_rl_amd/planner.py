@@ -21,8 +21,11 @@ Differences that cannot be hidden (DESIGN.md "Semantics"):
     collapseCloseVertices (K9) -- runs behind the attribute
     ``vertex_simplify`` (default False; not a constructor argument, the
     reference's 14 stay as they are), and shortcutPath, with the stub
-    checks of DESIGN.md, behind the attribute ``path_shortcut``; the
-    B-spline smoothing and checkAndRepair are not built;
+    checks of DESIGN.md, behind the attribute ``path_shortcut``, and
+    smoothBSpline, with the outer-half checks of DESIGN.md, behind the
+    attribute ``path_smooth``.  The three together are ``simplify()``'s
+    schedule without its wall clock; checkAndRepair is not built (every
+    segment of a result has itself passed the motion check);
   * ``glue_bodies`` must be empty (the reference never passes any).
 """
 from __future__ import annotations
@@ -67,13 +70,16 @@ class PyKinematicPlanner:
             raise NotImplementedError(f"algo={self.algo!r}: only 'rrt_connect' is implemented")
         if self.isSimplified:
             raise NotImplementedError("is_simplified=True (OMPL PathSimplifier) is not implemented; its two vertex-removing passes "
-                                      "(reduceVertices, collapseCloseVertices) and its shortcutPath are: set the attributes "
-                                      "vertex_simplify = True and / or path_shortcut = True")
+                                      "(reduceVertices, collapseCloseVertices), its shortcutPath and its smoothBSpline are: set "
+                                      "the attributes vertex_simplify = True, path_shortcut = True and / or path_smooth = True "
+                                      "(the three together are simplify()'s schedule without its wall clock)")
         #: K9: plan() runs reduceVertices + collapseCloseVertices over the solved path (`vertex_simplify_passes`: 1 / 2 / 3)
         self.vertex_simplify = False
         self.vertex_simplify_passes = 3
         #: K9: plan() runs shortcutPath over the solved path, in front of the vertex passes when `vertex_simplify` is set too
         self.path_shortcut = False
+        #: K9: plan() runs smoothBSpline over the solved path, behind shortcutPath and in front of the vertex passes
+        self.path_smooth = False
         self._model = load_scene(self.xml_filename)
         self._scene = _lib.Scene(self._model, self.passive_joint_idx, self.ignored_contacts, self.contact_threshold,
                                  range_=self._range, resolution=0.005, seed=self.seed)
@@ -90,7 +96,7 @@ class PyKinematicPlanner:
         # every plan() call of one planner object draws a fresh sample stream
         status, path, _ = self._scene.plan(start, goal, max_iters=max_iters, max_nodes=MAX_NODES, max_path=MAX_PATH,
                                            seed=self.seed, env_id=self._plan_count)
-        if (self.vertex_simplify or self.path_shortcut) and status == _lib.PLAN_OK and len(path) >= 3:
+        if (self.vertex_simplify or self.path_shortcut or self.path_smooth) and status == _lib.PLAN_OK and len(path) >= 3:
             path = self._simplify(path, self._plan_count)
         self._plan_count += 1
         nq = self._scene.nq
@@ -107,6 +113,16 @@ class PyKinematicPlanner:
         ordinal = self._scene._ctor[7]          # the scene's device (-1: the current one, where it was created)
         dev = torch.device("cuda", ordinal if ordinal >= 0 else torch.cuda.current_device())
         plen = torch.tensor([len(path)], dtype=torch.int32, device=dev)
+        if self.path_smooth:            # a smoothing step nearly doubles the vertices: the largest capacity the kernel's lists hold
+            bp = BatchPlanner(self._scene)
+            cap = min(MAX_PATH, int(_lib.lib().mopa_smooth_paths_max_path(self._scene.handle)))
+            if len(path) > cap:
+                raise _lib.MopaError(f"path_smooth: the path has {len(path)} rows, the smoothing kernel holds {cap}")
+            rows = torch.zeros(1, cap, path.shape[1], dtype=torch.float64, device=dev)
+            rows[0, :len(path)] = torch.from_numpy(np.ascontiguousarray(path)).to(dev)
+            bp.smooth_paths(rows, plen, None, seed=self.seed, env_id_base=stream_id,
+                            passes=8 | (4 if self.path_shortcut else 0) | (self.vertex_simplify_passes if self.vertex_simplify else 0))
+            return rows[0, :int(plen[0])].cpu().numpy()
         if self.path_shortcut:          # a shortcut can add a vertex: the rows get the planner's own capacity
             rows = torch.zeros(1, MAX_PATH, path.shape[1], dtype=torch.float64, device=dev)
             rows[0, :len(path)] = torch.from_numpy(np.ascontiguousarray(path)).to(dev)

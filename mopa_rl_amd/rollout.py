@@ -71,13 +71,17 @@ class RolloutConfig:
     seed: int = 1234
     # K9: OMPL's two vertex-removing simplifier passes (reduceVertices, collapseCloseVertices) directly behind every launch of the
     # main / the simple planner (`BatchPlanner.plan(vertex_simplify=True)`); un-wrap and densification then work on the shorter
-    # rows.  Not the reference's is_simplified (shortcutPath, B-spline smoothing and checkAndRepair are not built).
+    # rows.  Not the reference's is_simplified (shortcutPath and the B-spline smoothing have their own flags below).
     vertex_simplify: bool = False
     simple_planner_vertex_simplify: bool = False
     # K9 shortcutPath in front of those passes (`BatchPlanner.plan(path_shortcut=True)`): the launch behind the planner's cuts
     # corners through the interior of segments, so the executed rows include states that are no planner rows
     path_shortcut: bool = False
     simple_planner_path_shortcut: bool = False
+    # K9 smoothBSpline between shortcutPath and those passes (`BatchPlanner.plan(path_smooth=True)`): the launch behind the
+    # planner's is `smooth_paths`; with all three flags it runs PathSimplifier::simplify's schedule without its wall clock
+    path_smooth: bool = False
+    simple_planner_path_smooth: bool = False
     # data-parallel runs (sample streams keyed by (seed, GLOBAL env id, iteration), so results do not depend on how
     # the envs are sharded): this rank's envs are rows env_id_base .. env_id_base + E - 1 of env_id_total envs in all
     # (rank * E and world * E; 0 total = this rank alone)
@@ -573,6 +577,7 @@ class BatchMoPARollout:
             seeds = (self.t_env[ids] + cfg.seed).contiguous()
         gids = (ids + int(cfg.env_id_base)).contiguous() if cfg.env_id_base else ids       # the planner's stream id: the GLOBAL env id
         iters = self.main_iters if iters is None else int(iters)
+        smooth = {"path_smooth": True} if cfg.path_smooth else {}       # (flag off: the launches get the keywords they always got)
         job = {"ids": ids, "cur": cur_f, "target": target_f, "steps": self.t_env[ids].clone() if steps is None else steps, "event": None, "stage": "rrt", "stream": stream,
                "iters": iters}
         if self._seam_idx:       # the planner sees the wrapped endpoints; job["cur"] stays the caller's state
@@ -580,13 +585,14 @@ class BatchMoPARollout:
         if stream is None:
             job["path"], job["plen"], job["status"], _ = self.bp.plan(cur_f, target_f, max_iters=iters, max_nodes=cfg.max_nodes,
                                                                       max_path=cfg.max_path, seed=cfg.seed, env_ids=gids, seeds=seeds,
-                                                                      vertex_simplify=cfg.vertex_simplify, path_shortcut=cfg.path_shortcut)
+                                                                      vertex_simplify=cfg.vertex_simplify, path_shortcut=cfg.path_shortcut,
+                                                                      **smooth)
         else:
             stream.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(stream):
                 res = self.bp.plan(cur_f, target_f, max_iters=iters, max_nodes=cfg.max_nodes, max_path=cfg.max_path, seed=cfg.seed,
                                    env_ids=gids, seeds=seeds, stream=stream, max_workgroups=cfg.planner_workgroups,
-                                   keep_state=keep, resume=resume, vertex_simplify=cfg.vertex_simplify, path_shortcut=cfg.path_shortcut,
+                                   keep_state=keep, resume=resume, vertex_simplify=cfg.vertex_simplify, path_shortcut=cfg.path_shortcut, **smooth,
                                    exclusive=cfg.planner_exclusive >= 2 or (cfg.planner_exclusive == 1 and (resume is not None or not keep) and iters == self.main_iters))
                 job["path"], job["plen"], job["status"] = res[0], res[1], res[2]
                 if keep:
@@ -598,7 +604,7 @@ class BatchMoPARollout:
                     rb = self.bp.plan(cur_f, target_f, max_iters=self.main_iters, max_nodes=cfg.max_nodes, max_path=cfg.max_path,
                                       seed=cfg.seed, env_ids=gids, seeds=seeds, stream=stream,
                                       max_workgroups=cfg.planner_chain_workgroups or cfg.planner_workgroups,
-                                      resume=res[4], exclusive=cfg.planner_exclusive >= 1, vertex_simplify=cfg.vertex_simplify, path_shortcut=cfg.path_shortcut)
+                                      resume=res[4], exclusive=cfg.planner_exclusive >= 1, vertex_simplify=cfg.vertex_simplify, path_shortcut=cfg.path_shortcut, **smooth)
                     ev_b = torch.cuda.Event()
                     ev_b.record(stream)
                     job["chain"] = {"path": rb[0], "plen": rb[1], "status": rb[2], "event": ev_b}
@@ -813,17 +819,18 @@ class BatchMoPARollout:
         job["stage"] = stage
         simplify = cfg.simple_planner_vertex_simplify if stage == "simple" else cfg.vertex_simplify
         shortcut = cfg.simple_planner_path_shortcut if stage == "simple" else cfg.path_shortcut
+        smooth = {"path_smooth": True} if (cfg.simple_planner_path_smooth if stage == "simple" else cfg.path_smooth) else {}
         if stream is None:
             job["path"], job["plen"], job["status"], _ = scene_bp.plan(starts, ends, max_iters=iters, max_nodes=cfg.max_nodes,
                                                                        max_path=cfg.max_path, seed=cfg.seed, env_ids=ids, seeds=seeds,
-                                                                       vertex_simplify=simplify, path_shortcut=shortcut)
+                                                                       vertex_simplify=simplify, path_shortcut=shortcut, **smooth)
         else:
             stream.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(stream):
                 job["path"], job["plen"], job["status"], _ = scene_bp.plan(starts, ends, max_iters=iters, max_nodes=cfg.max_nodes,
                                                                            max_path=cfg.max_path, seed=cfg.seed, env_ids=ids, seeds=seeds,
                                                                            stream=stream, max_workgroups=cfg.planner_workgroups,
-                                                                           vertex_simplify=simplify, path_shortcut=shortcut)
+                                                                           vertex_simplify=simplify, path_shortcut=shortcut, **smooth)
                 job["keep"] = (starts, ends, ids, seeds)
                 job["event"] = torch.cuda.Event()
                 job["event"].record(stream)

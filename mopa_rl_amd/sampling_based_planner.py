@@ -29,7 +29,7 @@ def joint_convert(angle):
 class SamplingBasedPlanner:
     def __init__(self, config, xml_path, num_actions, non_limited_idx, planner_type=None, passive_joint_idx=[],
                  glue_bodies=[], ignored_contacts=[], contact_threshold=0.0, goal_bias=0.05, is_simplified=False,
-                 simplified_duration=0.1, range_=None, vertex_simplify=False, path_shortcut=False):
+                 simplified_duration=0.1, range_=None, vertex_simplify=False, path_shortcut=False, path_smooth=False):
         self.config = config
         self.non_limited_idx = non_limited_idx
         algo = config.planner_type if planner_type is None else planner_type
@@ -43,6 +43,8 @@ class SamplingBasedPlanner:
         self.planner.vertex_simplify = bool(vertex_simplify)
         # K9 shortcutPath, likewise: corners are cut through the interior of segments, so `states` holds rows the planner never made
         self.planner.path_shortcut = bool(path_shortcut)
+        # K9 smoothBSpline, likewise: vertices are added and pulled towards their neighbours, so rows of the planner change too
+        self.planner.path_smooth = bool(path_smooth)
 
     # ------------------------------------------------------------------
     def convert_nonlimited(self, state):
