@@ -281,6 +281,52 @@ int mopa_smooth_paths_batch(MopaScene *scene, int64_t E, int32_t max_path, doubl
                             int32_t passes, int32_t max_rounds, int64_t *info_dev /*[E,10] nullable*/, void *stream);
 int mopa_smooth_paths_max_path(const MopaScene *scene);
 
+/* K3b: E independent RRT* queries (the reference's planner_type "rrt": OMPL geometric::RRTstar with k-nearest neighbourhoods and
+ * the path-length objective), one wave per query, asynchronous on `stream` with no read-back.  A single tree that chooses every
+ * new node's parent by cost among its k nearest nodes and rewires those neighbours through the new node; the planner is anytime
+ * and always runs its whole iteration budget.  The routine, every floating-point operation of it and its deviations from OMPL (an
+ * iteration budget for the wall clock, the counter sample stream, a node capacity) are defined in DESIGN.md ("K3b RRT*"); the
+ * sequential form is tests/rrtstar_ref.py.
+ *   draws:        iteration `it` of query e uses counters it * (na + 1) (goal bias) and it * (na + 1) + 1 + a (coordinate a) of the
+ *                 stream (seed, id) -- seed, env_id_base, env_ids_dev, seeds_dev as in MopaPlanParams; K9's draws stay disjoint.
+ *   neighbours:   k(n) = ceil(rewire_factor * (e + e / na) * ln(n + 1)) of the n nodes (mopa_plan_star_k), at most 64.
+ *   motion checks: mopa_check_motion_batch's rule, with the passive entries of start[e].
+ *   goal nodes:   new states within goal_threshold (L1, SO(2) the short way) of the goal; until one exists a sample is the goal
+ *                 itself with probability goal_bias.
+ *   results:      status[e] in {0, -4, -5}; path rows hold full qpos vectors with the passive columns of start (the chain of the
+ *                 cheapest goal node; more than max_path rows: -4); path_len[e] = 0 and cost[e] = +inf unless status[e] = 0;
+ *                 cost[e] = that node's cost, the chain's top-down sum of L1 segment lengths.
+ *   info_dev:     nullable, [E,8]: iterations run, nodes, motion checks, rewires, goal nodes, first goal iteration (-1: none),
+ *                 descendant cost updates, iterations that found the tree full.
+ * The trees live in the library's scratch, one per resident wave (memory does not grow with E).
+ * Argument errors return before any launch: NULL scene / params / buffers, E < 0, max_iters < 0, max_nodes < 2, max_path < 2,
+ * goal_bias outside [0, 1], goal_threshold < 0, rewire_factor <= 0 (MOPA_ERR_INVALID_ARG); k(max_nodes) > 64 or trees the scratch
+ * cannot hold (MOPA_ERR_UNSUPPORTED). */
+typedef struct MopaStarParams {
+    int32_t max_iters;     /* iteration budget: always spent */
+    int32_t max_nodes;     /* node capacity of the tree; an iteration that finds it full does nothing */
+    int32_t max_path;      /* rows available per query in `path` */
+    uint64_t seed;
+    uint64_t env_id_base;
+    const uint64_t *env_ids_dev;   /* nullable, [E] */
+    const uint64_t *seeds_dev;     /* nullable, [E] */
+    double goal_bias;              /* OMPL's default: 0.05 */
+    double goal_threshold;         /* the reference's `threshold` (0: the goal sample itself has to be reached) */
+    double rewire_factor;          /* OMPL's default: 1.1 */
+    int32_t max_workgroups;        /* > 0: cap on the persistent workgroups of the launch; otherwise two per CU */
+} MopaStarParams;
+int mopa_plan_star_batch(MopaScene *scene, const double *start_dev /*[E,nq]*/, const double *goal_dev /*[E,nq]*/, int64_t E,
+                         const MopaStarParams *params, double *path_dev /*[E,max_path,nq]*/, int32_t *path_len_dev /*[E]*/,
+                         int32_t *status_dev /*[E]*/, double *cost_dev /*[E] nullable*/, int64_t *info_dev /*[E,8] nullable*/,
+                         void *stream);
+/* the single-query host form of mopa_plan_star_batch (host pointers, stream id = env_id_base, synchronous) */
+int mopa_plan_star(MopaScene *scene, const double *start_host, const double *goal_host, const MopaStarParams *params,
+                   double *path_host /*[max_path,nq]*/, int32_t *path_len_out, int32_t *status_out, double *cost_out /*nullable*/,
+                   int64_t *info_out /*[8] nullable*/);
+/* k(n) of a scene with na active coordinates, computed on the host in double with libm's log (-1: na < 1 or n < 1) */
+int mopa_plan_star_k(int32_t na, int64_t n, double rewire_factor);
+int mopa_star_params_size(void);
+
 /* The rollout's invalid-target back-off (rl/mopa_rollouts.py:133-143) for E envs, asynchronous (no read-back unless E * num_trials
  * rows would exceed 1 GiB of scratch; E < 256: one wave per env walks its trials, otherwise all candidate rows of all
  * invalid targets go through one validity launch -- same results): while target[e] (a full

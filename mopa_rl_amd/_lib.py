@@ -26,7 +26,8 @@ EXPORTED_SYMBOLS = [
     "mopa_last_error", "mopa_version", "mopa_device_count", "mopa_scene_create", "mopa_scene_destroy",
     "mopa_scene_num_active", "mopa_scene_active_idx", "mopa_scene_num_pairs", "mopa_scene_lds_bytes", "mopa_scene_valid_kernel",
     "mopa_scene_k1_baked", "mopa_scene_k1_export", "mopa_scene_hdr_offset", "mopa_k1_baked_fk_host",
-    "mopa_is_valid_batch", "mopa_check_motion_batch", "mopa_plan_batch", "mopa_simplify_paths_batch", "mopa_simplify_paths_max_path", "mopa_shortcut_paths_batch", "mopa_shortcut_paths_max_path", "mopa_smooth_paths_batch", "mopa_smooth_paths_max_path", "mopa_pullback_batch", "mopa_is_valid_state", "mopa_plan",
+    "mopa_is_valid_batch", "mopa_check_motion_batch", "mopa_plan_batch", "mopa_simplify_paths_batch", "mopa_simplify_paths_max_path", "mopa_shortcut_paths_batch", "mopa_shortcut_paths_max_path", "mopa_smooth_paths_batch", "mopa_smooth_paths_max_path",
+    "mopa_plan_star_batch", "mopa_plan_star", "mopa_plan_star_k", "mopa_star_params_size", "mopa_pullback_batch", "mopa_is_valid_state", "mopa_plan",
     "mopa_planner_status", "mopa_debug_fk", "mopa_debug_pair_dist", "mopa_contacts_batch", "mopa_contacts_state",
     "mopa_env_create", "mopa_env_destroy", "mopa_env_obs_dim", "mopa_env_action_dim", "mopa_env_step_batch", "mopa_env_exec_batch", "mopa_env_desired_batch",
     "mopa_env_attach_dynamics", "mopa_env_attach_contacts", "mopa_env_set_contact_stats", "mopa_rollout_stage", "mopa_rollout_pool_pick", "mopa_rollout_step_size", "mopa_reuse_batch", "mopa_replay_append", "mopa_replay_sample", "mopa_ct_desc_size", "mopa_env_contact_arena", "mopa_env_dyn_dofs", "mopa_env_dyn_qvel_width", "mopa_env_dyn_forward_batch", "mopa_env_dyn_substeps_batch", "mopa_env_step_dyn_batch",
@@ -151,6 +152,17 @@ class MopaPlanParams(C.Structure):
                 ("resume_tree_q", C.c_void_p), ("resume_tree_p", C.c_void_p), ("resume_state", C.c_void_p)]
 
 
+class MopaStarParams(C.Structure):
+    """include/mopa_hip.h MopaStarParams (K3b RRT*)"""
+    _fields_ = [("max_iters", C.c_int32), ("max_nodes", C.c_int32), ("max_path", C.c_int32), ("seed", C.c_uint64),
+                ("env_id_base", C.c_uint64), ("env_ids_dev", C.c_void_p), ("seeds_dev", C.c_void_p), ("goal_bias", C.c_double),
+                ("goal_threshold", C.c_double), ("rewire_factor", C.c_double), ("max_workgroups", C.c_int32)]
+
+
+STAR_INFO_COLS = 8          # iterations run, nodes, motion checks, rewires, goal nodes, first goal iteration, descendant updates, full-tree iterations
+STAR_REWIRE_FACTOR = 1.1    # OMPL's default
+STAR_GOAL_BIAS = 0.05       # OMPL's default
+
 _lib: Optional[C.CDLL] = None
 
 
@@ -190,6 +202,11 @@ def lib() -> C.CDLL:
     L.mopa_shortcut_paths_max_path.argtypes = [vp]
     L.mopa_smooth_paths_batch.argtypes = [vp, C.c_int64, C.c_int32, vp, vp, vp, C.c_uint64, C.c_uint64, vp, vp, C.c_int32, C.c_int32, vp, vp]
     L.mopa_smooth_paths_max_path.argtypes = [vp]
+    L.mopa_plan_star_batch.argtypes = [vp, vp, vp, C.c_int64, C.POINTER(MopaStarParams), vp, vp, vp, vp, vp, vp]
+    L.mopa_plan_star.argtypes = [vp, _dp, _dp, C.POINTER(MopaStarParams), _dp, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                 C.POINTER(C.c_double), C.POINTER(C.c_int64)]
+    L.mopa_plan_star_k.argtypes = [C.c_int32, C.c_int64, C.c_double]
+    L.mopa_star_params_size.argtypes = []
     L.mopa_pullback_batch.argtypes = [vp, vp, vp, C.c_int64, C.c_double, C.c_int32, vp, vp, vp]
     L.mopa_is_valid_state.argtypes = [vp, _dp, C.POINTER(C.c_int32), _dp]
     L.mopa_plan.argtypes = [vp, _dp, _dp, C.POINTER(MopaPlanParams), _dp, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
@@ -467,6 +484,21 @@ class Scene:
         check(lib().mopa_plan(self._h, sp, gp, C.byref(prm), path.ctypes.data_as(_dp), C.byref(plen), C.byref(st),
                               C.byref(chk)))
         return st.value, path[:plen.value].copy(), chk.value
+
+    def plan_star(self, start, goal, max_iters: int, max_nodes: Optional[int] = None, max_path: int = 512, seed: Optional[int] = None,
+                  env_id: int = 0, goal_bias: float = STAR_GOAL_BIAS, goal_threshold: float = 0.0, rewire_factor: float = STAR_REWIRE_FACTOR):
+        """one RRT* query (K3b): -> (status, path rows, cost, info [8] int64); max_nodes=None: max_iters + 1"""
+        s, sp = _d(start)
+        g, gp = _d(goal)
+        nodes = int(max_iters) + 1 if max_nodes is None else int(max_nodes)
+        prm = MopaStarParams(int(max_iters), max(nodes, 2), int(max_path), int(self.seed if seed is None else seed) & 0xFFFFFFFFFFFFFFFF,
+                             int(env_id), None, None, float(goal_bias), float(goal_threshold), float(rewire_factor), 0)
+        path = np.zeros((max_path, self.nq))
+        info = np.zeros(STAR_INFO_COLS, dtype=np.int64)
+        plen, st, cost = C.c_int32(0), C.c_int32(0), C.c_double(0.0)
+        check(lib().mopa_plan_star(self._h, sp, gp, C.byref(prm), path.ctypes.data_as(_dp), C.byref(plen), C.byref(st), C.byref(cost),
+                                   info.ctypes.data_as(C.POINTER(C.c_int64))))
+        return st.value, path[:plen.value].copy(), cost.value, info
 
     def valid_kernel(self, n_states: int) -> str:
         """name of the validity kernel `mopa_is_valid_batch` dispatches for a batch of n_states"""

@@ -280,6 +280,55 @@ class BatchPlanner:
                                 passes=simplify_passes, stream=stream)
         return (path, plen, status, nchk, ps) if keep_state else (path, plen, status, nchk)
 
+    def plan_star(self, start, goal, max_iters: int = 2000, max_nodes: Optional[int] = None, max_path: int = 256, seed: int = 0,
+                  env_id_base: int = 0, stream=None, env_ids=None, seeds=None, max_workgroups: int = 0,
+                  goal_bias: float = _lib.STAR_GOAL_BIAS, goal_threshold: float = 0.0, rewire_factor: float = _lib.STAR_REWIRE_FACTOR,
+                  want_info: bool = False, vertex_simplify: bool = False, simplify_passes: int = 3, path_shortcut: bool = False,
+                  path_smooth: bool = False):
+        """E independent RRT* queries (K3b: the reference's planner_type "rrt"; DESIGN.md "K3b RRT*").  Returns (path [E, max_path,
+        nq], path_len [E], status [E], cost [E]) -- cost = the L1 length of the returned chain, +inf unless status is 0 -- and with
+        `want_info` a fifth element, an int64 [E, 8] tensor: iterations run, nodes, motion checks, rewires, goal nodes, first goal
+        iteration (-1: none), descendant cost updates, iterations that found the tree full.  The planner is anytime: every query
+        spends all of `max_iters`.  max_nodes=None: max_iters + 1, which no query can fill.  goal_threshold: a new state this close
+        to the goal (L1) is a goal node; 0 = the goal sample itself, drawn with probability `goal_bias` until one exists.
+        env_ids / seeds / env_id_base / seed / stream: as for `plan`.  max_workgroups > 0 caps the persistent workgroups.
+        vertex_simplify / simplify_passes / path_shortcut / path_smooth: exactly as in `plan`, the K9 launch goes behind this one on
+        the same stream with the same seed / ids / seeds (its draws are disjoint from the planner's); `cost` stays the planner's."""
+        torch = _torch()
+        _check_f64(start, "start", self.nq)
+        _check_f64(goal, "goal", self.nq)
+        E = start.shape[0]
+        dev = start.device
+        for t, name in ((env_ids, "env_ids"), (seeds, "seeds")):
+            if t is not None and (t.dtype != torch.int64 or not t.is_cuda or not t.is_contiguous() or tuple(t.shape) != (E,)):
+                raise _lib.MopaError(f"{name} must be a contiguous int64 GPU tensor of shape [E]")
+        nodes = int(max_iters) + 1 if max_nodes is None else int(max_nodes)
+
+        def alloc():
+            return (torch.zeros(E, max_path, self.nq, dtype=torch.float64, device=dev), torch.zeros(E, dtype=torch.int32, device=dev),
+                    torch.zeros(E, dtype=torch.int32, device=dev), torch.zeros(E, dtype=torch.float64, device=dev),
+                    torch.zeros(E, _lib.STAR_INFO_COLS, dtype=torch.int64, device=dev) if want_info else None)
+        if stream is not None:
+            with torch.cuda.stream(stream):
+                path, plen, status, cost, info = alloc()
+        else:
+            path, plen, status, cost, info = alloc()
+        prm = _lib.MopaStarParams(int(max_iters), max(nodes, 2), int(max_path), int(seed) & 0xFFFFFFFFFFFFFFFF, int(env_id_base),
+                                  _ptr(env_ids) if env_ids is not None else None, _ptr(seeds) if seeds is not None else None,
+                                  float(goal_bias), float(goal_threshold), float(rewire_factor), int(max_workgroups))
+        _lib.check(_lib.lib().mopa_plan_star_batch(self.scene.handle, _ptr(start), _ptr(goal), E, C.byref(prm), _ptr(path), _ptr(plen),
+                                                   _ptr(status), _ptr(cost), _ptr(info) if info is not None else None, _stream_handle(stream)))
+        if path_smooth:
+            self.smooth_paths(path, plen, status, seed=seed, env_id_base=env_id_base, env_ids=env_ids, seeds=seeds,
+                              passes=8 | (4 if path_shortcut else 0) | (int(simplify_passes) if vertex_simplify else 0), stream=stream)
+        elif path_shortcut:
+            self.shortcut_paths(path, plen, status, seed=seed, env_id_base=env_id_base, env_ids=env_ids, seeds=seeds,
+                                passes=4 | (int(simplify_passes) if vertex_simplify else 0), stream=stream)
+        elif vertex_simplify:
+            self.simplify_paths(path, plen, status, seed=seed, env_id_base=env_id_base, env_ids=env_ids, seeds=seeds,
+                                passes=simplify_passes, stream=stream)
+        return (path, plen, status, cost, info) if want_info else (path, plen, status, cost)
+
     def simplify_paths(self, path, plen, status=None, seed: int = 0, env_id_base: int = 0, env_ids=None, seeds=None, passes: int = 3,
                        stream=None, want_info: bool = False):
         """K9, in place: OMPL's reduceVertices (passes bit 0) and collapseCloseVertices (bit 1) over the planner's rows -- `path`

@@ -47,6 +47,7 @@ static void contacts_register_lds();        // defined with the contact report (
 static void simplify_register_lds();        // defined with K9 (mopa_simplify.inc)
 static void shortcut_register_lds();        // defined with K9 shortcutPath (mopa_shortcut.inc)
 static void smooth_register_lds();          // defined with K9 smoothBSpline (mopa_smooth.inc)
+static void star_register_lds();            // defined with K3b RRT* (mopa_rrtstar.inc)
 static void k1_register_lds();              // defined with the K1 kernel table (mopa_valid_launch.inc)
 
 extern "C" const char *mopa_last_error(void) { return g_err.c_str(); }
@@ -110,6 +111,9 @@ struct StreamScratch {
     DevBuf ip_walk;                                           // straight-line pre-check: walk states + verdicts (mopa_paths.inc)
     DevBuf pb_small, pb_rows, pb_act;                         // batched pull-back: verdicts / slots, candidate rows, their active coordinates + verdicts
     DevBuf ct_valid, ct_md, ct_ctr;                           // contact report (mopa_contacts.inc): stage 1's verdicts and depths, stage 2's chunk counter
+    DevBuf star_tree, star_k;                                 // RRT* (mopa_rrtstar.inc): one tree slab per wave of a launch, the table k(n)
+    int star_k_n = 0;                                         // entries of star_k, computed for rewire factor star_k_rf
+    double star_k_rf = 0.0;
 };
 
 // The scene's share of the K1 policy: filled once, by the last step of the scene compiler (mopa_scene_build.inc: SceneBuild::k1_policy);
@@ -675,6 +679,7 @@ extern "C" int mopa_scene_create(const MopaSceneDesc *desc, MopaScene **out) {
     simplify_register_lds();
     shortcut_register_lds();
     smooth_register_lds();
+    star_register_lds();
     *out = S;
     return MOPA_OK;
 }
@@ -688,7 +693,7 @@ extern "C" void mopa_scene_destroy(MopaScene *S) {
     for (auto &kv : S->scratch) {
         StreamScratch &sc = kv.second;
         for (DevBuf *b : {&sc.slab, &sc.mpr, &sc.cen, &sc.mesh_list, &sc.mesh_rows, &sc.mv_cnt, &sc.mv_off, &sc.mv_env, &sc.mv_q, &sc.mv_valid, &sc.mv_scan, &sc.plan_q,
-                          &sc.plan_p, &sc.plan_ctr, &sc.pb_small, &sc.pb_rows, &sc.pb_act, &sc.ip_walk, &sc.ct_valid, &sc.ct_md, &sc.ct_ctr})
+                          &sc.plan_p, &sc.plan_ctr, &sc.pb_small, &sc.pb_rows, &sc.pb_act, &sc.ip_walk, &sc.ct_valid, &sc.ct_md, &sc.ct_ctr, &sc.star_tree, &sc.star_k})
             if (b->p) (void)hipFree(b->p);
     }
     for (void *q : S->retired) (void)hipFree(q);
@@ -810,5 +815,7 @@ extern "C" const char *mopa_planner_status(const MopaScene *S) { return S ? S->s
 // pass the smoothing uses
 #include "mopa_shortcut.inc"
 #include "mopa_smooth.inc"
+// K3b: RRT*, the reference's other planner algorithm (k_rrt_star, mopa_plan_star_batch); k_simplify_paths' shape
+#include "mopa_rrtstar.inc"
 #include "mopa_ik.inc"
 #include "mopa_paths.inc"

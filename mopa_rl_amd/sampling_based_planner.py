@@ -32,6 +32,7 @@ class SamplingBasedPlanner:
                  simplified_duration=0.1, range_=None, vertex_simplify=False, path_shortcut=False, path_smooth=False):
         self.config = config
         self.non_limited_idx = non_limited_idx
+        # planner_type: "rrt_connect", or "rrt_star" for RRT* (K3b; what the reference's configs call "rrt", a name that keeps raising here)
         algo = config.planner_type if planner_type is None else planner_type
         step = config.range if range_ is None else range_
         enc = lambda text: text.encode("utf-8")
