@@ -424,6 +424,18 @@ def ik_targets_torch(site_pos, site_mat, ac, action_range, world_lo, world_hi):
     return target_cart, target_quat
 
 
+def sit_out_action(ac, alive, use_ik_target: bool):
+    """The action `run_episode` hands to `agent_step`: the policy's rows for the envs still in their episode, a neutral row for the
+    envs that sit out.  Neutral is all zeros -- except, with `use_ik_target`, the rotation entries ac[3:7]: `k_ik_targets` divides them
+    by their norm as the reference does (rl/mopa_rollouts.py:696), so they are the identity quaternion (1, 0, 0, 0); a zero row would
+    make the IK target, the joint displacement and from there `env.qpos` of the env NaN."""
+    torch = _torch()
+    neutral = torch.zeros_like(ac, dtype=torch.float64)
+    if use_ik_target:
+        neutral[:, 3] = 1.0
+    return torch.where(alive[:, None], ac.to(torch.float64), neutral).contiguous()
+
+
 class BatchMoPARollout:
     def reuse_transitions(self, out, rng, max_reuse_data: int = 30):
         """`reuse_transitions` on a recorded step of this rollout, with the env's gripper joint supplied where its action has
@@ -1648,8 +1660,10 @@ class BatchMoPARollout:
     def run_episode(self, policy, max_step: int = 10000, is_train: bool = True, random_exploration: bool = False, reset: bool = True):
         """`MoPARolloutRunner.run_episode` (reference rl/mopa_rollouts.py:401-678: the evaluation loop -- ONE episode, `while not done
         and ep_len < max_step`, every agent step the same routing as `run`) for all E envs at once: each env runs one episode from
-        `env.reset()` (`reset=False`: from the state the env is in) and sits out once its episode is over (it gets the zero action
-        and nothing of it is recorded any more).  Lock-step only: a call is one agent step of every env still in its episode.
+        `env.reset()` (`reset=False`: from the state the env is in) and sits out once its episode is over: it gets the neutral action
+        of `sit_out_action`, nothing of it is recorded any more, and after every call it is put back into the state its episode ended
+        in -- when the loop returns, `env.qpos` is `qpos_final` and `env.obs` the final obs of every env.  Lock-step only: a call is one
+        agent step of every env still in its episode.
 
         policy(ob [E, obs_dim], is_train=..., random_exploration=...) -> ac [E, >= ac_dim] (float64, in [-1, 1]; with
         `discrete_action` a pair (ac, ac_type [E])) -- the batched `pi.act` (:432-437).
@@ -1690,7 +1704,7 @@ class BatchMoPARollout:
             while True:
                 got = policy(env.obs.clone(), is_train=is_train, random_exploration=random_exploration)
                 ac, ac_type = got if cfg.discrete_action else (got, None)
-                ac = torch.where(alive[:, None], ac.to(torch.float64), torch.zeros_like(ac, dtype=torch.float64)).contiguous()
+                ac = sit_out_action(ac, alive, cfg.use_ik_target)
                 if ac_type is not None:
                     ac_type = torch.where(alive, ac_type.reshape(-1).to(torch.int64), torch.zeros(E, dtype=torch.int64, device=dev))
                 before = {k: self.counters[k].clone() for k in COUNTERS}
@@ -1709,6 +1723,10 @@ class BatchMoPARollout:
                 valids.append(alive.clone())
                 last_ob = torch.where(alive[:, None], out["ob_next"], last_ob)
                 last_q = torch.where(alive[:, None], env.qpos, last_q)
+                # (the step a sitting-out env took with its neutral action is undone: with `use_ik_target` that action still moves the arm --
+                #  the IK aims at the [3, 0, 1, 1]-indexed site quaternion --, and a drifting env could end up anywhere)
+                env.qpos.copy_(last_q)
+                env.obs.copy_(last_ob)
                 alive = alive & ~(out["done"].bool() | (ep_len >= max_step))
                 if not bool(alive.any()):         # (one host read per agent step: this is the evaluation loop, not the training one)
                     break

@@ -606,29 +606,75 @@ def test_pool_pick_kernel_equals_nonzero_and_gathers():
             assert torch.equal(m2, mask) and bool((ids == -1).all())
 
 
-@pytest.mark.parametrize("env_name,tag", [("SawyerPushObstacle-v0", "push"), ("SawyerLiftObstacle-v0", "lift")])
-def test_run_episode_equals_reference_evaluation_loop(env_name, tag):
-    """`BatchMoPARollout.run_episode` against the REFERENCE'S OWN `MoPARolloutRunner.run_episode` (rl/mopa_rollouts.py:401-678), run
-    in the build container env by env on the same scripted actions from the same start states (tests/golden/ref_py_episode_*.npz,
-    tools/gen_ref_py_golden.py `episode`): whole episodes, free-running -- nothing is re-loaded between agent steps.  Agent steps per
-    episode, episode length, the six counters, done flags and success must be identical; per-step rewards (plain sums over a path's
-    waypoints, not the SMDP return) and the episode reward agree to round-off; the final joint state is identical bit for bit in
-    episodes without an invalid-target back-off and to 1e-12 in the others (see _check_qpos)."""
+def _episode_policy(G, env, discrete=False):
+    """the fixture's scripted actions as the batched `pi.act` of `run_episode` (zeros once they are used up), and its call counter"""
     import torch
-    from mopa_rl_amd.rollout import COUNTERS
-    G = np.load(os.path.join(GOLD, f"ref_py_episode_{tag}.npz"))
-    E, T = G["ac"].shape[:2]
-    env, ro = _make(G, E, env_name)
-    _load_state(env, G["qpos_start"][:, 0], np.zeros(E, dtype=np.int64))
     AC = torch.tensor(G["ac"], device=env.device)
+    TY = torch.tensor(G["ac_type"], device=env.device) if discrete else None
+    T = AC.shape[1]
     calls = {"t": 0}
 
     def policy(ob, is_train=True, random_exploration=False):
         t = calls["t"]
         calls["t"] += 1
         assert is_train and not random_exploration
-        return AC[:, t] if t < T else torch.zeros_like(AC[:, 0])
+        assert bool(torch.isfinite(ob).all()), f"call {t}: the policy is shown a non-finite obs"
+        ac = AC[:, t] if t < T else torch.zeros_like(AC[:, 0])
+        if not discrete:
+            return ac
+        return ac, (TY[:, t] if t < T else torch.zeros_like(TY[:, 0]))
 
+    return policy, calls
+
+
+def _check_state_after_episode(G, env_name, kw, env, ro, rollout, info):
+    """What `run_episode` leaves behind.  Its outputs are masked by `alive`, so they cannot show what became of the envs that sat out;
+    the env's own state can: every env is in the state its episode ended in -- finite --, every returned tensor is finite, and a second
+    episode on the same objects (`reset=True`) is, bit for bit, the first episode of fresh objects at the same seed and step count."""
+    import torch
+    from mopa_rl_amd.rollout import COUNTERS
+    E = env.qpos.shape[0]
+    assert bool(torch.isfinite(env.qpos).all()), "env.qpos after the episode loop"
+    assert bool(torch.isfinite(env.obs).all()), "env.obs after the episode loop"
+    for name, d in (("rollout", rollout), ("ep_info", info)):
+        for k, v in d.items():
+            assert bool(torch.isfinite(v.to(torch.float64)).all()), f"{name}[{k}]"
+    assert torch.equal(env.qpos, rollout["qpos_final"]), "a sitting-out env left the state its episode ended in"
+    assert torch.equal(env.obs, rollout["ob"][rollout["n_steps"], torch.arange(E, device=env.device)])
+    assert not bool(ro.busy.any())
+    discrete = bool(kw.get("discrete_action"))
+    t0 = ro.t
+    again, info_a = ro.run_episode(_episode_policy(G, env, discrete)[0], reset=True)
+    env_f, ro_f = _make(G, E, env_name, **kw)
+    ro_f.t = t0
+    fresh, info_f = ro_f.run_episode(_episode_policy(G, env_f, discrete)[0], reset=True)
+    assert torch.equal(again["n_steps"], fresh["n_steps"]) and torch.equal(info_a["len"], info_f["len"])
+    for k in COUNTERS:
+        assert torch.equal(info_a[k], info_f[k]), k
+    assert np.array_equal(_bits(again["qpos_final"].cpu().numpy()), _bits(fresh["qpos_final"].cpu().numpy()))
+    assert bool(torch.isfinite(env.qpos).all()) and bool(torch.isfinite(env.obs).all())
+    env_f.close(); ro_f.close()
+
+
+@pytest.mark.parametrize("env_name,tag", [("SawyerPushObstacle-v0", "push"), ("SawyerLiftObstacle-v0", "lift"),
+                                          ("SawyerPushObstacle-v0", "push_discrete")])
+def test_run_episode_equals_reference_evaluation_loop(env_name, tag):
+    """`BatchMoPARollout.run_episode` against the REFERENCE'S OWN `MoPARolloutRunner.run_episode` (rl/mopa_rollouts.py:401-678), run
+    in the build container env by env on the same scripted actions from the same start states (tests/golden/ref_py_episode_*.npz,
+    tools/gen_ref_py_golden.py `episode`): whole episodes, free-running -- nothing is re-loaded between agent steps.  Agent steps per
+    episode, episode length, the six counters, done flags and success must be identical; per-step rewards (plain sums over a path's
+    waypoints, not the SMDP return) and the episode reward agree to round-off; the final joint state is identical bit for bit in
+    episodes without an invalid-target back-off and to 1e-12 in the others (see _check_qpos).
+    `push_discrete`: the same loop under `discrete_action` (the policy returns (ac, ac_type); the head routes the step and direct
+    actions are not rescaled, :458-459,:631-634), episodes of 2 to 11 agent steps.  Then, for the discrete run and the joint-space Push
+    run, what the loop leaves behind (_check_state_after_episode)."""
+    from mopa_rl_amd.rollout import COUNTERS
+    G = np.load(os.path.join(GOLD, f"ref_py_episode_{tag}.npz"))
+    E, T = G["ac"].shape[:2]
+    kw = {"discrete_action": True} if tag.endswith("_discrete") else {}
+    env, ro = _make(G, E, env_name, **kw)
+    _load_state(env, G["qpos_start"][:, 0], np.zeros(E, dtype=np.int64))
+    policy, calls = _episode_policy(G, env, bool(kw))
     gamma = ro.cfg.discount_factor
     rollout, info = ro.run_episode(policy, reset=False)
     assert ro.cfg.discount_factor == gamma                      # (the loop sums rewards undiscounted and restores the SMDP discount)
@@ -650,4 +696,62 @@ def test_run_episode_equals_reference_evaluation_loop(env_name, tag):
     ob = rollout["ob"].cpu().numpy()                             # [Tn + 1, E, obs_dim]
     np.testing.assert_allclose(ob[:Tn].transpose(1, 0, 2)[valid], G["ob"][:, :Tn][valid], rtol=1e-12, atol=1e-12, err_msg="obs before each step")
     np.testing.assert_allclose(ob[n, np.arange(E)], G["ob_final"], rtol=1e-12, atol=1e-12, err_msg="final obs")
+    if tag in ("push", "push_discrete"):
+        _check_state_after_episode(G, env_name, kw, env, ro, rollout, info)
+    env.close(); ro.close()
+
+
+# max |deviation| from the reference's episode, measured on an MI355X (see the docstring below), times 4, rounded up to one significant digit
+IK_EPISODE_ATOL = {"qpos_final": 3e-8, "ob": 3e-8, "rew": 8e-9, "ep_rew": 3e-8}
+
+
+def test_run_episode_with_ik_targets_equals_reference_evaluation_loop():
+    """`run_episode` under BASELINE config 5's action space (`use_ik_target`, SawyerAssemblyObstacle) against the reference's own
+    `run_episode` (tests/golden/ref_py_episode_assembly_ik.npz): 16 envs started from the fixture's joint states and episode counters
+    (`ep_len_start` = 0 / 3 / 6 / 9: the time cap ends them after 14, 11, 8 or 5 env steps), eight of them over the hole, which they
+    reach -- success -- after 1 to 4 agent steps, two of those in the middle of a planner path; episodes take 1 to 8 agent steps, so in
+    most calls of the batched loop most envs sit out (tests/test_ref_py_episode.py asserts all this of the fixture).
+    Identical: agent steps per episode, episode length, the six counters, the valid mask, done flags, success.
+    Joint states, obs and rewards cannot be: the reference takes the IK's orientation target from an eigen-decomposition of a float32
+    rotation matrix, the batched form from the closed-form quaternion of the same matrix (see
+    test_ik_action_space_rollout_equals_reference_runner, which re-loads the state every step and needs 2e-6 / 1e-5); here the run is
+    free and the difference compounds over an episode.  Measured max |deviation| on an MI355X:
+        qpos_final 7.193e-09   ob 7.193e-09   rew 1.926e-09   ep_rew 5.278e-09
+    (below the per-step test's bounds: those allow for the solver stopping an iteration apart, which no step of this fixture does).
+    Then what the loop leaves behind (_check_state_after_episode): with the all-zero action that finished envs used to get, the IK's
+    target quaternion, the joint displacement and `env.qpos` of every such env were NaN."""
+    from mopa_rl_amd.rollout import COUNTERS
+    env_name, kw = "SawyerAssemblyObstacle-v0", {"use_ik_target": True}
+    G = np.load(os.path.join(GOLD, "ref_py_episode_assembly_ik.npz"))
+    E, T = G["ac"].shape[:2]
+    env, ro = _make(G, E, env_name, **kw)
+    assert ro.ac_dim == 7
+    _load_state(env, G["qpos_start"][:, 0], G["ep_len_start"])
+    policy, calls = _episode_policy(G, env)
+    rollout, info = ro.run_episode(policy, reset=False)
+    n = G["n_steps"]
+    valid = rollout["valid"].cpu().numpy().T                     # [E, Tn]
+    Tn = valid.shape[1]
+    ob = rollout["ob"].cpu().numpy()                             # [Tn + 1, E, obs_dim]
+    same_shape = Tn == int(n.max()) and np.array_equal(valid, np.arange(Tn)[None, :] < n[:, None])
+    if same_shape:
+        dev = {"qpos_final": np.abs(rollout["qpos_final"].cpu().numpy() - G["qpos_final"]).max(),
+               "ob": max(np.abs(ob[:Tn].transpose(1, 0, 2)[valid] - G["ob"][:, :Tn][valid]).max(), np.abs(ob[n, np.arange(E)] - G["ob_final"]).max()),
+               "rew": np.abs(rollout["rew"].cpu().numpy().T[valid] - G["rew"][:, :Tn][valid]).max(),
+               "ep_rew": np.abs(info["rew"].cpu().numpy() - G["ep_rew"]).max()}
+        print("run_episode, use_ik_target: max |deviation| from the reference:", {k: f"{v:.3e}" for k, v in dev.items()})
+    assert np.array_equal(rollout["n_steps"].cpu().numpy(), n), "agent steps per episode"
+    assert calls["t"] == int(n.max()) and same_shape
+    assert np.array_equal(info["len"].cpu().numpy(), G["ep_len"]), "episode length"
+    assert np.array_equal(np.stack([info[k].cpu().numpy() for k in COUNTERS], axis=1), G["counters"]), "counters"
+    assert np.array_equal(rollout["done"].cpu().numpy().T.astype(np.int64)[valid], G["done"][:, :Tn][valid]), "done flags"
+    assert np.array_equal(info["success"].cpu().numpy().astype(np.int64), G["ep_success"]), "success"
+    assert G["ep_success"].sum() >= 2 and (G["ep_len"][G["ep_success"] == 1] < 14 - G["ep_len_start"][G["ep_success"] == 1]).all()
+    tol = IK_EPISODE_ATOL
+    np.testing.assert_allclose(rollout["qpos_final"].cpu().numpy(), G["qpos_final"], rtol=0, atol=tol["qpos_final"], err_msg="final joint state")
+    np.testing.assert_allclose(ob[:Tn].transpose(1, 0, 2)[valid], G["ob"][:, :Tn][valid], rtol=0, atol=tol["ob"], err_msg="obs before each step")
+    np.testing.assert_allclose(ob[n, np.arange(E)], G["ob_final"], rtol=0, atol=tol["ob"], err_msg="final obs")
+    np.testing.assert_allclose(rollout["rew"].cpu().numpy().T[valid], G["rew"][:, :Tn][valid], rtol=0, atol=tol["rew"], err_msg="per-step rewards")
+    np.testing.assert_allclose(info["rew"].cpu().numpy(), G["ep_rew"], rtol=0, atol=tol["ep_rew"], err_msg="episode reward")
+    _check_state_after_episode(G, env_name, kw, env, ro, rollout, info)
     env.close(); ro.close()

@@ -540,36 +540,76 @@ def gen_rollout(env_name="SawyerPushObstacle-v0", tag="push", E=32, T=5, reuse=F
 # ------------------------------------------------------------------------------------------------------------------
 # section "episode": rl/mopa_rollouts.py:MoPARolloutRunner.run_episode (the evaluation loop, :401-678), env by env, scripted actions
 # ------------------------------------------------------------------------------------------------------------------
-def gen_episode(env_name="SawyerPushObstacle-v0", tag="push", E=24, discrete=False):
+def gen_episode(env_name="SawyerPushObstacle-v0", tag="push", E=24, discrete=False, ik=False):
     """One whole episode per env through the reference's `run_episode` (max_step 10000, is_train=True): what it returns -- the rollout's
     rew / done lists, ep_info's len / rew / counters / episode_success -- plus the joint state at every policy call and at the end.
-    `get_contact_force` (MuJoCo's contact solver, env/base.py:568) is set to 0: no kinematic counterpart."""
+    `get_contact_force` (MuJoCo's contact solver, env/base.py:568) is set to 0: no kinematic counterpart.
+
+    ik=True: the MoPA + IK action space (`use_ik_target`, wired as in gen_rollout).  Its episodes are made unequal: env e starts with
+    `_episode_length` = 3 (e % 4) (recorded as `ep_len_start`), so the time cap ends it after 14, 11, 8 or 5 env steps; and the envs of
+    IK_HOLE_ENVS start with the peg head a few centimetres above the hole's bottom (gen_env's recipe: the reference's own IK aims the grip
+    site) and are driven down into it, so that their episode ends on `episode_success` before the cap; those of IK_INSIDE_ENVS start
+    within the success distance, so that their first step -- the first waypoint of a planner path -- ends it."""
     import util.env as ref_util_env
     from rl.mopa_rollouts import MoPARolloutRunner
     ref_util_env.np = refshim.NumpyCompat()
     P = ROLLOUT_PARAMS
-    cfg = make_config(env_name, timelimit=P["timelimit"], num_trials=P["num_trials"], discrete_action=discrete, stochastic_eval=False)
+    cfg = make_config(env_name, timelimit=P["timelimit"], num_trials=P["num_trials"], discrete_action=discrete, stochastic_eval=False,
+                      use_ik_target=ik)
     n_ac = 8 if env_name == "SawyerLiftObstacle-v0" else 7
     agent, pi = make_agent(env_name, cfg, ac_dim=n_ac)
     st = Streams(agent, E, P["seed"], P["max_nodes"], P["max_path"])
     rng = np.random.default_rng(23)
     T = P["max_episode_steps"]                      # an agent step takes at least one env step
-    AC = rng.uniform(-1, 1, size=(E, T, n_ac)) * rng.choice([0.5, 0.68, 0.9, 1.0], size=(E, T, 1))
-    AC[: E // 3, 1::3, 1] = 1.0                     # far targets towards the table / bin: blocked lines, invalid targets, failed plans
-    AC[: E // 3, 1::3, 3] = -1.0
+    if ik:
+        from env.inverse_kinematics import qpos_from_site_pose
+        # gen_rollout's recipe: Cartesian displacement (3) + rotation quaternion (4) in [-1, 1]
+        AC = rng.uniform(-1, 1, size=(E, T, 7))
+        AC[:, :, :3] *= rng.choice([0.05, 0.3, 1.0], size=(E, T, 1))
+        AC[:, :, 3] = np.abs(AC[:, :, 3]) + 0.5
+        AC[: E // 4, :, 3:] = rng.uniform(-1, 1, size=(E // 4, T, 4))
+        hole_rng = np.random.default_rng(29)
+    else:
+        AC = rng.uniform(-1, 1, size=(E, T, n_ac)) * rng.choice([0.5, 0.68, 0.9, 1.0], size=(E, T, 1))
+        AC[: E // 3, 1::3, 1] = 1.0                     # far targets towards the table / bin: blocked lines, invalid targets, failed plans
+        AC[: E // 3, 1::3, 3] = -1.0
     AC_TYPE = rng.integers(0, 2, size=(E, T)) if discrete else None
     nq = pi.model.nq
     out = dict(ac=AC, qpos_start=np.zeros((E, T, nq)), qpos_final=np.zeros((E, nq)), n_steps=np.zeros(E, dtype=np.int64),
                rew=np.zeros((E, T)), done=np.zeros((E, T), dtype=np.int64), pulled_back=np.zeros((E, T), dtype=np.int64),
                ep_len=np.zeros(E, dtype=np.int64), ep_rew=np.zeros(E), ep_success=np.zeros(E, dtype=np.int64),
                counters=np.zeros((E, len(COUNTERS)), dtype=np.int64), ob=None, ob_final=None)
+    if ik:
+        out["ep_len_start"] = np.zeros(E, dtype=np.int64)
     for e in range(E):
         env = make_ref_env(env_name, seed=300 + e, max_episode_steps=P["max_episode_steps"])
         env.get_contact_force = lambda: 0.0
         env.color_agent = env.reset_color_agent = lambda: None          # geom_rgba only (rendering)
         state = {"t": -1}
+        at_hole, inside = ik and e in IK_HOLE_ENVS, ik and e in IK_INSIDE_ENVS
+        if ik:
+            def reset_staggered(env=env, e=e, over_hole=at_hole or inside, inside=inside, orig=env.reset):
+                orig()
+                if over_hole:
+                    # peg upright (its axis along world z, head down: the hole opens upwards), turned so that the arm clears the furniture's
+                    # legs, head on the hole's axis a few centimetres above its bottom: a state the validity check accepts
+                    d, mul = env.sim.data, refshim.mju_mulQuat
+                    conj = np.array([1.0, -1.0, -1.0, -1.0])
+                    q_site, q_rel, q_tgt = np.zeros(4), np.zeros(4), np.zeros(4)
+                    refshim.mju_mat2Quat(q_site, np.array(d.get_site_xmat("grip_site"), dtype=np.float64).ravel())
+                    mul(q_rel, q_site * conj, np.array(d.body_xquat[env.sim.model.body_name2id("peg")], dtype=np.float64))
+                    mul(q_tgt, np.array([np.sqrt(0.5), 0.0, 0.0, -np.sqrt(0.5)]), q_rel * conj)
+                    above = np.array([0.0, 0.0, 0.01 if inside else hole_rng.uniform(0.04, 0.075)]) + hole_rng.normal(0, 0.001, 3)
+                    for _ in range(8):      # (a few restarts: re-aim the grip site at the head's remaining offset)
+                        tgt = d.get_site_xpos("grip_site") + (d.get_site_xpos("hole_bottom") + above - d.get_site_xpos("pegHead"))
+                        qpos_from_site_pose(env, "grip_site", target_pos=tgt, target_quat=q_tgt, joint_names=env.robot_joints, max_steps=100, tol=1e-4)
+                    assert agent.isValidState(d.qpos.copy())
+                env._episode_length = 3 * (e % 4)
+                out["ep_len_start"][e] = env._episode_length
+                return env._get_obs()
+            env.reset = reset_staggered
 
-        def act(ob, is_train=True, return_stds=False, random_exploration=False, e=e, env=env, state=state):
+        def act(ob, is_train=True, return_stds=False, random_exploration=False, e=e, env=env, state=state, at_hole=at_hole):
             state["t"] += 1
             t = state["t"]
             st.begin(e, t)
@@ -578,6 +618,22 @@ def gen_episode(env_name="SawyerPushObstacle-v0", tag="push", E=24, discrete=Fal
             if out["ob"] is None:
                 out["ob"], out["ob_final"] = np.zeros((E, T, len(fo))), np.zeros((E, len(fo)))
             out["ob"][e, t] = fo
+            if ik:
+                if at_hole:
+                    # a scripted closed loop, recorded in `ac` like every other action: straight towards the hole's bottom, with the rotation
+                    # that undoes the runner's [3, 0, 1, 1] indexing of the site quaternion (so that the IK holds the orientation and its joint
+                    # displacement stays a direct action)
+                    d = env.sim.data
+                    to_go = d.get_site_xpos("hole_bottom") - d.get_site_xpos("pegHead")
+                    AC[e, t, :3] = to_go * min(IK_HOLE_GAIN, IK_HOLE_REACH / np.linalg.norm(to_go)) / cfg.action_range
+                    cur = np.zeros(4)
+                    refshim.mju_mat2Quat(cur, np.array(d.get_site_xmat("grip_site"), dtype=np.float64).ravel())
+                    scr = ref_util_env.mat2quat(d.get_site_xmat("grip_site"))[[3, 0, 1, 1]].astype(np.float64)
+                    inv = scr * np.array([1.0, -1.0, -1.0, -1.0])
+                    q = np.zeros(4)
+                    refshim.mju_mulQuat(q, inv, cur)
+                    AC[e, t, 3:] = q / np.abs(q).max()
+                return OrderedDict([("default", AC[e, t, :3].copy()), ("quat", AC[e, t, 3:].copy())]), None, None
             a = OrderedDict(default=AC[e, t].copy())
             if discrete:
                 a["ac_type"] = np.array([int(AC_TYPE[e, t])])
@@ -592,6 +648,8 @@ def gen_episode(env_name="SawyerPushObstacle-v0", tag="push", E=24, discrete=Fal
         agent.act = act
         runner = object.__new__(MoPARolloutRunner)
         runner._config, runner._env, runner._env_eval, runner._pi, runner._ik_env = cfg, env, None, agent, None
+        if ik:
+            runner._ik_env = make_ref_env(env_name, seed=900 + e, max_episode_steps=P["max_episode_steps"])
         rollout, info, _frames = runner.run_episode(max_step=10000, is_train=True, record=False)
         n = state["t"] + 1
         # (the evaluation loop adds ob / ac to its rollout for planner steps only, :577-585 vs :648-653: the lists of rew / done are complete)
@@ -604,16 +662,29 @@ def gen_episode(env_name="SawyerPushObstacle-v0", tag="push", E=24, discrete=Fal
         out["ep_success"][e] = int(info.get("episode_success", 0))
         out["counters"][e] = [info[k] for k in COUNTERS]
     print(f"  episode[{tag}]: agent steps / episode", out["n_steps"].tolist(), "len", out["ep_len"].tolist(), "counters",
-          dict(zip(COUNTERS, out["counters"].sum(0).tolist())), "success", int(out["ep_success"].sum()), "pulled back", int(out["pulled_back"].sum()))
+          dict(zip(COUNTERS, out["counters"].sum(0).tolist())), "success", out["ep_success"].tolist() if ik else int(out["ep_success"].sum()),
+          "pulled back", int(out["pulled_back"].sum()))
     if discrete:
         out["ac_type"] = AC_TYPE
-    save(f"ref_py_episode_{tag}{'_discrete' if discrete else ''}.npz",
+    save(f"ref_py_episode_{tag}{'_ik' if ik else ''}{'_discrete' if discrete else ''}.npz",
          params=np.array([P["timelimit"], P["max_nodes"], P["max_path"], P["seed"], P["max_episode_steps"], P["num_trials"]]), **out)
+
+
+# the Assembly + IK episode: the envs that start above the hole and are driven into it, and the drive -- a direct step executes ac_scale / omega of
+# the IK's joint displacement, so the action asks for several times the remaining offset, up to a reach whose joint displacement stays below omega
+# (a larger one would be a planner action: with this action space a zero-length path, rl/mopa_rollouts.py:483) --; and the envs that start with
+# the head already within the success distance of the hole's bottom, on the recipe's actions: whatever their first step is, it ends the
+# episode -- a planner step after the first of its two waypoints
+IK_HOLE_ENVS = (0, 2, 5, 7, 8, 13)
+IK_INSIDE_ENVS = (10, 15)
+IK_HOLE_GAIN, IK_HOLE_REACH = 6.0, 0.2
 
 
 def gen_episodes():
     gen_episode()
     gen_episode("SawyerLiftObstacle-v0", "lift", E=16)
+    gen_episode("SawyerAssemblyObstacle-v0", "assembly", E=16, ik=True)
+    gen_episode(E=16, discrete=True)
 
 
 # ------------------------------------------------------------------------------------------------------------------
