@@ -121,6 +121,20 @@ def pair_geom_ids(model, pair) -> np.ndarray:
     return out
 
 
+def k9_passes(vertex_simplify, simplify_passes, path_shortcut, path_smooth) -> int:
+    """The passes word of the K9 launch that the flags of `plan` select (bit 0 reduceVertices, bit 1 collapseCloseVertices, bit 2
+    shortcutPath, bit 3 smoothBSpline); 0: no K9 launch."""
+    vertex = int(simplify_passes) if vertex_simplify else 0
+    if path_smooth:
+        return 8 | (4 if path_shortcut else 0) | vertex
+    return (4 if path_shortcut else 0) | vertex
+
+
+def k9_entry(vertex_simplify, path_shortcut, path_smooth) -> Optional[str]:
+    """The `BatchPlanner` method that takes that word: the kernel of the highest stage asked for; None when all flags are off."""
+    return "smooth_paths" if path_smooth else "shortcut_paths" if path_shortcut else "simplify_paths" if vertex_simplify else None
+
+
 class BatchPlanner:
     """N-state validity / motion checks and E-env RRT-Connect on one GPU."""
 
@@ -269,15 +283,7 @@ class BatchPlanner:
         if resume is not None and stream is not None:
             for t in (resume.tree_q, resume.tree_p, resume.state):
                 t.record_stream(stream)
-        if path_smooth:
-            self.smooth_paths(path, plen, status, seed=seed, env_id_base=env_id_base, env_ids=env_ids, seeds=seeds,
-                              passes=8 | (4 if path_shortcut else 0) | (int(simplify_passes) if vertex_simplify else 0), stream=stream)
-        elif path_shortcut:
-            self.shortcut_paths(path, plen, status, seed=seed, env_id_base=env_id_base, env_ids=env_ids, seeds=seeds,
-                                passes=4 | (int(simplify_passes) if vertex_simplify else 0), stream=stream)
-        elif vertex_simplify:
-            self.simplify_paths(path, plen, status, seed=seed, env_id_base=env_id_base, env_ids=env_ids, seeds=seeds,
-                                passes=simplify_passes, stream=stream)
+        self._k9_behind(path, plen, status, seed, env_id_base, env_ids, seeds, vertex_simplify, simplify_passes, path_shortcut, path_smooth, stream)
         return (path, plen, status, nchk, ps) if keep_state else (path, plen, status, nchk)
 
     def plan_star(self, start, goal, max_iters: int = 2000, max_nodes: Optional[int] = None, max_path: int = 256, seed: int = 0,
@@ -318,15 +324,7 @@ class BatchPlanner:
                                   float(goal_bias), float(goal_threshold), float(rewire_factor), int(max_workgroups))
         _lib.check(_lib.lib().mopa_plan_star_batch(self.scene.handle, _ptr(start), _ptr(goal), E, C.byref(prm), _ptr(path), _ptr(plen),
                                                    _ptr(status), _ptr(cost), _ptr(info) if info is not None else None, _stream_handle(stream)))
-        if path_smooth:
-            self.smooth_paths(path, plen, status, seed=seed, env_id_base=env_id_base, env_ids=env_ids, seeds=seeds,
-                              passes=8 | (4 if path_shortcut else 0) | (int(simplify_passes) if vertex_simplify else 0), stream=stream)
-        elif path_shortcut:
-            self.shortcut_paths(path, plen, status, seed=seed, env_id_base=env_id_base, env_ids=env_ids, seeds=seeds,
-                                passes=4 | (int(simplify_passes) if vertex_simplify else 0), stream=stream)
-        elif vertex_simplify:
-            self.simplify_paths(path, plen, status, seed=seed, env_id_base=env_id_base, env_ids=env_ids, seeds=seeds,
-                                passes=simplify_passes, stream=stream)
+        self._k9_behind(path, plen, status, seed, env_id_base, env_ids, seeds, vertex_simplify, simplify_passes, path_shortcut, path_smooth, stream)
         return (path, plen, status, cost, info) if want_info else (path, plen, status, cost)
 
     def simplify_paths(self, path, plen, status=None, seed: int = 0, env_id_base: int = 0, env_ids=None, seeds=None, passes: int = 3,
@@ -338,28 +336,8 @@ class BatchPlanner:
         `plan` was given (the draws come from the planner's sample stream of the query, at counters from 2^63 on).  shortcutPath,
         B-spline smoothing and checkAndRepair of OMPL's simplify() are not built.  Returns None, or with `want_info` an int64
         [E, 2] tensor: motion checks made, draws consumed (0 for untouched paths)."""
-        torch = _torch()
-        if path.dtype != torch.float64 or not path.is_cuda or not path.is_contiguous() or path.dim() != 3 or path.shape[2] != self.nq:
-            raise _lib.MopaError(f"path must be a contiguous float64 GPU tensor of shape [E, max_path, {self.nq}]")
-        E, max_path = int(path.shape[0]), int(path.shape[1])
-        for t, name in ((plen, "plen"), (status, "status")):
-            if t is not None and (t.dtype != torch.int32 or not t.is_cuda or not t.is_contiguous() or tuple(t.shape) != (E,)):
-                raise _lib.MopaError(f"{name} must be a contiguous int32 GPU tensor of shape [E]")
-        for t, name in ((env_ids, "env_ids"), (seeds, "seeds")):
-            if t is not None and (t.dtype != torch.int64 or not t.is_cuda or not t.is_contiguous() or tuple(t.shape) != (E,)):
-                raise _lib.MopaError(f"{name} must be a contiguous int64 GPU tensor of shape [E]")
-        info = None
-        if want_info:
-            if stream is not None:
-                with torch.cuda.stream(stream):
-                    info = torch.zeros(E, 2, dtype=torch.int64, device=path.device)
-            else:
-                info = torch.zeros(E, 2, dtype=torch.int64, device=path.device)
-        _lib.check(_lib.lib().mopa_simplify_paths_batch(
-            self.scene.handle, E, max_path, _ptr(path), _ptr(plen), _ptr(status) if status is not None else None,
-            int(seed) & 0xFFFFFFFFFFFFFFFF, int(env_id_base), _ptr(env_ids) if env_ids is not None else None,
-            _ptr(seeds) if seeds is not None else None, int(passes), _ptr(info) if info is not None else None, _stream_handle(stream)))
-        return info
+        return self._k9_rows_launch(_lib.lib().mopa_simplify_paths_batch, 2, path, plen, status, seed, env_id_base, env_ids, seeds, passes, None,
+                                    stream, want_info)
 
     def shortcut_paths(self, path, plen, status=None, seed: int = 0, env_id_base: int = 0, env_ids=None, seeds=None, passes: int = 7,
                        max_rounds: int = 16, stream=None, want_info: bool = False):
@@ -392,7 +370,8 @@ class BatchPlanner:
                                     stream, want_info)
 
     def _k9_rows_launch(self, entry, info_cols, path, plen, status, seed, env_id_base, env_ids, seeds, passes, max_rounds, stream, want_info):
-        """argument checks and launch shared by `shortcut_paths` and `smooth_paths` (the two entry points take the same arguments)"""
+        """argument checks and launch shared by `simplify_paths`, `shortcut_paths` and `smooth_paths`; max_rounds=None: the entry
+        point takes no such argument (`simplify_paths`)"""
         torch = _torch()
         if path.dtype != torch.float64 or not path.is_cuda or not path.is_contiguous() or path.dim() != 3 or path.shape[2] != self.nq:
             raise _lib.MopaError(f"path must be a contiguous float64 GPU tensor of shape [E, max_path, {self.nq}]")
@@ -413,9 +392,18 @@ class BatchPlanner:
         _lib.check(entry(
             self.scene.handle, E, max_path, _ptr(path), _ptr(plen), _ptr(status) if status is not None else None,
             int(seed) & 0xFFFFFFFFFFFFFFFF, int(env_id_base), _ptr(env_ids) if env_ids is not None else None,
-            _ptr(seeds) if seeds is not None else None, int(passes), int(max_rounds), _ptr(info) if info is not None else None,
-            _stream_handle(stream)))
+            _ptr(seeds) if seeds is not None else None, int(passes), *(() if max_rounds is None else (int(max_rounds),)),
+            _ptr(info) if info is not None else None, _stream_handle(stream)))
         return info
+
+    def _k9_behind(self, path, plen, status, seed, env_id_base, env_ids, seeds, vertex_simplify, simplify_passes, path_shortcut, path_smooth,
+                   stream):
+        """the K9 launch the flags of `plan` / `plan_star` select, behind the planner's on the same stream with the same seed / ids /
+        seeds; none when all flags are off"""
+        name = k9_entry(vertex_simplify, path_shortcut, path_smooth)
+        if name is not None:
+            getattr(self, name)(path, plen, status, seed=seed, env_id_base=env_id_base, env_ids=env_ids, seeds=seeds,
+                                passes=k9_passes(vertex_simplify, simplify_passes, path_shortcut, path_smooth), stream=stream)
 
     def plan_laddered(self, batches, max_iters: int = 2000, first_iters: int = 100, max_nodes: int = 1024, max_path: int = 256,
                       retry_streams=None, first_stream=None, max_workgroups_first: int = -1, retry_min: int = 1024, resume: bool = True,

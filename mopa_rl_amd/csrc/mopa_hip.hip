@@ -44,9 +44,7 @@ int mopa_fail(int code, const std::string &msg) {
 constexpr double kV5MaxReach = 32.0;        // metres: beyond this the FP32 broad phase is not used (see mopa_scene_create)
 static void plan_register_lds();            // defined with K3 (mopa_planner.inc)
 static void contacts_register_lds();        // defined with the contact report (mopa_contacts.inc)
-static void simplify_register_lds();        // defined with K9 (mopa_simplify.inc)
-static void shortcut_register_lds();        // defined with K9 shortcutPath (mopa_shortcut.inc)
-static void smooth_register_lds();          // defined with K9 smoothBSpline (mopa_smooth.inc)
+static void k9_register_lds();              // defined with K9 path simplification (mopa_k9.inc)
 static void star_register_lds();            // defined with K3b RRT* (mopa_rrtstar.inc)
 static void k1_register_lds();              // defined with the K1 kernel table (mopa_valid_launch.inc)
 
@@ -527,6 +525,25 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(2, 2))) 
     }
 }
 
+// The same rule for the kernels that run one wave per path or query (K9, RRT*): the segment from ends[0..na) to ends[na..2 na), both
+// in the wave's LDS and written by the caller just before; `tst` as above, `lh` the header copy in LDS.  The verdict is wave-uniform.
+MOPA_D bool motion_valid_ends(const SceneHdr &h, const LdsView &v, const SceneHdr *lh, int lane, const double *ends, double *tst,
+                              const double *row) {
+    const int na = h.na;
+    wave_sync();
+    const int nd = __builtin_amdgcn_readfirstlane(valid_segment_count(h, v, ends, ends + na));
+    bool ok = true;
+    for (int k = nd; k >= (nd > 0 ? 1 : 0) && ok; k--) {
+        const double t = (nd > 0) ? (double)k / (double)nd : 1.0;
+        for (int i = lane; i < na; i += 64) tst[i] = (k == nd) ? ends[na + i] : interp_dim(h, v, i, ends[i], ends[na + i], t);
+        wave_sync();
+        ok = plan_state_valid_impl(lh, v.dbl, v.ints, v.grec, v.qbuf, v.wl, lane, tst, row);
+    }
+    ok = __builtin_amdgcn_readfirstlane((int)ok) != 0;
+    wave_sync();
+    return ok;
+}
+
 // ---------------------------------------------------------------------------
 // debug kernels (parity hooks): posed geoms and per-pair distances of one state
 // ---------------------------------------------------------------------------
@@ -676,9 +693,7 @@ extern "C" int mopa_scene_create(const MopaSceneDesc *desc, MopaScene **out) {
     k1_register_lds();
     plan_register_lds();
     contacts_register_lds();
-    simplify_register_lds();
-    shortcut_register_lds();
-    smooth_register_lds();
+    k9_register_lds();
     star_register_lds();
     *out = S;
     return MOPA_OK;
@@ -739,9 +754,6 @@ extern "C" int mopa_check_motion_batch(MopaScene *S, const double *qa, const dou
     HIP_TRY(hipGetLastError());
     return MOPA_OK;
 }
-
-// K9: vertex-reducing path simplification, one wave per path (k_simplify_paths, mopa_simplify_paths_batch)
-#include "mopa_simplify.inc"
 
 // split a full qpos into (active vector, env row) on the scene's scratch
 static int upload_state(MopaScene *S, const double *qpos_host) {
@@ -810,12 +822,11 @@ extern "C" const char *mopa_planner_status(const MopaScene *S) { return S ? S->s
 // The planner entry points are defined in mopa_planner.inc (K3).
 #include "mopa_planner.inc"
 #include "mopa_pullback.inc"
-// K9: shortcutPath in front of the vertex passes, new states included (k_shortcut_paths, mopa_shortcut_paths_batch), and the same
-// body with smoothBSpline behind it (k_smooth_paths, mopa_smooth_paths_batch); behind the planner, whose multi-state validity
-// pass the smoothing uses
-#include "mopa_shortcut.inc"
-#include "mopa_smooth.inc"
-// K3b: RRT*, the reference's other planner algorithm (k_rrt_star, mopa_plan_star_batch); k_simplify_paths' shape
+// K9: path simplification, one kernel body at three levels -- the vertex-removing passes (k_simplify_paths, mopa_simplify_paths_batch),
+// shortcutPath in front of them (k_shortcut_paths, mopa_shortcut_paths_batch), smoothBSpline between the two (k_smooth_paths,
+// mopa_smooth_paths_batch); behind the planner, whose multi-state validity pass the smoothing uses
+#include "mopa_k9.inc"
+// K3b: RRT*, the reference's other planner algorithm (k_rrt_star, mopa_plan_star_batch); the K9 kernels' shape
 #include "mopa_rrtstar.inc"
 #include "mopa_ik.inc"
 #include "mopa_paths.inc"

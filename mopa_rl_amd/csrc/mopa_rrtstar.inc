@@ -1,5 +1,5 @@
 // mopa_rrtstar.inc -- K3b: RRT* (the reference's planner_type "rrt"), one wave per query, persistent waves.
-// (included by mopa_hip.hip behind the K9 kernels: the kernel has the shape of k_simplify_paths)
+// (included by mopa_hip.hip behind mopa_k9.inc: the kernel has the shape of the K9 kernels)
 //
 // OMPL's geometric::RRTstar restated as the reference configures it -- k-nearest neighbourhoods, path-length objective, no cost
 // threshold -- with an iteration budget in place of the wall clock (DESIGN.md "K3b RRT*").  The sequential form of
@@ -14,7 +14,7 @@
 // lanes.  A rewire refreshes the costs below the rewired node by stamped sweeps over the node array: a node is refreshed once its
 // parent carries the current stamp, until a sweep changes nothing (rewiring breaks parent < child, so one ascending sweep is not
 // enough).  Every decision is taken from wave-uniform values, the counters are scalars.  No atomics; all stores are vector
-// stores.  A motion check is k_check_motion's loop, with the start row as the env row.
+// stores.  A motion check is motion_valid_ends, k_check_motion's loop, with the start row as the env row.
 
 struct StarArgs {
     const double *start, *goal;         // [E, nq]
@@ -88,18 +88,8 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(2, 2))) 
         };
         // K2's rule from ends[0..na) to ends[na..2 na)
         auto check_ends = [&]() -> bool {
-            wave_sync();
             n_checks++;
-            const int nd = __builtin_amdgcn_readfirstlane(valid_segment_count(h, v, ends, ends + na));
-            bool ok = true;
-            for (int k = nd; k >= (nd > 0 ? 1 : 0) && ok; k--) {
-                const double t = (nd > 0) ? (double)k / (double)nd : 1.0;
-                for (int i = lane; i < na; i += 64) tst[i] = (k == nd) ? ends[na + i] : interp_dim(h, v, i, ends[i], ends[na + i], t);
-                wave_sync();
-                ok = uni(plan_state_valid_impl(lh, v.dbl, v.ints, v.grec, v.qbuf, v.wl, lane, tst, row));
-            }
-            wave_sync();
-            return ok;
+            return motion_valid_ends(h, v, lh, lane, ends, tst, row);
         };
         // the smallest (distance, index) pair of the wave, on every lane
         auto reduce_min = [&](double &bd, int &bi) {

@@ -125,29 +125,23 @@ class PyKinematicPlanner:
     def _simplify(self, path: np.ndarray, stream_id: int) -> np.ndarray:
         """K9 over one solved path: the draws come from the sample stream (seed, stream_id) the plan itself used"""
         import torch
-        from .batch import BatchPlanner
+        from .batch import BatchPlanner, k9_entry, k9_passes
         ordinal = self._scene._ctor[7]          # the scene's device (-1: the current one, where it was created)
         dev = torch.device("cuda", ordinal if ordinal >= 0 else torch.cuda.current_device())
         plen = torch.tensor([len(path)], dtype=torch.int32, device=dev)
+        flags = (self.vertex_simplify, self.path_shortcut, self.path_smooth)
+        cap = len(path)                 # the vertex passes only remove rows
         if self.path_smooth:            # a smoothing step nearly doubles the vertices: the largest capacity the kernel's lists hold
-            bp = BatchPlanner(self._scene)
             cap = min(MAX_PATH, int(_lib.lib().mopa_smooth_paths_max_path(self._scene.handle)))
             if len(path) > cap:
                 raise _lib.MopaError(f"path_smooth: the path has {len(path)} rows, the smoothing kernel holds {cap}")
-            rows = torch.zeros(1, cap, path.shape[1], dtype=torch.float64, device=dev)
-            rows[0, :len(path)] = torch.from_numpy(np.ascontiguousarray(path)).to(dev)
-            bp.smooth_paths(rows, plen, None, seed=self.seed, env_id_base=stream_id,
-                            passes=8 | (4 if self.path_shortcut else 0) | (self.vertex_simplify_passes if self.vertex_simplify else 0))
-            return rows[0, :int(plen[0])].cpu().numpy()
-        if self.path_shortcut:          # a shortcut can add a vertex: the rows get the planner's own capacity
-            rows = torch.zeros(1, MAX_PATH, path.shape[1], dtype=torch.float64, device=dev)
-            rows[0, :len(path)] = torch.from_numpy(np.ascontiguousarray(path)).to(dev)
-            BatchPlanner(self._scene).shortcut_paths(rows, plen, None, seed=self.seed, env_id_base=stream_id,
-                                                     passes=4 | (self.vertex_simplify_passes if self.vertex_simplify else 0))
-            return rows[0, :int(plen[0])].cpu().numpy()
-        rows = torch.from_numpy(np.ascontiguousarray(path[None])).to(dev)
-        BatchPlanner(self._scene).simplify_paths(rows, plen, None, seed=self.seed, env_id_base=stream_id,
-                                                 passes=self.vertex_simplify_passes)
+        elif self.path_shortcut:        # a shortcut can add a vertex: the rows get the planner's own capacity
+            cap = MAX_PATH
+        rows = torch.zeros(1, cap, path.shape[1], dtype=torch.float64, device=dev)
+        rows[0, :len(path)] = torch.from_numpy(np.ascontiguousarray(path)).to(dev)
+        getattr(BatchPlanner(self._scene), k9_entry(*flags))(
+            rows, plen, None, seed=self.seed, env_id_base=stream_id,
+            passes=k9_passes(flags[0], self.vertex_simplify_passes, flags[1], flags[2]))
         return rows[0, :int(plen[0])].cpu().numpy()
 
     def getPlannerStatus(self) -> bytes:

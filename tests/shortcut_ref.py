@@ -1,4 +1,4 @@
-"""Sequential reference of K9's shortcutPath (csrc/mopa_shortcut.inc, DESIGN.md "K9 path simplification: shortcutPath") for
+"""Sequential reference of K9's shortcutPath (csrc/mopa_k9.inc, DESIGN.md "K9 path simplification: shortcutPath") for
 test_shortcut_host.py and test_shortcut_gpu.py: OMPL's PathSimplifier::shortcutPath restated over `OracleScene.check_motion`,
 in front of simplify_ref.py's reduceVertices / collapseCloseVertices, which run unchanged on the vertex list.  shortcutPath
 creates new floating-point states, so every operation is fixed here: plain float64 adds, subtractions, one product or one

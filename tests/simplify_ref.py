@@ -1,4 +1,4 @@
-"""Sequential reference of K9 (csrc/mopa_simplify.inc, DESIGN.md "K9 path simplification") for test_simplify_host.py and
+"""Sequential reference of K9 (csrc/mopa_k9.inc, DESIGN.md "K9 path simplification") for test_simplify_host.py and
 test_simplify_gpu.py: OMPL's reduceVertices and collapseCloseVertices restated over `OracleScene.check_motion`, plain float64
 adds and reuse_ref.py's counter RNG.  This form is the definition: the kernel has to reproduce it exactly."""
 import math

@@ -1,4 +1,4 @@
-"""Sequential reference of K9's smoothBSpline (csrc/mopa_smooth.inc, DESIGN.md "K9 path simplification: smoothBSpline") for
+"""Sequential reference of K9's smoothBSpline (csrc/mopa_k9.inc, DESIGN.md "K9 path simplification: smoothBSpline") for
 test_smooth_host.py and test_smooth_gpu.py: OMPL's PathSimplifier::smoothBSpline restated over `OracleScene.check_motion` and
 `OracleScene.is_valid_batch`, between shortcut_ref.py's shortcutPath loop and the vertex passes of a round.  Every new state is
 made by `interpolate` (one fma per coordinate); the pass draws nothing.  Three deviations from OMPL keep every segment of a

@@ -1,4 +1,4 @@
-"""K9 shortcutPath on the GPU: k_shortcut_paths (csrc/mopa_shortcut.inc) against the sequential reference shortcut_ref.py -- the
+"""K9 shortcutPath on the GPU: k_shortcut_paths (csrc/mopa_k9.inc) against the sequential reference shortcut_ref.py -- the
 rows, new states included, on bit patterns, lengths and all six info columns -- over the blocked Push / Pusher queries of
 test_shortcut_host.py and over synthetic paths; the vertex passes alone against k_simplify_paths, skipped paths, ids / seeds,
 streams, continuation, argument errors, and the flag through SamplingBasedPlanner and the rollout."""

@@ -1,4 +1,4 @@
-"""K9 on the GPU: k_simplify_paths (csrc/mopa_simplify.inc) against the sequential reference simplify_ref.py -- surviving rows on
+"""K9 on the GPU: k_simplify_paths (csrc/mopa_k9.inc) against the sequential reference simplify_ref.py -- surviving rows on
 bit patterns, lengths, motion-check and draw counts -- over the device planner's own paths of the blocked Push / Pusher queries
 of test_simplify_host.py and over synthetic paths; skipped paths, launch shapes, ids / seeds, continuation, streams, argument
 errors, and the flag through SamplingBasedPlanner and the rollout."""

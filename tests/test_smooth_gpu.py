@@ -1,4 +1,4 @@
-"""K9 smoothBSpline on the GPU: k_smooth_paths (csrc/mopa_smooth.inc) against the sequential reference smooth_ref.py -- the rows,
+"""K9 smoothBSpline on the GPU: k_smooth_paths (csrc/mopa_k9.inc) against the sequential reference smooth_ref.py -- the rows,
 new and moved states included, on bit patterns, lengths and all ten info columns -- over the blocked Push / Pusher queries of
 test_smooth_host.py and over synthetic paths; bit 3 clear against k_shortcut_paths, skipped paths, ids / seeds, streams,
 continuation, argument errors, and the flag through SamplingBasedPlanner and the rollout."""
