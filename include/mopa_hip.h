@@ -327,6 +327,48 @@ int mopa_plan_star(MopaScene *scene, const double *start_host, const double *goa
 int mopa_plan_star_k(int32_t na, int64_t n, double rewire_factor);
 int mopa_star_params_size(void);
 
+/* K3 race: E RRT-Connect queries, each run by `portfolio` = K members that share start, goal, env row and stream id and differ in
+ * their seed only; asynchronous on `stream`, no read-back.  The result of a query is that of ONE member, chosen by a rule that does
+ * not depend on timing (DESIGN.md "K3 race"; the sequential form is tests/race_ref.py):
+ *   members:   member m of query g runs stream id env_ids_dev[g] (or env_id_base + g) with the seed (seed_g + m * 0x9E3779B97F4A7C15)
+ *              mod 2^64, seed_g = seeds_dev[g] or seed, and the full budget.  Member 0 is exactly the query mopa_plan_batch runs, so
+ *              portfolio = 1 gives mopa_plan_batch's status, rows, path_len and n_checks.
+ *   winner:    the solved member (status 0; a solution of more than max_path rows is not solved) with the smallest (consumed checks,
+ *              m).  A member stops early only when its count so far already exceeds a solved member's final count -- when it could no
+ *              longer win --, so launch order, residency and placement cannot change a result.
+ *   results:   the winner's rows (as mopa_plan_batch writes them), path_len, status 0, the winner's n_checks, winner = m, win_seed =
+ *              its seed.  No solved member: status -5 if the goal is invalid (every member agrees), else -4; winner = -1, path_len =
+ *              0, n_checks and win_seed are member 0's.
+ *   info_dev:  nullable, [E,3]: members cut, checks spent by all members until they stopped, the winner's iterations (-1: none).
+ *              Columns 0 and 1 DEPEND ON TIMING unless no_abort is set (then 0 and the sum of all members' full counts).
+ *   memory:    the trees of all members live in the library's scratch: E * K * 2 * max_nodes * na doubles plus E * K * 2 * max_nodes
+ *              int32 parents; MOPA_ERR_LIMIT, with the byte count in mopa_last_error(), when the device cannot hold them.
+ *   launch:    mopa_plan_batch's policy over the E * K slots (slot v = member v / E of query v % E); max_workgroups as there.
+ * Argument errors return before anything touches a device: NULL scene / params / buffers (info_dev alone is nullable), E < 0,
+ * max_iters < 0, max_nodes < 2, max_path < 2, portfolio outside 1..256 (MOPA_ERR_INVALID_ARG). */
+typedef struct MopaRaceParams {
+    int32_t max_iters;     /* iteration budget of every member */
+    int32_t max_nodes;     /* per-tree node capacity of every member */
+    int32_t max_path;      /* rows available per query in `path` */
+    int32_t portfolio;     /* K: members per query, 1..256 */
+    uint64_t seed;
+    uint64_t env_id_base;
+    const uint64_t *env_ids_dev;   /* nullable, [E] */
+    const uint64_t *seeds_dev;     /* nullable, [E] */
+    int32_t max_workgroups;        /* as in MopaPlanParams */
+    int32_t no_abort;              /* nonzero: no member is cut, every member runs to its own end (tests, measurements) */
+} MopaRaceParams;
+int mopa_plan_race_batch(MopaScene *scene, const double *start_dev /*[E,nq]*/, const double *goal_dev /*[E,nq]*/, int64_t E,
+                         const MopaRaceParams *params, double *path_dev /*[E,max_path,nq]*/, int32_t *path_len_dev /*[E]*/,
+                         int32_t *status_dev /*[E]*/, int64_t *n_checks_dev /*[E]*/, int32_t *winner_dev /*[E]*/,
+                         uint64_t *win_seed_dev /*[E]*/, int64_t *info_dev /*[E,3] nullable*/, void *stream);
+/* the single-query host form of mopa_plan_race_batch (host pointers, stream id = env_id_base, synchronous); sets the planner status
+ * string as mopa_plan does.  n_checks_out, winner_out, win_seed_out and info_out [3] are nullable */
+int mopa_plan_race(MopaScene *scene, const double *start_host, const double *goal_host, const MopaRaceParams *params,
+                   double *path_host /*[max_path,nq]*/, int32_t *path_len_out, int32_t *status_out, int64_t *n_checks_out,
+                   int32_t *winner_out, uint64_t *win_seed_out, int64_t *info_out);
+int mopa_race_params_size(void);
+
 /* The rollout's invalid-target back-off (rl/mopa_rollouts.py:133-143) for E envs, asynchronous (no read-back unless E * num_trials
  * rows would exceed 1 GiB of scratch; E < 256: one wave per env walks its trials, otherwise all candidate rows of all
  * invalid targets go through one validity launch -- same results): while target[e] (a full

@@ -27,7 +27,8 @@ EXPORTED_SYMBOLS = [
     "mopa_scene_num_active", "mopa_scene_active_idx", "mopa_scene_num_pairs", "mopa_scene_lds_bytes", "mopa_scene_valid_kernel",
     "mopa_scene_k1_baked", "mopa_scene_k1_export", "mopa_scene_hdr_offset", "mopa_k1_baked_fk_host",
     "mopa_is_valid_batch", "mopa_check_motion_batch", "mopa_plan_batch", "mopa_simplify_paths_batch", "mopa_simplify_paths_max_path", "mopa_shortcut_paths_batch", "mopa_shortcut_paths_max_path", "mopa_smooth_paths_batch", "mopa_smooth_paths_max_path",
-    "mopa_plan_star_batch", "mopa_plan_star", "mopa_plan_star_k", "mopa_star_params_size", "mopa_pullback_batch", "mopa_is_valid_state", "mopa_plan",
+    "mopa_plan_star_batch", "mopa_plan_star", "mopa_plan_star_k", "mopa_star_params_size",
+    "mopa_plan_race_batch", "mopa_plan_race", "mopa_race_params_size", "mopa_pullback_batch", "mopa_is_valid_state", "mopa_plan",
     "mopa_planner_status", "mopa_debug_fk", "mopa_debug_pair_dist", "mopa_contacts_batch", "mopa_contacts_state",
     "mopa_env_create", "mopa_env_destroy", "mopa_env_obs_dim", "mopa_env_action_dim", "mopa_env_step_batch", "mopa_env_exec_batch", "mopa_env_desired_batch",
     "mopa_env_attach_dynamics", "mopa_env_attach_contacts", "mopa_env_set_contact_stats", "mopa_rollout_stage", "mopa_rollout_pool_pick", "mopa_rollout_step_size", "mopa_reuse_batch", "mopa_replay_append", "mopa_replay_sample", "mopa_ct_desc_size", "mopa_env_contact_arena", "mopa_env_dyn_dofs", "mopa_env_dyn_qvel_width", "mopa_env_dyn_forward_batch", "mopa_env_dyn_substeps_batch", "mopa_env_step_dyn_batch",
@@ -159,6 +160,15 @@ class MopaStarParams(C.Structure):
                 ("goal_threshold", C.c_double), ("rewire_factor", C.c_double), ("max_workgroups", C.c_int32)]
 
 
+class MopaRaceParams(C.Structure):
+    """include/mopa_hip.h MopaRaceParams (K3 race: `portfolio` seeded RRT-Connect members per query)"""
+    _fields_ = [("max_iters", C.c_int32), ("max_nodes", C.c_int32), ("max_path", C.c_int32), ("portfolio", C.c_int32), ("seed", C.c_uint64),
+                ("env_id_base", C.c_uint64), ("env_ids_dev", C.c_void_p), ("seeds_dev", C.c_void_p), ("max_workgroups", C.c_int32),
+                ("no_abort", C.c_int32)]
+
+
+RACE_INFO_COLS = 3          # members cut, checks spent by all members, the winner's iterations (-1: none)
+RACE_SEED_STEP = 0x9E3779B97F4A7C15     # member m of a query runs the seed (seed + m * RACE_SEED_STEP) mod 2^64
 STAR_INFO_COLS = 8          # iterations run, nodes, motion checks, rewires, goal nodes, first goal iteration, descendant updates, full-tree iterations
 STAR_REWIRE_FACTOR = 1.1    # OMPL's default
 STAR_GOAL_BIAS = 0.05       # OMPL's default
@@ -207,6 +217,10 @@ def lib() -> C.CDLL:
                                  C.POINTER(C.c_double), C.POINTER(C.c_int64)]
     L.mopa_plan_star_k.argtypes = [C.c_int32, C.c_int64, C.c_double]
     L.mopa_star_params_size.argtypes = []
+    L.mopa_plan_race_batch.argtypes = [vp, vp, vp, C.c_int64, C.POINTER(MopaRaceParams), vp, vp, vp, vp, vp, vp, vp, vp]
+    L.mopa_plan_race.argtypes = [vp, _dp, _dp, C.POINTER(MopaRaceParams), _dp, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                 C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_uint64), C.POINTER(C.c_int64)]
+    L.mopa_race_params_size.argtypes = []
     L.mopa_pullback_batch.argtypes = [vp, vp, vp, C.c_int64, C.c_double, C.c_int32, vp, vp, vp]
     L.mopa_is_valid_state.argtypes = [vp, _dp, C.POINTER(C.c_int32), _dp]
     L.mopa_plan.argtypes = [vp, _dp, _dp, C.POINTER(MopaPlanParams), _dp, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
@@ -499,6 +513,22 @@ class Scene:
         check(lib().mopa_plan_star(self._h, sp, gp, C.byref(prm), path.ctypes.data_as(_dp), C.byref(plen), C.byref(st), C.byref(cost),
                                    info.ctypes.data_as(C.POINTER(C.c_int64))))
         return st.value, path[:plen.value].copy(), cost.value, info
+
+    def plan_race(self, start, goal, portfolio: int, max_iters: int, max_nodes: int = 4096, max_path: int = 512, seed: Optional[int] = None,
+                  env_id: int = 0, no_abort: bool = False):
+        """one RRT-Connect query run by `portfolio` members that differ in their seed only (K3 race): -> (status, path rows,
+        the winner's consumed checks, winner, the winner's seed, info [3] int64 = members cut, checks spent by all members, the
+        winner's iterations); without a solved member winner = -1 and checks / seed are member 0's"""
+        s, sp = _d(start)
+        g, gp = _d(goal)
+        prm = MopaRaceParams(int(max_iters), int(max_nodes), int(max_path), int(portfolio), int(self.seed if seed is None else seed) & 0xFFFFFFFFFFFFFFFF,
+                             int(env_id), None, None, 0, 1 if no_abort else 0)
+        path = np.zeros((max_path, self.nq))
+        info = np.zeros(RACE_INFO_COLS, dtype=np.int64)
+        plen, st, chk, win, wseed = C.c_int32(0), C.c_int32(0), C.c_int64(0), C.c_int32(0), C.c_uint64(0)
+        check(lib().mopa_plan_race(self._h, sp, gp, C.byref(prm), path.ctypes.data_as(_dp), C.byref(plen), C.byref(st), C.byref(chk), C.byref(win),
+                                   C.byref(wseed), info.ctypes.data_as(C.POINTER(C.c_int64))))
+        return st.value, path[:plen.value].copy(), chk.value, win.value, wseed.value, info
 
     def valid_kernel(self, n_states: int) -> str:
         """name of the validity kernel `mopa_is_valid_batch` dispatches for a batch of n_states"""

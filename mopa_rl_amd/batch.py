@@ -327,6 +327,49 @@ class BatchPlanner:
         self._k9_behind(path, plen, status, seed, env_id_base, env_ids, seeds, vertex_simplify, simplify_passes, path_shortcut, path_smooth, stream)
         return (path, plen, status, cost, info) if want_info else (path, plen, status, cost)
 
+    def plan_race(self, start, goal, portfolio: int = 4, max_iters: int = 2000, max_nodes: int = 1024, max_path: int = 256, seed: int = 0,
+                  env_id_base: int = 0, env_ids=None, seeds=None, stream=None, max_workgroups: int = 0, no_abort: bool = False,
+                  want_info: bool = False, vertex_simplify: bool = False, simplify_passes: int = 3, path_shortcut: bool = False,
+                  path_smooth: bool = False):
+        """E RRT-Connect queries, each run by `portfolio` (1 .. 256) members that share start, goal and stream id and differ in their
+        seed only: member m runs (seed + m * 0x9E3779B97F4A7C15) mod 2^64, member 0 is exactly the query `plan` runs (K3 race,
+        DESIGN.md).  The result of a query is that of ONE member: the solved one with the smallest (consumed checks, m) -- a rule that
+        does not depend on timing; members that can no longer win stop early unless `no_abort`.  Returns (path [E, max_path, nq],
+        path_len [E], status [E], n_checks [E] = the winner's, winner [E] int32 (-1: no member solved; n_checks and win_seed are
+        then member 0's), win_seed [E] int64 (bit pattern of the winner's seed)) and with `want_info` a seventh element, an int64
+        [E, 3] tensor: members cut, checks spent by all members until they stopped (both depend on timing unless `no_abort`), the
+        winner's iterations (-1: none).  Tree scratch is E * portfolio * 2 * max_nodes * na doubles plus parents.
+        env_ids / seeds / env_id_base / seed / stream / max_workgroups: as for `plan`, the launch policy applied to E * portfolio slots.
+        vertex_simplify / simplify_passes / path_shortcut / path_smooth: as in `plan`, but the K9 launch draws with seeds=win_seed,
+        the winner's stream."""
+        torch = _torch()
+        _check_f64(start, "start", self.nq)
+        _check_f64(goal, "goal", self.nq)
+        E = start.shape[0]
+        dev = start.device
+        for t, name in ((env_ids, "env_ids"), (seeds, "seeds")):
+            if t is not None and (t.dtype != torch.int64 or not t.is_cuda or not t.is_contiguous() or tuple(t.shape) != (E,)):
+                raise _lib.MopaError(f"{name} must be a contiguous int64 GPU tensor of shape [E]")
+
+        def alloc():
+            return (torch.zeros(E, max_path, self.nq, dtype=torch.float64, device=dev), torch.zeros(E, dtype=torch.int32, device=dev),
+                    torch.zeros(E, dtype=torch.int32, device=dev), torch.zeros(E, dtype=torch.int64, device=dev),
+                    torch.zeros(E, dtype=torch.int32, device=dev), torch.zeros(E, dtype=torch.int64, device=dev),
+                    torch.zeros(E, _lib.RACE_INFO_COLS, dtype=torch.int64, device=dev) if want_info else None)
+        if stream is not None:
+            with torch.cuda.stream(stream):
+                path, plen, status, nchk, winner, wseed, info = alloc()
+        else:
+            path, plen, status, nchk, winner, wseed, info = alloc()
+        prm = _lib.MopaRaceParams(int(max_iters), int(max_nodes), int(max_path), int(portfolio), int(seed) & 0xFFFFFFFFFFFFFFFF, int(env_id_base),
+                                  _ptr(env_ids) if env_ids is not None else None, _ptr(seeds) if seeds is not None else None,
+                                  int(max_workgroups), 1 if no_abort else 0)
+        _lib.check(_lib.lib().mopa_plan_race_batch(self.scene.handle, _ptr(start), _ptr(goal), E, C.byref(prm), _ptr(path), _ptr(plen), _ptr(status),
+                                                   _ptr(nchk), _ptr(winner), _ptr(wseed), _ptr(info) if info is not None else None,
+                                                   _stream_handle(stream)))
+        self._k9_behind(path, plen, status, seed, env_id_base, env_ids, wseed, vertex_simplify, simplify_passes, path_shortcut, path_smooth, stream)
+        return (path, plen, status, nchk, winner, wseed, info) if want_info else (path, plen, status, nchk, winner, wseed)
+
     def simplify_paths(self, path, plen, status=None, seed: int = 0, env_id_base: int = 0, env_ids=None, seeds=None, passes: int = 3,
                        stream=None, want_info: bool = False):
         """K9, in place: OMPL's reduceVertices (passes bit 0) and collapseCloseVertices (bit 1) over the planner's rows -- `path`

@@ -106,6 +106,7 @@ struct StreamScratch {
     size_t slab_waves = 0;
     DevBuf mv_cnt, mv_off, mv_env, mv_q, mv_valid, mv_scan;   // expanded motion validation (mopa_motion.inc)
     DevBuf plan_q, plan_p, plan_ctr;                          // planner: both trees of every env, env counter (mopa_planner.inc)
+    DevBuf race_rec, race_word;                               // K3 race (mopa_race.inc): the members' records, one race word per query
     DevBuf ip_walk;                                           // straight-line pre-check: walk states + verdicts (mopa_paths.inc)
     DevBuf pb_small, pb_rows, pb_act;                         // batched pull-back: verdicts / slots, candidate rows, their active coordinates + verdicts
     DevBuf ct_valid, ct_md, ct_ctr;                           // contact report (mopa_contacts.inc): stage 1's verdicts and depths, stage 2's chunk counter
@@ -708,7 +709,7 @@ extern "C" void mopa_scene_destroy(MopaScene *S) {
     for (auto &kv : S->scratch) {
         StreamScratch &sc = kv.second;
         for (DevBuf *b : {&sc.slab, &sc.mpr, &sc.cen, &sc.mesh_list, &sc.mesh_rows, &sc.mv_cnt, &sc.mv_off, &sc.mv_env, &sc.mv_q, &sc.mv_valid, &sc.mv_scan, &sc.plan_q,
-                          &sc.plan_p, &sc.plan_ctr, &sc.pb_small, &sc.pb_rows, &sc.pb_act, &sc.ip_walk, &sc.ct_valid, &sc.ct_md, &sc.ct_ctr, &sc.star_tree, &sc.star_k})
+                          &sc.plan_p, &sc.plan_ctr, &sc.pb_small, &sc.pb_rows, &sc.pb_act, &sc.ip_walk, &sc.ct_valid, &sc.ct_md, &sc.ct_ctr, &sc.star_tree, &sc.star_k, &sc.race_rec, &sc.race_word})
             if (b->p) (void)hipFree(b->p);
     }
     for (void *q : S->retired) (void)hipFree(q);

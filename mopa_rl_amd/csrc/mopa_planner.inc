@@ -454,6 +454,7 @@ MOPA_D int wave_argmin_f64(double bd, int bi) {
     return wave_min_i32(bd == m ? bi : 0x7fffffff);
 }
 
+#define MOPA_K3_RACE 0      // 1: the race build (mopa_race.inc)
 #define MOPA_K3_WG 0
 #define MOPA_K3_WAVES 2
 namespace k3w2 {
@@ -473,11 +474,15 @@ namespace k3wg {
 #define MOPA_K3_WG 0
 #undef MOPA_K3_WAVES
 
+// K3 race: the fourth instantiation (namespace k3race), k_race_pick, mopa_plan_race_batch / mopa_plan_race
+#include "mopa_race.inc"
+
 static void plan_register_more();   // kernels defined after this file (mopa_pullback.inc)
 static void plan_register_lds() {
     (void)hipFuncSetAttribute((const void *)k3w2::k_rrt_connect, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLdsBytes);
     (void)hipFuncSetAttribute((const void *)k3w1::k_rrt_connect, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLdsBytes);
     (void)hipFuncSetAttribute((const void *)k3wg::k_rrt_connect, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLdsBytes);
+    (void)hipFuncSetAttribute((const void *)k3race::k_rrt_connect, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLdsBytes);
     plan_register_more();
 }
 

@@ -11,7 +11,9 @@
 //                   nearest node, steered state, first connect state) and evaluate those.  Nearest neighbours and verdicts of
 //                   future iterations wait in a small table (kFSlots entries) and are used only when the sequential algorithm
 //                   arrives at exactly that query / that state: results and consumed-check counts cannot change.
-// Same source, same results; only register allocation and the few MOPA_K3_WAVES / MOPA_K3_WG switches below differ.
+//   namespace k3race, MOPA_K3_RACE 1 on the k3w1 settings (mopa_race.inc): launch slot v is member v / Eq of query v % Eq; a member
+//                   leaves a record instead of path rows and stops when the query's race word says that it can no longer win.
+// Same source, same results; only register allocation and the few MOPA_K3_WAVES / MOPA_K3_WG / MOPA_K3_RACE switches below differ.
 struct PlanCtx {
     LdsView v;
     const SceneHdr *lh;    // the scene header's copy in LDS (what the non-inlined validity routines read)
@@ -1010,7 +1012,11 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(MOPA_K3_
                                                         const double *__restrict__ start, const double *__restrict__ goal, long long E,
                                                         MopaPlanParams prm, PlanWs ws, double *__restrict__ path,
                                                         int32_t *__restrict__ path_len, int32_t *__restrict__ status,
-                                                        long long *__restrict__ n_checks, int plan_lds_off, unsigned long long *__restrict__ env_ctr, int nn_cap) {
+                                                        long long *__restrict__ n_checks, int plan_lds_off, unsigned long long *__restrict__ env_ctr, int nn_cap
+#if MOPA_K3_RACE
+                                                        , RaceArgs ra
+#endif
+                                                        ) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     LdsView v = make_view(h, smem);
     stage_scene(h, g_dbl, g_int, const_cast<double *>(v.dbl), const_cast<int *>(v.ints));
@@ -1076,6 +1082,11 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(MOPA_K3_
     }
 #endif
     if (e >= E) { tile_ctr_release(env_ctr, lane); return; }       // (the last wave out leaves the counter at zero for the next launch)
+#if MOPA_K3_RACE
+    // e is the launch SLOT (trees, record); start, goal, env row, stream id and seed are query eq's -- no K-fold copy of the inputs
+    const int member = (int)(e / ra.Eq);
+    const long long eq = e - (long long)member * ra.Eq;
+#endif
 #ifdef MOPA_PLAN_STATS
     const unsigned long long tq0_ = wall_clock64();
 #endif
@@ -1085,7 +1096,11 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(MOPA_K3_
     unsigned char *pbase = smem + plan_lds_off + wave * wave_plan_bytes;
     PlanCtx c;
     c.v = v; c.lane = lane; c.lh = lh;
+#if MOPA_K3_RACE
+    c.row = start + eq * h.nq;
+#else
     c.row = start + e * h.nq;
+#endif
     c.rs = reinterpret_cast<double *>(pbase); c.xs = c.rs + na; c.ns = c.xs + na; c.ts = c.ns + na; c.r2 = c.ts + na;
     c.memo_q = c.r2 + na; c.spec_q = c.memo_q + kMemo * na; c.nn_q = c.spec_q + kSpec * na;
     c.queue = reinterpret_cast<short *>(c.nn_q + 2 * na);
@@ -1145,13 +1160,22 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(MOPA_K3_
             wave_sync();
         }
     }
+#if MOPA_K3_RACE
+    const uint64_t stream_id = prm.env_ids_dev ? prm.env_ids_dev[eq] : prm.env_id_base + (uint64_t)eq;
+    const uint64_t seed_q = (prm.seeds_dev ? prm.seeds_dev[eq] : prm.seed) + (uint64_t)member * kRaceSeedStep;
+#else
     const uint64_t stream_id = prm.env_ids_dev ? prm.env_ids_dev[e] : prm.env_id_base + (uint64_t)e;
     const uint64_t seed_q = prm.seeds_dev ? prm.seeds_dev[e] : prm.seed;
+#endif
     c.seed = seed_q; c.stream = stream_id; c.rng_k = rng_key(seed_q, stream_id); c.max_iters = prm.max_iters;
     c.so2 = __ballot(lane < na && v.ints[h.o_act_so2 + (lane < na ? lane : 0)] != 0);
     const int *I = v.ints;
     const double *D = v.dbl;
+#if MOPA_K3_RACE
+    const double *grow_ = goal + eq * h.nq;
+#else
     const double *grow_ = goal + e * h.nq;
+#endif
     // roots
     if (!resumed) {
         if (lane < na) {
@@ -1189,6 +1213,10 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(MOPA_K3_
     };
     if (!resumed && !root_valid(tree_q(c, 1))) st = MOPA_PLAN_INVALID_GOAL;
     int it_end = 0;
+#if MOPA_K3_RACE
+    int race_sm = -1, race_gm = -1;      // the solution's two motions, for k_race_pick
+    bool race_cut = false;
+#endif
     if (st == MOPA_PLAN_OK) {
         int max_iters = prm.max_iters;
         if (!resumed) {
@@ -1199,6 +1227,17 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(MOPA_K3_
         int start_motion = -1, goal_motion = -1;
         int it = it0;
         for (; it < max_iters && !solved; it++) {
+#if MOPA_K3_RACE
+            // the race word holds the smallest key = consumed checks * K + member of the members that have solved.  Consumed checks only
+            // grow, so a member whose key so far is already larger can no longer win: it stops.  (An atomic load by one lane, never
+            // a plain or scalar one; a stale value only delays the cut.)
+            if (!ra.no_abort) {
+                unsigned long long w = 0ull;
+                if (lane == 0) w = __hip_atomic_load(ra.word + eq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                w = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(w >> 32)) << 32) | (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)w);
+                if ((unsigned long long)c.n_checks * (unsigned long long)ra.K + (unsigned long long)member > w) { race_cut = true; break; }
+            }
+#endif
             int tree = start_tree ? 0 : 1;
             bool tgi_start = start_tree;
             start_tree = !start_tree;
@@ -1254,6 +1293,12 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(MOPA_K3_
             for (int m = goal_motion; m != -1; m = tree_p(c, 1)[m]) n2++;
             if (n1 + n2 > prm.max_path) { st = MOPA_PLAN_NO_EXACT; keep_final = true; }
             else {
+#if MOPA_K3_RACE
+                // no path rows: the trees stay in the launch's scratch and k_race_pick traces the winner's
+                race_sm = start_motion; race_gm = goal_motion;
+                if (lane == 0) (void)__hip_atomic_fetch_min(ra.word + eq, (unsigned long long)c.n_checks * (unsigned long long)ra.K + (unsigned long long)member,
+                                                            __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#else
                 double *pe = path + (size_t)e * prm.max_path * h.nq;
 #if MOPA_K3_WG
                 if (wave == 0) {
@@ -1277,9 +1322,13 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(MOPA_K3_
 #if MOPA_K3_WG
                 }
 #endif
+#endif
                 plen = n1 + n2;
             }
         } else st = MOPA_PLAN_NO_EXACT;
+#if MOPA_K3_RACE
+        if (race_cut) st = kRaceCut;
+#endif
         it_end = it;
     }
 #if MOPA_K3_WG
@@ -1294,6 +1343,12 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(MOPA_K3_
 #ifdef MOPA_PLAN_STATS
     if (threadIdx.x == 0) atomicAdd(&g_plan_t[44], wall_clock64() - tq0_);
 #endif
+#if MOPA_K3_RACE
+    if (lane == 0) {       // the member's record (slot order) instead of the query's outputs: k_race_pick writes those
+        long long *r = ra.rec + (size_t)kRaceRec * (size_t)e;
+        r[0] = st; r[1] = c.n_checks; r[2] = it_end; r[3] = race_sm; r[4] = race_gm; r[5] = plen;
+    }
+#else
     if (lane == 0) {
         status[e] = st;
         path_len[e] = plen;
@@ -1302,6 +1357,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(MOPA_K3_
         if (n_checks) n_checks[e] = (c.n_checks & 0xffff) | (c.st_pass << 16) | (c.st_states << 30) | ((long long)tree_n(c, 0) << 44) | ((long long)tree_n(c, 1) << 54);
 #endif
     }
+#endif
     }
 #if defined(MOPA_PLAN_STATS) && MOPA_K3_WG
     if (lane == 0) {    // table hits and pass causes (wave 0's counts = every wave's), states posed per wave

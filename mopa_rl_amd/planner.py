@@ -87,6 +87,8 @@ class PyKinematicPlanner:
         self.path_shortcut = False
         #: K9: plan() runs smoothBSpline over the solved path, behind shortcutPath and in front of the vertex passes
         self.path_smooth = False
+        #: K3 race: with rrt_connect, plan() runs `portfolio` seeded members per query and returns the winner's path (DESIGN.md "K3 race")
+        self.portfolio = 1
         self._model = load_scene(self.xml_filename)
         self._scene = _lib.Scene(self._model, self.passive_joint_idx, self.ignored_contacts, self.contact_threshold,
                                  range_=self._range, resolution=0.005, seed=self.seed)
@@ -103,17 +105,24 @@ class PyKinematicPlanner:
         goal = np.asarray(goal_vec, dtype=np.float64)
         max_iters = max(1, int(round(float(timelimit) * ITERS_PER_SECOND)))
         # every plan() call of one planner object draws a fresh sample stream
+        k9_seed = self.seed
+        if int(self.portfolio) > 1 and self.algo == "rrt_star":
+            raise NotImplementedError("portfolio > 1 is built for rrt_connect only (RRT* always spends its whole budget: nothing to race)")
         if self.algo == "rrt_star":
             # goal bias: OMPL's default 0.05, not the constructor's `goal_bias` -- the reference never forwards that argument to
             # the planner it builds (KinematicPlanner.cpp:42-120); the goal threshold is the constructor's `threshold`
             status, path, self.last_cost, _ = self._scene.plan_star(start, goal, max_iters=max_iters, max_nodes=max_iters + 1, max_path=MAX_PATH,
                                                                     seed=self.seed, env_id=self._plan_count, goal_bias=_lib.STAR_GOAL_BIAS,
                                                                     goal_threshold=self.threshold)
+        elif int(self.portfolio) > 1:
+            # the simplifier draws from the winner's stream
+            status, path, _, _, k9_seed, _ = self._scene.plan_race(start, goal, int(self.portfolio), max_iters=max_iters, max_nodes=MAX_NODES,
+                                                                   max_path=MAX_PATH, seed=self.seed, env_id=self._plan_count)
         else:
             status, path, _ = self._scene.plan(start, goal, max_iters=max_iters, max_nodes=MAX_NODES, max_path=MAX_PATH,
                                                seed=self.seed, env_id=self._plan_count)
         if (self.vertex_simplify or self.path_shortcut or self.path_smooth) and status == _lib.PLAN_OK and len(path) >= 3:
-            path = self._simplify(path, self._plan_count)
+            path = self._simplify(path, self._plan_count, k9_seed)
         self._plan_count += 1
         nq = self._scene.nq
         if status == _lib.PLAN_INVALID_GOAL:
@@ -122,8 +131,10 @@ class PyKinematicPlanner:
             return [[-4.0] * nq]
         return path.tolist()
 
-    def _simplify(self, path: np.ndarray, stream_id: int) -> np.ndarray:
-        """K9 over one solved path: the draws come from the sample stream (seed, stream_id) the plan itself used"""
+    def _simplify(self, path: np.ndarray, stream_id: int, seed=None) -> np.ndarray:
+        """K9 over one solved path: the draws come from the sample stream (seed, stream_id) the plan itself used (a race: the
+        winner's seed)"""
+        seed = self.seed if seed is None else seed
         import torch
         from .batch import BatchPlanner, k9_entry, k9_passes
         ordinal = self._scene._ctor[7]          # the scene's device (-1: the current one, where it was created)
@@ -140,7 +151,7 @@ class PyKinematicPlanner:
         rows = torch.zeros(1, cap, path.shape[1], dtype=torch.float64, device=dev)
         rows[0, :len(path)] = torch.from_numpy(np.ascontiguousarray(path)).to(dev)
         getattr(BatchPlanner(self._scene), k9_entry(*flags))(
-            rows, plen, None, seed=self.seed, env_id_base=stream_id,
+            rows, plen, None, seed=seed, env_id_base=stream_id,
             passes=k9_passes(flags[0], self.vertex_simplify_passes, flags[1], flags[2]))
         return rows[0, :int(plen[0])].cpu().numpy()
 

@@ -29,7 +29,8 @@ def joint_convert(angle):
 class SamplingBasedPlanner:
     def __init__(self, config, xml_path, num_actions, non_limited_idx, planner_type=None, passive_joint_idx=[],
                  glue_bodies=[], ignored_contacts=[], contact_threshold=0.0, goal_bias=0.05, is_simplified=False,
-                 simplified_duration=0.1, range_=None, vertex_simplify=False, path_shortcut=False, path_smooth=False):
+                 simplified_duration=0.1, range_=None, vertex_simplify=False, path_shortcut=False, path_smooth=False,
+                 portfolio=1):
         self.config = config
         self.non_limited_idx = non_limited_idx
         # planner_type: "rrt_connect", or "rrt_star" for RRT* (K3b; what the reference's configs call "rrt", a name that keeps raising here)
@@ -46,6 +47,8 @@ class SamplingBasedPlanner:
         self.planner.path_shortcut = bool(path_shortcut)
         # K9 smoothBSpline, likewise: vertices are added and pulled towards their neighbours, so rows of the planner change too
         self.planner.path_smooth = bool(path_smooth)
+        # K3 race (not in the reference's argument list): rrt_connect runs `portfolio` seeded members per query and returns the winner's rows
+        self.planner.portfolio = int(portfolio)
 
     # ------------------------------------------------------------------
     def convert_nonlimited(self, state):
