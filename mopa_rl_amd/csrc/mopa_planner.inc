@@ -51,7 +51,7 @@ constexpr int kMemo = 8;    // states with a known verdict (ring)
 constexpr int kSpec = 3;    // states queued for speculative evaluation
 constexpr int kPlanVecs = 5 + kMemo + kSpec + 2;   // rs xs ns ts r2 | memo | spec | nn queries
 MOPA_HD int plan_vec_bytes(int na) { return (kPlanVecs * na * 8 + 2 * kQCap * 2 + 15) & ~15; }
-// ---- the workgroup-per-query build (namespace k3wg, mopa_planner_k3.inc): four waves run ONE query --------------------------
+// ---- the workgroup-per-query build (tag K3WG, mopa_planner_k3.inc): four waves run ONE query --------------------------
 // Table of FUTURE iterations, one slot per iteration modulo kFSlots: what waves 1-3 found out about iteration j while wave 0
 // evaluated the states the sequential algorithm was asking about.  An entry is kFStride doubles:
 //   8 ints: [0] iteration j  [1] flags  [2,3] nearest node of sample(j) in tree j&1: (tree size then, index)
@@ -454,37 +454,20 @@ MOPA_D int wave_argmin_f64(double bd, int bi) {
     return wave_min_i32(bd == m ? bi : 0x7fffffff);
 }
 
-#define MOPA_K3_RACE 0      // 1: the race build (mopa_race.inc)
-#define MOPA_K3_WG 0
-#define MOPA_K3_WAVES 2
-namespace k3w2 {
-#include "mopa_planner_k3.inc"
-}
-#undef MOPA_K3_WAVES
-#define MOPA_K3_WAVES 1
-namespace k3w1 {
-#include "mopa_planner_k3.inc"
-}
-#undef MOPA_K3_WG
-#define MOPA_K3_WG 1
-namespace k3wg {
-#include "mopa_planner_k3.inc"
-}
-#undef MOPA_K3_WG
-#define MOPA_K3_WG 0
-#undef MOPA_K3_WAVES
+// The race's kernel-side declarations (everything else of the race is mopa_race.inc): the planner body names them.
+struct RaceArgs {
+    long long Eq;                  // queries of the launch (the kernel's E is Eq * K slots)
+    int K;
+    int no_abort;                  // nonzero: the comparison with the race word is off, every member runs to its own end
+    unsigned long long *word;      // [Eq]
+    long long *rec;                // [Eq * K][kRaceRec], slot order
+};
+constexpr int kRaceRec = 8;        // status | consumed checks | iterations | start motion | goal motion | rows of the solution | - | -
+constexpr int kRaceCut = -100;     // record status of a member that stopped because it could no longer win
+constexpr unsigned long long kRaceSeedStep = 0x9E3779B97F4A7C15ull;
 
-// K3 race: the fourth instantiation (namespace k3race), k_race_pick, mopa_plan_race_batch / mopa_plan_race
-#include "mopa_race.inc"
-
-static void plan_register_more();   // kernels defined after this file (mopa_pullback.inc)
-static void plan_register_lds() {
-    (void)hipFuncSetAttribute((const void *)k3w2::k_rrt_connect, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLdsBytes);
-    (void)hipFuncSetAttribute((const void *)k3w1::k_rrt_connect, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLdsBytes);
-    (void)hipFuncSetAttribute((const void *)k3wg::k_rrt_connect, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLdsBytes);
-    (void)hipFuncSetAttribute((const void *)k3race::k_rrt_connect, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLdsBytes);
-    plan_register_more();
-}
+// the planner body: k_rrt_connect<B> for the build tags K3W2, K3W1, K3WG and K3Race
+#include "mopa_planner_k3.inc"
 
 
 #ifdef MOPA_PLAN_STATS
@@ -571,6 +554,57 @@ extern "C" int mopa_debug_plan_mpr_pairs(unsigned *out8192, int reset) {
 }
 #endif
 
+// Launch geometry of the K3 builds that run four queries per workgroup (K3W2 / K3W1 / K3Race), worked out once for mopa_plan_batch
+// and mopa_plan_race_batch: the LDS of a workgroup, the launch's counter, the workgroup count, the FP32 tree mirrors' share.
+struct PlanGeom {
+    int scene_bytes, lds;              // scene blobs; + the four waves' planner slabs + the header's copy
+    int lds_launch, nn_cap;            // what the launch asks for; nodes per query that the FP32 tree mirror holds (nn_fast)
+    int64_t nblk;
+    unsigned long long *ctr;
+};
+// n queries (the race: slots).  `lone`: the launch keeps its CUs to itself whatever the parameters say and reads no A/B knob (the race,
+// whose build holds one wave per SIMD: a CU holds one workgroup at a time).
+static int plan_geometry(MopaScene *S, StreamScratch &sc, int64_t n, int max_workgroups, int max_nodes, bool lone, int exclusive_cu /* read unless lone */, PlanGeom &g) {
+    if (!sc.plan_ctr.p) {       // [next query | waves done]: zeroed once, self-resetting afterwards (tile_ctr_release)
+        HIP_TRY(grow(S, sc.plan_ctr, 64));
+        HIP_TRY(hipMemset(sc.plan_ctr.p, 0, 64));       // (synchronously, once: see the validity kernels' counter in mopa_hip.hip)
+    }
+    g.ctr = sc.plan_ctr.as<unsigned long long>();
+    const int per_wave = plan_vec_bytes(S->na) + ms_bytes_per_wave(S->hdr.nmg, S->na, S->hdr.n_pq, ms_sc_doubles(S->hdr.nmj, S->hdr.nmb), S->hdr.npair);
+    // (the kernel poses states in its multi-state slabs only: the single-state slabs behind the scene blobs are not laid out)
+    g.scene_bytes = S->lds_bytes - kWavesPerBlock * S->hdr.wave_bytes;
+    const int lds = g.lds = g.scene_bytes + kWavesPerBlock * per_wave + (int)sizeof(SceneHdr);
+    if (lds > kMaxLdsBytes) return fail(MOPA_ERR_LIMIT, "planner LDS does not fit");
+    // persistent workgroups: max_workgroups > 0 caps them, < 0 asks for as many as the chip holds at once (two per CU where
+    // LDS allows: throughput, for launches that overlap others), 0 = one per CU -- a lone launch ends with its slowest
+    // query, and two budget-exhausting queries on one SIMD slow each other down
+    const int64_t resident = (int64_t)S->n_cu * (lone ? 1 : std::min(2, std::max(1, kMaxLdsBytes / lds)));
+    // (a launch that keeps the chip to itself spreads few queries one per workgroup -- the kernel's first-query rule; launches that share
+    //  it stay packed four to a workgroup: spread over every CU's LDS they block the launches they overlap with: ladder 478 -> 274 k plans/s)
+    g.nblk = std::min<int64_t>(max_workgroups == 0 ? n : (n + kWavesPerBlock - 1) / kWavesPerBlock, resident);
+    if (max_workgroups > 0) g.nblk = std::min<int64_t>(g.nblk, max_workgroups);
+    else if (max_workgroups == 0) g.nblk = std::min<int64_t>(g.nblk, S->n_cu);
+    // a launch of at most one workgroup per CU asks for more than half a CU's LDS: no second planner workgroup (of this or
+    // of an overlapping launch) can then land on its CUs, whatever the dispatcher's placement
+    bool excl = lone;
+    if (!lone) {
+        const char *ex = std::getenv("MOPA_PLAN_EXCLUSIVE");       // A/B knob: 0 = never, 1 = every launch of <= n_cu workgroups
+        excl = ex ? (ex[0] == '1' && g.nblk <= S->n_cu) : (max_workgroups == 0 || exclusive_cu != 0);
+    }
+    g.lds_launch = excl ? std::max(lds, kMaxLdsBytes / 2 + 1024) : lds;
+    // the rest of the launch's LDS share holds the FP32 tree mirrors of the workgroup's four queries (nn_fast)
+    // (a launch that keeps its CUs to itself takes all of a CU's LDS; one that shares them two workgroups per CU, half)
+    const int share = (g.lds_launch > lds || 2 * lds > kMaxLdsBytes) ? kMaxLdsBytes : kMaxLdsBytes / 2;
+    const int mirror_off = lds + 16;
+    g.nn_cap = ((share - mirror_off) / kWavesPerBlock / (4 * std::max(1, S->na))) & ~63;
+    g.nn_cap = std::max(0, std::min(g.nn_cap, 2 * max_nodes));
+    if (g.lds_launch <= kMaxLdsBytes / 2) g.nn_cap = 0;      // (the two-waves-per-SIMD build does not use the mirror)
+    if (!lone)
+        if (const char *ev = std::getenv("MOPA_PLAN_NN_CAP")) g.nn_cap = std::min(g.nn_cap, std::max(0, atoi(ev)) & ~63);      // A/B knob
+    g.lds_launch = std::max(g.lds_launch, mirror_off + kWavesPerBlock * g.nn_cap * 4 * S->na);
+    return MOPA_OK;
+}
+
 extern "C" int mopa_plan_batch(MopaScene *S, const double *start, const double *goal, int64_t E, const MopaPlanParams *params,
                                double *path, int32_t *path_len, int32_t *status, int64_t *n_checks, void *stream) {
     if (!S || !params || (E > 0 && (!start || !goal || !path || !path_len || !status)))
@@ -586,55 +620,18 @@ extern "C" int mopa_plan_batch(MopaScene *S, const double *start, const double *
     StreamScratch &sc = scratch_for(S, (hipStream_t)stream);
     HIP_TRY(grow(S, sc.plan_q, (size_t)E * 2 * (size_t)params->max_nodes * S->na * sizeof(double) + 64));   // + pad: nn_node8 reads 8 doubles per node
     HIP_TRY(grow(S, sc.plan_p, (size_t)E * 2 * (size_t)params->max_nodes * sizeof(int32_t)));
-    if (!sc.plan_ctr.p) {       // [next query | waves done]: zeroed once, self-resetting afterwards (tile_ctr_release)
-        HIP_TRY(grow(S, sc.plan_ctr, 64));
-        HIP_TRY(hipMemset(sc.plan_ctr.p, 0, 64));       // (synchronously, once: see the validity kernels' counter in mopa_hip.hip)
-    }
     PlanWs ws{sc.plan_q.as<double>(), sc.plan_p.as<int32_t>()};
-    unsigned long long *plan_ctr = sc.plan_ctr.as<unsigned long long>();
-    int per_wave = plan_vec_bytes(S->na) + ms_bytes_per_wave(S->hdr.nmg, S->na, S->hdr.n_pq, ms_sc_doubles(S->hdr.nmj, S->hdr.nmb), S->hdr.npair);
-    // (the kernel poses states in its multi-state slabs only: the single-state slabs behind the scene blobs are not laid out)
-    const int scene_bytes = S->lds_bytes - kWavesPerBlock * S->hdr.wave_bytes;
-    int lds = scene_bytes + kWavesPerBlock * per_wave + (int)sizeof(SceneHdr);
-    if (lds > kMaxLdsBytes) return fail(MOPA_ERR_LIMIT, "planner LDS does not fit");
-    // persistent workgroups: max_workgroups > 0 caps them, < 0 asks for as many as the chip holds at once (two per CU where
-    // LDS allows: throughput, for launches that overlap others), 0 = one per CU -- a lone launch ends with its slowest
-    // query, and two budget-exhausting queries on one SIMD slow each other down
-    const int64_t resident = (int64_t)S->n_cu * std::min(2, std::max(1, kMaxLdsBytes / lds));
-    // (a launch that keeps the chip to itself spreads few queries one per workgroup -- the kernel's first-query rule; launches that share
-    //  it stay packed four to a workgroup: spread over every CU's LDS they block the launches they overlap with: ladder 478 -> 274 k plans/s)
-    int64_t nblk = std::min<int64_t>(params->max_workgroups == 0 ? E : (E + kWavesPerBlock - 1) / kWavesPerBlock, resident);
-    if (params->max_workgroups > 0) nblk = std::min<int64_t>(nblk, params->max_workgroups);
-    else if (params->max_workgroups == 0) nblk = std::min<int64_t>(nblk, S->n_cu);
-    dim3 grid((unsigned)nblk), block(kBlock);
-    // a launch of at most one workgroup per CU asks for more than half a CU's LDS: no second planner workgroup (of this or
-    // of an overlapping launch) can then land on its CUs, whatever the dispatcher's placement
-    int lds_launch = lds;
-    {
-        const char *ex = std::getenv("MOPA_PLAN_EXCLUSIVE");       // A/B knob: 0 = never, 1 = every launch of <= n_cu workgroups
-        const bool excl = ex ? (ex[0] == '1' && nblk <= S->n_cu) : (params->max_workgroups == 0 || params->exclusive_cu != 0);
-        if (excl) lds_launch = std::max(lds, kMaxLdsBytes / 2 + 1024);
-    }
-    // the rest of the launch's LDS share holds the FP32 tree mirrors of the workgroup's four queries (nn_fast)
-    int nn_cap = 0;
-    {
-        // (a launch that keeps its CUs to itself takes all of a CU's LDS; one that shares them two workgroups per CU, half)
-        const int share = (lds_launch > lds || 2 * lds > kMaxLdsBytes) ? kMaxLdsBytes : kMaxLdsBytes / 2;
-        const int mirror_off = lds + 16;
-        nn_cap = ((share - mirror_off) / kWavesPerBlock / (4 * std::max(1, S->na))) & ~63;
-        nn_cap = std::max(0, std::min(nn_cap, 2 * params->max_nodes));
-        if (lds_launch <= kMaxLdsBytes / 2) nn_cap = 0;      // (the two-waves-per-SIMD build does not use the mirror)
-        if (const char *ev = std::getenv("MOPA_PLAN_NN_CAP")) nn_cap = std::min(nn_cap, std::max(0, atoi(ev)) & ~63);      // A/B knob
-        lds_launch = std::max(lds_launch, mirror_off + kWavesPerBlock * nn_cap * 4 * S->na);
-        if (std::getenv("MOPA_DEBUG")) fprintf(stderr, "[mopa] plan launch: %lld queries, %lld workgroups, LDS %d + mirror %d nodes/query = %d bytes\n", (long long)E, (long long)nblk, lds, nn_cap, lds_launch);
-    }
+    PlanGeom g;
+    if (const int rc = plan_geometry(S, sc, E, params->max_workgroups, params->max_nodes, false, params->exclusive_cu, g)) return rc;
+    if (std::getenv("MOPA_DEBUG")) fprintf(stderr, "[mopa] plan launch: %lld queries, %lld workgroups, LDS %d + mirror %d nodes/query = %d bytes\n", (long long)E, (long long)g.nblk, g.lds, g.nn_cap, g.lds_launch);
+    dim3 block(kBlock);
     // a launch that keeps its CUs to itself (lds_launch forces one workgroup per CU) runs a one-wave-per-SIMD build: the workgroup-per-
-    // query one (k3wg: four waves on one query) where it applies, else four queries per workgroup (k3w1).  MOPA_PLAN_BUILD = w1 | w2 | wg
+    // query one (K3WG: four waves on one query) where it applies, else four queries per workgroup (K3W1).  MOPA_PLAN_BUILD = w1 | w2 | wg
     // is the A/B knob (results are the same whatever runs).
-    const bool lone = lds_launch > kMaxLdsBytes / 2;
+    const bool lone = g.lds_launch > kMaxLdsBytes / 2;
     const char *bsel = std::getenv("MOPA_PLAN_BUILD");
     const int per_wave_wg = plan_vec_bytes_wg(S->na) + ms_bytes_per_wave(S->hdr.nmg, S->na, S->hdr.n_pq, ms_sc_doubles(S->hdr.nmj, S->hdr.nmb), S->hdr.npair);
-    const int wg_mirror_off = scene_bytes + kWavesPerBlock * per_wave_wg + (((int)sizeof(SceneHdr) + 15) & ~15) + plan_wg_shared_bytes();
+    const int wg_mirror_off = g.scene_bytes + kWavesPerBlock * per_wave_wg + (((int)sizeof(SceneHdr) + 15) & ~15) + plan_wg_shared_bytes();
     const bool wg_fits = S->na <= 8 && wg_mirror_off + 64 * 4 * S->na <= kMaxLdsBytes;
     bool use_wg = lone && wg_fits;
     if (bsel && bsel[0] == 'w' && bsel[1] == 'g') use_wg = wg_fits;
@@ -647,54 +644,75 @@ extern "C" int mopa_plan_batch(MopaScene *S, const double *start, const double *
         if (const char *ev = std::getenv("MOPA_PLAN_NN_CAP")) cap = std::min(cap, std::max(0, atoi(ev)) & ~63);
         const int lds_wg = std::max(wg_mirror_off + cap * 4 * S->na, kMaxLdsBytes / 2 + 1024);
         if (std::getenv("MOPA_DEBUG")) fprintf(stderr, "[mopa] plan launch (workgroup per query): %lld queries, %lld workgroups, mirror %d nodes, LDS %d bytes\n", (long long)E, (long long)nb, cap, lds_wg);
-        hipLaunchKernelGGL(k3wg::k_rrt_connect, dim3((unsigned)nb), block, lds_wg, (hipStream_t)stream, S->hdr, S->d_dbl, S->d_int, start, goal, (long long)E,
-                           *params, ws, path, path_len, status, (long long *)n_checks, scene_bytes, plan_ctr, cap);
+        hipLaunchKernelGGL(k_rrt_connect<K3WG>, dim3((unsigned)nb), block, lds_wg, (hipStream_t)stream, S->hdr, S->d_dbl, S->d_int, start, goal, (long long)E,
+                           *params, ws, path, path_len, status, (long long *)n_checks, g.scene_bytes, g.ctr, cap, K3NoArgs{});
     } else {
         const bool w1 = (bsel && bsel[0] == 'w' && bsel[1] == '2') ? false : lone;
-        hipLaunchKernelGGL(w1 ? k3w1::k_rrt_connect : k3w2::k_rrt_connect, grid, block, lds_launch, (hipStream_t)stream, S->hdr, S->d_dbl, S->d_int, start, goal, (long long)E,
-                           *params, ws, path, path_len, status, (long long *)n_checks, scene_bytes, plan_ctr, nn_cap);
+        hipLaunchKernelGGL(w1 ? k_rrt_connect<K3W1> : k_rrt_connect<K3W2>, dim3((unsigned)g.nblk), block, g.lds_launch, (hipStream_t)stream, S->hdr, S->d_dbl, S->d_int, start, goal, (long long)E,
+                           *params, ws, path, path_len, status, (long long *)n_checks, g.scene_bytes, g.ctr, g.nn_cap, K3NoArgs{});
     }
     HIP_TRY(hipGetLastError());
     return MOPA_OK;
 }
 
-extern "C" int mopa_plan(MopaScene *S, const double *start_host, const double *goal_host, const MopaPlanParams *params,
-                         double *path_host, int32_t *path_len_out, int32_t *status_out, int64_t *n_checks_out) {
-    if (!S || !start_host || !goal_host || !params || !path_host || !path_len_out || !status_out)
-        return fail(MOPA_ERR_INVALID_ARG, "null argument");
+// The single-query host form of a planner entry (mopa_plan, mopa_plan_race, mopa_plan_star): one device block (start | goal | path |
+// path length, status | the entry's further outputs, `extra_bytes` of them, 8-byte aligned), the batch entry on the default stream
+// through `launch(start, goal, path, path_len, status, extra)`, then length and status, `copy_extra(extra)` and the path's rows back.
+// Synchronous; the block is freed on every path.
+template <class Launch, class CopyExtra>
+static int plan_single(MopaScene *S, const double *start_host, const double *goal_host, int max_path, double *path_host, int32_t *path_len_out,
+                       int32_t *status_out, size_t extra_bytes, Launch launch, CopyExtra copy_extra) {
     ON_DEVICE(S->device);
-    size_t nq = S->nq;
-    size_t path_d = (size_t)params->max_path * nq;
+    const size_t nq = (size_t)S->nq, path_d = (size_t)max_path * nq;
     double *d_buf = nullptr;
-    HIP_TRY(hipMalloc((void **)&d_buf, sizeof(double) * (2 * nq + path_d) + 32));
+    HIP_TRY(hipMalloc((void **)&d_buf, sizeof(double) * (2 * nq + path_d) + 8 + extra_bytes));
     double *d_start = d_buf, *d_goal = d_buf + nq, *d_path = d_buf + 2 * nq;
-    int32_t *d_len = reinterpret_cast<int32_t *>(d_path + path_d);
-    int32_t *d_status = d_len + 1;
-    long long *d_chk = reinterpret_cast<long long *>(d_len + 2);
-    int rc = MOPA_OK;
+    int32_t *d_len = reinterpret_cast<int32_t *>(d_path + path_d), *d_status = d_len + 1;
     hipError_t e = hipMemcpy(d_start, start_host, sizeof(double) * nq, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(d_goal, goal_host, sizeof(double) * nq, hipMemcpyHostToDevice);
     if (e != hipSuccess) { (void)hipFree(d_buf); return fail(MOPA_ERR_HIP, hipGetErrorString(e)); }
-    MopaPlanParams one = *params;
-    one.env_ids_dev = nullptr;   // single query: the stream id is env_id_base
-    one.seeds_dev = nullptr;
-    one.max_workgroups = 0;
-    rc = mopa_plan_batch(S, d_start, d_goal, 1, &one, d_path, d_len, d_status, (int64_t *)d_chk, nullptr);
+    int rc = launch(d_start, d_goal, d_path, d_len, d_status, static_cast<void *>(d_len + 2));
     if (rc == MOPA_OK) {
         int32_t ls[2];
-        long long chk = 0;
-        e = hipMemcpy(ls, d_len, 8, hipMemcpyDeviceToHost);
-        if (e == hipSuccess) e = hipMemcpy(&chk, d_chk, 8, hipMemcpyDeviceToHost);
+        e = hipMemcpy(ls, d_len, 8, hipMemcpyDeviceToHost);        // (the default stream: waits for the launch)
+        if (e == hipSuccess) e = copy_extra(static_cast<const void *>(d_len + 2));
         if (e == hipSuccess && ls[0] > 0) e = hipMemcpy(path_host, d_path, sizeof(double) * (size_t)ls[0] * nq, hipMemcpyDeviceToHost);
         if (e != hipSuccess) rc = fail(MOPA_ERR_HIP, hipGetErrorString(e));
         else {
             *path_len_out = ls[0];
             *status_out = ls[1];
-            if (n_checks_out) *n_checks_out = chk;
             // OMPL PlannerStatus::asString() equivalents (KinematicPlanner.cpp:189)
             S->status = (ls[1] == MOPA_PLAN_OK) ? "Exact solution" : (ls[1] == MOPA_PLAN_INVALID_GOAL ? "Invalid goal" : "Timeout");
         }
     }
     (void)hipFree(d_buf);
     return rc;
+}
+
+extern "C" int mopa_plan(MopaScene *S, const double *start_host, const double *goal_host, const MopaPlanParams *params,
+                         double *path_host, int32_t *path_len_out, int32_t *status_out, int64_t *n_checks_out) {
+    if (!S || !start_host || !goal_host || !params || !path_host || !path_len_out || !status_out)
+        return fail(MOPA_ERR_INVALID_ARG, "null argument");
+    MopaPlanParams one = *params;
+    one.env_ids_dev = nullptr;   // single query: the stream id is env_id_base
+    one.seeds_dev = nullptr;
+    one.max_workgroups = 0;
+    long long chk = 0;
+    const int rc = plan_single(S, start_host, goal_host, params->max_path, path_host, path_len_out, status_out, 8,
+        [&](const double *s, const double *g, double *p, int32_t *len, int32_t *st, void *x) { return mopa_plan_batch(S, s, g, 1, &one, p, len, st, (int64_t *)x, nullptr); },
+        [&](const void *x) { return hipMemcpy(&chk, x, 8, hipMemcpyDeviceToHost); });
+    if (rc == MOPA_OK && n_checks_out) *n_checks_out = chk;
+    return rc;
+}
+
+// K3 race: RaceArgs, k_race_pick, mopa_plan_race_batch / mopa_plan_race
+#include "mopa_race.inc"
+
+static void plan_register_more();   // kernels defined after this file (mopa_pullback.inc)
+static void plan_register_lds() {
+    (void)hipFuncSetAttribute((const void *)k_rrt_connect<K3W2>, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLdsBytes);
+    (void)hipFuncSetAttribute((const void *)k_rrt_connect<K3W1>, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLdsBytes);
+    (void)hipFuncSetAttribute((const void *)k_rrt_connect<K3WG>, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLdsBytes);
+    (void)hipFuncSetAttribute((const void *)k_rrt_connect<K3Race>, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLdsBytes);
+    plan_register_more();
 }

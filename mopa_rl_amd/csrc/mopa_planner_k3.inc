@@ -1,19 +1,29 @@
 // mopa_planner_k3.inc -- the body of K3 (planner context, motion validation, nearest neighbour, speculation, growTree and the
-// kernel), included TWICE by mopa_planner.inc, once per occupancy the kernel is built for:
-//   namespace k3w2, MOPA_K3_WAVES 2: two waves per SIMD (256 registers) -- launches that share the chip (the ladder's first
-//                   launches, the rollouts' planner streams): a second wave on the SIMD is nearly free throughput;
-//   namespace k3w1, MOPA_K3_WAVES 1: one wave per SIMD (512 registers, nothing spilled) -- launches that keep their CUs to
-//                   themselves (a lone full-budget launch, retry launches): what counts there is the latency of one query.
-//   namespace k3wg, MOPA_K3_WG 1 (MOPA_K3_WAVES 1): ONE query per workgroup of four waves -- a budget-exhausting query alone on
-//                   its CU gets all four SIMDs.  Every wave runs the sequential algorithm (same data, same control flow, so no
-//                   wave ever waits for another outside a validity pass); AT a pass wave 0 evaluates the states the algorithm
-//                   asks about while waves 1-3 work out what the NEXT iterations will ask (their samples are known in advance:
-//                   nearest node, steered state, first connect state) and evaluate those.  Nearest neighbours and verdicts of
-//                   future iterations wait in a small table (kFSlots entries) and are used only when the sequential algorithm
-//                   arrives at exactly that query / that state: results and consumed-check counts cannot change.
-//   namespace k3race, MOPA_K3_RACE 1 on the k3w1 settings (mopa_race.inc): launch slot v is member v / Eq of query v % Eq; a member
-//                   leaves a record instead of path rows and stops when the query's race word says that it can no longer win.
-// Same source, same results; only register allocation and the few MOPA_K3_WAVES / MOPA_K3_WG / MOPA_K3_RACE switches below differ.
+// kernel), included once by mopa_planner.inc.  The kernel and the few helpers that differ between builds are templates over a
+// build tag B; k_rrt_connect<B> is instantiated for four tags (their names are the kernels' names in traces and resource tables):
+//   K3W2    kWaves 2: two waves per SIMD (256 registers) -- launches that share the chip (the ladder's first launches, the
+//           rollouts' planner streams): a second wave on the SIMD is nearly free throughput.  The FP32 mirror sweeps (nn_fast)
+//           are not instantiated and no first-query flag is kept.
+//   K3W1    kWaves 1: one wave per SIMD (512 registers, nothing spilled) -- launches that keep their CUs to themselves (a lone
+//           full-budget launch, retry launches): what counts there is the latency of one query.  A wave's first query is fixed
+//           by its place; nearest neighbours go through the FP32 mirror in LDS.
+//   K3WG    kWg (kWaves 1): ONE query per workgroup of four waves -- a budget-exhausting query alone on its CU gets all four
+//           SIMDs.  Every wave runs the sequential algorithm (same data, same control flow, so no wave ever waits for another
+//           outside a validity pass); AT a pass wave 0 evaluates the states the algorithm asks about while waves 1-3 work out
+//           what the NEXT iterations will ask (their samples are known in advance: nearest node, steered state, first connect
+//           state) and evaluate those.  Nearest neighbours and verdicts of future iterations wait in a small table (kFSlots
+//           entries) and are used only when the sequential algorithm arrives at exactly that query / that state: results and
+//           consumed-check counts cannot change.  Changes: the query fetch, the pass of plan_check_motion, the first
+//           speculation and the table look-ups of plan_grow; only wave 0 writes outputs.
+//   K3Race  kRace on the K3W1 settings (mopa_race.inc): launch slot v is member v / Eq of query v % Eq; a member leaves a
+//           record instead of path rows and stops when the query's race word says that it can no longer win.  The kernel takes
+//           one more argument (RaceArgs).
+// Same source, same results; only register allocation and the `if constexpr` switches on the tag below differ.
+struct K3W2 { static constexpr int kWaves = 2; static constexpr bool kWg = false, kRace = false; };
+struct K3W1 { static constexpr int kWaves = 1; static constexpr bool kWg = false, kRace = false; };
+struct K3WG { static constexpr int kWaves = 1; static constexpr bool kWg = true, kRace = false; };
+struct K3Race { static constexpr int kWaves = 1; static constexpr bool kWg = false, kRace = true; };
+struct K3NoArgs {};    // what the builds other than K3Race take in place of RaceArgs (mopa_planner.inc, in front of this file)
 struct PlanCtx {
     LdsView v;
     const SceneHdr *lh;    // the scene header's copy in LDS (what the non-inlined validity routines read)
@@ -51,7 +61,10 @@ struct PlanCtx {
     long long n_checks;
     int xmotion;
     bool overflow;
-#if MOPA_K3_WG
+};
+// the workgroup-per-query build's context (a type of its own: K3W1 and K3Race keep the context in their scratch frame, where members
+// that those builds never touch would still take their 80 bytes per lane)
+struct PlanCtxWg : PlanCtx {
     int wave;              // 0: evaluates what the algorithm asks; 1-3: future iterations
     double *ftab;          // LDS [kFSlots][kFStride], this wave's copy of the future table (all copies are equal)
     double *mbox;          // LDS, shared: [2 parities][4 waves][kMbStride]
@@ -62,8 +75,8 @@ struct PlanCtx {
 #ifdef MOPA_PLAN_STATS
     long long st_fnn = 0, st_fmemo = 0, st_fstates = 0, st_fast = 0, st_c0 = 0, st_c1 = 0, st_c2 = 0, st_c3 = 0;
 #endif
-#endif
 };
+template <class B> using K3Ctx = std::conditional_t<B::kWg, PlanCtxWg, PlanCtx>;
 
 MOPA_D int tree_n(const PlanCtx &c, int t) { return t ? c.n1 : c.n0; }
 MOPA_D double *tree_q(const PlanCtx &c, int t) { return t ? c.tq1 : c.tq0; }
@@ -71,6 +84,8 @@ MOPA_D int32_t *tree_p(const PlanCtx &c, int t) { return t ? c.tp1 : c.tp0; }
 
 // K3's own non-inlined copy for its two cold checks (goal, start): a device function inherits a kernel's register limit only
 // when ALL its callers carry it, and k_rrt_connect is held to two waves per SIMD while the pull-back kernel is not.
+// (a template over the build tag for the same reason: one copy per build, called by that build's kernel alone)
+template <class B>
 __device__ __noinline__ unsigned plan_states_valid_ms_k3(const SceneHdr *hp, const double *dbl, const int *ints, double *ms_grec,
                                                          double *ms_qbuf, unsigned *ms_wl, const double *ms_qs, int lane, int ns,
                                                          const double *row) {
@@ -328,45 +343,44 @@ MOPA_D void nn_mirror_sweep(const PlanCtx &c, int na, int t, int cnt, const doub
         if (TWO) { nn_key_update(kb, db1, i, true); nn_key_update(kb, db2, i2, live2); }
     }
 }
-template <bool TWO>
+template <class B, bool TWO>
 MOPA_D bool nn_fast(const SceneHdr &h, PlanCtx &c, int t, const double *qa, const double *qb, int &ia, int &ib) {
-#if MOPA_K3_WAVES == 2
-    return false;       // (256-register build: the sweep's registers would be spilled around every call; it keeps the FP64 sweeps)
-#else
-    const int n = tree_n(c, t), na = h.na;
-    if (na > 8) return false;
-    const int cnt = t ? c.nn_cnt1 : c.nn_cnt0;
-    NnKey ka{3.0e38f, 3.0e38f, 0x7fffffff}, kb{3.0e38f, 3.0e38f, 0x7fffffff};
-    if (cnt > 0) {
-        if (na == 7 && c.so2 == 0ull) nn_mirror_sweep<TWO, 7>(c, na, t, cnt, qa, qb, ka, kb);
-        else nn_mirror_sweep<TWO, 0>(c, na, t, cnt, qa, qb, ka, kb);
-    }
-    if (cnt < n) {       // the part of the tree that is not mirrored: FP64 from HBM, as plan_nearest
+    if constexpr (B::kWaves == 2) return false;       // (256-register build: the sweep's registers would be spilled around every call; it keeps the FP64 sweeps)
+    else {
+        const int n = tree_n(c, t), na = h.na;
+        if (na > 8) return false;
+        const int cnt = t ? c.nn_cnt1 : c.nn_cnt0;
+        NnKey ka{3.0e38f, 3.0e38f, 0x7fffffff}, kb{3.0e38f, 3.0e38f, 0x7fffffff};
+        if (cnt > 0) {
+            if (na == 7 && c.so2 == 0ull) nn_mirror_sweep<TWO, 7>(c, na, t, cnt, qa, qb, ka, kb);
+            else nn_mirror_sweep<TWO, 0>(c, na, t, cnt, qa, qb, ka, kb);
+        }
+        if (cnt < n) {       // the part of the tree that is not mirrored: FP64 from HBM, as plan_nearest
             const double *tq = tree_q(c, t);
-        const NnQuery QA = nn_query(qa, na), QB = nn_query(TWO ? qb : qa, na);
-        for (int i = cnt + c.lane; i < n; i += 64 * kNnU2) {
-            double x[kNnU2][8];
+            const NnQuery QA = nn_query(qa, na), QB = nn_query(TWO ? qb : qa, na);
+            for (int i = cnt + c.lane; i < n; i += 64 * kNnU2) {
+                double x[kNnU2][8];
 #pragma unroll
-            for (int u = 0; u < kNnU2; u++) {
-                const int iu = i + 64 * u;
-                nn_node8(tq + (size_t)(iu < n ? iu : i) * na, na, x[u]);
-            }
+                for (int u = 0; u < kNnU2; u++) {
+                    const int iu = i + 64 * u;
+                    nn_node8(tq + (size_t)(iu < n ? iu : i) * na, na, x[u]);
+                }
 #pragma unroll
-            for (int u = 0; u < kNnU2; u++) {
-                const int iu = i + 64 * u;
-                nn_key_update(ka, (float)nn_dist8(x[u], QA, c.so2), iu, iu < n);
-                if (TWO) nn_key_update(kb, (float)nn_dist8(x[u], QB, c.so2), iu, iu < n);
+                for (int u = 0; u < kNnU2; u++) {
+                    const int iu = i + 64 * u;
+                    nn_key_update(ka, (float)nn_dist8(x[u], QA, c.so2), iu, iu < n);
+                    if (TWO) nn_key_update(kb, (float)nn_dist8(x[u], QB, c.so2), iu, iu < n);
+                }
             }
         }
+        ia = nn_resolve(ka, c.nn_eps2);
+        if (ia < 0) return false;
+        if (TWO) {
+            ib = nn_resolve(kb, c.nn_eps2);
+            if (ib < 0) return false;
+        }
+        return true;
     }
-    ia = nn_resolve(ka, c.nn_eps2);
-    if (ia < 0) return false;
-    if (TWO) {
-        ib = nn_resolve(kb, c.nn_eps2);
-        if (ib < 0) return false;
-    }
-    return true;
-#endif
 }
 // a node joins the mirror when every earlier node of its tree is in it and a slot is free
 MOPA_D void nn_mirror_put(const SceneHdr &h, PlanCtx &c, int t, int i, const double *q /*[na]*/) {
@@ -377,8 +391,7 @@ MOPA_D void nn_mirror_put(const SceneHdr &h, PlanCtx &c, int t, int i, const dou
     if (t) c.nn_cnt1++; else c.nn_cnt0++;
 }
 
-#if MOPA_K3_WG
-// ---- workgroup-per-query build: the future table ---------------------------------------------------------------
+// ---- workgroup-per-query build: the future table (reached from the kWg branches only) ---------------------------
 MOPA_D int wg_rfl(int x) { return __builtin_amdgcn_readfirstlane(x); }
 // FP64 distance of a tree node (global memory) from q (LDS): the sum of plan_dist_l1 / nn_dist8, same terms in the same order
 MOPA_D double wg_dist_node(const SceneHdr &h, const PlanCtx &c, const double *node, const double *q) {
@@ -424,7 +437,7 @@ MOPA_D int wg_refine(const SceneHdr &h, PlanCtx &c, int t, const double *q, int 
 // anything else: nothing.  A tree that grew by a few nodes since the entry was made is caught up exactly: the recorded node is the
 // nearest of the first `size` nodes (lowest index among equals), so only the new ones are compared -- strictly smaller wins, as in
 // the sweep.
-MOPA_D int wg_nn_lookup(const SceneHdr &h, PlanCtx &c, int t, int it, int role, const double *q) {
+MOPA_D int wg_nn_lookup(const SceneHdr &h, PlanCtxWg &c, int t, int it, int role, const double *q) {
     if (role > 1) return -1;
     const double *e = c.ftab + (it & (kFSlots - 1)) * kFStride;
     const int *ei = reinterpret_cast<const int *>(e);
@@ -447,7 +460,7 @@ MOPA_D int wg_nn_lookup(const SceneHdr &h, PlanCtx &c, int t, int it, int role, 
     return idx;
 }
 // verdict of `dstate` if the table holds exactly that state for this call: 0 / 1, else -1
-MOPA_D int wg_memo_lookup(const SceneHdr &h, PlanCtx &c, int it, int role, const double *dstate) {
+MOPA_D int wg_memo_lookup(const SceneHdr &h, PlanCtxWg &c, int it, int role, const double *dstate) {
     if (role > 1) return -1;
     const double *e = c.ftab + (it & (kFSlots - 1)) * kFStride;
     const int *ei = reinterpret_cast<const int *>(e);
@@ -463,7 +476,7 @@ MOPA_D int wg_memo_lookup(const SceneHdr &h, PlanCtx &c, int it, int role, const
 }
 // which future iterations wave 1 / 2 / 3 takes at this pass: the not yet tabulated ones among it+1 .. it+kFSlots-1, in pairs of the same
 // parity (their nearest-neighbour sweeps run over the same tree and are fused), the nearest iteration's parity first
-MOPA_D void wg_assign(const SceneHdr &h, const PlanCtx &c, int it, int &ja, int &jb, unsigned &idle /* bit w: wave w has no iteration to work out */) {
+MOPA_D void wg_assign(const SceneHdr &h, const PlanCtxWg &c, int it, int &ja, int &jb, unsigned &idle /* bit w: wave w has no iteration to work out */) {
     bool und = false;
     if (c.lane >= 1 && c.lane < kFSlots) {
         const int j = it + c.lane;
@@ -490,7 +503,8 @@ MOPA_D void wg_assign(const SceneHdr &h, const PlanCtx &c, int it, int &ja, int 
 // here -- after the pass's first barrier every wave has every entry and the states without a verdict are shared out over all sixteen
 // slots of the workgroup (wg_complete).  Da_given (wave 0): iteration ja's D is the state the algorithm is testing now -- only its
 // connect step is prepared (Da_valid: its verdict is already known to be "valid").
-MOPA_D void wg_speculate(const SceneHdr &h, PlanCtx &c, int ja, int jb, const double *Da_given, bool Da_valid, double *mb, int &n_ent) {
+template <class B>
+MOPA_D void wg_speculate(const SceneHdr &h, PlanCtxWg &c, int ja, int jb, const double *Da_given, bool Da_valid, double *mb, int &n_ent) {
     const int na = h.na, lane = c.lane;
     double *ea = mb + kMbHdr, *eb = ea + kFStride;
     int *ia = reinterpret_cast<int *>(ea), *ib = reinterpret_cast<int *>(eb);
@@ -521,7 +535,7 @@ MOPA_D void wg_speculate(const SceneHdr &h, PlanCtx &c, int ja, int jb, const do
         const double *q0 = stage ? (a_live ? Da : Db) : c.f0;
         const double *q1 = stage ? (b_live ? Db : Da) : c.f1;
         int i0, i1;
-        if (!nn_fast<true>(h, c, tr, q0, q1, i0, i1)) plan_nearest2(h, c, tr, q0, q1, i0, i1);
+        if (!nn_fast<B, true>(h, c, tr, q0, q1, i0, i1)) plan_nearest2(h, c, tr, q0, q1, i0, i1);
         const int sz = tree_n(c, tr);
         for (int x = 0; x < 2; x++) {
             if (!(x ? b_live : a_live)) continue;
@@ -577,7 +591,7 @@ MOPA_D void wg_speculate(const SceneHdr &h, PlanCtx &c, int ja, int jb, const do
 }
 // after the pass's first barrier: every wave copies every wave's entries into its own table (slot = iteration modulo kFSlots; the
 // iterations of one pass are distinct modulo kFSlots: the current one and futures up to it+kFSlots-1)
-MOPA_D void wg_merge(PlanCtx &c) {
+MOPA_D void wg_merge(PlanCtxWg &c) {
     const double *base = c.mbox + (size_t)(c.pass_par * kWavesPerBlock) * kMbStride;
     for (int idx = c.lane; idx < kWavesPerBlock * 2 * kFStride; idx += 64) {
         const int ent = idx / kFStride, word = idx - ent * kFStride;
@@ -594,7 +608,7 @@ MOPA_D void wg_merge(PlanCtx &c) {
 // iterations it .. it+kFSlots-1, nearest first; D, its interior state, CF, its interior state in that order (of the current iteration
 // only the connect step: its D is what the algorithm is testing) -- and takes its share from the top: wave 0 what its own batch leaves
 // (cap0), then four each for waves 1, 2, 3.  What a wave takes it records in its mailbox header (iteration, kind).
-MOPA_D void wg_complete(const SceneHdr &h, PlanCtx &c, int it, double *mb, int &ns, int &n_comp, unsigned &comp_slots, int cap0) {
+MOPA_D void wg_complete(const SceneHdr &h, PlanCtxWg &c, int it, double *mb, int &ns, int &n_comp, unsigned &comp_slots, int cap0) {
     n_comp = 0; comp_slots = 0u;
     int m = 0;
     if (c.lane < kFSlots) {
@@ -633,7 +647,7 @@ MOPA_D void wg_complete(const SceneHdr &h, PlanCtx &c, int it, double *mb, int &
     wave_sync();
 }
 // header of this wave's mailbox block: its batch's verdict bits, and the verdicts of the table states it took as flag bits
-MOPA_D void wg_publish(const PlanCtx &c, double *mb, int my_ns, unsigned my_ok, int n_comp, unsigned comp_slots) {
+MOPA_D void wg_publish(const PlanCtxWg &c, double *mb, int my_ns, unsigned my_ok, int n_comp, unsigned comp_slots) {
     if (c.lane == 0) {
         int *mbi = reinterpret_cast<int *>(mb);
         mbi[0] = my_ns; mbi[1] = (int)my_ok; mbi[3] = n_comp;
@@ -645,7 +659,7 @@ MOPA_D void wg_publish(const PlanCtx &c, double *mb, int my_ns, unsigned my_ok, 
     }
 }
 // after the pass's second barrier: the verdicts every wave found, into this wave's table
-MOPA_D void wg_apply(PlanCtx &c) {
+MOPA_D void wg_apply(PlanCtxWg &c) {
     const double *base = c.mbox + (size_t)(c.pass_par * kWavesPerBlock) * kMbStride;
     if (c.lane < 4 * kWavesPerBlock) {
         const int *wh = reinterpret_cast<const int *>(base + (size_t)(c.lane >> 2) * kMbStride);
@@ -658,7 +672,6 @@ MOPA_D void wg_apply(PlanCtx &c) {
     }
     wave_sync();
 }
-#endif
 
 // OMPL DiscreteMotionValidator::checkMotion(a, b), optionally preceded by isValid(pre) (growTree tests the new
 // state before the motion when it grows the goal tree).  OMPL's order -- [pre], end state b, then the interior
@@ -666,7 +679,8 @@ MOPA_D void wg_apply(PlanCtx &c) {
 // consumed checks is what the sequential loop would have consumed (up to and including the first invalid one).
 // Free slots of a pass carry the queued speculative states (c.spec_q); a lead state whose verdict is already in
 // the memo is counted but not evaluated again.
-MOPA_D bool plan_check_motion(const SceneHdr &h, PlanCtx &c, const double *a, const double *b, const double *pre, int lead_v /* verdict of the lead state if known: 0 / 1, else -1 */) {
+template <class B>
+MOPA_D bool plan_check_motion(const SceneHdr &h, K3Ctx<B> &c, const double *a, const double *b, const double *pre, int lead_v /* verdict of the lead state if known: 0 / 1, else -1 */) {
     const int na = h.na;
     const double *lead = pre ? pre : b;
     bool lead_known = false;
@@ -714,18 +728,17 @@ MOPA_D bool plan_check_motion(const SceneHdr &h, PlanCtx &c, const double *a, co
             ns++; n_spec++;
         }
         wave_sync();
-#if MOPA_K3_WG
-        // every wave arrives here with the same batch; wave 0 evaluates it (plus the connect step's first state), the others replace
-        // it by states of future iterations; one barrier, then every wave takes wave 0's verdicts and files everybody's findings
         unsigned ok;
-        {
+        if constexpr (B::kWg) {
+            // every wave arrives here with the same batch; wave 0 evaluates it (plus the connect step's first state), the others replace
+            // it by states of future iterations; one barrier, then every wave takes wave 0's verdicts and files everybody's findings
             double *mb = c.mbox + (size_t)(c.pass_par * kWavesPerBlock + c.wave) * kMbStride;
             int n_ent = 0, ja, jb;
             unsigned idle;
             wg_assign(h, c, c.cur_it, ja, jb, idle);
             if (c.wave == 0) {
-                if (c.sp_pending) wg_speculate(h, c, c.sp_it, -1, lead, !lead_in_batch, mb, n_ent);
-            } else if (ja >= 0) wg_speculate(h, c, ja, jb, nullptr, false, mb, n_ent);
+                if (c.sp_pending) wg_speculate<B>(h, c, c.sp_it, -1, lead, !lead_in_batch, mb, n_ent);
+            } else if (ja >= 0) wg_speculate<B>(h, c, ja, jb, nullptr, false, mb, n_ent);
             if (c.lane == 0) reinterpret_cast<int *>(mb)[2] = n_ent;
             __syncthreads();
             wg_merge(c);
@@ -745,10 +758,7 @@ MOPA_D bool plan_check_motion(const SceneHdr &h, PlanCtx &c, const double *a, co
             c.st_fstates += my_ns;
             { const int cause = lead_in_batch ? c.cur_role : 3; if (cause == 0) c.st_c0++; else if (cause == 1) c.st_c1++; else if (cause == 2) c.st_c2++; else c.st_c3++; }
 #endif
-        }
-#else
-        const unsigned ok = plan_states_valid_ms_body<false>(c.lh, c.v.dbl, c.v.ints, c.ms.grec, c.ms.qbuf, c.ms.wl, c.ms.qs, c.lane, ns, c.row);
-#endif
+        } else ok = plan_states_valid_ms_body<false>(c.lh, c.v.dbl, c.v.ints, c.ms.grec, c.ms.qbuf, c.ms.wl, c.ms.qs, c.lane, ns, c.row);
 #ifdef MOPA_PLAN_STATS
         c.st_pass++; c.st_states += ns;
 #endif
@@ -807,15 +817,16 @@ enum { SPEC_NONE = 0, SPEC_FIRST = 1, SPEC_CONNECT = 2 };
 //               added now is the nearest node next time.
 // A wrong guess costs a slot of a pass that runs anyway; verdicts are looked up by exact state, so it can
 // never change a result.
-MOPA_D void plan_speculate(const SceneHdr &h, PlanCtx &c, int mode, int t, const double *dstate, bool reach, int it) {
+template <class B>
+MOPA_D void plan_speculate(const SceneHdr &h, K3Ctx<B> &c, int mode, int t, const double *dstate, bool reach, int it) {
     const int na = h.na;
     c.spec_n = 0;
-#if MOPA_K3_WG
-    if (mode == SPEC_FIRST) {       // worked out AT the pass, by wave 0, next to the other waves' future iterations (wg_speculate)
-        c.sp_pending = true; c.sp_it = it;
-        return;
+    if constexpr (B::kWg) {
+        if (mode == SPEC_FIRST) {       // worked out AT the pass, by wave 0, next to the other waves' future iterations (wg_speculate)
+            c.sp_pending = true; c.sp_it = it;
+            return;
+        }
     }
-#endif
     if (mode == SPEC_FIRST) {
         const int o = 1 - t;
         const bool want2 = it + 1 < c.max_iters;
@@ -830,7 +841,7 @@ MOPA_D void plan_speculate(const SceneHdr &h, PlanCtx &c, int mode, int t, const
         int ia, ib;
         const int lane = c.lane; (void)lane;
         { PLAN_T0();
-        if (!(want2 ? nn_fast<true>(h, c, o, c.nn_q, c.nn_q + na, ia, ib) : nn_fast<false>(h, c, o, c.nn_q, c.nn_q, ia, ib))) {
+        if (!(want2 ? nn_fast<B, true>(h, c, o, c.nn_q, c.nn_q + na, ia, ib) : nn_fast<B, false>(h, c, o, c.nn_q, c.nn_q, ia, ib))) {
 #ifdef MOPA_PLAN_STATS
             if (threadIdx.x == 0) atomicAdd(&g_plan_t[47], 1ull);
 #endif
@@ -886,68 +897,66 @@ MOPA_D void plan_append(const SceneHdr &h, PlanCtx &c, int t, int nm, const doub
 }
 
 // OMPL RRTConnect::growTree(tree, tgi, rmotion)
-MOPA_D int plan_grow(const SceneHdr &h, PlanCtx &c, int t, bool is_start, int spec_mode, int it, int role /* k3wg: 0 = the iteration's first call, 1 = first call of its connect step, 2 = later ones */) {
+template <class B>
+MOPA_D int plan_grow(const SceneHdr &h, K3Ctx<B> &c, int t, bool is_start, int spec_mode, int it, int role /* K3WG: 0 = the iteration's first call, 1 = first call of its connect step, 2 = later ones */) {
     const int lane = c.lane; (void)lane;
     int nm;
-#if MOPA_K3_WG
-    c.sp_pending = false;
-    c.cur_role = role;
-    if (role <= 1) {
-        // the whole call from the table: nearest node unchanged (tree as it was) -> the steering outcome, the state, the segment count
-        // of its motion and (if it was evaluated) its verdict are the ones recorded; what is left is the bookkeeping of growTree
-        PLAN_T0();
-        const double *e = c.ftab + (it & (kFSlots - 1)) * kFStride;
-        const int4 e03 = *reinterpret_cast<const int4 *>(e), e47 = *reinterpret_cast<const int4 *>(e + 2);      // the entry's eight ints in one go
-        const int fl = wg_rfl(e03.y);
-        const int need = role ? (FF_NNC | FF_DS) : FF_NND;
-        const int cur = tree_n(c, t), size = wg_rfl(role ? e47.x : e03.z);
-        if (wg_rfl(e03.x) == it && (fl & need) == need && size <= cur && cur - size <= 32 && (role == 0 || plan_same_state(c, h.na, e + FO_D, c.rs))) {
-            int gs = -1;
-            const int idx = wg_rfl(role ? e47.y : e03.w);
-            if (size < cur && wg_refine(h, c, t, c.rs, idx, size, cur) != idx) gs = -2;        // another node is nearer now: the general path
-            else if (fl & (role ? FF_CTRAP : FF_DTRAP)) gs = GROW_TRAPPED;
-            else if (fl & (role ? FF_CS : FF_DS)) {
-                int v = -1;
-                if (role == 0) { if (fl & FF_D) v = (fl & FF_DOK) ? 1 : 0; }
-                else if (fl & FF_CREACH) v = 1;        // (the state the first call has just added)
-                else if (fl & FF_C) v = (fl & FF_COK) ? 1 : 0;
-                const int nd = wg_rfl(role ? e47.w : e47.z);
-                const int iv = nd < 2 ? 1 : ((nd == 2 && (fl & (role ? FF_CI : FF_DI))) ? ((fl & (role ? FF_CIOK : FF_DIOK)) ? 1 : 0) : -1);
-                if (cur >= c.cap) gs = GROW_TRAPPED;
-                else if (v == 0) { c.n_checks++; gs = GROW_TRAPPED; }
-                else if (v == 1 && iv >= 0) {
-                    c.n_checks += (is_start ? 1 : 2) + (nd < 2 ? 0 : 1);      // the new state [, the tree node behind it], the interior state
-                    if (!iv) gs = GROW_TRAPPED;
-                    else {
-                        const double *ds = e + (role ? FO_C : FO_D);
-                        const bool rch = (fl & (role ? FF_CREACH : FF_DREACH)) != 0;
-                        if (!rch && lane < h.na) c.xs[lane] = ds[lane];
-                        plan_append(h, c, t, idx, ds);
-                        gs = rch ? GROW_REACHED : GROW_ADVANCED;
+    if constexpr (B::kWg) {
+        c.sp_pending = false;
+        c.cur_role = role;
+        if (role <= 1) {
+            // the whole call from the table: nearest node unchanged (tree as it was) -> the steering outcome, the state, the segment count
+            // of its motion and (if it was evaluated) its verdict are the ones recorded; what is left is the bookkeeping of growTree
+            PLAN_T0();
+            const double *e = c.ftab + (it & (kFSlots - 1)) * kFStride;
+            const int4 e03 = *reinterpret_cast<const int4 *>(e), e47 = *reinterpret_cast<const int4 *>(e + 2);      // the entry's eight ints in one go
+            const int fl = wg_rfl(e03.y);
+            const int need = role ? (FF_NNC | FF_DS) : FF_NND;
+            const int cur = tree_n(c, t), size = wg_rfl(role ? e47.x : e03.z);
+            if (wg_rfl(e03.x) == it && (fl & need) == need && size <= cur && cur - size <= 32 && (role == 0 || plan_same_state(c, h.na, e + FO_D, c.rs))) {
+                int gs = -1;
+                const int idx = wg_rfl(role ? e47.y : e03.w);
+                if (size < cur && wg_refine(h, c, t, c.rs, idx, size, cur) != idx) gs = -2;        // another node is nearer now: the general path
+                else if (fl & (role ? FF_CTRAP : FF_DTRAP)) gs = GROW_TRAPPED;
+                else if (fl & (role ? FF_CS : FF_DS)) {
+                    int v = -1;
+                    if (role == 0) { if (fl & FF_D) v = (fl & FF_DOK) ? 1 : 0; }
+                    else if (fl & FF_CREACH) v = 1;        // (the state the first call has just added)
+                    else if (fl & FF_C) v = (fl & FF_COK) ? 1 : 0;
+                    const int nd = wg_rfl(role ? e47.w : e47.z);
+                    const int iv = nd < 2 ? 1 : ((nd == 2 && (fl & (role ? FF_CI : FF_DI))) ? ((fl & (role ? FF_CIOK : FF_DIOK)) ? 1 : 0) : -1);
+                    if (cur >= c.cap) gs = GROW_TRAPPED;
+                    else if (v == 0) { c.n_checks++; gs = GROW_TRAPPED; }
+                    else if (v == 1 && iv >= 0) {
+                        c.n_checks += (is_start ? 1 : 2) + (nd < 2 ? 0 : 1);      // the new state [, the tree node behind it], the interior state
+                        if (!iv) gs = GROW_TRAPPED;
+                        else {
+                            const double *ds = e + (role ? FO_C : FO_D);
+                            const bool rch = (fl & (role ? FF_CREACH : FF_DREACH)) != 0;
+                            if (!rch && lane < h.na) c.xs[lane] = ds[lane];
+                            plan_append(h, c, t, idx, ds);
+                            gs = rch ? GROW_REACHED : GROW_ADVANCED;
+                        }
                     }
                 }
-            }
-            if (gs >= 0) {
+                if (gs >= 0) {
 #ifdef MOPA_PLAN_STATS
-                c.st_fast++;
+                    c.st_fast++;
 #endif
-                PLAN_T(39);
-                return gs;
+                    PLAN_T(39);
+                    return gs;
+                }
             }
+            PLAN_T(39);
         }
-        PLAN_T(39);
     }
-#endif
     {
         PLAN_T0();
-#if MOPA_K3_WG
-        nm = wg_nn_lookup(h, c, t, it, role, c.rs);
-#else
-        nm = nn_known(h, c, t, c.rs);
-#endif
+        if constexpr (B::kWg) nm = wg_nn_lookup(h, c, t, it, role, c.rs);
+        else nm = nn_known(h, c, t, c.rs);
         if (nm < 0) {
             int dummy;
-            if (!nn_fast<false>(h, c, t, c.rs, c.rs, nm, dummy)) {
+            if (!nn_fast<B, false>(h, c, t, c.rs, c.rs, nm, dummy)) {
 #ifdef MOPA_PLAN_STATS
                 if (threadIdx.x == 0) atomicAdd(&g_plan_t[47], 1ull);
 #endif
@@ -979,10 +988,10 @@ MOPA_D int plan_grow(const SceneHdr &h, PlanCtx &c, int t, bool is_start, int sp
         PLAN_T0();
         const int lead_k = memo_find(h, c, dstate);
         lead_v = lead_k >= 0 ? (int)((c.memo_ok >> lead_k) & 1u) : -1;
-#if MOPA_K3_WG
-        if (lead_v < 0) lead_v = wg_memo_lookup(h, c, it, role, dstate);
-#endif
-        if (lead_v != 0) plan_speculate(h, c, spec_mode, t, dstate, reach, it);
+        if constexpr (B::kWg) {
+            if (lead_v < 0) lead_v = wg_memo_lookup(h, c, it, role, dstate);
+        }
+        if (lead_v != 0) plan_speculate<B>(h, c, spec_mode, t, dstate, reach, it);
         else c.spec_n = 0;
         PLAN_T(7);
     }
@@ -990,7 +999,7 @@ MOPA_D int plan_grow(const SceneHdr &h, PlanCtx &c, int t, bool is_start, int sp
 #ifdef MOPA_PLAN_STATS
     const unsigned long long tcm0_ = wall_clock64();
 #endif
-    const bool ok = plan_check_motion(h, c, is_start ? c.ns : dstate, is_start ? dstate : c.ns, is_start ? nullptr : dstate, lead_v);
+    const bool ok = plan_check_motion<B>(h, c, is_start ? c.ns : dstate, is_start ? dstate : c.ns, is_start ? nullptr : dstate, lead_v);
 #ifdef MOPA_PLAN_STATS
     if (threadIdx.x == 0) atomicAdd(&g_plan_t[49], wall_clock64() - tcm0_);
     const unsigned long long tap0_ = wall_clock64();
@@ -1003,30 +1012,48 @@ MOPA_D int plan_grow(const SceneHdr &h, PlanCtx &c, int t, bool is_start, int sp
     return reach ? GROW_REACHED : GROW_ADVANCED;
 }
 
+// A solution's rows into the caller's path (k_rrt_connect; k_race_pick for the race's winner): the start tree's chain from node sm backwards
+// into rows n1-1 .. 0, the goal tree's from node gm forwards into rows n1 ...  Per row the env row first, then -- behind a fence -- the
+// active entries: their columns may alias columns of the env row.  GUARDED (k_race_pick, which walks what another kernel recorded): a node
+// index outside the tree, or a row outside the solution's `total` rows or the path's max_path, ends the walk; the unguarded form takes no guards.
+template <bool GUARDED>
+MOPA_D void plan_write_rows(int lane, int na, int nq, const int *act_adr, const double *row, double *pe, const double *tq0, const int32_t *tp0,
+                            const double *tq1, const int32_t *tp1, int sm, int gm, int n1, int max_nodes = 0, int total = 0, int max_path = 0 /* the guards */) {
+    auto put = [&](int k, const double *node) {
+        double *rowo = pe + (size_t)k * nq;
+        for (int i = lane; i < nq; i += 64) rowo[i] = row[i];
+        __threadfence_block();
+        wave_sync();
+        if (lane < na) rowo[act_adr[lane]] = node[lane];
+    };
+    int k = n1 - 1;
+    for (int m = sm; m != -1 && (!GUARDED || (m >= 0 && m < max_nodes && k >= 0)); m = tp0[m], k--) put(k, tq0 + (size_t)m * na);
+    k = n1;
+    for (int m = gm; m != -1 && (!GUARDED || (m >= 0 && m < max_nodes && k < total && k < max_path)); m = tp1[m], k++) put(k, tq1 + (size_t)m * na);
+}
+
 // Two waves per SIMD (256 registers): the planner is latency-bound per wave -- one env, one dependency chain -- so a second
 // wave on the SIMD is nearly free throughput (a stream of batches through the ladder: 360 -> 438 k plans/s).  What made that
 // possible: wave-uniform indices through readfirstlane (22 pointers had lived in vector registers: 310 -> 264 registers) and
 // the single inlined validity call site (no ABI register saves around every pass).  A lone launch is capped to one workgroup
 // per CU by default (mopa_plan_batch): two budget-exhausting queries that share a SIMD both finish late (47 vs 54 ms).
-__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(MOPA_K3_WAVES, MOPA_K3_WAVES))) void k_rrt_connect(SceneHdr h, const double *__restrict__ g_dbl, const int32_t *__restrict__ g_int,
+template <class B>
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(B::kWaves, B::kWaves))) void k_rrt_connect(SceneHdr h, const double *__restrict__ g_dbl, const int32_t *__restrict__ g_int,
                                                         const double *__restrict__ start, const double *__restrict__ goal, long long E,
                                                         MopaPlanParams prm, PlanWs ws, double *__restrict__ path,
                                                         int32_t *__restrict__ path_len, int32_t *__restrict__ status,
-                                                        long long *__restrict__ n_checks, int plan_lds_off, unsigned long long *__restrict__ env_ctr, int nn_cap
-#if MOPA_K3_RACE
-                                                        , RaceArgs ra
-#endif
-                                                        ) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+                                                        long long *__restrict__ n_checks, int plan_lds_off, unsigned long long *__restrict__ env_ctr, int nn_cap,
+                                                        std::conditional_t<B::kRace, RaceArgs, K3NoArgs> ra) {
+    // The planner's own name for the dynamic LDS (every such array starts at the same address).  Sharing the other kernels' `smem`
+    // ties the compiler's treatment of their address arithmetic to this kernel's: with it K3W2 had 36 VGPR spills instead of 33 and
+    // k_contact_rows one more SGPR spill (profiles/r20).
+    extern __shared__ __attribute__((aligned(16))) unsigned char k3_smem[];
+    unsigned char *const smem = k3_smem;
     LdsView v = make_view(h, smem);
     stage_scene(h, g_dbl, g_int, const_cast<double *>(v.dbl), const_cast<int *>(v.ints));
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int na = h.na;
-#if MOPA_K3_WG
-    const int vec_bytes = plan_vec_bytes_wg(na);
-#else
-    const int vec_bytes = plan_vec_bytes(na);
-#endif
+    const int vec_bytes = B::kWg ? plan_vec_bytes_wg(na) : plan_vec_bytes(na);
     const int wave_plan_bytes = vec_bytes + ms_bytes_per_wave(h.nmg, na, h.n_pq, ms_sc_doubles(h.nmj, h.nmb), h.npair);
     SceneHdr *lh = reinterpret_cast<SceneHdr *>(smem + plan_lds_off + kWavesPerBlock * wave_plan_bytes);
     {
@@ -1041,52 +1068,44 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(MOPA_K3_
     // The first query of a wave is fixed by its place -- wave w of workgroup b takes query b + w x (workgroups) --, so that a launch of few
     // queries (a retry launch: budget-exhausting queries only) puts ONE on every workgroup before any gets a second: four such queries
     // on one CU run 12 % slower each (40.6 vs 35.6 ms) than one alone.
-    // (one-wave-per-SIMD build only: the 256-register build spills more with this one flag alive -- ladder 478 -> 425 k plans/s)
-#if MOPA_K3_WG
+    // (one-wave-per-SIMD builds only: the 256-register build spills more with this one flag alive -- ladder 478 -> 425 k plans/s;
+    //  there it is the constant `false` and the first branch below is gone)
+    bool first_query = B::kWaves == 1;
+    // what lies behind the header's copy: the FP32 mirrors of the workgroup's four queries, or -- one query per workgroup -- the pass
+    // mailbox, the two query-index words and the workgroup's one mirror
+    unsigned char *wg_sh = smem + plan_lds_off + kWavesPerBlock * wave_plan_bytes + (((int)sizeof(SceneHdr) + 15) & ~15);
     // one query per workgroup: the first by the workgroup's place, later ones from the counter, fetched by wave 0 and handed to the
     // others through LDS (two words in turn: a wave cannot be two fetches ahead of another, each fetch has a barrier)
-    unsigned char *wg_sh = smem + plan_lds_off + kWavesPerBlock * wave_plan_bytes + (((int)sizeof(SceneHdr) + 15) & ~15);
     long long *sh_e = reinterpret_cast<long long *>(wg_sh + 2 * kWavesPerBlock * kMbStride * 8);
     int fetch_par = 0;
-#endif
-#if MOPA_K3_WAVES == 1
-    bool first_query = true;
-#endif
     for (;;) {
     long long e = 0;
-#if MOPA_K3_WG
     if (first_query) {
         first_query = false;
-        e = (long long)blockIdx.x;
-    } else {
+        e = (long long)blockIdx.x + (B::kWg ? 0ll : (long long)gridDim.x * wave);
+    } else if constexpr (B::kWg) {
         if (wave == 0 && lane == 0) sh_e[fetch_par] = (long long)(atomicAdd(env_ctr, 1ull) + (unsigned long long)gridDim.x);
         __syncthreads();
         const long long t = sh_e[fetch_par];
         e = (long long)(((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(t >> 32)) << 32) |
                         (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)t));
         fetch_par ^= 1;
-    }
-#else
-#if MOPA_K3_WAVES == 1
-    if (first_query) {
-        first_query = false;
-        e = (long long)blockIdx.x + (long long)gridDim.x * wave;
-    } else
-#endif
-    {
+    } else {
         unsigned long long t = 0;
-        if (lane == 0) t = atomicAdd(env_ctr, 1ull) + ((MOPA_K3_WAVES == 1) ? (unsigned long long)gridDim.x * kWavesPerBlock : 0ull);
+        if (lane == 0) t = atomicAdd(env_ctr, 1ull) + ((B::kWaves == 1) ? (unsigned long long)gridDim.x * kWavesPerBlock : 0ull);
         // scalar registers for the env index (and so for the tree / row pointers derived from it)
         e = (long long)(((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(t >> 32)) << 32) |
                         (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)t));
     }
-#endif
     if (e >= E) { tile_ctr_release(env_ctr, lane); return; }       // (the last wave out leaves the counter at zero for the next launch)
-#if MOPA_K3_RACE
-    // e is the launch SLOT (trees, record); start, goal, env row, stream id and seed are query eq's -- no K-fold copy of the inputs
-    const int member = (int)(e / ra.Eq);
-    const long long eq = e - (long long)member * ra.Eq;
-#endif
+    // the race: e is the launch SLOT (trees, record); start, goal, env row, stream id and seed are query eq's -- no K-fold copy of
+    // the inputs.  Every other build: the slot is the query.
+    int member = 0;
+    long long eq = e;
+    if constexpr (B::kRace) {
+        member = (int)(e / ra.Eq);
+        eq = e - (long long)member * ra.Eq;
+    }
 #ifdef MOPA_PLAN_STATS
     const unsigned long long tq0_ = wall_clock64();
 #endif
@@ -1094,34 +1113,28 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(MOPA_K3_
     if (prm.resume_state && prm.resume_state[4 * e] == -2) continue;
     // planner vectors live behind the validity slabs of all waves
     unsigned char *pbase = smem + plan_lds_off + wave * wave_plan_bytes;
-    PlanCtx c;
+    K3Ctx<B> c;
     c.v = v; c.lane = lane; c.lh = lh;
-#if MOPA_K3_RACE
     c.row = start + eq * h.nq;
-#else
-    c.row = start + e * h.nq;
-#endif
     c.rs = reinterpret_cast<double *>(pbase); c.xs = c.rs + na; c.ns = c.xs + na; c.ts = c.ns + na; c.r2 = c.ts + na;
     c.memo_q = c.r2 + na; c.spec_q = c.memo_q + kMemo * na; c.nn_q = c.spec_q + kSpec * na;
     c.queue = reinterpret_cast<short *>(c.nn_q + 2 * na);
     c.memo_ok = 0; c.memo_cnt = 0; c.spec_n = 0;
     c.nn_tree0 = c.nn_tree1 = -1; c.nn_size0 = c.nn_size1 = 0; c.nn_idx0 = c.nn_idx1 = 0;
-#if MOPA_K3_WG
-    // ONE mirror for the workgroup (nn_cap = all of it): every wave appends the same values in the same order and only sweeps what it
-    // has itself appended
-    c.nn_f = reinterpret_cast<float *>(wg_sh + plan_wg_shared_bytes());
-    c.wave = wave;
-    c.ftab = reinterpret_cast<double *>(pbase + plan_vec_bytes(na));
-    c.f0 = c.ftab + kFSlots * kFStride; c.f1 = c.f0 + 8; c.f2 = c.f1 + 8;
-    c.mbox = reinterpret_cast<double *>(wg_sh);
-    c.pass_par = 0; c.sp_pending = false; c.sp_it = 0; c.cur_it = 0; c.cur_role = 0;
-    if (lane < kFSlots) {
-        int *ei = reinterpret_cast<int *>(c.ftab + lane * kFStride);
-        ei[0] = -1; ei[1] = 0;
-    }
-#else
-    c.nn_f = reinterpret_cast<float *>(smem + plan_lds_off + kWavesPerBlock * wave_plan_bytes + (((int)sizeof(SceneHdr) + 15) & ~15)) + (size_t)wave * nn_cap * na;
-#endif
+    if constexpr (B::kWg) {
+        // ONE mirror for the workgroup (nn_cap = all of it): every wave appends the same values in the same order and only sweeps what it
+        // has itself appended
+        c.nn_f = reinterpret_cast<float *>(wg_sh + plan_wg_shared_bytes());
+        c.wave = wave;
+        c.ftab = reinterpret_cast<double *>(pbase + plan_vec_bytes(na));
+        c.f0 = c.ftab + kFSlots * kFStride; c.f1 = c.f0 + 8; c.f2 = c.f1 + 8;
+        c.mbox = reinterpret_cast<double *>(wg_sh);
+        c.pass_par = 0; c.sp_pending = false; c.sp_it = 0; c.cur_it = 0; c.cur_role = 0;
+        if (lane < kFSlots) {
+            int *ei = reinterpret_cast<int *>(c.ftab + lane * kFStride);
+            ei[0] = -1; ei[1] = 0;
+        }
+    } else c.nn_f = reinterpret_cast<float *>(wg_sh) + (size_t)wave * nn_cap * na;
     c.nn_cap = nn_cap; c.nn_cnt0 = c.nn_cnt1 = 0; c.nn_eps2 = (float)(2.0 * h.nn_eps);
     c.ms.grec = reinterpret_cast<double *>(pbase + vec_bytes);
     c.ms.qbuf = c.ms.grec + kMS * h.nmg * kGeomStride;
@@ -1160,22 +1173,14 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(MOPA_K3_
             wave_sync();
         }
     }
-#if MOPA_K3_RACE
     const uint64_t stream_id = prm.env_ids_dev ? prm.env_ids_dev[eq] : prm.env_id_base + (uint64_t)eq;
-    const uint64_t seed_q = (prm.seeds_dev ? prm.seeds_dev[eq] : prm.seed) + (uint64_t)member * kRaceSeedStep;
-#else
-    const uint64_t stream_id = prm.env_ids_dev ? prm.env_ids_dev[e] : prm.env_id_base + (uint64_t)e;
-    const uint64_t seed_q = prm.seeds_dev ? prm.seeds_dev[e] : prm.seed;
-#endif
+    uint64_t seed_q = prm.seeds_dev ? prm.seeds_dev[eq] : prm.seed;
+    if constexpr (B::kRace) seed_q += (uint64_t)member * kRaceSeedStep;
     c.seed = seed_q; c.stream = stream_id; c.rng_k = rng_key(seed_q, stream_id); c.max_iters = prm.max_iters;
     c.so2 = __ballot(lane < na && v.ints[h.o_act_so2 + (lane < na ? lane : 0)] != 0);
     const int *I = v.ints;
     const double *D = v.dbl;
-#if MOPA_K3_RACE
     const double *grow_ = goal + eq * h.nq;
-#else
-    const double *grow_ = goal + e * h.nq;
-#endif
     // roots
     if (!resumed) {
         if (lane < na) {
@@ -1209,14 +1214,12 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(MOPA_K3_
     auto root_valid = [&](const double *qa) -> bool {      // validity of a tree root through the multi-state routine (one state)
         if (lane < na) c.ms.qs[lane] = qa[lane];
         wave_sync();
-        return (plan_states_valid_ms_k3(c.lh, c.v.dbl, c.v.ints, c.ms.grec, c.ms.qbuf, c.ms.wl, c.ms.qs, lane, 1, c.row) & 1u) != 0u;
+        return (plan_states_valid_ms_k3<B>(c.lh, c.v.dbl, c.v.ints, c.ms.grec, c.ms.qbuf, c.ms.wl, c.ms.qs, lane, 1, c.row) & 1u) != 0u;
     };
     if (!resumed && !root_valid(tree_q(c, 1))) st = MOPA_PLAN_INVALID_GOAL;
     int it_end = 0;
-#if MOPA_K3_RACE
-    int race_sm = -1, race_gm = -1;      // the solution's two motions, for k_race_pick
+    int race_sm = -1, race_gm = -1;      // the race: the solution's two motions, for k_race_pick
     bool race_cut = false;
-#endif
     if (st == MOPA_PLAN_OK) {
         int max_iters = prm.max_iters;
         if (!resumed) {
@@ -1227,17 +1230,17 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(MOPA_K3_
         int start_motion = -1, goal_motion = -1;
         int it = it0;
         for (; it < max_iters && !solved; it++) {
-#if MOPA_K3_RACE
-            // the race word holds the smallest key = consumed checks * K + member of the members that have solved.  Consumed checks only
-            // grow, so a member whose key so far is already larger can no longer win: it stops.  (An atomic load by one lane, never
-            // a plain or scalar one; a stale value only delays the cut.)
-            if (!ra.no_abort) {
-                unsigned long long w = 0ull;
-                if (lane == 0) w = __hip_atomic_load(ra.word + eq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                w = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(w >> 32)) << 32) | (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)w);
-                if ((unsigned long long)c.n_checks * (unsigned long long)ra.K + (unsigned long long)member > w) { race_cut = true; break; }
+            if constexpr (B::kRace) {
+                // the race word holds the smallest key = consumed checks * K + member of the members that have solved.  Consumed checks only
+                // grow, so a member whose key so far is already larger can no longer win: it stops.  (An atomic load by one lane, never
+                // a plain or scalar one; a stale value only delays the cut.)
+                if (!ra.no_abort) {
+                    unsigned long long w = 0ull;
+                    if (lane == 0) w = __hip_atomic_load(ra.word + eq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    w = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(w >> 32)) << 32) | (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)w);
+                    if ((unsigned long long)c.n_checks * (unsigned long long)ra.K + (unsigned long long)member > w) { race_cut = true; break; }
+                }
             }
-#endif
             int tree = start_tree ? 0 : 1;
             bool tgi_start = start_tree;
             start_tree = !start_tree;
@@ -1248,9 +1251,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(MOPA_K3_
             }
             wave_sync();
             int role = 0;
-#if MOPA_K3_WG
-            c.cur_it = it;
-#endif
+            if constexpr (B::kWg) c.cur_it = it;
             // growTree(tree, sample), then -- unless trapped -- growTree(other, new state) while it advances: the same
             // sequence of calls as OMPL's loop, issued from ONE site (a two-phase trip) so that everything below it,
             // the validity pass included, is inlined exactly once
@@ -1260,7 +1261,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(MOPA_K3_
 #ifdef MOPA_PLAN_STATS
                 const unsigned long long tg0_ = wall_clock64();
 #endif
-                const int gs = plan_grow(h, c, extend ? tree : other, extend ? tgi_start : start_tree, extend ? SPEC_FIRST : SPEC_CONNECT, it, role);
+                const int gs = plan_grow<B>(h, c, extend ? tree : other, extend ? tgi_start : start_tree, extend ? SPEC_FIRST : SPEC_CONNECT, it, role);
 #ifdef MOPA_PLAN_STATS
                 if (threadIdx.x == 0) { atomicAdd(&g_plan_t[45], wall_clock64() - tg0_); atomicAdd(&g_plan_t[46], 1ull); }
 #endif
@@ -1293,48 +1294,23 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(MOPA_K3_
             for (int m = goal_motion; m != -1; m = tree_p(c, 1)[m]) n2++;
             if (n1 + n2 > prm.max_path) { st = MOPA_PLAN_NO_EXACT; keep_final = true; }
             else {
-#if MOPA_K3_RACE
-                // no path rows: the trees stay in the launch's scratch and k_race_pick traces the winner's
-                race_sm = start_motion; race_gm = goal_motion;
-                if (lane == 0) (void)__hip_atomic_fetch_min(ra.word + eq, (unsigned long long)c.n_checks * (unsigned long long)ra.K + (unsigned long long)member,
-                                                            __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#else
-                double *pe = path + (size_t)e * prm.max_path * h.nq;
-#if MOPA_K3_WG
-                if (wave == 0) {
-#endif
-                int k = n1 - 1;
-                for (int m = start_motion; m != -1; m = tree_p(c, 0)[m], k--) {
-                    double *rowo = pe + (size_t)k * h.nq;
-                    for (int i = lane; i < h.nq; i += 64) rowo[i] = c.row[i];
-                    __threadfence_block();
-                    wave_sync();
-                    if (lane < na) rowo[I[h.o_act_adr + lane]] = tree_q(c, 0)[(size_t)m * na + lane];
-                }
-                k = n1;
-                for (int m = goal_motion; m != -1; m = tree_p(c, 1)[m], k++) {
-                    double *rowo = pe + (size_t)k * h.nq;
-                    for (int i = lane; i < h.nq; i += 64) rowo[i] = c.row[i];
-                    __threadfence_block();
-                    wave_sync();
-                    if (lane < na) rowo[I[h.o_act_adr + lane]] = tree_q(c, 1)[(size_t)m * na + lane];
-                }
-#if MOPA_K3_WG
-                }
-#endif
-#endif
+                if constexpr (B::kRace) {
+                    // no path rows: the trees stay in the launch's scratch and k_race_pick traces the winner's
+                    race_sm = start_motion; race_gm = goal_motion;
+                    if (lane == 0) (void)__hip_atomic_fetch_min(ra.word + eq, (unsigned long long)c.n_checks * (unsigned long long)ra.K + (unsigned long long)member,
+                                                                __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                } else if (!B::kWg || wave == 0)
+                    plan_write_rows<false>(lane, na, h.nq, I + h.o_act_adr, c.row, path + (size_t)e * prm.max_path * h.nq, c.tq0, c.tp0, c.tq1, c.tp1,
+                                           start_motion, goal_motion, n1);
                 plen = n1 + n2;
             }
         } else st = MOPA_PLAN_NO_EXACT;
-#if MOPA_K3_RACE
-        if (race_cut) st = kRaceCut;
-#endif
+        if constexpr (B::kRace) {
+            if (race_cut) st = kRaceCut;
+        }
         it_end = it;
     }
-#if MOPA_K3_WG
-    if (wave == 0)
-#endif
-    {
+    if (!B::kWg || wave == 0) {
     if (lane == 0 && prm.state_dev) {
         int64_t *so = prm.state_dev + 4 * e;
         so[0] = (st != MOPA_PLAN_NO_EXACT) ? -2ll : (keep_final ? -1ll : (long long)it_end);     // -2: settled (solved / invalid goal)
@@ -1343,13 +1319,12 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(MOPA_K3_
 #ifdef MOPA_PLAN_STATS
     if (threadIdx.x == 0) atomicAdd(&g_plan_t[44], wall_clock64() - tq0_);
 #endif
-#if MOPA_K3_RACE
-    if (lane == 0) {       // the member's record (slot order) instead of the query's outputs: k_race_pick writes those
-        long long *r = ra.rec + (size_t)kRaceRec * (size_t)e;
-        r[0] = st; r[1] = c.n_checks; r[2] = it_end; r[3] = race_sm; r[4] = race_gm; r[5] = plen;
-    }
-#else
-    if (lane == 0) {
+    if constexpr (B::kRace) {
+        if (lane == 0) {       // the member's record (slot order) instead of the query's outputs: k_race_pick writes those
+            long long *r = ra.rec + (size_t)kRaceRec * (size_t)e;
+            r[0] = st; r[1] = c.n_checks; r[2] = it_end; r[3] = race_sm; r[4] = race_gm; r[5] = plen;
+        }
+    } else if (lane == 0) {
         status[e] = st;
         path_len[e] = plen;
         if (n_checks) n_checks[e] = c.n_checks;
@@ -1357,17 +1332,18 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(MOPA_K3_
         if (n_checks) n_checks[e] = (c.n_checks & 0xffff) | (c.st_pass << 16) | (c.st_states << 30) | ((long long)tree_n(c, 0) << 44) | ((long long)tree_n(c, 1) << 54);
 #endif
     }
-#endif
     }
-#if defined(MOPA_PLAN_STATS) && MOPA_K3_WG
-    if (lane == 0) {    // table hits and pass causes (wave 0's counts = every wave's), states posed per wave
-        if (wave == 0) {
-            atomicAdd(&g_plan_t[51], (unsigned long long)c.st_fnn); atomicAdd(&g_plan_t[52], (unsigned long long)c.st_fmemo);
-            atomicAdd(&g_plan_t[57], (unsigned long long)c.st_fast);
-            atomicAdd(&g_plan_t[58], (unsigned long long)c.st_c0); atomicAdd(&g_plan_t[59], (unsigned long long)c.st_c1);
-            atomicAdd(&g_plan_t[60], (unsigned long long)c.st_c2); atomicAdd(&g_plan_t[61], (unsigned long long)c.st_c3);
+#ifdef MOPA_PLAN_STATS
+    if constexpr (B::kWg) {
+        if (lane == 0) {    // table hits and pass causes (wave 0's counts = every wave's), states posed per wave
+            if (wave == 0) {
+                atomicAdd(&g_plan_t[51], (unsigned long long)c.st_fnn); atomicAdd(&g_plan_t[52], (unsigned long long)c.st_fmemo);
+                atomicAdd(&g_plan_t[57], (unsigned long long)c.st_fast);
+                atomicAdd(&g_plan_t[58], (unsigned long long)c.st_c0); atomicAdd(&g_plan_t[59], (unsigned long long)c.st_c1);
+                atomicAdd(&g_plan_t[60], (unsigned long long)c.st_c2); atomicAdd(&g_plan_t[61], (unsigned long long)c.st_c3);
+            }
+            atomicAdd(&g_plan_t[53 + wave], (unsigned long long)c.st_fstates);
         }
-        atomicAdd(&g_plan_t[53 + wave], (unsigned long long)c.st_fstates);
     }
 #endif
     wave_sync();

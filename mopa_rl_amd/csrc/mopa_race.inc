@@ -1,7 +1,7 @@
 // mopa_race.inc -- K3 race: every query is run by `portfolio` = K RRT-Connect members that share start, goal, env row and stream id and
 // differ in their seed only (member m: seed + m * kRaceSeedStep; member 0 is the query mopa_plan_batch runs).  The result of a query is
 // that of ONE member -- the solved one with the smallest (consumed checks, m) -- whatever the timing:
-//   * k3race::k_rrt_connect (the fourth instantiation of mopa_planner_k3.inc, on the one-wave-per-SIMD settings of k3w1): launch slot v
+//   * k_rrt_connect<K3Race> (the race build of mopa_planner_k3.inc, on the one-wave-per-SIMD settings of K3W1): launch slot v
 //     is member v / E of query v % E, so every query gets its first member before any query gets a second.  A member writes no path
 //     rows; it leaves a record (status, consumed checks, iterations, the two motions of its solution, their row count) and its trees
 //     in the launch's scratch.
@@ -11,28 +11,9 @@
 //     with the smallest final key can never be cut: the winner is the sequential form's (tests/race_ref.py) whatever the dispatch
 //     order.  A stale read only delays a cut.  No member waits for another.
 //   * k_race_pick, behind it on the stream, one wave per query: arg-min of the keys of the solved members, the winner's two trees traced
-//     into the caller's path rows exactly as k_rrt_connect writes them, the outputs.  No atomics, no read-back.
-// (included by mopa_planner.inc behind the three plain instantiations)
-struct RaceArgs {
-    long long Eq;                  // queries of the launch (the kernel's E is Eq * K slots)
-    int K;
-    int no_abort;                  // nonzero: the comparison with the race word is off, every member runs to its own end
-    unsigned long long *word;      // [Eq]
-    long long *rec;                // [Eq * K][kRaceRec], slot order
-};
-constexpr int kRaceRec = 8;        // status | consumed checks | iterations | start motion | goal motion | rows of the solution | - | -
-constexpr int kRaceCut = -100;     // record status of a member that stopped because it could no longer win
-constexpr unsigned long long kRaceSeedStep = 0x9E3779B97F4A7C15ull;
-
-#define MOPA_K3_WAVES 1
-#undef MOPA_K3_RACE
-#define MOPA_K3_RACE 1
-namespace k3race {
-#include "mopa_planner_k3.inc"
-}
-#undef MOPA_K3_RACE
-#define MOPA_K3_RACE 0
-#undef MOPA_K3_WAVES
+//     into the caller's path rows by k_rrt_connect's row writer (plan_write_rows), the outputs.  No atomics, no read-back.
+// (included by mopa_planner.inc behind the planner body and mopa_plan_batch; RaceArgs and the race's constants, which the body names,
+//  are defined in mopa_planner.inc in front of the body)
 
 __global__ __launch_bounds__(kBlock) void k_race_pick(int na, int nq, int o_act_adr, const int32_t *__restrict__ g_int, const double *__restrict__ start,
                                                       long long E, int K, int max_nodes, int max_path, unsigned long long seed,
@@ -77,23 +58,8 @@ __global__ __launch_bounds__(kBlock) void k_race_pick(int na, int nq, int o_act_
             const int total = (int)rw[5];          // n1 + n2 <= max_path: checked by the member before it reported "solved"
             int n1 = 0;
             for (int m = sm; m >= 0 && m < max_nodes && n1 < total; m = tp0[m]) n1++;
-            // rows as k_rrt_connect writes them: the env row first, then the active entries (a row index outside the path never is written)
-            int k = n1 - 1;
-            for (int m = sm; m >= 0 && m < max_nodes && k >= 0; m = tp0[m], k--) {
-                double *rowo = pe + (size_t)k * nq;
-                for (int i = lane; i < nq; i += 64) rowo[i] = row[i];
-                __threadfence_block();
-                wave_sync();
-                if (lane < na) rowo[g_int[o_act_adr + lane]] = tq0[(size_t)m * na + lane];
-            }
-            k = n1;
-            for (int m = gm; m >= 0 && m < max_nodes && k < total && k < max_path; m = tp1[m], k++) {
-                double *rowo = pe + (size_t)k * nq;
-                for (int i = lane; i < nq; i += 64) rowo[i] = row[i];
-                __threadfence_block();
-                wave_sync();
-                if (lane < na) rowo[g_int[o_act_adr + lane]] = tq1[(size_t)m * na + lane];
-            }
+            // (a row index outside the path never is written)
+            plan_write_rows<true>(lane, na, nq, g_int + o_act_adr, row, pe, tq0, tp0, tq1, tp1, sm, gm, n1, max_nodes, total, max_path);
             plen = total;
         }
         if (lane == 0) {
@@ -148,32 +114,20 @@ extern "C" int mopa_plan_race_batch(MopaScene *S, const double *start, const dou
     }
     HIP_TRY(grow(S, sc.race_rec, (size_t)slots * kRaceRec * sizeof(long long)));
     HIP_TRY(grow(S, sc.race_word, (size_t)E * sizeof(unsigned long long)));
-    if (!sc.plan_ctr.p) {       // as in mopa_plan_batch: zeroed once, self-resetting afterwards
-        HIP_TRY(grow(S, sc.plan_ctr, 64));
-        HIP_TRY(hipMemset(sc.plan_ctr.p, 0, 64));
-    }
     PlanWs ws{sc.plan_q.as<double>(), sc.plan_p.as<int32_t>()};
-    const int per_wave = plan_vec_bytes(S->na) + ms_bytes_per_wave(S->hdr.nmg, S->na, S->hdr.n_pq, ms_sc_doubles(S->hdr.nmj, S->hdr.nmb), S->hdr.npair);
-    const int scene_bytes = S->lds_bytes - kWavesPerBlock * S->hdr.wave_bytes;
-    const int lds = scene_bytes + kWavesPerBlock * per_wave + (int)sizeof(SceneHdr);
-    if (lds > kMaxLdsBytes) return fail(MOPA_ERR_LIMIT, "planner LDS does not fit");
     // mopa_plan_batch's policy over the E * K slots.  The build holds one wave per SIMD, so a CU holds one workgroup at a time: the
     // launch always asks for more than half a CU's LDS and the rest of the CU's LDS holds the FP32 tree mirrors of its four members
-    int64_t nblk = std::min<int64_t>(params->max_workgroups == 0 ? slots : (slots + kWavesPerBlock - 1) / kWavesPerBlock, (int64_t)S->n_cu);
-    if (params->max_workgroups > 0) nblk = std::min<int64_t>(nblk, params->max_workgroups);
-    const int mirror_off = lds + 16;
-    int nn_cap = ((kMaxLdsBytes - mirror_off) / kWavesPerBlock / (4 * std::max(1, S->na))) & ~63;
-    nn_cap = std::max(0, std::min(nn_cap, 2 * params->max_nodes));
-    const int lds_launch = std::max(std::max(lds, kMaxLdsBytes / 2 + 1024), mirror_off + kWavesPerBlock * nn_cap * 4 * S->na);
-    if (std::getenv("MOPA_DEBUG")) fprintf(stderr, "[mopa] race launch: %lld queries x %d members, %lld workgroups, mirror %d nodes/member, LDS %d bytes\n", (long long)E, K, (long long)nblk, nn_cap, lds_launch);
+    PlanGeom g;
+    if (const int rc = plan_geometry(S, sc, slots, params->max_workgroups, params->max_nodes, true, 0, g)) return rc;
+    if (std::getenv("MOPA_DEBUG")) fprintf(stderr, "[mopa] race launch: %lld queries x %d members, %lld workgroups, mirror %d nodes/member, LDS %d bytes\n", (long long)E, K, (long long)g.nblk, g.nn_cap, g.lds_launch);
     MopaPlanParams prm{};
     prm.max_iters = params->max_iters; prm.max_nodes = params->max_nodes; prm.max_path = params->max_path;
     prm.seed = params->seed; prm.env_id_base = params->env_id_base; prm.env_ids_dev = params->env_ids_dev; prm.seeds_dev = params->seeds_dev;
     RaceArgs ra{(long long)E, K, params->no_abort ? 1 : 0, sc.race_word.as<unsigned long long>(), sc.race_rec.as<long long>()};
     // all-ones in front of EVERY launch: the kernel never relies on what an earlier launch left in the word
     HIP_TRY(hipMemsetAsync(sc.race_word.p, 0xff, (size_t)E * sizeof(unsigned long long), st));
-    hipLaunchKernelGGL(k3race::k_rrt_connect, dim3((unsigned)nblk), dim3(kBlock), lds_launch, st, S->hdr, S->d_dbl, S->d_int, start, goal, (long long)slots, prm, ws,
-                       (double *)nullptr, (int32_t *)nullptr, (int32_t *)nullptr, (long long *)nullptr, scene_bytes, sc.plan_ctr.as<unsigned long long>(), nn_cap, ra);
+    hipLaunchKernelGGL(k_rrt_connect<K3Race>, dim3((unsigned)g.nblk), dim3(kBlock), g.lds_launch, st, S->hdr, S->d_dbl, S->d_int, start, goal, (long long)slots, prm, ws,
+                       (double *)nullptr, (int32_t *)nullptr, (int32_t *)nullptr, (long long *)nullptr, g.scene_bytes, g.ctr, g.nn_cap, ra);
     HIP_TRY(hipGetLastError());
     const int64_t pick_blocks = std::max<int64_t>(1, std::min<int64_t>((E + kWavesPerBlock - 1) / kWavesPerBlock, (int64_t)S->n_cu * 8));
     hipLaunchKernelGGL(k_race_pick, dim3((unsigned)pick_blocks), dim3(kBlock), 0, st, S->na, S->nq, S->hdr.o_act_adr, S->d_int, start, (long long)E, K, params->max_nodes,
@@ -189,40 +143,24 @@ extern "C" int mopa_plan_race(MopaScene *S, const double *start_host, const doub
     if (!S || !start_host || !goal_host || !params || !path_host || !path_len_out || !status_out)
         return fail(MOPA_ERR_INVALID_ARG, "null argument");
     if (params->max_path < 2) return fail(MOPA_ERR_INVALID_ARG, "bad plan parameters");
-    ON_DEVICE(S->device);
-    const size_t nq = S->nq, path_d = (size_t)params->max_path * nq;
-    double *d_buf = nullptr;
-    HIP_TRY(hipMalloc((void **)&d_buf, sizeof(double) * (2 * nq + path_d) + 64));
-    double *d_start = d_buf, *d_goal = d_buf + nq, *d_path = d_buf + 2 * nq;
-    // [0] checks [1] win_seed [2..4] info [5] = path_len, status [6] = winner
-    long long *d_out = reinterpret_cast<long long *>(d_path + path_d);
-    hipError_t e = hipMemcpy(d_start, start_host, sizeof(double) * nq, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_goal, goal_host, sizeof(double) * nq, hipMemcpyHostToDevice);
-    if (e != hipSuccess) { (void)hipFree(d_buf); return fail(MOPA_ERR_HIP, hipGetErrorString(e)); }
     MopaRaceParams one = *params;
     one.env_ids_dev = nullptr;   // single query: the stream id is env_id_base
     one.seeds_dev = nullptr;
     one.max_workgroups = 0;
-    int rc = mopa_plan_race_batch(S, d_start, d_goal, 1, &one, d_path, reinterpret_cast<int32_t *>(d_out + 5), reinterpret_cast<int32_t *>(d_out + 5) + 1,
-                                  (int64_t *)d_out, reinterpret_cast<int32_t *>(d_out + 6), reinterpret_cast<uint64_t *>(d_out + 1), (int64_t *)(d_out + 2), nullptr);
+    long long out[6];            // [0] checks [1] win_seed [2..4] info [5] winner
+    const int rc = plan_single(S, start_host, goal_host, params->max_path, path_host, path_len_out, status_out, sizeof out,
+        [&](const double *s, const double *g, double *p, int32_t *len, int32_t *st, void *x) {
+            long long *o = static_cast<long long *>(x);
+            return mopa_plan_race_batch(S, s, g, 1, &one, p, len, st, (int64_t *)o, reinterpret_cast<int32_t *>(o + 5), reinterpret_cast<uint64_t *>(o + 1), (int64_t *)(o + 2), nullptr);
+        },
+        [&](const void *x) { return hipMemcpy(out, x, sizeof out, hipMemcpyDeviceToHost); });
     if (rc == MOPA_OK) {
-        long long out[7];
-        e = hipMemcpy(out, d_out, sizeof out, hipMemcpyDeviceToHost);
-        int32_t ls[2], win;
-        std::memcpy(ls, out + 5, 8);
-        std::memcpy(&win, out + 6, 4);
-        if (e == hipSuccess && ls[0] > 0) e = hipMemcpy(path_host, d_path, sizeof(double) * (size_t)ls[0] * nq, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) rc = fail(MOPA_ERR_HIP, hipGetErrorString(e));
-        else {
-            *path_len_out = ls[0];
-            *status_out = ls[1];
-            if (n_checks_out) *n_checks_out = out[0];
-            if (winner_out) *winner_out = win;
-            if (win_seed_out) *win_seed_out = (uint64_t)out[1];
-            if (info_out) { info_out[0] = out[2]; info_out[1] = out[3]; info_out[2] = out[4]; }
-            S->status = (ls[1] == MOPA_PLAN_OK) ? "Exact solution" : (ls[1] == MOPA_PLAN_INVALID_GOAL ? "Invalid goal" : "Timeout");
-        }
+        int32_t win;
+        std::memcpy(&win, out + 5, 4);
+        if (n_checks_out) *n_checks_out = out[0];
+        if (winner_out) *winner_out = win;
+        if (win_seed_out) *win_seed_out = (uint64_t)out[1];
+        if (info_out) { info_out[0] = out[2]; info_out[1] = out[3]; info_out[2] = out[4]; }
     }
-    (void)hipFree(d_buf);
     return rc;
 }

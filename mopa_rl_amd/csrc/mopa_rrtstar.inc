@@ -374,33 +374,17 @@ extern "C" int mopa_plan_star(MopaScene *S, const double *start_host, const doub
                               int32_t *path_len_out, int32_t *status_out, double *cost_out, int64_t *info_out) {
     if (!S || !start_host || !goal_host || !params || !path_host || !path_len_out || !status_out) return fail(MOPA_ERR_INVALID_ARG, "null argument");
     if (params->max_path < 2) return fail(MOPA_ERR_INVALID_ARG, "max_path < 2");
-    ON_DEVICE(S->device);
-    const size_t nq = (size_t)S->nq, path_d = (size_t)params->max_path * nq;
-    double *d_buf = nullptr;
-    HIP_TRY(hipMalloc((void **)&d_buf, sizeof(double) * (2 * nq + path_d + 1 + kStarInfoCols) + 16));
-    double *d_start = d_buf, *d_goal = d_buf + nq, *d_path = d_buf + 2 * nq, *d_cost = d_path + path_d;
-    long long *d_info = reinterpret_cast<long long *>(d_cost + 1);
-    int32_t *d_len = reinterpret_cast<int32_t *>(d_info + kStarInfoCols), *d_status = d_len + 1;
-    hipError_t e = hipMemcpy(d_start, start_host, sizeof(double) * nq, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_goal, goal_host, sizeof(double) * nq, hipMemcpyHostToDevice);
-    if (e != hipSuccess) { (void)hipFree(d_buf); return fail(MOPA_ERR_HIP, hipGetErrorString(e)); }
     MopaStarParams one = *params;
     one.env_ids_dev = nullptr;
     one.seeds_dev = nullptr;
-    int rc = mopa_plan_star_batch(S, d_start, d_goal, 1, &one, d_path, d_len, d_status, d_cost, (int64_t *)d_info, nullptr);
-    if (rc == MOPA_OK) {
-        int32_t ls[2];
-        e = hipMemcpy(ls, d_len, 8, hipMemcpyDeviceToHost);        // (the default stream: waits for the launch)
-        if (e == hipSuccess && cost_out) e = hipMemcpy(cost_out, d_cost, 8, hipMemcpyDeviceToHost);
-        if (e == hipSuccess && info_out) e = hipMemcpy(info_out, d_info, 8 * kStarInfoCols, hipMemcpyDeviceToHost);
-        if (e == hipSuccess && ls[0] > 0) e = hipMemcpy(path_host, d_path, sizeof(double) * (size_t)ls[0] * nq, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) rc = fail(MOPA_ERR_HIP, hipGetErrorString(e));
-        else {
-            *path_len_out = ls[0];
-            *status_out = ls[1];
-            S->status = (ls[1] == MOPA_PLAN_OK) ? "Exact solution" : (ls[1] == MOPA_PLAN_INVALID_GOAL ? "Invalid goal" : "Timeout");
-        }
-    }
-    (void)hipFree(d_buf);
-    return rc;
+    // further outputs: cost | info[kStarInfoCols]
+    return plan_single(S, start_host, goal_host, params->max_path, path_host, path_len_out, status_out, 8 * (1 + kStarInfoCols),
+        [&](const double *s, const double *g, double *p, int32_t *len, int32_t *st, void *x) {
+            return mopa_plan_star_batch(S, s, g, 1, &one, p, len, st, static_cast<double *>(x), static_cast<int64_t *>(x) + 1, nullptr);
+        },
+        [&](const void *x) {
+            hipError_t e = cost_out ? hipMemcpy(cost_out, x, 8, hipMemcpyDeviceToHost) : hipSuccess;
+            if (e == hipSuccess && info_out) e = hipMemcpy(info_out, static_cast<const int64_t *>(x) + 1, 8 * kStarInfoCols, hipMemcpyDeviceToHost);
+            return e;
+        });
 }

@@ -955,9 +955,9 @@ def test_nearest_neighbour_mirror_sizes_do_not_change_plans(oracle_mod, monkeypa
 @pytest.mark.gpu
 @pytest.mark.parametrize("env", SUPPORTED_ENVS)
 def test_planner_builds_agree(env, oracle_mod, monkeypatch):
-    """K3's three builds -- four queries per workgroup at one / two waves per SIMD (k3w1 / k3w2) and ONE query per workgroup of four
-    waves (k3wg: waves 1-3 work out and evaluate what future iterations will ask; mopa_planner_k3.inc) -- give the same status, path
-    bits and consumed-check count on every scene, on queries that are trivial, solvable, budget-exhausting and invalid; so does k3wg
+    """K3's three builds -- four queries per workgroup at one / two waves per SIMD (K3W1 / K3W2) and ONE query per workgroup of four
+    waves (K3WG: waves 1-3 work out and evaluate what future iterations will ask; mopa_planner_k3.inc) -- give the same status, path
+    bits and consumed-check count on every scene, on queries that are trivial, solvable, budget-exhausting and invalid; so does K3WG
     with a tiny tree mirror (its exact FP64 fall-backs) and with fewer workgroups than queries (the workgroup's query hand-over).
     A few queries are checked against the oracle as well."""
     import torch

@@ -1,4 +1,4 @@
-"""K3 race on the GPU: k3race::k_rrt_connect + k_race_pick (csrc/mopa_planner_k3.inc, mopa_race.inc) against the sequential form
+"""K3 race on the GPU: k_rrt_connect<K3Race> + k_race_pick (csrc/mopa_planner_k3.inc, mopa_race.inc) against the sequential form
 race_ref.py over the shared cases of race_cases.py -- every output on bit patterns, no tolerances --, portfolio 1 against `plan`, the
 independence of the result from timing (no_abort, three workgroups, a permutation, a side stream), K9 behind the race and the drop-in
 class."""
