@@ -163,6 +163,38 @@ int mopa_device_count(void);
 
 int mopa_scene_create(const MopaSceneDesc *desc, MopaScene **out);
 void mopa_scene_destroy(MopaScene *scene);
+
+/* glue_bodies (KinematicPlanner's constructor argument; the reference: GlueTransformation, mujoco_ompl_interface.cpp:810-907): the
+ * GLUED compile of the same description.  body_b (a model body id) carries exactly one free joint -- the manipulated object -- and is
+ * posed as a jointless child of body_a, a body the active joints move (the gripper): for any active joint values
+ *     p_b' = p_a' + R_a' t,   q_b' = normalize(q_a' * rq),
+ * where the offset t = R(q_a)^T (p_b - p_a), rq = conj(q_a) * q_b is taken where forward kinematics leaves the two bodies at the
+ * ATTACH row's own joint values.  This is the weld form of the reference's write-back form (it writes the world pose into the free
+ * joint's qpos and runs FK again): the poses are equal up to rounding; on the CPU oracle the verdicts were equal on every state
+ * compared, and min_dist equal except on 0.2 % of them, where the narrow phase's depth is not continuous in the pose (DESIGN.md
+ * section 3).  The candidate pairs and ignored_pairs are the description's; the caller
+ * ignores the object-gripper pairs, as with the reference.  desc->pair_cull_radius is not applied to pairs with a geom on body_b or
+ * below it (the proofs behind it do not cover a carried object).  The FP32 broad phase's coordinate bound stays the caller's
+ * responsibility for the offset, as it is for free-joint positions.
+ * Which row attaches: mopa_is_valid_batch / mopa_check_motion_batch -- env row qpos_env[e], at its own active values, for every state
+ * or segment of env e; mopa_plan_batch / mopa_plan -- the start row (the goal row's free-joint slots are not read), and in every row
+ * of a solved path the 7 free-joint columns hold (p_b', q_b') at that waypoint; mopa_is_valid_state -- the state itself.  These
+ * take ordinary qpos rows and attach internally, and so do mopa_debug_fk / mopa_debug_pair_dist (the state itself).  Every other
+ * entry point that takes a scene and states (mopa_plan_star*, mopa_plan_race*, the K9 passes, mopa_pullback_batch, mopa_contacts_*,
+ * mopa_interpolate_batch, the FK timing probe of the stats build) and the planner continuation of MopaPlanParams return
+ * MOPA_ERR_UNSUPPORTED on a glued scene.  A glued scene runs the generic validity kernels (never a baked one).
+ * Refused with MOPA_ERR_UNSUPPORTED: body_b without exactly one free joint (the reference's two-slide branch is not built), body_a
+ * static, body_a >= body_b in body order, body_a inside body_b's subtree. */
+int mopa_scene_create_glued(const MopaSceneDesc *desc, int32_t body_a, int32_t body_b, MopaScene **out);
+/* out[0], out[1] = body_a, body_b of a glued scene; -1, -1 for an ordinary one */
+int mopa_scene_glue(const MopaScene *scene, int32_t out[2]);
+/* E qpos rows -> their ATTACHED rows: copies whose 7 free-joint slots of body_b hold the offset (t[3], rq[4]) at the row's own
+ * joint values (k_glue_attach, one lane per row; not in place).  What the entry points above do internally. */
+int mopa_glue_attach_batch(MopaScene *scene, const double *rows_dev /*[E,nq]*/, int64_t E, double *attached_dev /*[E,nq]*/, void *stream);
+/* path rows in place: in rows r < min(path_len[e], max_path) of env e the 7 free-joint columns of body_b get (p_b', q_b') at the
+ * row's active values, with the offset and the other passive values of attached_dev[e] (k_glue_rows, one lane per row) */
+int mopa_glue_rows_batch(MopaScene *scene, double *path_dev /*[E,max_path,nq]*/, const int32_t *path_len_dev /*[E]*/,
+                         const double *attached_dev /*[E,nq]*/, int64_t E, int32_t max_path, void *stream);
 /* introspection used by the host shim and the tests */
 int mopa_scene_num_active(const MopaScene *scene);
 int mopa_scene_active_idx(const MopaScene *scene, int32_t *out /*[na]*/);
@@ -171,6 +203,9 @@ int mopa_scene_lds_bytes(const MopaScene *scene);
 /* name of the validity kernel mopa_is_valid_batch dispatches for a batch of N states on this scene ("k_is_valid_v5",
  * "k_is_valid_v2" or "k_is_valid"); the benchmark labels its roofline line and selects profiler rows with it */
 int mopa_scene_valid_kernel(const MopaScene *scene, int64_t N, char *out, int32_t cap /* >= 24 */);
+/* the form mopa_check_motion_batch takes for N segments on this scene: "k_check_motion" (one wave per segment) or
+ * "k_motion_expand" (the segments expanded into their states for the lane-per-state validity kernel) */
+int mopa_scene_motion_kernel(const MopaScene *scene, int64_t N, char *out, int32_t cap /* >= 24 */);
 /* k_is_valid_v5 on this scene: 0 = the generic instantiation, i > 0 = the i-th baked scene (mopa_valid_v5_baked.inc) */
 int mopa_scene_k1_baked(const MopaScene *scene);
 /* host-only export of what k_is_valid_v5 reads from a scene (no device needed; tools/bake_k1_scenes.py):
@@ -182,6 +217,9 @@ int mopa_scene_k1_export(const MopaSceneDesc *desc, int64_t *sizes /*[8]*/, doub
 /* byte offset of a field of the exported header (mopa_scene_k1_export's hdr) by name, -1 for an unknown name: the layout
  * tools/bake_k1_scenes.py reads the header with, taken from the compiler rather than restated */
 int mopa_scene_hdr_offset(const char *field);
+/* mopa_scene_k1_export of the glued compile (mopa_scene_create_glued's host half: its refusals are this call's status codes) */
+int mopa_scene_k1_export_glued(const MopaSceneDesc *desc, int32_t body_a, int32_t body_b, int64_t *sizes /*[8]*/, double *dbl, int32_t *ints,
+                               int32_t *tab, void *hdr, uint64_t *fingerprint);
 /* host run of the forward kinematics compiled into the i-th baked scene (no device needed; tests): n states, state s =
  * q_active[s] (na values) over the env row qpos_env[s] (nq values); out[s][nmg][12] = each moving geom's world position
  * and row-major rotation matrix.  Returns MOPA_ERR_INVALID_ARG for an index that names no baked scene */
@@ -206,7 +244,8 @@ int mopa_check_motion_batch(MopaScene *scene, const double *qa_dev /*[N,na]*/, c
                             uint8_t *valid_dev /*[N]*/, void *stream);
 
 /* E independent RRT-Connect queries (one per env).  path rows hold full qpos vectors with the passive
- * columns copied from start (KinematicPlanner.cpp:236-240).  status[e] in {0,-4,-5}. */
+ * columns copied from start (KinematicPlanner.cpp:236-240; a glued scene: the carried body's free-joint columns hold its pose at
+ * the waypoint, see mopa_scene_create_glued).  status[e] in {0,-4,-5}. */
 int mopa_plan_batch(MopaScene *scene, const double *start_dev /*[E,nq]*/, const double *goal_dev /*[E,nq]*/, int64_t E,
                     const MopaPlanParams *params, double *path_dev /*[E,max_path,nq]*/, int32_t *path_len_dev /*[E]*/,
                     int32_t *status_dev /*[E]*/, int64_t *n_checks_dev /*[E] or NULL*/, void *stream);

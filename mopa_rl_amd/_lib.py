@@ -24,7 +24,9 @@ _ip = C.POINTER(C.c_int32)
 # every symbol include/mopa_hip.h declares (checked by tests/test_abi.py)
 EXPORTED_SYMBOLS = [
     "mopa_last_error", "mopa_version", "mopa_device_count", "mopa_scene_create", "mopa_scene_destroy",
+    "mopa_scene_create_glued", "mopa_scene_glue", "mopa_glue_attach_batch", "mopa_glue_rows_batch", "mopa_scene_k1_export_glued",
     "mopa_scene_num_active", "mopa_scene_active_idx", "mopa_scene_num_pairs", "mopa_scene_lds_bytes", "mopa_scene_valid_kernel",
+    "mopa_scene_motion_kernel",
     "mopa_scene_k1_baked", "mopa_scene_k1_export", "mopa_scene_hdr_offset", "mopa_k1_baked_fk_host",
     "mopa_is_valid_batch", "mopa_check_motion_batch", "mopa_plan_batch", "mopa_simplify_paths_batch", "mopa_simplify_paths_max_path", "mopa_shortcut_paths_batch", "mopa_shortcut_paths_max_path", "mopa_smooth_paths_batch", "mopa_smooth_paths_max_path",
     "mopa_plan_star_batch", "mopa_plan_star", "mopa_plan_star_k", "mopa_star_params_size",
@@ -199,6 +201,11 @@ def lib() -> C.CDLL:
     L.mopa_scene_create.argtypes = [C.POINTER(MopaSceneDesc), C.POINTER(vp)]
     L.mopa_scene_destroy.argtypes = [vp]
     L.mopa_scene_destroy.restype = None
+    L.mopa_scene_create_glued.argtypes = [C.POINTER(MopaSceneDesc), C.c_int32, C.c_int32, C.POINTER(vp)]
+    L.mopa_scene_glue.argtypes = [vp, _ip]
+    L.mopa_glue_attach_batch.argtypes = [vp, vp, C.c_int64, vp, vp]
+    L.mopa_glue_rows_batch.argtypes = [vp, vp, vp, vp, C.c_int64, C.c_int32, vp]
+    L.mopa_scene_k1_export_glued.argtypes = [vp, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp]
     L.mopa_scene_num_active.argtypes = [vp]
     L.mopa_scene_active_idx.argtypes = [vp, _ip]
     L.mopa_scene_num_pairs.argtypes = [vp]
@@ -271,6 +278,7 @@ def lib() -> C.CDLL:
     L.mopa_ik_site_pose_batch.argtypes = [vp, C.c_int64, vp, vp, vp, vp]
     L.mopa_ik_targets_batch.argtypes = [vp, C.c_int64, vp, vp, vp, C.c_int64, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double), vp, vp, vp]
     L.mopa_scene_valid_kernel.argtypes = [vp, C.c_int64, C.c_char_p, C.c_int32]
+    L.mopa_scene_motion_kernel.argtypes = [vp, C.c_int64, C.c_char_p, C.c_int32]
     L.mopa_scene_k1_baked.argtypes = [vp]
     L.mopa_scene_k1_export.argtypes = [vp, vp, vp, vp, vp, vp, vp]
     L.mopa_scene_hdr_offset.argtypes = [C.c_char_p]
@@ -318,12 +326,40 @@ def model_struct(m, keep: list, pair_geom=None) -> MopaModel:
         len(m.mesh_vertnum), len(m.mesh_vert), i(m.mesh_vertadr), i(m.mesh_vertnum), d(m.mesh_vert), i(m.geom_dataid))
 
 
+def glue_ids(model, body_a, body_b):
+    """(body_a, body_b) of a glue_bodies pair as model body ids; names (str / bytes) or ids"""
+    def one(b):
+        if isinstance(b, (bytes, bytearray)):
+            b = b.decode("utf-8")
+        if isinstance(b, str):
+            names = list(model.body_names)
+            if b not in names:
+                raise MopaError(f"glue_bodies: the model has no body named {b!r}")
+            return names.index(b)
+        return int(b)
+    return one(body_a), one(body_b)
+
+
+def glue_subtree_geoms(model, body_b: int) -> np.ndarray:
+    """bool per collidable geom: it sits on body_b or on a body below it"""
+    par = np.asarray(model.body_parent)
+    sub = np.zeros(len(par), dtype=bool)
+    if 0 < body_b < len(par):
+        sub[body_b] = True
+        for b in range(body_b + 1, len(par)):
+            sub[b] = sub[par[b]]
+    return sub[np.asarray(model.geom_body)]
+
+
 def scene_desc(model, passive_joint_idx, ignored_contacts, contact_threshold: float, range_: float = 0.1, resolution: float = 0.005,
-               seed: int = 0, device: int = -1, prune_pairs: Optional[bool] = None):
+               seed: int = 0, device: int = -1, prune_pairs: Optional[bool] = None, glue=None):
     """The MopaSceneDesc that Scene hands to mopa_scene_create (pair pruning and per-pair cull radii applied as described
-    there) + the numpy buffers it points at + (pairs pruned, pairs with a tightened cull radius)."""
+    there) + the numpy buffers it points at + (pairs pruned, pairs with a tightened cull radius).
+    glue = (body_a, body_b) ids: the description of the glued scene -- the pruning proofs were made with the object where the env row
+    puts it, so every candidate pair with a geom on body_b or below it is kept, with no tightened cull radius."""
     m = model
     keep = []
+    carried = glue_subtree_geoms(m, int(glue[1])) if glue is not None else np.zeros(len(m.geom_type), dtype=bool)
     if prune_pairs is None:
         prune_pairs = os.environ.get("MOPA_PRUNE_PAIRS", "1") != "0"
     pairs = np.asarray(m.pair_geom, dtype=np.int32).reshape(-1, 2)
@@ -335,7 +371,7 @@ def scene_desc(model, passive_joint_idx, ignored_contacts, contact_threshold: fl
     npair_pruned = 0
     if prune_pairs and len(never) and float(contact_threshold) <= 0.0:
         drop = {(int(a), int(b)) for a, b in never} | {(int(b), int(a)) for a, b in never}
-        keep_row = np.array([(int(a), int(b)) not in drop for a, b in pairs], dtype=bool)
+        keep_row = np.array([(int(a), int(b)) not in drop or bool(carried[a] or carried[b]) for a, b in pairs], dtype=bool)
         npair_pruned = int((~keep_row).sum())
         pairs = np.ascontiguousarray(pairs[keep_row])
 
@@ -355,7 +391,8 @@ def scene_desc(model, passive_joint_idx, ignored_contacts, contact_threshold: fl
     npair_tightened = 0
     if prune_pairs and cr and float(contact_threshold) <= float(cr.get("threshold", -np.inf)):
         rad = {(int(a), int(b)): float(r) for a, b, r in cr.get("pairs") or []}
-        arr = np.array([rad.get((int(a), int(b)), rad.get((int(b), int(a)), 0.0)) for a, b in pairs], dtype=np.float64)
+        arr = np.array([0.0 if (carried[a] or carried[b]) else rad.get((int(a), int(b)), rad.get((int(b), int(a)), 0.0)) for a, b in pairs],
+                       dtype=np.float64)
         if (arr > 0).any():
             npair_tightened = int((arr > 0).sum())
             desc.pair_cull_radius = d(arr)
@@ -373,40 +410,58 @@ def scene_desc(model, passive_joint_idx, ignored_contacts, contact_threshold: fl
 
 def k1_export(*args, **kw) -> dict:
     """Host-only export of what k_is_valid_v5 reads from a scene (mopa_scene_k1_export: no device needed); the arguments are
-    those of Scene.  Returns the two blobs, the FP32 pair table, the header bytes, the fingerprint and the launch facts."""
+    those of Scene.  Returns the two blobs, the FP32 pair table, the header bytes, the fingerprint and the launch facts.
+    glue=(body_a, body_b) ids: the glued compile (mopa_scene_k1_export_glued; its refusals raise MopaError)."""
     L = lib()
-    desc, keep, _, _ = scene_desc(*args, **kw)
+    desc, keep, npruned, ntight = scene_desc(*args, **kw)
+    glue = kw.get("glue")
     sizes = np.zeros(8, dtype=np.int64)
-    check(L.mopa_scene_k1_export(C.byref(desc), sizes.ctypes.data_as(C.c_void_p), None, None, None, None, None))
+    if glue is not None:
+        def export(*bufs):
+            return L.mopa_scene_k1_export_glued(C.byref(desc), int(glue[0]), int(glue[1]), sizes.ctypes.data_as(C.c_void_p), *bufs)
+    else:
+        def export(*bufs):
+            return L.mopa_scene_k1_export(C.byref(desc), sizes.ctypes.data_as(C.c_void_p), *bufs)
+    check(export(None, None, None, None, None))
     dbl = np.zeros(int(sizes[0]), dtype=np.float64)
     ints = np.zeros(int(sizes[1]), dtype=np.int32)
     tab = np.zeros(int(sizes[2]), dtype=np.int32)
     hdr = np.zeros(int(sizes[3]), dtype=np.uint8)
     fp = C.c_uint64()
-    check(L.mopa_scene_k1_export(C.byref(desc), sizes.ctypes.data_as(C.c_void_p), dbl.ctypes.data_as(C.c_void_p), ints.ctypes.data_as(C.c_void_p),
-                                 tab.ctypes.data_as(C.c_void_p), hdr.ctypes.data_as(C.c_void_p), C.byref(fp)))
+    check(export(dbl.ctypes.data_as(C.c_void_p), ints.ctypes.data_as(C.c_void_p), tab.ctypes.data_as(C.c_void_p), hdr.ctypes.data_as(C.c_void_p),
+                 C.byref(fp)))
+    npair = int(desc.model.npair)
+    pairs = np.ctypeslib.as_array(desc.model.pair_geom, shape=(max(npair, 1), 2))[:npair].copy()
+    radius = (np.ctypeslib.as_array(desc.pair_cull_radius, shape=(max(npair, 1),))[:npair].copy() if desc.pair_cull_radius
+              else np.zeros(npair))
     del keep
     return {"dbl": dbl, "ints": ints, "tab": tab, "hdr": hdr, "fingerprint": int(fp.value), "use_v5": bool(sizes[4]),
-            "cen_lds": bool(sizes[5]), "n_mesh_pairs": int(sizes[6]), "nmg": int(sizes[7])}
+            "cen_lds": bool(sizes[5]), "n_mesh_pairs": int(sizes[6]), "nmg": int(sizes[7]),
+            "pair_geom": pairs, "pair_cull_radius": radius, "npair_pruned": npruned, "npair_tightened": ntight}
 
 
 class Scene:
     """Owns one MopaScene* (== one KinematicPlanner instance of the reference)."""
 
     def __init__(self, model, passive_joint_idx, ignored_contacts, contact_threshold: float, range_: float = 0.1,
-                 resolution: float = 0.005, seed: int = 0, device: int = -1, prune_pairs: Optional[bool] = None):
+                 resolution: float = 0.005, seed: int = 0, device: int = -1, prune_pairs: Optional[bool] = None, glue=None):
         """prune_pairs (default: on, MOPA_PRUNE_PAIRS=0 turns it off): candidate pairs that the scene's compile-time proof
         (tools/prove_separated_pairs.py, `meta["never_violating_pairs"]`: a Lipschitz branch-and-bound over the joint ranges)
         shows can never reach the contact threshold are not handed to the kernels at all.  Verdicts and depths are
         unchanged for joint values inside their ranges inflated by the proof's guard band (`meta["prune_guard_band"]`: 0.05 rad /
         2 mm) -- the states OMPL samples and the rollouts clip to, and what MuJoCo's soft joint limits let through.  The reference's
         isValidState takes ANY state (motion_planners/KinematicPlanner.cpp:253-286): `is_valid_state` here, and `BatchPlanner.
-        is_valid(guard=True)`, send a state with a joint beyond range + band through a sibling scene with the full pair list."""
+        is_valid(guard=True)`, send a state with a joint beyond range + band through a sibling scene with the full pair list.
+        glue = (body_a, body_b), names or ids: the glued scene (mopa_scene_create_glued, include/mopa_hip.h) -- what `glued()` creates."""
         L = lib()
         m = model
+        self.glue = None if glue is None else glue_ids(m, *glue)
+        self._glued = {}
+        self._prune_pairs = prune_pairs
         self._ctor = (model, list(passive_joint_idx), list(ignored_contacts), float(contact_threshold), float(range_), float(resolution), int(seed),
                       int(device))
         self._full = None
+        self._h = C.c_void_p()
         # the box inside which the pruning is proven: range + guard band of every limited joint (scenes proven without a band: the range)
         band = getattr(m, "meta", {}).get("prune_guard_band") or {}
         lim = np.asarray(m.jnt_limited).astype(bool) & (np.asarray(m.jnt_type) != 0)
@@ -415,9 +470,12 @@ class Scene:
         self.guard_lo = (np.asarray(m.jnt_range, dtype=np.float64)[:, 0] - bw)[lim]
         self.guard_hi = (np.asarray(m.jnt_range, dtype=np.float64)[:, 1] + bw)[lim]
         desc, keep, self.npair_pruned, self.npair_tightened = scene_desc(model, passive_joint_idx, ignored_contacts, contact_threshold, range_,
-                                                                         resolution, seed, device, prune_pairs)
+                                                                         resolution, seed, device, prune_pairs, glue=self.glue)
         h = C.c_void_p()
-        check(L.mopa_scene_create(C.byref(desc), C.byref(h)))
+        if self.glue is not None:
+            check(L.mopa_scene_create_glued(C.byref(desc), self.glue[0], self.glue[1], C.byref(h)))
+        else:
+            check(L.mopa_scene_create(C.byref(desc), C.byref(h)))
         self._h = h
         self.model = m
         self.nq = m.nq
@@ -436,6 +494,9 @@ class Scene:
         if getattr(self, "_full", None) is not None:
             self._full.close()
             self._full = None
+        for g in list(getattr(self, "_glued", {}).values()):
+            g.close()
+        self._glued = {}
         if getattr(self, "_h", None) is not None and self._h.value:
             lib().mopa_scene_destroy(self._h)
             self._h = C.c_void_p()
@@ -450,6 +511,18 @@ class Scene:
     def handle(self):
         return self._h
 
+    def glued(self, body_a, body_b) -> "Scene":
+        """the sibling scene that plans with body_b -- the manipulated object, a body with one free joint -- attached to body_a, a
+        body the active joints move (names or ids; PyKinematicPlanner's `glue_bodies`).  Created once per pair, closed with this scene.
+        It serves is_valid_state / plan here and is_valid / check_motion / plan of BatchPlanner; everything else raises."""
+        if self.glue is not None:
+            raise MopaError("glued() of a glued scene")
+        key = glue_ids(self.model, body_a, body_b)
+        if key not in self._glued:
+            mdl, pas, ign, thr, rng, res, seed, dev = self._ctor
+            self._glued[key] = Scene(mdl, pas, ign, thr, range_=rng, resolution=res, seed=seed, device=dev, prune_pairs=self._prune_pairs, glue=key)
+        return self._glued[key]
+
     def full(self) -> "Scene":
         """the sibling scene with the FULL candidate-pair list (created on first use): where states outside the pruning proof's
         box -- a joint beyond its range + guard band -- are evaluated"""
@@ -457,7 +530,7 @@ class Scene:
             return self
         if self._full is None:
             mdl, pas, ign, thr, rng, res, seed, dev = self._ctor
-            self._full = Scene(mdl, pas, ign, thr, range_=rng, resolution=res, seed=seed, device=dev, prune_pairs=False)
+            self._full = Scene(mdl, pas, ign, thr, range_=rng, resolution=res, seed=seed, device=dev, prune_pairs=False, glue=self.glue)
         return self._full
 
     def contact_scene(self) -> "Scene":
@@ -467,7 +540,7 @@ class Scene:
             return self
         if self._full is None:
             mdl, pas, ign, thr, rng, res, seed, dev = self._ctor
-            self._full = Scene(mdl, pas, ign, thr, range_=rng, resolution=res, seed=seed, device=dev, prune_pairs=False)
+            self._full = Scene(mdl, pas, ign, thr, range_=rng, resolution=res, seed=seed, device=dev, prune_pairs=False, glue=self.glue)
         return self._full
 
     def outside_guard(self, qpos_rows) -> np.ndarray:
@@ -534,6 +607,12 @@ class Scene:
         """name of the validity kernel `mopa_is_valid_batch` dispatches for a batch of n_states"""
         buf = C.create_string_buffer(32)
         check(lib().mopa_scene_valid_kernel(self._h, int(n_states), buf, 32))
+        return buf.value.decode()
+
+    def motion_kernel(self, n_segments: int) -> str:
+        """the form `mopa_check_motion_batch` takes for n_segments: "k_check_motion" or "k_motion_expand" """
+        buf = C.create_string_buffer(32)
+        check(lib().mopa_scene_motion_kernel(self._h, int(n_segments), buf, 32))
         return buf.value.decode()
 
     def planner_status(self) -> bytes:

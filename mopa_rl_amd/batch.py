@@ -213,6 +213,30 @@ class BatchPlanner:
                                                   _ptr(count), _ptr(pair), _ptr(dist), _stream_handle(stream)))
         return ContactReport(count, pair, dist, self.scene.model)
 
+    def glue_attach(self, rows, stream=None):
+        """glued scene (`Scene.glued`): rows [E, nq] -> their attached rows, copies whose free-joint slots of the carried body hold
+        its offset (t, rq) under body_a at the row's own joint values (mopa_glue_attach_batch); `is_valid`, `check_motion` and `plan`
+        do this internally"""
+        torch = _torch()
+        _check_f64(rows, "rows", self.nq)
+        out = torch.empty_like(rows)
+        _lib.check(_lib.lib().mopa_glue_attach_batch(self.scene.handle, _ptr(rows), rows.shape[0], _ptr(out), _stream_handle(stream)))
+        return out
+
+    def glue_rows(self, path, path_len, attached, stream=None):
+        """glued scene: the carried body's pose at every waypoint into the free-joint columns of the rows r < path_len[e] of
+        path [E, max_path, nq], in place (mopa_glue_rows_batch); `plan` does this internally"""
+        torch = _torch()
+        _check_f64(attached, "attached", self.nq)
+        if (path.dtype != torch.float64 or not path.is_cuda or not path.is_contiguous() or path.dim() != 3 or path.shape[2] != self.nq
+                or path.shape[0] != attached.shape[0]):
+            raise _lib.MopaError("path must be a contiguous float64 GPU tensor [E, max_path, nq] with E = attached.shape[0]")
+        if path_len.dtype != torch.int32 or not path_len.is_cuda or not path_len.is_contiguous() or path_len.shape != (path.shape[0],):
+            raise _lib.MopaError("path_len must be a contiguous int32 GPU tensor [E]")
+        _lib.check(_lib.lib().mopa_glue_rows_batch(self.scene.handle, _ptr(path), _ptr(path_len), _ptr(attached), path.shape[0], path.shape[1],
+                                                   _stream_handle(stream)))
+        return path
+
     def check_motion(self, qa, qb, qpos_env, samples_per_env: Optional[int] = None, stream=None):
         torch = _torch()
         _check_f64(qa, "qa", self.na)

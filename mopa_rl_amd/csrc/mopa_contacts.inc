@@ -112,6 +112,7 @@ static void contacts_register_lds() {
 extern "C" int mopa_contacts_batch(MopaScene *S, const double *q_active, const double *qpos_env, int64_t N, int64_t samples_per_env,
                                    double cutoff, int32_t K, int32_t *count, int32_t *pair, double *dist, void *stream) {
     if (!S || !count || !pair || !dist || (N > 0 && (!q_active || !qpos_env))) return fail(MOPA_ERR_INVALID_ARG, "null argument");
+    MOPA_REFUSE_GLUED(S, "the contact report (mopa_contacts_batch)");
     if (N < 0 || samples_per_env <= 0) return fail(MOPA_ERR_INVALID_ARG, "N < 0 or samples_per_env <= 0");
     if (!std::isfinite(cutoff) || !(cutoff < 0.0)) return fail(MOPA_ERR_INVALID_ARG, "cutoff must be finite and < 0 (the broad phase culls at zero margin)");
     if (K < 1) return fail(MOPA_ERR_INVALID_ARG, "max_contacts must be >= 1");
@@ -147,6 +148,7 @@ extern "C" int mopa_contacts_batch(MopaScene *S, const double *q_active, const d
 
 extern "C" int mopa_contacts_state(MopaScene *S, const double *qpos_host, double cutoff, int32_t K, int32_t *count, int32_t *pair, double *dist) {
     if (!S || !qpos_host || !count || !pair || !dist) return fail(MOPA_ERR_INVALID_ARG, "null argument");
+    MOPA_REFUSE_GLUED(S, "the contact report (mopa_contacts_state)");
     if (K < 1) return fail(MOPA_ERR_INVALID_ARG, "max_contacts must be >= 1");
     ON_DEVICE(S->device);
     int rc = upload_state(S, qpos_host);

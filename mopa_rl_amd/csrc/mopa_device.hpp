@@ -33,7 +33,9 @@ constexpr int kMprMaxIt = 50;              // MuJoCo mpr_iterations
 constexpr int kMprPortalMaxIt = 100;       // guard for libccd's two unbounded loops
 
 enum GeomType : int { G_PLANE = 0, G_SPHERE = 2, G_CAPSULE = 3, G_CYLINDER = 5, G_BOX = 6, G_MESH = 7 };
-enum JntType : int { J_FREE = 0, J_BALL = 1, J_SLIDE = 2, J_HINGE = 3 };
+// J_GLUE is no MuJoCo joint type: a glued scene (mopa_scene_create_glued) marks the carried body with it -- a jointless body whose local pose
+// (pos[3] quat[4]) is read from the state's 7 free-joint slots instead of the body record
+enum JntType : int { J_FREE = 0, J_BALL = 1, J_SLIDE = 2, J_HINGE = 3, J_GLUE = 4 };
 
 // pair type codes, cheapest narrow phase first (the pair list is sorted by this)
 enum PairCode : int {

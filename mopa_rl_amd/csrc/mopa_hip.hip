@@ -111,6 +111,7 @@ struct StreamScratch {
     DevBuf pb_small, pb_rows, pb_act;                         // batched pull-back: verdicts / slots, candidate rows, their active coordinates + verdicts
     DevBuf ct_valid, ct_md, ct_ctr;                           // contact report (mopa_contacts.inc): stage 1's verdicts and depths, stage 2's chunk counter
     DevBuf star_tree, star_k;                                 // RRT* (mopa_rrtstar.inc): one tree slab per wave of a launch, the table k(n)
+    DevBuf glue_rows;                                         // glued scene: the attached rows of a call's env rows (mopa_glue.inc)
     int star_k_n = 0;                                         // entries of star_k, computed for rewire factor star_k_rf
     double star_k_rf = 0.0;
 };
@@ -158,6 +159,8 @@ struct MopaScene {
     int n_cu = 256;
     int32_t *d_gp_tab = nullptr;   // v5: FP32 broad-phase table [n_gp][8]
     K1Policy k1;              // which validity kernels the scene gets (filled by the scene compiler's last step)
+    // glued scene (mopa_scene_create_glued): model body ids (-1: not glued), their moving-body ids, qpos address of body_b's free joint
+    int glue_a = -1, glue_b = -1, glue_mb_a = -1, glue_mb_b = -1, glue_adr = -1;
     int k1_baked = 0;         // k_is_valid_v5 on a baked scene: its index in MOPA_K1_BAKED_SCENES (0: the generic instantiation)
     // Launch scratch, one set PER STREAM: a scene may be driven from several streams at once (validity on one stream while
     // the planner or the previous step's motion check runs on another); calls on the same stream are ordered by the
@@ -306,6 +309,12 @@ MOPA_D void fk_one_geom(const SceneHdr &h, const LdsView &v, int lane) {
             const double *qp = v.qbuf + qsrc0;
             pos = V3{qp[0], qp[1], qp[2]};
             quat = quat_normalize(Q4{qp[3], qp[4], qp[5], qp[6]});
+        } else if (jt0 == J_GLUE) {
+            // a glued scene's carried body: the jointless step under body_a (a moving body, so k > 0: pos / quat / mat are the parent's),
+            // local pose out of the state's free-joint slots
+            const double *qp = v.qbuf + qsrc0;
+            pos = add3(pos, mat_vec(mat, ld3(qp)));
+            quat = quat_normalize(quat_mul(quat, Q4{qp[3], qp[4], qp[5], qp[6]}));
         } else {
             V3 ppos;
             Q4 pquat;
@@ -584,11 +593,11 @@ __global__ __launch_bounds__(kBlock) void k_debug_state(SceneHdr h, const double
 
 // Host export of what K1 reads from a scene (no device needed): sizes[8] = n_dbl, n_int, n_tab (int32 words of the FP32 pair
 // table + its per-geom tail), sizeof(SceneHdr), use_v5, centres in LDS, mesh pairs, nmg.  The buffers may be null (sizes only).
-extern "C" int mopa_scene_k1_export(const MopaSceneDesc *desc, int64_t *sizes, double *dbl, int32_t *ints, int32_t *tab, void *hdr,
-                                    uint64_t *fingerprint) {
+static int scene_k1_export(const MopaSceneDesc *desc, int glue_a, int glue_b, int64_t *sizes, double *dbl, int32_t *ints, int32_t *tab, void *hdr,
+                           uint64_t *fingerprint) {
     if (!desc || !sizes) return fail(MOPA_ERR_INVALID_ARG, "null argument");
     MopaScene *S = new MopaScene();
-    const int rc = scene_build_host(desc, S);
+    const int rc = scene_build_host(desc, S, glue_a, glue_b);
     if (rc != MOPA_OK) { delete S; return rc; }
     sizes[0] = (int64_t)S->h_dbl.size(); sizes[1] = (int64_t)S->h_int.size(); sizes[2] = (int64_t)S->h_gp_tab.size();
     sizes[3] = (int64_t)sizeof(SceneHdr); sizes[4] = S->k1.use_v5; sizes[5] = S->k1.v5_cen_lds ? 1 : 0; sizes[6] = S->n_mesh_gp; sizes[7] = S->hdr.nmg;
@@ -600,6 +609,16 @@ extern "C" int mopa_scene_k1_export(const MopaSceneDesc *desc, int64_t *sizes, d
     delete S;
     return MOPA_OK;
 }
+extern "C" int mopa_scene_k1_export(const MopaSceneDesc *desc, int64_t *sizes, double *dbl, int32_t *ints, int32_t *tab, void *hdr,
+                                    uint64_t *fingerprint) {
+    return scene_k1_export(desc, -1, -1, sizes, dbl, ints, tab, hdr, fingerprint);
+}
+// the same export of the glued compile (mopa_scene_create_glued's host half; its refusals are this call's status codes)
+extern "C" int mopa_scene_k1_export_glued(const MopaSceneDesc *desc, int32_t body_a, int32_t body_b, int64_t *sizes, double *dbl, int32_t *ints,
+                                          int32_t *tab, void *hdr, uint64_t *fingerprint) {
+    if (body_a < 0 || body_b < 0) return fail(MOPA_ERR_INVALID_ARG, "glue: body id out of range");
+    return scene_k1_export(desc, body_a, body_b, sizes, dbl, ints, tab, hdr, fingerprint);
+}
 
 // Offsets of the header fields tools/bake_k1_scenes.py reads from an exported header (the compiler's layout, by name).
 extern "C" int mopa_scene_hdr_offset(const char *field) {
@@ -609,6 +628,8 @@ extern "C" int mopa_scene_hdr_offset(const char *field) {
     MOPA_HDR_FIELD(n_save) MOPA_HDR_FIELD(n_pas_b) MOPA_HDR_FIELD(n_dbl) MOPA_HDR_FIELD(n_int) MOPA_HDR_FIELD(o_mbr) MOPA_HDR_FIELD(o_mbd)
     MOPA_HDR_FIELD(o_mgd) MOPA_HDR_FIELD(o_sf_pos) MOPA_HDR_FIELD(o_sf_quat) MOPA_HDR_FIELD(o_sf_mat) MOPA_HDR_FIELD(o_act_ref)
     MOPA_HDR_FIELD(o_pq_adr) MOPA_HDR_FIELD(o_mg_geom) MOPA_HDR_FIELD(thr)
+    MOPA_HDR_FIELD(o_mb_parent) MOPA_HDR_FIELD(o_chain_adr) MOPA_HDR_FIELD(o_chain_len) MOPA_HDR_FIELD(o_chain_items) MOPA_HDR_FIELD(o_g_mb)
+    MOPA_HDR_FIELD(o_mb_load) MOPA_HDR_FIELD(o_mb_save) MOPA_HDR_FIELD(pfk_maxlen) MOPA_HDR_FIELD(n_gp) MOPA_HDR_FIELD(npair) MOPA_HDR_FIELD(o_pairs)
 #undef MOPA_HDR_FIELD
     return -1;
 }
@@ -639,18 +660,19 @@ extern "C" int mopa_k1_baked_fk_host(int index, int64_t n, const double *q_activ
     return fail(MOPA_ERR_INVALID_ARG, "no baked scene #" + std::to_string(index));
 }
 
-extern "C" int mopa_scene_create(const MopaSceneDesc *desc, MopaScene **out) {
+static int scene_create(const MopaSceneDesc *desc, int glue_a, int glue_b, MopaScene **out) {
     if (!desc || !out) return fail(MOPA_ERR_INVALID_ARG, "null argument");
     MopaScene *S = new MopaScene();
     {
-        const int rc = scene_build_host(desc, S);
+        const int rc = scene_build_host(desc, S, glue_a, glue_b);
         if (rc != MOPA_OK) { delete S; return rc; }
     }
     {
         // K1 on a baked scene (mopa_valid_v5_baked.inc) when the fingerprint matches; MOPA_K1_BAKED=0: always the generic kernel (A/B runs)
         const char *eb = std::getenv("MOPA_K1_BAKED");
         const uint64_t fp = k1_fingerprint(S);
-        const bool allowed = !(eb && std::string(eb) == "0") && S->k1.use_v5 && S->k1.v5_cen_lds && S->n_mesh_gp == 0;
+        // (a glued scene's tables never equal a baked scene's: it runs the generic kernels)
+        const bool allowed = !(eb && std::string(eb) == "0") && S->k1.use_v5 && S->k1.v5_cen_lds && S->n_mesh_gp == 0 && S->glue_b < 0;
         S->k1_baked = allowed ? k1_baked_index(fp) : 0;
         if (std::getenv("MOPA_DEBUG"))
             fprintf(stderr, "[mopa] scene fingerprint %016llx: k_is_valid_v5 %s%s\n", (unsigned long long)fp, S->k1_baked ? "baked #" : "generic",
@@ -699,6 +721,11 @@ extern "C" int mopa_scene_create(const MopaSceneDesc *desc, MopaScene **out) {
     *out = S;
     return MOPA_OK;
 }
+extern "C" int mopa_scene_create(const MopaSceneDesc *desc, MopaScene **out) { return scene_create(desc, -1, -1, out); }
+extern "C" int mopa_scene_create_glued(const MopaSceneDesc *desc, int32_t body_a, int32_t body_b, MopaScene **out) {
+    if (body_a < 0 || body_b < 0) return fail(MOPA_ERR_INVALID_ARG, "glue: body id out of range");
+    return scene_create(desc, body_a, body_b, out);
+}
 
 extern "C" void mopa_scene_destroy(MopaScene *S) {
     if (!S) return;
@@ -709,7 +736,7 @@ extern "C" void mopa_scene_destroy(MopaScene *S) {
     for (auto &kv : S->scratch) {
         StreamScratch &sc = kv.second;
         for (DevBuf *b : {&sc.slab, &sc.mpr, &sc.cen, &sc.mesh_list, &sc.mesh_rows, &sc.mv_cnt, &sc.mv_off, &sc.mv_env, &sc.mv_q, &sc.mv_valid, &sc.mv_scan, &sc.plan_q,
-                          &sc.plan_p, &sc.plan_ctr, &sc.pb_small, &sc.pb_rows, &sc.pb_act, &sc.ip_walk, &sc.ct_valid, &sc.ct_md, &sc.ct_ctr, &sc.star_tree, &sc.star_k, &sc.race_rec, &sc.race_word})
+                          &sc.plan_p, &sc.plan_ctr, &sc.pb_small, &sc.pb_rows, &sc.pb_act, &sc.ip_walk, &sc.ct_valid, &sc.ct_md, &sc.ct_ctr, &sc.star_tree, &sc.star_k, &sc.race_rec, &sc.race_word, &sc.glue_rows})
             if (b->p) (void)hipFree(b->p);
     }
     for (void *q : S->retired) (void)hipFree(q);
@@ -733,6 +760,9 @@ static int grid_for(const MopaScene *S, int64_t N) {
     return (int)std::max<int64_t>(1, std::min(blocks, cap));
 }
 
+// glue_bodies: k_glue_attach / k_glue_rows, mopa_glue_attach_batch / mopa_glue_rows_batch / mopa_scene_glue, MOPA_REFUSE_GLUED
+#include "mopa_glue.inc"
+
 // K1 host side: thresholds, kernel table, k1_plan, launch_is_valid, mopa_is_valid_batch, mopa_scene_valid_kernel
 #include "mopa_valid_launch.inc"
 
@@ -745,6 +775,10 @@ extern "C" int mopa_check_motion_batch(MopaScene *S, const double *qa, const dou
     if (N == 0) return MOPA_OK;
     ON_DEVICE(S->device);
     hipStream_t st = (hipStream_t)stream;
+    if (S->glue_b >= 0) {       // glued scene: every env row attaches at its own joint values
+        const int rc = glue_attach_scratch(S, qpos_env, (N + samples_per_env - 1) / samples_per_env, st, &qpos_env);
+        if (rc) return rc;
+    }
     // large batches: expand every segment into its states, validate them with the lane-per-state kernel, AND per segment
     if (S->k1.use_v2 && N >= k1_motion_expand_min(S)) return motion_expanded(S, qa, qb, qpos_env, N, samples_per_env, valid, st);
     dim3 grid(grid_for(S, N)), block(kBlock);
@@ -783,8 +817,13 @@ static int run_debug(MopaScene *S, const double *qpos_host) {
     ON_DEVICE(S->device);
     int rc = upload_state(S, qpos_host);
     if (rc) return rc;
+    const double *row = S->d_q;
+    if (S->glue_b >= 0) {       // glued scene: the state attaches at its own joint values, as in mopa_is_valid_state
+        rc = glue_attach_scratch(S, S->d_q, 1, nullptr, &row);
+        if (rc) return rc;
+    }
     hipLaunchKernelGGL(S->hdr.has_mesh ? k_debug_state<true> : k_debug_state<false>, dim3(1), dim3(kBlock), S->lds_bytes, nullptr, S->hdr, S->d_dbl, S->d_int, S->d_q + S->nq,
-                       S->d_q, S->d_dbg, S->d_dbg + (size_t)kGeomStride * S->hdr.ng);
+                       row, S->d_dbg, S->d_dbg + (size_t)kGeomStride * S->hdr.ng);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipDeviceSynchronize());
     return MOPA_OK;

@@ -606,6 +606,7 @@ static int k9_launch(int level, MopaScene *S, int64_t E, int32_t max_path, doubl
     static const char *const what[3] = {"simplification", "shortcutting", "smoothing"};
     const int top = (4 << level) - 1;           // passes: 1..3, 1..7, 1..15
     if (!S || (E > 0 && (!path_dev || !path_len_dev))) return fail(MOPA_ERR_INVALID_ARG, "null argument");
+    MOPA_REFUSE_GLUED(S, std::string("path ") + what[level]);
     if (E < 0 || max_path < 2 || passes < 1 || passes > top || (level >= 1 && max_rounds < 1))
         return fail(MOPA_ERR_INVALID_ARG, "E < 0, max_path < 2" + std::string(level ? "," : " or") + " passes outside 1.." + std::to_string(top) +
                                               (level ? " or max_rounds < 1" : ""));

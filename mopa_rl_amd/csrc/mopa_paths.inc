@@ -284,6 +284,7 @@ extern "C" int mopa_interpolate_batch(MopaScene *S, int64_t E, int32_t n_arm, in
                                       double ac_scale, double *traj_dev, int32_t *traj_len_dev, uint8_t *ok_dev, int32_t *n_steps_dev,
                                       void *stream) {
     if (!S || (E > 0 && (!cur_dev || !target_dev || !traj_dev || !traj_len_dev || !ok_dev || !n_steps_dev))) return fail(MOPA_ERR_INVALID_ARG, "null argument");
+    MOPA_REFUSE_GLUED(S, "the straight-line pre-check (mopa_interpolate_batch)");
     if (E < 0 || K <= 0 || K > 64 || n_arm < S->na || n_arm > S->nq) return fail(MOPA_ERR_INVALID_ARG, "bad pre-check sizes (1 <= K <= 64, na <= n_arm <= nq)");
     if (n_arm != S->na) return fail(MOPA_ERR_UNSUPPORTED, "the interpolated joints must be the planner's active joints");
     for (int a = 0; a < S->na; a++)

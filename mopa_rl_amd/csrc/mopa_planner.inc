@@ -294,6 +294,10 @@ MOPA_D void ms_fk(const SceneHdr &h, const double *D, const int *I, const double
                 const double *qp = qb + (cur.w7 >> 8);
                 pos = V3{qp[0], qp[1], qp[2]};
                 quat = quat_normalize(Q4{qp[3], qp[4], qp[5], qp[6]});
+            } else if (jt0 == J_GLUE) {     // the carried body of a glued scene: the jointless step, local pose out of the state's free-joint slots
+                const double *qp = qb + (cur.w7 >> 8);
+                pos = add3(pos, mat_vec(mat, ld3(qp)));
+                quat = quat_normalize(quat_mul(quat, Q4{qp[3], qp[4], qp[5], qp[6]}));
             } else {
                 const double *bd = D + h.o_mbd + 16 * body;
                 pos = add3(pos, mat_vec(mat, cur.bp));
@@ -521,6 +525,8 @@ __global__ __launch_bounds__(64) void k_debug_ms_fk(SceneHdr h, const double *__
     for (int i = lane; i < ns * gstride; i += 64) sink[i] = grec[i];
 }
 extern "C" int mopa_debug_fk_bench(MopaScene *S, const double *row_dev, const double *qs_dev, int ns, int iters, unsigned long long *ticks3, double *sink_dev) {
+    if (!S) return fail(MOPA_ERR_INVALID_ARG, "null argument");
+    MOPA_REFUSE_GLUED(S, "the FK timing probe (mopa_debug_fk_bench)");
     ON_DEVICE(S->device);
     unsigned long long *d_t = nullptr;
     HIP_TRY(hipMalloc((void **)&d_t, 24));
@@ -615,8 +621,18 @@ extern "C" int mopa_plan_batch(MopaScene *S, const double *start, const double *
         return fail(MOPA_ERR_INVALID_ARG, "keeping planner state needs tree_q_dev, tree_p_dev and state_dev together");
     if (params->resume_state && (!params->resume_tree_q || !params->resume_tree_p))
         return fail(MOPA_ERR_INVALID_ARG, "resume_state needs resume_tree_q and resume_tree_p");
+    if (S->glue_b >= 0 && (params->tree_q_dev || params->state_dev || params->resume_state))
+        return fail(MOPA_ERR_UNSUPPORTED, "planner continuation (kept / resumed planner state) is not built for a glued scene (glue_bodies)");
     if (E == 0) return MOPA_OK;
     ON_DEVICE(S->device);
+    // glued scene: the start row attaches (passive values come from it, the goal row's free-joint slots are never read); k_glue_rows
+    // behind the planner writes the carried body's pose into the free-joint columns of the solved paths
+    const double *glue_att = nullptr;
+    if (S->glue_b >= 0) {
+        const int rc = glue_attach_scratch(S, start, E, (hipStream_t)stream, &glue_att);
+        if (rc) return rc;
+        start = glue_att;
+    }
     StreamScratch &sc = scratch_for(S, (hipStream_t)stream);
     HIP_TRY(grow(S, sc.plan_q, (size_t)E * 2 * (size_t)params->max_nodes * S->na * sizeof(double) + 64));   // + pad: nn_node8 reads 8 doubles per node
     HIP_TRY(grow(S, sc.plan_p, (size_t)E * 2 * (size_t)params->max_nodes * sizeof(int32_t)));
@@ -652,6 +668,7 @@ extern "C" int mopa_plan_batch(MopaScene *S, const double *start, const double *
                            *params, ws, path, path_len, status, (long long *)n_checks, g.scene_bytes, g.ctr, g.nn_cap, K3NoArgs{});
     }
     HIP_TRY(hipGetLastError());
+    if (glue_att) return mopa_glue_rows_batch(S, path, path_len, glue_att, E, params->max_path, stream);
     return MOPA_OK;
 }
 

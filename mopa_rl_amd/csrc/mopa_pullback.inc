@@ -243,6 +243,7 @@ extern "C" int mopa_pullback_batch(MopaScene *S, const double *cur, double *targ
                                    int32_t *n_trials, uint8_t *valid, void *stream) {
     if (!S || (E > 0 && (!cur || !target || !n_trials || !valid))) return fail(MOPA_ERR_INVALID_ARG, "null argument");
     if (E < 0 || num_trials < 0) return fail(MOPA_ERR_INVALID_ARG, "bad pull-back parameters");
+    MOPA_REFUSE_GLUED(S, "the pull-back (mopa_pullback_batch)");
     if (E == 0) return MOPA_OK;
     ON_DEVICE(S->device);
     hipStream_t st = (hipStream_t)stream;

@@ -89,6 +89,7 @@ extern "C" int mopa_plan_race_batch(MopaScene *S, const double *start, const dou
     if (E < 0 || params->max_nodes < 2 || params->max_path < 2 || params->max_iters < 0)
         return fail(MOPA_ERR_INVALID_ARG, "bad plan parameters");
     if (params->portfolio < 1 || params->portfolio > 256) return fail(MOPA_ERR_INVALID_ARG, "portfolio must be 1 .. 256");
+    MOPA_REFUSE_GLUED(S, "the K3 race (mopa_plan_race)");
     if (E == 0) return MOPA_OK;
     ON_DEVICE(S->device);
     hipStream_t st = (hipStream_t)stream;
@@ -143,6 +144,7 @@ extern "C" int mopa_plan_race(MopaScene *S, const double *start_host, const doub
     if (!S || !start_host || !goal_host || !params || !path_host || !path_len_out || !status_out)
         return fail(MOPA_ERR_INVALID_ARG, "null argument");
     if (params->max_path < 2) return fail(MOPA_ERR_INVALID_ARG, "bad plan parameters");
+    MOPA_REFUSE_GLUED(S, "the K3 race (mopa_plan_race)");
     MopaRaceParams one = *params;
     one.env_ids_dev = nullptr;   // single query: the stream id is env_id_base
     one.seeds_dev = nullptr;

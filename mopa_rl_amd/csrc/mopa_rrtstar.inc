@@ -318,6 +318,7 @@ extern "C" int mopa_plan_star_batch(MopaScene *S, const double *start, const dou
                                     int32_t *path_len, int32_t *status, double *cost, int64_t *info, void *stream) {
     if (!S || !params || (E > 0 && (!start || !goal || !path || !path_len || !status))) return fail(MOPA_ERR_INVALID_ARG, "null argument");
     const MopaStarParams &p = *params;
+    MOPA_REFUSE_GLUED(S, "RRT* (mopa_plan_star)");
     if (E < 0 || p.max_iters < 0 || p.max_nodes < 2 || p.max_path < 2 || !(p.goal_bias >= 0.0 && p.goal_bias <= 1.0) || !(p.goal_threshold >= 0.0) ||
         !(p.rewire_factor > 0.0) || !std::isfinite(p.rewire_factor))
         return fail(MOPA_ERR_INVALID_ARG, "bad RRT* parameters (E < 0, max_iters < 0, max_nodes < 2, max_path < 2, goal_bias outside [0, 1], "
@@ -374,6 +375,7 @@ extern "C" int mopa_plan_star(MopaScene *S, const double *start_host, const doub
                               int32_t *path_len_out, int32_t *status_out, double *cost_out, int64_t *info_out) {
     if (!S || !start_host || !goal_host || !params || !path_host || !path_len_out || !status_out) return fail(MOPA_ERR_INVALID_ARG, "null argument");
     if (params->max_path < 2) return fail(MOPA_ERR_INVALID_ARG, "max_path < 2");
+    MOPA_REFUSE_GLUED(S, "RRT* (mopa_plan_star)");
     MopaStarParams one = *params;
     one.env_ids_dev = nullptr;
     one.seeds_dev = nullptr;

@@ -22,7 +22,14 @@ struct SceneBuild {
     MopaScene *S;
     SceneHdr &h;
     Builder B;
-    SceneBuild(const MopaSceneDesc *desc_, MopaScene *S_) : desc(desc_), m(desc_->model), S(S_), h(S_->hdr) {}
+    // glued compile (mopa_scene_create_glued): model body ids, -1 = the ordinary compile.  body glue_b is compiled as a jointless child of
+    // glue_a whose local pose comes from the state's free-joint slots (J_GLUE); `par` is the body tree every step walks.
+    int glue_a = -1, glue_b = -1;
+    std::vector<int> par;
+    std::vector<char> in_glue;         // [nbody] 1 = glue_b or below it
+    SceneBuild(const MopaSceneDesc *desc_, MopaScene *S_, int glue_a_ = -1, int glue_b_ = -1)
+        : desc(desc_), m(desc_->model), S(S_), h(S_->hdr), glue_a(glue_a_), glue_b(glue_b_) {}
+    bool glued() const { return glue_b >= 0; }
 
     // 1.
     double reach = 0.0;
@@ -83,16 +90,35 @@ int SceneBuild::check_model() {
     // depending on the cull, and MuJoCo's own contact list (dist < margin) would have to be reproduced.  The reference
     // passes negative thresholds (config/sawyer.py:98-100, config/pusher.py:79-81); 0 keeps "any penetration".
     if (desc->contact_threshold > 0.0) return fail(MOPA_ERR_UNSUPPORTED, "contact_threshold > 0 is not supported (the broad phase culls at zero margin)");
+    par.assign(m.body_parent, m.body_parent + m.nbody);
+    in_glue.assign(m.nbody, 0);
+    if (glued()) {
+        // (the reference: GlueTransformation, mujoco_ompl_interface.cpp:810-907; its two-slide branch is not built)
+        if (glue_a <= 0 || glue_a >= m.nbody || glue_b <= 0 || glue_b >= m.nbody) return fail(MOPA_ERR_INVALID_ARG, "glue: body id out of range (the world body cannot be glued)");
+        if (m.body_jntnum[glue_b] != 1 || m.jnt_type[m.body_jntadr[glue_b]] != J_FREE)
+            return fail(MOPA_ERR_UNSUPPORTED, "glue: body_b must carry exactly one free joint (the reference's two-slide branch is not built)");
+        bool a_static = true;
+        for (int b = glue_a; b > 0; b = m.body_parent[b])
+            if (m.body_jntnum[b] > 0) a_static = false;
+        if (a_static) return fail(MOPA_ERR_UNSUPPORTED, "glue: body_a is static (no joint moves it)");
+        for (int b = glue_a; b > 0; b = m.body_parent[b])
+            if (b == glue_b) return fail(MOPA_ERR_UNSUPPORTED, "glue: body_a lies inside body_b's subtree");
+        if (glue_a >= glue_b) return fail(MOPA_ERR_UNSUPPORTED, "glue: body_a must come before body_b in body order");
+        par[glue_b] = glue_a;
+        in_glue[glue_b] = 1;
+        for (int b = glue_b + 1; b < m.nbody; b++) in_glue[b] = in_glue[m.body_parent[b]];
+    }
     // FP32 broad phase (third-generation kernel): its conservativeness proof assumes coordinates of a few metres (absolute
     // slack 2e-5 m vs the float rounding of a coordinate).  `reach` bounds every model-determined coordinate; larger scenes
     // use the FP64 cull of the second generation.  Free-joint positions come from qpos at run time and are the caller's
-    // responsibility (the Sawyer world box is +-1.2 m x 2 m, env/sawyer/sawyer.py:52-53).
+    // responsibility (the Sawyer world box is +-1.2 m x 2 m, env/sawyer/sawyer.py:52-53).  So is, in a glued compile, the offset
+    // of the carried body from body_a: `reach` counts body_b at the origin of body_a, the attach state decides how far away it is.
     reach = 0.0;
     {
         std::vector<double> rb(m.nbody, 0.0);
         for (int b = 1; b < m.nbody; b++) {
             const double *p = m.body_pos + 3 * b;
-            rb[b] = rb[m.body_parent[b]] + sqrt(p[0] * p[0] + p[1] * p[1] + p[2] * p[2]);
+            rb[b] = (b == glue_b) ? rb[glue_a] : rb[m.body_parent[b]] + sqrt(p[0] * p[0] + p[1] * p[1] + p[2] * p[2]);
             for (int j = m.body_jntadr[b]; j >= 0 && j < m.body_jntadr[b] + m.body_jntnum[b]; j++)
                 if (m.jnt_type[j] == J_SLIDE && m.jnt_limited[j]) rb[b] += std::max(fabs(m.jnt_range[2 * j]), fabs(m.jnt_range[2 * j + 1]));
         }
@@ -170,11 +196,11 @@ int SceneBuild::static_frames() {
     is_static.assign(m.nbody, 0);
     for (int g = 0; g < m.ngeom; g++) {
         int b = m.geom_body[g];
-        while (b > 0 && !needed[b]) { needed[b] = 1; b = m.body_parent[b]; }
+        while (b > 0 && !needed[b]) { needed[b] = 1; b = par[b]; }
     }
     needed[0] = 1;
     is_static[0] = 1;
-    for (int b = 1; b < m.nbody; b++) is_static[b] = (m.body_jntnum[b] == 0) && is_static[m.body_parent[b]];
+    for (int b = 1; b < m.nbody; b++) is_static[b] = (m.body_jntnum[b] == 0) && is_static[par[b]];
 
     // static world frames (host FK with the same arithmetic as the device path)
     xpos.assign(3 * m.nbody, 0.0);
@@ -222,12 +248,26 @@ int SceneBuild::moving_bodies() {
     };
     for (int k = 0; k < nmb; k++) {
         int b = mb_body[k];
-        int pid = m.body_parent[b];
+        int pid = par[b];
         mb_parent.push_back(mb_of_body[pid] >= 0 ? mb_of_body[pid] : -(sf_index(pid) + 1));
         mb_pos.insert(mb_pos.end(), m.body_pos + 3 * b, m.body_pos + 3 * b + 3);
         mb_quat.insert(mb_quat.end(), m.body_quat + 4 * b, m.body_quat + 4 * b + 4);
         mb_jntadr.push_back((int)mj_type.size());
         mb_jntnum.push_back(m.body_jntnum[b]);
+        if (b == glue_b) {
+            // the carried body: one J_GLUE "joint" whose value slots are the free joint's 7 passive slots, read as the body's local pose
+            // (pos[3] quat[4]) under body_a; the joint itself applies nothing (apply_joint knows slide and hinge only)
+            const int adr = m.jnt_qposadr[m.body_jntadr[b]];
+            mj_type.push_back(J_GLUE);
+            mj_axis.insert(mj_axis.end(), 3, 0.0);
+            mj_pos.insert(mj_pos.end(), 3, 0.0);
+            mj_ref.push_back(0.0);
+            const int first = passive_slot(adr);
+            for (int c = 1; c < 7; c++)
+                if (passive_slot(adr + c) != first + c) { return fail(MOPA_ERR_UNSUPPORTED, "free joint qpos not contiguous in the passive list"); }
+            mj_qsrc.push_back(first);
+            continue;
+        }
         for (int j = m.body_jntadr[b]; j < m.body_jntadr[b] + m.body_jntnum[b]; j++) {
             int t = m.jnt_type[j];
             if (t == J_BALL) { return fail(MOPA_ERR_UNSUPPORTED, "ball joints are not supported (the reference throws as well: mujoco_ompl_interface.cpp:217-229)"); }
@@ -355,6 +395,15 @@ int SceneBuild::dfs_program() {
             else if (pk == k - 1) mb_load[k] = -1;
             else mb_load[k] = mb_save[pk];
         }
+        if (glued() && mb_save[mb_of_body[glue_a]] >= 0) {
+            // The save slots above are numbered by depth, which is right for a tree in depth-first body order.  The carried body comes
+            // long after body_a's own subtree, and whatever was parked at body_a's depth in between has overwritten its slot: body_a gets a
+            // slot of its own.
+            const int ka = mb_of_body[glue_a];
+            mb_save[ka] = n_save++;
+            for (int k = 0; k < nmb; k++)
+                if (mb_parent[k] == ka && mb_load[k] >= 0) mb_load[k] = mb_save[ka];
+        }
     }
     // moving geoms are in geom-id order == body order, so each body's geoms are a contiguous slot range
     for (int mslot = 0; mslot < nmg; mslot++) {
@@ -445,7 +494,8 @@ int SceneBuild::fp32_table() {
                     const float rg = (float)g_rbound[mg_geom[mslot]] + kCullEps;
                     auto ff2i = [](float f) { int32_t i; std::memcpy(&i, &f, 4); return i; };
                     float rs = rg + (float)g_rbound[pg];
-                    if (desc->pair_cull_radius) {
+                    // (a glued compile: the proofs were made with the carried body where the env row puts it -- not for its pairs)
+                    if (desc->pair_cull_radius && !in_glue[m.geom_body[mg_geom[mslot]]] && !in_glue[m.geom_body[pg]]) {
                         // a proven bound on the centre distance at which this pair can reach the threshold at all
                         const int own = mg_geom[mslot];
                         for (int pp = 0; pp < m.npair; pp++) {
@@ -744,8 +794,10 @@ int SceneBuild::k1_policy() {
 }  // namespace
 
 // Host half of scene creation: runs the steps in order; the first refusal ends it.
-static int scene_build_host(const MopaSceneDesc *desc, MopaScene *S) {
-    SceneBuild W(desc, S);
+// glue_a / glue_b >= 0: the glued compile of the same description (mopa_scene_create_glued); the ordinary compile's output does not
+// depend on any of the glue code (every glued step is behind glued()).
+static int scene_build_host(const MopaSceneDesc *desc, MopaScene *S, int glue_a = -1, int glue_b = -1) {
+    SceneBuild W(desc, S, glue_a, glue_b);
     for (int (SceneBuild::*step)() : {&SceneBuild::check_model, &SceneBuild::split_active, &SceneBuild::static_frames, &SceneBuild::moving_bodies,
                                       &SceneBuild::geoms_and_pairs, &SceneBuild::dfs_program, &SceneBuild::pair_lists, &SceneBuild::fp32_table,
                                       &SceneBuild::packed_records, &SceneBuild::assemble_tables, &SceneBuild::tile_poses, &SceneBuild::planner_fk,
@@ -756,6 +808,12 @@ static int scene_build_host(const MopaSceneDesc *desc, MopaScene *S) {
     S->hdr_mesh = S->hdr;
     S->hdr_mesh.o_mgr = W.o_mgr_mesh; S->hdr_mesh.o_gp_word = W.o_gp_word_mesh; S->hdr_mesh.n_gp = (int)W.gp_word_mesh.size();
     S->n_mesh_gp = (int)W.gp_word_mesh.size();
+    if (W.glued()) {
+        S->glue_a = glue_a; S->glue_b = glue_b;
+        S->glue_mb_a = W.mb_of_body[glue_a]; S->glue_mb_b = W.mb_of_body[glue_b];
+        S->glue_adr = desc->model.jnt_qposadr[desc->model.body_jntadr[glue_b]];
+        if (S->glue_mb_a < 0 || S->glue_mb_b < 0) return fail(MOPA_ERR_UNSUPPORTED, "glue: body_b carries no collidable geom (nothing to glue)");
+    }
     return MOPA_OK;
 }
 

@@ -171,17 +171,30 @@ extern "C" int mopa_scene_valid_kernel(const MopaScene *S, int64_t N, char *out,
     std::snprintf(out, (size_t)cap, "%s", !p.lane ? "k_is_valid" : (p.v5 ? "k_is_valid_v5" : "k_is_valid_v2"));
     return MOPA_OK;
 }
+// the form mopa_check_motion_batch takes for N segments: the wave-per-segment kernel, or the expansion into states
+extern "C" int mopa_scene_motion_kernel(const MopaScene *S, int64_t N, char *out, int32_t cap) {
+    if (!S || !out || cap < 24) return fail(MOPA_ERR_INVALID_ARG, "null argument / buffer under 24 bytes");
+    std::snprintf(out, (size_t)cap, "%s", S->k1.use_v2 && N >= k1_motion_expand_min(S) ? "k_motion_expand" : "k_check_motion");
+    return MOPA_OK;
+}
 
 // state validity of N states; env row of state i = env_idx ? env_idx[i] : i / samples_per_env
 // n_dev (nullable): the number of states is only known on the device (*n_dev <= N, N then sizes the launch): served by the
 // lane-per-state kernel, which reads it when it starts -- no host read-back between the producer of the states and this launch
+// attach (the public entry point; env_idx == nullptr): on a glued scene qpos_env holds ordinary rows, and every env row attaches at its
+// own joint values behind the argument checks, as in mopa_check_motion_batch; every other caller hands over attached rows
 static int launch_is_valid(MopaScene *S, const double *q_active, const double *qpos_env, int64_t N, int64_t samples_per_env,
-                           const int *env_idx, uint8_t *valid, double *min_dist, void *stream, const long long *n_dev = nullptr) {
+                           const int *env_idx, uint8_t *valid, double *min_dist, void *stream, const long long *n_dev = nullptr,
+                           bool attach = false) {
     if (!S || !valid || (N > 0 && (!q_active || !qpos_env))) return fail(MOPA_ERR_INVALID_ARG, "null argument");
     if (N < 0 || samples_per_env <= 0) return fail(MOPA_ERR_INVALID_ARG, "N < 0 or samples_per_env <= 0");
     if (N == 0) return MOPA_OK;
     ON_DEVICE(S->device);
     hipStream_t st = (hipStream_t)stream;
+    if (attach && S->glue_b >= 0) {
+        const int rc = glue_attach_scratch(S, qpos_env, (N + samples_per_env - 1) / samples_per_env, st, &qpos_env);
+        if (rc) return rc;
+    }
     dim3 block(kBlock);
     const K1Plan p = k1_plan(S, N, min_dist != nullptr, env_idx != nullptr, n_dev != nullptr);
     if (p.refusal) return fail(MOPA_ERR_UNSUPPORTED, p.refusal);
@@ -268,5 +281,5 @@ static int launch_is_valid(MopaScene *S, const double *q_active, const double *q
 
 extern "C" int mopa_is_valid_batch(MopaScene *S, const double *q_active, const double *qpos_env, int64_t N,
                                    int64_t samples_per_env, uint8_t *valid, double *min_dist, void *stream) {
-    return launch_is_valid(S, q_active, qpos_env, N, samples_per_env, nullptr, valid, min_dist, stream);
+    return launch_is_valid(S, q_active, qpos_env, N, samples_per_env, nullptr, valid, min_dist, stream, nullptr, true);
 }

@@ -216,9 +216,15 @@ __global__ __launch_bounds__(kBlock) void k_is_valid_v2(SceneHdr h, const double
                     ppos = pos;
                     pquat = quat;
                 }
-                V3 vv = mat_vec(mat, ld3(bd));
-                pos = add3(ppos, vv);
-                quat = quat_mul(pquat, Q4{bd[3], bd[4], bd[5], bd[6]});
+                if (jt0 == J_GLUE) {            // the carried body of a glued scene: local pose out of the env row's free-joint slots
+                    const double *qp = env_row + GI[h.o_pq_adr + (qsrc0 - h.na)];
+                    pos = add3(ppos, mat_vec(mat, ld3(qp)));
+                    quat = quat_mul(pquat, Q4{qp[3], qp[4], qp[5], qp[6]});
+                } else {
+                    V3 vv = mat_vec(mat, ld3(bd));
+                    pos = add3(ppos, vv);
+                    quat = quat_mul(pquat, Q4{bd[3], bd[4], bd[5], bd[6]});
+                }
                 for (int jj = 0; jj < bi.jn; jj++) {
                     V3 ax, jp;
                     double ref;

@@ -31,7 +31,14 @@ Differences that cannot be hidden (DESIGN.md "Semantics"):
     attribute ``path_smooth``.  The three together are ``simplify()``'s
     schedule without its wall clock; checkAndRepair is not built (every
     segment of a result has itself passed the motion check);
-  * ``glue_bodies`` must be empty (the reference never passes any).
+  * ``glue_bodies = [body_a, body_b]`` (names, str or bytes) plans with
+    ``body_b`` -- the manipulated object, a body with one free joint --
+    attached to ``body_a``: ``plan`` attaches at the start state,
+    ``isValidState`` at the state itself, and the free-joint columns of a
+    solved path hold the object's pose at every waypoint (the weld form of
+    the reference's GlueTransformation).  Built for
+    rrt_connect with ``portfolio == 1`` and no K9 switch; the reference's
+    two-slide branch (Pusher's box) is not built.
 """
 from __future__ import annotations
 
@@ -70,7 +77,9 @@ class PyKinematicPlanner:
         self.simplifiedDuration = float(simplified_duration)
         self.seed = int(seed)
         if self.glue_bodies:
-            raise NotImplementedError("glue_bodies: never used by the reference callers, not implemented")
+            if len(self.glue_bodies) != 2 or not all(isinstance(b, (str, bytes, bytearray)) for b in self.glue_bodies):
+                raise NotImplementedError("glue_bodies: only the empty list and two body names [body_a, body_b] (str or bytes) are implemented")
+            self.glue_bodies = [_to_str(b) for b in self.glue_bodies]
         if self.algo not in ("rrt_connect", "rrt_star"):
             raise NotImplementedError(f"algo={self.algo!r}: only 'rrt_connect' and 'rrt_star' (the reference's 'rrt' = RRT*) are implemented")
         if self.algo == "rrt_star" and self.opt not in ("", "path_length"):
@@ -89,16 +98,19 @@ class PyKinematicPlanner:
         self.path_smooth = False
         #: K3 race: with rrt_connect, plan() runs `portfolio` seeded members per query and returns the winner's path (DESIGN.md "K3 race")
         self.portfolio = 1
+        self._check_glue_combination()
         self._model = load_scene(self.xml_filename)
         self._scene = _lib.Scene(self._model, self.passive_joint_idx, self.ignored_contacts, self.contact_threshold,
                                  range_=self._range, resolution=0.005, seed=self.seed)
+        #: the scene plan() and isValidState() run on: with glue_bodies the glued sibling (closed with `_scene`)
+        self._query_scene = self._scene.glued(*self.glue_bodies) if self.glue_bodies else self._scene
         self._plan_count = 0
         #: RRT*: the cost (L1 length) of the last plan()'s path, +inf when it found none
         self.last_cost = float("inf")
 
     # -- reference API -----------------------------------------------------
     def isValidState(self, state_vec) -> bool:
-        return self._scene.is_valid_state(np.asarray(state_vec, dtype=np.float64))
+        return self._query_scene.is_valid_state(np.asarray(state_vec, dtype=np.float64))
 
     def plan(self, start_vec, goal_vec, timelimit) -> List[List[float]]:
         start = np.asarray(start_vec, dtype=np.float64)
@@ -106,6 +118,7 @@ class PyKinematicPlanner:
         max_iters = max(1, int(round(float(timelimit) * ITERS_PER_SECOND)))
         # every plan() call of one planner object draws a fresh sample stream
         k9_seed = self.seed
+        self._check_glue_combination()
         if int(self.portfolio) > 1 and self.algo == "rrt_star":
             raise NotImplementedError("portfolio > 1 is built for rrt_connect only (RRT* always spends its whole budget: nothing to race)")
         if self.algo == "rrt_star":
@@ -119,8 +132,8 @@ class PyKinematicPlanner:
             status, path, _, _, k9_seed, _ = self._scene.plan_race(start, goal, int(self.portfolio), max_iters=max_iters, max_nodes=MAX_NODES,
                                                                    max_path=MAX_PATH, seed=self.seed, env_id=self._plan_count)
         else:
-            status, path, _ = self._scene.plan(start, goal, max_iters=max_iters, max_nodes=MAX_NODES, max_path=MAX_PATH,
-                                               seed=self.seed, env_id=self._plan_count)
+            status, path, _ = self._query_scene.plan(start, goal, max_iters=max_iters, max_nodes=MAX_NODES, max_path=MAX_PATH,
+                                                     seed=self.seed, env_id=self._plan_count)
         if (self.vertex_simplify or self.path_shortcut or self.path_smooth) and status == _lib.PLAN_OK and len(path) >= 3:
             path = self._simplify(path, self._plan_count, k9_seed)
         self._plan_count += 1
@@ -130,6 +143,18 @@ class PyKinematicPlanner:
         if status != _lib.PLAN_OK:
             return [[-4.0] * nq]
         return path.tolist()
+
+    def _check_glue_combination(self) -> None:
+        """glue_bodies is built for plain rrt_connect: the combinations that are not raise, naming themselves"""
+        if not self.glue_bodies:
+            return
+        if self.algo == "rrt_star":
+            raise NotImplementedError("glue_bodies with algo='rrt_star': glue is built for rrt_connect only")
+        if int(self.portfolio) > 1:
+            raise NotImplementedError("glue_bodies with portfolio > 1: the K3 race is not built for a glued scene")
+        on = [n for n in ("vertex_simplify", "path_shortcut", "path_smooth") if getattr(self, n)]
+        if on:
+            raise NotImplementedError(f"glue_bodies with {' / '.join(on)}: path simplification (K9) is not built for a glued scene")
 
     def _simplify(self, path: np.ndarray, stream_id: int, seed=None) -> np.ndarray:
         """K9 over one solved path: the draws come from the sample stream (seed, stream_id) the plan itself used (a race: the
@@ -156,12 +181,17 @@ class PyKinematicPlanner:
         return rows[0, :int(plen[0])].cpu().numpy()
 
     def getPlannerStatus(self) -> bytes:
-        return self._scene.planner_status()
+        return self._query_scene.planner_status()
 
     # -- extras used by the batched host code --------------------------------
     @property
     def scene(self) -> "_lib.Scene":
-        return self._scene
+        """the scene plan() and isValidState() run on: with glue_bodies the glued one, whose unbuilt entry points refuse.  The
+        glued scene belongs to the ordinary one: `close()` below releases both"""
+        return self._query_scene
+
+    def close(self) -> None:
+        self._scene.close()
 
     @property
     def model(self):
@@ -169,5 +199,8 @@ class PyKinematicPlanner:
 
     def contacts(self, state_vec) -> List[Tuple[str, str, float]]:
         """the pairs that make `state_vec` invalid -- (geom1_name, geom2_name, dist) with dist <= contact_threshold, what the
-        reference's checker finds in d->contact[i] (mujoco_ompl_interface.cpp:917-978); empty for a valid state"""
+        reference's checker finds in d->contact[i] (mujoco_ompl_interface.cpp:917-978); empty for a valid state.  With
+        glue_bodies it raises: the contact report is not built for a glued scene"""
+        if self.glue_bodies:
+            raise NotImplementedError("contacts() with glue_bodies: the contact report is not built for a glued scene")
         return self._scene.contacts_state(np.asarray(state_vec, dtype=np.float64))
