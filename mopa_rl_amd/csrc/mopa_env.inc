@@ -186,8 +186,7 @@ __device__ __forceinline__ void env_step_lane(const EnvHdr &h, const double *__r
         const double *bd = GD + h.o_bd + 16 * b;   // pos[3] quat[4] axis[3] jpos[3] ref
         if (bi.jn == 1 && bi.jt == J_FREE) {
             const double *qp = row + bi.qadr;
-            pos = V3{qp[0], qp[1], qp[2]};
-            quat = quat_normalize(Q4{qp[3], qp[4], qp[5], qp[6]});
+            fk_free_step(qp, pos, quat);
         } else {
             V3 ppos;
             Q4 pquat;
@@ -197,8 +196,7 @@ __device__ __forceinline__ void env_step_lane(const EnvHdr &h, const double *__r
                 quat2mat(mat, pquat);
             } else if (bi.load >= 0) {      // parent pose was parked when the DFS left its subtree
                 const double *sp = save + (size_t)bi.load * 7 * 64 + lane;
-                ppos = V3{sp[0], sp[64], sp[128]};
-                pquat = Q4{sp[192], sp[256], sp[320], sp[384]};
+                pose7_ld<64>(sp, ppos, pquat);
                 quat2mat(mat, pquat);
             } else {                        // parent is the previous body (mat still holds its rotation)
                 ppos = pos;
@@ -226,8 +224,7 @@ __device__ __forceinline__ void env_step_lane(const EnvHdr &h, const double *__r
         quat2mat(mat, quat);
         if (bi.save >= 0) {
             double *sp = save + (size_t)bi.save * 7 * 64 + lane;
-            sp[0] = pos.x; sp[64] = pos.y; sp[128] = pos.z;
-            sp[192] = quat.w; sp[256] = quat.x; sp[320] = quat.y; sp[384] = quat.z;
+            pose7_st<64>(sp, pos, quat);
         }
         // frames on this body (wave-uniform tests)
 #pragma unroll

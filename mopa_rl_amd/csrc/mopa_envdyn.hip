@@ -17,6 +17,7 @@
 
 #include "../../include/mopa_hip.h"
 #include "mopa_device.hpp"
+#include "mopa_fk.hpp"
 #include "mopa_host.hpp"
 
 using namespace mopa;

@@ -12,8 +12,8 @@
 // second time): the same pose up to rounding; on the CPU oracle equal verdicts on every state compared, min_dist equal on all but 0.2 % of them
 // (DESIGN.md section 3).
 
-// World pose of moving body `mb` for one state: the walk of fk_one_geom down the body's chain, with the same arithmetic in the same
-// order (sin / cos of half a hinge angle through apply_joint = mopa_sincos(0.5 * dq), what the sin/cos tables hold).  Value slot s of the
+// World pose of moving body `mb` for one state: the walk of fk_one_geom down the body's chain over the same pieces (mopa_fk.hpp), with the
+// same arithmetic in the same order (sin / cos of half a hinge angle through apply_joint = mopa_sincos(0.5 * dq), what the sin/cos tables hold).  Value slot s of the
 // state is act_row[act_adr[s]] for s < na, else pas_row[pq_adr[s - na]] (both full qpos rows).  Only body_a's chain is walked, and
 // body_b is never on it (body_a below body_b is refused by the scene compiler), so there is no J_GLUE step here.
 MOPA_D void glue_walk(const SceneHdr &h, const double *D, const int *I, int mb, const double *act_row, const double *pas_row, V3 &pos, Q4 &quat,
@@ -30,19 +30,13 @@ MOPA_D void glue_walk(const SceneHdr &h, const double *D, const int *I, int mb, 
         const int jt0 = w7 & 0x7f, qsrc0 = w7 >> 8;
         if (jn == 1 && jt0 == J_FREE) {
             const double *qp = slot_ptr(qsrc0);        // (7 contiguous passive slots: checked by the scene compiler)
-            pos = V3{qp[0], qp[1], qp[2]};
-            quat = quat_normalize(Q4{qp[3], qp[4], qp[5], qp[6]});
+            fk_free_step(qp, pos, quat);
         } else {
             V3 ppos;
             Q4 pquat;
             if (k == 0) {
                 const int sf = r[3];
-                ppos = ld3(D + h.o_sf_pos + 3 * sf);
-                const double *sq = D + h.o_sf_quat + 4 * sf;
-                pquat = Q4{sq[0], sq[1], sq[2], sq[3]};
-                const double *sm = D + h.o_sf_mat + 9 * sf;
-#pragma unroll
-                for (int i = 0; i < 9; i++) mat[i] = sm[i];
+                sf_frame_ld(h, D, sf, ppos, pquat, mat);
             } else {
                 ppos = pos;
                 pquat = quat;

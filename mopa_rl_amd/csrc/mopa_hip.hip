@@ -29,6 +29,7 @@
 #include <mutex>
 #include "../../include/mopa_hip.h"
 #include "mopa_device.hpp"
+#include "mopa_fk.hpp"
 #include "mopa_host.hpp"
 
 using namespace mopa;
@@ -290,7 +291,7 @@ MOPA_D bool pair_culled(const SceneHdr &h, const LdsView &v, int g1, int g2, con
 MOPA_D void fk_one_geom(const SceneHdr &h, const LdsView &v, int lane) {
     // Reads the PACKED per-body records (ints o_mbr: jn, jntadr, -, static-frame id, -, -, -, joint-0 word; doubles o_mbd:
     // pos[3] quat[4] axis[3] jpos[3] ref) -- two levels of dependent LDS reads per body (chain item -> record -> joint value)
-    // where the separate tables needed six; the arithmetic and its order are unchanged.
+    // where the separate tables needed six; the arithmetic and its order are unchanged; the pieces are mopa_fk.hpp's.
     const double *D = v.dbl;
     const int *I = v.ints;
     const int g = I[h.o_mg_geom + lane];
@@ -307,25 +308,19 @@ MOPA_D void fk_one_geom(const SceneHdr &h, const LdsView &v, int lane) {
         const int jt0 = w7 & 0x7f, qsrc0 = w7 >> 8;
         if (jn == 1 && jt0 == J_FREE) {
             const double *qp = v.qbuf + qsrc0;
-            pos = V3{qp[0], qp[1], qp[2]};
-            quat = quat_normalize(Q4{qp[3], qp[4], qp[5], qp[6]});
+            fk_free_step(qp, pos, quat);
         } else if (jt0 == J_GLUE) {
             // a glued scene's carried body: the jointless step under body_a (a moving body, so k > 0: pos / quat / mat are the parent's),
             // local pose out of the state's free-joint slots
             const double *qp = v.qbuf + qsrc0;
-            pos = add3(pos, mat_vec(mat, ld3(qp)));
-            quat = quat_normalize(quat_mul(quat, Q4{qp[3], qp[4], qp[5], qp[6]}));
+            fk_glue_step(pos, quat, mat, qp, pos, quat);
+            quat = quat_normalize(quat);
         } else {
             V3 ppos;
             Q4 pquat;
             if (k == 0) {
                 const int sf = r[3];
-                ppos = ld3(D + h.o_sf_pos + 3 * sf);
-                const double *sq = D + h.o_sf_quat + 4 * sf;
-                pquat = Q4{sq[0], sq[1], sq[2], sq[3]};
-                const double *sm = D + h.o_sf_mat + 9 * sf;
-#pragma unroll
-                for (int i = 0; i < 9; i++) mat[i] = sm[i];
+                sf_frame_ld(h, D, sf, ppos, pquat, mat);
             } else {
                 ppos = pos;
                 pquat = quat;
@@ -345,18 +340,10 @@ MOPA_D void fk_one_geom(const SceneHdr &h, const LdsView &v, int lane) {
         }
         quat2mat(mat, quat);
     }
-    double *rec = v.grec + lane * kGeomStride;
-    const double *gd = D + h.o_mgd + 8 * lane;               // lpos[3] lquat[4] rbound of moving geom `lane`
-    V3 gp = add3(pos, mat_vec(mat, ld3(gd)));
-    Q4 gq = quat_mul(quat, Q4{gd[3], gd[4], gd[5], gd[6]});
-    double gm[9];
-    quat2mat(gm, gq);
-    st3(rec + GO_POS, gp);
-#pragma unroll
-    for (int i = 0; i < 9; i++) rec[GO_MAT + i] = gm[i];
-    // size is constant: copied from the shared record
-    const double *srec = D + h.o_g_rec + g * kGeomStride;
-    rec[GO_SIZE] = srec[GO_SIZE]; rec[GO_SIZE + 1] = srec[GO_SIZE + 1]; rec[GO_SIZE + 2] = srec[GO_SIZE + 2];
+    V3 gp;
+    Q4 gq;
+    fk_geom_pose(pos, quat, mat, D + h.o_mgd + 8 * lane, gp, gq);       // lpos[3] lquat[4] rbound of moving geom `lane`
+    fk_geom_rec_st(v.grec + lane * kGeomStride, gp, gq, D + h.o_g_rec + g * kGeomStride);    // (the size is constant: copied from the shared record)
 }
 MOPA_D void wave_fk(const SceneHdr &h, const LdsView &v, int lane) {
     if (lane < h.nmg) fk_one_geom(h, v, lane);

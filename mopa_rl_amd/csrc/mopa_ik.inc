@@ -111,8 +111,7 @@ __global__ __launch_bounds__(64) void k_ik_solve(IkHdr h, const double *__restri
             const double *bd = GD + h.o_bd + 16 * b;   // pos[3] quat[4] axis[3] jpos[3] ref
             if (bi.jn == 1 && bi.jt == J_FREE) {
                 const double *qp = row + bi.qadr;
-                pos = V3{qp[0], qp[1], qp[2]};
-                quat = quat_normalize(Q4{qp[3], qp[4], qp[5], qp[6]});
+                fk_free_step(qp, pos, quat);
             } else {
                 V3 ppos;
                 Q4 pquat;
@@ -122,8 +121,7 @@ __global__ __launch_bounds__(64) void k_ik_solve(IkHdr h, const double *__restri
                     quat2mat(mat, pquat);
                 } else if (bi.load >= 0) {
                     const double *sp = save + (size_t)bi.load * 7 * 64 + lane;
-                    ppos = V3{sp[0], sp[64], sp[128]};
-                    pquat = Q4{sp[192], sp[256], sp[320], sp[384]};
+                    pose7_ld<64>(sp, ppos, pquat);
                     quat2mat(mat, pquat);
                 } else {
                     ppos = pos;
@@ -147,8 +145,7 @@ __global__ __launch_bounds__(64) void k_ik_solve(IkHdr h, const double *__restri
             if (b + 1 == h.n_pre) { pos0 = pos; quat0 = quat; }
             if (bi.save >= 0) {
                 double *sp = save + (size_t)bi.save * 7 * 64 + lane;
-                sp[0] = pos.x; sp[64] = pos.y; sp[128] = pos.z;
-                sp[192] = quat.w; sp[256] = quat.x; sp[320] = quat.y; sp[384] = quat.z;
+                pose7_st<64>(sp, pos, quat);
             }
             if (bi.col >= 0) {       // [3P] mj_jacSite inputs: joint axis and anchor in the world frame
                 const V3 ax = mat_vec(mat, ld3(bd + 7));
@@ -251,8 +248,7 @@ __global__ __launch_bounds__(64) void k_ik_site_pose(IkHdr h, const double *__re
         const double *bd = GD + h.o_bd + 16 * b;
         if (bi.jn == 1 && bi.jt == J_FREE) {
             const double *qp = row + bi.qadr;
-            pos = V3{qp[0], qp[1], qp[2]};
-            quat = quat_normalize(Q4{qp[3], qp[4], qp[5], qp[6]});
+            fk_free_step(qp, pos, quat);
         } else {
             V3 ppos;
             Q4 pquat;
@@ -262,8 +258,7 @@ __global__ __launch_bounds__(64) void k_ik_site_pose(IkHdr h, const double *__re
                 quat2mat(mat, pquat);
             } else if (bi.load >= 0) {
                 const double *sp = save + (size_t)bi.load * 7 * 64 + lane;
-                ppos = V3{sp[0], sp[64], sp[128]};
-                pquat = Q4{sp[192], sp[256], sp[320], sp[384]};
+                pose7_ld<64>(sp, ppos, pquat);
                 quat2mat(mat, pquat);
             } else {
                 ppos = pos;
@@ -280,8 +275,7 @@ __global__ __launch_bounds__(64) void k_ik_site_pose(IkHdr h, const double *__re
         quat2mat(mat, quat);
         if (bi.save >= 0) {
             double *sp = save + (size_t)bi.save * 7 * 64 + lane;
-            sp[0] = pos.x; sp[64] = pos.y; sp[128] = pos.z;
-            sp[192] = quat.w; sp[256] = quat.x; sp[320] = quat.y; sp[384] = quat.z;
+            pose7_st<64>(sp, pos, quat);
         }
         if (b == h.site_k) {
             st3(site_pos + 3 * e, add3(pos, mat_vec(mat, ld3(GD + h.o_off))));

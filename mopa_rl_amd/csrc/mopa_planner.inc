@@ -243,8 +243,8 @@ MOPA_D unsigned ms_collide(const SceneHdr &h, const LdsView &v0, const MsLds &m,
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// The planner's forward kinematics.  Same arithmetic, in the same order, as fk_one_geom (one lane per moving geom, walking
-// its ancestor chain), restructured for a lone wave that waits on every dependent LDS read:
+// The planner's forward kinematics.  Same arithmetic, in the same order, over the same pieces (mopa_fk.hpp) as fk_one_geom
+// (one lane per moving geom, its ancestor chain), restructured for a lone wave that waits on every dependent LDS read:
 //   * the lane's chain comes packed in four words (h.o_pfk), so the body of step k is register arithmetic, not a read;
 //   * sin / cos AND the displacement of a body's first joint sit in a per-state table indexed by BODY (written by the
 //     pass's table phase), so everything a step needs is one level of reads off the body index ...
@@ -269,13 +269,10 @@ MOPA_D void ms_fk(const SceneHdr &h, const double *D, const int *I, const double
     const int *pw = I + h.o_pfk + 8 * l;
     const unsigned cw0 = (unsigned)pw[0], cw1 = (unsigned)pw[1], cw2 = (unsigned)pw[2], cw3 = (unsigned)pw[3];
     const int clen = pw[4], sf = pw[5];
-    V3 pos = ld3(D + h.o_sf_pos + 3 * sf);
-    const double *sq = D + h.o_sf_quat + 4 * sf;
-    Q4 quat{sq[0], sq[1], sq[2], sq[3]};
+    V3 pos;
+    Q4 quat;
     double mat[9];
-    const double *sm = D + h.o_sf_mat + 9 * sf;
-#pragma unroll
-    for (int i = 0; i < 9; i++) mat[i] = sm[i];
+    sf_frame_ld(h, D, sf, pos, quat, mat);
     const int maxlen = h.pfk_maxlen;
     for (int k = 0; k < maxlen; k++) {
         if (k < clen) {
@@ -291,13 +288,10 @@ MOPA_D void ms_fk(const SceneHdr &h, const double *D, const int *I, const double
                 if (hinge0) q = qj;
                 quat = quat_normalize(q);
             } else if (cur.jn == 1 && jt0 == J_FREE) {
-                const double *qp = qb + (cur.w7 >> 8);
-                pos = V3{qp[0], qp[1], qp[2]};
-                quat = quat_normalize(Q4{qp[3], qp[4], qp[5], qp[6]});
+                fk_free_step(qb + (cur.w7 >> 8), pos, quat);
             } else if (jt0 == J_GLUE) {     // the carried body of a glued scene: the jointless step, local pose out of the state's free-joint slots
-                const double *qp = qb + (cur.w7 >> 8);
-                pos = add3(pos, mat_vec(mat, ld3(qp)));
-                quat = quat_normalize(quat_mul(quat, Q4{qp[3], qp[4], qp[5], qp[6]}));
+                fk_glue_step(pos, quat, mat, qb + (cur.w7 >> 8), pos, quat);
+                quat = quat_normalize(quat);
             } else {
                 const double *bd = D + h.o_mbd + 16 * body;
                 pos = add3(pos, mat_vec(mat, cur.bp));
@@ -313,17 +307,10 @@ MOPA_D void ms_fk(const SceneHdr &h, const double *D, const int *I, const double
             quat2mat(mat, quat);
         }
     }
-    double *rec = grec + l * kGeomStride;
-    const double *gd = D + h.o_mgd + 8 * l;               // lpos[3] lquat[4] rbound of moving geom l
-    const V3 gp = add3(pos, mat_vec(mat, ld3(gd)));
-    const Q4 gq = quat_mul(quat, Q4{gd[3], gd[4], gd[5], gd[6]});
-    double gm[9];
-    quat2mat(gm, gq);
-    st3(rec + GO_POS, gp);
-#pragma unroll
-    for (int i = 0; i < 9; i++) rec[GO_MAT + i] = gm[i];
-    const double *srec = D + h.o_g_rec + I[h.o_mg_geom + l] * kGeomStride;
-    rec[GO_SIZE] = srec[GO_SIZE]; rec[GO_SIZE + 1] = srec[GO_SIZE + 1]; rec[GO_SIZE + 2] = srec[GO_SIZE + 2];
+    V3 gp;
+    Q4 gq;
+    fk_geom_pose(pos, quat, mat, D + h.o_mgd + 8 * l, gp, gq);       // lpos[3] lquat[4] rbound of moving geom l
+    fk_geom_rec_st(grec + l * kGeomStride, gp, gq, D + h.o_g_rec + I[h.o_mg_geom + l] * kGeomStride);
 }
 
 // bit s of the result = state s (active coordinates m.qs[s]) is valid.  K3 inlines this body at its ONE call site (the

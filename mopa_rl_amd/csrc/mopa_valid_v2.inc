@@ -195,22 +195,15 @@ __global__ __launch_bounds__(kBlock) void k_is_valid_v2(SceneHdr h, const double
             const bool jp00 = (bi.jt_qsrc & 0x80) != 0;   // joint anchor at the body origin (wave-uniform => scalar branch)
             if (bi.jn == 1 && jt0 == J_FREE) {
                 const double *qp = env_row + GI[h.o_pq_adr + (qsrc0 - h.na)];   // free joints are never planned over
-                pos = V3{qp[0], qp[1], qp[2]};
-                quat = quat_normalize(Q4{qp[3], qp[4], qp[5], qp[6]});
+                fk_free_step(qp, pos, quat);
             } else {
                 V3 ppos;
                 Q4 pquat;
                 if (bi.load == -2) {            // parent is a static frame
-                    ppos = ld3(s_dbl + h.o_sf_pos + 3 * bi.sf);
-                    const double *sq = s_dbl + h.o_sf_quat + 4 * bi.sf;
-                    pquat = Q4{sq[0], sq[1], sq[2], sq[3]};
-                    const double *sm = s_dbl + h.o_sf_mat + 9 * bi.sf;
-#pragma unroll
-                    for (int i = 0; i < 9; i++) mat[i] = sm[i];
+                    sf_frame_ld(h, s_dbl, bi.sf, ppos, pquat, mat);
                 } else if (bi.load >= 0) {      // parent pose was parked when the DFS left its subtree
                     const double *sp = slab + (size_t)(h.nmg + bi.load) * kSlabStride;
-                    ppos = V3{sp[0], sp[64], sp[128]};
-                    pquat = Q4{sp[192], sp[256], sp[320], sp[384]};
+                    pose7_ld<64>(sp, ppos, pquat);
                     quat2mat(mat, pquat);
                 } else {                        // parent is the previous body
                     ppos = pos;
@@ -218,8 +211,7 @@ __global__ __launch_bounds__(kBlock) void k_is_valid_v2(SceneHdr h, const double
                 }
                 if (jt0 == J_GLUE) {            // the carried body of a glued scene: local pose out of the env row's free-joint slots
                     const double *qp = env_row + GI[h.o_pq_adr + (qsrc0 - h.na)];
-                    pos = add3(ppos, mat_vec(mat, ld3(qp)));
-                    quat = quat_mul(pquat, Q4{qp[3], qp[4], qp[5], qp[6]});
+                    fk_glue_step(ppos, pquat, mat, qp, pos, quat);
                 } else {
                     V3 vv = mat_vec(mat, ld3(bd));
                     pos = add3(ppos, vv);
@@ -254,8 +246,7 @@ __global__ __launch_bounds__(kBlock) void k_is_valid_v2(SceneHdr h, const double
             V2_ACC(0);
             if (bi.save >= 0) {
                 double *sp = slab + (size_t)(h.nmg + bi.save) * kSlabStride;
-                sp[0] = pos.x; sp[64] = pos.y; sp[128] = pos.z;
-                sp[192] = quat.w; sp[256] = quat.x; sp[320] = quat.y; sp[384] = quat.z;
+                pose7_st<64>(sp, pos, quat);
             }
             // ---------- moving geoms of this body ----------
             for (int m = bi.mgadr; m < bi.mgadr + bi.mgnum; m++) {
@@ -266,8 +257,7 @@ __global__ __launch_bounds__(kBlock) void k_is_valid_v2(SceneHdr h, const double
                 const Q4 gq = quat_mul(quat, Q4{gd[3], gd[4], gd[5], gd[6]});
                 if (gi.store & 1) {
                     double *sp = slab + (size_t)m * kSlabStride;
-                    sp[0] = gp.x; sp[64] = gp.y; sp[128] = gp.z;
-                    sp[192] = gq.w; sp[256] = gq.x; sp[320] = gq.y; sp[384] = gq.z;
+                    pose7_st<64>(sp, gp, gq);
                 }
                 const double rbg = gd[7];
                 V2_ACC(1);

@@ -109,9 +109,7 @@ MOPA_HD void k1_fk_body(K1FkRegs<TR> &r, const double *qact, const double *sn, c
     constexpr const unsigned long long *bd = TR::fk_bd[B];   // pos[3] quat[4] axis[3] jpos[3] ref
     static_assert(jn <= 1 && sizeof...(G) == bi[4], "baked walk: one joint per body at most");
     if constexpr (jn == 1 && jt == J_FREE) {
-        const double *qp = pv + (src - TR::na);
-        r.pos = V3{qp[0], qp[1], qp[2]};
-        r.quat = quat_normalize(Q4{qp[3], qp[4], qp[5], qp[6]});
+        fk_free_step(pv + (src - TR::na), r.pos, r.quat);
     } else {
         V3 ppos;
         Q4 pquat;
@@ -169,8 +167,7 @@ struct V5FkSink {
     float *cen;     // this lane's place in the centre table
     MOPA_D void operator()(int m, V3 gp, Q4 gq) {
         double *sp = slab + (size_t)m * kSlabStride;
-        sp[0] = gp.x; sp[64] = gp.y; sp[128] = gp.z;
-        sp[192] = gq.w; sp[256] = gq.x; sp[320] = gq.y; sp[384] = gq.z;
+        pose7_st<64>(sp, gp, gq);
         float *cp = cen + (size_t)m * 3 * 64;
         cp[0] = (float)gp.x; cp[64] = (float)gp.y; cp[128] = (float)gp.z;
     }
@@ -481,24 +478,17 @@ __global__ __launch_bounds__(kBlock, TR::kBaked ? 2 : 1) void k_is_valid_v5(Scen
                         Q4 quat;
                         if (bi.jn == 1 && jt0 == J_FREE) {
                             const double *qp = env_row + s_int[h.o_pq_adr + (qsrc0 - h.na)];
-                            pos = V3{qp[0], qp[1], qp[2]};
-                            quat = quat_normalize(Q4{qp[3], qp[4], qp[5], qp[6]});
+                            fk_free_step(qp, pos, quat);
                         } else {
                             V3 ppos;
                             Q4 pquat;
                             double mat[9];
                             const int par = s_int[h.o_mb_parent + b];
                             if (par < 0) {
-                                ppos = ld3(s_dbl + h.o_sf_pos + 3 * bi.sf);
-                                const double *sq = s_dbl + h.o_sf_quat + 4 * bi.sf;
-                                pquat = Q4{sq[0], sq[1], sq[2], sq[3]};
-                                const double *sm = s_dbl + h.o_sf_mat + 9 * bi.sf;
-#pragma unroll
-                                for (int k = 0; k < 9; k++) mat[k] = sm[k];
+                                sf_frame_ld(h, s_dbl, bi.sf, ppos, pquat, mat);
                             } else {
                                 const double *pp = ps + 7 * (s_int[h.o_mb_pas + par] & 0xffff);
-                                ppos = V3{pp[0], pp[1], pp[2]};
-                                pquat = Q4{pp[3], pp[4], pp[5], pp[6]};
+                                pose7_ld<1>(pp, ppos, pquat);
                                 quat2mat(mat, pquat);
                             }
                             pos = add3(ppos, mat_vec(mat, ld3(bd)));
@@ -521,7 +511,7 @@ __global__ __launch_bounds__(kBlock, TR::kBaked ? 2 : 1) void k_is_valid_v5(Scen
                             quat = quat_normalize(quat);
                         }
                         double *pp = ps + 7 * i;
-                        pp[0] = pos.x; pp[1] = pos.y; pp[2] = pos.z; pp[3] = quat.w; pp[4] = quat.x; pp[5] = quat.y; pp[6] = quat.z;
+                        pose7_st<1>(pp, pos, quat);
                     }
                     wave_sync();
                 }
@@ -535,7 +525,7 @@ __global__ __launch_bounds__(kBlock, TR::kBaked ? 2 : 1) void k_is_valid_v5(Scen
                     const V3 gp = add3(V3{pp[0], pp[1], pp[2]}, mat_vec(mat, ld3(gd)));
                     const Q4 gq = quat_mul(bq, Q4{gd[3], gd[4], gd[5], gd[6]});
                     double *gpp = ps + 7 * (h.n_pas_b + lane);
-                    gpp[0] = gp.x; gpp[1] = gp.y; gpp[2] = gp.z; gpp[3] = gq.w; gpp[4] = gq.x; gpp[5] = gq.y; gpp[6] = gq.z;
+                    pose7_st<1>(gpp, gp, gq);
                 }
                 wave_sync();
             }
@@ -559,23 +549,18 @@ __global__ __launch_bounds__(kBlock, TR::kBaked ? 2 : 1) void k_is_valid_v5(Scen
                     const int pw = GI[h.o_mb_pas + b];
                     if (pw >= 0) {          // posed by the tile: the pose, its save slot, its geoms -- copied, not computed
                         const double *pp = ps + 7 * (pw & 0xffff);
-                        pos = V3{pp[0], pp[1], pp[2]};
-                        quat = Q4{pp[3], pp[4], pp[5], pp[6]};
+                        pose7_ld<1>(pp, pos, quat);
                         if (!(pw & (1 << 16))) {
                             quat2mat(mat, quat);
                             if (bi.save >= 0) {
                                 double *sp = slab + (size_t)(h.nmg + bi.save) * kSlabStride;
-                                sp[0] = pos.x; sp[64] = pos.y; sp[128] = pos.z;
-                                sp[192] = quat.w; sp[256] = quat.x; sp[320] = quat.y; sp[384] = quat.z;
+                                pose7_st<64>(sp, pos, quat);
                             }
                         }
                         for (int m = bi.mgadr; m < bi.mgadr + bi.mgnum; m++) {
                             const double *gp = ps + 7 * (h.n_pas_b + GI[h.o_mg_pas + m]);
-                            if (lane == 0) {        // one pose for the tile (v5_flush reads lane 0's place for these geoms)
-                                double *sp = slab + (size_t)m * kSlabStride;
-                                sp[0] = gp[0]; sp[64] = gp[1]; sp[128] = gp[2];
-                                sp[192] = gp[3]; sp[256] = gp[4]; sp[320] = gp[5]; sp[384] = gp[6];
-                            }
+                            // one pose for the tile (v5_flush reads lane 0's place for these geoms)
+                            if (lane == 0) pose7_st<64>(slab + (size_t)m * kSlabStride, ld3(gp), Q4{gp[3], gp[4], gp[5], gp[6]});
                             float *cp = CEN_LDS ? q.cen + (size_t)m * 3 * 64 + lane : gcen + (size_t)m * 3 * 64;
                             cp[0] = (float)gp[0]; cp[64] = (float)gp[1]; cp[128] = (float)gp[2];
                         }
@@ -584,22 +569,15 @@ __global__ __launch_bounds__(kBlock, TR::kBaked ? 2 : 1) void k_is_valid_v5(Scen
                 }
                 if (bi.jn == 1 && jt0 == J_FREE) {
                     const double *qp = env_row + GI[h.o_pq_adr + (qsrc0 - h.na)];
-                    pos = V3{qp[0], qp[1], qp[2]};
-                    quat = quat_normalize(Q4{qp[3], qp[4], qp[5], qp[6]});
+                    fk_free_step(qp, pos, quat);
                 } else {
                     V3 ppos;
                     Q4 pquat;
                     if (bi.load == -2) {
-                        ppos = ld3(s_dbl + h.o_sf_pos + 3 * bi.sf);
-                        const double *sq = s_dbl + h.o_sf_quat + 4 * bi.sf;
-                        pquat = Q4{sq[0], sq[1], sq[2], sq[3]};
-                        const double *sm = s_dbl + h.o_sf_mat + 9 * bi.sf;
-#pragma unroll
-                        for (int i = 0; i < 9; i++) mat[i] = sm[i];
+                        sf_frame_ld(h, s_dbl, bi.sf, ppos, pquat, mat);
                     } else if (bi.load >= 0) {
                         const double *sp = slab + (size_t)(h.nmg + bi.load) * kSlabStride;
-                        ppos = V3{sp[0], sp[64], sp[128]};
-                        pquat = Q4{sp[192], sp[256], sp[320], sp[384]};
+                        pose7_ld<64>(sp, ppos, pquat);
                         quat2mat(mat, pquat);
                     } else {
                         ppos = pos;
@@ -607,8 +585,7 @@ __global__ __launch_bounds__(kBlock, TR::kBaked ? 2 : 1) void k_is_valid_v5(Scen
                     }
                     if (jt0 == J_GLUE) {        // the carried body of a glued scene: local pose out of the env row's free-joint slots
                         const double *qp = env_row + GI[h.o_pq_adr + (qsrc0 - h.na)];
-                        pos = add3(ppos, mat_vec(mat, ld3(qp)));
-                        quat = quat_mul(pquat, Q4{qp[3], qp[4], qp[5], qp[6]});
+                        fk_glue_step(ppos, pquat, mat, qp, pos, quat);
                     } else {
                         pos = add3(ppos, mat_vec(mat, ld3(bd)));
                         quat = quat_mul(pquat, Q4{bd[3], bd[4], bd[5], bd[6]});
@@ -644,16 +621,14 @@ __global__ __launch_bounds__(kBlock, TR::kBaked ? 2 : 1) void k_is_valid_v5(Scen
                 quat2mat(mat, quat);
                 if (bi.save >= 0) {
                     double *sp = slab + (size_t)(h.nmg + bi.save) * kSlabStride;
-                    sp[0] = pos.x; sp[64] = pos.y; sp[128] = pos.z;
-                    sp[192] = quat.w; sp[256] = quat.x; sp[320] = quat.y; sp[384] = quat.z;
+                    pose7_st<64>(sp, pos, quat);
                 }
                 for (int m = bi.mgadr; m < bi.mgadr + bi.mgnum; m++) {
                     const double *gd = s_dbl + h.o_mgd + 8 * m;   // lpos[3] lquat[4] rbound
                     const V3 gp = add3(pos, mat_vec(mat, ld3(gd)));
                     const Q4 gq = quat_mul(quat, Q4{gd[3], gd[4], gd[5], gd[6]});
                     double *sp = slab + (size_t)m * kSlabStride;
-                    sp[0] = gp.x; sp[64] = gp.y; sp[128] = gp.z;
-                    sp[192] = gq.w; sp[256] = gq.x; sp[320] = gq.y; sp[384] = gq.z;
+                    pose7_st<64>(sp, gp, gq);
                     float *cp = CEN_LDS ? q.cen + (size_t)m * 3 * 64 + lane : gcen + (size_t)m * 3 * 64;
                     cp[0] = (float)gp.x; cp[64] = (float)gp.y; cp[128] = (float)gp.z;
                 }
