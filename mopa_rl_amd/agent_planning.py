@@ -8,6 +8,7 @@ A10-A11), for E environments at once on torch tensors:
     JointLimits.clip_target    rl/mopa_rollouts.py:119-131  a planner target is clipped onto the limits
     simple_interpolate_batch   rl/sac_agent.py:262-318      straight line in steps <= 0.8 ac_scale, every step validated
     handle_invalid_target_batch rl/mopa_rollouts.py:133-143 invalid target walked back toward the current state
+    wrap_unlimited / seam_steps_np motion_planners/sampling_based_planner.py:51-55,79-97  unlimited joints across the +-3.14 seam
 
 The reference keeps these as per-environment numpy methods on its SAC/TD3 agents; its agents keep using their own.  The
 forms here exist for the batched rollout (rollout.py): one validity launch covers all environments, every arithmetic
@@ -103,6 +104,41 @@ class JointLimits:
         lo, hi, lo_s, hi_s = self._np
         beyond = ((q < lo) | (q > hi)).any(axis=-1, keepdims=True)
         return np.where(beyond, np.minimum(np.maximum(q, lo_s), hi_s), q)
+
+
+def wrap_unlimited(q, idx):
+    """`SamplingBasedPlanner.convert_nonlimited` (motion_planners/sampling_based_planner.py:51-55) for rows of states [M, nq]
+    (torch): `util.env.joint_convert` (util/env.py:15-25) on the columns `idx` of the unlimited joints -- Python's float // and %
+    spelled out (fmod; the quotient rounded to the nearest integer).  Returns a copy (or `q` itself when `idx` is empty); the
+    caller's un-wrapped state, from which the trajectory is rebuilt, is left alone."""
+    if not len(idx):
+        return q
+    torch = _torch()
+    q = q.clone()
+    for j in idx:
+        a = q[:, j]
+        m = torch.fmod(a, 3.14)                                           # a % 3.14 for a > 0, a % -3.14 for a <= 0 (sign of a either way)
+        k = torch.round((a - m) / torch.where(a > 0, a.new_tensor(3.14), a.new_tensor(-3.14)))       # a // +-3.14 (the divisor in a's float64)
+        odd = torch.remainder(k, 2.0) != 0
+        r = torch.where(odd, torch.where(a > 0, m - 3.14, m + 3.14), m)
+        q[:, j] = torch.where(a == 0, torch.full_like(a, -0.0), r)        # (0.0 % -3.14 is -0.0 in Python)
+    return q
+
+
+def seam_steps_np(P, idx):
+    """successive differences P[..., k+1, :] - P[..., k, :] of planner rows (numpy) with the seam rule of the reference's un-wrap
+    loop on the unlimited joints' columns `idx` (sampling_based_planner.py:79-97; same sums, same order)"""
+    prev, cur = P[..., :-1, :], P[..., 1:, :]
+    step = cur - prev
+    for j in idx:
+        p, c = prev[..., j], cur[..., j]
+        jump = np.abs(c - p) > 3.14
+        up = jump & (p > 0) & (c <= 0)
+        down = jump & ~up & (p < 0) & (c > 0)
+        sj = step[..., j]
+        sj[up] = ((3.14 - p[up]) + c[up]) + 3.14
+        sj[down] = -(((3.14 - c[down]) + p[down]) + 3.14)
+    return step
 
 
 def interpolation_steps(diff, ac_scale: float, ac_low: float = -1.0, ac_high: float = 1.0):

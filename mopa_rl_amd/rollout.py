@@ -38,8 +38,9 @@ import numpy as np
 
 from . import _lib
 from .agent_planning import (JointLimits, action_to_displacement, displacement_to_action, interpolation_steps, max_interpolation_steps,
-                             is_planner_action, simple_interpolate_batch)
+                             is_planner_action, seam_steps_np, simple_interpolate_batch, wrap_unlimited)
 from .batch import BatchPlanner, _torch
+from .plan_jobs import PlanJob, PlannerJobs, merge_paths
 from .planner import ITERS_PER_SECOND
 from .kinematic_env import KIND_PUSHER
 from .scene import ENV_SPECS, planner_inputs
@@ -361,42 +362,6 @@ def _side_streams(dev, n):
     return pool[:n]
 
 
-def wrap_unlimited(q, idx):
-    """`SamplingBasedPlanner.convert_nonlimited` (motion_planners/sampling_based_planner.py:51-55) for rows of states [M, nq]
-    (torch): `util.env.joint_convert` (util/env.py:15-25) on the columns `idx` of the unlimited joints -- Python's float // and %
-    spelled out (fmod; the quotient rounded to the nearest integer).  Returns a copy (or `q` itself when `idx` is empty); the
-    caller's un-wrapped state, from which the trajectory is rebuilt, is left alone."""
-    if not len(idx):
-        return q
-    torch = _torch()
-    q = q.clone()
-    for j in idx:
-        a = q[:, j]
-        m = torch.fmod(a, 3.14)                                           # a % 3.14 for a > 0, a % -3.14 for a <= 0 (sign of a either way)
-        k = torch.round((a - m) / torch.where(a > 0, a.new_tensor(3.14), a.new_tensor(-3.14)))       # a // +-3.14 (the divisor in a's float64)
-        odd = torch.remainder(k, 2.0) != 0
-        r = torch.where(odd, torch.where(a > 0, m - 3.14, m + 3.14), m)
-        q[:, j] = torch.where(a == 0, torch.full_like(a, -0.0), r)        # (0.0 % -3.14 is -0.0 in Python)
-    return q
-
-
-def seam_steps_np(P, idx):
-    """successive differences P[..., k+1, :] - P[..., k, :] of planner rows (numpy) with the seam rule of the reference's un-wrap
-    loop on the unlimited joints' columns `idx` (sampling_based_planner.py:79-97; same sums, same order)"""
-    prev, cur = P[..., :-1, :], P[..., 1:, :]
-    step = cur - prev
-    for j in idx:
-        p, c = prev[..., j], cur[..., j]
-        jump = np.abs(c - p) > 3.14
-        up = jump & (p > 0) & (c <= 0)
-        down = jump & ~up & (p < 0) & (c > 0)
-        sj = step[..., j]
-        sj[up] = ((3.14 - p[up]) + c[up]) + 3.14
-        sj[down] = -(((3.14 - c[down]) + p[down]) + 3.14)
-    return step
-
-
-
 def ik_targets_torch(site_pos, site_mat, ac, action_range, world_lo, world_hi):
     """The IK problem of `ik_displacement` as array operations (what `BatchIK.targets` computes in one launch): returns (target_cart, target_quat)."""
     torch = _torch()
@@ -463,7 +428,7 @@ class BatchMoPARollout:
         pi = planner_inputs(env.env_name, env.model)
         # unlimited joints (`non_limited_idx`, rl/trainer.py:80-82; Pusher: joint0): SamplingBasedPlanner wraps a query's start and
         # goal into (-3.14, 3.14) there before planning and takes the returned steps across the seam the short way round
-        # (motion_planners/sampling_based_planner.py:51-55,60-99) -- `_wrap_q` / the seam mask of the path post-processing
+        # (motion_planners/sampling_based_planner.py:51-55,60-99) -- `wrap_unlimited` / the seam mask of the path post-processing
         self._seam_idx = [int(i) for i in pi.non_limited_idx]
         self._seam_mask = sum(1 << i for i in self._seam_idx)
         self.pi = pi
@@ -471,7 +436,7 @@ class BatchMoPARollout:
         mk = lambda r: _lib.Scene(pi.model, pi.passive_joint_idx, pi.ignored_contacts, self.cfg.contact_threshold, range_=r,
                                   seed=self.cfg.seed, device=dev_index)
         self.scene, self.simple_scene = mk(self.cfg.range), mk(self.cfg.simple_planner_range)
-        self.bp, self._bp_simple = BatchPlanner(self.scene), BatchPlanner(self.simple_scene)
+        self.bp, bp_simple = BatchPlanner(self.scene), BatchPlanner(self.simple_scene)
         self.E, self.nq, self.n = env.E, env.nq, env.n_arm
         self.arm = list(int(i) for i in env.facts.arm_qpos_idx)
         assert self.arm == list(range(self.n)), "the reference slices qpos[:n] (rl/sac_agent.py:275-278)"
@@ -483,7 +448,9 @@ class BatchMoPARollout:
         self._t = 0
         self._t_dev = torch.zeros((), dtype=torch.int64, device=dev)         # the same counter on the device (captured launches read it)
         self.busy = torch.zeros(self.E, dtype=torch.bool, device=dev)        # env waits for an RRT-Connect query (async_planner)
-        self._jobs = []
+        self._jobs = []          # PlanJobs in flight (plan_jobs.py)
+        # created on first use: profiling dict (set from outside) + its last mark, HIP graphs, fused step struct, walk_chunk state, pool counts
+        self.timing = self._mark_t = self._graphs = self._fs = self._walk = self._count_ring = self._count_free = self._pool_counts = None
         # blocked envs waiting for the next RRT-Connect launch: mask + their (clipped) current state and target
         self._pool_mask = torch.zeros(self.E, dtype=torch.bool, device=dev)
         self._res = None      # per-env parking buffers of planner state between a first-phase launch and its retry (_park_state)
@@ -503,6 +470,8 @@ class BatchMoPARollout:
         self._next_stream = 0
         self.main_iters = max(1, int(round(self.cfg.timelimit * ITERS_PER_SECOND)))
         self.simple_iters = max(1, int(round(self.cfg.simple_planner_timelimit * ITERS_PER_SECOND)))
+        self.jobs = PlannerJobs(self.cfg, self.bp, bp_simple, self.limits, self._valid, self.n, self.nq, self._seam_idx, self._seam_mask, self.E,
+                                self.main_iters, self.simple_iters, dev)
         self.ik = None
         if self.cfg.use_ik_target:
             from .ik import BatchIK
@@ -573,386 +542,9 @@ class BatchMoPARollout:
         self._t_dev.fill_(int(value))
         self.t_env.fill_(int(value))
 
-    def _wrap_q(self, q):
-        return wrap_unlimited(q, self._seam_idx)
-
-    def _seam_steps_np(self, P):
-        return seam_steps_np(P, self._seam_idx)
-
-    def _rrt_launch(self, cur_f, target_f, ids, stream=None, iters=None, keep=False, resume=None, chain=False, steps=None, seeds=None):
-        """RRT-Connect (K3) for the envs `ids` whose straight line is blocked (:205-209): asynchronous, optionally on a side
-        stream.  The sample stream of a query is keyed by (cfg.seed + the env's own step count, env id), so an env's plans do
-        not depend on which other envs are planned with it or when."""
-        torch = _torch()
-        cfg = self.cfg
-        if seeds is None:
-            seeds = (self.t_env[ids] + cfg.seed).contiguous()
-        gids = (ids + int(cfg.env_id_base)).contiguous() if cfg.env_id_base else ids       # the planner's stream id: the GLOBAL env id
-        iters = self.main_iters if iters is None else int(iters)
-        smooth = {"path_smooth": True} if cfg.path_smooth else {}       # (flag off: the launches get the keywords they always got)
-        job = {"ids": ids, "cur": cur_f, "target": target_f, "steps": self.t_env[ids].clone() if steps is None else steps, "event": None, "stage": "rrt", "stream": stream,
-               "iters": iters}
-        if self._seam_idx:       # the planner sees the wrapped endpoints; job["cur"] stays the caller's state
-            cur_f, target_f = self._wrap_q(cur_f).contiguous(), self._wrap_q(target_f).contiguous()
-        if stream is None:
-            job["path"], job["plen"], job["status"], _ = self.bp.plan(cur_f, target_f, max_iters=iters, max_nodes=cfg.max_nodes,
-                                                                      max_path=cfg.max_path, seed=cfg.seed, env_ids=gids, seeds=seeds,
-                                                                      vertex_simplify=cfg.vertex_simplify, path_shortcut=cfg.path_shortcut,
-                                                                      **smooth)
-        else:
-            stream.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(stream):
-                res = self.bp.plan(cur_f, target_f, max_iters=iters, max_nodes=cfg.max_nodes, max_path=cfg.max_path, seed=cfg.seed,
-                                   env_ids=gids, seeds=seeds, stream=stream, max_workgroups=cfg.planner_workgroups,
-                                   keep_state=keep, resume=resume, vertex_simplify=cfg.vertex_simplify, path_shortcut=cfg.path_shortcut, **smooth,
-                                   exclusive=cfg.planner_exclusive >= 2 or (cfg.planner_exclusive == 1 and (resume is not None or not keep) and iters == self.main_iters))
-                job["path"], job["plen"], job["status"] = res[0], res[1], res[2]
-                if keep:
-                    job["pstate"] = res[4]      # trees + counters of the queries this budget leaves unsolved (see _seg_plan)
-                if chain:
-                    # the quick queries' results are complete HERE; what follows on this stream is the continuation of the rest
-                    job["event"] = torch.cuda.Event()
-                    job["event"].record(stream)
-                    rb = self.bp.plan(cur_f, target_f, max_iters=self.main_iters, max_nodes=cfg.max_nodes, max_path=cfg.max_path,
-                                      seed=cfg.seed, env_ids=gids, seeds=seeds, stream=stream,
-                                      max_workgroups=cfg.planner_chain_workgroups or cfg.planner_workgroups,
-                                      resume=res[4], exclusive=cfg.planner_exclusive >= 1, vertex_simplify=cfg.vertex_simplify, path_shortcut=cfg.path_shortcut, **smooth)
-                    ev_b = torch.cuda.Event()
-                    ev_b.record(stream)
-                    job["chain"] = {"path": rb[0], "plen": rb[1], "status": rb[2], "event": ev_b}
-                    job["post_on_main"] = True      # this stream is busy with the continuation: post-process on the caller's
-                    for t in (cur_f, target_f, ids, gids, seeds):
-                        t.record_stream(stream)
-                    return job
-                for t in (cur_f, target_f, ids, gids, seeds):
-                    t.record_stream(stream)
-                job["event"] = torch.cuda.Event()
-                job["event"].record(stream)
-        return job
-
-    def _rrt_advance(self, job, wait: bool):
-        """Drive a planner job through its stages; returns True when it is finished (job["result"] = (trajs: row -> [L, nq]
-        numpy for the successful rows; success, valid, exact as numpy bool arrays over the job's rows)).
-          stage "rrt"     results of the main RRT-Connect launch: sentinel decoding, the un-wrapped trajectory of
-                          `SamplingBasedPlanner.plan` / `PlannerAgent.plan`, densification (rl/sac_agent.py:216-233): a path
-                          segment longer than ac_scale in some joint is cut by the straight-line rule from its clipped start; all
-                          interior states of all segments are validated in ONE launch
-          stage "simple"  the (rare) segments with an invalid interior state: simple planner, one batched launch (:300-303)
-          stage "main"    those it could not connect: main planner, one batched launch (:304-306); else the segment stays [end]
-        With `wait` every stage is waited for (lock-step); otherwise a stage whose launch has not finished returns False."""
-        torch = _torch()
-        cfg, n = self.cfg, self.n
-        if job["stage"] == "split":
-            return self._rrt_join(job, wait)
-        if job["stage"] in ("rrt", "device") and cfg.device_paths and self.nq <= 64 and "bucketed" not in job and "unwrapped" not in job:
-            return self._rrt_device(job, wait)
-        while True:
-            if job["event"] is not None:
-                if wait:
-                    job["event"].synchronize()
-                elif not job["event"].query():
-                    return False
-            plen_h, st_h = job["plen"].cpu().numpy(), job["status"].cpu().numpy()
-            if job["stage"] == "rrt" and len(plen_h) > 64 and "bucketed" not in job:
-                return self._rrt_split(job, plen_h, wait)
-            path_h = job["path"][:, :max(1, int(plen_h.max()))].cpu().numpy()      # the [max_path] tail of every row is unused
-            path_h[np.arange(path_h.shape[1])[None, :] >= plen_h[:, None]] = 0.0   # ... and holds whatever the allocator left
-            if job["stage"] == "rrt":
-                cur_h = job["cur"].cpu().numpy()
-                job["ids_h"], job["steps_h"] = job["ids"].cpu().numpy(), job["steps"].cpu().numpy()
-                M = len(job["ids_h"])
-                bad = st_h != 0        # sentinel rows (sampling_based_planner.py:64-69): -5 goal invalid, -4 no exact solution
-                valid, exact = np.ones(M, dtype=bool), np.ones(M, dtype=bool)
-                valid[bad] = st_h[bad] != _lib.PLAN_INVALID_GOAL
-                exact[bad] = st_h[bad] != _lib.PLAN_NO_EXACT
-                good = np.where(~bad)[0]
-                job.update(flags=(~bad, valid, exact), good=good, replacement={}, fb=[], seg_r=np.zeros(0, dtype=np.int64),
-                           seg_i=np.zeros(0, dtype=np.int64), T=None, nrow=np.zeros(0, dtype=np.int64))
-                if len(good):
-                    # SamplingBasedPlanner.plan rebuilds the trajectory from successive differences (:71-99) and PlannerAgent
-                    # drops row 0: tr[k] = tr[k-1] + (states[k] - states[k-1]), tr[0] = cur.  np.add.accumulate is that same
-                    # strictly sequential sum, for all paths at once (rows past a path's length hold garbage and are cut off).
-                    P = path_h[good]
-                    if job.get("unwrapped"):       # rows that went through mopa_paths_unwrap_batch already (row 0 = cur)
-                        T = P
-                    else:
-                        A = np.concatenate([cur_h[good][:, None, :], self._seam_steps_np(P)], axis=1)
-                        T = np.add.accumulate(A, axis=1)
-                    nrow = plen_h[good] - 1
-                    job["T"], job["nrow"] = T, nrow
-                    if cfg.interpolation and T.shape[1] > 1:
-                        step = T[:, 1:, :n] - T[:, :-1, :n]                      # waypoint i minus its predecessor (cur for i = 0)
-                        far = ((step < -cfg.ac_scale) | (step > cfg.ac_scale)).any(axis=2)
-                        far &= np.arange(far.shape[1])[None, :] < nrow[:, None]
-                        job["seg_r"], job["seg_i"] = np.nonzero(far)             # segment k: waypoint seg_i[k] of path seg_r[k]
-                if len(job["seg_r"]):
-                    self._densify_cut(job)
-                if not job["fb"]:
-                    return self._rrt_done(job)
-                self._fallback_launch(job, "simple")
-                continue
-            # a fallback stage came back: rows = job["fb"] (indices into seg_jobs)
-            left = []
-            for r, k in enumerate(job["fb"]):
-                if st_h[r] == 0:
-                    p = path_h[r, :plen_h[r]]
-                    # SamplingBasedPlanner.plan: start + running sum of successive differences; PlannerAgent drops row 0
-                    job["replacement"][k] = np.add.accumulate(np.vstack([job["starts"][k][None], self._seam_steps_np(p)]), axis=0)[1:]
-                elif job["stage"] == "simple":
-                    left.append(k)
-                else:
-                    job["replacement"][k] = job["ends"][k][None]
-            job["fb"] = left
-            if not left:
-                return self._rrt_done(job)
-            self._fallback_launch(job, "main")
-
-    def _rrt_device(self, job, wait: bool):
-        """Stage "rrt" with the path post-processing on the device (batch.postprocess_paths: three small launches around one
-        validity launch on the job's stream; one read-back of two totals).  Queries whose densification met an invalid
-        interior state -- they need the fallback planners -- go through the host form as a sub-job, from their un-wrapped
-        rows.  job["result"] then holds device tensors."""
-        import contextlib
-        torch = _torch()
-        cfg = self.cfg
-        just_enqueued = False
-        if job["stage"] == "rrt":
-            if job["event"] is not None:
-                if wait:
-                    job["event"].synchronize()
-                elif not job["event"].query():
-                    return False
-            just_enqueued = True
-            if "lazy" in job:        # continuation half of a chained launch: its rows of the continuation's outputs
-                src, rows = job.pop("lazy")
-                if job["stream"] is not None and job.get("built") is not None:
-                    job["stream"].wait_event(job.pop("built"))
-                with (torch.cuda.stream(job["stream"]) if job["stream"] is not None else contextlib.nullcontext()):
-                    job["path"], job["plen"], job["status"] = src["path"][rows], src["plen"][rows], src["status"][rows]
-            pstream = None if job.get("post_on_main") else job["stream"]
-            if job.get("post_on_main"):
-                for x in (job["path"], job["plen"], job["status"], job["cur"]):
-                    x.record_stream(torch.cuda.current_stream())
-            ctx = torch.cuda.stream(pstream) if pstream is not None else contextlib.nullcontext()
-            with ctx:
-                from .batch import postprocess_paths
-                out, ln, need = postprocess_paths(job["path"], job["plen"], job["status"], job["cur"], self.n, cfg.ac_scale,
-                                                  cfg.interpolation, self.limits, self._valid, stream=pstream, seam_mask=self._seam_mask)
-                st = job["status"]
-                ok = st == 0           # sentinel rows (sampling_based_planner.py:64-69): -5 goal invalid, -4 no exact solution
-                job["dev"] = [out, ln, ok, st != _lib.PLAN_INVALID_GOAL, st != _lib.PLAN_NO_EXACT]
-                rows = torch.nonzero(need).flatten()
-                if len(rows):
-                    sub = {k: job[k][rows].contiguous() for k in ("ids", "cur", "target", "steps", "plen", "status")}
-                    sub.update(path=job["path"][rows].contiguous(), event=None, stage="rrt", stream=pstream, unwrapped=True)
-                    job["sub"], job["sub_rows"] = sub, rows
-                if pstream is not None:
-                    job["event"] = torch.cuda.Event()
-                    job["event"].record(pstream)
-                else:
-                    job["event"] = None
-            job["stage"] = "device"
-        # stage "device": the launches above (and the sub-job, if any) have to be finished.  Right after the post-processing
-        # was enqueued what is left of it is one small assemble launch (its read-backs already waited for the rest): waiting
-        # those microseconds out here saves the job -- and the envs that wait for it -- a whole call
-        if job["event"] is not None:
-            if wait or (just_enqueued and "sub" not in job):
-                job["event"].synchronize()
-            elif not job["event"].query():
-                return False
-        out, ln, ok, v, e = job["dev"]
-        if "sub" in job:
-            if not self._rrt_advance(job["sub"], wait):
-                return False
-            tr_s, ln_s, *_ = job["sub"]["result"]
-            rows = job["sub_rows"]
-            tr_s, ln_s = torch.as_tensor(tr_s, device=out.device), torch.as_tensor(ln_s, device=out.device)
-            if tr_s.shape[1] > out.shape[1]:
-                out = torch.cat([out, torch.zeros(out.shape[0], tr_s.shape[1] - out.shape[1], self.nq, dtype=out.dtype, device=out.device)], dim=1)
-            out[rows, :tr_s.shape[1]] = tr_s
-            ln[rows] = ln_s
-        job["result"] = (out, ln, ok, v, e)
-        return True
-
-    _BUCKETS = (6, 12, 24, 48)
-
-    def _rrt_split(self, job, plen_h, wait):
-        """A finished launch's paths are post-processed as padded [rows, longest path, nq] arrays; a few long paths among many
-        short ones would make that mostly padding.  Split the job's rows by path length into sub-jobs (each padded to its own
-        longest path) and advance those; job["result"] is put together from theirs."""
-        torch = _torch()
-        edges = np.searchsorted(np.array(self._BUCKETS), plen_h, side="left")
-        subs, result_rows = [], []
-        for b in np.unique(edges):
-            rows = np.nonzero(edges == b)[0]
-            rt = torch.as_tensor(rows, device=job["path"].device)
-            L = max(1, int(plen_h[rows].max()))
-            sub = {k: job[k][rt] for k in ("ids", "cur", "target", "steps", "plen", "status")}
-            sub.update(path=job["path"][rt, :L], event=None, stage="rrt", stream=job["stream"], bucketed=True)
-            if job.get("unwrapped"):
-                sub["unwrapped"] = True
-            subs.append(sub)
-            result_rows.append(rows)
-        job["subs"], job["sub_rows"], job["stage"] = subs, result_rows, "split"
-        return self._rrt_join(job, wait)
-
-    def _rrt_join(self, job, wait):
-        done = True
-        for sub in job["subs"]:
-            if "result" not in sub:
-                done &= bool(self._rrt_advance(sub, wait))
-        if not done:
-            return False
-        M, nq = len(job["plen"]), self.nq
-        L = max(s["result"][0].shape[1] for s in job["subs"])
-        traj, ln = np.zeros((M, L, nq)), np.zeros(M, dtype=np.int64)
-        flags = [np.zeros(M, dtype=bool) for _ in range(3)]
-        for sub, rows in zip(job["subs"], job["sub_rows"]):
-            tr, l, *fl = sub["result"]
-            traj[rows, :tr.shape[1]], ln[rows] = tr, l
-            for f, g in zip(flags, fl):
-                f[rows] = g
-        job["result"] = (traj, ln) + tuple(flags)
-        return True
-
-    def _fallback_launch(self, job, stage):
-        torch = _torch()
-        cfg = self.cfg
-        dev = self.env.device
-        ks = job["fb"]
-        scene_bp, iters, base = ((self._bp_simple, self.simple_iters, 1) if stage == "simple" else (self.bp, self.main_iters, 2))
-        starts = self._wrap_q(torch.tensor(job["starts"][ks], device=dev))
-        ends = self._wrap_q(torch.tensor(job["ends"][ks], device=dev))
-        rows = job["good"][job["seg_r"][ks]]
-        total = int(cfg.env_id_total) if cfg.env_id_total else self.E
-        ids = torch.tensor(total * base + int(cfg.env_id_base) + job["ids_h"][rows], dtype=torch.int64, device=dev)
-        seeds = torch.tensor(cfg.seed + job["steps_h"][rows], dtype=torch.int64, device=dev)
-        stream = job["stream"]
-        job["stage"] = stage
-        simplify = cfg.simple_planner_vertex_simplify if stage == "simple" else cfg.vertex_simplify
-        shortcut = cfg.simple_planner_path_shortcut if stage == "simple" else cfg.path_shortcut
-        smooth = {"path_smooth": True} if (cfg.simple_planner_path_smooth if stage == "simple" else cfg.path_smooth) else {}
-        if stream is None:
-            job["path"], job["plen"], job["status"], _ = scene_bp.plan(starts, ends, max_iters=iters, max_nodes=cfg.max_nodes,
-                                                                       max_path=cfg.max_path, seed=cfg.seed, env_ids=ids, seeds=seeds,
-                                                                       vertex_simplify=simplify, path_shortcut=shortcut, **smooth)
-        else:
-            stream.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(stream):
-                job["path"], job["plen"], job["status"], _ = scene_bp.plan(starts, ends, max_iters=iters, max_nodes=cfg.max_nodes,
-                                                                           max_path=cfg.max_path, seed=cfg.seed, env_ids=ids, seeds=seeds,
-                                                                           stream=stream, max_workgroups=cfg.planner_workgroups,
-                                                                           vertex_simplify=simplify, path_shortcut=shortcut, **smooth)
-                job["keep"] = (starts, ends, ids, seeds)
-                job["event"] = torch.cuda.Event()
-                job["event"].record(stream)
-
-    def _rrt_done(self, job):
-        """assemble the final trajectories: [M, L, nq] padded + lengths (0 for the failed rows).  Waypoint i of path r becomes
-        `pieces[r, i]` rows: itself, or -- densified -- its cut (count interior states + the waypoint), or a fallback path."""
-        M, nq = len(job["ids_h"]), self.nq
-        good, T, nrow = job["good"], job["T"], job["nrow"]
-        if not len(good):
-            job["result"] = (np.zeros((M, 1, nq)), np.zeros(M, dtype=np.int64)) + job["flags"]
-            return True
-        R, W = T.shape[0], T.shape[1] - 1
-        seg_r, seg_i = job["seg_r"], job["seg_i"]
-        pieces = (np.arange(W)[None, :] < nrow[:, None]).astype(np.int64)
-        seg_len = np.zeros(len(seg_r), dtype=np.int64)
-        if len(seg_r):
-            seg_len[:] = job["count"] + 1
-            for k, rep in job["replacement"].items():
-                seg_len[k] = len(rep)
-            pieces[seg_r, seg_i] = seg_len
-        off = np.cumsum(pieces, axis=1) - pieces                       # first output row of waypoint i
-        length = pieces.sum(axis=1)
-        out = np.zeros((R, max(1, int(length.max())), nq))
-        r_idx, i_idx = np.nonzero(np.arange(W)[None, :] < nrow[:, None])
-        out[r_idx, off[r_idx, i_idx] + pieces[r_idx, i_idx] - 1] = T[r_idx, i_idx + 1]      # every piece ends in its waypoint
-        if len(seg_r):
-            plain = np.array([k not in job["replacement"] for k in range(len(seg_r))])
-            kk = np.nonzero(plain)[0]
-            if len(kk):
-                cnt = job["count"][kk]
-                kr = np.repeat(kk, cnt)                                                      # (segment, interior state c) pairs
-                c = np.arange(int(cnt.sum())) - np.repeat(np.cumsum(cnt) - cnt, cnt)
-                out[seg_r[kr], off[seg_r[kr], seg_i[kr]] + c] = job["walk"][kr, c]
-            for k, rep in job["replacement"].items():
-                o = off[seg_r[k], seg_i[k]]
-                out[seg_r[k], o:o + len(rep)] = rep
-        traj = np.zeros((M, out.shape[1], nq))
-        ln = np.zeros(M, dtype=np.int64)
-        traj[good], ln[good] = out, length
-        job["result"] = (traj, ln) + job["flags"]
-        return True
-
-    def _rrt_finish(self, job):
-        self._rrt_advance(job, wait=True)
-        return job["result"]
-
     def plan(self, cur, target, env_ids):
-        """`SACAgent.plan` (rl/sac_agent.py:198-235) for M envs, synchronously.  Returns (traj [M, L, nq] device tensor, length
-        [M] device int64 -- 0 where the plan failed --, and the boolean numpy arrays success, interpolation, valid, exact).
-        Straight lines that validate never leave the GPU; only the envs that needed RRT-Connect are post-processed on the
-        host (ragged paths: successive differences, densification) and uploaded into their rows."""
-        torch = _torch()
-        cfg = self.cfg
-        M = cur.shape[0]
-        cur = self.clip_qpos(cur)
-        traj_t, tlen, succ, _ = simple_interpolate_batch(self.bp, cur, target, cfg.ac_scale, self.arm)
-        succ_h = succ.cpu().numpy()
-        success, interpolation = succ_h.copy(), np.ones(M, dtype=bool)
-        valid, exact = succ_h.copy(), succ_h.copy()
-        lens = torch.where(succ, tlen.to(torch.int64), torch.zeros_like(tlen, dtype=torch.int64))
-        fail = np.where(~succ_h)[0]
-        if len(fail) == 0:
-            return traj_t, lens, success, interpolation, valid, exact
-        fi = torch.as_tensor(fail, device=cur.device)
-        job = self._rrt_launch(cur[fi].contiguous(), target[fi].contiguous(), env_ids[fi].contiguous())
-        tr_j, ln_j, s_j, v_j, e_j = self._rrt_finish(job)
-        s_j, v_j, e_j = (x.cpu().numpy() if hasattr(x, "cpu") else x for x in (s_j, v_j, e_j))
-        interpolation[fail] = False
-        success[fail], valid[fail], exact[fail] = s_j, v_j, e_j
-        traj_t, lens = self._merge_paths(traj_t, lens, tr_j, ln_j, fi)
-        return traj_t, lens, success, interpolation, valid, exact
-
-    def _merge_paths(self, traj_t, lens, tr_j, ln_j, rows):
-        """write a job's padded trajectories (tr_j [M, L, nq], ln_j [M]; 0 = no path; device tensors or host arrays) into rows
-        `rows` (device index tensor) of traj_t / lens"""
-        torch = _torch()
-        L = int(tr_j.shape[1])
-        if L > traj_t.shape[1]:
-            traj_t = torch.cat([traj_t, torch.zeros(traj_t.shape[0], L - traj_t.shape[1], self.nq, dtype=traj_t.dtype, device=traj_t.device)], dim=1)
-        traj_t[rows, :L] = torch.as_tensor(tr_j, device=traj_t.device)
-        lens[rows] = torch.as_tensor(ln_j, device=traj_t.device)
-        return traj_t, lens
-
-    def _densify_cut(self, job):
-        """cut every long segment of a job by the straight-line rule (steps <= 0.8 ac_scale from the segment's clipped start,
-        then the segment's end), validate all interior states in one launch; segments whose interior states are all valid are
-        done, the others are listed in job["fb"] for the fallback planners.  All segments at once (array operations)."""
-        torch = _torch()
-        cfg, n = self.cfg, self.n
-        T, seg_r, seg_i = job["T"], job["seg_r"], job["seg_i"]
-        starts = self.limits.clip_state_np(T[seg_r, seg_i])                         # :266 clip_qpos on every segment start
-        ends = T[seg_r, seg_i + 1]
-        S = len(seg_r)
-        bound = cfg.ac_scale * 0.8
-        diff = ends[:, :n] - starts[:, :n]
-        ratio = np.maximum(np.where(diff > bound, diff / bound, 0.0), np.where(diff < -bound, diff / -bound, 0.0))
-        scale = np.maximum(ratio.max(axis=1), 1.0)
-        count = scale.astype(np.int64)                                              # int(): truncation
-        per_step = diff / scale[:, None]
-        K = int(count.max())
-        walk = np.repeat(starts[:, None, :], K, axis=1)
-        acc = starts[:, :n].copy()
-        for k in range(K):                                                          # K dependent additions, as the scalar rule
-            acc = acc + per_step
-            walk[:, k, :n] = acc
-        live = np.arange(K)[None, :] < count[:, None]
-        verdict = np.ones((S, K), dtype=bool)
-        verdict[live] = self._valid(torch.tensor(walk[live], device=self.env.device)).cpu().numpy()
-        job.update(starts=starts, ends=ends, count=count, walk=walk, fb=list(np.nonzero(~verdict.all(axis=1))[0]))
+        """`SACAgent.plan` (rl/sac_agent.py:198-235) for M envs, synchronously: `PlannerJobs.plan` with this rollout's step counts"""
+        return self.jobs.plan(cur, target, env_ids, self.t_env)
 
     # ------------------------------------------------------------------
     def agent_step(self, ac, record: bool = False, ac_type=None):
@@ -976,7 +568,7 @@ class BatchMoPARollout:
             if ac_type is None:
                 raise _lib.MopaError("discrete_action: agent_step needs the policy's ac_type [E] (1 = motion planner, 0 = direct)")
             self._ac_type_in.copy_(ac_type.reshape(-1))
-        if self.cfg.use_graphs and not record and getattr(self, "timing", None) is None:
+        if self.cfg.use_graphs and not record and self.timing is None:
             return self._agent_step_graphs(ac)
         if self._cf_mark is not None:      # envs that begin an agent step in this call (a reset since the last one has zeroed their total)
             self._cf_mark.copy_(_torch().where(self.busy, self._cf_mark, self.env.contact_force_total))
@@ -996,7 +588,7 @@ class BatchMoPARollout:
         if getattr(self.env, "dynamics", False):
             # waypoint execution through the physics loops over a data-dependent path length on the host: not capturable
             raise _lib.MopaError("use_graphs serves the kinematic env (a dynamics env executes waypoints step by step on the host)")
-        G = getattr(self, "_graphs", None)
+        G = self._graphs
         main = torch.cuda.current_stream(self.env.device)
         if G is None:
             G = self._graphs = {"calls": 0, "stream": torch.cuda.Stream(device=self.env.device), "pool": torch.cuda.graph_pool_handle(),
@@ -1049,16 +641,15 @@ class BatchMoPARollout:
         return res
 
     def _mark(self, name):
-        tm = getattr(self, "timing", None)     # optional dict: phase -> seconds (each mark synchronises; profiling only)
+        tm = self.timing     # optional dict: phase -> seconds (each mark synchronises; profiling only)
         if tm is None:
             return
         import time as _time
         torch = _torch()
         torch.cuda.current_stream().synchronize()    # the main stream only: planner launches on side streams go on
         now = _time.perf_counter()
-        last = getattr(self, "_mark_t", None)
-        if last is not None and name is not None:
-            tm[name] = tm.get(name, 0.0) + now - last
+        if self._mark_t is not None and name is not None:
+            tm[name] = tm.get(name, 0.0) + now - self._mark_t
         self._mark_t = now
 
     # The three parts of a call.  _seg_pre and _seg_exec have fixed shapes, touch persistent state only IN PLACE and read no
@@ -1163,29 +754,44 @@ class BatchMoPARollout:
         for x in (ps.tree_q, ps.tree_p, ps.state):
             x.record_stream(torch.cuda.current_stream())
 
+    def _pick_rows(self, mask, kind_in_flight, min_job, cap):
+        """the waiting envs of `mask` that go into a launch now, taken out of the mask: (ids ascending, start rows, target rows, step
+        counts, seeds), or None -- nothing waits, or too few while a launch of their kind is in flight (the pool waits for company)"""
+        torch, cfg = _torch(), self.cfg
+        if cfg.fused and cfg.async_planner and mask.is_cuda:
+            # the pick-up in one library launch (ids ascending as torch.nonzero lists them, mask cleared, start / target rows, step counts
+            # and seeds gathered) when the count lies within [what a launch waits for, the launch's cap]; one read-back as before
+            picked = self._pool_pick(mask, 1 if not kind_in_flight else min_job, cap)
+            if picked[0] == 0 or (picked[1] is None and picked[0] <= cap):
+                return None
+            if picked[1] is not None:
+                return picked[1:]
+        bi = torch.nonzero(mask).flatten()
+        if not (len(bi) and (not cfg.async_planner or len(bi) >= min_job or not kind_in_flight)):
+            return None
+        if cfg.async_planner and len(bi) > cap:
+            # the envs that have waited longest go first (a plain prefix would starve the high env indices whenever more wait than a launch takes)
+            bi = bi[torch.argsort(self._wait_since[bi], stable=True)[:cap]]
+        bi = bi.contiguous()
+        mask[bi] = False
+        cur, tgt, seeds = self._q_cur[bi].contiguous(), self._q_tgt[bi].contiguous(), (self.t_env[bi] + cfg.seed).contiguous()
+        return bi, cur, tgt, self.t_env[bi].clone(), seeds
+
     def _seg_plan(self, bag):
         """RRT-Connect launches for the pooled envs, pick-up of the launches that are done (host logic, dynamic shapes)"""
-        torch = _torch()
-        env, cfg, E, n = self.env, self.cfg, self.E, self.n
-        dev = env.device
-        mark = self._mark
-        plan_ok, traj_pad, path_len = bag["plan_ok"], bag["traj_pad"], bag["path_len"]
+        torch, cfg = _torch(), self.cfg
         # One K3 launch takes about as long for 40 queries as for 4000 (its time is the latency of the slowest query), so the
         # waiting envs of several calls share a launch: a job starts only when a side stream has no job in flight (and only
         # then the waiting envs are listed: the one read-back of this part).
         two_phase = cfg.async_planner and 0 < cfg.planner_first_iters < self.main_iters
         for retry in ((False, True) if two_phase else (False,)):
-            side = None
-            if cfg.async_planner:
-                used = {j["stream"] for j in self._jobs}
-                free = [st for st in self._streams if st not in used]
-                side = free[0] if free else None
+            used = {j.stream for j in self._jobs}
+            side = next((st for st in self._streams if st not in used), None)      # (lock-step: there are no side streams)
             if side is None and cfg.async_planner:
                 break
-            mask = self._retry_mask if retry else self._pool_mask
             # (a launch costs the host about as much as a call: with several streams free, small pools wait for company
             # unless nothing of their kind is in flight)
-            kind_in_flight = any(j.get("retry", False) == retry for j in self._jobs)
+            kind_in_flight = any(j.retry == retry for j in self._jobs)
             min_job = cfg.planner_min_job // 4 if retry else cfg.planner_min_job
             known = self._pool_counts_known() if cfg.async_planner else None
             if known is not None:
@@ -1193,119 +799,88 @@ class BatchMoPARollout:
                 # the count an earlier call left behind says a launch is due
                 if not (known[int(retry)] >= min_job or (known[int(retry)] > 0 and not kind_in_flight)):
                     continue
-            cap = cfg.planner_job_cap // 4 if retry else cfg.planner_job_cap
-            picked = None
-            if cfg.fused and cfg.async_planner and mask.is_cuda:
-                # the pick-up in one library launch (ids ascending as torch.nonzero lists them, mask cleared, start / target rows, step counts
-                # and seeds gathered) when the count lies within [what a launch waits for, the launch's cap]; one read-back as before
-                picked = self._pool_pick(mask, 1 if not kind_in_flight else min_job, cap)
-                if picked[0] == 0 or (picked[1] is None and picked[0] <= cap):
-                    continue          # nothing waits / too few: the pool waits for company
-            if picked is not None and picked[1] is not None:
-                n_p, bi, cur_p, tgt_p, steps_p, seeds_p = picked
-                if bool(self._interp_overflow):
-                    raise _lib.MopaError(f"a straight-line pre-check needed more than {self._k_interp} steps (targets further than "
-                                         "action_range from the current state?)")
-                iters = cfg.planner_first_iters if (two_phase and not retry) else self.main_iters
-                res_in = None
-                if retry and self._res is not None:
-                    from .batch import PlanState
-                    res_in = PlanState(self._res.tree_q, self._res.tree_p, self._res.state, cfg.max_nodes, self._res.na).rows(bi)
-                chain = bool(cfg.planner_chain) and two_phase and not retry and side is not None and cfg.device_paths and self.nq <= 64
-                job = self._rrt_launch(cur_p, tgt_p, bi, side, iters=iters, keep=two_phase and not retry and side is not None, resume=res_in,
-                                       chain=chain, steps=steps_p, seeds=seeds_p)
-                job["retry"] = retry
-                self._jobs.append(job)
+            picked = self._pick_rows(self._retry_mask if retry else self._pool_mask, kind_in_flight, min_job,
+                                     cfg.planner_job_cap // 4 if retry else cfg.planner_job_cap)
+            if picked is None:
                 continue
-            bi = torch.nonzero(mask).flatten()
-            if len(bi) and (not cfg.async_planner or len(bi) >= min_job or not kind_in_flight):
-                if bool(self._interp_overflow):
-                    raise _lib.MopaError(f"a straight-line pre-check needed more than {self._k_interp} steps (targets further than "
-                                         "action_range from the current state?)")
-                if cfg.async_planner and len(bi) > cap:
-                    # the envs that have waited longest go first (a plain prefix would starve the high env indices whenever
-                    # more envs wait than a launch takes)
-                    bi = bi[torch.argsort(self._wait_since[bi], stable=True)[:cap]]
-                bi = bi.contiguous()
-                mask[bi] = False
-                iters = cfg.planner_first_iters if (two_phase and not retry) else self.main_iters
-                # a first-phase launch keeps its trees; the retry launch of its unsolved queries continues from them (parked per
-                # env in between) instead of retracing the first iterations
-                res_in = None
-                if retry and self._res is not None:
-                    from .batch import PlanState
-                    res_in = PlanState(self._res.tree_q, self._res.tree_p, self._res.state, cfg.max_nodes, self._res.na).rows(bi)
-                chain = bool(cfg.planner_chain) and two_phase and not retry and side is not None and cfg.device_paths and self.nq <= 64
-                job = self._rrt_launch(self._q_cur[bi].contiguous(), self._q_tgt[bi].contiguous(), bi, side, iters=iters,
-                                       keep=two_phase and not retry and side is not None, resume=res_in, chain=chain)
-                job["retry"] = retry
-                self._jobs.append(job)
+            if bool(self._interp_overflow):
+                raise _lib.MopaError(f"a straight-line pre-check needed more than {self._k_interp} steps (targets further than "
+                                     "action_range from the current state?)")
+            bi, cur_p, tgt_p, steps_p, seeds_p = picked
+            # a first-phase launch keeps its trees; the retry launch of its unsolved queries continues from them (parked per
+            # env in between) instead of retracing the first iterations -- or, chained, goes behind it on its stream
+            first = two_phase and not retry and side is not None
+            res_in = None
+            if retry and self._res is not None:
+                from .batch import PlanState
+                res_in = PlanState(self._res.tree_q, self._res.tree_p, self._res.state, cfg.max_nodes, self._res.na).rows(bi)
+            job = self.jobs.launch(cur_p, tgt_p, bi, steps_p, seeds_p, stream=side, keep=first, resume=res_in,
+                                   iters=cfg.planner_first_iters if (two_phase and not retry) else self.main_iters,
+                                   chain=bool(cfg.planner_chain) and first and cfg.device_paths and self.nq <= 64)
+            job.retry = retry
+            self._jobs.append(job)
         # ---- RRT-Connect jobs that are done (lock-step: all of them) ----
-        finished = torch.zeros(E, dtype=torch.bool, device=dev) if self._jobs else None
-        n_fin = 0
-        still = []
-        for job in self._jobs:
-            if not cfg.async_planner:
-                self._rrt_advance(job, wait=True)
-            elif not self._rrt_advance(job, wait=False):
-                still.append(job)
-                continue
-            tr_j, ln_j, s_j, v_j, e_j = job["result"]
-            if job["stream"] is not None:
-                # results allocated on the job's side stream are read by this stream's launches below: tell the allocator,
-                # or the next job could be handed their memory while those launches are still queued
-                for x in (tr_j, ln_j, s_j, v_j, e_j):
-                    if hasattr(x, "record_stream"):
-                        x.record_stream(torch.cuda.current_stream())
-            jid = job["ids"]
-            t = lambda x: torch.as_tensor(x, device=dev)
-            s_t, v_t, e_t = t(s_j), t(v_j), t(e_j)
-            # (everything below is index arithmetic over the job's rows with a `fin` mask -- no boolean-mask indexing: each `x[mask]` is a
-            #  torch.nonzero underneath, three launches, a memset and a read-back the host waits for)
-            fin = None
-            if job["iters"] < self.main_iters:
-                # first-phase launch: "no exact solution" may only mean that the short budget ran out -- those queries run
-                # again with the full budget (their envs stay busy); everything else is final
-                again = ~s_t & ~e_t
-                if "chain" in job:
-                    # their continuation is already running behind this launch on its stream: a job of its own, finished at
-                    # the second event
-                    rows = torch.nonzero(again).flatten()
-                    if len(rows):
-                        lazy = {"ids": jid[rows], "cur": job["cur"][rows], "target": job["target"][rows], "steps": job["steps"][rows],
-                                "event": job["chain"]["event"], "stage": "rrt", "stream": job["stream"], "iters": self.main_iters,
-                                "retry": True, "lazy": (job["chain"], rows)}
-                        # its tensors come from THIS stream's ops (nonzero, gathers) and are read on the side stream later:
-                        # an event the side stream waits for, and the allocator told about the second reader
-                        lazy["built"] = torch.cuda.Event()
-                        lazy["built"].record(torch.cuda.current_stream())
-                        if job["stream"] is not None:
-                            for x in (lazy["ids"], lazy["cur"], lazy["target"], lazy["steps"], rows):
-                                x.record_stream(job["stream"])
-                        still.append(lazy)
-                else:
-                    self._retry_mask[jid] = self._retry_mask[jid] | again
-                    if "pstate" in job:
-                        self._park_state(job["pstate"], jid, again)
-                self.n_retried = self.n_retried + again.sum()
-                fin = ~again
-            ok_f = s_t if fin is None else (s_t & fin)
-            bad_f = ~s_t if fin is None else (~s_t & fin)
-            finished[jid] = True if fin is None else fin
-            n_fin += 1
-            plan_ok[jid] = s_t if fin is None else torch.where(fin, s_t, plan_ok[jid])
-            self.counters["mp"].index_add_(0, jid, ok_f.to(self.counters["mp"].dtype))
-            self.counters["mp_fail"].index_add_(0, jid, bad_f.to(self.counters["mp_fail"].dtype))
-            self.counters["approximate"].index_add_(0, jid, (bad_f & ~e_t).to(self.counters["approximate"].dtype))
-            self.counters["invalid"].index_add_(0, jid, (bad_f & ~v_t).to(self.counters["invalid"].dtype))
-            ln_t = t(ln_j)
-            if fin is not None:      # (the rows of the queries that run again keep their length 0: their trajectory rows are never read)
-                ln_t = torch.where(fin, ln_t.to(path_len.dtype), path_len[jid])
-            traj_pad, path_len = self._merge_paths(traj_pad, path_len, t(tr_j), ln_t, jid)
-            self.busy[jid] = False if fin is None else (self.busy[jid] & ~fin)
-        self._jobs = still
-        mark("plan")
-        bag.update(plan_ok=plan_ok, traj_pad=traj_pad, path_len=path_len, finished=finished, n_finished=n_fin)
+        bag["finished"] = torch.zeros(self.E, dtype=torch.bool, device=self.env.device) if self._jobs else None
+        jobs, self._jobs = self._jobs, []
+        for job in jobs:
+            if self.jobs.advance(job, wait=not cfg.async_planner):
+                self._fold(job, bag)
+            else:
+                self._jobs.append(job)
+        self._mark("plan")
+
+    def _fold(self, job, bag):
+        """a finished job's rows -> plan_ok / traj_pad / path_len of the call, `busy` and the counters; the queries a first-phase launch
+        left unsolved go on to their retry (pooled: `_retry_mask`; chained: a job of their own joins `_jobs`)"""
+        torch, dev, plan_ok, path_len = _torch(), self.env.device, bag["plan_ok"], bag["path_len"]
+        tr_j, ln_j, s_j, v_j, e_j = job.result
+        if job.stream is not None:
+            # results allocated on the job's side stream are read by this stream's launches below: tell the allocator,
+            # or the next job could be handed their memory while those launches are still queued
+            for x in job.result:
+                if hasattr(x, "record_stream"):
+                    x.record_stream(torch.cuda.current_stream())
+        jid, t = job.ids, lambda x: torch.as_tensor(x, device=dev)
+        s_t, v_t, e_t = t(s_j), t(v_j), t(e_j)
+        # (everything below is index arithmetic over the job's rows with a `fin` mask -- no boolean-mask indexing: each `x[mask]` is a
+        #  torch.nonzero underneath, three launches, a memset and a read-back the host waits for)
+        fin = None
+        if job.iters < self.main_iters:
+            # first-phase launch: "no exact solution" may only mean that the short budget ran out -- those queries run
+            # again with the full budget (their envs stay busy); everything else is final
+            again = ~s_t & ~e_t
+            if job.chain is not None:
+                rows = torch.nonzero(again).flatten()
+                if len(rows):
+                    nxt = PlanJob.continuation(job, rows, self.main_iters)
+                    # its tensors come from THIS stream's ops (nonzero, gathers) and are read on the side stream later:
+                    # an event the side stream waits for, and the allocator told about the second reader
+                    nxt.built = torch.cuda.Event()
+                    nxt.built.record(torch.cuda.current_stream())
+                    if job.stream is not None:
+                        for x in (nxt.ids, nxt.cur, nxt.target, nxt.steps, rows):
+                            x.record_stream(job.stream)
+                    self._jobs.append(nxt)
+            else:
+                self._retry_mask[jid] = self._retry_mask[jid] | again
+                if job.pstate is not None:
+                    self._park_state(job.pstate, jid, again)
+            self.n_retried = self.n_retried + again.sum()
+            fin = ~again
+        ok_f = s_t if fin is None else (s_t & fin)
+        bad_f = ~s_t if fin is None else (~s_t & fin)
+        bag["finished"][jid] = True if fin is None else fin
+        bag["n_finished"] += 1
+        plan_ok[jid] = s_t if fin is None else torch.where(fin, s_t, plan_ok[jid])
+        self.counters["mp"].index_add_(0, jid, ok_f.to(self.counters["mp"].dtype))
+        self.counters["mp_fail"].index_add_(0, jid, bad_f.to(self.counters["mp_fail"].dtype))
+        self.counters["approximate"].index_add_(0, jid, (bad_f & ~e_t).to(self.counters["approximate"].dtype))
+        self.counters["invalid"].index_add_(0, jid, (bad_f & ~v_t).to(self.counters["invalid"].dtype))
+        ln_t = t(ln_j)
+        if fin is not None:      # (the rows of the queries that run again keep their length 0: their trajectory rows are never read)
+            ln_t = torch.where(fin, ln_t.to(path_len.dtype), path_len[jid])
+        bag["traj_pad"], bag["path_len"] = merge_paths(bag["traj_pad"], path_len, t(tr_j), ln_t, jid)
+        self.busy[jid] = False if fin is None else (self.busy[jid] & ~fin)
 
     def _seg_exec(self, bag, record: bool = False):
         """direct steps, failed-plan steps and waypoint execution; counters and the returned transition"""
@@ -1374,9 +949,8 @@ class BatchMoPARollout:
     # ---- the same two parts with the elementwise work in the library's bookkeeping kernels (cfg.fused) ----
     def _fused_struct(self):
         torch = _torch()
-        S = getattr(self, "_fs", None)
-        if S is not None:
-            return S
+        if self._fs is not None:
+            return self._fs
         import ctypes as C
         env, cfg = self.env, self.cfg
         if _lib.lib().mopa_rollout_step_size() != C.sizeof(_lib.MopaRolloutStep):
@@ -1430,7 +1004,7 @@ class BatchMoPARollout:
     def _pool_counts_known(self):
         """(envs waiting for a planner launch, for a retry launch) as of the latest earlier call whose bookkeeping has finished
         on the device, or None (torch form of the calls / no such call yet): copied to pinned memory behind each call"""
-        ring = getattr(self, "_count_ring", None)
+        ring = self._count_ring
         if not ring:
             return None
         for k in range(len(ring) - 1, -1, -1):
@@ -1442,10 +1016,9 @@ class BatchMoPARollout:
 
     def _pool_counts_push(self):
         torch = _torch()
-        ring = getattr(self, "_count_ring", None)
-        if ring is None:
-            ring = self._count_ring = []
-            self._count_free = []
+        if self._count_ring is None:
+            self._count_ring, self._count_free = [], []
+        ring = self._count_ring
         # at most two calls enqueued ahead of the device: the planner's pick-ups are decided on the host's clock, and a host
         # far ahead would enqueue calls in which envs sit out although their query has long finished
         pending = [r for r in ring if not r[0].query()]
@@ -1526,7 +1099,7 @@ class BatchMoPARollout:
              "done_out": em(E, dt=torch.uint8), "intra": em(E, dt=i64), "ob_next": em(E, S.obs_dim), "success_out": em(E, dt=env.success.dtype)}
         # (the planner's pick-ups may have replaced plan_ok / path_len rows in place and widened traj_pad)
         counting = cfg.async_planner and not cfg.use_graphs
-        if counting and getattr(self, "_pool_counts", None) is None:
+        if counting and self._pool_counts is None:
             self._pool_counts = torch.zeros(2, dtype=i64, device=dev)
         self._fused_bind(finished=bag.get("finished"), plan_ok=plan_ok, path_len=path_len, active=bag["active"], is_pl=bag["is_pl"], a=bag["a"],
                          extra_ac=bag["_extra_buf"], retry_mask=self._retry_mask if counting else None,
@@ -1580,7 +1153,7 @@ class BatchMoPARollout:
         dev = env.device
         plan_ok, traj_pad, path_len = bag["plan_ok"], bag["traj_pad"], bag["path_len"]
         L = int(traj_pad.shape[1])
-        W = getattr(self, "_walk", None)
+        W = self._walk
         if W is None:
             z = lambda *sh, dt=torch.float64: torch.zeros(*sh, dtype=dt, device=dev)
             W = self._walk = {"on": z(E, dt=torch.bool), "traj": z(E, L, self.nq), "len": z(E, dt=torch.int64), "pos": z(E, dt=torch.int64),
@@ -1653,9 +1226,8 @@ class BatchMoPARollout:
     def drain(self):
         """wait for every RRT-Connect launch in flight (async_planner); their envs complete their step in a following agent_step"""
         for job in self._jobs:
-            if job["event"] is not None:
-                job["event"].synchronize()
-
+            if job.event is not None:
+                job.event.synchronize()
 
     def run_episode(self, policy, max_step: int = 10000, is_train: bool = True, random_exploration: bool = False, reset: bool = True):
         """`MoPARolloutRunner.run_episode` (reference rl/mopa_rollouts.py:401-678: the evaluation loop -- ONE episode, `while not done

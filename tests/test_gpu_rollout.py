@@ -487,10 +487,10 @@ def test_device_path_postprocessing_equals_host_form(env_name):
         tgt = ro.limits.clip_target(tgt)
         tgt, _, tv = ro.bp.pullback(cur.contiguous(), tgt.contiguous(), 0.02, 100)
         ids = torch.arange(E, device=env.device)
-        job = ro._rrt_launch(cur.contiguous(), tgt.contiguous(), ids)
-        tr, ln, s, v, e = ro._rrt_finish(job)
+        job = ro.jobs.launch(cur.contiguous(), tgt.contiguous(), ids, ro.t_env[ids].clone())
+        tr, ln, s, v, e = ro.jobs.finish(job)
         conv = lambda x: x.cpu().numpy() if hasattr(x, "cpu") else np.asarray(x)
-        res[dev_paths] = tuple(conv(x) for x in (tr, ln, s, v, e)) + (conv(job["plen"]),)
+        res[dev_paths] = tuple(conv(x) for x in (tr, ln, s, v, e)) + (conv(job.plen),)
     (tr_h, ln_h, s_h, v_h, e_h, pl), (tr_d, ln_d, s_d, v_d, e_d, _) = res[False], res[True]
     assert np.array_equal(ln_h, ln_d) and np.array_equal(s_h, s_d) and np.array_equal(v_h, v_d) and np.array_equal(e_h, e_d)
     assert s_h.sum() > E // 3 and ((~s_h).sum() > 0 or env_name != "SawyerPushObstacle-v0")     # Push: sentinel rows too

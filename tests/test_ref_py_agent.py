@@ -6,30 +6,14 @@ same lengths and the same success / interpolation / valid / exact flags.
 CPU leg: the batched code on CPU tensors with the oracle as validity checker (pins the host logic).  GPU leg: the
 product path -- HIP validity (K1), HIP RRT-Connect (K3) -- through BatchMoPARollout.plan."""
 import os
-import types
 
 import numpy as np
 import pytest
 
+from oracle_bp import OracleBP, bits as _bits
+
 ENV = "SawyerPushObstacle-v0"
 G = np.load(os.path.join(os.path.dirname(__file__), "golden", "ref_py_agent_push.npz"))
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
-
-
-class OracleBP:
-    """BatchPlanner look-alike over the CPU oracle (test infrastructure)."""
-
-    def __init__(self, orc):
-        self.orc, self.na, self.nq = orc, orc.na, orc.nq
-        self.scene = types.SimpleNamespace(active_idx=orc.active_idx)
-
-    def is_valid(self, q_active, qpos_env, samples_per_env=None, **kw):
-        import torch
-        v, _ = self.orc.is_valid_batch(q_active.numpy(), qpos_env.numpy(), samples_per_env=samples_per_env, want_min_dist=False)
-        return torch.from_numpy(v)
 
 
 def _check_si(traj, tlen, success):

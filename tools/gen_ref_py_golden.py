@@ -237,9 +237,15 @@ def agent_cases(pi, K, rng):
 
 
 def gen_agent():
+    gen_agent_recording("ref_py_agent_push.npz")
+    # the same cases with a planner range of 0.5: most steps of the RRT-Connect paths exceed ac_scale and are densified
+    gen_agent_recording("ref_py_agent_push_long.npz", range_=0.5)
+
+
+def gen_agent_recording(name, range_=None):
     env = "SawyerPushObstacle-v0"
     P = AGENT_PARAMS
-    cfg = make_config(env, timelimit=P["timelimit"])
+    cfg = make_config(env, timelimit=P["timelimit"], **({} if range_ is None else {"range": range_}))
     agent, pi = make_agent(env, cfg)
     K = 64
     st = Streams(agent, K, P["seed"], P["max_nodes"], P["max_path"])
@@ -263,8 +269,9 @@ def gen_agent():
     print("  agent: simple_interpolate ok", int(si_f[:, 0].sum()), "/", K, "| plan success", int(pl_f[:, 0].sum()),
           "interpolation", int((pl_f[:, 0] & pl_f[:, 1]).sum()), "rrt", int((pl_f[:, 0] & (1 - pl_f[:, 1])).sum()),
           "target valid", int(tgt_valid.sum()), "max len", L)
-    save("ref_py_agent_push.npz", cur=cur, tgt=tgt, tgt_valid=tgt_valid, si_traj=si_t, si_len=si_l, si_flags=si_f, plan_traj=pl_t,
-         plan_len=pl_l, plan_flags=pl_f, params=np.array([P["timelimit"], P["max_nodes"], P["max_path"], P["seed"], 0.05]))
+    params = [P["timelimit"], P["max_nodes"], P["max_path"], P["seed"], 0.05] + ([] if range_ is None else [range_])
+    save(name, cur=cur, tgt=tgt, tgt_valid=tgt_valid, si_traj=si_t, si_len=si_l, si_flags=si_f, plan_traj=pl_t,
+         plan_len=pl_l, plan_flags=pl_f, params=np.array(params))
 
 
 # ------------------------------------------------------------------------------------------------------------------

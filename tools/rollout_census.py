@@ -28,4 +28,4 @@ a = np.array(rows, dtype=float)
 print("mean over 200 calls: busy %.0f, in pool %.0f, in retry pool %.0f, launches in flight %.1f, stepped %.0f (planner steps %.0f)" % tuple(a.mean(0)))
 wait = (ro._t - ro._wait_since[ro.busy]).float()
 print("waiting time of the busy envs now (calls): mean %.1f median %.1f p90 %.1f max %.0f" % (wait.mean().item(), wait.median().item(), wait.quantile(0.9).item(), wait.max().item()))
-for j in ro._jobs[:6]: print({k: (v if isinstance(v, (int, float, str, bool)) else type(v).__name__) for k, v in j.items() if k in ("n", "phase", "iters", "stage", "keep", "chain")}, "ids" , int(j["ids"].numel()) if "ids" in j else None)
+for j in ro._jobs[:6]: print({"iters": j.iters, "stage": j.stage, "retry": j.retry, "chained": j.chain is not None}, "ids", int(j.ids.numel()))

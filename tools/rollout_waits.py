@@ -31,12 +31,12 @@ for t in range(calls):
     now = time.perf_counter()
     ids = set(id(j) for j in ro._jobs)
     for j in ro._jobs:
-        if id(j) not in born: born[id(j)] = (t, now, len(j["ids"]), bool(j.get("retry")), )
+        if id(j) not in born: born[id(j)] = (t, now, len(j.ids), j.retry)
     for k in [k for k in born if k not in ids]:
         t0, w0, n, r = born.pop(k); rows.append((n, r, t - t0, (now - w0) * 1e3))
     if t >= 50 and t % 25 == 0:
-        in_first = sum(len(j["ids"]) for j in ro._jobs if not j.get("retry")); in_retry = sum(len(j["ids"]) for j in ro._jobs if j.get("retry"))
-        print(f"call {t}: busy {int(ro.busy.sum())} = pool {int(ro._pool_mask.sum())} + first-phase jobs {in_first} ({sum(1 for j in ro._jobs if not j.get('retry'))}) + retry pool {int(ro._retry_mask.sum())} + retry jobs {in_retry} ({sum(1 for j in ro._jobs if j.get('retry'))}); stepped {int(out['stepped'].sum())}; stages {[j['stage'] for j in ro._jobs]}", flush=True)
+        in_first = sum(len(j.ids) for j in ro._jobs if not j.retry); in_retry = sum(len(j.ids) for j in ro._jobs if j.retry)
+        print(f"call {t}: busy {int(ro.busy.sum())} = pool {int(ro._pool_mask.sum())} + first-phase jobs {in_first} ({sum(1 for j in ro._jobs if not j.retry)}) + retry pool {int(ro._retry_mask.sum())} + retry jobs {in_retry} ({sum(1 for j in ro._jobs if j.retry)}); stepped {int(out['stepped'].sum())}; stages {[j.stage for j in ro._jobs]}", flush=True)
 print("ms per call %.2f" % ((time.perf_counter() - t_start) / calls * 1e3))
 r = np.array([(a, b, c, d) for a, b, c, d in rows if True], dtype=float)
 for kind in (0, 1):
