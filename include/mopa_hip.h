@@ -919,6 +919,29 @@ int mopa_ik_targets_batch(MopaIk *ik, int64_t E, const double *site_pos_dev /*[E
                           const double *ac_dev /*[E,ac_stride]*/, int64_t ac_stride, double action_range, const double *world_lo /*[3] host*/,
                           const double *world_hi /*[3] host*/, double *target_cart_dev /*[E,3]*/, double *target_quat_dev /*[E,4]*/, void *stream);
 
+/* The position-only form of that problem: an env whose world box has n_cart = 2 or 3 entries and whose action carries no quaternion
+ * (PusherObstacle-v0, scripts/2d/mopa_ik.sh; rl/trainer.py:93-110, rl/mopa_rollouts.py:91-98,684-690).  Components below n_cart:
+ * clip(site_pos + action_range * ac, world box) -- a product, then a sum, then np.clip's comparisons; components at or above n_cart: the
+ * site's own.  ac rows are ac_stride (>= n_cart) doubles apart; world_lo / world_hi: n_cart HOST doubles each.  One launch.
+ * MOPA_ERR_INVALID_ARG before any launch: n_cart outside 2..3, a NULL buffer, E < 0, ac_stride < n_cart. */
+int mopa_ik_targets_pos_batch(MopaIk *ik, int64_t E, const double *site_pos_dev /*[E,3]*/, const double *ac_dev /*[E,ac_stride]*/,
+                              int64_t ac_stride, int32_t n_cart, double action_range, const double *world_lo /*[n_cart] host*/,
+                              const double *world_hi /*[n_cart] host*/, double *target_cart_dev /*[E,3]*/, void *stream);
+
+/* The whole pre-step of a position-only MoPA + IK rollout call (`_cart2dispalcement` with target_quat = None, rl/mopa_rollouts.py:683-728)
+ * in ONE launch, one lane per env: site pose of qpos -> the target of mopa_ik_targets_pos_batch -> the position-only solve of
+ * mopa_ik_solve_batch on the lane's own copy of the movable joints (qpos_dev is only read) -> clip of the movable joints to
+ * jnt_lo / jnt_hi -> displacement = clipped - qpos[movable].  Bit for bit the composition of the separate launches
+ * (site_pose, targets_pos, solve, elementwise maximum / minimum / subtraction).  err_norm_dev / steps_dev / success_dev (as IKResult)
+ * may each be NULL.  Argument errors as above (plus max_steps <= 0), before any launch. */
+int mopa_ik_displacement_pos_batch(MopaIk *ik, int64_t E, const double *qpos_dev /*[E,nq]*/, const double *ac_dev /*[E,ac_stride]*/,
+                                   int64_t ac_stride, int32_t n_cart, double action_range, const double *world_lo /*[n_cart] host*/,
+                                   const double *world_hi /*[n_cart] host*/, int32_t max_steps, double tol, double max_update_norm,
+                                   double progress_thresh, double regularization_strength, const double *jnt_lo_dev /*[n_joints]*/,
+                                   const double *jnt_hi_dev /*[n_joints]*/, double *displacement_dev /*[E,n_joints]*/,
+                                   double *err_norm_dev /*[E] or NULL*/, int32_t *steps_dev /*[E] or NULL*/,
+                                   uint8_t *success_dev /*[E] or NULL*/, void *stream);
+
 /* The straight-line pre-check of SACAgent.plan / simple_interpolate (rl/sac_agent.py:198-204, 236-272) for E envs: the line
  * cur -> target is cut into int(s) equal steps, s = max(1, max_j |diff_j| / (0.8 ac_scale)) over the arm joints qpos[:n_arm]
  * (= the scene's active joints), each interior state a running sum from cur and validated (env row = cur); traj[e] = the

@@ -37,6 +37,7 @@ EXPORTED_SYMBOLS = [
     "mopa_pusher_dyn_desc_size", "mopa_env_attach_pusher_dynamics", "mopa_env_set_pusher_stats", "mopa_env_pusher_substeps_batch",
     "mopa_env_step_pusher_batch", "mopa_env_set_contact_force",
     "mopa_ik_create", "mopa_ik_destroy", "mopa_ik_solve_batch", "mopa_ik_site_pose_batch", "mopa_ik_targets_batch",
+    "mopa_ik_targets_pos_batch", "mopa_ik_displacement_pos_batch",
     "mopa_paths_unwrap_batch", "mopa_paths_unwrap_seam_batch", "mopa_paths_walk_batch", "mopa_paths_assemble_batch", "mopa_interpolate_batch",
 ]
 
@@ -277,6 +278,9 @@ def lib() -> C.CDLL:
                                       vp, vp, vp, vp]
     L.mopa_ik_site_pose_batch.argtypes = [vp, C.c_int64, vp, vp, vp, vp]
     L.mopa_ik_targets_batch.argtypes = [vp, C.c_int64, vp, vp, vp, C.c_int64, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double), vp, vp, vp]
+    L.mopa_ik_targets_pos_batch.argtypes = [vp, C.c_int64, vp, vp, C.c_int64, C.c_int32, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double), vp, vp]
+    L.mopa_ik_displacement_pos_batch.argtypes = [vp, C.c_int64, vp, vp, C.c_int64, C.c_int32, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                                 C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double, vp, vp, vp, vp, vp, vp, vp]
     L.mopa_scene_valid_kernel.argtypes = [vp, C.c_int64, C.c_char_p, C.c_int32]
     L.mopa_scene_motion_kernel.argtypes = [vp, C.c_int64, C.c_char_p, C.c_int32]
     L.mopa_scene_k1_baked.argtypes = [vp]

@@ -65,35 +65,25 @@ MOPA_D void ik_chol_solve(double (&H)[kIkMaxJ][kIkMaxJ], const double (&g)[kIkMa
     }
 }
 
+// One lane's solve: the iteration of `k_ik_solve` and of the fused position-only pre-step `k_ik_displacement_pos`.  `row` is the lane's
+// qpos row (read: the joints on the chain that are not movable), `qj_io` the movable joints' values -- in: the start, out: the result --,
+// `cols` / `save` the wave's LDS ([kIkMaxJ][6][64] and [n_save][7][64] doubles).  steps_io / success_io / err_norm_io as IKResult; the caller
+// presets steps = max_steps - 1, success = 0, err_norm = 0.  `__any` inside: every lane of the wave calls it, idle ones with active = false.
 // ROT: position + orientation target (6 x n Jacobian [jacp; jacr], inverse_kinematics.py:38-44,88-107)
 template <bool ROT>
-__global__ __launch_bounds__(64) void k_ik_solve(IkHdr h, const double *__restrict__ GD, const int32_t *__restrict__ GI, long long E,
-                                                 double *__restrict__ qpos, const double *__restrict__ target,
-                                                 const double *__restrict__ target_quat, double rot_weight, int max_steps, double tol,
-                                                 double max_update_norm, double progress_thresh, double reg,
-                                                 double *__restrict__ err_norm_out, int *__restrict__ steps_out,
-                                                 unsigned char *__restrict__ success_out) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    double *cols = reinterpret_cast<double *>(smem);                 // [kIkMaxJ][6][64]: world axis, anchor
-    double *save = cols + kIkMaxJ * 6 * 64;                          // [n_save][7][64]
-    const int lane = threadIdx.x;
-    const long long e0 = (long long)blockIdx.x * 64 + lane;
-    const bool in_range = e0 < E;
-    const long long e = in_range ? e0 : E - 1;
-    double *row = qpos + e * h.nq;
-    const V3 tgt = ld3(target + 3 * e);
-    Q4 tq{1.0, 0.0, 0.0, 0.0};
-    if (ROT) tq = Q4{target_quat[4 * e], target_quat[4 * e + 1], target_quat[4 * e + 2], target_quat[4 * e + 3]};
-    bool active = in_range;
-    int steps = max_steps - 1, success = 0;
-    double err_norm = 0.0;
-    for (int c = 0; c < kIkMaxJ; c++)          // columns of joints that are not on the site's chain stay zero
-        for (int i = 0; i < 6; i++) cols[(c * 6 + i) * 64 + lane] = 0.0;
-    // the movable joints' values live in registers for the whole solve (written back once, at the end): updated through the qpos row they made
-    // a store -> load round trip through memory in every iteration's chain walk
+MOPA_D void ik_solve_lane(const IkHdr &h, const double *__restrict__ GD, const int32_t *__restrict__ GI, const double *__restrict__ row,
+                          double (&qj_io)[kIkMaxJ], const V3 tgt, const Q4 tq, double rot_weight, int max_steps, double tol,
+                          double max_update_norm, double progress_thresh, double reg, double *cols, double *save, const int lane,
+                          bool active, double &err_norm_io, int &steps_io, int &success_io) {
+    // (the solve works on locals of its own and hands them back at the end: updated through the caller's references, hipcc kept the joint values,
+    //  the error norm and the two flags in 80 B of scratch per lane)
     double qj[kIkMaxJ];
 #pragma unroll
-    for (int k = 0; k < kIkMaxJ; k++) qj[k] = (k < h.n_joints) ? row[GI[h.o_col_adr + k]] : 0.0;
+    for (int k = 0; k < kIkMaxJ; k++) qj[k] = qj_io[k];
+    double err_norm = err_norm_io;
+    int steps = steps_io, success = success_io;
+    for (int c = 0; c < kIkMaxJ; c++)          // columns of joints that are not on the site's chain stay zero
+        for (int i = 0; i < 6; i++) cols[(c * 6 + i) * 64 + lane] = 0.0;
     V3 pos0{0.0, 0.0, 0.0};
     Q4 quat0{1.0, 0.0, 0.0, 0.0};
 
@@ -219,6 +209,38 @@ __global__ __launch_bounds__(64) void k_ik_solve(IkHdr h, const double *__restri
                 if (k < h.n_joints) qj[k] = qj[k] + (cap ? x[k] * sc : x[k]);
         }
     }
+#pragma unroll
+    for (int k = 0; k < kIkMaxJ; k++) qj_io[k] = qj[k];
+    err_norm_io = err_norm; steps_io = steps; success_io = success;
+}
+
+template <bool ROT>
+__global__ __launch_bounds__(64) void k_ik_solve(IkHdr h, const double *__restrict__ GD, const int32_t *__restrict__ GI, long long E,
+                                                 double *__restrict__ qpos, const double *__restrict__ target,
+                                                 const double *__restrict__ target_quat, double rot_weight, int max_steps, double tol,
+                                                 double max_update_norm, double progress_thresh, double reg,
+                                                 double *__restrict__ err_norm_out, int *__restrict__ steps_out,
+                                                 unsigned char *__restrict__ success_out) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    double *cols = reinterpret_cast<double *>(smem);                 // [kIkMaxJ][6][64]: world axis, anchor
+    double *save = cols + kIkMaxJ * 6 * 64;                          // [n_save][7][64]
+    const int lane = threadIdx.x;
+    const long long e0 = (long long)blockIdx.x * 64 + lane;
+    const bool in_range = e0 < E;
+    const long long e = in_range ? e0 : E - 1;
+    double *row = qpos + e * h.nq;
+    const V3 tgt = ld3(target + 3 * e);
+    Q4 tq{1.0, 0.0, 0.0, 0.0};
+    if (ROT) tq = Q4{target_quat[4 * e], target_quat[4 * e + 1], target_quat[4 * e + 2], target_quat[4 * e + 3]};
+    int steps = max_steps - 1, success = 0;
+    double err_norm = 0.0;
+    // the movable joints' values live in registers for the whole solve (written back once, at the end): updated through the qpos row they made
+    // a store -> load round trip through memory in every iteration's chain walk
+    double qj[kIkMaxJ];
+#pragma unroll
+    for (int k = 0; k < kIkMaxJ; k++) qj[k] = (k < h.n_joints) ? row[GI[h.o_col_adr + k]] : 0.0;
+    ik_solve_lane<ROT>(h, GD, GI, row, qj, tgt, tq, rot_weight, max_steps, tol, max_update_norm, progress_thresh, reg, cols, save, lane, in_range,
+                       err_norm, steps, success);
     if (in_range) {
 #pragma unroll
         for (int k = 0; k < kIkMaxJ; k++)
@@ -229,17 +251,10 @@ __global__ __launch_bounds__(64) void k_ik_solve(IkHdr h, const double *__restri
     }
 }
 
-// World pose of the site for E states: what the MoPA+IK rollouts read before they pose the IK problem
-// (`env.sim.data.get_site_xpos / get_site_xmat(config.ik_target)`, rl/mopa_rollouts.py:91-99,692).  Same chain walk as the solver.
-__global__ __launch_bounds__(64) void k_ik_site_pose(IkHdr h, const double *__restrict__ GD, const int32_t *__restrict__ GI, long long E,
-                                                     const double *__restrict__ qpos, double *__restrict__ site_pos,
-                                                     double *__restrict__ site_mat) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    double *save = reinterpret_cast<double *>(smem);                 // [n_save][7][64]
-    const int lane = threadIdx.x;
-    const long long e = (long long)blockIdx.x * 64 + lane;
-    if (e >= E) return;
-    const double *row = qpos + e * h.nq;
+// The chain walk of the site's pose at `row` (the solver's first iteration without its Jacobian columns): psite = world position of the
+// site, mat = world orientation of its body (row-major).  `save`: the wave's [n_save][7][64] doubles of LDS.
+MOPA_D void ik_site_walk(const IkHdr &h, const double *__restrict__ GD, const int32_t *__restrict__ GI, const double *__restrict__ row,
+                         double *save, const int lane, V3 &psite, double (&smat)[9]) {
     V3 pos{0.0, 0.0, 0.0};
     Q4 quat{1.0, 0.0, 0.0, 0.0};
     double mat[9];
@@ -277,15 +292,32 @@ __global__ __launch_bounds__(64) void k_ik_site_pose(IkHdr h, const double *__re
             double *sp = save + (size_t)bi.save * 7 * 64 + lane;
             pose7_st<64>(sp, pos, quat);
         }
-        if (b == h.site_k) {
-            st3(site_pos + 3 * e, add3(pos, mat_vec(mat, ld3(GD + h.o_off))));
-            const double *sl = GD + h.o_smat;       // identity when the site carries no rotation of its own
-            double *out = site_mat + 9 * e;
-            for (int r = 0; r < 3; r++)
-                for (int c = 0; c < 3; c++)
-                    out[3 * r + c] = h.has_smat ? fma(mat[3 * r + 2], sl[6 + c], fma(mat[3 * r + 1], sl[3 + c], mat[3 * r] * sl[c])) : mat[3 * r + c];
-        }
     }
+    // (the chain ends at the site's body: mopa_ik_create walks up from it, site_k = nb - 1)
+    psite = add3(pos, mat_vec(mat, ld3(GD + h.o_off)));
+#pragma unroll
+    for (int k = 0; k < 9; k++) smat[k] = mat[k];
+}
+
+// World pose of the site for E states: what the MoPA+IK rollouts read before they pose the IK problem
+// (`env.sim.data.get_site_xpos / get_site_xmat(config.ik_target)`, rl/mopa_rollouts.py:91-99,692).  Same chain walk as the solver.
+__global__ __launch_bounds__(64) void k_ik_site_pose(IkHdr h, const double *__restrict__ GD, const int32_t *__restrict__ GI, long long E,
+                                                     const double *__restrict__ qpos, double *__restrict__ site_pos,
+                                                     double *__restrict__ site_mat) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    double *save = reinterpret_cast<double *>(smem);                 // [n_save][7][64]
+    const int lane = threadIdx.x;
+    const long long e = (long long)blockIdx.x * 64 + lane;
+    if (e >= E) return;
+    V3 psite{0.0, 0.0, 0.0};
+    double mat[9] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0};
+    ik_site_walk(h, GD, GI, qpos + e * h.nq, save, lane, psite, mat);
+    st3(site_pos + 3 * e, psite);
+    const double *sl = GD + h.o_smat;       // identity when the site carries no rotation of its own
+    double *out = site_mat + 9 * e;
+    for (int r = 0; r < 3; r++)
+        for (int c = 0; c < 3; c++)
+            out[3 * r + c] = h.has_smat ? fma(mat[3 * r + 2], sl[6 + c], fma(mat[3 * r + 1], sl[3 + c], mat[3 * r] * sl[c])) : mat[3 * r + c];
 }
 
 // The IK problem of the MoPA + IK action space posed for E envs in one launch, one lane per env (`MoPARolloutRunner._cart2dispalcement`,
@@ -335,6 +367,80 @@ __global__ __launch_bounds__(64) void k_ik_targets(long long E, const double *__
     tq[1] = ((aw * bx + ax * bw) + ay * bz) - az * by;
     tq[2] = ((aw * by - ax * bz) + ay * bw) + az * bx;
     tq[3] = ((aw * bz + ax * by) - ay * bx) + az * bw;
+}
+
+// The position-only IK problem of the MoPA + IK action space (an env whose world box has n_cart = 2 or 3 entries and whose action has no
+// `quat` entry -- PusherObstacle-v0; rl/mopa_rollouts.py:91-98,684-690): components below n_cart = clip(site + action_range * ac, box),
+// the others = the site's own.  A product, then a sum (no contraction: the numpy expression, bit for bit); np.clip's comparisons.
+MOPA_D V3 ik_target_pos(const V3 site, const double *__restrict__ a, int n_cart, double action_range, const double (&lo)[3], const double (&hi)[3]) {
+    const double sp[3] = {site.x, site.y, site.z};
+    double out[3];
+#pragma unroll
+    for (int i = 0; i < 3; i++) {
+        out[i] = sp[i];
+        if (i < n_cart) {
+            const double t = sp[i] + action_range * a[i];
+            const double u = (t < lo[i]) ? lo[i] : t;
+            out[i] = (u > hi[i]) ? hi[i] : u;
+        }
+    }
+    return V3{out[0], out[1], out[2]};
+}
+
+__global__ __launch_bounds__(64) void k_ik_targets_pos(long long E, const double *__restrict__ site_pos, const double *__restrict__ ac,
+                                                       long long ac_stride, int n_cart, double action_range, double lo0, double lo1, double lo2,
+                                                       double hi0, double hi1, double hi2, double *__restrict__ target_cart) {
+    const long long e = (long long)blockIdx.x * 64 + threadIdx.x;
+    if (e >= E) return;
+    const double lo[3] = {lo0, lo1, lo2}, hi[3] = {hi0, hi1, hi2};
+    st3(target_cart + 3 * e, ik_target_pos(ld3(site_pos + 3 * e), ac + e * ac_stride, n_cart, action_range, lo, hi));
+}
+
+// The whole pre-step of a position-only MoPA + IK rollout call in one launch, one lane per env (`_cart2dispalcement` with target_quat = None,
+// rl/mopa_rollouts.py:683-728): site pose of qpos -> the target above -> the solve of k_ik_solve<false> on the lane's own copy of the movable
+// joints (qpos is only read) -> clip to jnt_lo / jnt_hi -> displacement = clipped - qpos[movable].  The pieces are the separate launches'
+// own routines, so the result is theirs bit for bit (k_ik_site_pose, k_ik_targets_pos, k_ik_solve<false>, then torch's maximum / minimum /
+// subtraction: a NaN stays a NaN).
+__global__ __launch_bounds__(64) void k_ik_displacement_pos(IkHdr h, const double *__restrict__ GD, const int32_t *__restrict__ GI, long long E,
+                                                            const double *__restrict__ qpos, const double *__restrict__ ac, long long ac_stride,
+                                                            int n_cart, double action_range, double lo0, double lo1, double lo2, double hi0,
+                                                            double hi1, double hi2, int max_steps, double tol, double max_update_norm,
+                                                            double progress_thresh, double reg, const double *__restrict__ jnt_lo,
+                                                            const double *__restrict__ jnt_hi, double *__restrict__ displacement,
+                                                            double *__restrict__ err_norm_out, int *__restrict__ steps_out,
+                                                            unsigned char *__restrict__ success_out) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    double *cols = reinterpret_cast<double *>(smem);                 // [kIkMaxJ][6][64]: world axis, anchor
+    double *save = cols + kIkMaxJ * 6 * 64;                          // [n_save][7][64]
+    const int lane = threadIdx.x;
+    const long long e0 = (long long)blockIdx.x * 64 + lane;
+    const bool in_range = e0 < E;
+    const long long e = in_range ? e0 : E - 1;      // (lanes behind the last env walk its row and write nothing)
+    const double *row = qpos + e * h.nq;
+    V3 psite{0.0, 0.0, 0.0};
+    double smat[9];
+    ik_site_walk(h, GD, GI, row, save, lane, psite, smat);
+    const double lo[3] = {lo0, lo1, lo2}, hi[3] = {hi0, hi1, hi2};
+    const V3 tgt = ik_target_pos(psite, ac + e * ac_stride, n_cart, action_range, lo, hi);
+    int steps = max_steps - 1, success = 0;
+    double err_norm = 0.0;
+    double qj[kIkMaxJ];
+#pragma unroll
+    for (int k = 0; k < kIkMaxJ; k++) qj[k] = (k < h.n_joints) ? row[GI[h.o_col_adr + k]] : 0.0;
+    ik_solve_lane<false>(h, GD, GI, row, qj, tgt, Q4{1.0, 0.0, 0.0, 0.0}, 0.0, max_steps, tol, max_update_norm, progress_thresh, reg, cols, save,
+                         lane, in_range, err_norm, steps, success);
+    if (in_range) {
+#pragma unroll
+        for (int k = 0; k < kIkMaxJ; k++)
+            if (k < h.n_joints) {
+                const double u = (qj[k] < jnt_lo[k]) ? jnt_lo[k] : qj[k];
+                const double c = (u > jnt_hi[k]) ? jnt_hi[k] : u;
+                displacement[e * h.n_joints + k] = c - row[GI[h.o_col_adr + k]];
+            }
+        if (err_norm_out) err_norm_out[e] = err_norm;
+        if (steps_out) steps_out[e] = steps;
+        if (success_out) success_out[e] = (unsigned char)success;
+    }
 }
 
 extern "C" int mopa_ik_create(const MopaIkDesc *desc, MopaIk **out) {
@@ -480,6 +586,49 @@ extern "C" int mopa_ik_targets_batch(MopaIk *ik, int64_t E, const double *site_p
     hipLaunchKernelGGL(k_ik_targets, dim3((unsigned)((E + 63) / 64)), dim3(64), 0, (hipStream_t)stream, (long long)E, site_pos_dev, site_mat_dev, ac_dev,
                        (long long)ac_stride, action_range, world_lo[0], world_lo[1], world_lo[2], world_hi[0], world_hi[1], world_hi[2],
                        target_cart_dev, target_quat_dev);
+    HIP_TRY(hipGetLastError());
+    return MOPA_OK;
+}
+
+static int ik_pos_action_args(const MopaIk *ik, int64_t E, int64_t ac_stride, int32_t n_cart) {
+    if (!ik) return fail(MOPA_ERR_INVALID_ARG, "null ik");
+    if (E < 0) return fail(MOPA_ERR_INVALID_ARG, "negative E");
+    if (n_cart < 2 || n_cart > 3) return fail(MOPA_ERR_INVALID_ARG, "n_cart must be 2 or 3 (the entries of the env's world box)");
+    if (ac_stride < n_cart) return fail(MOPA_ERR_INVALID_ARG, "an action row shorter than n_cart");
+    return MOPA_OK;
+}
+
+extern "C" int mopa_ik_targets_pos_batch(MopaIk *ik, int64_t E, const double *site_pos_dev, const double *ac_dev, int64_t ac_stride,
+                                         int32_t n_cart, double action_range, const double *world_lo, const double *world_hi,
+                                         double *target_cart_dev, void *stream) {
+    if (const int rc = ik_pos_action_args(ik, E, ac_stride, n_cart)) return rc;
+    if (!site_pos_dev || !ac_dev || !world_lo || !world_hi || !target_cart_dev) return fail(MOPA_ERR_INVALID_ARG, "null argument");
+    if (E == 0) return MOPA_OK;
+    ON_DEVICE(ik->device);
+    const double lo2 = n_cart > 2 ? world_lo[2] : 0.0, hi2 = n_cart > 2 ? world_hi[2] : 0.0;
+    hipLaunchKernelGGL(k_ik_targets_pos, dim3((unsigned)((E + 63) / 64)), dim3(64), 0, (hipStream_t)stream, (long long)E, site_pos_dev, ac_dev,
+                       (long long)ac_stride, (int)n_cart, action_range, world_lo[0], world_lo[1], lo2, world_hi[0], world_hi[1], hi2, target_cart_dev);
+    HIP_TRY(hipGetLastError());
+    return MOPA_OK;
+}
+
+extern "C" int mopa_ik_displacement_pos_batch(MopaIk *ik, int64_t E, const double *qpos_dev, const double *ac_dev, int64_t ac_stride, int32_t n_cart,
+                                              double action_range, const double *world_lo, const double *world_hi, int32_t max_steps, double tol,
+                                              double max_update_norm, double progress_thresh, double reg_strength, const double *jnt_lo_dev,
+                                              const double *jnt_hi_dev, double *displacement_dev, double *err_norm_dev, int32_t *steps_dev,
+                                              uint8_t *success_dev, void *stream) {
+    if (const int rc = ik_pos_action_args(ik, E, ac_stride, n_cart)) return rc;
+    if (max_steps <= 0) return fail(MOPA_ERR_INVALID_ARG, "max_steps <= 0");
+    if (!qpos_dev || !ac_dev || !world_lo || !world_hi || !jnt_lo_dev || !jnt_hi_dev || !displacement_dev) return fail(MOPA_ERR_INVALID_ARG, "null argument");
+    if (!(reg_strength > 0.0)) return fail(MOPA_ERR_UNSUPPORTED, "regularization_strength must be > 0 (the reference always regularises: inverse_kinematics.py:113-115)");
+    if (E == 0) return MOPA_OK;
+    ON_DEVICE(ik->device);
+    const size_t lds = ((size_t)kIkMaxJ * 6 * 64 + (size_t)std::max(ik->hdr.n_save, 1) * 7 * 64) * sizeof(double);
+    const double lo2 = n_cart > 2 ? world_lo[2] : 0.0, hi2 = n_cart > 2 ? world_hi[2] : 0.0;
+    hipLaunchKernelGGL(k_ik_displacement_pos, dim3((unsigned)((E + 63) / 64)), dim3(64), lds, (hipStream_t)stream, ik->hdr, ik->d_dbl, ik->d_int,
+                       (long long)E, qpos_dev, ac_dev, (long long)ac_stride, (int)n_cart, action_range, world_lo[0], world_lo[1], lo2, world_hi[0],
+                       world_hi[1], hi2, (int)max_steps, tol, max_update_norm, progress_thresh, reg_strength, jnt_lo_dev, jnt_hi_dev,
+                       displacement_dev, err_norm_dev, steps_dev, success_dev);
     HIP_TRY(hipGetLastError());
     return MOPA_OK;
 }

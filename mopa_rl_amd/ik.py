@@ -84,6 +84,69 @@ class BatchIK:
                                                     lo, hi, _ptr(cart), _ptr(quat), _stream_handle(stream)))
         return cart, quat
 
+    @staticmethod
+    def _check_pos_action(ac, E, n_cart):
+        torch = _torch()
+        if n_cart not in (2, 3):
+            raise _lib.MopaError("n_cart must be 2 or 3 (len(env.min_world_size))")
+        if ac.dim() != 2 or ac.shape[0] != E or ac.shape[1] < n_cart or ac.stride(1) != 1 or ac.dtype != torch.float64 or not ac.is_cuda:
+            raise _lib.MopaError(f"ac must be a float64 GPU tensor [E, >= {n_cart}] with unit column stride")
+
+    def targets_pos(self, site_pos, ac, n_cart: int, action_range: float, world_lo, world_hi, stream=None):
+        """The position-only IK problem of the MoPA + IK action space (an env whose world box has `n_cart` = 2 or 3 entries and whose
+        action carries no quaternion: PusherObstacle-v0, rl/mopa_rollouts.py:91-98,684-690) in ONE launch: target_cart [E,3] with
+        components below n_cart = clip(site_pos + action_range * ac, world box), the others = the site's own.  ac [E, >= n_cart];
+        world_lo / world_hi: n_cart floats each."""
+        torch = _torch()
+        E = site_pos.shape[0]
+        self._check_pos_action(ac, E, n_cart)
+        if site_pos.dtype != torch.float64 or not site_pos.is_cuda or not site_pos.is_contiguous() or tuple(site_pos.shape) != (E, 3):
+            raise _lib.MopaError("site_pos must be a contiguous float64 GPU tensor [E, 3]")
+        if len(world_lo) != n_cart or len(world_hi) != n_cart:
+            raise _lib.MopaError("world_lo / world_hi must hold n_cart entries")
+        cart = torch.empty(E, 3, dtype=torch.float64, device=site_pos.device)
+        lo = (C.c_double * 3)(*[float(x) for x in world_lo])
+        hi = (C.c_double * 3)(*[float(x) for x in world_hi])
+        _lib.check(_lib.lib().mopa_ik_targets_pos_batch(self._h, E, _ptr(site_pos), _ptr(ac), int(ac.stride(0)), int(n_cart), float(action_range),
+                                                        lo, hi, _ptr(cart), _stream_handle(stream)))
+        return cart
+
+    def displacement_pos(self, qpos, ac, n_cart: int, action_range: float, world_lo, world_hi, lo, hi, max_steps: int = 100,
+                         tol: float = 1e-2, max_update_norm: float = 2.0, progress_thresh: float = 20.0,
+                         regularization_strength: float = 3e-2, want_result: bool = False, stream=None):
+        """`MoPARolloutRunner._cart2dispalcement` without a quaternion for E envs in ONE launch, one lane per env: site pose of qpos ->
+        `targets_pos` -> the position-only solve on a private copy of the row (qpos is not written) -> clip of the movable joints
+        to lo / hi ([n_joints] float64 GPU tensors) -> displacement [E, n_joints] = clipped - qpos[movable].  Bit for bit the
+        composition site_pose -> targets_pos -> solve -> clamp -> subtract.  max_steps / tol default to the rollouts' call
+        (rl/mopa_rollouts.py:701-709).  want_result: also return IKResult(qpos=None, err_norm, steps, success)."""
+        torch = _torch()
+        E = qpos.shape[0]
+        self._check_pos_action(ac, E, n_cart)
+        if qpos.dtype != torch.float64 or not qpos.is_cuda or not qpos.is_contiguous() or qpos.dim() != 2 or qpos.shape[1] != self.nq:
+            raise _lib.MopaError(f"qpos must be a contiguous float64 GPU tensor of shape [E, {self.nq}]")
+        nj = len(self.joint_ids)
+        for t, name in ((lo, "lo"), (hi, "hi")):
+            if t.dtype != torch.float64 or not t.is_cuda or not t.is_contiguous() or tuple(t.shape) != (nj,):
+                raise _lib.MopaError(f"{name} must be a contiguous float64 GPU tensor [{nj}]")
+        if len(world_lo) != n_cart or len(world_hi) != n_cart:
+            raise _lib.MopaError("world_lo / world_hi must hold n_cart entries")
+        disp = torch.empty(E, nj, dtype=torch.float64, device=qpos.device)
+        err = steps = succ = None
+        if want_result:
+            err = torch.empty(E, dtype=torch.float64, device=qpos.device)
+            steps = torch.empty(E, dtype=torch.int32, device=qpos.device)
+            succ = torch.empty(E, dtype=torch.uint8, device=qpos.device)
+        wlo = (C.c_double * 3)(*[float(x) for x in world_lo])
+        whi = (C.c_double * 3)(*[float(x) for x in world_hi])
+        opt = lambda t: _ptr(t) if t is not None else None
+        _lib.check(_lib.lib().mopa_ik_displacement_pos_batch(
+            self._h, E, _ptr(qpos), _ptr(ac), int(ac.stride(0)), int(n_cart), float(action_range), wlo, whi, int(max_steps), float(tol),
+            float(max_update_norm), float(progress_thresh), float(regularization_strength), _ptr(lo), _ptr(hi), _ptr(disp), opt(err), opt(steps),
+            opt(succ), _stream_handle(stream)))
+        if want_result:
+            return disp, IKResult(qpos=None, err_norm=err, steps=steps, success=succ)
+        return disp
+
     def solve(self, qpos, target_pos, target_quat=None, max_steps: int = 100, rot_weight: float = 1.0, tol: float = 1e-14,
               max_update_norm: float = 2.0, progress_thresh: float = 20.0, regularization_strength: float = 3e-2, stream=None) -> IKResult:
         """qpos [E, nq] (updated in place), target_pos [E, 3], target_quat [E, 4] wxyz or None: contiguous float64 GPU tensors.

@@ -10,7 +10,8 @@ the SMDP reward `sum_i gamma^i r_i` and `intra_steps` are accumulated (:152-199)
 the current reward (:303-334).  Counters `mp / rl / interpolation / mp_fail / approximate / invalid` are kept per env.
 
 Action spaces: joint-space MoPA-SAC, and MoPA + IK (`use_ik_target`: Cartesian displacement + rotation quaternion of the
-ik_target site, turned into a joint displacement by the batched damped-LS IK -- BASELINE config 5), and `discrete_action`
+ik_target site, turned into a joint displacement by the batched damped-LS IK -- BASELINE config 5; on an env with a 2-D world
+box, PusherObstacle-v0, the 2 Cartesian entries alone and a position-only IK -- scripts/2d/mopa_ik.sh), and `discrete_action`
 (the policy's `ac_type` head routes a step, :86-88,106-111,349).  Envs: the three Sawyer
 obstacle envs (7 arm entries per action, Lift adds the gripper entry, which a planner step applies at
 the last waypoint of its path, :163-167) and PusherObstacle-v0 (4 joints, joint0 UNLIMITED: query endpoints are wrapped into
@@ -137,6 +138,17 @@ class RolloutConfig:
     ik_target: str = "grip_site"
     min_world_size: tuple = (-1.2, -1.2, 0.0)        # env/sawyer/sawyer.py:52-53
     max_world_size: tuple = (1.2, 1.2, 2.0)
+    # (the Cartesian width of the IK action is len(min_world_size), rl/trainer.py:93-110: 3 + a rotation quaternion for the Sawyer envs; a
+    #  2-D world box -- PusherObstacle-v0 -- makes it 2 entries and NO quaternion, and the IK position-only: scripts/2d/mopa_ik.sh)
+
+    @property
+    def n_cart(self) -> int:
+        return len(self.min_world_size)
+
+    @property
+    def ik_has_quat(self) -> bool:
+        """rl/trainer.py:100-104: the action has its `quat` entry only when the world box is 3-D"""
+        return len(self.min_world_size) == 3
 
     @classmethod
     def for_env(cls, env_name: str, **over):
@@ -148,8 +160,15 @@ class RolloutConfig:
         kw = dict(omega=sp.omega, action_range=sp.action_range, ac_scale=sp.ac_scale, num_trials=sp.num_trials, step_size=sp.step_size,
                   timelimit=sp.timelimit, simple_planner_timelimit=sp.simple_planner_timelimit, range=sp.range,
                   simple_planner_range=sp.simple_planner_range, joint_margin=sp.joint_margin, contact_threshold=sp.contact_threshold)
+        if over.get("use_ik_target"):
+            kw.update(IK_ENV_DEFAULTS.get(env_name, {}))
         kw.update(over)
         return cls(**kw)
+
+
+# what `use_ik_target` reads from the env and its launch script where they differ from the Sawyer defaults of RolloutConfig:
+# PusherObstacle-v0 (scripts/2d/mopa_ik.sh: --ik_target fingertip; env/pusher/pusher_obstacle.py:34-35: a 2-D world box)
+IK_ENV_DEFAULTS = {"PusherObstacle-v0": dict(ik_target="fingertip", min_world_size=(-0.41, -0.41), max_world_size=(0.41, 0.41))}
 
 
 def reuse_transitions(out, cfg, n_arm: int, rng, max_reuse_data: int = 30, grip_qpos_idx=None):
@@ -389,14 +408,24 @@ def ik_targets_torch(site_pos, site_mat, ac, action_range, world_lo, world_hi):
     return target_cart, target_quat
 
 
-def sit_out_action(ac, alive, use_ik_target: bool):
+def ik_targets_pos_np(site_pos, ac, n_cart: int, action_range: float, world_lo, world_hi):
+    """The position-only IK target in the reference's own numpy words (rl/mopa_rollouts.py:91-98, then :684-690 for a 2-D world box):
+    the checker of `BatchIK.targets_pos` (bit for bit).  site_pos [E, 3], ac [E, >= n_cart] -> target_cart [E, 3]."""
+    site_pos, ac = np.asarray(site_pos, dtype=np.float64), np.asarray(ac, dtype=np.float64)
+    lo, hi = np.asarray(world_lo, dtype=np.float64), np.asarray(world_hi, dtype=np.float64)
+    cart = np.clip(site_pos[:, :n_cart] + action_range * ac[:, :n_cart], lo, hi)
+    return np.concatenate((cart, site_pos[:, n_cart:]), axis=1)
+
+
+def sit_out_action(ac, alive, use_ik_target: bool, has_quat: bool = True):
     """The action `run_episode` hands to `agent_step`: the policy's rows for the envs still in their episode, a neutral row for the
     envs that sit out.  Neutral is all zeros -- except, with `use_ik_target`, the rotation entries ac[3:7]: `k_ik_targets` divides them
     by their norm as the reference does (rl/mopa_rollouts.py:696), so they are the identity quaternion (1, 0, 0, 0); a zero row would
-    make the IK target, the joint displacement and from there `env.qpos` of the env NaN."""
+    make the IK target, the joint displacement and from there `env.qpos` of the env NaN.  An IK action without a quaternion
+    (`has_quat=False`: a 2-D world box, RolloutConfig.ik_has_quat) has nothing to divide by: its neutral row is all zeros too."""
     torch = _torch()
     neutral = torch.zeros_like(ac, dtype=torch.float64)
-    if use_ik_target:
+    if use_ik_target and has_quat:
         neutral[:, 3] = 1.0
     return torch.where(alive[:, None], ac.to(torch.float64), neutral).contiguous()
 
@@ -482,7 +511,13 @@ class BatchMoPARollout:
             # joints carry +-3.14 there, env/base.py:85-86) -- only the arm entries are read back
             self._ik_lo = torch.tensor(f.qpos_min[self.arm], dtype=f64, device=dev)
             self._ik_hi = torch.tensor(f.qpos_max[self.arm], dtype=f64, device=dev)
-        self.ac_dim = (7 if self.cfg.use_ik_target else self.n) + (env.action_dim - self.n)
+            if self.cfg.n_cart not in (2, 3) or len(self.cfg.max_world_size) != self.cfg.n_cart:
+                raise _lib.MopaError("min_world_size / max_world_size must both hold 2 or 3 entries")
+            if not self.cfg.ik_has_quat and env.action_dim != self.n:
+                raise NotImplementedError("a position-only IK action with further action entries (no such env in the reference)")
+        # Cartesian entries of the IK action: 3 + the rotation quaternion, or the 2 of a 2-D world box without one
+        self._ik_ac = (self.cfg.n_cart + (4 if self.cfg.ik_has_quat else 0)) if self.cfg.use_ik_target else 0
+        self.ac_dim = (self._ik_ac if self.cfg.use_ik_target else self.n) + (env.action_dim - self.n)
         self._pend_ob = torch.zeros(self.E, env.obs_dim, dtype=f64, device=dev)      # ob / ac of the step a busy env is in
         self._pend_ac = torch.zeros(self.E, self.ac_dim, dtype=f64, device=dev)
         self._ac_type_in = torch.zeros(self.E, dtype=torch.int64, device=dev)      # discrete_action: this call's ac_type / that of a pending step
@@ -517,6 +552,11 @@ class BatchMoPARollout:
         closed-form quaternion used here, to the float32 rounding of the matrix -- a 1e-7 effect on the target.)"""
         torch = _torch()
         cfg = self.cfg
+        if not cfg.ik_has_quat:
+            # a 2-D world box (PusherObstacle-v0): no `quat` entry, target_quat=None, the site's own z appended to the 2-D target
+            # (:684-699) -- the whole pre-step in one launch (`BatchIK.displacement_pos`; cur is read, not written)
+            return self.ik.displacement_pos(cur.contiguous(), ac, cfg.n_cart, cfg.action_range, cfg.min_world_size, cfg.max_world_size,
+                                            self._ik_lo, self._ik_hi, max_steps=100, tol=1e-2)
         site_pos, site_mat = self.ik.site_pose(cur.contiguous())
         # (one launch; the module's `ik_targets_torch` is the array-operation form it replaced -- ~70 elementwise launches per call -- kept as
         #  the checker of tests/test_gpu_ik.py)
@@ -670,7 +710,7 @@ class BatchMoPARollout:
         if cfg.use_ik_target:
             # MoPA + IK: the action is Cartesian; its joint displacement decides planner / direct and IS the direct action
             a = self.ik_displacement(ac, cur)
-            extra_ac = ac_tr[:, 7:7 + (env.action_dim - n)]
+            extra_ac = ac_tr[:, self._ik_ac:self._ik_ac + (env.action_dim - n)]
             mark("ik")
         else:
             a = ac[:, :n].contiguous()
@@ -1276,7 +1316,7 @@ class BatchMoPARollout:
             while True:
                 got = policy(env.obs.clone(), is_train=is_train, random_exploration=random_exploration)
                 ac, ac_type = got if cfg.discrete_action else (got, None)
-                ac = sit_out_action(ac, alive, cfg.use_ik_target)
+                ac = sit_out_action(ac, alive, cfg.use_ik_target, cfg.ik_has_quat)
                 if ac_type is not None:
                     ac_type = torch.where(alive, ac_type.reshape(-1).to(torch.int64), torch.zeros(E, dtype=torch.int64, device=dev))
                 before = {k: self.counters[k].clone() for k in COUNTERS}

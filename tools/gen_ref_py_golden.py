@@ -389,6 +389,27 @@ def flat_ob(ob):
 # ------------------------------------------------------------------------------------------------------------------
 ROLLOUT_PARAMS = dict(timelimit=0.15, max_nodes=512, max_path=128, seed=1234, max_episode_steps=14, num_trials=10)
 COUNTERS = ("mp", "rl", "interpolation", "mp_fail", "approximate", "invalid")
+# scripts/2d/mopa_ik.sh: MoPA-SAC on PusherObstacle-v0 with --use_ik_target True --ik_target fingertip --omega 0.1 --action_range 0.1
+PUSHER_IK_CONFIG = dict(ik_target="fingertip", omega=0.1, action_range=0.1)
+
+
+def tame_invalid_start(agent, env, AC, e, t):
+    """A direct step of the IK action space executes displacement / omega unchecked, so it can end inside an obstacle.  A PLANNER step from
+    such a state is undefined in the reference: with `use_ik_target` the target is the current state, the invalid-target back-off divides
+    by |curr - target| = 0 (rl/mopa_rollouts.py:141-142) and the NaN target goes on into the env.  The scripted action of a step that starts
+    from an invalid state is therefore scaled down to a short, direct one -- recorded in `ac` like every other action."""
+    q = env.sim.data.qpos
+    assert abs(q[0]) <= 3.14, f"env {e}, step {t}: joint0 beyond the seam -- the reference's next step is undefined; choose other actions"
+    if not agent.isValidState(q.copy()):
+        AC[e, t] *= 0.05
+
+
+def set_module_config(cfg):
+    """`MoPARolloutRunner._cart2dispalcement` reads a bare `config` in its 2-D branch (rl/mopa_rollouts.py:684-690: `config.ik_target`;
+    everywhere else the method says `self._config`): a NameError as the reference stands.  The name is supplied as a module global holding
+    the runner's own config -- what the line means --; the reference's code runs unmodified."""
+    import rl.mopa_rollouts as ref_mr
+    ref_mr.config = cfg
 
 
 def rollout_actions(E, T, n_ac, rng):
@@ -424,14 +445,23 @@ def gen_rollout(env_name="SawyerPushObstacle-v0", tag="push", E=32, T=5, reuse=F
     P = ROLLOUT_PARAMS
     if env_name == "PusherObstacle-v0":
         P = dict(P, timelimit=0.5)            # the cluttered Pusher scene: 1000 iterations, so that some blocked lines get planned
-    cfg = make_config(env_name, timelimit=P["timelimit"], reuse_data=reuse, num_trials=P["num_trials"], use_ik_target=ik,
-                      discrete_action=discrete)
     pusher = env_name == "PusherObstacle-v0"
+    cfg = make_config(env_name, timelimit=P["timelimit"], reuse_data=reuse, num_trials=P["num_trials"], use_ik_target=ik,
+                      discrete_action=discrete, **(PUSHER_IK_CONFIG if (pusher and ik) else {}))
     n_ac = 8 if env_name == "SawyerLiftObstacle-v0" else (4 if pusher else 7)
     agent, pi = make_agent(env_name, cfg, ac_dim=n_ac)
     st = Streams(agent, E, P["seed"], P["max_nodes"], P["max_path"])
     rng = np.random.default_rng(11)
-    if ik:
+    n_seam = E // 2 if pusher else 0
+    if ik and pusher:
+        # scripts/2d/mopa_ik.sh: a 2-D Cartesian displacement of the fingertip site and nothing else (rl/trainer.py:93-110: the `quat` entry
+        # exists for a 3-D world box only).  Small steps (direct actions) and long reaches (joint displacements beyond omega: planner steps).
+        # No starts next to the seam of joint0: a direct step that carries joint0 beyond +-3.14 leaves a state the planner calls invalid, and
+        # every later step is a planner step from it (the clip to +-3.14 alone exceeds omega) -- see tame_invalid_start
+        set_module_config(cfg)
+        AC = rng.uniform(-1, 1, size=(E, T, 2)) * rng.choice([0.05, 0.3, 1.0], size=(E, T, 1))
+        n_seam = 0
+    elif ik:
         # MoPA + IK action space (rl/trainer.py:93-125): Cartesian displacement (3) + rotation quaternion (4) in [-1, 1]
         AC = rng.uniform(-1, 1, size=(E, T, 7))
         AC[:, :, :3] *= rng.choice([0.05, 0.3, 1.0], size=(E, T, 1))           # small steps (direct) and long reaches (planner)
@@ -457,7 +487,7 @@ def gen_rollout(env_name="SawyerPushObstacle-v0", tag="push", E=32, T=5, reuse=F
     for e in range(E):
         env = make_ref_env(env_name, seed=100 + e, max_episode_steps=P["max_episode_steps"])
         state = {"t": -1}
-        if pusher and e < E // 2:
+        if pusher and e < n_seam:
             def reset_at_seam(env=env, arm=seam_starts[e], orig=env.reset):
                 orig()
                 q = env.sim.data.qpos.copy()
@@ -482,6 +512,9 @@ def gen_rollout(env_name="SawyerPushObstacle-v0", tag="push", E=32, T=5, reuse=F
             if out["ob"] is None:
                 out["ob"], out["ob_next"] = np.zeros((E, T, len(fo))), np.zeros((E, T, len(fo)))
             out["ob"][e, t] = fo
+            if ik and pusher:
+                tame_invalid_start(agent, env, AC, e, t)
+                return OrderedDict([("default", AC[e, t].copy())]), None, None
             if ik:
                 return OrderedDict([("default", AC[e, t, :3].copy()), ("quat", AC[e, t, 3:].copy())]), None, None
             a = OrderedDict(default=AC[e, t].copy())
@@ -540,6 +573,8 @@ def gen_rollout(env_name="SawyerPushObstacle-v0", tag="push", E=32, T=5, reuse=F
                    x_intra=np.array([x[6] for x in extra]), x_ob_next=np.array([x[7] for x in extra]))
     if discrete:
         out["ac_type"] = AC_TYPE
+    if ik and pusher:
+        out.update(omega=np.array(cfg.omega), action_range=np.array(cfg.action_range))
     save(f"ref_py_rollout_{tag}{'_reuse' if reuse else ''}{'_ik' if ik else ''}{'_discrete' if discrete else ''}.npz",
          params=np.array([P["timelimit"], P["max_nodes"], P["max_path"], P["seed"], P["max_episode_steps"], P["num_trials"]]), **out)
 
@@ -561,14 +596,20 @@ def gen_episode(env_name="SawyerPushObstacle-v0", tag="push", E=24, discrete=Fal
     from rl.mopa_rollouts import MoPARolloutRunner
     ref_util_env.np = refshim.NumpyCompat()
     P = ROLLOUT_PARAMS
+    pusher = env_name == "PusherObstacle-v0"        # (with ik=True only: the 2-D, position-only action of scripts/2d/mopa_ik.sh, as in gen_rollout)
+    if pusher:
+        P = dict(P, timelimit=0.5)
     cfg = make_config(env_name, timelimit=P["timelimit"], num_trials=P["num_trials"], discrete_action=discrete, stochastic_eval=False,
-                      use_ik_target=ik)
-    n_ac = 8 if env_name == "SawyerLiftObstacle-v0" else 7
+                      use_ik_target=ik, **(PUSHER_IK_CONFIG if (pusher and ik) else {}))
+    n_ac = 8 if env_name == "SawyerLiftObstacle-v0" else (4 if pusher else 7)
     agent, pi = make_agent(env_name, cfg, ac_dim=n_ac)
     st = Streams(agent, E, P["seed"], P["max_nodes"], P["max_path"])
     rng = np.random.default_rng(23)
     T = P["max_episode_steps"]                      # an agent step takes at least one env step
-    if ik:
+    if ik and pusher:
+        set_module_config(cfg)
+        AC = rng.uniform(-1, 1, size=(E, T, 2)) * rng.choice([0.05, 0.3, 1.0], size=(E, T, 1))
+    elif ik:
         from env.inverse_kinematics import qpos_from_site_pose
         # gen_rollout's recipe: Cartesian displacement (3) + rotation quaternion (4) in [-1, 1]
         AC = rng.uniform(-1, 1, size=(E, T, 7))
@@ -593,7 +634,7 @@ def gen_episode(env_name="SawyerPushObstacle-v0", tag="push", E=24, discrete=Fal
         env.get_contact_force = lambda: 0.0
         env.color_agent = env.reset_color_agent = lambda: None          # geom_rgba only (rendering)
         state = {"t": -1}
-        at_hole, inside = ik and e in IK_HOLE_ENVS, ik and e in IK_INSIDE_ENVS
+        at_hole, inside = ik and not pusher and e in IK_HOLE_ENVS, ik and not pusher and e in IK_INSIDE_ENVS
         if ik:
             def reset_staggered(env=env, e=e, over_hole=at_hole or inside, inside=inside, orig=env.reset):
                 orig()
@@ -640,6 +681,9 @@ def gen_episode(env_name="SawyerPushObstacle-v0", tag="push", E=24, discrete=Fal
                     q = np.zeros(4)
                     refshim.mju_mulQuat(q, inv, cur)
                     AC[e, t, 3:] = q / np.abs(q).max()
+                if pusher:
+                    tame_invalid_start(agent, env, AC, e, t)
+                    return OrderedDict([("default", AC[e, t].copy())]), None, None
                 return OrderedDict([("default", AC[e, t, :3].copy()), ("quat", AC[e, t, 3:].copy())]), None, None
             a = OrderedDict(default=AC[e, t].copy())
             if discrete:
@@ -673,6 +717,8 @@ def gen_episode(env_name="SawyerPushObstacle-v0", tag="push", E=24, discrete=Fal
           "pulled back", int(out["pulled_back"].sum()))
     if discrete:
         out["ac_type"] = AC_TYPE
+    if ik and pusher:
+        out.update(omega=np.array(cfg.omega), action_range=np.array(cfg.action_range))
     save(f"ref_py_episode_{tag}{'_ik' if ik else ''}{'_discrete' if discrete else ''}.npz",
          params=np.array([P["timelimit"], P["max_nodes"], P["max_path"], P["seed"], P["max_episode_steps"], P["num_trials"]]), **out)
 
@@ -741,6 +787,53 @@ def gen_ik():
         out.update({f"{tag}_qpos": q_in, f"{tag}_target_pos": tp, f"{tag}_target_quat": tq, f"{tag}_use_quat": use_q,
                     f"{tag}_qpos_out": q_out, f"{tag}_err_norm": en, f"{tag}_steps": st, f"{tag}_success": su})
     save("ref_py_ik.npz", **out)
+
+
+def gen_ik_pusher():
+    """48 position-only `qpos_from_site_pose` problems on the reference Pusher env as `_cart2dispalcement` calls it without a `quat`
+    entry (site fingertip, the four robot joints, target_quat=None, max_steps=100, tol=1e-2): a planar chain of 4 hinges, joint0
+    unlimited, the site on a jointless leaf body.  Starts: 16 next to the seam of joint0 (pusher_seam_starts), 32 anywhere.  Targets, by
+    k % 3: already there (inside tol: 0 steps), in reach (a few centimetres off the site), out of reach (beyond the stretched arm:
+    never converges).  The site's own z is the target's, as the runner appends it (rl/mopa_rollouts.py:684-690)."""
+    from env.inverse_kinematics import qpos_from_site_pose
+    rng = np.random.default_rng(7)
+    pi = planner_inputs("PusherObstacle-v0")
+    env = make_ref_env_pusher(seed=3)
+    env.reset()
+    K, site = 48, "fingertip"
+    nq = env.sim.model.nq
+    seam = pusher_seam_starts(pi, rng, 16)
+    q_in, tp = np.zeros((K, nq)), np.zeros((K, 3))
+    q_out, en, st, su = np.zeros((K, nq)), np.zeros(K), np.zeros(K, dtype=np.int64), np.zeros(K, dtype=np.int64)
+    for k in range(K):
+        env.reset()
+        q = env.sim.data.qpos.copy()
+        if k < 16:
+            q[:4] = seam[k]
+        else:
+            q[0], q[1:4] = rng.uniform(-3.0, 3.0), rng.uniform(-2.5, 2.5, 3)
+        env.set_state(q, env.sim.data.qvel.copy())
+        p = env.sim.data.get_site_xpos(site).copy()
+        kind = k % 3
+        if kind == 0:
+            target_pos = p + np.r_[rng.uniform(-1, 1, 2) * 0.004, 0.0]
+        elif kind == 1:
+            target_pos = p + np.r_[rng.uniform(-1, 1, 2) * (0.02, 0.06)[(k // 3) % 2], 0.0]
+        else:
+            ang = rng.uniform(-np.pi, np.pi)
+            target_pos = np.r_[rng.uniform(0.7, 0.9) * np.cos(ang), rng.uniform(0.7, 0.9) * np.sin(ang), p[2]]
+        q_in[k], tp[k] = q, target_pos
+        r = qpos_from_site_pose(env, site, target_pos=target_pos, target_quat=None, joint_names=env.robot_joints, max_steps=100, tol=1e-2)
+        q_out[k], en[k], st[k], su[k] = np.array(r.qpos), r.err_norm, r.steps, int(r.success)
+    print(f"  ik[pusher]: success {int(su.sum())}/{K}  steps {st.tolist()}")
+    save("ref_py_ik_pusher.npz", pusher_qpos=q_in, pusher_target_pos=tp, pusher_kind=np.arange(K) % 3, pusher_qpos_out=q_out,
+         pusher_err_norm=en, pusher_steps=st, pusher_success=su)
+
+
+def gen_pusher_ik():
+    gen_ik_pusher()
+    gen_rollout("PusherObstacle-v0", "pusher", E=32, T=5, ik=True)
+    gen_episode("PusherObstacle-v0", "pusher", E=24, ik=True)
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -927,7 +1020,8 @@ def gen_rollout_pusher():
     gen_rollout("PusherObstacle-v0", "pusher", E=24, T=5)
 
 
-SECTIONS = OrderedDict(host=gen_host, agent=gen_agent, rollout=gen_rollouts, ik=gen_ik, env=gen_env, env_pusher=gen_env_pusher, rollout_pusher=gen_rollout_pusher, pusher_pid=gen_pusher_pid, episode=gen_episodes)
+SECTIONS = OrderedDict(host=gen_host, agent=gen_agent, rollout=gen_rollouts, ik=gen_ik, env=gen_env, env_pusher=gen_env_pusher, rollout_pusher=gen_rollout_pusher, pusher_pid=gen_pusher_pid, episode=gen_episodes,
+                       pusher_ik=gen_pusher_ik)
 
 
 def main():
