@@ -1187,7 +1187,7 @@ __device__ __forceinline__ void ct_force_readout(const CtHdr &ch, const double *
 // mode 1: n_steps sub-steps towards the given ctrl rows [E, nd].  qvel rows are [nd + 6].
 // ch.cf (optional, cf.force != nullptr): the contact-force readout of the last sub-step, for the envs that ran one -- in the header the
 // kernel reads through scalar loads anyway, so the kernel's arguments (and what it keeps in registers over the sub-step loop) stay as they were.
-template <int KIND, int SOLVER>
+template <int SOLVER>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void k_env_dyn_ct(
     EnvHdr h, const DynHdr *__restrict__ dhp, const CtHdr *__restrict__ chp, const double *__restrict__ GD, const int32_t *__restrict__ GI,
     const double *__restrict__ DD, const double *__restrict__ FT, const double *__restrict__ PR, long long E,
@@ -1213,12 +1213,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void
     const unsigned flags = move_mask ? move_mask[e] : 1u;
     if (flags & 2u) live = false;
     double *row = qpos + e * h.nq;
-    for (int i = 0; i < dh.nd; i++) {
-        DLW(DL_Q + i) = row[dh.qadr[i]];
-        DLW(DL_V + i) = qvel[e * dh.nv + i];
-        DLW(DL_LAG + i) = bias_lag[e * dh.nd + i];
-        DLW(DL_CTRL + i) = 0.0;
-    }
+    // (all 16 lanes of an env's group fill its columns and form its command with the same values; lane 0 records it)
+    dyn_cols_load<ST>(dh, W, e, row, qvel, bias_lag);
     CtObj o;
     const bool has_obj = ch.obj_qadr >= 0;       // (false: the contact-free form -- stage A's smooth dynamics in this kernel's 16-lane mapping)
     o.p = V3{0.0, 0.0, 0.0}; o.q = Q4{1.0, 0.0, 0.0, 0.0}; o.v = V3{0.0, 0.0, 0.0}; o.w = V3{0.0, 0.0, 0.0};
@@ -1229,6 +1225,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void
         o.w = V3{qvel[e * dh.nv + dh.nd + 3], qvel[e * dh.nv + dh.nd + 4], qvel[e * dh.nv + dh.nd + 5]};
     }
     if (mode == 0) {
+        // dyn_command's loop (mopa_dyn.inc), kept here with a fence before lane 0 records the command.  The fence ORDERS NOTHING and is
+        // no correctness requirement: the 16 lanes of a group store the same values in program order within one wave, and the kernel
+        // fences again after the loop; dyn_command in its place passes every bit-exact test.  It only holds the code generation: without
+        // it the compiler allocates the registers of the sub-step loop differently, and Lift with contacts lost 1 % (profiles/r24)
         double *prev = prev_state + e * h.n_arm;
         const bool use_prev = is_planner && has_prev[e];
         const double *act = action + e * h.adim;
@@ -1237,9 +1237,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void
             if (k < 0) continue;
             double target;
             if (k < h.n_arm) {
-                const double pv = use_prev ? prev[k] : DLW(DL_Q + i);
-                const double a = is_planner ? act[k] : act[k] * h.ac_scale;
-                target = pv + clampd(a, -h.ac_scale, h.ac_scale);
+                target = env_desired(h, use_prev ? prev[k] : DLW(DL_Q + i), act[k], is_planner, false);
                 ct_fence();
                 if (live && l == 0) prev[k] = target;
             } else target = DLW(DL_Q + i) + act[h.n_arm];
@@ -1273,11 +1271,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void
 #endif
     if (ch.cf.force) ct_force_readout<ST, SOLVER>(ch, W, l, grp, dh.nd, nwarm, live && n_steps > 0, e, ch.cf);
     if (live && l == 0) {
-        for (int i = 0; i < dh.nd; i++) {
-            row[dh.qadr[i]] = DLW(DL_Q + i);
-            qvel[e * dh.nv + i] = DLW(DL_V + i);
-            bias_lag[e * dh.nd + i] = DLW(DL_LAG + i);
-        }
+        dyn_cols_store<ST>(dh, W, e, row, qvel, bias_lag);
         if (has_obj) {
             row[ch.obj_qadr] = o.p.x; row[ch.obj_qadr + 1] = o.p.y; row[ch.obj_qadr + 2] = o.p.z;
             row[ch.obj_qadr + 3] = o.q.w; row[ch.obj_qadr + 4] = o.q.x; row[ch.obj_qadr + 5] = o.q.y; row[ch.obj_qadr + 6] = o.q.z;
@@ -1408,9 +1402,7 @@ extern "C" int mopa_env_attach_contacts(MopaEnv *env, const MopaCtDesc *d) {
     env->cf = CfOut{nullptr, nullptr, nullptr, nullptr, 0};
     env->dyn.nv = nd + (smooth_only ? 0 : 6);
     HIP_TRY(hipMemcpy(env->d_dynhdr, &env->dyn, sizeof(DynHdr), hipMemcpyHostToDevice));
-    for (const void *k : {(const void *)k_env_dyn_ct<0, 0>, (const void *)k_env_dyn_ct<1, 0>, (const void *)k_env_dyn_ct<2, 0>,
-                          (const void *)k_env_dyn_ct<0, 1>, (const void *)k_env_dyn_ct<1, 1>, (const void *)k_env_dyn_ct<2, 1>,
-                          (const void *)k_env_dyn_ct<0, 2>, (const void *)k_env_dyn_ct<1, 2>, (const void *)k_env_dyn_ct<2, 2>})
+    for (const void *k : {(const void *)k_env_dyn_ct<0>, (const void *)k_env_dyn_ct<1>, (const void *)k_env_dyn_ct<2>})
         (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLdsBytes);
     return MOPA_OK;
 }
@@ -1426,10 +1418,8 @@ extern "C" int mopa_env_set_contact_stats(MopaEnv *env, int32_t *stats_dev) {
 static int env_ct_launch(MopaEnv *env, int64_t E, int mode, int n_steps, double *qpos, double *qvel, double *bias_lag, double *prev_state,
                          uint8_t *has_prev, const double *action, int is_planner, const uint8_t *move_mask, const double *ctrl, hipStream_t st) {
     const unsigned blocks = (unsigned)((E + 3) / 4);
-    auto kern = env->hdr.kind == MOPA_ENV_PUSH ? k_env_dyn_ct<0, 0> : (env->hdr.kind == MOPA_ENV_LIFT ? k_env_dyn_ct<1, 0> : k_env_dyn_ct<2, 0>);
-    if (env->ct_solver == 1) kern = env->hdr.kind == MOPA_ENV_PUSH ? k_env_dyn_ct<0, 1> : (env->hdr.kind == MOPA_ENV_LIFT ? k_env_dyn_ct<1, 1> : k_env_dyn_ct<2, 1>);
-    if (env->ct_solver == 2) kern = env->hdr.kind == MOPA_ENV_PUSH ? k_env_dyn_ct<0, 2> : (env->hdr.kind == MOPA_ENV_LIFT ? k_env_dyn_ct<1, 2> : k_env_dyn_ct<2, 2>);
-    hipLaunchKernelGGL(kern, dim3(blocks), dim3(64), env->ct_lds, st, env->hdr, env->d_dynhdr, env->d_cthdr, env->d_dbl, env->d_int, env->d_dyn,
+    static constexpr decltype(&k_env_dyn_ct<0>) kerns[3] = {k_env_dyn_ct<0>, k_env_dyn_ct<1>, k_env_dyn_ct<2>};      // by solver (attach_contacts admits 0 .. 2)
+    hipLaunchKernelGGL(kerns[env->ct_solver], dim3(blocks), dim3(64), env->ct_lds, st, env->hdr, env->d_dynhdr, env->d_cthdr, env->d_dbl, env->d_int, env->d_dyn,
                        env->d_ct + env->ct_ft_off, env->d_ct + env->ct_pr_off, (long long)E, mode, n_steps, qpos, qvel, bias_lag, prev_state,
                        has_prev, action, is_planner, move_mask, ctrl, env->ct_stats);
     HIP_TRY(hipGetLastError());

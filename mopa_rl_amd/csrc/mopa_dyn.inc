@@ -669,13 +669,53 @@ __device__ __forceinline__ void dyn_substep(const DynHdr &dh, const double *__re
     dyn_solve_integrate<ST>(dh, DD, W, bias, A);
 }
 
+// ---- what the dynamics kernels share around the sub-steps: the column load / store (k_env_dyn, k_env_dyn4's wave 0, the contact kernel
+// k_env_dyn_ct) and mode 0's command (k_env_dyn, k_env_dyn4; k_env_dyn_ct keeps its own fenced loop around the same env_desired) ----
+// env e's Q / V / LAG columns from its qpos row and its rows of qvel / bias_lag (CTRL cleared), and back
+template <int ST = 64>
+__device__ __forceinline__ void dyn_cols_load(const DynHdr &dh, double *W, long long e, const double *row, const double *qvel, const double *bias_lag) {
+    for (int i = 0; i < dh.nd; i++) {
+        DLW(DL_Q + i) = row[dh.qadr[i]];
+        DLW(DL_V + i) = qvel[e * dh.nv + i];
+        DLW(DL_LAG + i) = bias_lag[e * dh.nd + i];
+        DLW(DL_CTRL + i) = 0.0;
+    }
+}
+template <int ST = 64>
+__device__ __forceinline__ void dyn_cols_store(const DynHdr &dh, const double *W, long long e, double *row, double *qvel, double *bias_lag) {
+    for (int i = 0; i < dh.nd; i++) {
+        row[dh.qadr[i]] = DLW(DL_Q + i);
+        qvel[e * dh.nv + i] = DLW(DL_V + i);
+        bias_lag[e * dh.nd + i] = DLW(DL_LAG + i);
+    }
+}
+// mode 0's command -- `_step`: desired_state = prev_state + clip(action [* ac_scale]) (env_desired; the Pusher has its own kernel, K8);
+// ctrl = [desired_state, gripper targets], ctrlrange-clamped, into the CTRL column.  prev / has: the env's prev_state row and
+// has_prev entry, written where `write` holds (the lanes that stand for the env and may record the command).
+template <int ST = 64>
+__device__ __forceinline__ void dyn_command(const EnvHdr &h, const DynHdr &dh, const double *__restrict__ GD, double *W, const double *act,
+                                            int is_planner, double *prev, unsigned char *has, bool write) {
+    const bool use_prev = is_planner && *has;
+#pragma unroll 1      // (runs once per env.step; rolled, the sub-step loops behind it compile to the instruction sequence they had)
+    for (int i = 0; i < dh.nd; i++) {
+        const int k = dh.act_of[i];
+        if (k < 0) continue;
+        double target;
+        if (k < h.n_arm) {
+            target = env_desired(h, use_prev ? prev[k] : DLW(DL_Q + i), act[k], is_planner, false);
+            if (write) prev[k] = target;      // `self._prev_state = np.copy(desired_state)`
+        } else target = DLW(DL_Q + i) + act[h.n_arm];      // Lift: gripper qpos + action[-1]
+        DLW(DL_CTRL + i) = clampd(target, GD[h.o_act_lo + k], GD[h.o_act_hi + k]);
+    }
+    if (write) *has = 1;
+}
+
 // mode 0: env.step's physics -- ctrl from the action (the `_step` arithmetic of k_env_step, nothing moved kinematically),
 //         prev_state / has_prev updated, dh.nsub sub-steps when the env's move flag is set;
 // mode 1: n_steps sub-steps towards the given ctrl rows [E, nd] (tests, parity per sub-step);
 // mode 2: mj_forward only: bias_lag <- qfrc_bias(qpos, qvel); M_out (optional) <- packed lower triangle of M [E, nd (nd + 1) / 2].
 // (the dynamics header comes through a pointer: by value its ~100 ints sat in SGPRs and 219 of them spilled;
 // amdgpu_waves_per_eu(1, 1): LDS allows one wave per CU anyway, so the whole register file is this wave's)
-template <int KIND>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void k_env_dyn(EnvHdr h, const DynHdr *__restrict__ dhp, const double *__restrict__ GD, const int32_t *__restrict__ GI,
                                                 const double *__restrict__ DD, const double *__restrict__ OD, long long E, int mode, int n_steps,
                                                 double *__restrict__ qpos, double *__restrict__ qvel, double *__restrict__ bias_lag,
@@ -692,12 +732,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void
     const unsigned flags = move_mask ? move_mask[e] : 1u;
     if (flags & 2u) return;
     double *row = qpos + e * h.nq;
-    for (int i = 0; i < dh.nd; i++) {
-        DLW(DL_Q + i) = row[dh.qadr[i]];
-        DLW(DL_V + i) = qvel[e * dh.nv + i];
-        DLW(DL_LAG + i) = bias_lag[e * dh.nd + i];
-        DLW(DL_CTRL + i) = 0.0;
-    }
+    dyn_cols_load(dh, W, e, row, qvel, bias_lag);
     if (dh.obj_on) {
 #pragma unroll
         for (int k = 0; k < 7; k++) DLW(DL_OBJ + k) = row[dh.obj_qadr + k];
@@ -705,23 +740,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void
         for (int k = 0; k < 6; k++) DLW(DL_OBJ + 7 + k) = qvel[e * dh.nv + dh.nd + k];
     }
     if (mode == 0) {
-        // `_step`: desired_state = prev_state + clip(action [* ac_scale]); ctrl = [desired_state, gripper targets], ctrlrange-clamped
-        double *prev = prev_state + e * h.n_arm;
-        const bool use_prev = is_planner && has_prev[e];
-        const double *act = action + e * h.adim;
-        for (int i = 0; i < dh.nd; i++) {
-            const int k = dh.act_of[i];
-            if (k < 0) continue;
-            double target;
-            if (k < h.n_arm) {
-                const double pv = use_prev ? prev[k] : DLW(DL_Q + i);
-                const double a = is_planner ? act[k] : act[k] * h.ac_scale;
-                target = pv + clampd(a, -h.ac_scale, h.ac_scale);
-                prev[k] = target;      // `self._prev_state = np.copy(desired_state)`
-            } else target = DLW(DL_Q + i) + act[h.n_arm];      // Lift: gripper qpos + action[-1]
-            DLW(DL_CTRL + i) = clampd(target, GD[h.o_act_lo + k], GD[h.o_act_hi + k]);
-        }
-        has_prev[e] = 1;
+        dyn_command(h, dh, GD, W, action + e * h.adim, is_planner, prev_state + e * h.n_arm, has_prev + e, true);
         if (!(flags & 1u)) return;
         n_steps = dh.nsub;
     } else if (mode == 1) {
@@ -746,11 +765,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void
     unsigned long long mine = 0ull, any = 0ull;      // stage B: collider masks of the last full scan
 #pragma unroll 1
     for (int it = 0; it < n_steps; it++) dyn_substep(dh, DD, W, OD, it, mine, any);
-    for (int i = 0; i < dh.nd; i++) {
-        row[dh.qadr[i]] = DLW(DL_Q + i);
-        qvel[e * dh.nv + i] = DLW(DL_V + i);
-        bias_lag[e * dh.nd + i] = DLW(DL_LAG + i);
-    }
+    dyn_cols_store(dh, W, e, row, qvel, bias_lag);
     if (dh.obj_on) {
 #pragma unroll
         for (int k = 0; k < 7; k++) row[dh.obj_qadr + k] = DLW(DL_OBJ + k);
@@ -771,7 +786,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void
 //   P4  wave 0: gather M, forces, L D L^T solve, integration, joint stops
 // with workgroup barriers between the phases.  Every quantity is produced by the same instruction sequence as in the
 // single-wave kernel (and the CPU checker), so results are bit-identical; what changes is who computes it and when.
-template <int KIND>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void k_env_dyn4(EnvHdr h, const DynHdr *__restrict__ dhp, const double *__restrict__ GD, const int32_t *__restrict__ GI,
                                                 const double *__restrict__ DD, const double *__restrict__ OD, long long E, int mode, int n_steps,
                                                 double *__restrict__ qpos, double *__restrict__ qvel, double *__restrict__ bias_lag,
@@ -793,30 +807,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     const bool obj = dh.obj_on != 0;
     const int w_obj = 3;
     if (wv == 0) {
-        for (int i = 0; i < dh.nd; i++) {
-            DLW(DL_Q + i) = row[dh.qadr[i]];
-            DLW(DL_V + i) = qvel[e * dh.nv + i];
-            DLW(DL_LAG + i) = bias_lag[e * dh.nd + i];
-            DLW(DL_CTRL + i) = 0.0;
-        }
+        dyn_cols_load(dh, W, e, row, qvel, bias_lag);
         if (mode == 0) {
-            // `_step`: desired_state = prev_state + clip(action [* ac_scale]); ctrl = [desired_state, gripper targets], ctrlrange-clamped
-            double *prev = prev_state + e * h.n_arm;
-            const bool use_prev = is_planner && has_prev[e];
-            const double *act = action + e * h.adim;
-            for (int i = 0; i < dh.nd; i++) {
-                const int k = dh.act_of[i];
-                if (k < 0) continue;
-                double target;
-                if (k < h.n_arm) {
-                    const double pv = use_prev ? prev[k] : DLW(DL_Q + i);
-                    const double a = is_planner ? act[k] : act[k] * h.ac_scale;
-                    target = pv + clampd(a, -h.ac_scale, h.ac_scale);
-                    if (live) prev[k] = target;      // `self._prev_state = np.copy(desired_state)`
-                } else target = DLW(DL_Q + i) + act[h.n_arm];      // Lift: gripper qpos + action[-1]
-                DLW(DL_CTRL + i) = clampd(target, GD[h.o_act_lo + k], GD[h.o_act_hi + k]);
-            }
-            if (live) has_prev[e] = 1;
+            dyn_command(h, dh, GD, W, action + e * h.adim, is_planner, prev_state + e * h.n_arm, has_prev + e, live);
         } else if (mode == 1) {
             for (int i = 0; i < dh.nd; i++) DLW(DL_CTRL + i) = ctrl_in[e * dh.nd + i];
         }
@@ -884,13 +877,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         }
         __syncthreads();
     }
-    if (wv == 0 && live) {
-        for (int i = 0; i < dh.nd; i++) {
-            row[dh.qadr[i]] = DLW(DL_Q + i);
-            qvel[e * dh.nv + i] = DLW(DL_V + i);
-            bias_lag[e * dh.nd + i] = DLW(DL_LAG + i);
-        }
-    }
+    if (wv == 0 && live) dyn_cols_store(dh, W, e, row, qvel, bias_lag);
     if (wv == w_obj && obj && live) {
 #pragma unroll
         for (int k = 0; k < 7; k++) row[dh.obj_qadr + k] = DLW(DL_OBJ + k);
@@ -1039,8 +1026,7 @@ extern "C" int mopa_env_attach_dynamics(MopaEnv *env, const MopaDynDesc *d) {
     if (!env->d_dynhdr) HIP_TRY(hipMalloc((void **)&env->d_dynhdr, sizeof(DynHdr)));
     HIP_TRY(hipMemcpy(env->d_dynhdr, &dh, sizeof(DynHdr), hipMemcpyHostToDevice));
     env->dyn_lds = lds;
-    for (const void *k : {(const void *)k_env_dyn<0>, (const void *)k_env_dyn<1>, (const void *)k_env_dyn<2>, (const void *)k_env_dyn4<0>,
-                          (const void *)k_env_dyn4<1>, (const void *)k_env_dyn4<2>})
+    for (const void *k : {(const void *)k_env_dyn, (const void *)k_env_dyn4})
         (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLdsBytes);
     return MOPA_OK;
 }
@@ -1059,9 +1045,7 @@ static int env_dyn_launch(MopaEnv *env, int64_t E, int mode, int n_steps, double
     // MOPA_DYN_KERNEL=wave pins the single-wave form (one wave per 64 envs) for A/B runs and tests; default: the workgroup form
     const char *force = getenv("MOPA_DYN_KERNEL");
     const bool wg = !(force && std::strcmp(force, "wave") == 0);
-    auto kern1 = env->hdr.kind == MOPA_ENV_PUSH ? k_env_dyn<0> : (env->hdr.kind == MOPA_ENV_LIFT ? k_env_dyn<1> : k_env_dyn<2>);
-    auto kern4 = env->hdr.kind == MOPA_ENV_PUSH ? k_env_dyn4<0> : (env->hdr.kind == MOPA_ENV_LIFT ? k_env_dyn4<1> : k_env_dyn4<2>);
-    auto kern = wg ? kern4 : kern1;
+    auto kern = wg ? k_env_dyn4 : k_env_dyn;
     hipLaunchKernelGGL(kern, dim3(blocks), dim3(wg ? 256 : 64), env->dyn_lds, st, env->hdr, env->d_dynhdr, env->d_dbl, env->d_int, env->d_dyn, env->d_obj,
                        (long long)E, mode, n_steps, qpos, qvel, bias_lag, prev_state, has_prev, action, is_planner, move_mask, ctrl, M_out);
     HIP_TRY(hipGetLastError());

@@ -103,6 +103,14 @@ struct alignas(32) EnvBodyI { int jn, jntadr, load, save, jt, qadr, pad0, pad1; 
 constexpr int env_nframes(int kind) { return kind == 1 ? 3 : (kind == 3 ? 4 : 5); }
 constexpr int kTgStride = 12;    // touch geom record in the blob: local pos[3] quat[4] size[3] type rbound
 
+// `_step`'s desired state of one arm joint: prev_state + clip(action [* ac_scale]) -- the planner's action comes unscaled.
+// Pusher (env/pusher/pusher_obstacle.py:262-266): `desired_state = self._prev_state + action` overrides both scaled forms.
+// The one statement of the rule: K4's env_advance / k_env_exec_pre / k_env_desired and the dynamics kernels' dyn_command
+// (mopa_dyn.inc) call it; the ctrl-range and joint-limit clamps that follow differ per caller and stay with them.
+__device__ __forceinline__ double env_desired(const EnvHdr &h, double pv, double a0, int is_planner, bool pusher) {
+    return pusher ? pv + a0 : pv + clampd(is_planner ? a0 : a0 * h.ac_scale, -h.ac_scale, h.ac_scale);
+}
+
 // The state change of one env.step on one qpos row (`_step` around the physics + the joint-limit clamp): desired_state =
 // prev_state + clip(action [* ac_scale]), the actuated joints reach their ctrl-range clamped targets (kinematic limit of
 // the position servos), prev[] <- desired_state.  act: the env's action row, or nullptr when stepping from a trajectory row.
@@ -118,9 +126,7 @@ __device__ __forceinline__ void env_advance(const EnvHdr &h, const double *__res
         const double pv = use_prev ? prev[j * PS] : row[adr * RS];
         // traj_row: the action is env.form_action(next_qpos) = waypoint - current arm state (rl/mopa_rollouts.py:160)
         const double a0 = traj_row ? traj_row[adr] - row[adr * RS] : act[j];
-        const double a = is_planner ? a0 : a0 * h.ac_scale;
-        // Pusher (env/pusher/pusher_obstacle.py:262-266): `desired_state = self._prev_state + action` overrides both scaled forms
-        const double desired = KIND == 3 ? pv + a0 : pv + clampd(a, -h.ac_scale, h.ac_scale);
+        const double desired = env_desired(h, pv, a0, is_planner, KIND == 3);
         // kinematic limit of the position servo: the joint reaches its (ctrl-range clamped) target
         if (move) row[adr * RS] = clampd(desired, GD[h.o_act_lo + j], GD[h.o_act_hi + j]);
         prev[j * PS] = desired;   // `self._prev_state = np.copy(desired_state)`
@@ -500,8 +506,7 @@ __global__ __launch_bounds__(256) void k_env_exec_pre(EnvHdr h, const double *__
             if (gk >= 0) row = clampd(row + ga, act_lo, act_hi);
         }
         if (j >= 0) {
-            const double p0 = has ? pv : row;
-            const double desired = KIND == 3 ? p0 + (wp - row) : p0 + clampd(wp - row, -h.ac_scale, h.ac_scale);
+            const double desired = env_desired(h, has ? pv : row, wp - row, 1, KIND == 3);
             row = clampd(desired, act_lo, act_hi);
             pv = desired;
         }
@@ -586,9 +591,7 @@ __global__ __launch_bounds__(256) void k_env_desired(EnvHdr h, const double *__r
     const int j = (int)(i - e * h.n_arm);
     const int adr = GI[h.o_arm + j];
     const double prev = (is_planner && has_prev[e]) ? prev_state[i] : qpos[e * h.nq + adr];
-    const double a0 = action[e * h.adim + j];
-    const double a = is_planner ? a0 : a0 * h.ac_scale;
-    double d = clampd(h.kind == 3 ? prev + a0 : prev + clampd(a, -h.ac_scale, h.ac_scale), GD[h.o_act_lo + j], GD[h.o_act_hi + j]);
+    double d = clampd(env_desired(h, prev, action[e * h.adim + j], is_planner, h.kind == 3), GD[h.o_act_lo + j], GD[h.o_act_hi + j]);
     if (GI[h.o_lim + adr]) d = clampd(d, GD[h.o_lo + adr], GD[h.o_hi + adr]);
     desired[i] = d;
 }

@@ -20,7 +20,8 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from .mjcf import JNT_HINGE, JNT_SLIDE, _quat_mul, _quat_to_mat
+from .mjcf import (GEOM_BOX, GEOM_CAPSULE, GEOM_CYLINDER, GEOM_MESH, GEOM_PLANE, GEOM_SPHERE, JNT_FREE, JNT_HINGE, JNT_SLIDE, _quat_mul,
+                   _quat_to_mat)
 
 DYN_MAX = 9   # dofs the kernel keeps per env (LDS budget, csrc/mopa_dyn.inc)
 
@@ -60,6 +61,54 @@ def _compose(p1, q1, p2, q2):
     return p1 + _quat_to_mat(q1) @ p2, _quat_mul(q1, q2)
 
 
+def _frame_in(m, b, anc):
+    """pose of body b's frame in the frame of its ancestor `anc` (0 = world)"""
+    p, q = np.zeros(3), np.array([1.0, 0.0, 0.0, 0.0])
+    chain = []
+    while b != anc:
+        chain.append(b)
+        b = int(m.body_parent[b])
+    for c in reversed(chain):
+        p, q = _compose(p, q, np.asarray(m.body_pos[c], dtype=np.float64), np.asarray(m.body_quat[c], dtype=np.float64))
+    return p, q
+
+
+def _owner(m, idx, b):
+    """the dynamic body (`idx`: model body id -> dynamic body index) a possibly welded body moves with; -1: fixed to the world"""
+    while b > 0 and b not in idx:
+        b = int(m.body_parent[b])
+    return idx.get(b, -1)
+
+
+def _rbound(t, s):
+    """bounding-sphere radius of a geom of type t and size s about its own origin"""
+    return {GEOM_SPHERE: s[0], GEOM_CAPSULE: s[0] + s[1], GEOM_CYLINDER: float(np.hypot(s[0], s[1])), GEOM_BOX: float(np.linalg.norm(s)),
+            GEOM_PLANE: 0.0}[t]
+
+
+def _lump(m, bodies, frame, what):
+    """`bodies` (those without mass skipped) as one rigid body in the frame of body `frame`, which they are welded to (exact: a weld
+    is rigid) -> total mass, centre of mass, 3 x 3 inertia about it (parallel axes)"""
+    parts = []
+    for w in bodies:
+        if m.body_mass[w] <= 0.0:
+            continue
+        p, q = _frame_in(m, w, frame)
+        R = _quat_to_mat(q)
+        xx, yy, zz, xy, xz, yz = m.body_inertia[w]
+        T = R @ np.array([[xx, xy, xz], [xy, yy, yz], [xz, yz, zz]]) @ R.T
+        parts.append((float(m.body_mass[w]), p + R @ np.asarray(m.body_ipos[w], dtype=np.float64), T))
+    mt = sum(p[0] for p in parts)
+    if mt <= 0.0:
+        raise ValueError(f"{what} has no mass")
+    c = sum(p[0] * p[1] for p in parts) / mt
+    T = np.zeros((3, 3))
+    for pm, pc, pT in parts:
+        d = pc - c
+        T += pT + pm * (float(d @ d) * np.eye(3) - np.outer(d, d))
+    return mt, c, T
+
+
 def dyn_facts(model, facts, frame_dt: float = 0.15) -> DynFacts:
     """`facts`: the env's :class:`EnvFacts` (arm / actuator qpos addresses, joint limits as the env clamps them)."""
     m = model
@@ -89,52 +138,16 @@ def dyn_facts(model, facts, frame_dt: float = 0.15) -> DynFacts:
         raise ValueError(f"{nd} dofs in the actuated tree, the kernel keeps at most {DYN_MAX}")
     idx = {b: i for i, b in enumerate(dyn_bodies)}
 
-    def owner(b):      # the dynamic body a (possibly welded) body moves with; -1: fixed to the world
-        while b > 0 and b not in idx:
-            b = int(m.body_parent[b])
-        return idx.get(b, -1)
-
-    def frame_in(b, anc):   # pose of body b's frame in the frame of its ancestor `anc` (0 = world)
-        p, q = np.zeros(3), np.array([1.0, 0.0, 0.0, 0.0])
-        chain = []
-        while b != anc:
-            chain.append(b)
-            b = int(m.body_parent[b])
-        for c in reversed(chain):
-            p, q = _compose(p, q, np.asarray(m.body_pos[c], dtype=np.float64), np.asarray(m.body_quat[c], dtype=np.float64))
-        return p, q
-
     parent = np.full(nd, -1, dtype=np.int32)
     rel_pos, rel_quat = np.zeros((nd, 3)), np.zeros((nd, 4))
     mass, ipos, inertia = np.zeros(nd), np.zeros((nd, 3)), np.zeros((nd, 6))
     for i, b in enumerate(dyn_bodies):
         pb = int(m.body_parent[b])
-        parent[i] = owner(pb)
+        parent[i] = _owner(m, idx, pb)
         anc = dyn_bodies[parent[i]] if parent[i] >= 0 else 0
-        rel_pos[i], rel_quat[i] = frame_in(b, anc)
+        rel_pos[i], rel_quat[i] = _frame_in(m, b, anc)
         # lump: the body itself + everything welded to it
-        parts = []
-        for w in sub:
-            if owner(w) != i:
-                continue
-            if w != b and m.body_jntnum[w] > 0:
-                continue
-            if m.body_mass[w] <= 0.0:
-                continue
-            p, q = frame_in(w, b)
-            R = _quat_to_mat(q)
-            xx, yy, zz, xy, xz, yz = m.body_inertia[w]
-            T = R @ np.array([[xx, xy, xz], [xy, yy, yz], [xz, yz, zz]]) @ R.T
-            parts.append((float(m.body_mass[w]), p + R @ np.asarray(m.body_ipos[w], dtype=np.float64), T))
-        mt = sum(p[0] for p in parts)
-        if mt <= 0.0:
-            raise ValueError(f"dynamic body {m.body_names[b]!r} has no mass")
-        c = sum(p[0] * p[1] for p in parts) / mt
-        T = np.zeros((3, 3))
-        for pm, pc, pT in parts:
-            d = pc - c
-            T += pT + pm * (float(d @ d) * np.eye(3) - np.outer(d, d))
-        mass[i], ipos[i] = mt, c
+        mass[i], ipos[i], T = _lump(m, [w for w in sub if _owner(m, idx, w) == i], b, f"dynamic body {m.body_names[b]!r}")
         inertia[i] = [T[0, 0], T[1, 1], T[2, 2], T[0, 1], T[0, 2], T[1, 2]]
 
     jid = np.array([int(m.body_jntadr[b]) for b in dyn_bodies])
@@ -201,7 +214,6 @@ class ObjFacts:
 
 
 def obj_facts(model, dyn: DynFacts, geom_name: str = "cube", kn: float = 500.0, dn: float = 3.0, eps_v: float = 1e-3) -> ObjFacts:
-    from .mjcf import GEOM_BOX, GEOM_CAPSULE, GEOM_CYLINDER, GEOM_PLANE, GEOM_SPHERE, JNT_FREE
     m = model
     cg = int(np.where(m.geom_mjid == m.geom_name2id(geom_name))[0][0])
     if int(m.geom_type[cg]) != GEOM_BOX:
@@ -220,12 +232,6 @@ def obj_facts(model, dyn: DynFacts, geom_name: str = "cube", kn: float = 500.0, 
     faces = [[a * half[0], 0.0, 0.0] for a in sg] + [[0.0, a * half[1], 0.0] for a in sg] + [[0.0, 0.0, a * half[2]] for a in sg]
     feat = np.array(verts + edges + faces, dtype=np.float64)
     idx = {int(b): i for i, b in enumerate(dyn.body)}
-    nb = len(m.body_names)
-
-    def owner(b):
-        while b > 0 and b not in idx:
-            b = int(m.body_parent[b])
-        return idx.get(b, -1)
 
     def moving(b):
         while b > 0:
@@ -233,20 +239,6 @@ def obj_facts(model, dyn: DynFacts, geom_name: str = "cube", kn: float = 500.0, 
                 return True
             b = int(m.body_parent[b])
         return False
-
-    def frame_in(b, anc):
-        p, q = np.zeros(3), np.array([1.0, 0.0, 0.0, 0.0])
-        chain = []
-        while b != anc:
-            chain.append(b)
-            b = int(m.body_parent[b])
-        for c in reversed(chain):
-            p, q = _compose(p, q, np.asarray(m.body_pos[c], dtype=np.float64), np.asarray(m.body_quat[c], dtype=np.float64))
-        return p, q
-
-    def rbound(t, s):
-        return {GEOM_SPHERE: s[0], GEOM_CAPSULE: s[0] + s[1], GEOM_CYLINDER: float(np.hypot(s[0], s[1])), GEOM_BOX: float(np.linalg.norm(s)),
-                GEOM_PLANE: 0.0}[t]
 
     cols = []
     for a, b in m.pair_geom:
@@ -257,14 +249,14 @@ def obj_facts(model, dyn: DynFacts, geom_name: str = "cube", kn: float = 500.0, 
         if t not in (GEOM_PLANE, GEOM_SPHERE, GEOM_CAPSULE, GEOM_CYLINDER, GEOM_BOX):
             raise ValueError("unsupported collider type")
         gb = int(m.geom_body[g])
-        own = owner(gb)
+        own = _owner(m, idx, gb)
         if own < 0 and moving(gb):
             continue          # a moving body outside the dynamic tree (nothing of the kind in the Sawyer scenes)
         anc = int(dyn.body[own]) if own >= 0 else 0
-        bp, bq = frame_in(gb, anc)
+        bp, bq = _frame_in(m, gb, anc)
         gp, gq = _compose(bp, bq, np.asarray(m.geom_pos[g], dtype=np.float64), np.asarray(m.geom_quat[g], dtype=np.float64))
         cols.append((own, t, np.asarray(m.geom_size[g], dtype=np.float64), gp, _quat_to_mat(gq).ravel(),
-                     max(float(m.geom_friction[g]), float(m.geom_friction[cg])), rbound(t, m.geom_size[g])))
+                     max(float(m.geom_friction[g]), float(m.geom_friction[cg])), _rbound(t, m.geom_size[g])))
     cols.sort(key=lambda c: (c[0] >= 0, c[0]))        # static ones first, then by dynamic body (stable)
     mass = float(m.body_mass[ob])
     return ObjFacts(
@@ -411,7 +403,6 @@ def contact_facts(model, dyn: DynFacts, object_body: str, maxcon: int = None, ma
                   noslip_iterations: int = 5, noslip_tolerance: float = 1e-6, solver: str = "newton", cone: str = None, limit_rows=None,
                   limit_solref=(0.02, 1.0), limit_solimp=(0.9, 0.95, 0.001),
                   qpos_ref: np.ndarray = None, condim: str = "xml", arena: int = None) -> CtFacts:
-    from .mjcf import GEOM_BOX, GEOM_CAPSULE, GEOM_CYLINDER, GEOM_MESH, GEOM_PLANE, GEOM_SPHERE, JNT_FREE
     m = model
     if len(getattr(m, "geom_solref", ())) == 0:
         raise ValueError("compiled scene carries no solver parameters (recompile with tools/compile_scenes.py)")
@@ -454,35 +445,8 @@ def contact_facts(model, dyn: DynFacts, object_body: str, maxcon: int = None, ma
             c = int(m.body_parent[c])
         return -1, 0
 
-    def frame_in(b, anc):
-        p, q = np.zeros(3), np.array([1.0, 0.0, 0.0, 0.0])
-        chain = []
-        while b != anc:
-            chain.append(b)
-            b = int(m.body_parent[b])
-        for c in reversed(chain):
-            p, q = _compose(p, q, np.asarray(m.body_pos[c], dtype=np.float64), np.asarray(m.body_quat[c], dtype=np.float64))
-        return p, q
-
     # ---- the object's inertial: the free body + everything welded below it
-    parts = []
-    for w in range(1, len(names)):
-        ow, _ = owner(w)
-        if ow != nd or float(m.body_mass[w]) <= 0.0:
-            continue
-        p, q = frame_in(w, ob)
-        R = _quat_to_mat(q)
-        xx, yy, zz, xy, xz, yz = m.body_inertia[w]
-        T = R @ np.array([[xx, xy, xz], [xy, yy, yz], [xz, yz, zz]]) @ R.T
-        parts.append((float(m.body_mass[w]), p + R @ np.asarray(m.body_ipos[w], dtype=np.float64), T))
-    mt = sum(p[0] for p in parts)
-    if mt <= 0.0:
-        raise ValueError("the object has no mass")
-    com = sum(p[0] * p[1] for p in parts) / mt
-    T = np.zeros((3, 3))
-    for pm, pc, pT in parts:
-        dd = pc - com
-        T += pT + pm * (float(dd @ dd) * np.eye(3) - np.outer(dd, dd))
+    mt, com, T = _lump(m, [w for w in range(1, len(names)) if owner(w)[0] == nd], ob, "the object")
     if np.abs(T - np.diag(np.diag(T))).max() <= 1e-12 * np.abs(T).max():
         prin, iquat = np.diag(T).copy(), np.array([1.0, 0.0, 0.0, 0.0])
     else:
@@ -495,10 +459,6 @@ def contact_facts(model, dyn: DynFacts, object_body: str, maxcon: int = None, ma
     damp = float(m.jnt_damping[jo])
 
     # ---- shapes and features
-    def rbound(t, s):
-        return {GEOM_SPHERE: s[0], GEOM_CAPSULE: s[0] + s[1], GEOM_CYLINDER: float(np.hypot(s[0], s[1])), GEOM_BOX: float(np.linalg.norm(s)),
-                GEOM_PLANE: 0.0}[t]
-
     ng = len(m.geom_type)
     shape_of = {}
     sh = []
@@ -508,7 +468,7 @@ def contact_facts(model, dyn: DynFacts, object_body: str, maxcon: int = None, ma
         own, fb = owner(gb)
         if own is None:
             continue
-        bp, bq = frame_in(gb, fb)
+        bp, bq = _frame_in(m, gb, fb)
         gp, gq = _compose(bp, bq, np.asarray(m.geom_pos[g], dtype=np.float64), np.asarray(m.geom_quat[g], dtype=np.float64))
         R = _quat_to_mat(gq)
         t = int(m.geom_type[g])
@@ -550,7 +510,7 @@ def contact_facts(model, dyn: DynFacts, object_body: str, maxcon: int = None, ma
         elif t != GEOM_PLANE:
             raise ValueError("unsupported collider type")
         shape_of[g] = len(sh)
-        sh.append((g, own, t, size, gp, R.ravel(), rbound(t, size)))
+        sh.append((g, own, t, size, gp, R.ravel(), _rbound(t, size)))
         feats_of.append((gp + pts @ R.T, rad))
 
     # Pairs left out of the contact tables: only those PROVEN to stay beyond this stage's own reach -- tools/prove_separated_pairs.py shows

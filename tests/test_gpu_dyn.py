@@ -606,6 +606,37 @@ def test_contact_env_rollout_bit_identical_to_oracle(oracle_mod, torch_mod, env_
         assert np.array_equal(done.cpu().numpy(), ref.done)
 
 
+@pytest.mark.parametrize("env_name", ["SawyerPushObstacle-v0", "SawyerLiftObstacle-v0"])
+@pytest.mark.parametrize("solver", ["newton", "newton-pyramidal", "pgs"])
+def test_contact_env_command_planner_and_move_mask_bit_identical_to_oracle(oracle_mod, torch_mod, env_name, solver):
+    """the contact kernel's command path beyond unmasked policy actions: a policy step, a planner step under a move mask (bit 0 clear: the
+    command is recorded and nothing moves; bit 1: the env sits out), a planner step that reads the prev_state / has_prev the masked step
+    wrote.  Lift drives the gripper branch of the command.  After every step the carried state equals the oracle's, bit for bit."""
+    torch = torch_mod
+    E = 22                  # not a multiple of 4: the last wave carries idle groups
+    opts = {"newton": {"solver": "newton"}, "newton-pyramidal": {"solver": "newton", "cone": "pyramidal"}, "pgs": {"solver": "pgs"}}[solver]
+    pi, orc, env, ref = _setup_ct(oracle_mod, env_name, E, contact_options=opts)
+    assert env.ct.solver == {"pgs": 0, "newton-pyramidal": 1, "newton": 2}[solver]
+    q, _ = _ct_states(env, orc, E, seed=31)
+    env.set_state(torch.tensor(q, device=env.device))
+    ref.set_state(q)
+    mm = np.random.default_rng(2).integers(0, 4, size=E).astype(np.uint8)
+    assert np.bincount(mm, minlength=4).min() >= 2, "every mask value occurs at least twice"
+    rng = np.random.default_rng(9)
+    for t, (is_planner, mask) in enumerate([(False, None), (True, mm), (True, None)]):
+        a = rng.uniform(-0.08, 0.08, size=(E, env.action_dim)) if is_planner else rng.uniform(-1.5, 1.5, size=(E, env.action_dim))
+        if mask is None:
+            env.step(torch.tensor(a, device=env.device), is_planner=is_planner)
+            ref.step(a, is_planner=is_planner, nthreads=8)
+        else:
+            env._launch(torch.tensor(a, device=env.device), is_planner, torch.tensor(mask, device=env.device))
+            ref.step(a, is_planner=is_planner, move_mask=mask, nthreads=8)
+        for name in ("qpos", "qvel", "bias_lag", "obs", "prev_state"):
+            assert np.array_equal(_bits(getattr(env, name).cpu().numpy()), _bits(getattr(ref, name))), f"step {t}: {name}"
+        assert np.array_equal(env.has_prev.cpu().numpy(), ref.has_prev), f"step {t}: has_prev"
+        assert np.array_equal(env.ep_len.cpu().numpy(), ref.ep_len), f"step {t}: ep_len"
+
+
 def test_contact_free_envs_equal_the_servo_dynamics(oracle_mod, torch_mod):
     """an env in which nothing touches anything and the object is in free fall far away: K7's arm state after a step equals
     K6's (stage A) bit for bit -- the contact stage adds exact zeros"""
