@@ -449,6 +449,34 @@ int mopa_contacts_batch(MopaScene *scene, const double *q_active_dev /*[N,na]*/,
 int mopa_contacts_state(MopaScene *scene, const double *qpos_host /*[nq]*/, double cutoff, int32_t max_contacts /*K*/,
                         int32_t *count /*[1]*/, int32_t *pair /*[K]*/, double *dist /*[K]*/);
 
+/* Contact frames: the contact report plus, per record, what the reference reads off d->contact[i].frame / pos
+ * (util/contact_info.py).  ONE frame per reported pair -- that of the deepest contact -- where MuJoCo may emit several contacts
+ * (box-box, capsule-plane ...).  For record (state i, slot k) with geoms (g1, g2) as MopaModel.pair_geom orders them:
+ *   normal[i,k,:]  unit vector from g1 towards g2: translating g2 by -dist * normal removes the overlap along it
+ *   pos[i,k,:]     midpoint of two witness points, w1 on g1 and w2 on g2, with w2 - w1 = dist * normal
+ * count / pair / dist are exactly mopa_contacts_batch's (same launches, same bytes); unused slots of normal / pos hold 0.0.
+ * Same argument rules and status codes as mopa_contacts_batch, including the glued-scene and pair_cull_radius refusals.  One
+ * more launch behind the report's two (a wave per state with a record), deterministic.  The definition per pair class is in
+ * DESIGN.md section 4 ("Contact frames"; PARITY UNPINNED -- MuJoCo's multi-point manifolds are not reproduced). */
+int mopa_contact_frames_batch(MopaScene *scene, const double *q_active_dev /*[N,na]*/, const double *qpos_env_dev /*[E,nq]*/,
+                              int64_t N, int64_t samples_per_env, double cutoff, int32_t max_contacts /*K*/,
+                              int32_t *count_dev /*[N]*/, int32_t *pair_dev /*[N,K]*/, double *dist_dev /*[N,K]*/,
+                              double *normal_dev /*[N,K,3]*/, double *pos_dev /*[N,K,3]*/, void *stream);
+/* the same for one state (host pointers, synchronous) */
+int mopa_contact_frames_state(MopaScene *scene, const double *qpos_host /*[nq]*/, double cutoff, int32_t max_contacts /*K*/,
+                              int32_t *count /*[1]*/, int32_t *pair /*[K]*/, double *dist /*[K]*/, double *normal /*[K,3]*/,
+                              double *pos /*[K,3]*/);
+/* Pair level: M posed primitive pairs, one lane each.  types [M,2] (MuJoCo geom type codes, either order: the pair is evaluated
+ * in the narrow phase's canonical order and the normal negated on the way out when that is the reverse), recs [M,2,15] =
+ * pos[3] mat[9] size[3] per geom, out [M,7] = dist, normal[3], pos[3]; dist = MOPA_FAR (and a zero frame) where the narrow phase
+ * reports no overlap or the type pair is unsupported.  Meshes are not served at this level on the device. */
+int mopa_geom_frames_batch(int32_t device, int64_t M, const int32_t *types_dev, const double *recs_dev, double *out_dev, void *stream);
+/* The host compile of the same functions -- the sequential form the kernels match bit for bit.  Needs no GPU and makes no HIP
+ * call.  A mesh as the second geom of every pair of type 7: its hull vertices mesh_verts [nvert,3] in the mesh frame (nullable
+ * with nvert = 0). */
+int mopa_geom_frames_host(int64_t M, const int32_t *types, const double *recs, const double *mesh_verts /*nullable*/, int32_t nvert,
+                          double *out);
+
 /* ======================================================================================================
  * (BASELINE configs 3-5) batched KINEMATIC env.step for the three Sawyer obstacle envs --
  * the "env-steps/sec" half of the metric.  Restates what the reference envs compute around the physics:

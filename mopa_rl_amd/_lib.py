@@ -32,6 +32,7 @@ EXPORTED_SYMBOLS = [
     "mopa_plan_star_batch", "mopa_plan_star", "mopa_plan_star_k", "mopa_star_params_size",
     "mopa_plan_race_batch", "mopa_plan_race", "mopa_race_params_size", "mopa_pullback_batch", "mopa_is_valid_state", "mopa_plan",
     "mopa_planner_status", "mopa_debug_fk", "mopa_debug_pair_dist", "mopa_contacts_batch", "mopa_contacts_state",
+    "mopa_contact_frames_batch", "mopa_contact_frames_state", "mopa_geom_frames_batch", "mopa_geom_frames_host",
     "mopa_env_create", "mopa_env_destroy", "mopa_env_obs_dim", "mopa_env_action_dim", "mopa_env_step_batch", "mopa_env_exec_batch", "mopa_env_desired_batch",
     "mopa_env_attach_dynamics", "mopa_env_attach_contacts", "mopa_env_set_contact_stats", "mopa_rollout_stage", "mopa_rollout_pool_pick", "mopa_rollout_step_size", "mopa_reuse_batch", "mopa_replay_append", "mopa_replay_sample", "mopa_ct_desc_size", "mopa_env_contact_arena", "mopa_env_dyn_dofs", "mopa_env_dyn_qvel_width", "mopa_env_dyn_forward_batch", "mopa_env_dyn_substeps_batch", "mopa_env_step_dyn_batch",
     "mopa_pusher_dyn_desc_size", "mopa_env_attach_pusher_dynamics", "mopa_env_set_pusher_stats", "mopa_env_pusher_substeps_batch",
@@ -239,6 +240,10 @@ def lib() -> C.CDLL:
     L.mopa_debug_pair_dist.argtypes = [vp, _dp, _dp]
     L.mopa_contacts_batch.argtypes = [vp, vp, vp, C.c_int64, C.c_int64, C.c_double, C.c_int32, vp, vp, vp, vp]
     L.mopa_contacts_state.argtypes = [vp, _dp, C.c_double, C.c_int32, _ip, _ip, _dp]
+    L.mopa_contact_frames_batch.argtypes = [vp, vp, vp, C.c_int64, C.c_int64, C.c_double, C.c_int32, vp, vp, vp, vp, vp, vp]
+    L.mopa_contact_frames_state.argtypes = [vp, _dp, C.c_double, C.c_int32, _ip, _ip, _dp, _dp, _dp]
+    L.mopa_geom_frames_batch.argtypes = [C.c_int32, C.c_int64, vp, vp, vp, vp]
+    L.mopa_geom_frames_host.argtypes = [C.c_int64, _ip, _dp, _dp, C.c_int32, _dp]
     L.mopa_env_create.argtypes = [C.POINTER(MopaEnvDesc), C.POINTER(vp)]
     L.mopa_env_destroy.argtypes = [vp]
     L.mopa_env_destroy.restype = None
@@ -310,6 +315,20 @@ def _d(a):
 def _i(a):
     a = np.ascontiguousarray(a, dtype=np.int32)
     return a, a.ctypes.data_as(_ip)
+
+
+def geom_frames_host(types, recs, mesh_verts=None) -> np.ndarray:
+    """mopa_geom_frames_host: M posed pairs -- types [M, 2] (MuJoCo geom type codes, either order), recs [M, 2, 15] = pos[3]
+    mat[9] size[3] per geom -> [M, 7] = dist, normal[3], pos[3] by the host compile of the kernels' functions (no GPU).
+    mesh_verts [n, 3]: the hull of the mesh that every pair with a second geom of type 7 has."""
+    t, tp = _i(np.asarray(types).reshape(-1, 2))
+    r, rp = _d(np.asarray(recs, dtype=np.float64).reshape(-1, 30))
+    if len(t) != len(r):
+        raise MopaError(f"{len(t)} type pairs for {len(r)} record pairs")
+    out = np.zeros((len(t), 7))
+    v, vp_ = _d(np.asarray(mesh_verts, dtype=np.float64).reshape(-1, 3)) if mesh_verts is not None else (np.zeros((0, 3)), None)
+    check(lib().mopa_geom_frames_host(len(t), tp, rp, vp_, len(v), out.ctypes.data_as(_dp)))
+    return out
 
 
 def model_struct(m, keep: list, pair_geom=None) -> MopaModel:
@@ -642,15 +661,38 @@ class Scene:
                                         pair.ctypes.data_as(_ip), dist.ctypes.data_as(_dp)))
         return int(cnt.value), pair, dist
 
-    def contacts_state(self, qpos, cutoff: Optional[float] = None):
+    def contact_frames_state_raw(self, qpos, cutoff: Optional[float] = None, max_contacts: int = 64):
+        """(count, pair [K] int32, dist [K], normal [K, 3], pos [K, 3]) of one state: `contacts_state_raw` with the contact
+        frame of every record (mopa_contact_frames_state); unused slots of normal / pos hold 0.0"""
+        sc = self.contact_scene()
+        q, qp = _d(qpos)
+        if q.shape != (self.nq,):
+            raise MopaError(f"state has dimension {q.shape}, expected nq={self.nq}")
+        K = int(max_contacts)
+        cnt = C.c_int32(0)
+        pair = np.full(max(K, 1), -1, dtype=np.int32)
+        dist = np.full(max(K, 1), MOPA_FAR)
+        normal = np.zeros((max(K, 1), 3))
+        pos = np.zeros((max(K, 1), 3))
+        check(lib().mopa_contact_frames_state(sc._h, qp, float(self.contact_threshold if cutoff is None else cutoff), K, C.byref(cnt),
+                                              pair.ctypes.data_as(_ip), dist.ctypes.data_as(_dp), normal.ctypes.data_as(_dp), pos.ctypes.data_as(_dp)))
+        return int(cnt.value), pair, dist, normal, pos
+
+    def contacts_state(self, qpos, cutoff: Optional[float] = None, frames: bool = False):
         """The pairs in contact in one state, as the reference's checker sees them in `d->contact[i]`: a list of
         (geom1_name, geom2_name, dist) over the non-ignored candidate pairs with dist <= cutoff, in `model.pair_geom` order.
-        cutoff=None: the scene's contact_threshold -- the pairs that make the state invalid.  cutoff must be < 0."""
+        cutoff=None: the scene's contact_threshold -- the pairs that make the state invalid.  cutoff must be < 0.
+        frames=True: (geom1_name, geom2_name, dist, normal, pos) -- ONE contact frame per pair, that of the deepest contact
+        (MuJoCo may emit several contacts for a pair): `normal` [3] a unit vector from geom1 towards geom2, `pos` [3] the
+        midpoint of the two witness points ("Contact frames")."""
         m = self.model
         K = max(1, len(m.pair_geom))
-        n, pair, dist = self.contacts_state_raw(qpos, cutoff, K)
         g = np.asarray(m.pair_geom).reshape(-1, 2)
         name = lambda k: m.all_geom_names[int(m.geom_mjid[int(k)])]
+        if frames:
+            n, pair, dist, normal, pos = self.contact_frames_state_raw(qpos, cutoff, K)
+            return [(name(g[p, 0]), name(g[p, 1]), float(d), normal[k].copy(), pos[k].copy()) for k, (p, d) in enumerate(zip(pair[:n], dist[:n]))]
+        n, pair, dist = self.contacts_state_raw(qpos, cutoff, K)
         return [(name(g[p, 0]), name(g[p, 1]), float(d)) for p, d in zip(pair[:n], dist[:n])]
 
     def debug_pair_dist(self, qpos):

@@ -90,10 +90,13 @@ class PlanState:
 class ContactReport:
     """`BatchPlanner.contacts`: per state the number of pairs at or below the cutoff (`count` [N] int32, not capped), their
     indices into `model.pair_geom` in ascending order (`pair` [N, K] int32, -1 in unused slots) and their signed distances
-    (`dist` [N, K] float64, MOPA_FAR in unused slots)."""
+    (`dist` [N, K] float64, MOPA_FAR in unused slots).  With `frames=True` also ONE contact frame per record, that of the
+    deepest contact: `normal` [N, K, 3], a unit vector from the pair's first geom (as `geoms()` orders them) towards its second,
+    and `pos` [N, K, 3], the midpoint of the two witness points; 0.0 in unused slots.  Both are None otherwise."""
 
-    def __init__(self, count, pair, dist, model):
+    def __init__(self, count, pair, dist, model, normal=None, pos=None):
         self.count, self.pair, self.dist, self.model = count, pair, dist, model
+        self.normal, self.pos = normal, pos
 
     def __iter__(self):
         return iter((self.count, self.pair, self.dist))
@@ -118,6 +121,23 @@ def pair_geom_ids(model, pair) -> np.ndarray:
     g = np.asarray(model.geom_mjid, dtype=np.int64)[np.asarray(model.pair_geom, dtype=np.int64).reshape(-1, 2)]
     out = g[np.clip(pair, 0, max(len(g) - 1, 0))] if len(g) else np.zeros(pair.shape + (2,), dtype=np.int64)
     out[pair < 0] = -1
+    return out
+
+
+def geom_frames(types, recs, stream=None):
+    """mopa_geom_frames_batch: M posed primitive pairs, one lane each -- types [M, 2] int32 (MuJoCo geom type codes, either
+    order), recs [M, 2, 15] float64 (pos[3] mat[9] size[3] per geom), both contiguous on the GPU -> [M, 7] = dist, normal[3],
+    pos[3]; the bits of `_lib.geom_frames_host`.  Meshes are not served at this level."""
+    torch = _torch()
+    _check_f64(recs, "recs")
+    if types.dtype != torch.int32 or not types.is_cuda or not types.is_contiguous() or types.dim() != 2 or types.shape[1] != 2:
+        raise _lib.MopaError("types must be a contiguous int32 GPU tensor [M, 2]")
+    M = types.shape[0]
+    if recs.numel() != M * 30:
+        raise _lib.MopaError(f"recs must have shape [{M}, 2, 15], got {tuple(recs.shape)}")
+    out = torch.empty(M, 7, dtype=torch.float64, device=recs.device)
+    dev = recs.device.index if recs.device.index is not None else torch.cuda.current_device()
+    _lib.check(_lib.lib().mopa_geom_frames_batch(int(dev), M, _ptr(types), _ptr(recs), _ptr(out), _stream_handle(stream)))
     return out
 
 
@@ -190,11 +210,12 @@ class BatchPlanner:
         return (valid, md) if want_min_dist else valid
 
     def contacts(self, q_active, qpos_env, samples_per_env: Optional[int] = None, cutoff: Optional[float] = None,
-                 max_contacts: int = 16, stream=None) -> ContactReport:
+                 max_contacts: int = 16, stream=None, frames: bool = False) -> ContactReport:
         """Which pairs are in contact, for every state of a batch (states as in `is_valid`): one record per non-ignored
         candidate pair with dist <= cutoff, ascending index into `model.pair_geom`; `count` is not capped by `max_contacts`,
         the records with the lowest indices are kept.  cutoff=None: the scene's contact_threshold, i.e. the pairs that make a
-        state invalid; any other cutoff must be < 0.  Runs on the scene with the full pair list (`Scene.contact_scene`)."""
+        state invalid; any other cutoff must be < 0.  Runs on the scene with the full pair list (`Scene.contact_scene`).
+        frames=True: the report also carries `.normal` and `.pos` (one more launch; count / pair / dist are the same bytes)."""
         torch = _torch()
         _check_f64(q_active, "q_active", self.na)
         _check_f64(qpos_env, "qpos_env", self.nq)
@@ -208,6 +229,13 @@ class BatchPlanner:
         count = torch.empty(N, dtype=torch.int32, device=dev)
         pair = torch.empty(N, max(K, 1), dtype=torch.int32, device=dev)
         dist = torch.empty(N, max(K, 1), dtype=torch.float64, device=dev)
+        if frames:
+            normal = torch.empty(N, max(K, 1), 3, dtype=torch.float64, device=dev)
+            pos = torch.empty(N, max(K, 1), 3, dtype=torch.float64, device=dev)
+            _lib.check(_lib.lib().mopa_contact_frames_batch(sc.handle, _ptr(q_active), _ptr(qpos_env), N, spe,
+                                                            float(self.scene.contact_threshold if cutoff is None else cutoff), K,
+                                                            _ptr(count), _ptr(pair), _ptr(dist), _ptr(normal), _ptr(pos), _stream_handle(stream)))
+            return ContactReport(count, pair, dist, self.scene.model, normal, pos)
         _lib.check(_lib.lib().mopa_contacts_batch(sc.handle, _ptr(q_active), _ptr(qpos_env), N, spe,
                                                   float(self.scene.contact_threshold if cutoff is None else cutoff), K,
                                                   _ptr(count), _ptr(pair), _ptr(dist), _stream_handle(stream)))

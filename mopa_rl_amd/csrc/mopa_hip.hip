@@ -29,6 +29,7 @@
 #include <mutex>
 #include "../../include/mopa_hip.h"
 #include "mopa_device.hpp"
+#include "mopa_frames.hpp"
 #include "mopa_fk.hpp"
 #include "mopa_host.hpp"
 
@@ -45,6 +46,7 @@ int mopa_fail(int code, const std::string &msg) {
 constexpr double kV5MaxReach = 32.0;        // metres: beyond this the FP32 broad phase is not used (see mopa_scene_create)
 static void plan_register_lds();            // defined with K3 (mopa_planner.inc)
 static void contacts_register_lds();        // defined with the contact report (mopa_contacts.inc)
+static void contact_frames_register_lds();  // defined with the contact frames (mopa_contact_frames.inc)
 static void k9_register_lds();              // defined with K9 path simplification (mopa_k9.inc)
 static void star_register_lds();            // defined with K3b RRT* (mopa_rrtstar.inc)
 static void k1_register_lds();              // defined with the K1 kernel table (mopa_valid_launch.inc)
@@ -147,6 +149,7 @@ struct MopaScene {
     std::vector<int32_t> pair_slot;   // model pair index -> device pair index or -1
     std::vector<int32_t> pair_model;  // device pair index -> model pair index (contact report)
     int32_t *d_pair_model = nullptr;
+    int32_t *d_pair_slot = nullptr;   // pair_slot on the device (contact frames)
     bool pruned = false;              // created with pair_cull_radius: the pair list is proven down to the contact threshold only
     std::vector<int32_t> geom_model_of_dev;  // (identity; device geoms == model collidable geoms)
     uint64_t seed = 0;
@@ -688,6 +691,7 @@ static int scene_create(const MopaSceneDesc *desc, int glue_a, int glue_b, MopaS
     hipError_t e2 = up((void **)&S->d_int, S->h_int.data(), S->h_int.size() * 4);
     if (e2 == hipSuccess) e2 = up((void **)&S->d_gp_tab, S->h_gp_tab.data(), S->h_gp_tab.size() * 4);
     if (e2 == hipSuccess) e2 = up((void **)&S->d_pair_model, S->pair_model.data(), S->pair_model.size() * 4);
+    if (e2 == hipSuccess) e2 = up((void **)&S->d_pair_slot, S->pair_slot.data(), S->pair_slot.size() * 4);
     S->dbg_doubles = (size_t)kGeomStride * m.ngeom + (size_t)h.npair + 8;
     hipError_t e3 = hipMalloc((void **)&S->d_q, sizeof(double) * (size_t)(m.nq + S->na + 8));
     hipError_t e4 = hipMalloc((void **)&S->d_valid, 8);
@@ -703,6 +707,7 @@ static int scene_create(const MopaSceneDesc *desc, int glue_a, int glue_b, MopaS
     k1_register_lds();
     plan_register_lds();
     contacts_register_lds();
+    contact_frames_register_lds();
     k9_register_lds();
     star_register_lds();
     *out = S;
@@ -718,7 +723,7 @@ extern "C" void mopa_scene_destroy(MopaScene *S) {
     if (!S) return;
     DeviceGuard guard(S->device);
     (void)hipDeviceSynchronize();      // nothing of this scene may still be running when its tables go away
-    for (void *q : {(void *)S->d_dbl, (void *)S->d_int, (void *)S->d_q, (void *)S->d_valid, (void *)S->d_md, (void *)S->d_dbg, (void *)S->d_gp_tab, (void *)S->d_pair_model})
+    for (void *q : {(void *)S->d_dbl, (void *)S->d_int, (void *)S->d_q, (void *)S->d_valid, (void *)S->d_md, (void *)S->d_dbg, (void *)S->d_gp_tab, (void *)S->d_pair_model, (void *)S->d_pair_slot})
         if (q) (void)hipFree(q);
     for (auto &kv : S->scratch) {
         StreamScratch &sc = kv.second;
@@ -845,6 +850,8 @@ extern "C" const char *mopa_planner_status(const MopaScene *S) { return S ? S->s
 
 // batched contact report: mopa_contacts_batch / mopa_contacts_state
 #include "mopa_contacts.inc"
+// contact frames behind it: mopa_contact_frames_batch / _state, pair level mopa_geom_frames_batch / _host
+#include "mopa_contact_frames.inc"
 
 // The planner entry points are defined in mopa_planner.inc (K3).
 #include "mopa_planner.inc"

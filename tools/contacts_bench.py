@@ -2,8 +2,10 @@
 """Time of the batched contact report next to the validity call it extends, per scene, on the headline batch (4096 x 256 states,
 bench.py's generator): `contacts(cutoff=thr, K=16)`, its first stage alone (the min-depth launch on the full pair list) and
 `is_valid(want_min_dist=True)` as the planner calls it -- in interleaved rounds (device events), median / min / max.
+--frames: also `contacts(frames=True)` in the same rounds, frames on against off: both times and their ratio.
 
     python tools/contacts_bench.py --out profiles/r10/contacts_bench.txt
+    python tools/contacts_bench.py --frames --out profiles/r25/contacts_frames_bench.txt
 """
 from __future__ import annotations
 
@@ -25,6 +27,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=12)
     ap.add_argument("--reps", type=int, default=5, help="calls per timed window")
     ap.add_argument("--max-contacts", type=int, default=16)
+    ap.add_argument("--frames", action="store_true", help="also time contacts(frames=True): frames on against off")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     import torch
@@ -47,6 +50,8 @@ def main():
             "stage 1 (full pair list)": lambda: bp_full.is_valid(qa, rows, samples_per_env=args.samples, want_min_dist=True),
             "contacts": lambda: bp.contacts(qa, rows, samples_per_env=args.samples, max_contacts=args.max_contacts),
         }
+        if args.frames:
+            forms["contacts(frames=True)"] = lambda: bp.contacts(qa, rows, samples_per_env=args.samples, max_contacts=args.max_contacts, frames=True)
         for f in forms.values():           # warm-up: code objects, scratch buffers
             for _ in range(3):
                 f()
@@ -70,6 +75,9 @@ def main():
             lines.append(f"    {k:<26s} {med[k]:8.3f} [{min(v):.3f} .. {max(v):.3f}]")
         lines.append(f"    stage 2 (k_contact_rows) = contacts - stage 1: {med['contacts'] - med['stage 1 (full pair list)']:.3f} ms;  "
                      f"contacts / is_valid(want_min_dist) = {med['contacts'] / med['is_valid(want_min_dist)']:.2f}")
+        if args.frames:
+            on, off = med["contacts(frames=True)"], med["contacts"]
+            lines.append(f"    frames on {on:.3f} ms against off {off:.3f} ms: k_contact_frames = {on - off:.3f} ms, on / off = {on / off:.3f}")
         lines.append("")
         sc.close()
     text = "\n".join(lines)
