@@ -224,6 +224,9 @@ int mopa_scene_k1_export_glued(const MopaSceneDesc *desc, int32_t body_a, int32_
  * q_active[s] (na values) over the env row qpos_env[s] (nq values); out[s][nmg][12] = each moving geom's world position
  * and row-major rotation matrix.  Returns MOPA_ERR_INVALID_ARG for an index that names no baked scene */
 int mopa_k1_baked_fk_host(int index, int64_t n, const double *q_active, const double *qpos_env, double *out);
+/* the resident pairs of baked scene #index (pairs the baked walk evaluates in place), as the walk computes them on the host:
+   out[n][n_res] distances in the order of the traits' list; *n_res (nullable) receives their number */
+int mopa_k1_baked_resident_host(int index, int64_t n, const double *q_active, const double *qpos_env, double *out, int32_t *n_res);
 
 /* N states: state i = qpos_env[i / samples_per_env] with its active entries replaced by q_active[i].
  * valid[i] = 1 iff no non-ignored pair has dist <= contact_threshold.
@@ -232,6 +235,11 @@ int mopa_k1_baked_fk_host(int index, int64_t n, const double *q_active, const do
 int mopa_is_valid_batch(MopaScene *scene, const double *q_active_dev /*[N,na]*/, const double *qpos_env_dev /*[E,nq]*/,
                         int64_t N, int64_t samples_per_env, uint8_t *valid_dev /*[N]*/, double *min_dist_dev /*[N] or NULL*/,
                         void *stream);
+/* The same with the number of states only known on the device: *n_dev <= N, N sizes the launch and the buffers; states from
+ * *n_dev on are neither read nor written.  Needs a scene the lane-per-state kernel serves (MOPA_ERR_UNSUPPORTED otherwise). */
+int mopa_is_valid_batch_counted(MopaScene *scene, const double *q_active_dev /*[N,na]*/, const double *qpos_env_dev /*[E,nq]*/,
+                                int64_t N, int64_t samples_per_env, uint8_t *valid_dev /*[N]*/, double *min_dist_dev /*[N] or NULL*/,
+                                const int64_t *n_dev, void *stream);
 
 /* N segments qa[i] -> qb[i] (active coordinates), OMPL DiscreteMotionValidator semantics:
  * valid[i] = 1 iff qb[i] and every interior state interpolate(qa,qb,k/nd), k=1..nd-1, is valid,

@@ -165,8 +165,10 @@ class BatchPlanner:
 
     # valid[i] for state i = qpos_env[i // samples_per_env] with active entries <- q_active[i]
     def is_valid(self, q_active, qpos_env, samples_per_env: Optional[int] = None, want_min_dist: bool = False,
-                 out=None, stream=None, guard: bool = False):
-        """guard: states with a joint beyond its range + the pruning proof's guard band are re-evaluated with the full pair list
+                 out=None, stream=None, guard: bool = False, n_dev=None):
+        """n_dev: int64 device tensor of one element, the number of states when only the device knows it (<= N; states from it on
+        are neither read nor written; `out` then keeps what it held there).
+        guard: states with a joint beyond its range + the pruning proof's guard band are re-evaluated with the full pair list
         (a device-side range test, one host read of the count; off on the hot paths, whose states are sampled / clipped inside
         the ranges -- `Scene.is_valid_state`, the reference's isValidState, always guards)."""
         torch = _torch()
@@ -178,6 +180,12 @@ class BatchPlanner:
             raise _lib.MopaError("qpos_env has fewer rows than ceil(N / samples_per_env)")
         valid = out if out is not None else torch.empty(N, dtype=torch.uint8, device=q_active.device)
         md = torch.empty(N, dtype=torch.float64, device=q_active.device) if want_min_dist else None
+        if n_dev is not None:
+            if guard or n_dev.dtype != torch.int64 or n_dev.numel() != 1 or n_dev.device != q_active.device:
+                raise _lib.MopaError("n_dev: one int64 on the states' device, without guard")
+            _lib.check(_lib.lib().mopa_is_valid_batch_counted(self.scene.handle, _ptr(q_active), _ptr(qpos_env), N, spe, _ptr(valid),
+                                                              _ptr(md) if md is not None else None, _ptr(n_dev), _stream_handle(stream)))
+            return (valid, md) if want_min_dist else valid
         _lib.check(_lib.lib().mopa_is_valid_batch(self.scene.handle, _ptr(q_active), _ptr(qpos_env), N, spe, _ptr(valid),
                                                   _ptr(md) if md is not None else None, _stream_handle(stream)))
         if guard and self.scene.npair_pruned and N:

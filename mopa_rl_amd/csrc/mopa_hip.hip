@@ -620,6 +620,7 @@ extern "C" int mopa_scene_hdr_offset(const char *field) {
     MOPA_HDR_FIELD(o_pq_adr) MOPA_HDR_FIELD(o_mg_geom) MOPA_HDR_FIELD(thr)
     MOPA_HDR_FIELD(o_mb_parent) MOPA_HDR_FIELD(o_chain_adr) MOPA_HDR_FIELD(o_chain_len) MOPA_HDR_FIELD(o_chain_items) MOPA_HDR_FIELD(o_g_mb)
     MOPA_HDR_FIELD(o_mb_load) MOPA_HDR_FIELD(o_mb_save) MOPA_HDR_FIELD(pfk_maxlen) MOPA_HDR_FIELD(n_gp) MOPA_HDR_FIELD(npair) MOPA_HDR_FIELD(o_pairs)
+    MOPA_HDR_FIELD(o_g_rec) MOPA_HDR_FIELD(o_g_type)
 #undef MOPA_HDR_FIELD
     return -1;
 }
@@ -633,11 +634,25 @@ struct K1HostSink {
         o[0] = gp.x; o[1] = gp.y; o[2] = gp.z;
         quat2mat(o + 3, gq);
     }
+    void resident(int, double) {}
+};
+// the resident pairs' distances alone (what the kernel folds into verdict and depth before pass A)
+struct K1ResHostSink {
+    double *out;   // [n_res]
+    void operator()(int, V3, Q4) {}
+    void resident(int r, double d) { out[r] = d; }
 };
 template <class TR>
 void k1_fk_host(int64_t n, const double *q_active, const double *qpos_env, double *out) {
     for (int64_t s = 0; s < n; s++) {
         K1HostSink sink{out + (size_t)s * 12 * TR::nmg};
+        k1_fk_baked<TR>(q_active + (size_t)s * TR::na, qpos_env + (size_t)s * TR::nq, sink, std::make_integer_sequence<int, TR::nmb>{});
+    }
+}
+template <class TR>
+void k1_res_host(int64_t n, const double *q_active, const double *qpos_env, double *out) {
+    for (int64_t s = 0; s < n; s++) {
+        K1ResHostSink sink{out + (size_t)s * k1_n_res<TR>};
         k1_fk_baked<TR>(q_active + (size_t)s * TR::na, qpos_env + (size_t)s * TR::nq, sink, std::make_integer_sequence<int, TR::nmb>{});
     }
 }
@@ -647,6 +662,15 @@ extern "C" int mopa_k1_baked_fk_host(int index, int64_t n, const double *q_activ
 #define MOPA_K1_FK_HOST(i_, T_) if (index == i_) { k1_fk_host<T_>(n, q_active, qpos_env, out); return MOPA_OK; }
     MOPA_K1_BAKED_SCENES(MOPA_K1_FK_HOST)
 #undef MOPA_K1_FK_HOST
+    return fail(MOPA_ERR_INVALID_ARG, "no baked scene #" + std::to_string(index));
+}
+// The resident pairs of baked scene #index as the walk evaluates them, on the host: out[n][n_res] distances in the order of the
+// traits' list; *n_res (nullable) receives the number of resident pairs (0 in a MOPA_V5_NO_RESIDENT build).
+extern "C" int mopa_k1_baked_resident_host(int index, int64_t n, const double *q_active, const double *qpos_env, double *out, int32_t *n_res) {
+    if (n < 0 || (n > 0 && (!q_active || !qpos_env || !out))) return fail(MOPA_ERR_INVALID_ARG, "null argument / negative count");
+#define MOPA_K1_RES_HOST(i_, T_) if (index == i_) { if (n_res) *n_res = k1_n_res<T_>; if (k1_n_res<T_> > 0) k1_res_host<T_>(n, q_active, qpos_env, out); return MOPA_OK; }
+    MOPA_K1_BAKED_SCENES(MOPA_K1_RES_HOST)
+#undef MOPA_K1_RES_HOST
     return fail(MOPA_ERR_INVALID_ARG, "no baked scene #" + std::to_string(index));
 }
 

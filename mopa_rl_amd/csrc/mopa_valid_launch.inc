@@ -283,3 +283,9 @@ extern "C" int mopa_is_valid_batch(MopaScene *S, const double *q_active, const d
                                    int64_t samples_per_env, uint8_t *valid, double *min_dist, void *stream) {
     return launch_is_valid(S, q_active, qpos_env, N, samples_per_env, nullptr, valid, min_dist, stream, nullptr, true);
 }
+// the same with the state count on the device (*n_dev <= N; N sizes the launch): states from *n_dev on are neither read nor written
+extern "C" int mopa_is_valid_batch_counted(MopaScene *S, const double *q_active, const double *qpos_env, int64_t N, int64_t samples_per_env,
+                                           uint8_t *valid, double *min_dist, const int64_t *n_dev, void *stream) {
+    if (!n_dev) return fail(MOPA_ERR_INVALID_ARG, "null argument");
+    return launch_is_valid(S, q_active, qpos_env, N, samples_per_env, nullptr, valid, min_dist, stream, reinterpret_cast<const long long *>(n_dev), true);
+}

@@ -35,12 +35,31 @@ struct K1Generic {
 };
 #include "mopa_valid_v5_baked.inc"
 
+// Resident pairs of a baked scene (TR::res, chosen by tools/bake_k1_scenes.py): moving-moving pairs of a closed-form class that
+// pass A keeps in most states.  Both poses are in the owning lane's registers during the walk, so the lane evaluates the pair
+// there, on full lanes, with the operands and the routine v5_flush would use (same bits) -- instead of survivor bit, entry,
+// compaction, slab gather and a batch that costs the same for 3 lanes as for 64.  Pass A skips the pair's table entry.
+// MOPA_V5_NO_RESIDENT: no pair is resident (the knock-out build of tools/k1_knock.sh).
+constexpr int kResMax = 2;
+#ifdef MOPA_V5_NO_RESIDENT
+template <class TR> constexpr int k1_n_res = 0;
+#else
+template <class TR> constexpr int k1_n_res = TR::n_res;
+#endif
+template <class TR>
+MOPA_HD constexpr bool k1_is_resident(int M, int K) {
+    for (int r = 0; r < k1_n_res<TR>; r++)
+        if (TR::res[r][0] == M && TR::res[r][1] == K) return true;
+    return false;
+}
+
 // pass A of a baked scene, one candidate pair (entry padr[M] + K of the table): the same FP32 arithmetic and compares as
 // the generic loops of k_is_valid_v5, with the table values as literals.  An inscribed-ball bound of 0 (no bound) is
 // never exceeded (d2 >= 0 or NaN), so its test is left out.
 template <class TR, int M, bool WANT_MD, int K>
 MOPA_D void v5_cull_baked(float cx, float cy, float cz, const float *cen_lane, unsigned &surv_lo, unsigned &surv_hi,
                           unsigned long long &deep_mask, unsigned long long &any_kept) {
+    if constexpr (!k1_is_resident<TR>(M, K)) {      // (a resident pair is decided by the walk: no bit, no inscribed-ball test)
     constexpr int e = TR::padr[M] + K;
     constexpr float c0 = __builtin_bit_cast(float, TR::tab[8 * e + 0]), c1 = __builtin_bit_cast(float, TR::tab[8 * e + 1]);
     constexpr float c2 = __builtin_bit_cast(float, TR::tab[8 * e + 2]), c3 = __builtin_bit_cast(float, TR::tab[8 * e + 3]);
@@ -63,6 +82,7 @@ MOPA_D void v5_cull_baked(float cx, float cy, float cz, const float *cen_lane, u
     if constexpr (K < 32) surv_lo |= keep ? (1u << K) : 0u;
     else surv_hi |= keep ? (1u << (K - 32)) : 0u;
     any_kept |= __ballot(keep) ? (1ull << K) : 0ull;
+    }
 }
 template <class TR, int M, bool WANT_MD, int... K>
 MOPA_D void v5_pass_a_baked(float cx, float cy, float cz, const float *cen_lane, unsigned &surv_lo, unsigned &surv_hi,
@@ -92,13 +112,51 @@ struct K1FkRegs {
     double mat[9];
     V3 save_pos[TR::n_save];
     Q4 save_quat[TR::n_save];
+    V3 res_pos[kResMax];       // resident pair r: what its routine needs of the geom posed first -- the centre,
+    Q4 res_quat[kResMax];      // and for a capsule the quaternion
 };
+// posed record of one geom of a resident pair, as v5_load_rec2 builds it from the slab: position, quat2mat of the geom
+// quaternion, sizes.  (A sphere's matrix is read by none of the resident classes' routines: left zero, its quaternion is not kept.)
+template <int TYPE>
+MOPA_HD void k1_res_rec(double (&R)[15], const V3 &p, const Q4 &q, const unsigned long long *size) {
+    R[GO_POS] = p.x; R[GO_POS + 1] = p.y; R[GO_POS + 2] = p.z;
+    if constexpr (TYPE != G_SPHERE) {
+        quat2mat(R + GO_MAT, q);
+    } else {
+#pragma unroll
+        for (int i = 0; i < 9; i++) R[GO_MAT + i] = 0.0;
+    }
+    R[GO_SIZE] = k1_bits(size[0]); R[GO_SIZE + 1] = k1_bits(size[1]); R[GO_SIZE + 2] = k1_bits(size[2]);
+}
+// moving geom M has its pose: the first geom of resident pair R is kept, the second one completes the pair -> `sink.resident(R, dist)`
+template <class TR, int M, int R, class Sink>
+MOPA_HD void k1_fk_resident(K1FkRegs<TR> &r, const V3 &gp, const Q4 &gq, Sink &sink) {
+    constexpr int sa = TR::res[R][2], sb = TR::res[R][3], code = TR::res[R][4], ta = TR::res[R][5], tb = TR::res[R][6];
+    static_assert(sa != sb && ta <= tb && (code == PC_SPHERE_SPHERE || code == PC_SPHERE_CAPSULE || code == PC_CAPSULE_CAPSULE),
+                  "resident pair: two geoms in routine order, closed-form class");
+    constexpr bool a_first = sa < sb;           // (the walk poses the moving geoms in slot order)
+    if constexpr (M == (a_first ? sa : sb)) {
+        r.res_pos[R] = gp;
+        if constexpr ((a_first ? ta : tb) != G_SPHERE) r.res_quat[R] = gq;
+        else r.res_quat[R] = Q4{1.0, 0.0, 0.0, 0.0};
+    } else if constexpr (M == (a_first ? sb : sa)) {
+        double R1[15], R2[15];
+        k1_res_rec<ta>(R1, a_first ? r.res_pos[R] : gp, a_first ? r.res_quat[R] : gq, TR::res_size[R]);
+        k1_res_rec<tb>(R2, a_first ? gp : r.res_pos[R], a_first ? gq : r.res_quat[R], TR::res_size[R] + 3);
+        sink.resident(R, geom_dist<false>(code, R1, ta, R2, tb));
+    }
+}
+template <class TR, int M, class Sink, int... R>
+MOPA_HD void k1_fk_residents(K1FkRegs<TR> &r, const V3 &gp, const Q4 &gq, Sink &sink, std::integer_sequence<int, R...>) {
+    (k1_fk_resident<TR, M, R>(r, gp, gq, sink), ...);
+}
 template <class TR, int M, class Sink>
-MOPA_HD void k1_fk_geom(const K1FkRegs<TR> &r, Sink &sink) {
+MOPA_HD void k1_fk_geom(K1FkRegs<TR> &r, Sink &sink) {
     constexpr const unsigned long long *gd = TR::fk_gd[M];   // lpos[3] lquat[4]
     const V3 gp = add3(r.pos, mat_vec(r.mat, V3{k1_bits(gd[0]), k1_bits(gd[1]), k1_bits(gd[2])}));
     const Q4 gq = quat_mul(r.quat, Q4{k1_bits(gd[3]), k1_bits(gd[4]), k1_bits(gd[5]), k1_bits(gd[6])});
     sink(M, gp, gq);
+    k1_fk_residents<TR, M>(r, gp, gq, sink, std::make_integer_sequence<int, k1_n_res<TR>>{});
 }
 template <class TR, int B, class Sink, int... G>
 MOPA_HD void k1_fk_body(K1FkRegs<TR> &r, const double *qact, const double *sn, const double *cs, const double *pv, Sink &sink,
@@ -147,6 +205,7 @@ MOPA_HD void k1_fk_body(K1FkRegs<TR> &r, const double *qact, const double *sn, c
 template <class TR, class Sink, int... B>
 MOPA_HD void k1_fk_baked(const double *qa_row, const double *env_row, Sink &sink, std::integer_sequence<int, B...>) {
     static_assert(TR::na <= 8 && TR::n_pq >= 1 && TR::n_save >= 1, "baked walk: at most 8 active values; array sizes padded to 1");
+    static_assert(TR::n_res <= kResMax, "baked walk: at most kResMax resident pairs");
     double qact[TR::na], pv[TR::n_pq], sn[TR::na], cs[TR::na];
 #pragma unroll
     for (int a = 0; a < TR::na; a++) qact[a] = qa_row[a];
@@ -171,6 +230,8 @@ struct V5FkSink {
         float *cp = cen + (size_t)m * 3 * 64;
         cp[0] = (float)gp.x; cp[64] = (float)gp.y; cp[128] = (float)gp.z;
     }
+    double res_d[kResMax];   // distances of the resident pairs of this lane's state
+    MOPA_D void resident(int r, double d) { res_d[r] = d; }
 };
 
 struct V5Lds {
@@ -440,6 +501,7 @@ __global__ __launch_bounds__(kBlock, TR::kBaked ? 2 : 1) void k_is_valid_v5(Scen
         // ================= phase 1: forward kinematics, poses -> slab, FP32 centres -> LDS =================
         // (MOPA_V5_FK_REPS / _CULL_REPS / _KO_PASSB / _KO_DRAIN: knock-in / knock-out builds of tools/k1_knock.sh -- a phase run N
         //  times, or left out, and the kernel timed: per-phase cycle counters mislead when two waves share a SIMD)
+        double res_d[kResMax] = {};      // baked scenes: the resident pairs' distances for this lane's state
 #ifdef MOPA_V5_FK_REPS
         for (int fk_rep = 0; fk_rep < MOPA_V5_FK_REPS; fk_rep++)
 #endif
@@ -448,8 +510,10 @@ __global__ __launch_bounds__(kBlock, TR::kBaked ? 2 : 1) void k_is_valid_v5(Scen
             //  straight-line walk are hoisted out of the tile loop and held in VGPR pairs for the whole kernel)
             double *fk_slab = slab;
             asm volatile("" : "+v"(fk_slab));
-            V5FkSink sink{fk_slab, q.cen + lane};
+            V5FkSink sink{fk_slab, q.cen + lane, {}};
             k1_fk_baked<TR>(qa_row, env_row, sink, std::make_integer_sequence<int, TR::nmb>{});
+#pragma unroll
+            for (int r = 0; r < kResMax; r++) res_d[r] = sink.res_d[r];
 #ifdef MOPA_V5_FK_REPS
             asm volatile("" ::: "memory");   // each repetition loads, computes and stores again
 #endif
@@ -639,6 +703,25 @@ __global__ __launch_bounds__(kBlock, TR::kBaked ? 2 : 1) void k_is_valid_v5(Scen
         // ================= phase 2: FP32 broad phase out of LDS, queue, FP64 narrow phase =================
         bool dead = !act;
         bool need_mesh = false;
+        if constexpr (TR::kBaked) {
+            if constexpr (k1_n_res<TR> > 0) {
+                // the resident pairs are decided: the verdict as v5_flush folds it (d <= thr), the depth through the same
+                // order-preserving image; a verdict-only lane that is invalid builds no entries (as under deep_mask below)
+                bool rbad = false;
+                unsigned long long rmd = f64_sortable(0.0);
+#pragma unroll
+                for (int r = 0; r < k1_n_res<TR>; r++) {
+                    rbad = rbad || (res_d[r] <= h.thr);
+                    const unsigned long long im = f64_sortable(res_d[r]);
+                    rmd = im < rmd ? im : rmd;
+                }
+                rbad = rbad && act;
+                const unsigned long long rmask = __ballot(rbad);
+                if (lane == 0 && rmask) *q.bad |= rmask;
+                if (WANT_MD) q.md[lane] = rmd;
+                else dead = dead || rbad;
+            }
+        }
         int n_ent = 0;
         unsigned present = 0u;     // pair classes that have entries in the buffer
         for (int m = 0; m < h.nmg; m++) {

@@ -18,6 +18,8 @@ import os
 import struct
 import sys
 
+import numpy as np
+
 ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
 sys.path.insert(0, ROOT)
 
@@ -122,6 +124,96 @@ def fk_program(ex: dict) -> dict:
     return {"na": na, "nq": H["nq"], "nmb": nmb, "n_pq": n_pq, "n_save": n_save, "bodies": bodies, "bd": bd, "gd": gd, "sf": sf, "act_ref": act_ref, "pq_adr": pq_adr}
 
 
+RESIDENT_CLASSES = (4, 5, 8)      # PC_SPHERE_SPHERE, PC_SPHERE_CAPSULE, PC_CAPSULE_CAPSULE: closed-form routines of a few dozen operations
+RESIDENT_MAX = 2
+RESIDENT_MIN_SURVIVAL = 0.75
+RESIDENT_SAMPLE, RESIDENT_SEED = 2048, 20
+
+
+def resident_sample(pi, env: str, n: int, seed: int):
+    """Full qpos rows of the seeded sample behind the residency choice: active joints half uniform in the joint box, half near
+    the initial pose; gripper slides uniform in their range and the free-jointed object at its nominal pose + U(+-0.05) in xy
+    (the passive block of bench.make_inputs, drawn per state)."""
+    from mopa_rl_amd.scene import default_qpos
+    m = pi.model
+    rng = np.random.default_rng(seed)
+    row = default_qpos(env, m)
+    act = np.asarray(pi.ref_joint_pos_indexes)
+    lo, hi = np.asarray(pi.jnt_minimum), np.asarray(pi.jnt_maximum)
+    q = np.repeat(row[None], n, axis=0)
+    qa = rng.uniform(lo, hi, size=(n, len(act)))
+    qa[n // 2:] = np.clip(row[act] + rng.normal(0.0, 0.3, size=(n - n // 2, len(act))), lo, hi)
+    q[:, act] = qa
+    for name in ("rc_close", "lc_close"):
+        if name in m.jnt_names:
+            j = m.joint_name2id(name)
+            a, (r0, r1) = int(m.jnt_qposadr[j]), m.jnt_range[j]
+            q[:, a] = rng.uniform(r0, r1, size=n)
+    free = [int(m.jnt_qposadr[j]) for j in range(len(m.jnt_names)) if int(m.jnt_type[j]) == J_FREE]
+    if free:
+        q[:, free[0]: free[0] + 2] += rng.uniform(-0.05, 0.05, size=(n, 2))
+    return q
+
+
+def moving_pairs(ex: dict, tab, padr, nmov):
+    """The table's moving-moving entries: (owner slot M, entry K of the owner, partner slot, pair class, owner is geom 2)."""
+    out = []
+    for m in range(ex["nmg"]):
+        for k in range(nmov[m]):
+            fl = int(tab[8 * (padr[m] + k) + 7])
+            assert (fl >> 13) & 1, "an entry of the moving group without a moving partner"
+            out.append((m, k, (fl >> 14) & 0xFF, (fl >> 8) & 0xF, (fl >> 12) & 1))
+    return out
+
+
+def survival_rates(pi, ex: dict, tab, padr, pairs, q):
+    """Share of the states `q` (full qpos rows) in which pass A's sphere test keeps each of `pairs`: the oracle's geom
+    centres rounded to FP32 against the table's own FP32 squared cull radius."""
+    from oracle import oracle as O
+    orc = O.OracleScene(pi.model, pi.passive_joint_idx, pi.ignored_contacts, pi.spec.contact_threshold)
+    o = hdr_int(ex, "o_mg_geom")
+    mg = [int(g) for g in ex["ints"][o: o + ex["nmg"]]]
+    cen = np.stack([orc.fk(row)[0][mg] for row in q]).astype(np.float32)       # [n][nmg][3]
+    rates = []
+    for (m, k, ps, _code, _g2) in pairs:
+        rs2 = np.float32(tab[8 * (padr[m] + k) + 3: 8 * (padr[m] + k) + 4].view("<f4")[0])
+        d = cen[:, m] - cen[:, ps]
+        d2 = (d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]
+        rates.append(float(np.count_nonzero(~(d2 > rs2))) / len(q))
+    return rates
+
+
+def resident_pairs(env: str, pi, ex: dict, fk: dict, tab, padr, nmov) -> list:
+    """The scene's resident pairs (at most RESIDENT_MAX, by survival rate): moving-moving pairs of a closed-form class that pass A
+    keeps in at least RESIDENT_MIN_SURVIVAL of a seeded sample of states -- the baked walk evaluates them in place, on full lanes,
+    instead of sending them through survivor bit, entry, compaction, gather and batch.  A speed heuristic: residency changes where
+    a pair is evaluated, never the result.  (Baked scenes have no tile-posed geoms: fk_program refuses them.)
+    Per pair: owner slot M, table entry K, geom slots in routine order (type 1 <= type 2, as v5_flush orders them), class, both
+    types, both sizes as 64-bit patterns of the exported blob, survival in percent (rounded down)."""
+    # the walk poses the moving geoms in slot order: "first / second posed" below is the smaller / larger slot
+    adr = [b[3] for b in fk["bodies"] if b[4] > 0]
+    assert adr == sorted(adr), "moving geoms are not posed in slot order"
+    cand = [p for p in moving_pairs(ex, tab, padr, nmov) if p[3] in RESIDENT_CLASSES]
+    if not cand:
+        return []
+    rates = survival_rates(pi, ex, tab, padr, cand, resident_sample(pi, env, RESIDENT_SAMPLE, RESIDENT_SEED))
+    order = sorted(range(len(cand)), key=lambda i: (-rates[i], cand[i][0], cand[i][1]))
+    o_geom, o_rec, o_type = hdr_int(ex, "o_mg_geom"), hdr_int(ex, "o_g_rec"), hdr_int(ex, "o_g_type")
+    ints, bits = ex["ints"].astype("<i4"), ex["dbl"].astype("<f8").view("<u8")
+    out = []
+    for i in order[:RESIDENT_MAX]:
+        if rates[i] < RESIDENT_MIN_SURVIVAL:
+            break
+        m, k, ps, code, owner_is_g2 = cand[i]
+        sa, sb = (ps, m) if owner_is_g2 else (m, ps)
+        ga, gb = int(ints[o_geom + sa]), int(ints[o_geom + sb])
+        ta, tb = int(ints[o_type + ga]), int(ints[o_type + gb])
+        assert ta <= tb and sa != sb
+        size = [int(x) for x in bits[o_rec + 16 * ga + 12: o_rec + 16 * ga + 15]] + [int(x) for x in bits[o_rec + 16 * gb + 12: o_rec + 16 * gb + 15]]
+        out.append({"row": [m, k, sa, sb, code, ta, tb], "size": size, "pct": int(100.0 * rates[i])})
+    return out
+
+
 def bake(env: str, name: str) -> str:
     pi, args = scene_args(env)
     ex = _lib.k1_export(*args)
@@ -186,7 +278,15 @@ def bake(env: str, name: str) -> str:
     L += [f"        {u64(f)}," for f in fk["sf"]]
     L += ["    };",
           f"    static constexpr unsigned long long fk_act_ref[na] = {u64(fk['act_ref'])};",
-          f"    static constexpr int fk_pq_adr[n_pq] = {ints(fk['pq_adr'] + [0] * (n_pq - fk['n_pq']))};",
+          f"    static constexpr int fk_pq_adr[n_pq] = {ints(fk['pq_adr'] + [0] * (n_pq - fk['n_pq']))};"]
+    res = resident_pairs(env, pi, ex, fk, tab, padr, nmov)
+    n_res = max(len(res), 1)
+    L += ["    // resident pairs (evaluated inside the walk, skipped by pass A): owner slot M, table entry K, geom slots in routine order",
+          "    // (type 1 <= type 2), pair class, both types; then both sizes.  Chosen by pass A's survival rate on a seeded sample:",
+          "    // " + (", ".join(f"({r['row'][0]}, {r['row'][1]}) kept in {r['pct']} %" for r in res) or "none"),
+          f"    static constexpr int n_res = {len(res)};",
+          f"    static constexpr int res[{n_res}][7] = {{" + ", ".join(ints(r["row"]) for r in res or [{"row": [-1, -1, 0, 0, 0, 0, 0]}]) + "};",
+          f"    static constexpr unsigned long long res_size[{n_res}][6] = {{" + ", ".join(u64(r["size"]) for r in res or [{"size": [0] * 6}]) + "};",
           "};"]
     return "\n".join(L)
 

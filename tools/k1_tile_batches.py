@@ -1,0 +1,143 @@
+"""What K1's narrow phase does per 64-state tile (CPU model, no GPU): entries built, entries evaluated, same-class batches and
+their lane utilisation -- today's pipeline, and with one moving-moving pair taken out of it (evaluated by the forward-kinematics
+walk instead: a resident pair, DESIGN.md "K1 on a baked scene").  Reads the oracle and the scene only.
+
+The model: the oracle's poses and pair distances; the scene's pair pruning and tightened cull radii (model.meta); the kernel's
+cull rules in FP64 (moving pairs: bounding spheres or the tightened radius; static partners: sphere, then the partner's world AABB
+against the owner's bounding radius; planes: the plane test); verdict-only early-out -- the classes are drained cheapest first, and
+an entry whose state an earlier class has already made invalid is dropped at compaction.  Tiles are 64 states of one kind, drawn
+with tests/conftest.sample_states.  A batch costs the same for 3 lanes as for 64, so batches per tile is the figure to watch.
+
+    python tools/k1_tile_batches.py [--tiles 16] [--resident head,right_l2]
+"""
+import argparse
+import collections
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+from conftest import sample_states  # noqa: E402
+from mopa_rl_amd.scene import planner_inputs  # noqa: E402
+from oracle import oracle as O  # noqa: E402
+
+G_PLANE, G_SPHERE, G_CAPSULE, G_CYLINDER, G_BOX = 0, 2, 3, 5, 6
+# pair classes in drain order (cheapest first), as the library's PairCode
+CLASSES = {(G_PLANE, G_SPHERE): 0, (G_PLANE, G_CAPSULE): 1, (G_PLANE, G_CYLINDER): 2, (G_PLANE, G_BOX): 3, (G_SPHERE, G_SPHERE): 4,
+           (G_SPHERE, G_CAPSULE): 5, (G_SPHERE, G_CYLINDER): 6, (G_SPHERE, G_BOX): 7, (G_CAPSULE, G_CAPSULE): 8, (G_CAPSULE, G_BOX): 9,
+           (G_BOX, G_BOX): 10, (G_CAPSULE, G_CYLINDER): 11, (G_CYLINDER, G_CYLINDER): 11, (G_CYLINDER, G_BOX): 11}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--env", default="SawyerPushObstacle-v0")
+    ap.add_argument("--tiles", type=int, default=16, help="tiles of 64 states per kind")
+    ap.add_argument("--resident", default="head,right_l2", help="bodies of the pair taken out of the entry pipeline")
+    a = ap.parse_args()
+    pi = planner_inputs(a.env)
+    m = pi.model
+    thr = pi.spec.contact_threshold
+    orc = O.OracleScene(m, pi.passive_joint_idx, pi.ignored_contacts, thr)
+    T, S = m.geom_type, m.geom_size
+    ign = set(tuple(p) for p in pi.ignored_contacts)
+    never = {(int(x), int(y)) for x, y in m.meta.get("never_violating_pairs") or []}
+    at = m.meta.get("never_violating_pairs_thr") or {}
+    if at and thr <= float(at.get("threshold", -np.inf)):
+        never |= {(int(x), int(y)) for x, y in at.get("pairs") or []}
+    cr = m.meta.get("pair_cull_radius") or {}
+    tight = {(int(x), int(y)): float(r) for x, y, r in cr.get("pairs") or []} if cr and thr <= float(cr.get("threshold", -np.inf)) else {}
+
+    def moving(b):
+        while b > 0:
+            if m.body_jntnum[b] > 0:
+                return True
+            b = int(m.body_parent[b])
+        return False
+
+    mov = [moving(int(b)) for b in m.geom_body]
+    rb = [{G_PLANE: 1e9, G_SPHERE: s[0], G_CAPSULE: s[0] + s[1], G_CYLINDER: np.hypot(s[0], s[1])}.get(int(t), np.linalg.norm(s)) for t, s in zip(T, S)]
+
+    def extent(g, R):       # world AABB half extents of a static partner
+        t, s, ax = int(T[g]), S[g], R[:, 2]
+        if t == G_SPHERE:
+            return np.full(3, s[0])
+        if t == G_CAPSULE:
+            return s[0] + s[1] * np.abs(ax)
+        if t == G_CYLINDER:
+            return s[1] * np.abs(ax) + s[0] * np.sqrt(np.maximum(0.0, 1.0 - ax * ax))
+        return np.abs(R) @ s if t == G_BOX else np.full(3, rb[g])
+
+    pairs = []              # (oracle pair index, geom a, geom b, class)
+    for k, (x, y) in enumerate(m.pair_geom):
+        x, y = int(x), int(y)
+        ids = (min(int(m.geom_mjid[x]), int(m.geom_mjid[y])), max(int(m.geom_mjid[x]), int(m.geom_mjid[y])))
+        if ids in ign or (x, y) in never or (y, x) in never or not (mov[x] or mov[y]):
+            continue
+        t = tuple(sorted((int(T[x]), int(T[y]))))
+        if t in CLASSES:
+            pairs.append((k, x, y, CLASSES[t]))
+    want = set(a.resident.split(","))
+    res = [k for k, x, y, _ in pairs if {m.body_names[int(m.geom_body[x])], m.body_names[int(m.geom_body[y])]} == want and mov[x] and mov[y]]
+    assert len(res) == 1, f"no single moving pair on bodies {a.resident}"
+    res = res[0]
+
+    def survivors(q):
+        gp, gm = orc.fk(q)
+        pd = orc.pair_dist(q)
+        out = []
+        for k, x, y, code in pairs:
+            d = gp[x] - gp[y]
+            if T[x] == G_PLANE or T[y] == G_PLANE:
+                p, g = (x, y) if T[x] == G_PLANE else (y, x)
+                keep = np.dot(gp[g] - gp[p], gm[p][:, 2]) <= rb[g]
+            elif mov[x] and mov[y]:
+                keep = np.linalg.norm(d) <= min(rb[x] + rb[y], tight.get((x, y), tight.get((y, x), 1e9)))
+            else:
+                st, mv = (x, y) if not mov[x] else (y, x)
+                keep = np.linalg.norm(d) <= rb[x] + rb[y] and np.all(np.abs(d) <= extent(st, gm[st]) + rb[mv])
+            if keep:
+                out.append((k, code, pd[k] <= thr))
+        return out
+
+    def tile_stats(states, without):
+        """(entries built, entries evaluated, batches) of one tile; `without`: the resident pair's index or None"""
+        bad = np.zeros(len(states), bool)
+        ents = collections.defaultdict(list)
+        for i, sv in enumerate(states):
+            if without is not None and any(k == without and hit for k, _, hit in sv):
+                bad[i] = True           # decided by the walk: the lane builds no entries
+                continue
+            for k, code, hit in sv:
+                if k != without:
+                    ents[code].append((i, hit))
+        built = sum(len(v) for v in ents.values())
+        evaluated = batches = 0
+        for code in sorted(ents):
+            live = [(i, hit) for i, hit in ents[code] if not bad[i]]
+            evaluated += len(live)
+            batches += (len(live) + 63) // 64
+            for i, hit in live:
+                bad[i] |= hit
+        return built, evaluated, batches, 1.0 - bad.mean()
+
+    print(f"{a.env}: {len(pairs)} candidate pairs after pruning, {a.tiles} tiles of 64 states per kind; resident pair: {a.resident}")
+    print(f"{'tile kind':10s} {'pipeline':22s} {'valid':>6s} {'built':>7s} {'evaluated':>10s} {'batches':>8s} {'lane util':>10s}")
+    for kind, seed in (("uniform", 1), ("near", 2)):
+        qa, row = sample_states(pi, 64 * a.tiles, seed, kind)
+        q = np.repeat(row, len(qa), axis=0)
+        q[:, np.asarray(pi.ref_joint_pos_indexes)] = qa
+        sv = [survivors(r) for r in q]
+        for name, without in (("today", None), ("pair in the walk", res)):
+            st = np.array([tile_stats(sv[64 * t: 64 * t + 64], without) for t in range(a.tiles)]).mean(axis=0)
+            print(f"{kind:10s} {name:22s} {st[3]:6.2f} {st[0]:7.1f} {st[1]:10.1f} {st[2]:8.2f} {st[1] / (64 * st[2]):10.2f}")
+        n_res = sum(1 for s in sv if any(k == res for k, _, _ in s))
+        print(f"{kind:10s} the pair survives the cull in {n_res / len(sv):.2f} of the states, violates in "
+              f"{sum(1 for s in sv if any(k == res and hit for k, _, hit in s)) / len(sv):.3f}")
+
+
+if __name__ == "__main__":
+    main()
