@@ -227,6 +227,12 @@ int mopa_k1_baked_fk_host(int index, int64_t n, const double *q_active, const do
 /* the resident pairs of baked scene #index (pairs the baked walk evaluates in place), as the walk computes them on the host:
    out[n][n_res] distances in the order of the traits' list; *n_res (nullable) receives their number */
 int mopa_k1_baked_resident_host(int index, int64_t n, const double *q_active, const double *qpos_env, double *out, int32_t *n_res);
+/* the broad phase's test of the static non-plane partners of baked scene #index, per state, on the host: keep_new / keep_old
+   [n][n_ent] (n_ent: entries of the FP32 pair table, returned through the nullable *n_ent) hold 1 / 0 for such an entry kept /
+   culled under the built rule (per-axis reach of capsule and cylinder owners) and under the bounding-radius rule, 2 for every
+   other entry; axis[n][nmg][3] (float): the |axis| magnitudes the kernel unpacks for those owners, -1 for the other geoms */
+int mopa_k1_baked_static_host(int index, int64_t n, const double *q_active, const double *qpos_env, uint8_t *keep_new, uint8_t *keep_old,
+                              float *axis, int32_t *n_ent);
 
 /* N states: state i = qpos_env[i / samples_per_env] with its active entries replaced by q_active[i].
  * valid[i] = 1 iff no non-ignored pair has dist <= contact_threshold.

@@ -620,7 +620,7 @@ extern "C" int mopa_scene_hdr_offset(const char *field) {
     MOPA_HDR_FIELD(o_pq_adr) MOPA_HDR_FIELD(o_mg_geom) MOPA_HDR_FIELD(thr)
     MOPA_HDR_FIELD(o_mb_parent) MOPA_HDR_FIELD(o_chain_adr) MOPA_HDR_FIELD(o_chain_len) MOPA_HDR_FIELD(o_chain_items) MOPA_HDR_FIELD(o_g_mb)
     MOPA_HDR_FIELD(o_mb_load) MOPA_HDR_FIELD(o_mb_save) MOPA_HDR_FIELD(pfk_maxlen) MOPA_HDR_FIELD(n_gp) MOPA_HDR_FIELD(npair) MOPA_HDR_FIELD(o_pairs)
-    MOPA_HDR_FIELD(o_g_rec) MOPA_HDR_FIELD(o_g_type)
+    MOPA_HDR_FIELD(o_g_rec) MOPA_HDR_FIELD(o_g_type) MOPA_HDR_FIELD(o_g_aabb)
 #undef MOPA_HDR_FIELD
     return -1;
 }
@@ -635,13 +635,55 @@ struct K1HostSink {
         quat2mat(o + 3, gq);
     }
     void resident(int, double) {}
+    void axis(int, unsigned) {}
 };
 // the resident pairs' distances alone (what the kernel folds into verdict and depth before pass A)
 struct K1ResHostSink {
     double *out;   // [n_res]
     void operator()(int, V3, Q4) {}
     void resident(int r, double d) { out[r] = d; }
+    void axis(int, unsigned) {}
 };
+// what pass A reads: the FP32 centres and the packed axis words, as V5FkSink leaves them in LDS
+struct K1PassAHostSink {
+    float *cen;       // [nmg][3]
+    unsigned *axw;    // [n_ax]
+    void operator()(int m, V3 gp, Q4) { cen[3 * m] = (float)gp.x; cen[3 * m + 1] = (float)gp.y; cen[3 * m + 2] = (float)gp.z; }
+    void resident(int, double) {}
+    void axis(int slot, unsigned word) { axw[slot] = word; }
+};
+// static partner K of geom slot M under the built rule (keep_new) and the bounding-radius rule (keep_old); other entries stay 2
+template <class TR, int M, int K>
+void k1_static_host_pair(const float *c, float hx, float hy, float hz, uint8_t *keep_new, uint8_t *keep_old) {
+    if constexpr (K >= TR::nmov[M] && K < TR::nmov[M] + TR::nstat[M]) {
+        keep_new[TR::padr[M] + K] = k1_static_keep<TR, M, K, k1_axis_on<TR>>(c[0], c[1], c[2], hx, hy, hz) ? 1 : 0;
+        keep_old[TR::padr[M] + K] = k1_static_keep<TR, M, K, false>(c[0], c[1], c[2], 0.0f, 0.0f, 0.0f) ? 1 : 0;
+    }
+}
+template <class TR, int M, int... K>
+void k1_static_host_geom(const float *cen, const unsigned *axw, uint8_t *keep_new, uint8_t *keep_old, float *axis, std::integer_sequence<int, K...>) {
+    float hx = 0.0f, hy = 0.0f, hz = 0.0f;
+    if constexpr (k1_axis_owner<TR>(M)) {
+        k1_axis_unpack(axw[TR::ax_slot[M]], axis[3 * M], axis[3 * M + 1], axis[3 * M + 2]);
+        k1_axis_reach<TR, M>(axw[TR::ax_slot[M]], hx, hy, hz);
+    }
+    (k1_static_host_pair<TR, M, K>(cen + 3 * M, hx, hy, hz, keep_new, keep_old), ...);
+}
+template <class TR, int... M>
+void k1_static_host(int64_t n, const double *q_active, const double *qpos_env, uint8_t *keep_new, uint8_t *keep_old, float *axis, std::integer_sequence<int, M...>) {
+    constexpr int n_ent = (int)(sizeof(TR::tab) / (8 * sizeof(unsigned)));
+    for (int64_t s = 0; s < n; s++) {
+        float cen[3 * TR::nmg];
+        unsigned axw[k1_axis_words<TR> / 64 + 1] = {};
+        K1PassAHostSink sink{cen, axw};
+        k1_fk_baked<TR>(q_active + (size_t)s * TR::na, qpos_env + (size_t)s * TR::nq, sink, std::make_integer_sequence<int, TR::nmb>{});
+        uint8_t *kn = keep_new + (size_t)s * n_ent, *ko = keep_old + (size_t)s * n_ent;
+        float *a = axis + (size_t)s * 3 * TR::nmg;
+        std::memset(kn, 2, n_ent); std::memset(ko, 2, n_ent);
+        for (int i = 0; i < 3 * TR::nmg; i++) a[i] = -1.0f;
+        (k1_static_host_geom<TR, M>(cen, axw, kn, ko, a, std::make_integer_sequence<int, TR::pnum[M]>{}), ...);
+    }
+}
 template <class TR>
 void k1_fk_host(int64_t n, const double *q_active, const double *qpos_env, double *out) {
     for (int64_t s = 0; s < n; s++) {
@@ -671,6 +713,20 @@ extern "C" int mopa_k1_baked_resident_host(int index, int64_t n, const double *q
 #define MOPA_K1_RES_HOST(i_, T_) if (index == i_) { if (n_res) *n_res = k1_n_res<T_>; if (k1_n_res<T_> > 0) k1_res_host<T_>(n, q_active, qpos_env, out); return MOPA_OK; }
     MOPA_K1_BAKED_SCENES(MOPA_K1_RES_HOST)
 #undef MOPA_K1_RES_HOST
+    return fail(MOPA_ERR_INVALID_ARG, "no baked scene #" + std::to_string(index));
+}
+
+// Pass A's static partners of baked scene #index on the host, per state: keep_new / keep_old [n][n_ent] (n_ent: the table's
+// entries) hold 1 / 0 for a static non-plane entry kept / culled by the built rule (axis extents, unless the build is a
+// MOPA_V5_NO_AXIS_CULL one) and by the bounding-radius rule, 2 for every other entry; axis [n][nmg][3]: the unpacked |axis| of
+// the axis owners as pass A reads it before the clamp, -1 for the other geoms.  *n_ent (nullable) receives the entry count.
+extern "C" int mopa_k1_baked_static_host(int index, int64_t n, const double *q_active, const double *qpos_env, uint8_t *keep_new, uint8_t *keep_old,
+                                         float *axis, int32_t *n_ent) {
+    if (n < 0 || (n > 0 && (!q_active || !qpos_env || !keep_new || !keep_old || !axis))) return fail(MOPA_ERR_INVALID_ARG, "null argument / negative count");
+#define MOPA_K1_STATIC_HOST(i_, T_) if (index == i_) { if (n_ent) *n_ent = (int32_t)(sizeof(T_::tab) / (8 * sizeof(unsigned))); \
+        k1_static_host<T_>(n, q_active, qpos_env, keep_new, keep_old, axis, std::make_integer_sequence<int, T_::nmg>{}); return MOPA_OK; }
+    MOPA_K1_BAKED_SCENES(MOPA_K1_STATIC_HOST)
+#undef MOPA_K1_STATIC_HOST
     return fail(MOPA_ERR_INVALID_ARG, "no baked scene #" + std::to_string(index));
 }
 

@@ -48,6 +48,14 @@ static K1FnV5 k1_kernel_v5(bool want_md, bool cen_lds, bool gate, int baked) {
     return nullptr;
 }
 
+// LDS words per wave of baked scene #baked's axis table (0: none)
+static int k1_baked_axis_words(int baked) {
+#define MOPA_K1_AXW(i_, T_) if (baked == i_) return k1_axis_words<T_>;
+    MOPA_K1_BAKED_SCENES(MOPA_K1_AXW)
+#undef MOPA_K1_AXW
+    return 0;
+}
+
 // allow the dynamic LDS size
 // the attribute is per function, not per scene: register the device maximum once so scenes of different sizes can
 // coexist in one process in any creation order (each launch still passes its own, checked, size)
@@ -143,6 +151,13 @@ static K1Plan k1_plan(const MopaScene *S, int64_t N, bool want_md, bool has_env_
     p.cen_lds = P.v5_cen_lds;
     p.baked = S->k1_baked;       // (set only for scenes with the centre table in LDS and no mesh pairs)
     p.ent_cap = want_md ? P.v5_ent_cap_md : S->hdr.v5_ent_cap;
+    if (p.baked) {
+        // the axis table of a baked scene (k1_axis_words, a multiple of 64 words) comes out of the entry buffer: the wave's LDS, and
+        // with it two workgroups per CU, stay as the scene compiler sized them.  No room for it: the generic kernel
+        const int ax = k1_baked_axis_words(p.baked);
+        if (p.ent_cap - ax >= 256) p.ent_cap -= ax;
+        else if (ax > 0) p.baked = 0;
+    }
     p.lane_lds = !p.v5 ? P.v2_lds_bytes : (want_md ? P.v5_lds_bytes_md : P.v5_lds_bytes);
     // rows the gate may hand over per launch (typically 1-2 % of the states have one): beyond it a state goes to the state list
     p.rows_cap = knobs.rows_cap_set ? knobs.rows_cap : std::min<long long>(std::max<long long>(4096, (long long)N / 2), 1ll << 22);      // (at most 1 GiB of rows; beyond: the state list)

@@ -32,6 +32,7 @@ constexpr float kCullEps = 2.0e-5f;
 // header) equals the baked one -- the same bytes the constants were taken from.
 struct K1Generic {
     static constexpr bool kBaked = false;
+    static constexpr int n_ax = 0;
 };
 #include "mopa_valid_v5_baked.inc"
 
@@ -53,11 +54,92 @@ MOPA_HD constexpr bool k1_is_resident(int M, int K) {
     return false;
 }
 
+// Axis extents of a baked scene (TR::ax_*, written by tools/bake_k1_scenes.py).  Pass A tests a static partner's world AABB
+// against the owner's bounding radius r + hl -- a ball, where a capsule or cylinder is long and thin.  Along world axis i such
+// an owner reaches r + hl |a_i| from its centre (a: its axis, the third column of its rotation; exact for a capsule, encloses
+// a cylinder), so for these owners the three box tests become |d_i| > c_i' + hl a_i, c_i' = partner half extent + r + kCullEps
+// (the three products once per owner, then one addition of a literal per pair and axis: gfx950 has no FMA form that takes
+// two scalar constants, and constants kept in registers across the tile loop were what the allocator spilled).
+// The walk forms |a_i| in FP32 from the geom quaternion and leaves it in LDS as ONE word per owner and lane, three
+// magnitudes of 10 bits each (k1_axis_word), next to the centre table; pass A unpacks it once per owner.
+// Conservative by construction -- the unpacked value is never below the FP64 |a_i|:
+//   * a_f, the FP32 value: the quaternion rounded to FP32 (4 x 2^-24 relative), three roundings per product term, the
+//     terms' magnitudes sum to <= 1  =>  |a_f - |a_i|| < 1e-6;
+//   * the word holds u = ceil(1023 a_f + kAxisBias) (one FMA: t >= 1023 a_f + 0.02 - 6.2e-5), so u / 1023 >= a_f + 1.9e-5
+//     > |a_i|; clipped at 1023, where u / 1023 = 1;
+//   * unpacking multiplies by kAxisStep, the FP32 number just ABOVE 1/1023: u kAxisStep rounded to nearest is >= u / 1023.
+// It exceeds |a_i| by less than kAxisSlack = 1e-3 (1.02 / 1023 + the 1e-6 above + two roundings): the bound is looser than
+// the exact extent by at most hl kAxisSlack.  What is left for kCullEps (2e-5) is what it covers in every other test: the centres' and the
+// half extents' rounding to FP32 (~1e-7 at metre scale) and the roundings of the product and the sum.  The unpacked value is
+// then clamped to TR::ax_max[M], the largest FP32 a for which c_i' + hl a, in the kernel's FP32 arithmetic, stays <= the
+// bounding-radius constant c_i for every static pair and axis of the owner (found by the bake script in that arithmetic;
+// both operations are monotone in a): the new bound never exceeds the bounding-radius one, which stays valid on its own
+// (a cylinder's bounding radius hypot(r, hl) is below r + hl), so the survivors are a subset of that rule's.
+// MOPA_V5_NO_AXIS_CULL: the bounding-radius constants for every static pair, no axis table (the knock-out build of tools/k1_knock.sh).
+constexpr float kAxisBias = 0.02f;
+constexpr float kAxisStep = __builtin_bit_cast(float, 0x3a802009u);     // nextafter(1.0f / 1023.0f, 1.0f)
+constexpr float kAxisSlack = 1.0e-3f;
+#ifdef MOPA_V5_NO_AXIS_CULL
+template <class TR> constexpr bool k1_axis_on = false;
+#else
+template <class TR> constexpr bool k1_axis_on = TR::n_ax > 0;
+#endif
+// moving geom slot M is a capsule or cylinder with static non-plane partners: it owns a word of the axis table
+template <class TR>
+MOPA_HD constexpr bool k1_axis_owner(int M) {
+    if constexpr (k1_axis_on<TR>) return TR::ax_slot[M] >= 0;
+    else return false;
+}
+// LDS words per wave of the axis table ([n_ax][64]); they are taken out of the entry buffer (mopa_valid_launch.inc: k1_plan)
+template <class TR>
+constexpr int k1_axis_words_of() {
+    if constexpr (k1_axis_on<TR>) return TR::n_ax * 64;
+    else return 0;
+}
+template <class TR> constexpr int k1_axis_words = k1_axis_words_of<TR>();
+MOPA_HD unsigned k1_axis_q10(float a) {
+    const float t = ceilf(fmaf(fabsf(a), 1023.0f, kAxisBias));
+    return t < 1023.0f ? (unsigned)t : 1023u;
+}
+MOPA_HD unsigned k1_axis_word(const Q4 &q) {
+    const float w = (float)q.w, x = (float)q.x, y = (float)q.y, z = (float)q.z;
+    const float ax = 2.0f * (x * z + w * y), ay = 2.0f * (y * z - w * x), az = ((w * w - x * x) - y * y) + z * z;   // quat2mat: M[2], M[5], M[8]
+    return k1_axis_q10(ax) | (k1_axis_q10(ay) << 10) | (k1_axis_q10(az) << 20);
+}
+MOPA_HD void k1_axis_unpack(unsigned word, float &ax, float &ay, float &az) {
+    ax = (float)(word & 1023u) * kAxisStep; ay = (float)((word >> 10) & 1023u) * kAxisStep; az = (float)(word >> 20) * kAxisStep;
+}
+// what pass A uses of owner M's word: hl |a_i|, with the unpacked magnitudes clamped to TR::ax_max[M]
+template <class TR, int M>
+MOPA_HD void k1_axis_reach(unsigned word, float &hx, float &hy, float &hz) {
+    constexpr float amax = __builtin_bit_cast(float, TR::ax_max[M]), hl = __builtin_bit_cast(float, TR::ax_hl[M]);
+    k1_axis_unpack(word, hx, hy, hz);
+    hx = hl * fminf(hx, amax); hy = hl * fminf(hy, amax); hz = hl * fminf(hz, amax);
+}
+// pass A's test of one static non-plane partner (entry padr[M] + K): sphere, then the partner's world AABB against the owner's
+// bounding radius -- or, AXIS and the owner has an axis, against its per-axis reach ((hx, hy, hz): k1_axis_reach)
+template <class TR, int M, int K, bool AXIS>
+MOPA_HD bool k1_static_keep(float cx, float cy, float cz, float hx, float hy, float hz) {
+    constexpr int e = TR::padr[M] + K;
+    constexpr float c0 = __builtin_bit_cast(float, TR::tab[8 * e + 0]), c1 = __builtin_bit_cast(float, TR::tab[8 * e + 1]);
+    constexpr float c2 = __builtin_bit_cast(float, TR::tab[8 * e + 2]), c3 = __builtin_bit_cast(float, TR::tab[8 * e + 3]);
+    const float dx = cx - c0, dy = cy - c1, dz = cz - c2;
+    if constexpr (AXIS && k1_axis_owner<TR>(M)) {
+        constexpr float e4 = __builtin_bit_cast(float, TR::ax_tab[3 * e + 0]), e5 = __builtin_bit_cast(float, TR::ax_tab[3 * e + 1]);
+        constexpr float e6 = __builtin_bit_cast(float, TR::ax_tab[3 * e + 2]);
+        return !((fmaf(dz, dz, fmaf(dy, dy, dx * dx)) > c3) | (fabsf(dx) > e4 + hx) | (fabsf(dy) > e5 + hy) | (fabsf(dz) > e6 + hz));
+    } else {
+        constexpr float c4 = __builtin_bit_cast(float, TR::tab[8 * e + 4]), c5 = __builtin_bit_cast(float, TR::tab[8 * e + 5]);
+        constexpr float c6 = __builtin_bit_cast(float, TR::tab[8 * e + 6]);
+        return !((fmaf(dz, dz, fmaf(dy, dy, dx * dx)) > c3) | (fabsf(dx) > c4) | (fabsf(dy) > c5) | (fabsf(dz) > c6));
+    }
+}
+
 // pass A of a baked scene, one candidate pair (entry padr[M] + K of the table): the same FP32 arithmetic and compares as
 // the generic loops of k_is_valid_v5, with the table values as literals.  An inscribed-ball bound of 0 (no bound) is
 // never exceeded (d2 >= 0 or NaN), so its test is left out.
 template <class TR, int M, bool WANT_MD, int K>
-MOPA_D void v5_cull_baked(float cx, float cy, float cz, const float *cen_lane, unsigned &surv_lo, unsigned &surv_hi,
+MOPA_D void v5_cull_baked(float cx, float cy, float cz, const float *cen_lane, float hx, float hy, float hz, unsigned &surv_lo, unsigned &surv_hi,
                           unsigned long long &deep_mask, unsigned long long &any_kept) {
     if constexpr (!k1_is_resident<TR>(M, K)) {      // (a resident pair is decided by the walk: no bit, no inscribed-ball test)
     constexpr int e = TR::padr[M] + K;
@@ -73,8 +155,7 @@ MOPA_D void v5_cull_baked(float cx, float cy, float cz, const float *cen_lane, u
         if constexpr (!WANT_MD && TR::tab[8 * e + 0] != 0u) deep_mask |= __ballot(d2 < c0);
         keep = !(d2 > c3);
     } else if constexpr (K < TR::nmov[M] + TR::nstat[M]) {   // static partner: sphere, then world AABB
-        const float dx = cx - c0, dy = cy - c1, dz = cz - c2;
-        keep = !((fmaf(dz, dz, fmaf(dy, dy, dx * dx)) > c3) | (fabsf(dx) > c4) | (fabsf(dy) > c5) | (fabsf(dz) > c6));
+        keep = k1_static_keep<TR, M, K, k1_axis_on<TR>>(cx, cy, cz, hx, hy, hz);
     } else {                                  // plane: (c4, c5, c6) is the normal
         const float dx = cx - c0, dy = cy - c1, dz = cz - c2;
         keep = !(fmaf(dz, c6, fmaf(dy, c5, dx * c4)) > c3);
@@ -87,7 +168,10 @@ MOPA_D void v5_cull_baked(float cx, float cy, float cz, const float *cen_lane, u
 template <class TR, int M, bool WANT_MD, int... K>
 MOPA_D void v5_pass_a_baked(float cx, float cy, float cz, const float *cen_lane, unsigned &surv_lo, unsigned &surv_hi,
                             unsigned long long &deep_mask, unsigned long long &any_kept, std::integer_sequence<int, K...>) {
-    (v5_cull_baked<TR, M, WANT_MD, K>(cx, cy, cz, cen_lane, surv_lo, surv_hi, deep_mask, any_kept), ...);
+    float hx = 0.0f, hy = 0.0f, hz = 0.0f;
+    if constexpr (k1_axis_owner<TR>(M))         // its word follows the centre table; unpacked once for all its static partners
+        k1_axis_reach<TR, M>(reinterpret_cast<const unsigned *>(cen_lane)[(3 * TR::nmg + TR::ax_slot[M]) * 64], hx, hy, hz);
+    (v5_cull_baked<TR, M, WANT_MD, K>(cx, cy, cz, cen_lane, hx, hy, hz, surv_lo, surv_hi, deep_mask, any_kept), ...);
 }
 // geom slot m (wave-uniform) -> its straight-line pass A
 template <class TR, bool WANT_MD, int... M>
@@ -156,6 +240,7 @@ MOPA_HD void k1_fk_geom(K1FkRegs<TR> &r, Sink &sink) {
     const V3 gp = add3(r.pos, mat_vec(r.mat, V3{k1_bits(gd[0]), k1_bits(gd[1]), k1_bits(gd[2])}));
     const Q4 gq = quat_mul(r.quat, Q4{k1_bits(gd[3]), k1_bits(gd[4]), k1_bits(gd[5]), k1_bits(gd[6])});
     sink(M, gp, gq);
+    if constexpr (k1_axis_owner<TR>(M)) sink.axis(TR::ax_slot[M], k1_axis_word(gq));
     k1_fk_residents<TR, M>(r, gp, gq, sink, std::make_integer_sequence<int, k1_n_res<TR>>{});
 }
 template <class TR, int B, class Sink, int... G>
@@ -232,10 +317,13 @@ struct V5FkSink {
     }
     double res_d[kResMax];   // distances of the resident pairs of this lane's state
     MOPA_D void resident(int r, double d) { res_d[r] = d; }
+    int ax_row;     // first row of the axis table, in rows of the centre table (3 nmg: it follows the centres)
+    MOPA_D void axis(int slot, unsigned word) { reinterpret_cast<unsigned *>(cen)[(ax_row + slot) * 64] = word; }
 };
 
 struct V5Lds {
-    float *cen;                 // [nmg][3][64]   geom centres of this tile, FP32
+    float *cen;                 // [nmg][3][64]   geom centres of this tile, FP32; baked scenes: then [n_ax][64] packed |axis| words of
+                                //                the capsule / cylinder owners (k1_axis_word)
     unsigned *ent;              // [h.v5_ent_cap]    lane | owner slot << 6 | pair class << 12 | table index << 16
     unsigned *bat;              // [kBatCapV5]    entries of ONE pair class, compacted for the narrow phase
     unsigned *bat2;             // [kBatCapV5]    cylinder pairs that failed the capsule pre-test: dense batches for MPR
@@ -244,6 +332,7 @@ struct V5Lds {
     bool tp;                    // this tile's states share one env row and the scene has tile-posed geoms: their slab rows hold ONE pose, in lane 0's place
 };
 // (the 64 depth words `md` exist only in the instantiations that report depths: the verdict-only kernels give that LDS to `ent`)
+// (a baked scene's axis table counts as entries: k_is_valid_v5 passes h.v5_ent_cap + k1_axis_words<TR>, the capacity the scene compiler sized)
 MOPA_HD int v5_lds_per_wave(int nmg, int ent_cap, bool want_md) { return ((nmg * 3 * 64 * 4) + ent_cap * 4 + 2 * kBatCapV5 * 4 + (want_md ? 64 * 8 : 0) + 8 + 15) & ~15; }
 
 // posed record (pos, mat, size) of geom g for the state of lane `sl` of the tile: moving geoms from the pose slab,
@@ -464,9 +553,14 @@ __global__ __launch_bounds__(kBlock, TR::kBaked ? 2 : 1) void k_is_valid_v5(Scen
     V5Lds q;
     {
         const int n_cen = CEN_LDS ? h.nmg : 0;
-        unsigned char *base = reinterpret_cast<unsigned char *>(s_tab + ((8 * h.n_gp + kTail * h.nmg + 3) & ~3)) + wave * v5_lds_per_wave(n_cen, h.v5_ent_cap, WANT_MD);
+        int ent_words = h.v5_ent_cap;
+        if constexpr (k1_axis_words<TR> > 0) ent_words += k1_axis_words<TR>;
+        unsigned char *base = reinterpret_cast<unsigned char *>(s_tab + ((8 * h.n_gp + kTail * h.nmg + 3) & ~3)) + wave * v5_lds_per_wave(n_cen, ent_words, WANT_MD);
         q.cen = reinterpret_cast<float *>(base);
+        // (a baked scene's axis table, [n_ax][64] words, sits between the centre table and the entries: a constant offset from the
+        //  centres, so neither the walk nor pass A holds an address for it)
         q.ent = reinterpret_cast<unsigned *>(q.cen + n_cen * 3 * 64);
+        if constexpr (k1_axis_words<TR> > 0) q.ent += k1_axis_words<TR>;
         q.bat = q.ent + h.v5_ent_cap;
         q.bat2 = q.bat + kBatCapV5;
         q.md = reinterpret_cast<unsigned long long *>(q.bat2 + kBatCapV5);
@@ -510,7 +604,7 @@ __global__ __launch_bounds__(kBlock, TR::kBaked ? 2 : 1) void k_is_valid_v5(Scen
             //  straight-line walk are hoisted out of the tile loop and held in VGPR pairs for the whole kernel)
             double *fk_slab = slab;
             asm volatile("" : "+v"(fk_slab));
-            V5FkSink sink{fk_slab, q.cen + lane, {}};
+            V5FkSink sink{fk_slab, q.cen + lane, {}, 3 * TR::nmg};
             k1_fk_baked<TR>(qa_row, env_row, sink, std::make_integer_sequence<int, TR::nmb>{});
 #pragma unroll
             for (int r = 0; r < kResMax; r++) res_d[r] = sink.res_d[r];

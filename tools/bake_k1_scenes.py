@@ -214,6 +214,54 @@ def resident_pairs(env: str, pi, ex: dict, fk: dict, tab, padr, nmov) -> list:
     return out
 
 
+G_CAPSULE, G_CYLINDER = 3, 5
+K_CULL_EPS = np.float32(2.0e-5)                 # kCullEps of mopa_valid_v5.inc
+K_AXIS_STEP = np.uint32(0x3A802009).view(np.float32)   # kAxisStep
+
+
+def axis_extents(ex: dict, tab, padr, nmov, nstat) -> dict:
+    """Axis owners of the scene -- moving capsules / cylinders with static non-plane partners -- and what pass A needs to test
+    those partners' world AABBs against the owner's per-axis reach r + hl |a_i| instead of its bounding radius (mopa_valid_v5.inc,
+    "Axis extents"): per moving geom slot the owner's index (-1: none), hl (FP32 bits) and the clamp ax_max; per table entry
+    the three constants c_i' = (float)H_i + ((float)r + kCullEps), in the FP32 arithmetic that builds the table's own
+    c_i = (float)H_i + ((float)rbound + kCullEps) (checked here against the table).  ax_max: the largest FP32 a for which the
+    kernel's c_i' + hl a -- FP32 product, FP32 sum, as numpy's float32 computes them -- stays <= c_i for every static pair and axis of
+    the owner (both operations are monotone in a, so it holds for every smaller a too)."""
+    nmg = ex["nmg"]
+    o_geom, o_rec, o_type, o_aabb, o_mgd = (hdr_int(ex, f) for f in ("o_mg_geom", "o_g_rec", "o_g_type", "o_g_aabb", "o_mgd"))
+    ints, dbl = ex["ints"].astype("<i4"), ex["dbl"].astype("<f8")
+    f32 = lambda w: np.uint32(w).view(np.float32)
+    bits = lambda f: int(np.float32(f).view(np.uint32))
+    slot, hl_bits, amax_bits, etab = [-1] * nmg, [0] * nmg, [0] * nmg, [0] * (3 * (len(tab) - 3 * nmg) // 8)
+    n_ax = 0
+    for m in range(nmg):
+        g = int(ints[o_geom + m])
+        if int(ints[o_type + g]) not in (G_CAPSULE, G_CYLINDER) or nstat[m] == 0:
+            continue
+        r, hl = np.float32(dbl[o_rec + 16 * g + 12]), np.float32(dbl[o_rec + 16 * g + 13])
+        rg_old, rg_new = np.float32(dbl[o_mgd + 8 * m + 7]) + K_CULL_EPS, r + K_CULL_EPS
+        both = []
+        for k in range(nmov[m], nmov[m] + nstat[m]):
+            e = padr[m] + k
+            pg = int(tab[8 * e + 7]) & 0xFF
+            for i in range(3):
+                H = np.float32(dbl[o_aabb + 3 * pg + i])
+                c_old, c_new = np.float32(H + rg_old), np.float32(H + rg_new)
+                assert bits(c_old) == int(tab[8 * e + 4 + i]), f"slot {m} entry {k}: the table's half extent is not (float)H + rg"
+                etab[3 * e + i] = bits(c_new)
+                both.append((c_old, c_new))
+        a = np.float32(1023.0) * K_AXIS_STEP            # the largest value pass A unpacks
+        guess = np.float32(min((float(co) - float(cn)) / float(hl) for co, cn in both)) * np.float32(1.0 + 1e-6)
+        a = min(a, guess)
+        while any(np.float32(cn + np.float32(hl * a)) > co for co, cn in both):
+            a = np.nextafter(a, np.float32(0.0))
+        assert a > 0
+        slot[m], hl_bits[m], amax_bits[m] = n_ax, bits(hl), bits(a)
+        n_ax += 1
+    return {"n_ax": n_ax, "slot": slot, "hl": hl_bits, "amax": amax_bits, "tab": etab,
+            "n_pairs": sum(nstat[m] for m in range(nmg) if slot[m] >= 0)}
+
+
 def bake(env: str, name: str) -> str:
     pi, args = scene_args(env)
     ex = _lib.k1_export(*args)
@@ -286,8 +334,24 @@ def bake(env: str, name: str) -> str:
           "    // " + (", ".join(f"({r['row'][0]}, {r['row'][1]}) kept in {r['pct']} %" for r in res) or "none"),
           f"    static constexpr int n_res = {len(res)};",
           f"    static constexpr int res[{n_res}][7] = {{" + ", ".join(ints(r["row"]) for r in res or [{"row": [-1, -1, 0, 0, 0, 0, 0]}]) + "};",
-          f"    static constexpr unsigned long long res_size[{n_res}][6] = {{" + ", ".join(u64(r["size"]) for r in res or [{"size": [0] * 6}]) + "};",
-          "};"]
+          f"    static constexpr unsigned long long res_size[{n_res}][6] = {{" + ", ".join(u64(r["size"]) for r in res or [{"size": [0] * 6}]) + "};"]
+    ax = axis_extents(ex, tab, padr, nmov, nstat)
+
+    def u32(v):
+        return "{" + ", ".join(f"0x{x:08x}u" for x in v) + "}"
+
+    L += [f"    // axis owners (moving capsules / cylinders with static non-plane partners: {ax['n_ax']} geoms, {ax['n_pairs']} of the {sum(nstat)} static pairs):",
+          "    // per moving geom slot its word in the tile's axis table (-1: none), hl and the clamp of |axis| (FP32 bits); per table entry",
+          "    // the static partner's AABB half extents + r + kCullEps (FP32 bits; 0: not a static pair of an axis owner)",
+          f"    static constexpr int n_ax = {ax['n_ax']};",
+          f"    static constexpr int ax_slot[nmg] = {ints(ax['slot'])};",
+          f"    static constexpr unsigned ax_hl[nmg] = {u32(ax['hl'])};",
+          f"    static constexpr unsigned ax_max[nmg] = {u32(ax['amax'])};",
+          f"    static constexpr unsigned ax_tab[{3 * n5}] = {{"]
+    for m in range(nmg):
+        for e in range(padr[m], padr[m] + pnum[m]):
+            L.append("        " + ", ".join(f"0x{w:08x}u" for w in ax["tab"][3 * e: 3 * e + 3]) + ",")
+    L += ["    };", "};"]
     return "\n".join(L)
 
 

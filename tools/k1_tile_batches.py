@@ -8,7 +8,15 @@ against the owner's bounding radius; planes: the plane test); verdict-only early
 an entry whose state an earlier class has already made invalid is dropped at compaction.  Tiles are 64 states of one kind, drawn
 with tests/conftest.sample_states.  A batch costs the same for 3 lanes as for 64, so batches per tile is the figure to watch.
 
-    python tools/k1_tile_batches.py [--tiles 16] [--resident head,right_l2]
+    python tools/k1_tile_batches.py [--tiles 16] [--resident head,right_l2] [--axis-extents] [--defer-small 0,4,8,16]
+
+--axis-extents: a capsule / cylinder owner is tested against a static partner's AABB with its per-axis reach r + hl |a_i| (a: the
+owner's axis) instead of its bounding radius (DESIGN.md "Axis extents in the baked pass A").
+--defer-small K[,K...]: with the resident pair in the walk, the remainder of a class (what is left after its full batches of 64;
+not the cylinder / convex class) is not evaluated in its tile when it has <= K live entries: its rows wait in a per-wave ring
+across tiles (tiles of one kind in sequence = one wave) and are evaluated 64 rows at a time, one routine execution per class present
+among the 64.  Deferred entries do not make their state invalid in the tile, so later classes lose that early-out.  Reported per
+tile: in-tile batches, deferred rows, the share of tiles that need the gather-only batch, and the routine executions of the ring.
 """
 import argparse
 import collections
@@ -37,6 +45,8 @@ def main():
     ap.add_argument("--env", default="SawyerPushObstacle-v0")
     ap.add_argument("--tiles", type=int, default=16, help="tiles of 64 states per kind")
     ap.add_argument("--resident", default="head,right_l2", help="bodies of the pair taken out of the entry pipeline")
+    ap.add_argument("--axis-extents", action="store_true", help="static cull of capsule / cylinder owners with r + hl |a_i| per axis")
+    ap.add_argument("--defer-small", default="", help="comma list of K: class remainders of <= K live entries wait in a per-wave ring")
     a = ap.parse_args()
     pi = planner_inputs(a.env)
     m = pi.model
@@ -98,7 +108,10 @@ def main():
                 keep = np.linalg.norm(d) <= min(rb[x] + rb[y], tight.get((x, y), tight.get((y, x), 1e9)))
             else:
                 st, mv = (x, y) if not mov[x] else (y, x)
-                keep = np.linalg.norm(d) <= rb[x] + rb[y] and np.all(np.abs(d) <= extent(st, gm[st]) + rb[mv])
+                reach = rb[mv]
+                if a.axis_extents and int(T[mv]) in (G_CAPSULE, G_CYLINDER):
+                    reach = np.minimum(reach, S[mv][0] + S[mv][1] * np.abs(gm[mv][:, 2]))
+                keep = np.linalg.norm(d) <= rb[x] + rb[y] and np.all(np.abs(d) <= extent(st, gm[st]) + reach)
             if keep:
                 out.append((k, code, pd[k] <= thr))
         return out
@@ -124,7 +137,43 @@ def main():
                 bad[i] |= hit
         return built, evaluated, batches, 1.0 - bad.mean()
 
-    print(f"{a.env}: {len(pairs)} candidate pairs after pruning, {a.tiles} tiles of 64 states per kind; resident pair: {a.resident}")
+    def defer_stats(tiles, K):
+        """tiles of one wave in sequence, the resident pair in the walk: (in-tile batches, deferred rows, share of tiles with a gather-only
+        batch, ring executions) per tile"""
+        batches = rows = gathers = execs = 0
+        ring = []
+        for states in tiles:
+            bad = np.zeros(len(states), bool)
+            ents = collections.defaultdict(list)
+            for i, sv in enumerate(states):
+                if any(k == res and hit for k, _, hit in sv):
+                    bad[i] = True
+                    continue
+                for k, code, hit in sv:
+                    if k != res:
+                        ents[code].append((i, hit))
+            deferred = 0
+            for code in sorted(ents):
+                live = [(i, hit) for i, hit in ents[code] if not bad[i]]
+                rem = len(live) % 64
+                if code != 11 and 0 < rem <= K:
+                    live = live[:len(live) - rem]
+                    deferred += rem
+                    ring += [code] * rem
+                batches += (len(live) + 63) // 64
+                for i, hit in live:
+                    bad[i] |= hit
+            rows += deferred
+            gathers += deferred > 0
+            while len(ring) >= 64:
+                execs += len(set(ring[:64]))
+                ring = ring[64:]
+        execs += len(set(ring))
+        n = len(tiles)
+        return batches / n, rows / n, gathers / n, execs / n
+
+    print(f"{a.env}: {len(pairs)} candidate pairs after pruning, {a.tiles} tiles of 64 states per kind; resident pair: {a.resident}; "
+          f"static cull of capsule / cylinder owners: {'axis extents' if a.axis_extents else 'bounding radius'}")
     print(f"{'tile kind':10s} {'pipeline':22s} {'valid':>6s} {'built':>7s} {'evaluated':>10s} {'batches':>8s} {'lane util':>10s}")
     for kind, seed in (("uniform", 1), ("near", 2)):
         qa, row = sample_states(pi, 64 * a.tiles, seed, kind)
@@ -134,6 +183,9 @@ def main():
         for name, without in (("today", None), ("pair in the walk", res)):
             st = np.array([tile_stats(sv[64 * t: 64 * t + 64], without) for t in range(a.tiles)]).mean(axis=0)
             print(f"{kind:10s} {name:22s} {st[3]:6.2f} {st[0]:7.1f} {st[1]:10.1f} {st[2]:8.2f} {st[1] / (64 * st[2]):10.2f}")
+        for K in [int(x) for x in a.defer_small.split(",") if x]:
+            b, r, g, e = defer_stats([sv[64 * t: 64 * t + 64] for t in range(a.tiles)], K)
+            print(f"{kind:10s} defer <= {K:2d}: in-tile batches {b:5.2f}, deferred rows {r:5.2f}, gather-only batch in {g:4.2f} of the tiles, ring executions {e:4.2f} per tile")
         n_res = sum(1 for s in sv if any(k == res for k, _, _ in s))
         print(f"{kind:10s} the pair survives the cull in {n_res / len(sv):.2f} of the states, violates in "
               f"{sum(1 for s in sv if any(k == res and hit for k, _, hit in s)) / len(sv):.3f}")
