@@ -471,7 +471,7 @@ int mopa_contacts_state(MopaScene *scene, const double *qpos_host /*[nq]*/, doub
  * count / pair / dist are exactly mopa_contacts_batch's (same launches, same bytes); unused slots of normal / pos hold 0.0.
  * Same argument rules and status codes as mopa_contacts_batch, including the glued-scene and pair_cull_radius refusals.  One
  * more launch behind the report's two (a wave per state with a record), deterministic.  The definition per pair class is in
- * DESIGN.md section 4 ("Contact frames"; PARITY UNPINNED -- MuJoCo's multi-point manifolds are not reproduced). */
+ * DESIGN.md section 4 ("Contact frames"; PARITY UNPINNED -- the points of a multi-point contact: mopa_contact_manifolds_batch). */
 int mopa_contact_frames_batch(MopaScene *scene, const double *q_active_dev /*[N,na]*/, const double *qpos_env_dev /*[E,nq]*/,
                               int64_t N, int64_t samples_per_env, double cutoff, int32_t max_contacts /*K*/,
                               int32_t *count_dev /*[N]*/, int32_t *pair_dev /*[N,K]*/, double *dist_dev /*[N,K]*/,
@@ -490,6 +490,40 @@ int mopa_geom_frames_batch(int32_t device, int64_t M, const int32_t *types_dev, 
  * with nvert = 0). */
 int mopa_geom_frames_host(int64_t M, const int32_t *types, const double *recs, const double *mesh_verts /*nullable*/, int32_t nvert,
                           double *out);
+
+/* Contact manifolds: the contact report plus, per record, the frame's normal and UP TO max_points (P, 1..8) contact points --
+ * what the reference reads off d->contact[i].pos / frame / dist per contact where MuJoCo emits several for a pair (box-plane 4,
+ * capsule-plane 2, box-box up to 8).  [3P] The candidate points per pair class are restated from MuJoCo's documented behaviour,
+ * PARITY UNPINNED; the table is in DESIGN.md section 4 ("Contact manifolds").  For record (state i, slot k):
+ *   normal[i,k,:]        the bits mopa_contact_frames_batch reports: one normal per pair
+ *   npoint[i,k]          the number of points with dist_j <= point_cutoff, at most 8, NOT capped by P; 0 in unused slots
+ *   point_dist[i,k,j]    sorted ascending (deepest first, ties in generation order), the first P kept; MOPA_FAR in unused slots
+ *   point_pos[i,k,j,:]   midpoint of the point's two witnesses, w1 on g1 and w2 on g2, w2 - w1 = dist_j * normal; 0.0 when unused
+ * A class rule that yields no point under point_cutoff falls back to the single frame point (the bits of
+ * mopa_contact_frames_batch's pos and of dist), as every single-point class does.  count / pair / dist are exactly
+ * mopa_contacts_batch's (it is called first: same launches, same bytes, same argument rules and status codes, the glued-scene
+ * and pair_cull_radius refusals included).  P outside 1..8, point_cutoff not finite or < cutoff, a null output:
+ * MOPA_ERR_INVALID_ARG; a scene that does not fit LDS: MOPA_ERR_LIMIT.  One more launch behind the report's two, deterministic:
+ * every output word has one writer, plain stores. */
+int mopa_contact_manifolds_batch(MopaScene *scene, const double *q_active_dev /*[N,na]*/, const double *qpos_env_dev /*[E,nq]*/,
+                                 int64_t N, int64_t samples_per_env, double cutoff, double point_cutoff, int32_t max_contacts /*K*/,
+                                 int32_t max_points /*P*/, int32_t *count_dev /*[N]*/, int32_t *pair_dev /*[N,K]*/,
+                                 double *dist_dev /*[N,K]*/, double *normal_dev /*[N,K,3]*/, int32_t *npoint_dev /*[N,K]*/,
+                                 double *point_dist_dev /*[N,K,P]*/, double *point_pos_dev /*[N,K,P,3]*/, void *stream);
+/* the same for one state (host pointers, synchronous) */
+int mopa_contact_manifolds_state(MopaScene *scene, const double *qpos_host /*[nq]*/, double cutoff, double point_cutoff,
+                                 int32_t max_contacts /*K*/, int32_t max_points /*P*/, int32_t *count /*[1]*/, int32_t *pair /*[K]*/,
+                                 double *dist /*[K]*/, double *normal /*[K,3]*/, int32_t *npoint /*[K]*/, double *point_dist /*[K,P]*/,
+                                 double *point_pos /*[K,P,3]*/);
+/* Pair level: M posed primitive pairs, one lane each; types / recs as mopa_geom_frames_batch takes them.  normal_dist [M,4] =
+ * normal[3], dist (the pair's, mopa_geom_frames_batch's bits); npoint [M]; points [M,P,4] = pos[3], dist_j.  No cutoff applies
+ * to the pair itself at this level: only point_cutoff (finite) to its points.  Meshes are not served on the device. */
+int mopa_geom_manifolds_batch(int32_t device, int64_t M, const int32_t *types_dev, const double *recs_dev, double point_cutoff,
+                              int32_t max_points /*P*/, double *normal_dist_dev, int32_t *npoint_dev, double *points_dev, void *stream);
+/* The host compile of the same functions -- the sequential form the kernels match bit for bit; no GPU, no HIP call.  mesh_verts
+ * as in mopa_geom_frames_host. */
+int mopa_geom_manifolds_host(int64_t M, const int32_t *types, const double *recs, const double *mesh_verts /*nullable*/, int32_t nvert,
+                             double point_cutoff, int32_t max_points /*P*/, double *normal_dist, int32_t *npoint, double *points);
 
 /* ======================================================================================================
  * (BASELINE configs 3-5) batched KINEMATIC env.step for the three Sawyer obstacle envs --

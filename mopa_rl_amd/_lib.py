@@ -33,6 +33,7 @@ EXPORTED_SYMBOLS = [
     "mopa_plan_race_batch", "mopa_plan_race", "mopa_race_params_size", "mopa_pullback_batch", "mopa_is_valid_state", "mopa_plan",
     "mopa_planner_status", "mopa_debug_fk", "mopa_debug_pair_dist", "mopa_contacts_batch", "mopa_contacts_state",
     "mopa_contact_frames_batch", "mopa_contact_frames_state", "mopa_geom_frames_batch", "mopa_geom_frames_host",
+    "mopa_contact_manifolds_batch", "mopa_contact_manifolds_state", "mopa_geom_manifolds_batch", "mopa_geom_manifolds_host",
     "mopa_env_create", "mopa_env_destroy", "mopa_env_obs_dim", "mopa_env_action_dim", "mopa_env_step_batch", "mopa_env_exec_batch", "mopa_env_desired_batch",
     "mopa_env_attach_dynamics", "mopa_env_attach_contacts", "mopa_env_set_contact_stats", "mopa_rollout_stage", "mopa_rollout_pool_pick", "mopa_rollout_step_size", "mopa_reuse_batch", "mopa_replay_append", "mopa_replay_sample", "mopa_ct_desc_size", "mopa_env_contact_arena", "mopa_env_dyn_dofs", "mopa_env_dyn_qvel_width", "mopa_env_dyn_forward_batch", "mopa_env_dyn_substeps_batch", "mopa_env_step_dyn_batch",
     "mopa_pusher_dyn_desc_size", "mopa_env_attach_pusher_dynamics", "mopa_env_set_pusher_stats", "mopa_env_pusher_substeps_batch",
@@ -245,6 +246,10 @@ def lib() -> C.CDLL:
     L.mopa_contact_frames_state.argtypes = [vp, _dp, C.c_double, C.c_int32, _ip, _ip, _dp, _dp, _dp]
     L.mopa_geom_frames_batch.argtypes = [C.c_int32, C.c_int64, vp, vp, vp, vp]
     L.mopa_geom_frames_host.argtypes = [C.c_int64, _ip, _dp, _dp, C.c_int32, _dp]
+    L.mopa_contact_manifolds_batch.argtypes = [vp, vp, vp, C.c_int64, C.c_int64, C.c_double, C.c_double, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.mopa_contact_manifolds_state.argtypes = [vp, _dp, C.c_double, C.c_double, C.c_int32, C.c_int32, _ip, _ip, _dp, _dp, _ip, _dp, _dp]
+    L.mopa_geom_manifolds_batch.argtypes = [C.c_int32, C.c_int64, vp, vp, C.c_double, C.c_int32, vp, vp, vp, vp]
+    L.mopa_geom_manifolds_host.argtypes = [C.c_int64, _ip, _dp, _dp, C.c_int32, C.c_double, C.c_int32, _dp, _ip, _dp]
     L.mopa_env_create.argtypes = [C.POINTER(MopaEnvDesc), C.POINTER(vp)]
     L.mopa_env_destroy.argtypes = [vp]
     L.mopa_env_destroy.restype = None
@@ -332,6 +337,25 @@ def geom_frames_host(types, recs, mesh_verts=None) -> np.ndarray:
     v, vp_ = _d(np.asarray(mesh_verts, dtype=np.float64).reshape(-1, 3)) if mesh_verts is not None else (np.zeros((0, 3)), None)
     check(lib().mopa_geom_frames_host(len(t), tp, rp, vp_, len(v), out.ctypes.data_as(_dp)))
     return out
+
+
+def geom_manifolds_host(types, recs, mesh_verts=None, point_cutoff: float = 0.0, max_points: int = 4):
+    """mopa_geom_manifolds_host: M posed pairs as `geom_frames_host` takes them -> (normal_dist [M, 4] = normal[3], dist;
+    npoint [M] int32; points [M, P, 4] = pos[3], dist_i) by the host compile of the kernels' geom_manifold (no GPU): the frame's
+    normal and up to P = max_points contact points under point_cutoff, deepest first; MOPA_FAR / 0.0 in unused point slots
+    ("Contact manifolds"; PARITY UNPINNED)."""
+    t, tp = _i(np.asarray(types).reshape(-1, 2))
+    r, rp = _d(np.asarray(recs, dtype=np.float64).reshape(-1, 30))
+    if len(t) != len(r):
+        raise MopaError(f"{len(t)} type pairs for {len(r)} record pairs")
+    P = int(max_points)
+    nd = np.zeros((len(t), 4))
+    npoint = np.zeros(len(t), dtype=np.int32)
+    pts = np.zeros((len(t), max(P, 1), 4))
+    v, vp_ = _d(np.asarray(mesh_verts, dtype=np.float64).reshape(-1, 3)) if mesh_verts is not None else (np.zeros((0, 3)), None)
+    check(lib().mopa_geom_manifolds_host(len(t), tp, rp, vp_, len(v), float(point_cutoff), P, nd.ctypes.data_as(_dp), npoint.ctypes.data_as(_ip),
+                                         pts.ctypes.data_as(_dp)))
+    return nd, npoint, pts
 
 
 def model_struct(m, keep: list, pair_geom=None) -> MopaModel:
@@ -681,17 +705,48 @@ class Scene:
                                               pair.ctypes.data_as(_ip), dist.ctypes.data_as(_dp), normal.ctypes.data_as(_dp), pos.ctypes.data_as(_dp)))
         return int(cnt.value), pair, dist, normal, pos
 
-    def contacts_state(self, qpos, cutoff: Optional[float] = None, frames: bool = False):
+    def contact_manifolds_state_raw(self, qpos, cutoff: Optional[float] = None, max_contacts: int = 64, max_points: int = 4, point_cutoff: float = 0.0):
+        """(count, pair [K] int32, dist [K], normal [K, 3], npoint [K] int32, point_dist [K, P], point_pos [K, P, 3]) of one
+        state: `contacts_state_raw` with the contact manifold of every record (mopa_contact_manifolds_state); unused slots hold
+        normal / npoint / point_pos 0, point_dist MOPA_FAR"""
+        sc = self.contact_scene()
+        q, qp = _d(qpos)
+        if q.shape != (self.nq,):
+            raise MopaError(f"state has dimension {q.shape}, expected nq={self.nq}")
+        K, P = int(max_contacts), int(max_points)
+        k1, p1 = max(K, 1), max(P, 1)
+        cnt = C.c_int32(0)
+        pair = np.full(k1, -1, dtype=np.int32)
+        dist = np.full(k1, MOPA_FAR)
+        normal = np.zeros((k1, 3))
+        npoint = np.zeros(k1, dtype=np.int32)
+        pdist = np.full((k1, p1), MOPA_FAR)
+        ppos = np.zeros((k1, p1, 3))
+        check(lib().mopa_contact_manifolds_state(sc._h, qp, float(self.contact_threshold if cutoff is None else cutoff), float(point_cutoff), K, P,
+                                                 C.byref(cnt), pair.ctypes.data_as(_ip), dist.ctypes.data_as(_dp), normal.ctypes.data_as(_dp),
+                                                 npoint.ctypes.data_as(_ip), pdist.ctypes.data_as(_dp), ppos.ctypes.data_as(_dp)))
+        return int(cnt.value), pair, dist, normal, npoint, pdist, ppos
+
+    def contacts_state(self, qpos, cutoff: Optional[float] = None, frames: bool = False, manifold: bool = False, max_points: int = 4,
+                       point_cutoff: float = 0.0):
         """The pairs in contact in one state, as the reference's checker sees them in `d->contact[i]`: a list of
         (geom1_name, geom2_name, dist) over the non-ignored candidate pairs with dist <= cutoff, in `model.pair_geom` order.
         cutoff=None: the scene's contact_threshold -- the pairs that make the state invalid.  cutoff must be < 0.
         frames=True: (geom1_name, geom2_name, dist, normal, pos) -- ONE contact frame per pair, that of the deepest contact
         (MuJoCo may emit several contacts for a pair): `normal` [3] a unit vector from geom1 towards geom2, `pos` [3] the
-        midpoint of the two witness points ("Contact frames")."""
+        midpoint of the two witness points ("Contact frames").
+        manifold=True (takes precedence over frames): (geom1_name, geom2_name, dist, normal, [(pos, dist_i), ...]) -- the same
+        normal and up to max_points (1..8) contact points with dist_i <= point_cutoff, deepest first (DESIGN.md section 4,
+        "Contact manifolds"; PARITY UNPINNED)."""
         m = self.model
         K = max(1, len(m.pair_geom))
         g = np.asarray(m.pair_geom).reshape(-1, 2)
         name = lambda k: m.all_geom_names[int(m.geom_mjid[int(k)])]
+        if manifold:
+            n, pair, dist, normal, npoint, pdist, ppos = self.contact_manifolds_state_raw(qpos, cutoff, K, max_points, point_cutoff)
+            return [(name(g[p, 0]), name(g[p, 1]), float(d), normal[k].copy(),
+                     [(ppos[k, j].copy(), float(pdist[k, j])) for j in range(min(int(npoint[k]), pdist.shape[1]))])
+                    for k, (p, d) in enumerate(zip(pair[:n], dist[:n]))]
         if frames:
             n, pair, dist, normal, pos = self.contact_frames_state_raw(qpos, cutoff, K)
             return [(name(g[p, 0]), name(g[p, 1]), float(d), normal[k].copy(), pos[k].copy()) for k, (p, d) in enumerate(zip(pair[:n], dist[:n]))]

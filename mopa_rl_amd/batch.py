@@ -92,11 +92,16 @@ class ContactReport:
     indices into `model.pair_geom` in ascending order (`pair` [N, K] int32, -1 in unused slots) and their signed distances
     (`dist` [N, K] float64, MOPA_FAR in unused slots).  With `frames=True` also ONE contact frame per record, that of the
     deepest contact: `normal` [N, K, 3], a unit vector from the pair's first geom (as `geoms()` orders them) towards its second,
-    and `pos` [N, K, 3], the midpoint of the two witness points; 0.0 in unused slots.  Both are None otherwise."""
+    and `pos` [N, K, 3], the midpoint of the two witness points; 0.0 in unused slots.  Both are None otherwise.
+    With `manifold=True` the same `normal` and, per record, a contact manifold of up to P points: `npoint` [N, K] int32 (the
+    number of points under point_cutoff, at most 8, not capped by P; 0 in unused slots), `point_dist` [N, K, P] (ascending,
+    deepest first; MOPA_FAR in unused slots) and `point_pos` [N, K, P, 3] (0.0 in unused slots); None otherwise.  `pos` stays
+    tied to `frames=True`."""
 
-    def __init__(self, count, pair, dist, model, normal=None, pos=None):
+    def __init__(self, count, pair, dist, model, normal=None, pos=None, npoint=None, point_dist=None, point_pos=None):
         self.count, self.pair, self.dist, self.model = count, pair, dist, model
         self.normal, self.pos = normal, pos
+        self.npoint, self.point_dist, self.point_pos = npoint, point_dist, point_pos
 
     def __iter__(self):
         return iter((self.count, self.pair, self.dist))
@@ -139,6 +144,26 @@ def geom_frames(types, recs, stream=None):
     dev = recs.device.index if recs.device.index is not None else torch.cuda.current_device()
     _lib.check(_lib.lib().mopa_geom_frames_batch(int(dev), M, _ptr(types), _ptr(recs), _ptr(out), _stream_handle(stream)))
     return out
+
+
+def geom_manifolds(types, recs, point_cutoff: float = 0.0, max_points: int = 4, stream=None):
+    """mopa_geom_manifolds_batch: M posed primitive pairs, one lane each, as `geom_frames` takes them -> (normal_dist [M, 4] =
+    normal[3], dist; npoint [M] int32; points [M, P, 4] = pos[3], dist_i): the bits of `_lib.geom_manifolds_host`.  Meshes are
+    not served at this level."""
+    torch = _torch()
+    _check_f64(recs, "recs")
+    if types.dtype != torch.int32 or not types.is_cuda or not types.is_contiguous() or types.dim() != 2 or types.shape[1] != 2:
+        raise _lib.MopaError("types must be a contiguous int32 GPU tensor [M, 2]")
+    M, P = types.shape[0], int(max_points)
+    if recs.numel() != M * 30:
+        raise _lib.MopaError(f"recs must have shape [{M}, 2, 15], got {tuple(recs.shape)}")
+    nd = torch.empty(M, 4, dtype=torch.float64, device=recs.device)
+    npoint = torch.empty(M, dtype=torch.int32, device=recs.device)
+    pts = torch.empty(M, max(P, 1), 4, dtype=torch.float64, device=recs.device)
+    dev = recs.device.index if recs.device.index is not None else torch.cuda.current_device()
+    _lib.check(_lib.lib().mopa_geom_manifolds_batch(int(dev), M, _ptr(types), _ptr(recs), float(point_cutoff), P, _ptr(nd), _ptr(npoint), _ptr(pts),
+                                                    _stream_handle(stream)))
+    return nd, npoint, pts
 
 
 def k9_passes(vertex_simplify, simplify_passes, path_shortcut, path_smooth) -> int:
@@ -218,12 +243,17 @@ class BatchPlanner:
         return (valid, md) if want_min_dist else valid
 
     def contacts(self, q_active, qpos_env, samples_per_env: Optional[int] = None, cutoff: Optional[float] = None,
-                 max_contacts: int = 16, stream=None, frames: bool = False) -> ContactReport:
+                 max_contacts: int = 16, stream=None, frames: bool = False, manifold: bool = False, max_points: int = 4,
+                 point_cutoff: float = 0.0) -> ContactReport:
         """Which pairs are in contact, for every state of a batch (states as in `is_valid`): one record per non-ignored
         candidate pair with dist <= cutoff, ascending index into `model.pair_geom`; `count` is not capped by `max_contacts`,
         the records with the lowest indices are kept.  cutoff=None: the scene's contact_threshold, i.e. the pairs that make a
         state invalid; any other cutoff must be < 0.  Runs on the scene with the full pair list (`Scene.contact_scene`).
-        frames=True: the report also carries `.normal` and `.pos` (one more launch; count / pair / dist are the same bytes)."""
+        frames=True: the report also carries `.normal` and `.pos` (one more launch; count / pair / dist are the same bytes).
+        manifold=True: the report also carries `.normal`, `.npoint`, `.point_dist` and `.point_pos`: up to max_points (1..8)
+        contact points per record with dist_i <= point_cutoff (>= cutoff), deepest first (one more launch behind the report;
+        DESIGN.md section 4, "Contact manifolds", PARITY UNPINNED).  With both switches on the report runs once per switch and
+        writes the same bytes both times."""
         torch = _torch()
         _check_f64(q_active, "q_active", self.na)
         _check_f64(qpos_env, "qpos_env", self.nq)
@@ -237,6 +267,22 @@ class BatchPlanner:
         count = torch.empty(N, dtype=torch.int32, device=dev)
         pair = torch.empty(N, max(K, 1), dtype=torch.int32, device=dev)
         dist = torch.empty(N, max(K, 1), dtype=torch.float64, device=dev)
+        if manifold:
+            P = int(max_points)
+            normal = torch.empty(N, max(K, 1), 3, dtype=torch.float64, device=dev)
+            npoint = torch.empty(N, max(K, 1), dtype=torch.int32, device=dev)
+            pdist = torch.empty(N, max(K, 1), max(P, 1), dtype=torch.float64, device=dev)
+            ppos = torch.empty(N, max(K, 1), max(P, 1), 3, dtype=torch.float64, device=dev)
+            cut = float(self.scene.contact_threshold if cutoff is None else cutoff)
+            pos = None
+            if frames:      # (the frames call first: both write the same normal bits, the manifold's stay)
+                pos = torch.empty(N, max(K, 1), 3, dtype=torch.float64, device=dev)
+                _lib.check(_lib.lib().mopa_contact_frames_batch(sc.handle, _ptr(q_active), _ptr(qpos_env), N, spe, cut, K, _ptr(count), _ptr(pair), _ptr(dist),
+                                                                _ptr(normal), _ptr(pos), _stream_handle(stream)))
+            _lib.check(_lib.lib().mopa_contact_manifolds_batch(sc.handle, _ptr(q_active), _ptr(qpos_env), N, spe, cut, float(point_cutoff), K, P, _ptr(count),
+                                                               _ptr(pair), _ptr(dist), _ptr(normal), _ptr(npoint), _ptr(pdist), _ptr(ppos),
+                                                               _stream_handle(stream)))
+            return ContactReport(count, pair, dist, self.scene.model, normal, pos, npoint, pdist, ppos)
         if frames:
             normal = torch.empty(N, max(K, 1), 3, dtype=torch.float64, device=dev)
             pos = torch.empty(N, max(K, 1), 3, dtype=torch.float64, device=dev)

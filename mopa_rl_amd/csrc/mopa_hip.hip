@@ -30,6 +30,7 @@
 #include "../../include/mopa_hip.h"
 #include "mopa_device.hpp"
 #include "mopa_frames.hpp"
+#include "mopa_manifold.hpp"
 #include "mopa_fk.hpp"
 #include "mopa_host.hpp"
 
@@ -47,6 +48,7 @@ constexpr double kV5MaxReach = 32.0;        // metres: beyond this the FP32 broa
 static void plan_register_lds();            // defined with K3 (mopa_planner.inc)
 static void contacts_register_lds();        // defined with the contact report (mopa_contacts.inc)
 static void contact_frames_register_lds();  // defined with the contact frames (mopa_contact_frames.inc)
+static void contact_manifolds_register_lds();  // defined with the contact manifolds (mopa_contact_manifold.inc)
 static void k9_register_lds();              // defined with K9 path simplification (mopa_k9.inc)
 static void star_register_lds();            // defined with K3b RRT* (mopa_rrtstar.inc)
 static void k1_register_lds();              // defined with the K1 kernel table (mopa_valid_launch.inc)
@@ -788,6 +790,7 @@ static int scene_create(const MopaSceneDesc *desc, int glue_a, int glue_b, MopaS
     plan_register_lds();
     contacts_register_lds();
     contact_frames_register_lds();
+    contact_manifolds_register_lds();
     k9_register_lds();
     star_register_lds();
     *out = S;
@@ -932,6 +935,7 @@ extern "C" const char *mopa_planner_status(const MopaScene *S) { return S ? S->s
 #include "mopa_contacts.inc"
 // contact frames behind it: mopa_contact_frames_batch / _state, pair level mopa_geom_frames_batch / _host
 #include "mopa_contact_frames.inc"
+#include "mopa_contact_manifold.inc"
 
 // The planner entry points are defined in mopa_planner.inc (K3).
 #include "mopa_planner.inc"

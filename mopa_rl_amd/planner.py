@@ -197,11 +197,14 @@ class PyKinematicPlanner:
     def model(self):
         return self._model
 
-    def contacts(self, state_vec, frames: bool = False) -> List[Tuple]:
+    def contacts(self, state_vec, frames: bool = False, manifold: bool = False, max_points: int = 4, point_cutoff: float = 0.0) -> List[Tuple]:
         """the pairs that make `state_vec` invalid -- (geom1_name, geom2_name, dist) with dist <= contact_threshold, what the
         reference's checker finds in d->contact[i] (mujoco_ompl_interface.cpp:917-978); empty for a valid state.
-        frames=True: (geom1_name, geom2_name, dist, normal, pos), one contact frame per pair (`Scene.contacts_state`).  With
-        glue_bodies it raises: the contact report is not built for a glued scene"""
+        frames=True: (geom1_name, geom2_name, dist, normal, pos), one contact frame per pair (`Scene.contacts_state`).
+        manifold=True: (geom1_name, geom2_name, dist, normal, [(pos, dist_i), ...]), up to max_points contact points per pair
+        (`Scene.contacts_state`).  With glue_bodies it raises: the contact report is not built for a glued scene"""
         if self.glue_bodies:
             raise NotImplementedError("contacts() with glue_bodies: the contact report is not built for a glued scene")
+        if manifold:
+            return self._scene.contacts_state(np.asarray(state_vec, dtype=np.float64), manifold=True, max_points=max_points, point_cutoff=point_cutoff)
         return self._scene.contacts_state(np.asarray(state_vec, dtype=np.float64), frames=frames)

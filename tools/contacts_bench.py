@@ -3,6 +3,7 @@
 bench.py's generator): `contacts(cutoff=thr, K=16)`, its first stage alone (the min-depth launch on the full pair list) and
 `is_valid(want_min_dist=True)` as the planner calls it -- in interleaved rounds (device events), median / min / max.
 --frames: also `contacts(frames=True)` in the same rounds, frames on against off: both times and their ratio.
+--manifold: also `contacts(manifold=True, max_points=P)` in the same rounds, against off and against frames on.
 
     python tools/contacts_bench.py --out profiles/r10/contacts_bench.txt
     python tools/contacts_bench.py --frames --out profiles/r25/contacts_frames_bench.txt
@@ -28,6 +29,8 @@ def main():
     ap.add_argument("--reps", type=int, default=5, help="calls per timed window")
     ap.add_argument("--max-contacts", type=int, default=16)
     ap.add_argument("--frames", action="store_true", help="also time contacts(frames=True): frames on against off")
+    ap.add_argument("--manifold", action="store_true", help="also time contacts(manifold=True): manifold on against off (and against frames on)")
+    ap.add_argument("--max-points", type=int, default=4)
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     import torch
@@ -52,6 +55,9 @@ def main():
         }
         if args.frames:
             forms["contacts(frames=True)"] = lambda: bp.contacts(qa, rows, samples_per_env=args.samples, max_contacts=args.max_contacts, frames=True)
+        if args.manifold:
+            forms["contacts(manifold=True)"] = lambda: bp.contacts(qa, rows, samples_per_env=args.samples, max_contacts=args.max_contacts, manifold=True,
+                                                                   max_points=args.max_points)
         for f in forms.values():           # warm-up: code objects, scratch buffers
             for _ in range(3):
                 f()
@@ -78,6 +84,12 @@ def main():
         if args.frames:
             on, off = med["contacts(frames=True)"], med["contacts"]
             lines.append(f"    frames on {on:.3f} ms against off {off:.3f} ms: k_contact_frames = {on - off:.3f} ms, on / off = {on / off:.3f}")
+        if args.manifold:
+            on, off = med["contacts(manifold=True)"], med["contacts"]
+            lines.append(f"    manifold on (P = {args.max_points}) {on:.3f} ms against off {off:.3f} ms: k_contact_manifolds = {on - off:.3f} ms, on / off = {on / off:.3f}")
+            if args.frames:
+                fr = med["contacts(frames=True)"]
+                lines.append(f"    manifold on against frames on {fr:.3f} ms: manifold / frames = {on / fr:.3f}")
         lines.append("")
         sc.close()
     text = "\n".join(lines)
