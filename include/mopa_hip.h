@@ -21,6 +21,8 @@
  *     mujoco_ompl_interface.cpp:909-978
  *   si->checkMotion (OMPL DiscreteMotionValidator,   mopa_check_motion_batch()
  *     resolution KinematicPlanner.cpp:87)
+ *   ... its overload checkMotion(s1, s2, lastValid)  mopa_motion_report_batch() (N segments, device ptrs)
+ *     (not called by the reference) + the blockers   mopa_motion_report()       (1 segment, host ptrs)
  *   KinematicPlanner::plan(start, goal, timelimit)   mopa_plan()                (1 query, host ptrs)
  *     KinematicPlanner.cpp:125-251 (RRTConnect)      mopa_plan_batch()          (E queries, device ptrs)
  *   invalid-target back-off of the rollout runner    mopa_pullback_batch()      (E targets, device ptrs)
@@ -462,6 +464,50 @@ int mopa_contacts_batch(MopaScene *scene, const double *q_active_dev /*[N,na]*/,
 /* the same for one state (host pointers, synchronous) */
 int mopa_contacts_state(MopaScene *scene, const double *qpos_host /*[nq]*/, double cutoff, int32_t max_contacts /*K*/,
                         int32_t *count /*[1]*/, int32_t *pair /*[K]*/, double *dist /*[K]*/);
+
+/* Motion report: WHERE a segment is blocked and by which pairs -- OMPL's DiscreteMotionValidator::checkMotion(s1, s2, lastValid),
+ * the overload mopa_check_motion_batch leaves out, plus the contact report of the first blocked state.
+ * Segment i runs from qa[i] to qb[i] (active coordinates) on env row qpos_env[i / samples_per_env], as in mopa_check_motion_batch.
+ *   nd = validSegmentCount(qa, qb) (mopa_check_motion_batch's), c = max(nd, 1)
+ *   states s_k, k = 1 .. c: s_c = qb, its bits copied; for k < c, s_k[a] = interpolate(qa[a], qb[a], (double)k / (double)c) per
+ *   coordinate (SO(2) coordinates the short way round) -- the expressions mopa_check_motion_batch evaluates.  qa is NOT tested
+ *   (OMPL assumes s1 valid, and so does mopa_check_motion_batch).
+ * Outputs per segment:
+ *   valid         1 iff every s_k is valid: the byte mopa_check_motion_batch writes
+ *   n_states      c
+ *   first_bad     the smallest k with s_k invalid; 0 if the segment is valid
+ *   last_valid_t  1.0 if valid, else (double)(first_bad - 1) / (double)c (one division; first_bad == 1 gives 0.0)
+ *   last_valid_q  (nullable) qb if valid; the bits of qa if first_bad == 1; otherwise s_{first_bad - 1}, the very values that were
+ *                 validated at that index
+ *   first_bad_q   (nullable) s_{first_bad}; qb if the segment is valid, so that a contact report over these rows sees a valid
+ *                 state and writes an empty row
+ * Deviation: for nd == 0 (qa == qb) OMPL's (nd - 1) / nd is undefined; here c = 1, so an invalid qb gives first_bad = 1,
+ * last_valid_t = 0.0, last_valid_q = qa.
+ * Blockers (max_contacts = K >= 1; 0 with the three buffers NULL: off): block_count / block_pair / block_dist are, by definition,
+ * what mopa_contacts_batch writes for the states first_bad_q with the same env mapping, cutoff = the scene's contact_threshold and
+ * that K (it is called on them; first_bad_q lives in library scratch when the caller passed NULL).  A blocked segment has
+ * block_count >= 1; a valid one the "unused" row: count 0, pair -1, MOPA_FAR.  Everything mopa_contacts_batch refuses is refused
+ * here with its status, a scene whose contact_threshold is not negative included.  Frames and manifolds: pass first_bad_q to
+ * mopa_contact_frames_batch / mopa_contact_manifolds_batch.
+ * Two forms under mopa_check_motion_batch's dispatch rule (mopa_scene_motion_kernel names the form of both calls): one wave per
+ * segment that walks k upwards and stops at the first invalid state (a segment blocked only at its end costs c passes here, one in
+ * mopa_check_motion_batch), or the expansion into states with an ordered reduction; the latter reads the state count back once per
+ * chunk, i.e. it synchronises `stream` before it returns.  Deterministic: every output word has one writer.
+ * MOPA_ERR_INVALID_ARG: a NULL scene; with N > 0 a NULL qa / qb / qpos_env / valid / n_states / first_bad / last_valid_t; N < 0;
+ * samples_per_env <= 0; max_contacts < 0; max_contacts == 0 with a blocker buffer given; max_contacts >= 1 with a NULL blocker
+ * buffer (N > 0).  MOPA_ERR_UNSUPPORTED: a glued scene.  All of them before any launch; N == 0 returns MOPA_OK. */
+int mopa_motion_report_batch(MopaScene *scene, const double *qa_dev /*[N,na]*/, const double *qb_dev /*[N,na]*/,
+                             const double *qpos_env_dev /*[E,nq]*/, int64_t N, int64_t samples_per_env, uint8_t *valid_dev /*[N]*/,
+                             int32_t *n_states_dev /*[N]*/, int32_t *first_bad_dev /*[N]*/, double *last_valid_t_dev /*[N]*/,
+                             double *last_valid_q_dev /*[N,na] or NULL*/, double *first_bad_q_dev /*[N,na] or NULL*/,
+                             int32_t max_contacts /*K, 0 = off*/, int32_t *block_count_dev /*[N]*/, int32_t *block_pair_dev /*[N,K]*/,
+                             double *block_dist_dev /*[N,K]*/, void *stream);
+/* the same for one segment (host pointers, synchronous): from the active entries of qpos_a to those of qpos_b; the passive
+ * entries come from qpos_a, as in the path kernels.  The rows hold active coordinates. */
+int mopa_motion_report(MopaScene *scene, const double *qpos_a_host /*[nq]*/, const double *qpos_b_host /*[nq]*/, int32_t *valid_out,
+                       int32_t *n_states_out, int32_t *first_bad_out, double *last_valid_t_out, double *last_valid_q_out /*[na] or NULL*/,
+                       double *first_bad_q_out /*[na] or NULL*/, int32_t max_contacts /*K, 0 = off*/, int32_t *block_count /*[1]*/,
+                       int32_t *block_pair /*[K]*/, double *block_dist /*[K]*/);
 
 /* Contact frames: the contact report plus, per record, what the reference reads off d->contact[i].frame / pos
  * (util/contact_info.py).  ONE frame per reported pair -- that of the deepest contact -- where MuJoCo may emit several contacts

@@ -34,6 +34,7 @@ EXPORTED_SYMBOLS = [
     "mopa_planner_status", "mopa_debug_fk", "mopa_debug_pair_dist", "mopa_contacts_batch", "mopa_contacts_state",
     "mopa_contact_frames_batch", "mopa_contact_frames_state", "mopa_geom_frames_batch", "mopa_geom_frames_host",
     "mopa_contact_manifolds_batch", "mopa_contact_manifolds_state", "mopa_geom_manifolds_batch", "mopa_geom_manifolds_host",
+    "mopa_motion_report_batch", "mopa_motion_report",
     "mopa_env_create", "mopa_env_destroy", "mopa_env_obs_dim", "mopa_env_action_dim", "mopa_env_step_batch", "mopa_env_exec_batch", "mopa_env_desired_batch",
     "mopa_env_attach_dynamics", "mopa_env_attach_contacts", "mopa_env_set_contact_stats", "mopa_rollout_stage", "mopa_rollout_pool_pick", "mopa_rollout_step_size", "mopa_reuse_batch", "mopa_replay_append", "mopa_replay_sample", "mopa_ct_desc_size", "mopa_env_contact_arena", "mopa_env_dyn_dofs", "mopa_env_dyn_qvel_width", "mopa_env_dyn_forward_batch", "mopa_env_dyn_substeps_batch", "mopa_env_step_dyn_batch",
     "mopa_pusher_dyn_desc_size", "mopa_env_attach_pusher_dynamics", "mopa_env_set_pusher_stats", "mopa_env_pusher_substeps_batch",
@@ -250,6 +251,8 @@ def lib() -> C.CDLL:
     L.mopa_contact_manifolds_state.argtypes = [vp, _dp, C.c_double, C.c_double, C.c_int32, C.c_int32, _ip, _ip, _dp, _dp, _ip, _dp, _dp]
     L.mopa_geom_manifolds_batch.argtypes = [C.c_int32, C.c_int64, vp, vp, C.c_double, C.c_int32, vp, vp, vp, vp]
     L.mopa_geom_manifolds_host.argtypes = [C.c_int64, _ip, _dp, _dp, C.c_int32, C.c_double, C.c_int32, _dp, _ip, _dp]
+    L.mopa_motion_report_batch.argtypes = [vp, vp, vp, vp, C.c_int64, C.c_int64, vp, vp, vp, vp, vp, vp, C.c_int32, vp, vp, vp, vp]
+    L.mopa_motion_report.argtypes = [vp, _dp, _dp, _ip, _ip, _ip, _dp, _dp, _dp, C.c_int32, _ip, _ip, _dp]
     L.mopa_env_create.argtypes = [C.POINTER(MopaEnvDesc), C.POINTER(vp)]
     L.mopa_env_destroy.argtypes = [vp]
     L.mopa_env_destroy.restype = None
@@ -752,6 +755,57 @@ class Scene:
             return [(name(g[p, 0]), name(g[p, 1]), float(d), normal[k].copy(), pos[k].copy()) for k, (p, d) in enumerate(zip(pair[:n], dist[:n]))]
         n, pair, dist = self.contacts_state_raw(qpos, cutoff, K)
         return [(name(g[p, 0]), name(g[p, 1]), float(d)) for p, d in zip(pair[:n], dist[:n])]
+
+    def motion_report_raw(self, qpos_a, qpos_b, max_contacts: int = 0):
+        """(valid, n_states, first_bad, last_valid_t, last_valid_q [na], first_bad_q [na], blockers) of one segment: the
+        single-segment form of `BatchPlanner.motion_report` (mopa_motion_report) from the active entries of qpos_a to those of
+        qpos_b, the passive entries taken from qpos_a.  blockers: None with max_contacts = 0, else (count, pair [K] int32,
+        dist [K]) of the state first_bad_q at the contact threshold, pair indices into `model.pair_geom` -- in the same call on a
+        scene that holds the whole pair list, else through the sibling `contact_scene()` (the same bytes)."""
+        a, ap = _d(qpos_a)
+        b, bp = _d(qpos_b)
+        if a.shape != (self.nq,) or b.shape != (self.nq,):
+            raise MopaError(f"states have dimensions {a.shape} / {b.shape}, expected nq={self.nq}")
+        K = int(max_contacts)
+        chained = K != 0 and self.contact_scene() is self
+        v, n, fb, t = C.c_int32(0), C.c_int32(0), C.c_int32(0), C.c_double(0.0)
+        lvq, fbq = np.zeros(self.na), np.zeros(self.na)
+        cnt = C.c_int32(0)
+        pair = np.full(max(K, 1), -1, dtype=np.int32)
+        dist = np.full(max(K, 1), MOPA_FAR)
+        if K < 0:
+            raise MopaError("max_contacts must be >= 0")
+        check(lib().mopa_motion_report(self._h, ap, bp, C.byref(v), C.byref(n), C.byref(fb), C.byref(t), lvq.ctypes.data_as(_dp), fbq.ctypes.data_as(_dp),
+                                       K if chained else 0, C.byref(cnt) if chained else None, pair.ctypes.data_as(_ip) if chained else None,
+                                       dist.ctypes.data_as(_dp) if chained else None))
+        blockers = None
+        if chained:
+            blockers = (int(cnt.value), pair, dist)
+        elif K:
+            q = a.copy()
+            q[self.active_idx] = fbq
+            blockers = self.contacts_state_raw(q, None, K)
+        return bool(v.value), int(n.value), int(fb.value), float(t.value), lvq, fbq, blockers
+
+    def motion_report_state(self, qpos_a, qpos_b, max_contacts: int = 0):
+        """Where the straight line from qpos_a to qpos_b is blocked, and by what: OMPL's checkMotion(s1, s2, lastValid) over the
+        states s_k, k = 1 .. n_states (s_k at k / n_states along the segment, the last one qpos_b's active entries; qpos_a is
+        not tested).  -> dict: `valid`, `n_states`, `first_bad` (the smallest k with s_k invalid, 0 if valid), `last_valid_t`
+        ((first_bad - 1) / n_states, 1.0 if valid), `last_valid_q` / `first_bad_q` (active coordinates [na]; both qpos_b's if valid)
+        and `blockers`: None with max_contacts = 0, else the pairs that make s_first_bad invalid as (geom1_name, geom2_name,
+        dist), at most max_contacts of them in `model.pair_geom` order (the style of `contacts_state`), and `n_blockers`, their
+        uncapped number.  DESIGN.md section 4, "Motion report"."""
+        m = self.model
+        valid, n, fb, t, lvq, fbq, blk = self.motion_report_raw(qpos_a, qpos_b, max_contacts)
+        out = {"valid": valid, "n_states": n, "first_bad": fb, "last_valid_t": t, "last_valid_q": lvq, "first_bad_q": fbq, "blockers": None}
+        if blk is not None:
+            g = np.asarray(m.pair_geom).reshape(-1, 2)
+            name = lambda k: m.all_geom_names[int(m.geom_mjid[int(k)])]
+            cnt, pair, dist = blk
+            k = min(cnt, len(pair))
+            out["blockers"] = [(name(g[p, 0]), name(g[p, 1]), float(d)) for p, d in zip(pair[:k], dist[:k])]
+            out["n_blockers"] = cnt
+        return out
 
     def debug_pair_dist(self, qpos):
         q, qp = _d(qpos)

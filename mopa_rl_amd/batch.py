@@ -120,6 +120,19 @@ class ContactReport:
         return [(m.all_geom_names[int(a)], m.all_geom_names[int(b)], float(x)) for (a, b), x in zip(ids, d)]
 
 
+class MotionReport:
+    """`BatchPlanner.motion_report`: per segment `valid` [N] uint8 (the byte `check_motion` writes), `n_states` [N] int32 (c =
+    max(validSegmentCount, 1): the states s_1 .. s_c that were due, s_c = qb), `first_bad` [N] int32 (the smallest k with s_k
+    invalid, 0 if valid), `last_valid_t` [N] float64 ((first_bad - 1) / c, 1.0 if valid), and with states=True `last_valid_q` /
+    `first_bad_q` [N, na] float64 (s_{first_bad - 1}, qa's bits when first_bad == 1, and s_{first_bad}; both qb for a valid
+    segment), None otherwise.  `blockers`: a `ContactReport` of the states first_bad_q at the contact threshold (max_contacts >= 1:
+    a blocked segment has count >= 1, a valid one the unused row), or None."""
+
+    def __init__(self, valid, n_states, first_bad, last_valid_t, last_valid_q=None, first_bad_q=None, blockers=None):
+        self.valid, self.n_states, self.first_bad, self.last_valid_t = valid, n_states, first_bad, last_valid_t
+        self.last_valid_q, self.first_bad_q, self.blockers = last_valid_q, first_bad_q, blockers
+
+
 def pair_geom_ids(model, pair) -> np.ndarray:
     """pair indices (any shape, -1 = unused) -> [..., 2] MuJoCo geom ids of the pairs' geoms, -1 where unused"""
     pair = np.asarray(pair, dtype=np.int64)
@@ -330,6 +343,53 @@ class BatchPlanner:
         _lib.check(_lib.lib().mopa_check_motion_batch(self.scene.handle, _ptr(qa), _ptr(qb), _ptr(qpos_env), N, spe,
                                                       _ptr(valid), _stream_handle(stream)))
         return valid
+
+    def motion_report(self, qa, qb, qpos_env, samples_per_env: Optional[int] = None, states: bool = True, max_contacts: int = 0,
+                      stream=None) -> MotionReport:
+        """Where every segment qa[i] -> qb[i] is blocked, and by which pairs (mopa_motion_report_batch; segments and env rows as
+        in `check_motion`, whose bytes `.valid` holds): OMPL's checkMotion(s1, s2, lastValid) -- the first invalid state in
+        ascending order, the last valid parameter and state before it -- see `MotionReport`.  states=False leaves the two [N, na]
+        rows out.  max_contacts = K >= 1: `.blockers` is the contact report of the states first_bad_q at the scene's
+        contact_threshold with that K, the bytes of `contacts(first_bad_q, qpos_env, max_contacts=K)` -- in the same call on a
+        scene that holds the whole pair list, else on `Scene.contact_scene()` behind it.  The large-batch form
+        (`Scene.motion_kernel`) synchronises the stream once per call, as `check_motion`'s does."""
+        torch = _torch()
+        _check_f64(qa, "qa", self.na)
+        _check_f64(qb, "qb", self.na)
+        _check_f64(qpos_env, "qpos_env", self.nq)
+        N, K = qa.shape[0], int(max_contacts)
+        if qb.shape[0] != N:
+            raise _lib.MopaError("qa and qb must hold the same number of segments")
+        if K < 0:
+            raise _lib.MopaError("max_contacts must be >= 0")
+        spe = int(samples_per_env) if samples_per_env is not None else max(1, N // max(1, qpos_env.shape[0]))
+        if N and (N + spe - 1) // spe > qpos_env.shape[0]:
+            raise _lib.MopaError("qpos_env has fewer rows than ceil(N / samples_per_env)")
+        dev = qa.device
+        valid = torch.empty(N, dtype=torch.uint8, device=dev)
+        n_states = torch.empty(N, dtype=torch.int32, device=dev)
+        first_bad = torch.empty(N, dtype=torch.int32, device=dev)
+        t = torch.empty(N, dtype=torch.float64, device=dev)
+        csc = self.scene.contact_scene() if K else None
+        chained = K != 0 and csc is self.scene
+        lvq = torch.empty(N, self.na, dtype=torch.float64, device=dev) if states else None
+        fbq = torch.empty(N, self.na, dtype=torch.float64, device=dev) if (states or (K and not chained)) else None
+        count = pair = dist = None
+        if K:
+            count = torch.empty(N, dtype=torch.int32, device=dev)
+            pair = torch.empty(N, K, dtype=torch.int32, device=dev)
+            dist = torch.empty(N, K, dtype=torch.float64, device=dev)
+        opt = lambda x: _ptr(x) if x is not None else None
+        sh = _stream_handle(stream)
+        _lib.check(_lib.lib().mopa_motion_report_batch(self.scene.handle, _ptr(qa), _ptr(qb), _ptr(qpos_env), N, spe, _ptr(valid), _ptr(n_states),
+                                                       _ptr(first_bad), _ptr(t), opt(lvq), opt(fbq), K if chained else 0,
+                                                       opt(count) if chained else None, opt(pair) if chained else None,
+                                                       opt(dist) if chained else None, sh))
+        if K and not chained:
+            _lib.check(_lib.lib().mopa_contacts_batch(csc.handle, _ptr(fbq), _ptr(qpos_env), N, spe, float(self.scene.contact_threshold), K,
+                                                      _ptr(count), _ptr(pair), _ptr(dist), sh))
+        blockers = ContactReport(count, pair, dist, self.scene.model) if K else None
+        return MotionReport(valid, n_states, first_bad, t, lvq, fbq if states else None, blockers)
 
     def plan(self, start, goal, max_iters: int = 2000, max_nodes: int = 1024, max_path: int = 256, seed: int = 0,
              env_id_base: int = 0, stream=None, env_ids=None, seeds=None, max_workgroups: int = 0, exclusive: bool = False,

@@ -130,6 +130,7 @@ extern "C" int mopa_contacts_batch(MopaScene *S, const double *q_active, const d
     if (!sc.ct_ctr.p) {      // zeroed once, synchronously; the kernel puts it back to zero (tile_ctr_release)
         HIP_TRY(grow(S, sc.ct_ctr, 64));
         HIP_TRY(hipMemset(sc.ct_ctr.p, 0, 64));
+        HIP_TRY(hipStreamSynchronize(nullptr));      // (a device memset may return before it has run: `st` need not wait for the null stream)
     }
     // stage 1: deepest penetration of every state
     const int rc = launch_is_valid(S, q_active, qpos_env, N, samples_per_env, nullptr, sc.ct_valid.as<uint8_t>(), sc.ct_md.as<double>(), stream);

@@ -8,6 +8,7 @@
 //      k_is_valid (this file): one wave64 per state -- small batches, single-state API calls and the device
 //        routine the planner kernels call.  Scene constants (~10 KB) are staged once per workgroup in LDS.
 //   K2 k_check_motion  one wave per segment (OMPL DiscreteMotionValidator semantics)
+//      k_motion_report (mopa_motion_report.inc) the same walk in ascending order: where a segment is blocked, and by which pairs
 //   K3 k_rrt_connect   (mopa_planner.inc) one wave per env
 //   K4 k_env_step      (mopa_env.inc) one lane per env, kinematic env.step
 //   FP64 VALU bound, no MFMA (there is no dense contraction on this path).
@@ -47,6 +48,7 @@ int mopa_fail(int code, const std::string &msg) {
 constexpr double kV5MaxReach = 32.0;        // metres: beyond this the FP32 broad phase is not used (see mopa_scene_create)
 static void plan_register_lds();            // defined with K3 (mopa_planner.inc)
 static void contacts_register_lds();        // defined with the contact report (mopa_contacts.inc)
+static void motion_report_register_lds();   // defined with the motion report (mopa_motion_report.inc)
 static void contact_frames_register_lds();  // defined with the contact frames (mopa_contact_frames.inc)
 static void contact_manifolds_register_lds();  // defined with the contact manifolds (mopa_contact_manifold.inc)
 static void k9_register_lds();              // defined with K9 path simplification (mopa_k9.inc)
@@ -110,6 +112,7 @@ struct StreamScratch {
     DevBuf mesh_rows;   // complete records of the mesh pairs within reach ([cap][kMprRow] doubles; k_mesh_rows)
     size_t slab_waves = 0;
     DevBuf mv_cnt, mv_off, mv_env, mv_q, mv_valid, mv_scan;   // expanded motion validation (mopa_motion.inc)
+    DevBuf mr_fbq;                                            // motion report: first_bad_q when the caller keeps no rows but asks for blockers
     DevBuf plan_q, plan_p, plan_ctr;                          // planner: both trees of every env, env counter (mopa_planner.inc)
     DevBuf race_rec, race_word;                               // K3 race (mopa_race.inc): the members' records, one race word per query
     DevBuf ip_walk;                                           // straight-line pre-check: walk states + verdicts (mopa_paths.inc)
@@ -789,6 +792,7 @@ static int scene_create(const MopaSceneDesc *desc, int glue_a, int glue_b, MopaS
     k1_register_lds();
     plan_register_lds();
     contacts_register_lds();
+    motion_report_register_lds();
     contact_frames_register_lds();
     contact_manifolds_register_lds();
     k9_register_lds();
@@ -810,7 +814,7 @@ extern "C" void mopa_scene_destroy(MopaScene *S) {
         if (q) (void)hipFree(q);
     for (auto &kv : S->scratch) {
         StreamScratch &sc = kv.second;
-        for (DevBuf *b : {&sc.slab, &sc.mpr, &sc.cen, &sc.mesh_list, &sc.mesh_rows, &sc.mv_cnt, &sc.mv_off, &sc.mv_env, &sc.mv_q, &sc.mv_valid, &sc.mv_scan, &sc.plan_q,
+        for (DevBuf *b : {&sc.slab, &sc.mpr, &sc.cen, &sc.mesh_list, &sc.mesh_rows, &sc.mv_cnt, &sc.mv_off, &sc.mv_env, &sc.mv_q, &sc.mv_valid, &sc.mv_scan, &sc.mr_fbq, &sc.plan_q,
                           &sc.plan_p, &sc.plan_ctr, &sc.pb_small, &sc.pb_rows, &sc.pb_act, &sc.ip_walk, &sc.ct_valid, &sc.ct_md, &sc.ct_ctr, &sc.star_tree, &sc.star_k, &sc.race_rec, &sc.race_word, &sc.glue_rows})
             if (b->p) (void)hipFree(b->p);
     }
@@ -936,6 +940,8 @@ extern "C" const char *mopa_planner_status(const MopaScene *S) { return S ? S->s
 // contact frames behind it: mopa_contact_frames_batch / _state, pair level mopa_geom_frames_batch / _host
 #include "mopa_contact_frames.inc"
 #include "mopa_contact_manifold.inc"
+// K2 motion report: k_motion_report / k_motion_report_reduce, mopa_motion_report_batch / mopa_motion_report
+#include "mopa_motion_report.inc"
 
 // The planner entry points are defined in mopa_planner.inc (K3).
 #include "mopa_planner.inc"

@@ -1,0 +1,261 @@
+// mopa_motion_report.inc -- K2, motion report: WHERE a segment is blocked, and by which pairs.
+// (included by mopa_hip.hip after mopa_motion.inc and mopa_contacts.inc)
+//
+// OMPL's DiscreteMotionValidator::checkMotion(s1, s2, lastValid), restated over the pieces mopa_check_motion_batch is made of.
+// Segment i, c = max(nd, 1) states s_k, k = 1 .. c: s_c = qb (its bits), s_k = interp_dim(a, qa[a], qb[a], (double)k / (double)c)
+// for k < c -- the expressions of k_check_motion / k_motion_expand; qa is not tested.  Per segment:
+//   valid         1 iff every s_k is valid (mopa_check_motion_batch's byte)
+//   n_states      c
+//   first_bad     the smallest k with s_k invalid, 0 for a valid segment
+//   last_valid_t  1.0 if valid, else (double)(first_bad - 1) / (double)c
+//   last_valid_q  qb if valid, qa's bits if first_bad == 1, else s_{first_bad - 1}: the values that were validated at that index
+//   first_bad_q   s_{first_bad}; qb if valid
+// Two forms behind check_motion's dispatch rule (mopa_scene_motion_kernel names the form of both calls):
+//   small batches  k_motion_report, one wave per segment, k ASCENDING with a stop at the first invalid state.  k_check_motion tests the
+//                  end state first, which is right for the verdict and useless for "first blocked": a segment whose end state alone
+//                  is invalid costs c passes here and one there, which is why this is an entry point of its own.
+//   large batches  k_motion_count -> k_motion_scan_blocks -> k_motion_expand -> launch_is_valid, all unchanged, then
+//                  k_motion_report_reduce in place of k_motion_reduce and k_motion_report_rows.  k_motion_expand stores state k of a
+//                  segment at slot o + (c - k), so first_bad = c - (largest j with vstate[o + j] == 0); both rows are copied out of the
+//                  expanded state buffer: first_bad_q from slot j = c - first_bad, last_valid_q from slot j + 1 (qa when
+//                  first_bad == 1).  The 31-bit chunking loop of motion_expanded applies, and so does its one 8-byte read-back per
+//                  chunk: this form synchronises the stream before it returns.
+// Every output word has one writer and is a plain vector store; no atomics, so two runs write the same bytes.
+// Blockers (max_contacts = K >= 1): mopa_contacts_batch over the rows first_bad_q at the scene's contact_threshold -- no narrow-phase
+// code of its own.  A valid segment's first_bad_q is qb, a valid state, whose row is the "unused" pattern.
+
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_motion_report(
+    SceneHdr h, const double *__restrict__ g_dbl, const int32_t *__restrict__ g_int, const double *__restrict__ qa_all,
+    const double *__restrict__ qb_all, const double *__restrict__ qpos_env, long long N, long long samples_per_env,
+    unsigned char *__restrict__ valid, int32_t *__restrict__ n_states, int32_t *__restrict__ first_bad, double *__restrict__ last_valid_t,
+    double *__restrict__ last_valid_q /*nullable*/, double *__restrict__ first_bad_q /*nullable*/, int hdr_lds_off, int prev_lds_off) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    LdsView v = make_view(h, smem);
+    // (the header copy in LDS: as in k_check_motion)
+    SceneHdr *lh = reinterpret_cast<SceneHdr *>(smem + hdr_lds_off);
+    for (int i = threadIdx.x; i < (int)(sizeof(SceneHdr) / 4); i += blockDim.x)
+        reinterpret_cast<int *>(lh)[i] = reinterpret_cast<const int *>(&h)[i];
+    stage_scene(h, g_dbl, g_int, const_cast<double *>(v.dbl), const_cast<int *>(v.ints));
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    double *tst = v.qbuf + h.na + h.n_pq;                                             // the state under test, [na]
+    double *prev = reinterpret_cast<double *>(smem + prev_lds_off) + wave * h.na;     // the last state that passed, [na] per wave
+    const long long stride = (long long)gridDim.x * kWavesPerBlock;
+    for (long long s = (long long)blockIdx.x * kWavesPerBlock + wave; s < N; s += stride) {
+        const double *qa = qa_all + s * h.na, *qb = qb_all + s * h.na;
+        const double *row = qpos_env + (s / samples_per_env) * h.nq;
+        const int nd = __builtin_amdgcn_readfirstlane(valid_segment_count(h, v, qa, qb));
+        const int c = nd > 0 ? nd : 1;
+        // each lane keeps its own entries of `prev` (lane a: entries a, a + 64, ...), so the copies below need no wave_sync
+        for (int i = lane; i < h.na; i += 64) prev[i] = qa[i];
+        int bad = 0;
+        for (int k = 1; k <= c; k++) {          // one call site -> one copy of FK + collision
+            const double t = (double)k / (double)c;
+            for (int i = lane; i < h.na; i += 64) tst[i] = (k == c) ? qb[i] : interp_dim(h, v, i, qa[i], qb[i], t);
+            wave_sync();
+            const bool ok = plan_state_valid_impl(lh, v.dbl, v.ints, v.grec, v.qbuf, v.wl, lane, tst, row);
+            if (__builtin_amdgcn_readfirstlane((int)ok) == 0) { bad = k; break; }
+            if (k < c)
+                for (int i = lane; i < h.na; i += 64) prev[i] = tst[i];
+        }
+        // valid: tst holds s_c = qb, which is both rows
+        for (int i = lane; i < h.na; i += 64) {
+            const double x = tst[i];
+            if (first_bad_q) first_bad_q[s * h.na + i] = x;
+            if (last_valid_q) last_valid_q[s * h.na + i] = bad ? prev[i] : x;
+        }
+        if (lane == 0) {
+            valid[s] = bad ? 0 : 1;
+            n_states[s] = c;
+            first_bad[s] = bad;
+            last_valid_t[s] = bad ? (double)(bad - 1) / (double)c : 1.0;
+        }
+        wave_sync();      // tst is rewritten by the next segment
+    }
+}
+
+// large batches: per segment the ordered reduction over its slots of the expanded verdicts
+__global__ __launch_bounds__(256) void k_motion_report_reduce(const int *__restrict__ cnt, const int *__restrict__ off, const int *__restrict__ bsum,
+                                                              const unsigned char *__restrict__ vstate, long long N,
+                                                              unsigned char *__restrict__ valid, int32_t *__restrict__ n_states,
+                                                              int32_t *__restrict__ first_bad, double *__restrict__ last_valid_t) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= N) return;
+    const int c = cnt[i], o = off[i] + bsum[i >> 8];
+    int jmax = -1;                                   // state k sits at slot c - k: the first bad k is the LAST bad slot
+    for (int j = 0; j < c; j++)
+        if (!vstate[o + j]) jmax = j;
+    const int bad = jmax < 0 ? 0 : c - jmax;
+    valid[i] = bad ? 0 : 1;
+    n_states[i] = c;
+    first_bad[i] = bad;
+    last_valid_t[i] = bad ? (double)(bad - 1) / (double)c : 1.0;
+}
+
+// ... and its two rows, one lane per output double, copied out of the expanded state buffer (first_bad: what the kernel above wrote)
+__global__ __launch_bounds__(256) void k_motion_report_rows(int na, const int *__restrict__ cnt, const int *__restrict__ off,
+                                                            const int *__restrict__ bsum, const int32_t *__restrict__ first_bad,
+                                                            const double *__restrict__ q_states, const double *__restrict__ qa, long long N,
+                                                            double *__restrict__ last_valid_q /*nullable*/, double *__restrict__ first_bad_q /*nullable*/) {
+    const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= N * na) return;
+    const long long i = e / na;
+    const int a = (int)(e - i * na);
+    const int c = cnt[i], bad = first_bad[i];
+    const size_t o = (size_t)(off[i] + bsum[i >> 8]);
+    const int j = bad ? c - bad : 0;                 // slot 0 holds s_c = qb
+    if (first_bad_q) first_bad_q[e] = q_states[(o + j) * na + a];
+    if (last_valid_q) last_valid_q[e] = (bad == 0) ? q_states[o * na + a] : (bad == 1) ? qa[e] : q_states[(o + j + 1) * na + a];
+}
+
+// one chunk of segments: motion_expanded_chunk's pipeline with the ordered reduction at its end
+static int motion_report_expanded_chunk(MopaScene *S, StreamScratch &sc, const double *qa, const double *qb, const double *qpos_env, int64_t N,
+                                        int64_t samples_per_env, int64_t first, uint8_t *valid, int32_t *n_states, int32_t *first_bad,
+                                        double *last_valid_t, double *last_valid_q, double *first_bad_q, hipStream_t st) {
+    HIP_TRY(grow(S, sc.mv_cnt, sizeof(int32_t) * (size_t)N));
+    HIP_TRY(grow(S, sc.mv_off, sizeof(int32_t) * (size_t)N));
+    int32_t *cnt = sc.mv_cnt.as<int32_t>(), *off = sc.mv_off.as<int32_t>();
+    const unsigned nb = (unsigned)((N + 255) / 256);
+    HIP_TRY(grow(S, sc.mv_scan, sizeof(int32_t) * ((size_t)nb + 1)));
+    int32_t *bsum = sc.mv_scan.as<int32_t>();
+    hipLaunchKernelGGL(k_motion_count, dim3(nb), dim3(256), 0, st, S->hdr, S->d_dbl, S->d_int, qa, qb, (long long)N, cnt, off, bsum);
+    hipLaunchKernelGGL(k_motion_scan_blocks, dim3(1), dim3(1024), 0, st, bsum, (int)nb);
+    int32_t total = 0;
+    HIP_TRY(hipMemcpyAsync(&total, bsum + nb, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    const int64_t T = total;
+    if (T <= 0 || T > 0x7fffffffLL) return fail(MOPA_ERR_LIMIT, "motion report: state count of a chunk does not fit 31 bits");
+    const size_t cap = (size_t)T + (size_t)T / 4 + 64;
+    if ((size_t)T * S->na * sizeof(double) > sc.mv_q.cap) {
+        HIP_TRY(grow(S, sc.mv_q, sizeof(double) * cap * S->na));
+        HIP_TRY(grow(S, sc.mv_env, sizeof(int32_t) * cap));
+        HIP_TRY(grow(S, sc.mv_valid, cap));
+    }
+    hipLaunchKernelGGL(k_motion_expand, dim3(nb), dim3(256), 0, st, S->hdr, S->d_dbl, S->d_int, qa, qb, (long long)N,
+                       (long long)samples_per_env, (long long)first, cnt, off, bsum, sc.mv_q.as<double>(), sc.mv_env.as<int32_t>());
+    int rc = launch_is_valid(S, sc.mv_q.as<double>(), qpos_env, T, 1, sc.mv_env.as<int32_t>(), sc.mv_valid.as<uint8_t>(), nullptr, st);
+    if (rc != MOPA_OK) return rc;
+    hipLaunchKernelGGL(k_motion_report_reduce, dim3(nb), dim3(256), 0, st, cnt, off, bsum, sc.mv_valid.as<uint8_t>(), (long long)N, valid,
+                       n_states, first_bad, last_valid_t);
+    if (last_valid_q || first_bad_q) {
+        const unsigned nbr = (unsigned)((N * S->na + 255) / 256);
+        hipLaunchKernelGGL(k_motion_report_rows, dim3(nbr), dim3(256), 0, st, S->na, cnt, off, bsum, first_bad, sc.mv_q.as<double>(), qa,
+                           (long long)N, last_valid_q, first_bad_q);
+    }
+    HIP_TRY(hipGetLastError());
+    return MOPA_OK;
+}
+
+static int motion_report_expanded(MopaScene *S, const double *qa, const double *qb, const double *qpos_env, int64_t N, int64_t samples_per_env,
+                                  uint8_t *valid, int32_t *n_states, int32_t *first_bad, double *last_valid_t, double *last_valid_q,
+                                  double *first_bad_q, hipStream_t st) {
+    // (the chunk size of motion_expanded: every 32-bit offset of the count -> scan -> expand pipeline stays in range)
+    const double res = S->hdr.resolution;
+    const int64_t per_seg = (int64_t)std::ceil(1.0 / res) + 2;
+    const int64_t chunk = std::max<int64_t>(1, 0x7fffffffLL / per_seg);
+    StreamScratch &sc = scratch_for(S, st);
+    const size_t na = (size_t)S->na;
+    for (int64_t first = 0; first < N; first += chunk) {
+        const int64_t n = std::min(chunk, N - first);
+        int rc = motion_report_expanded_chunk(S, sc, qa + first * na, qb + first * na, qpos_env, n, samples_per_env, first, valid + first,
+                                              n_states + first, first_bad + first, last_valid_t + first,
+                                              last_valid_q ? last_valid_q + first * na : nullptr, first_bad_q ? first_bad_q + first * na : nullptr, st);
+        if (rc != MOPA_OK) return rc;
+    }
+    return MOPA_OK;
+}
+
+static void motion_report_register_lds() {
+    (void)hipFuncSetAttribute((const void *)k_motion_report, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLdsBytes);
+}
+
+extern "C" int mopa_motion_report_batch(MopaScene *S, const double *qa, const double *qb, const double *qpos_env, int64_t N, int64_t samples_per_env,
+                                        uint8_t *valid, int32_t *n_states, int32_t *first_bad, double *last_valid_t, double *last_valid_q,
+                                        double *first_bad_q, int32_t K, int32_t *block_count, int32_t *block_pair, double *block_dist, void *stream) {
+    if (!S) return fail(MOPA_ERR_INVALID_ARG, "null argument");
+    if (N > 0 && (!qa || !qb || !qpos_env || !valid || !n_states || !first_bad || !last_valid_t)) return fail(MOPA_ERR_INVALID_ARG, "null argument");
+    if (N < 0 || samples_per_env <= 0) return fail(MOPA_ERR_INVALID_ARG, "N < 0 or samples_per_env <= 0");
+    const bool blockers = K != 0 || block_count || block_pair || block_dist;
+    if (blockers && K < 1) return fail(MOPA_ERR_INVALID_ARG, "max_contacts must be >= 1 (0 with null blocker buffers: no blockers)");
+    if (blockers && N > 0 && (!block_count || !block_pair || !block_dist)) return fail(MOPA_ERR_INVALID_ARG, "null blocker buffer with max_contacts >= 1");
+    MOPA_REFUSE_GLUED(S, "the motion report (mopa_motion_report_batch)");
+    // (mopa_contacts_batch's cutoff rule, ahead of the first launch)
+    if (blockers && !(std::isfinite(S->hdr.thr) && S->hdr.thr < 0.0))
+        return fail(MOPA_ERR_INVALID_ARG, "blockers: cutoff = contact_threshold must be finite and < 0 (the broad phase culls at zero margin)");
+    if (N == 0) return MOPA_OK;
+    ON_DEVICE(S->device);
+    hipStream_t st = (hipStream_t)stream;
+    if (blockers && !first_bad_q) {     // the rows the contact report reads, in library scratch
+        StreamScratch &sc = scratch_for(S, st);
+        HIP_TRY(grow(S, sc.mr_fbq, sizeof(double) * (size_t)N * (size_t)S->na));
+        first_bad_q = sc.mr_fbq.as<double>();
+    }
+    if (S->k1.use_v2 && N >= k1_motion_expand_min(S)) {
+        const int rc = motion_report_expanded(S, qa, qb, qpos_env, N, samples_per_env, valid, n_states, first_bad, last_valid_t, last_valid_q, first_bad_q, st);
+        if (rc != MOPA_OK) return rc;
+    } else {
+        dim3 grid(grid_for(S, N)), block(kBlock);
+        const int hdr_off = (S->lds_bytes + 15) & ~15;
+        const int prev_off = (hdr_off + (int)sizeof(SceneHdr) + 15) & ~15;
+        const int lds = prev_off + kWavesPerBlock * S->na * (int)sizeof(double);
+        if (lds > kMaxLdsBytes) return fail(MOPA_ERR_LIMIT, "motion report LDS does not fit");
+        hipLaunchKernelGGL(k_motion_report, grid, block, lds, st, S->hdr, S->d_dbl, S->d_int, qa, qb, qpos_env, (long long)N, (long long)samples_per_env,
+                           valid, n_states, first_bad, last_valid_t, last_valid_q, first_bad_q, hdr_off, prev_off);
+        HIP_TRY(hipGetLastError());
+    }
+    if (!blockers) return MOPA_OK;
+    return mopa_contacts_batch(S, first_bad_q, qpos_env, N, samples_per_env, S->hdr.thr, K, block_count, block_pair, block_dist, stream);
+}
+
+// one segment, host pointers, synchronous: the active entries of qpos_a -> those of qpos_b, the passive entries from qpos_a
+extern "C" int mopa_motion_report(MopaScene *S, const double *qpos_a, const double *qpos_b, int32_t *valid_out, int32_t *n_states_out,
+                                  int32_t *first_bad_out, double *last_valid_t_out, double *last_valid_q_out, double *first_bad_q_out, int32_t K,
+                                  int32_t *block_count, int32_t *block_pair, double *block_dist) {
+    if (!S || !qpos_a || !qpos_b || !valid_out || !n_states_out || !first_bad_out || !last_valid_t_out) return fail(MOPA_ERR_INVALID_ARG, "null argument");
+    const bool blockers = K != 0 || block_count || block_pair || block_dist;
+    if (blockers && K < 1) return fail(MOPA_ERR_INVALID_ARG, "max_contacts must be >= 1 (0 with null blocker buffers: no blockers)");
+    if (blockers && (!block_count || !block_pair || !block_dist)) return fail(MOPA_ERR_INVALID_ARG, "null blocker buffer with max_contacts >= 1");
+    MOPA_REFUSE_GLUED(S, "the motion report (mopa_motion_report)");
+    ON_DEVICE(S->device);
+    int rc = upload_state(S, qpos_a);       // S->d_q: the env row, then a's active entries
+    if (rc) return rc;
+    const size_t na = (size_t)S->na, Kb = blockers ? (size_t)K : 0;
+    // doubles: qb | last_valid_q | first_bad_q | t | dist[K]; int32: n_states, first_bad, count, pair[K]; then the verdict byte
+    const size_t n_dbl = 3 * na + 1 + Kb, n_i32 = 3 + Kb;
+    std::vector<double> hb(na);
+    for (size_t a = 0; a < na; a++) hb[a] = qpos_b[S->active_idx[a]];
+    void *buf = nullptr;
+    HIP_TRY(hipMalloc(&buf, n_dbl * sizeof(double) + n_i32 * sizeof(int32_t) + 8));
+    double *d = static_cast<double *>(buf);
+    int32_t *w = reinterpret_cast<int32_t *>(d + n_dbl);
+    uint8_t *vb = reinterpret_cast<uint8_t *>(w + n_i32);
+    hipError_t e = hipMemcpy(d, hb.data(), na * sizeof(double), hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        rc = mopa_motion_report_batch(S, S->d_q + S->nq, d, S->d_q, 1, 1, vb, w, w + 1, d + 3 * na, d + na, d + 2 * na, K, blockers ? w + 2 : nullptr,
+                                      blockers ? w + 3 : nullptr, blockers ? d + 3 * na + 1 : nullptr, nullptr);
+        std::vector<double> hd(n_dbl);
+        std::vector<int32_t> hw(n_i32);
+        uint8_t hv = 0;
+        if (rc == MOPA_OK) {
+            e = hipMemcpy(hd.data(), d, n_dbl * sizeof(double), hipMemcpyDeviceToHost);      // (synchronises with the null stream's launches)
+            if (e == hipSuccess) e = hipMemcpy(hw.data(), w, n_i32 * sizeof(int32_t), hipMemcpyDeviceToHost);
+            if (e == hipSuccess) e = hipMemcpy(&hv, vb, 1, hipMemcpyDeviceToHost);
+        }
+        if (rc == MOPA_OK && e == hipSuccess) {
+            *valid_out = hv;
+            *n_states_out = hw[0];
+            *first_bad_out = hw[1];
+            *last_valid_t_out = hd[3 * na];
+            if (last_valid_q_out) std::memcpy(last_valid_q_out, &hd[na], na * sizeof(double));
+            if (first_bad_q_out) std::memcpy(first_bad_q_out, &hd[2 * na], na * sizeof(double));
+            if (blockers) {
+                *block_count = hw[2];
+                std::memcpy(block_pair, &hw[3], Kb * sizeof(int32_t));
+                std::memcpy(block_dist, &hd[3 * na + 1], Kb * sizeof(double));
+            }
+        }
+    }
+    (void)hipFree(buf);
+    if (rc != MOPA_OK) return rc;
+    HIP_TRY(e);
+    return MOPA_OK;
+}

@@ -561,6 +561,7 @@ static int plan_geometry(MopaScene *S, StreamScratch &sc, int64_t n, int max_wor
     if (!sc.plan_ctr.p) {       // [next query | waves done]: zeroed once, self-resetting afterwards (tile_ctr_release)
         HIP_TRY(grow(S, sc.plan_ctr, 64));
         HIP_TRY(hipMemset(sc.plan_ctr.p, 0, 64));       // (synchronously, once: see the validity kernels' counter in mopa_hip.hip)
+        HIP_TRY(hipStreamSynchronize(nullptr));         // (a device memset may return before it has run)
     }
     g.ctr = sc.plan_ctr.as<unsigned long long>();
     const int per_wave = plan_vec_bytes(S->na) + ms_bytes_per_wave(S->hdr.nmg, S->na, S->hdr.n_pq, ms_sc_doubles(S->hdr.nmj, S->hdr.nmb), S->hdr.npair);

@@ -236,6 +236,7 @@ static int launch_is_valid(MopaScene *S, const double *q_active, const double *q
         // last one puts [0] and [1] back to zero -- a kernel edit that adds an early return before the release breaks later launches.
         HIP_TRY(grow(S, sc.k1_ctr, 64));
         HIP_TRY(hipMemset(sc.k1_ctr.p, 0, 64));
+        HIP_TRY(hipStreamSynchronize(nullptr));      // (a device memset may return before it has run: `st` need not wait for the null stream)
     }
     unsigned long long *const d_ctr = sc.k1_ctr.as<unsigned long long>();
     double *const d_slab = sc.slab.as<double>();

@@ -208,3 +208,13 @@ class PyKinematicPlanner:
         if manifold:
             return self._scene.contacts_state(np.asarray(state_vec, dtype=np.float64), manifold=True, max_points=max_points, point_cutoff=point_cutoff)
         return self._scene.contacts_state(np.asarray(state_vec, dtype=np.float64), frames=frames)
+
+    def motion_report(self, start_vec, goal_vec, max_contacts: int = 0) -> dict:
+        """where the straight line from `start_vec` to `goal_vec` (full qpos vectors; the passive entries are start_vec's) is
+        blocked -- OMPL's checkMotion(s1, s2, lastValid): `valid`, `n_states`, `first_bad`, `last_valid_t`, `last_valid_q`,
+        `first_bad_q`, and with max_contacts >= 1 `blockers`, the pairs that make the first blocked state invalid as
+        (geom1_name, geom2_name, dist) (`Scene.motion_report_state`).  With glue_bodies it raises: the motion report is not built
+        for a glued scene"""
+        if self.glue_bodies:
+            raise NotImplementedError("motion_report() with glue_bodies: the motion report is not built for a glued scene")
+        return self._scene.motion_report_state(np.asarray(start_vec, dtype=np.float64), np.asarray(goal_vec, dtype=np.float64), max_contacts=max_contacts)
