@@ -226,6 +226,12 @@ int mopa_scene_k1_export_glued(const MopaSceneDesc *desc, int32_t body_a, int32_
  * q_active[s] (na values) over the env row qpos_env[s] (nq values); out[s][nmg][12] = each moving geom's world position
  * and row-major rotation matrix.  Returns MOPA_ERR_INVALID_ARG for an index that names no baked scene */
 int mopa_k1_baked_fk_host(int index, int64_t n, const double *q_active, const double *qpos_env, double *out);
+/* the kernel's walk is a sparse one (products with the scene's exact zeros and ones left out) guarded per state, with the dense walk
+ * run over it when the guard's flag is up: mopa_k1_baked_fk_host is that production path.  mopa_k1_baked_fk_sparse_host: the sparse
+ * walk alone, no re-run: out[s][nmg][7] = raw position and quaternion of each moving geom, tripped[s] = the guard's flag.
+ * mopa_k1_baked_fk_pose_host: the same layout from the dense walk */
+int mopa_k1_baked_fk_sparse_host(int index, int64_t n, const double *q_active, const double *qpos_env, double *out, uint8_t *tripped);
+int mopa_k1_baked_fk_pose_host(int index, int64_t n, const double *q_active, const double *qpos_env, double *out);
 /* the resident pairs of baked scene #index (pairs the baked walk evaluates in place), as the walk computes them on the host:
    out[n][n_res] distances in the order of the traits' list; *n_res (nullable) receives their number */
 int mopa_k1_baked_resident_host(int index, int64_t n, const double *q_active, const double *qpos_env, double *out, int32_t *n_res);

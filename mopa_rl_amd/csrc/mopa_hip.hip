@@ -689,11 +689,30 @@ void k1_static_host(int64_t n, const double *q_active, const double *qpos_env, u
         (k1_static_host_geom<TR, M>(cen, axw, kn, ko, a, std::make_integer_sequence<int, TR::pnum[M]>{}), ...);
     }
 }
+// the production path of the baked kernel per state: the sparse walk, and the dense one over it when the state's guard flag is up
 template <class TR>
 void k1_fk_host(int64_t n, const double *q_active, const double *qpos_env, double *out) {
     for (int64_t s = 0; s < n; s++) {
         K1HostSink sink{out + (size_t)s * 12 * TR::nmg};
-        k1_fk_baked<TR>(q_active + (size_t)s * TR::na, qpos_env + (size_t)s * TR::nq, sink, std::make_integer_sequence<int, TR::nmb>{});
+        bool trip = true;
+        if constexpr (k1_sparse_on<TR>)
+            trip = k1_fk_baked<TR, true>(q_active + (size_t)s * TR::na, qpos_env + (size_t)s * TR::nq, sink, std::make_integer_sequence<int, TR::nmb>{});
+        if (trip) k1_fk_baked<TR>(q_active + (size_t)s * TR::na, qpos_env + (size_t)s * TR::nq, sink, std::make_integer_sequence<int, TR::nmb>{});
+    }
+}
+// raw poses (position, quaternion) of one walk, no re-run: SPARSE with the guard's flag per state, dense with flags 0
+struct K1PoseHostSink {
+    double *out;   // [nmg][7]
+    void operator()(int m, V3 gp, Q4 gq) { pose7_st<1>(out + 7 * m, gp, gq); }
+    void resident(int, double) {}
+    void axis(int, unsigned) {}
+};
+template <class TR, bool SPARSE>
+void k1_pose_host(int64_t n, const double *q_active, const double *qpos_env, double *out, uint8_t *tripped) {
+    for (int64_t s = 0; s < n; s++) {
+        K1PoseHostSink sink{out + (size_t)s * 7 * TR::nmg};
+        const bool trip = k1_fk_baked<TR, SPARSE>(q_active + (size_t)s * TR::na, qpos_env + (size_t)s * TR::nq, sink, std::make_integer_sequence<int, TR::nmb>{});
+        if (tripped) tripped[s] = trip ? 1 : 0;
     }
 }
 template <class TR>
@@ -709,6 +728,23 @@ extern "C" int mopa_k1_baked_fk_host(int index, int64_t n, const double *q_activ
 #define MOPA_K1_FK_HOST(i_, T_) if (index == i_) { k1_fk_host<T_>(n, q_active, qpos_env, out); return MOPA_OK; }
     MOPA_K1_BAKED_SCENES(MOPA_K1_FK_HOST)
 #undef MOPA_K1_FK_HOST
+    return fail(MOPA_ERR_INVALID_ARG, "no baked scene #" + std::to_string(index));
+}
+// The sparse walk of baked scene #index alone, on the host: out[n][nmg][7] raw poses (position, quaternion), tripped[n] the guard's
+// flag per state; no dense re-run.  mopa_k1_baked_fk_pose_host: the same layout from the dense walk (what tools/bake_k1_scenes.py
+// looks for exact zeros in when it marks the sparse bodies).
+extern "C" int mopa_k1_baked_fk_sparse_host(int index, int64_t n, const double *q_active, const double *qpos_env, double *out, uint8_t *tripped) {
+    if (n < 0 || (n > 0 && (!q_active || !qpos_env || !out || !tripped))) return fail(MOPA_ERR_INVALID_ARG, "null argument / negative count");
+#define MOPA_K1_SPARSE_HOST(i_, T_) if (index == i_) { k1_pose_host<T_, true>(n, q_active, qpos_env, out, tripped); return MOPA_OK; }
+    MOPA_K1_BAKED_SCENES(MOPA_K1_SPARSE_HOST)
+#undef MOPA_K1_SPARSE_HOST
+    return fail(MOPA_ERR_INVALID_ARG, "no baked scene #" + std::to_string(index));
+}
+extern "C" int mopa_k1_baked_fk_pose_host(int index, int64_t n, const double *q_active, const double *qpos_env, double *out) {
+    if (n < 0 || (n > 0 && (!q_active || !qpos_env || !out))) return fail(MOPA_ERR_INVALID_ARG, "null argument / negative count");
+#define MOPA_K1_POSE_HOST(i_, T_) if (index == i_) { k1_pose_host<T_, false>(n, q_active, qpos_env, out, nullptr); return MOPA_OK; }
+    MOPA_K1_BAKED_SCENES(MOPA_K1_POSE_HOST)
+#undef MOPA_K1_POSE_HOST
     return fail(MOPA_ERR_INVALID_ARG, "no baked scene #" + std::to_string(index));
 }
 // The resident pairs of baked scene #index as the walk evaluates them, on the host: out[n][n_res] distances in the order of the

@@ -24,6 +24,13 @@ constexpr int kMprCapV5 = 128;     // per-wave ring of cylinder pairs waiting fo
 constexpr int kMprRow = 32;        // doubles per row: geom 1 record[15], geom 2 record[15], state index, types
 constexpr float kCullEps = 2.0e-5f;
 
+// Image of a pair distance for the depth minimum (atomicMin over f64_sortable images).  A NaN distance -- a state with a non-finite
+// joint value -- takes ONE image, that of the negative quiet NaN, below every number's: such a state's depth is then a NaN whatever
+// sign its NaNs carry.  Left to f64_sortable a negative NaN is the smallest image and a positive one the largest, and the sign
+// follows which operand of an instruction carried the NaN, which the compiler settles per instantiation: the generic and the baked
+// kernel then answer differently for the same state.
+MOPA_D unsigned long long v5_depth_image(double d) { return d != d ? 0x0007ffffffffffffull : f64_sortable(d); }
+
 // Scene traits of k_is_valid_v5.  K1Generic: every scene table is read at run time (LDS / scalar loads + v_readlane
 // broadcasts).  A baked scene (mopa_valid_v5_baked.inc, written by tools/bake_k1_scenes.py from the host export of a
 // committed scene) carries its FP32 pair table as compile-time constants: pass A becomes straight-line compares against
@@ -189,11 +196,105 @@ MOPA_D void v5_pass_a_dispatch(int m, float cx, float cy, float cz, const float 
 // inputs (active values, passive coordinates) are read before the first pose leaves, so the pose stores drain under the
 // rest of the walk and pass A.  `sink(m, pos, quat)` receives moving geom m's world pose.
 MOPA_HD constexpr double k1_bits(unsigned long long b) { return __builtin_bit_cast(double, b); }
+
+// Sparse form of the walk (bodies marked in TR::fk_sparse by tools/bake_k1_scenes.py).  The scene's literals are full of exact zeros
+// and ones -- identity geom quaternions, local positions (0, 0, z), hinge axes (0, 0, 1), slide axes (0, -+1, 0) -- but the compiler
+// may not fold x * 0.0 or fma(x, 0.0, acc) under IEEE rules, so the dense walk multiplies by them.  The sparse form drops every
+// product whose constant factor is an exact zero (a literal, or the hinge quaternion's 0 * sn), turns x * (+-1) into +-x, and keeps
+// the order and the fma / mul / add structure of the terms that remain.
+// Lemma (finite operands, no overflow): every intermediate and every result of the sparse walk is bit-equal to the dense walk's, or
+// a zero in both (possibly of different sign).  Induction over the operations: a * 0 = +-0 exactly; acc + (+-0) = acc for acc != 0
+// and a zero otherwise; fma(a, b, +-0) = round(a b) whichever zero, unless a b is itself a zero; fma(a, +-1, acc) = round(acc +- a);
+// products and sums of equal-or-both-zero operands are again equal-or-both-zero; quat_normalize's comparisons do not see a zero's sign.
+// So a sparse result that is nonzero has the dense walk's bits, and only the sign of an exact zero is in doubt.  The guard, one flag per lane:
+//   1. an active or passive input fails |x| <= 2^20 (written so that NaN fails).  Under the bound nothing overflows: every quaternion
+//      the walk holds is a product of normalised ones (components <= 1 + 1e-15), matrices have entries <= 3, positions are sums of at
+//      most nmb literal offsets (metres) and slide travels |dq| <= 2^20 times such entries, mopa_sincos reduces |x| <= 2^19 with
+//      k <= 2^19 exactly, and the free joint's norm^2 <= 2^42: all below 2^64, far from 2^1024;
+//   2. a stored pose component (3 position, 4 quaternion) of a marked body's geom is an exact zero (one compare each).
+// If any lane of the wave raises its flag, the wave runs the dense walk for the tile, which overwrites everything the sparse one left
+// (slab rows, FP32 centres, axis words, resident distances).  Without a flag those are the dense walk's bits already: they are
+// functions of the stored poses.  The marks affect speed only (a body whose geoms have structural zeros would trip in every tile):
+// the bake script marks a body only if no stored component of it or of a body below it was zero on a seeded sample, never a
+// free-jointed one, and only with every body below it.  MOPA_V5_NO_SPARSE_FK: dense walk only (the knock-out build of tools/k1_knock.sh).
+#ifdef MOPA_V5_NO_SPARSE_FK
+template <class TR> constexpr bool k1_sparse_on = false;
+#else
+template <class TR> constexpr bool k1_sparse_on = true;
+#endif
+template <class TR>
+MOPA_HD constexpr bool k1_body_sparse(int B) {
+    if constexpr (k1_sparse_on<TR>) return TR::fk_sparse[B];
+    else return false;
+}
+constexpr double kSparseInMax = 0x1p20;     // guard 1: bound on the inputs' magnitude
+enum K1Term : int { KT_ZERO = 0, KT_ONE, KT_NEG, KT_GEN };   // a constant factor: +-0, 1, -1, anything else
+MOPA_HD constexpr int k1_kind(unsigned long long b) {
+    return (b << 1) == 0ull ? KT_ZERO : b == 0x3ff0000000000000ull ? KT_ONE : b == 0xbff0000000000000ull ? KT_NEG : KT_GEN;
+}
+// acc <- fma(a, b, acc) for a factor b of kind KIND; FIRST: every term before this one was dropped (the dense code's accumulator is a zero)
+template <int KIND, bool FIRST>
+MOPA_HD double k1_term(double acc, double a, double b) {
+    if constexpr (KIND == KT_ZERO) return acc;
+    else if constexpr (FIRST) return KIND == KT_ONE ? a : KIND == KT_NEG ? -a : a * b;
+    else return KIND == KT_ONE ? acc + a : KIND == KT_NEG ? acc - a : fma(a, b, acc);
+}
+// fma(a2, b2, fma(a1, b1, a0 * b0)) / fma(a3, b3, ...) without the dropped terms (all dropped: 0)
+template <int K0, int K1, int K2>
+MOPA_HD double k1_chain3(double a0, double b0, double a1, double b1, double a2, double b2) {
+    double acc = 0.0;
+    acc = k1_term<K0, true>(acc, a0, b0);
+    acc = k1_term<K1, K0 == KT_ZERO>(acc, a1, b1);
+    acc = k1_term<K2, K0 == KT_ZERO && K1 == KT_ZERO>(acc, a2, b2);
+    return acc;
+}
+template <int K0, int K1, int K2, int K3>
+MOPA_HD double k1_chain4(double a0, double b0, double a1, double b1, double a2, double b2, double a3, double b3) {
+    double acc = k1_chain3<K0, K1, K2>(a0, b0, a1, b1, a2, b2);
+    return k1_term<K3, K0 == KT_ZERO && K1 == KT_ZERO && K2 == KT_ZERO>(acc, a3, b3);
+}
+// quat_mul(a, b), b's components of kinds KW KX KY KZ: the terms of quat_mul in its order
+template <int KW, int KX, int KY, int KZ>
+MOPA_HD Q4 k1_quat_mul_s(Q4 a, Q4 b) {
+    Q4 r;
+    r.w = k1_chain4<KW, KX, KY, KZ>(a.w, b.w, -a.x, b.x, -a.y, b.y, -a.z, b.z);
+    r.x = k1_chain4<KX, KW, KZ, KY>(a.w, b.x, a.x, b.w, a.y, b.z, -a.z, b.y);
+    r.y = k1_chain4<KY, KZ, KW, KX>(a.w, b.y, -a.x, b.z, a.y, b.w, a.z, b.x);
+    r.z = k1_chain4<KZ, KY, KX, KW>(a.w, b.z, a.x, b.y, -a.y, b.x, a.z, b.w);
+    return r;
+}
+// mat_vec(M, v), v's components of kinds KX KY KZ; matrix entries that only meet dropped terms are never read
+template <int KX, int KY, int KZ>
+MOPA_HD V3 k1_mat_vec_s(const double *M, V3 v) {
+    return V3{k1_chain3<KX, KY, KZ>(M[0], v.x, M[1], v.y, M[2], v.z), k1_chain3<KX, KY, KZ>(M[3], v.x, M[4], v.y, M[5], v.z),
+              k1_chain3<KX, KY, KZ>(M[6], v.x, M[7], v.y, M[8], v.z)};
+}
+// add3(p, mat_vec(M, v)); all three terms dropped: p + (+-0), a copy
+template <int KX, int KY, int KZ>
+MOPA_HD V3 k1_offset_s(V3 p, const double *M, V3 v) {
+    if constexpr (KX == KT_ZERO && KY == KT_ZERO && KZ == KT_ZERO) return p;
+    else return add3(p, k1_mat_vec_s<KX, KY, KZ>(M, v));
+}
+// guard 2: an exact zero among the seven stored components of a pose
+MOPA_HD bool k1_zero7(const V3 &p, const Q4 &q) {
+    return (p.x == 0.0) | (p.y == 0.0) | (p.z == 0.0) | (q.w == 0.0) | (q.x == 0.0) | (q.y == 0.0) | (q.z == 0.0);
+}
+// the flag is folded geom by geom: left to itself the compiler gathers the 63 compares at the end of the walk and keeps every pose
+// they read in registers until then (256 VGPRs and spills where the walk needs 238)
+MOPA_HD void k1_pin(unsigned &w) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("" : "+v"(w));
+#else
+    (void)w;
+#endif
+}
+
 template <class TR>
 struct K1FkRegs {
     V3 pos;
     Q4 quat;
     double mat[9];
+    unsigned trip;             // sparse walk: the lane's guard flag (0 / 1)
     V3 save_pos[TR::n_save];
     Q4 save_quat[TR::n_save];
     V3 res_pos[kResMax];       // resident pair r: what its routine needs of the geom posed first -- the centre,
@@ -234,16 +335,28 @@ template <class TR, int M, class Sink, int... R>
 MOPA_HD void k1_fk_residents(K1FkRegs<TR> &r, const V3 &gp, const Q4 &gq, Sink &sink, std::integer_sequence<int, R...>) {
     (k1_fk_resident<TR, M, R>(r, gp, gq, sink), ...);
 }
-template <class TR, int M, class Sink>
+// SP: the sparse form (its body is marked and the walk is the sparse one)
+template <class TR, int M, bool SP, class Sink>
 MOPA_HD void k1_fk_geom(K1FkRegs<TR> &r, Sink &sink) {
     constexpr const unsigned long long *gd = TR::fk_gd[M];   // lpos[3] lquat[4]
-    const V3 gp = add3(r.pos, mat_vec(r.mat, V3{k1_bits(gd[0]), k1_bits(gd[1]), k1_bits(gd[2])}));
-    const Q4 gq = quat_mul(r.quat, Q4{k1_bits(gd[3]), k1_bits(gd[4]), k1_bits(gd[5]), k1_bits(gd[6])});
+    const V3 lp{k1_bits(gd[0]), k1_bits(gd[1]), k1_bits(gd[2])};
+    const Q4 lq{k1_bits(gd[3]), k1_bits(gd[4]), k1_bits(gd[5]), k1_bits(gd[6])};
+    V3 gp;
+    Q4 gq;
+    if constexpr (SP) {
+        gp = k1_offset_s<k1_kind(gd[0]), k1_kind(gd[1]), k1_kind(gd[2])>(r.pos, r.mat, lp);
+        gq = k1_quat_mul_s<k1_kind(gd[3]), k1_kind(gd[4]), k1_kind(gd[5]), k1_kind(gd[6])>(r.quat, lq);
+        r.trip |= k1_zero7(gp, gq) ? 1u : 0u;
+        k1_pin(r.trip);
+    } else {
+        gp = add3(r.pos, mat_vec(r.mat, lp));
+        gq = quat_mul(r.quat, lq);
+    }
     sink(M, gp, gq);
     if constexpr (k1_axis_owner<TR>(M)) sink.axis(TR::ax_slot[M], k1_axis_word(gq));
     k1_fk_residents<TR, M>(r, gp, gq, sink, std::make_integer_sequence<int, k1_n_res<TR>>{});
 }
-template <class TR, int B, class Sink, int... G>
+template <class TR, int B, bool SPARSE, class Sink, int... G>
 MOPA_HD void k1_fk_body(K1FkRegs<TR> &r, const double *qact, const double *sn, const double *cs, const double *pv, Sink &sink,
                         std::integer_sequence<int, G...>) {
     constexpr const int *bi = TR::fk_body[B];                // load, static frame, save, first geom, geoms, joints, type, anchor 0, value slot
@@ -251,6 +364,7 @@ MOPA_HD void k1_fk_body(K1FkRegs<TR> &r, const double *qact, const double *sn, c
     constexpr bool jp0 = bi[7] != 0;
     constexpr const unsigned long long *bd = TR::fk_bd[B];   // pos[3] quat[4] axis[3] jpos[3] ref
     static_assert(jn <= 1 && sizeof...(G) == bi[4], "baked walk: one joint per body at most");
+    constexpr bool SP = SPARSE && k1_body_sparse<TR>(B) && !(jn == 1 && jt == J_FREE);
     if constexpr (jn == 1 && jt == J_FREE) {
         fk_free_step(pv + (src - TR::na), r.pos, r.quat);
     } else {
@@ -270,13 +384,37 @@ MOPA_HD void k1_fk_body(K1FkRegs<TR> &r, const double *qact, const double *sn, c
             ppos = r.pos;
             pquat = r.quat;
         }
-        r.pos = add3(ppos, mat_vec(r.mat, V3{k1_bits(bd[0]), k1_bits(bd[1]), k1_bits(bd[2])}));
-        r.quat = quat_mul(pquat, Q4{k1_bits(bd[3]), k1_bits(bd[4]), k1_bits(bd[5]), k1_bits(bd[6])});
+        const V3 bp{k1_bits(bd[0]), k1_bits(bd[1]), k1_bits(bd[2])};
+        const Q4 bq{k1_bits(bd[3]), k1_bits(bd[4]), k1_bits(bd[5]), k1_bits(bd[6])};
+        if constexpr (SP) {
+            r.pos = k1_offset_s<k1_kind(bd[0]), k1_kind(bd[1]), k1_kind(bd[2])>(ppos, r.mat, bp);
+            r.quat = k1_quat_mul_s<k1_kind(bd[3]), k1_kind(bd[4]), k1_kind(bd[5]), k1_kind(bd[6])>(pquat, bq);
+        } else {
+            r.pos = add3(ppos, mat_vec(r.mat, bp));
+            r.quat = quat_mul(pquat, bq);
+        }
         if constexpr (jn == 1) {
             const V3 ax{k1_bits(bd[7]), k1_bits(bd[8]), k1_bits(bd[9])}, jp{k1_bits(bd[10]), k1_bits(bd[11]), k1_bits(bd[12])};
             constexpr double ref = k1_bits(bd[13]);
-            if constexpr (src < TR::na) apply_joint_sc(jt, ax, jp, jp0, qact[src] - ref, sn[src], cs[src], r.pos, r.quat);
-            else apply_joint(jt, ax, jp, jp0, pv[src - TR::na] - ref, r.pos, r.quat);
+            constexpr int kax = k1_kind(bd[7]), kay = k1_kind(bd[8]), kaz = k1_kind(bd[9]);
+            if constexpr (SP && jt == J_HINGE && jp0 && kax == KT_ZERO && kay == KT_ZERO && kaz == KT_ONE) {
+                // axis (0, 0, 1): apply_joint_sc's ql = (cs, 0 sn, 0 sn, 1 sn) = (cs, +-0, +-0, sn)
+                double s1, c1;
+                if constexpr (src < TR::na) { s1 = sn[src]; c1 = cs[src]; }
+                else mopa_sincos(0.5 * (pv[src - TR::na] - ref), s1, c1);
+                r.quat = k1_quat_mul_s<KT_GEN, KT_ZERO, KT_ZERO, KT_GEN>(r.quat, Q4{c1, 0.0, 0.0, s1});
+            } else if constexpr (SP && jt == J_SLIDE) {
+                // apply_joint_sc's slide: with an axis-aligned axis one column of the matrix survives
+                double dq;
+                if constexpr (src < TR::na) dq = qact[src] - ref;
+                else dq = pv[src - TR::na] - ref;
+                double jm[9];
+                quat2mat(jm, r.quat);
+                r.pos = addscl3(r.pos, k1_mat_vec_s<kax, kay, kaz>(jm, ax), dq);
+            } else {
+                if constexpr (src < TR::na) apply_joint_sc(jt, ax, jp, jp0, qact[src] - ref, sn[src], cs[src], r.pos, r.quat);
+                else apply_joint(jt, ax, jp, jp0, pv[src - TR::na] - ref, r.pos, r.quat);
+            }
         }
         r.quat = quat_normalize(r.quat);
     }
@@ -285,10 +423,12 @@ MOPA_HD void k1_fk_body(K1FkRegs<TR> &r, const double *qact, const double *sn, c
         r.save_pos[save] = r.pos;
         r.save_quat[save] = r.quat;
     }
-    (k1_fk_geom<TR, mgadr + G>(r, sink), ...);
+    (k1_fk_geom<TR, mgadr + G, SP>(r, sink), ...);
 }
-template <class TR, class Sink, int... B>
-MOPA_HD void k1_fk_baked(const double *qa_row, const double *env_row, Sink &sink, std::integer_sequence<int, B...>) {
+// SPARSE: marked bodies take their sparse form; returns the lane's guard flag (the caller re-runs the dense walk, SPARSE = false,
+// when it is set; the dense walk returns false)
+template <class TR, bool SPARSE = false, class Sink, int... B>
+MOPA_HD bool k1_fk_baked(const double *qa_row, const double *env_row, Sink &sink, std::integer_sequence<int, B...>) {
     static_assert(TR::na <= 8 && TR::n_pq >= 1 && TR::n_save >= 1, "baked walk: at most 8 active values; array sizes padded to 1");
     static_assert(TR::n_res <= kResMax, "baked walk: at most kResMax resident pairs");
     double qact[TR::na], pv[TR::n_pq], sn[TR::na], cs[TR::na];
@@ -302,15 +442,28 @@ MOPA_HD void k1_fk_baked(const double *qa_row, const double *env_row, Sink &sink
     K1FkRegs<TR> r;
     r.pos = V3{0.0, 0.0, 0.0};
     r.quat = Q4{1.0, 0.0, 0.0, 0.0};
-    (k1_fk_body<TR, B>(r, qact, sn, cs, pv, sink, std::make_integer_sequence<int, TR::fk_body[B][4]>{}), ...);
+    r.trip = 0u;
+    if constexpr (SPARSE) {
+#pragma unroll
+        for (int a = 0; a < TR::na; a++) r.trip |= !(fabs(qact[a]) <= kSparseInMax) ? 1u : 0u;
+#pragma unroll
+        for (int k = 0; k < TR::n_pq; k++) r.trip |= !(fabs(pv[k]) <= kSparseInMax) ? 1u : 0u;
+        k1_pin(r.trip);
+    }
+    (k1_fk_body<TR, B, SPARSE>(r, qact, sn, cs, pv, sink, std::make_integer_sequence<int, TR::fk_body[B][4]>{}), ...);
+    return r.trip != 0u;
 }
 // the kernel's sink: pose -> the geom's slab row, FP32 centre -> the tile's centre table in LDS (what pass A, v5_flush and the
 // MPR ring read, exactly as the generic walk writes them)
-struct V5FkSink {
+// COLD: the dense walk behind the sparse one's guard.  Each geom's slab address passes through an empty asm: in that rarely run
+// block the compiler otherwise forms all the rows' addresses up front and spills VGPRs to hold them.
+template <bool COLD>
+struct V5FkSinkT {
     double *slab;   // this lane's place in the wave's slab
     float *cen;     // this lane's place in the centre table
     MOPA_D void operator()(int m, V3 gp, Q4 gq) {
         double *sp = slab + (size_t)m * kSlabStride;
+        if constexpr (COLD) asm volatile("" : "+v"(sp));
         pose7_st<64>(sp, gp, gq);
         float *cp = cen + (size_t)m * 3 * 64;
         cp[0] = (float)gp.x; cp[64] = (float)gp.y; cp[128] = (float)gp.z;
@@ -320,6 +473,7 @@ struct V5FkSink {
     int ax_row;     // first row of the axis table, in rows of the centre table (3 nmg: it follows the centres)
     MOPA_D void axis(int slot, unsigned word) { reinterpret_cast<unsigned *>(cen)[(ax_row + slot) * 64] = word; }
 };
+using V5FkSink = V5FkSinkT<false>;
 
 struct V5Lds {
     float *cen;                 // [nmg][3][64]   geom centres of this tile, FP32; baked scenes: then [n_ax][64] packed |axis| words of
@@ -412,7 +566,7 @@ MOPA_D int v5_flush(const SceneHdr &h, const LdsView &v, const V5Lds &q, const i
             d = geom_dist<false>(code, R1, t1, R2, t2, D);
         }
         if (d <= h.thr) atomicOr(q.bad, 1ull << sl);
-        if (WANT_MD) atomicMin(q.md + sl, f64_sortable(d));
+        if (WANT_MD) atomicMin(q.md + sl, v5_depth_image(d));
     }
     int added = 0;
     if (stage == 1) {
@@ -605,7 +759,23 @@ __global__ __launch_bounds__(kBlock, TR::kBaked ? 2 : 1) void k_is_valid_v5(Scen
             double *fk_slab = slab;
             asm volatile("" : "+v"(fk_slab));
             V5FkSink sink{fk_slab, q.cen + lane, {}, 3 * TR::nmg};
-            k1_fk_baked<TR>(qa_row, env_row, sink, std::make_integer_sequence<int, TR::nmb>{});
+            // the sparse walk; a guard flag anywhere in the wave (rare: an exact zero in a stored pose, an input beyond 2^20 or not
+            // finite): the dense walk for the tile, over everything the sparse one stored
+            if constexpr (k1_sparse_on<TR>) {
+                const bool fk_trip = k1_fk_baked<TR, true>(qa_row, env_row, sink, std::make_integer_sequence<int, TR::nmb>{});
+                if (__builtin_expect(__ballot(fk_trip) != 0ull, 0)) {
+                    // (the cold walk reads its inputs again through pointers the compiler cannot trace, so nothing of the sparse walk --
+                    //  inputs, sines, the first bodies -- has to stay in registers for it)
+                    const double *qa_cold = qa_row, *env_cold = env_row;
+                    asm volatile("" : "+v"(qa_cold), "+v"(env_cold) : : "memory");
+                    V5FkSinkT<true> cold{fk_slab, q.cen + lane, {}, 3 * TR::nmg};
+                    k1_fk_baked<TR>(qa_cold, env_cold, cold, std::make_integer_sequence<int, TR::nmb>{});
+#pragma unroll
+                    for (int r = 0; r < kResMax; r++) sink.res_d[r] = cold.res_d[r];
+                }
+            } else {
+                k1_fk_baked<TR>(qa_row, env_row, sink, std::make_integer_sequence<int, TR::nmb>{});
+            }
 #pragma unroll
             for (int r = 0; r < kResMax; r++) res_d[r] = sink.res_d[r];
 #ifdef MOPA_V5_FK_REPS
@@ -806,7 +976,7 @@ __global__ __launch_bounds__(kBlock, TR::kBaked ? 2 : 1) void k_is_valid_v5(Scen
 #pragma unroll
                 for (int r = 0; r < k1_n_res<TR>; r++) {
                     rbad = rbad || (res_d[r] <= h.thr);
-                    const unsigned long long im = f64_sortable(res_d[r]);
+                    const unsigned long long im = v5_depth_image(res_d[r]);
                     rmd = im < rmd ? im : rmd;
                 }
                 rbad = rbad && act;

@@ -214,6 +214,59 @@ def resident_pairs(env: str, pi, ex: dict, fk: dict, tab, padr, nmov) -> list:
     return out
 
 
+SPARSE_SAMPLE, SPARSE_SEED = 4096, 29
+
+
+def sparse_parents(fk: dict) -> list:
+    """Parent of every moving body in the walk's program (-1: a static frame, or a free-jointed body, which takes its pose from the
+    env row): `load` -1 is the body before, >= 0 the body that last filled that save slot."""
+    parent, saved = [], {}
+    for k, (load, _sf, save, _mgadr, _mgnum, jn, jt, _jp0, _src) in enumerate(fk["bodies"]):
+        if jn == 1 and jt == J_FREE or load == -2:
+            parent.append(-1)
+        elif load == -1:
+            parent.append(k - 1)
+        else:
+            parent.append(saved[load])
+        if save >= 0:
+            saved[save] = k
+    return parent
+
+
+def sparse_marks(index: int, env: str, pi, fk: dict, nmg: int, n: int = SPARSE_SAMPLE, seed: int = SPARSE_SEED) -> list:
+    """Bodies the baked walk takes in its sparse form (mopa_valid_v5.inc, "Sparse form of the walk").  The sparse walk equals the
+    dense one except for the sign of exact zeros, and a state with an exact zero in a stored pose component of a marked body's geom
+    runs the dense walk again: a body is marked only if no stored component (position, quaternion) of its geoms, or of the geoms of
+    any body below it, is an exact zero in the dense walk (scene #index of the loaded library) anywhere on a seeded sample of
+    bench-like states (resident_sample) -- and, more cautious than the guard needs, no entry of the rotation matrix of such a
+    quaternion either: an exact zero there is a pose on a structural symmetry (Push: the base bodies, whose axes stay parallel to the
+    world's), one step from a stored zero.  Never a free-jointed body: its pose comes from the env row.  The marks are closed
+    under descent by construction.  A speed heuristic: the marks change how often the guard trips, never the result."""
+    import ctypes as C
+    q = resident_sample(pi, env, n, seed)
+    qa = np.ascontiguousarray(q[:, np.asarray(pi.ref_joint_pos_indexes)])
+    out = np.full((n, nmg, 7), np.nan)
+    rc = _lib.lib().mopa_k1_baked_fk_pose_host(index, n, qa.ctypes.data_as(C.c_void_p), q.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p))
+    if rc != 0:
+        raise SystemExit(f"{env}: the loaded library has no baked scene #{index} to sample the dense walk of (build it first)")
+    w, x, y, z = (out[:, :, 3 + i] for i in range(4))
+    # (the entries of quat2mat, operation for operation: what the narrow phase forms from a stored quaternion)
+    mat = np.stack([((w * w + x * x) - y * y) - z * z, 2.0 * (x * y - w * z), 2.0 * (x * z + w * y),
+                    2.0 * (x * y + w * z), ((w * w - x * x) + y * y) - z * z, 2.0 * (y * z - w * x),
+                    2.0 * (x * z - w * y), 2.0 * (y * z + w * x), ((w * w - x * x) - y * y) + z * z], axis=-1)
+    geom_zero = (out == 0.0).any(axis=(0, 2)) | (mat == 0.0).any(axis=(0, 2))            # [nmg]
+    parent = sparse_parents(fk)
+    nmb = fk["nmb"]
+    zero = [bool(geom_zero[b[3]: b[3] + b[4]].any()) for b in fk["bodies"]]
+    for k in range(nmb - 1, -1, -1):                      # a body's zeros count against everything above it
+        if parent[k] >= 0 and zero[k]:
+            zero[parent[k]] = True
+    free = [b[5] == 1 and b[6] == J_FREE for b in fk["bodies"]]
+    marks = [not zero[k] and not free[k] for k in range(nmb)]
+    assert all(marks[k] or not marks[parent[k]] for k in range(nmb) if parent[k] >= 0), "marks not closed under descent"
+    return marks
+
+
 G_CAPSULE, G_CYLINDER = 3, 5
 K_CULL_EPS = np.float32(2.0e-5)                 # kCullEps of mopa_valid_v5.inc
 K_AXIS_STEP = np.uint32(0x3A802009).view(np.float32)   # kAxisStep
@@ -262,7 +315,7 @@ def axis_extents(ex: dict, tab, padr, nmov, nstat) -> dict:
             "n_pairs": sum(nstat[m] for m in range(nmg) if slot[m] >= 0)}
 
 
-def bake(env: str, name: str) -> str:
+def bake(env: str, name: str, index: int) -> str:
     pi, args = scene_args(env)
     ex = _lib.k1_export(*args)
     fp = fingerprint(ex)
@@ -326,7 +379,10 @@ def bake(env: str, name: str) -> str:
     L += [f"        {u64(f)}," for f in fk["sf"]]
     L += ["    };",
           f"    static constexpr unsigned long long fk_act_ref[na] = {u64(fk['act_ref'])};",
-          f"    static constexpr int fk_pq_adr[n_pq] = {ints(fk['pq_adr'] + [0] * (n_pq - fk['n_pq']))};"]
+          f"    static constexpr int fk_pq_adr[n_pq] = {ints(fk['pq_adr'] + [0] * (n_pq - fk['n_pq']))};",
+          "    // bodies the walk takes in its sparse form (products with the exact zeros and ones above left out, guarded at run time):",
+          f"    // no exact zero in a stored pose (or its rotation matrix) of theirs or below them on {SPARSE_SAMPLE} seeded states (seed {SPARSE_SEED}); never a free-jointed body",
+          "    static constexpr bool fk_sparse[nmb] = {" + ", ".join("true" if x else "false" for x in sparse_marks(index, env, pi, fk, nmg)) + "};"]
     res = resident_pairs(env, pi, ex, fk, tab, padr, nmov)
     n_res = max(len(res), 1)
     L += ["    // resident pairs (evaluated inside the walk, skipped by pass A): owner slot M, table entry K, geom slots in routine order",
@@ -360,8 +416,8 @@ def generate() -> str:
              "// the scene compiler (mopa_scene_build.inc) that builds the tables.  Included by mopa_valid_v5.inc.",
              "// Regenerate after changing either; tests/test_k1_baked_host.py checks that this file is current.",
              ""]
-    for env, name in SCENES:
-        parts.append(bake(env, name))
+    for i, (env, name) in enumerate(SCENES):
+        parts.append(bake(env, name, i + 1))
         parts.append("")
     parts.append("// X(index from 1, traits): every baked scene")
     parts.append("#define MOPA_K1_BAKED_SCENES(X) " + " ".join(f"X({i + 1}, {name})" for i, (_, name) in enumerate(SCENES)))
