@@ -210,6 +210,10 @@ int mopa_scene_valid_kernel(const MopaScene *scene, int64_t N, char *out, int32_
 int mopa_scene_motion_kernel(const MopaScene *scene, int64_t N, char *out, int32_t cap /* >= 24 */);
 /* k_is_valid_v5 on this scene: 0 = the generic instantiation, i > 0 = the i-th baked scene (mopa_valid_v5_baked.inc) */
 int mopa_scene_k1_baked(const MopaScene *scene);
+/* what the launch plan gives a batch of N states on the lane-per-state kernel k_is_valid_v5: *tiles_per_drain = 64-state tiles
+ * a wave walks before one narrow-phase drain (1, or 2 for a pair-drain scene's verdict-only launch), *ent_cap = survivor entries
+ * the wave's buffer holds (after the axis table and the second tile's words); both 0 when the batch goes to another kernel */
+int mopa_scene_k1_drain_plan(const MopaScene *scene, int64_t N, int32_t want_min_dist, int32_t *tiles_per_drain, int32_t *ent_cap);
 /* host-only export of what k_is_valid_v5 reads from a scene (no device needed; tools/bake_k1_scenes.py):
  * sizes[8] = n_dbl, n_int, n_tab, sizeof(SceneHdr), use_v5, centre table in LDS, mesh pairs, moving geoms;
  * dbl / ints / tab / hdr (nullable) receive the two blobs, the FP32 pair table and the header, *fingerprint (nullable)

@@ -27,7 +27,7 @@ EXPORTED_SYMBOLS = [
     "mopa_scene_create_glued", "mopa_scene_glue", "mopa_glue_attach_batch", "mopa_glue_rows_batch", "mopa_scene_k1_export_glued",
     "mopa_scene_num_active", "mopa_scene_active_idx", "mopa_scene_num_pairs", "mopa_scene_lds_bytes", "mopa_scene_valid_kernel",
     "mopa_scene_motion_kernel",
-    "mopa_scene_k1_baked", "mopa_scene_k1_export", "mopa_scene_hdr_offset", "mopa_k1_baked_fk_host", "mopa_k1_baked_fk_sparse_host", "mopa_k1_baked_fk_pose_host", "mopa_k1_baked_resident_host", "mopa_k1_baked_static_host",
+    "mopa_scene_k1_baked", "mopa_scene_k1_drain_plan", "mopa_scene_k1_export", "mopa_scene_hdr_offset", "mopa_k1_baked_fk_host", "mopa_k1_baked_fk_sparse_host", "mopa_k1_baked_fk_pose_host", "mopa_k1_baked_resident_host", "mopa_k1_baked_static_host",
     "mopa_is_valid_batch", "mopa_is_valid_batch_counted", "mopa_check_motion_batch", "mopa_plan_batch", "mopa_simplify_paths_batch", "mopa_simplify_paths_max_path", "mopa_shortcut_paths_batch", "mopa_shortcut_paths_max_path", "mopa_smooth_paths_batch", "mopa_smooth_paths_max_path",
     "mopa_plan_star_batch", "mopa_plan_star", "mopa_plan_star_k", "mopa_star_params_size",
     "mopa_plan_race_batch", "mopa_plan_race", "mopa_race_params_size", "mopa_pullback_batch", "mopa_is_valid_state", "mopa_plan",
@@ -298,6 +298,7 @@ def lib() -> C.CDLL:
     L.mopa_scene_valid_kernel.argtypes = [vp, C.c_int64, C.c_char_p, C.c_int32]
     L.mopa_scene_motion_kernel.argtypes = [vp, C.c_int64, C.c_char_p, C.c_int32]
     L.mopa_scene_k1_baked.argtypes = [vp]
+    L.mopa_scene_k1_drain_plan.argtypes = [vp, C.c_int64, C.c_int32, _ip, _ip]
     L.mopa_scene_k1_export.argtypes = [vp, vp, vp, vp, vp, vp, vp]
     L.mopa_scene_hdr_offset.argtypes = [C.c_char_p]
     L.mopa_k1_baked_fk_host.argtypes = [C.c_int, C.c_int64, vp, vp, vp]

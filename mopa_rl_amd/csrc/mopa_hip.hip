@@ -110,7 +110,7 @@ struct StreamScratch {
     DevBuf k1_ctr;      // validity kernels' tile counter + exit count (self-resetting: tile_ctr_release)
     DevBuf mesh_list;   // [0] = number of rows in mesh_rows, [1] = count, then the states with a mesh pair past the main pass's broad phase
     DevBuf mesh_rows;   // complete records of the mesh pairs within reach ([cap][kMprRow] doubles; k_mesh_rows)
-    size_t slab_waves = 0;
+    size_t slab_waves = 0, slab_tiles = 0;   // what `slab` is sized for: waves, and slab regions per wave (tiles per drain)
     DevBuf mv_cnt, mv_off, mv_env, mv_q, mv_valid, mv_scan;   // expanded motion validation (mopa_motion.inc)
     DevBuf mr_fbq;                                            // motion report: first_bad_q when the caller keeps no rows but asks for blockers
     DevBuf plan_q, plan_p, plan_ctr;                          // planner: both trees of every env, env counter (mopa_planner.inc)

@@ -56,6 +56,21 @@ static int k1_baked_axis_words(int baked) {
     return 0;
 }
 
+// tiles per narrow-phase drain of baked scene #baked (k1_tiles_per_drain; 0 / generic: 1), and the LDS words per wave its second
+// verdict word (and depth words) take out of the entry buffer
+static int k1_baked_tiles_per_drain(int baked, bool want_md) {
+#define MOPA_K1_TPD(i_, T_) if (baked == i_) return want_md ? k1_tiles_per_drain<T_, true> : k1_tiles_per_drain<T_, false>;
+    MOPA_K1_BAKED_SCENES(MOPA_K1_TPD)
+#undef MOPA_K1_TPD
+    return 1;
+}
+static int k1_baked_pair_words(int baked, bool want_md) {
+#define MOPA_K1_PRW(i_, T_) if (baked == i_) return want_md ? k1_pair_words<T_, true> : k1_pair_words<T_, false>;
+    MOPA_K1_BAKED_SCENES(MOPA_K1_PRW)
+#undef MOPA_K1_PRW
+    return 0;
+}
+
 // allow the dynamic LDS size
 // the attribute is per function, not per scene: register the device maximum once so scenes of different sizes can
 // coexist in one process in any creation order (each launch still passes its own, checked, size)
@@ -78,8 +93,8 @@ static void k1_register_lds() {
 // The launch knobs (all A/B and test knobs; this is the only place that reads them).  Read per call, but for the two grid
 // overrides, which are read once per process.
 struct K1Knobs {
-    bool no_dual_dispatch, debug_mesh, rows_cap_set;
-    long long rows_cap;
+    bool no_dual_dispatch, debug_mesh, rows_cap_set, pair_tail_set;
+    long long rows_cap, pair_tail;
     int rows_blocks, fb_blocks;  // 0: not set
 };
 static K1Knobs k1_knobs() {
@@ -91,6 +106,9 @@ static K1Knobs k1_knobs() {
     const char *rc = std::getenv("MOPA_MESH_ROWS_CAP");
     k.rows_cap_set = rc != nullptr;
     k.rows_cap = rc ? atoll(rc) : 0;
+    const char *pt = std::getenv("MOPA_K1_PAIR_TAIL_TILES");     // pair drain: the last tiles of a launch that are pulled one at a time
+    k.pair_tail_set = pt != nullptr;
+    k.pair_tail = pt ? atoll(pt) : 0;
     k.rows_blocks = rows_blocks;
     k.fb_blocks = fb_blocks;
     return k;
@@ -110,6 +128,8 @@ struct K1Plan {
     int lane_lds = 0, ent_cap = 0;   // ent_cap: hdr.v5_ent_cap of this launch
     bool cen_lds = false, gate = false;   // with `baked` and want_md: the k_is_valid_v5 instantiation; gate: the mesh gate (state list) is on
     int baked = 0;
+    int tiles_per_drain = 1;         // pose-slab regions per wave (a pair-drain scene: 2)
+    long long pair_tiles = 0;        // pair drain: the leading tiles pulled two at a time (even); the rest go out singly
     bool rows = false;               // the gate hands its mesh pairs to k_mesh_rows
     long long rows_cap = 0;          // rows the gate may hand over per launch; beyond it a state goes to the state list
     unsigned rows_grid = 0;
@@ -154,9 +174,14 @@ static K1Plan k1_plan(const MopaScene *S, int64_t N, bool want_md, bool has_env_
     if (p.baked) {
         // the axis table of a baked scene (k1_axis_words, a multiple of 64 words) comes out of the entry buffer: the wave's LDS, and
         // with it two workgroups per CU, stay as the scene compiler sized them.  No room for it: the generic kernel
-        const int ax = k1_baked_axis_words(p.baked);
+        // -- and so do the words a pair-drain scene needs for its second tile (k1_pair_words_of)
+        const int ax = k1_baked_axis_words(p.baked) + k1_baked_pair_words(p.baked, want_md);
         if (p.ent_cap - ax >= 256) p.ent_cap -= ax;
         else if (ax > 0) p.baked = 0;
+        p.tiles_per_drain = k1_baked_tiles_per_drain(p.baked, want_md);
+        // the last tiles go out one at a time, one per wave of the launch: the waves then finish within one tile of each other, as
+        // without the pair drain, and a batch of no more tiles than waves runs as it did (MOPA_K1_PAIR_TAIL_TILES: another tail; tests)
+        if (p.tiles_per_drain > 1) p.pair_tiles = std::max<long long>(0, (long long)tiles - (knobs.pair_tail_set ? std::max<long long>(0, knobs.pair_tail) : (long long)p.waves)) & ~1ll;
     }
     p.lane_lds = !p.v5 ? P.v2_lds_bytes : (want_md ? P.v5_lds_bytes_md : P.v5_lds_bytes);
     // rows the gate may hand over per launch (typically 1-2 % of the states have one): beyond it a state goes to the state list
@@ -184,6 +209,14 @@ extern "C" int mopa_scene_valid_kernel(const MopaScene *S, int64_t N, char *out,
     if (!S || !out || cap < 24) return fail(MOPA_ERR_INVALID_ARG, "null argument / buffer under 24 bytes");
     const K1Plan p = k1_plan(S, N, false, false, false);
     std::snprintf(out, (size_t)cap, "%s", !p.lane ? "k_is_valid" : (p.v5 ? "k_is_valid_v5" : "k_is_valid_v2"));
+    return MOPA_OK;
+}
+extern "C" int mopa_scene_k1_drain_plan(const MopaScene *S, int64_t N, int32_t want_md, int32_t *tiles_per_drain, int32_t *ent_cap) {
+    if (!S || !tiles_per_drain || !ent_cap) return fail(MOPA_ERR_INVALID_ARG, "null argument");
+    const K1Plan p = k1_plan(S, N, want_md != 0, false, false);
+    const bool v5 = p.lane && p.v5;
+    *tiles_per_drain = v5 ? p.tiles_per_drain : 0;
+    *ent_cap = v5 ? p.ent_cap : 0;
     return MOPA_OK;
 }
 // the form mopa_check_motion_batch takes for N segments: the wave-per-segment kernel, or the expansion into states
@@ -223,12 +256,15 @@ static int launch_is_valid(MopaScene *S, const double *q_active, const double *q
         return MOPA_OK;
     }
     StreamScratch &sc = scratch_for(S, st);
-    if (p.waves > sc.slab_waves) {
-        const size_t want = std::max(p.waves, (size_t)S->n_cu * 2 * kWavesPerBlock);
-        HIP_TRY(grow(S, sc.slab, (want * (size_t)(S->hdr.nmg + S->hdr.n_save) * kSlabStride + 16) * sizeof(double)));
+    if (p.waves > sc.slab_waves || (size_t)p.tiles_per_drain > sc.slab_tiles) {
+        // (a pair-drain plan keeps one slab region per tile of a drain: on Push 2 x 57 KB per wave, 235 MB per stream at 2048 waves)
+        const size_t want = std::max(std::max(p.waves, sc.slab_waves), (size_t)S->n_cu * 2 * kWavesPerBlock);
+        const size_t tiles = std::max((size_t)p.tiles_per_drain, sc.slab_tiles);
+        HIP_TRY(grow(S, sc.slab, (want * tiles * (size_t)(S->hdr.nmg + S->hdr.n_save) * kSlabStride + 16) * sizeof(double)));
         HIP_TRY(grow(S, sc.mpr, want * (size_t)kMprCapV5 * kMprRow * sizeof(double)));
         HIP_TRY(grow(S, sc.cen, want * (size_t)S->hdr.nmg * 3 * 64 * sizeof(float)));
         sc.slab_waves = want;
+        sc.slab_tiles = tiles;
     }
     if (!sc.k1_ctr.p) {
         // zeroed ONCE, synchronously (never inside a stream capture: a first call under capture fails loudly here instead of baking a
@@ -243,7 +279,7 @@ static int launch_is_valid(MopaScene *S, const double *q_active, const double *q
     dim3 grid((unsigned)p.blocks);
 #ifdef MOPA_V2_PROFILE
     // [6 profile words | 2 pad] live right behind the slabs of this launch's waves
-    double *d_tail = d_slab + (size_t)p.blocks * kWavesPerBlock * (S->hdr.nmg + S->hdr.n_save) * kSlabStride;
+    double *d_tail = d_slab + (size_t)p.blocks * kWavesPerBlock * p.tiles_per_drain * (S->hdr.nmg + S->hdr.n_save) * kSlabStride;
     unsigned long long *d_prof = (unsigned long long *)d_tail;
     (void)zero_async(d_prof, 6 * 8, st);
 #endif
@@ -265,7 +301,7 @@ static int launch_is_valid(MopaScene *S, const double *q_active, const double *q
         hk.v5_ent_cap = p.ent_cap;
         hipLaunchKernelGGL(k1_kernel_v5(min_dist != nullptr, p.cen_lds, p.gate, p.baked), grid, block, p.lane_lds, st, hk, S->d_dbl, S->d_int, S->d_gp_tab, q_active, qpos_env,
                            (long long)N, (long long)samples_per_env, valid, min_dist, d_slab, env_idx, sc.mpr.as<double>(), mesh_list, sc.cen.as<float>(),
-                           n_dev, d_ctr, mesh_rows, p.rows_cap, rows_cnt, p.n_small);
+                           n_dev, d_ctr, mesh_rows, p.rows_cap, rows_cnt, p.n_small, p.pair_tiles);
         if (p.rows)
             hipLaunchKernelGGL(min_dist ? k_mesh_rows<true> : k_mesh_rows<false>, dim3(p.rows_grid), block, p.rows_lds, st, S->hdr, S->d_dbl, (const double *)mesh_rows,
                                (const unsigned long long *)rows_cnt, p.rows_cap, S->n_mesh_dbl, valid, min_dist);

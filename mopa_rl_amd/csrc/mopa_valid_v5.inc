@@ -40,8 +40,33 @@ MOPA_D unsigned long long v5_depth_image(double d) { return d != d ? 0x0007fffff
 struct K1Generic {
     static constexpr bool kBaked = false;
     static constexpr int n_ax = 0;
+    static constexpr int kTilesPerDrain = 1;
 };
 #include "mopa_valid_v5_baked.inc"
+
+// Pair drain (TR::kTilesPerDrain = 2): a wave pulls two consecutive tiles, runs walk, resident fold, pass A and pass B on each
+// in turn (the "halves") and evaluates the entries of both in ONE drain -- a class batch costs the same for 3 busy lanes as for
+// 64 and runs once per class present, so two tiles sharing a drain fill the batches better.  Nothing moves: the entries stay
+// 4-byte words in the same buffer with their half in bit 31, the poses stay in the slab (one region per half, so the first
+// half's survive until the drain), and the verdict word / depth words exist once per half.  The FP32 centre table and the axis
+// words are the second half's once it has walked: v5_flush and the MPR ring read slab rows and scene tables only.
+// The extra LDS words come out of the entry capacity (k1_pair_words; mopa_valid_launch.inc: k1_plan), as the axis table's do.
+// MOPA_V5_TILES_PER_DRAIN=1: every scene drains tile by tile (the knock-out build of tools/k1_knock.sh).
+// The depth-reporting instantiations stay at one tile per drain: 64 more depth words per wave on top of the verdict word would
+// leave Push 192 entries, under the 256 the launch plan asks of a baked kernel.
+#ifdef MOPA_V5_TILES_PER_DRAIN
+template <class TR, bool WANT_MD> constexpr int k1_tiles_per_drain = TR::kBaked && !WANT_MD ? MOPA_V5_TILES_PER_DRAIN : 1;
+#else
+template <class TR, bool WANT_MD> constexpr int k1_tiles_per_drain = WANT_MD ? 1 : TR::kTilesPerDrain;
+#endif
+constexpr unsigned kEntHalfBit = 31;        // entry bit: the half; the table index keeps bits 16..30
+// LDS words per wave that the second half's verdict word (and depth words) take out of the entry buffer: a multiple of 64
+template <class TR, bool WANT_MD>
+constexpr int k1_pair_words_of() {
+    constexpr int T = k1_tiles_per_drain<TR, WANT_MD>;
+    return T > 1 ? (((T - 1) * (2 + (WANT_MD ? 128 : 0)) + 63) & ~63) : 0;
+}
+template <class TR, bool WANT_MD> constexpr int k1_pair_words = k1_pair_words_of<TR, WANT_MD>();
 
 // Resident pairs of a baked scene (TR::res, chosen by tools/bake_k1_scenes.py): moving-moving pairs of a closed-form class that
 // pass A keeps in most states.  Both poses are in the owning lane's registers during the walk, so the lane evaluates the pair
@@ -481,8 +506,8 @@ struct V5Lds {
     unsigned *ent;              // [h.v5_ent_cap]    lane | owner slot << 6 | pair class << 12 | table index << 16
     unsigned *bat;              // [kBatCapV5]    entries of ONE pair class, compacted for the narrow phase
     unsigned *bat2;             // [kBatCapV5]    cylinder pairs that failed the capsule pre-test: dense batches for MPR
-    unsigned long long *bad;    // [1]
-    unsigned long long *md;     // [64]
+    unsigned long long *bad;    // [T]       one verdict word per tile of a drain (T: k1_tiles_per_drain, 1 but for a pair-drain scene)
+    unsigned long long *md;     // [T][64]
     bool tp;                    // this tile's states share one env row and the scene has tile-posed geoms: their slab rows hold ONE pose, in lane 0's place
 };
 // (the 64 depth words `md` exist only in the instantiations that report depths: the verdict-only kernels give that LDS to `ent`)
@@ -524,7 +549,8 @@ MOPA_D void v5_load_rec2(double (&R1)[15], double (&R2)[15], const SceneHdr &h, 
 // narrow phase on `n` (<= 64) entries of pair class `code` (wave-uniform: one routine runs, on full lanes)
 // stage: 0 = the class routine; 1 = cylinder pairs, closed-form pre-test on the enclosing capsules only -- entries that are
 // not proven disjoint are appended to the second ring (returns their number); 2 = cylinder pairs, portal refinement only
-template <bool WANT_MD>
+// T > 1 (pair drain): bit 31 of an entry is its half -- which slab region, verdict word, depth words and tile it belongs to
+template <bool WANT_MD, int T = 1>
 MOPA_D int v5_flush(const SceneHdr &h, const LdsView &v, const V5Lds &q, const int *s_tab, const double *slab_tile, int lane,
                     int head, int n, int code, int stage = 0, int head2 = 0, int count2 = 0, double *mpr_ring = nullptr,
                     int mpr_head = 0, int *mpr_count = nullptr, long long tile_base = 0) {
@@ -534,7 +560,9 @@ MOPA_D int v5_flush(const SceneHdr &h, const LdsView &v, const V5Lds &q, const i
     int t1s = 0, t2s = 0;
     if (lane < n) {
         e = (stage == 2 ? q.bat2 : q.bat)[(head + lane) & (kBatCapV5 - 1)];
-        const int sl = e & 63, m = (e >> 6) & 63, fl = s_tab[8 * (e >> 16) + 7];
+        const int sl = e & 63, m = (e >> 6) & 63, hf = T > 1 ? (int)(e >> kEntHalfBit) : 0;
+        const int fl = s_tab[8 * (T > 1 ? (e >> 16) & 0x7fffu : e >> 16) + 7];
+        if constexpr (T > 1) slab_tile += (size_t)hf * (size_t)(h.nmg + h.n_save) * kSlabStride;
         const int pg = fl & 0xff, cur_is_g2 = (fl >> 12) & 1, pmov = (fl >> 13) & 1, pslot = (fl >> 14) & 0xff;
         const double *D = v.dbl;
         const int *I = v.ints;
@@ -565,8 +593,8 @@ MOPA_D int v5_flush(const SceneHdr &h, const LdsView &v, const V5Lds &q, const i
         } else {
             d = geom_dist<false>(code, R1, t1, R2, t2, D);
         }
-        if (d <= h.thr) atomicOr(q.bad, 1ull << sl);
-        if (WANT_MD) atomicMin(q.md + sl, v5_depth_image(d));
+        if (d <= h.thr) atomicOr(q.bad + hf, 1ull << sl);
+        if (WANT_MD) atomicMin(q.md + 64 * hf + sl, v5_depth_image(d));
     }
     int added = 0;
     if (stage == 1) {
@@ -579,7 +607,7 @@ MOPA_D int v5_flush(const SceneHdr &h, const LdsView &v, const V5Lds &q, const i
                 double *row = mpr_ring + (size_t)((mpr_head + *mpr_count + __popcll(mask & ((1ull << lane) - 1ull))) & (kMprCapV5 - 1)) * kMprRow;
 #pragma unroll
                 for (int i = 0; i < 15; i++) { row[i] = R1s[i]; row[15 + i] = R2s[i]; }
-                row[30] = __longlong_as_double(tile_base + (long long)(e & 63));
+                row[30] = __longlong_as_double(tile_base + (long long)(T > 1 ? ((e >> kEntHalfBit) << 6) | (e & 63) : e & 63));
                 row[31] = __longlong_as_double((long long)(t1s | (t2s << 8)));
             }
             *mpr_count += nadd;
@@ -616,7 +644,7 @@ MOPA_D void v5_mpr_rows(const SceneHdr &h, const double *ring, int head, int n, 
 // All buffered survivor entries of the tile, class by class (cheapest first): entries of class c are compacted into
 // the batch ring and evaluated 64 at a time.  Without WANT_MD, entries of states that are already invalid are
 // dropped at compaction time (the per-state early-out).
-template <bool WANT_MD>
+template <bool WANT_MD, int T = 1>
 MOPA_D void v5_drain(const SceneHdr &h, const LdsView &v, const V5Lds &q, const int *s_tab, const double *slab_tile, int lane,
                      int n_ent, unsigned present, double *mpr_ring, int mpr_head, int *mpr_count, long long tile_base) {
     wave_sync();
@@ -630,7 +658,7 @@ MOPA_D void v5_drain(const SceneHdr &h, const LdsView &v, const V5Lds &q, const 
             if (i < n_ent) {
                 e = q.ent[i];
                 take = (int)((e >> 12) & 0xf) == code;      // the class travels in the entry: no dependent table read
-                if (!WANT_MD) take = take && !((*q.bad >> (e & 63)) & 1ull);
+                if (!WANT_MD) take = take && !((q.bad[T > 1 ? e >> kEntHalfBit : 0u] >> (e & 63)) & 1ull);
             }
             const unsigned long long mask = __ballot(take);
             if (!mask) continue;
@@ -639,14 +667,14 @@ MOPA_D void v5_drain(const SceneHdr &h, const LdsView &v, const V5Lds &q, const 
             if (count >= 64) {
                 wave_sync();
                 if (code == PC_CONVEX) {
-                    count2 += v5_flush<WANT_MD>(h, v, q, s_tab, slab_tile, lane, head, 64, code, 1, head2, count2, mpr_ring, mpr_head, mpr_count, tile_base);
+                    count2 += v5_flush<WANT_MD, T>(h, v, q, s_tab, slab_tile, lane, head, 64, code, 1, head2, count2, mpr_ring, mpr_head, mpr_count, tile_base);
                     if (count2 >= 64) {
-                        v5_flush<WANT_MD>(h, v, q, s_tab, slab_tile, lane, head2, 64, code, 2);
+                        v5_flush<WANT_MD, T>(h, v, q, s_tab, slab_tile, lane, head2, 64, code, 2);
                         head2 = (head2 + 64) & (kBatCapV5 - 1);
                         count2 -= 64;
                     }
                 } else {
-                    v5_flush<WANT_MD>(h, v, q, s_tab, slab_tile, lane, head, 64, code);
+                    v5_flush<WANT_MD, T>(h, v, q, s_tab, slab_tile, lane, head, 64, code);
                 }
                 head = (head + 64) & (kBatCapV5 - 1);
                 count -= 64;
@@ -654,13 +682,13 @@ MOPA_D void v5_drain(const SceneHdr &h, const LdsView &v, const V5Lds &q, const 
         }
         if (count > 0) {
             wave_sync();
-            if (code == PC_CONVEX) count2 += v5_flush<WANT_MD>(h, v, q, s_tab, slab_tile, lane, head, count, code, 1, head2, count2, mpr_ring, mpr_head, mpr_count, tile_base);
-            else v5_flush<WANT_MD>(h, v, q, s_tab, slab_tile, lane, head, count, code);
+            if (code == PC_CONVEX) count2 += v5_flush<WANT_MD, T>(h, v, q, s_tab, slab_tile, lane, head, count, code, 1, head2, count2, mpr_ring, mpr_head, mpr_count, tile_base);
+            else v5_flush<WANT_MD, T>(h, v, q, s_tab, slab_tile, lane, head, count, code);
         }
         if (code == PC_CONVEX) {
             while (count2 > 0) {      // the cylinder pairs the capsule test could not separate: dense MPR batches
                 const int nb = count2 < 64 ? count2 : 64;
-                v5_flush<WANT_MD>(h, v, q, s_tab, slab_tile, lane, head2, nb, code, 2);
+                v5_flush<WANT_MD, T>(h, v, q, s_tab, slab_tile, lane, head2, nb, code, 2);
                 head2 = (head2 + nb) & (kBatCapV5 - 1);
                 count2 -= nb;
             }
@@ -688,7 +716,11 @@ __global__ __launch_bounds__(kBlock, TR::kBaked ? 2 : 1) void k_is_valid_v5(Scen
                                                          const long long *__restrict__ n_dev /* nullable: the state count lives on the device (<= N) */, unsigned long long *__restrict__ tile_ctr,
                                                          double *__restrict__ mesh_rows /* nullable; GATE: [cap][kMprRow] complete records of the mesh pairs within reach (k_mesh_rows evaluates them) */,
                                                          long long mesh_rows_cap, unsigned long long *__restrict__ mesh_rows_cnt,
-                                                         long long n_small /* with n_dev: counts below it are served by the wave-per-state launch in front of this one */) {
+                                                         long long n_small /* with n_dev: counts below it are served by the wave-per-state launch in front of this one */,
+                                                         long long pair_tiles /* pair drain: the leading tiles (an even number) that are pulled two at a time */) {
+    constexpr int T = k1_tiles_per_drain<TR, WANT_MD>;        // tiles per drain ("Pair drain" above)
+    static_assert(T == 1 || (T == 2 && TR::kBaked), "pair drain: two tiles, baked scenes only (the generic phase 0 borrows the entry buffer)");
+    if constexpr (T > 1) static_assert(TR::padr[TR::nmg - 1] + TR::pnum[TR::nmg - 1] < (1 << 15), "pair drain: the entry's table index leaves bit 31 to the half");
     if (n_dev) {
         const long long nd = *n_dev;
         if (nd < N) N = nd;
@@ -709,6 +741,7 @@ __global__ __launch_bounds__(kBlock, TR::kBaked ? 2 : 1) void k_is_valid_v5(Scen
         const int n_cen = CEN_LDS ? h.nmg : 0;
         int ent_words = h.v5_ent_cap;
         if constexpr (k1_axis_words<TR> > 0) ent_words += k1_axis_words<TR>;
+        if constexpr (T > 1) ent_words += k1_pair_words<TR, WANT_MD>;    // (the second half's verdict / depth words, behind the first's)
         unsigned char *base = reinterpret_cast<unsigned char *>(s_tab + ((8 * h.n_gp + kTail * h.nmg + 3) & ~3)) + wave * v5_lds_per_wave(n_cen, ent_words, WANT_MD);
         q.cen = reinterpret_cast<float *>(base);
         // (a baked scene's axis table, [n_ax][64] words, sits between the centre table and the entries: a constant offset from the
@@ -718,13 +751,14 @@ __global__ __launch_bounds__(kBlock, TR::kBaked ? 2 : 1) void k_is_valid_v5(Scen
         q.bat = q.ent + h.v5_ent_cap;
         q.bat2 = q.bat + kBatCapV5;
         q.md = reinterpret_cast<unsigned long long *>(q.bat2 + kBatCapV5);
-        q.bad = WANT_MD ? q.md + 64 : q.md;
+        q.bad = WANT_MD ? q.md + 64 * T : q.md;
         q.tp = false;
     }
     const double *__restrict__ GD = g_dbl;
     const int32_t *__restrict__ GI = g_int;
     const int nslab = h.nmg + h.n_save;
-    double *slab = slab_all + ((size_t)blockIdx.x * kWavesPerBlock + wave) * (size_t)nslab * kSlabStride + lane;
+    // (pair drain: T slab regions per wave, one per half)
+    double *slab = slab_all + ((size_t)blockIdx.x * kWavesPerBlock + wave) * (size_t)(T * nslab) * kSlabStride + lane;
     const double *slab_tile = slab - lane;
     double *mpr_ring = mpr_all + ((size_t)blockIdx.x * kWavesPerBlock + wave) * (size_t)kMprCapV5 * kMprRow;
     float *gcen = CEN_LDS ? nullptr : cen_all + ((size_t)blockIdx.x * kWavesPerBlock + wave) * (size_t)h.nmg * 3 * 64 + lane;
@@ -734,17 +768,39 @@ __global__ __launch_bounds__(kBlock, TR::kBaked ? 2 : 1) void k_is_valid_v5(Scen
     // (tile_ctr_release), so no launch has to zero them first
     for (;;) {
         long long tile = 0;
-        if (lane == 0) tile = (long long)atomicAdd(tile_ctr, 1ull);
+        if (lane == 0) tile = (long long)atomicAdd(tile_ctr, (unsigned long long)T);
         tile = __shfl(tile, 0, 64);
-        const bool fin = tile >= n_tiles;
+        // pair drain: every pull adds 2.  Below pair_tiles a pull is the pair (tile, tile + 1); from there on it stands for ONE tile
+        // (pulls pair_tiles, pair_tiles + 2, ... are the tiles pair_tiles, pair_tiles + 1, ...): the last tiles of a launch go out one
+        // at a time, so the waves finish within one tile of each other as they did, not within two -- and a batch of fewer tiles than
+        // the launch has waves still keeps every wave busy (k1_plan sets pair_tiles)
+        bool single = false;
+        if constexpr (T > 1) {
+            if (tile >= pair_tiles) {
+                tile = pair_tiles + ((tile - pair_tiles) >> 1);
+                single = true;
+            }
+        }
+        const bool fin = tile >= n_tiles;      // (pair drain: decided on the first tile of the pair)
         if (!fin) {
-        long long s = tile * 64 + lane;
-        const bool act = s < N;
+        int n_ent;                 // survivor entries in the buffer and the pair classes among them: zeroed by the first half, and
+        unsigned present;          // by every drain
+        long long s;
+        bool act, need_mesh;
+        // pair drain: the halves, tile and tile + 1, one after the other through the same code (not unrolled); the entries of both wait
+        // in the buffer for the drain behind the loop.  Nothing per lane lives across halves but what is in LDS and the slab.
+        // (a do-while on a compile-time condition: with T == 1 there is no loop at all, and the kernel is the one it was)
+        int hf = 0;
+#pragma unroll 1
+        do {
+        if (T > 1 && hf > 0 && (single || tile + hf >= n_tiles)) break;       // no second tile (a single pull; an odd tile count or a device-side count that ends in the pair)
+        s = (tile + hf) * 64 + lane;
+        act = s < N;
         if (!act) s = N - 1;
         const double *qa_row = q_active + s * h.na;
         const double *env_row = qpos_env + (env_idx ? (long long)env_idx[s] : s / samples_per_env) * h.nq;
-        if (lane == 0) *q.bad = 0ull;
-        if (WANT_MD) q.md[lane] = f64_sortable(0.0);
+        if (lane == 0) q.bad[hf] = 0ull;
+        if (WANT_MD) q.md[64 * hf + lane] = f64_sortable(0.0);
 
         // ================= phase 1: forward kinematics, poses -> slab, FP32 centres -> LDS =================
         // (MOPA_V5_FK_REPS / _CULL_REPS / _KO_PASSB / _KO_DRAIN: knock-in / knock-out builds of tools/k1_knock.sh -- a phase run N
@@ -756,7 +812,7 @@ __global__ __launch_bounds__(kBlock, TR::kBaked ? 2 : 1) void k_is_valid_v5(Scen
         if constexpr (TR::kBaked) {       // (the baked scenes have no tile-posed bodies: q.tp stays false)
             // (the slab pointer passes through an empty asm once per tile: otherwise the 98 loop-invariant store addresses of the
             //  straight-line walk are hoisted out of the tile loop and held in VGPR pairs for the whole kernel)
-            double *fk_slab = slab;
+            double *fk_slab = T > 1 ? slab + (size_t)hf * (size_t)nslab * kSlabStride : slab;
             asm volatile("" : "+v"(fk_slab));
             V5FkSink sink{fk_slab, q.cen + lane, {}, 3 * TR::nmg};
             // the sparse walk; a guard flag anywhere in the wave (rare: an exact zero in a stored pose, an input beyond 2^20 or not
@@ -966,7 +1022,7 @@ __global__ __launch_bounds__(kBlock, TR::kBaked ? 2 : 1) void k_is_valid_v5(Scen
 
         // ================= phase 2: FP32 broad phase out of LDS, queue, FP64 narrow phase =================
         bool dead = !act;
-        bool need_mesh = false;
+        need_mesh = false;
         if constexpr (TR::kBaked) {
             if constexpr (k1_n_res<TR> > 0) {
                 // the resident pairs are decided: the verdict as v5_flush folds it (d <= thr), the depth through the same
@@ -981,13 +1037,15 @@ __global__ __launch_bounds__(kBlock, TR::kBaked ? 2 : 1) void k_is_valid_v5(Scen
                 }
                 rbad = rbad && act;
                 const unsigned long long rmask = __ballot(rbad);
-                if (lane == 0 && rmask) *q.bad |= rmask;
-                if (WANT_MD) q.md[lane] = rmd;
+                if (lane == 0 && rmask) q.bad[hf] |= rmask;
+                if (WANT_MD) q.md[64 * hf + lane] = rmd;
                 else dead = dead || rbad;
             }
         }
-        int n_ent = 0;
-        unsigned present = 0u;     // pair classes that have entries in the buffer
+        if (T == 1 || hf == 0) {
+            n_ent = 0;
+            present = 0u;
+        }
         for (int m = 0; m < h.nmg; m++) {
             int p0, pn;
             if (GATE) {          // the table of a scene with mesh pairs lists them too: its own (first entry, count) per geom
@@ -1103,7 +1161,7 @@ __global__ __launch_bounds__(kBlock, TR::kBaked ? 2 : 1) void k_is_valid_v5(Scen
 #undef V5_KEEP
             }
             if (!WANT_MD && deep_mask) {       // proven invalid in the broad phase: verdict set, no entries from here on, and the
-                if (lane == 0) atomicOr(q.bad, deep_mask);      // ones already queued are dropped when their class is compacted
+                if (lane == 0) atomicOr(q.bad + hf, deep_mask);      // ones already queued are dropped when their class is compacted
                 dead = dead || ((deep_mask >> lane) & 1ull);
             }
             if (dead) { surv_lo = 0u; surv_hi = 0u; }
@@ -1148,14 +1206,14 @@ __global__ __launch_bounds__(kBlock, TR::kBaked ? 2 : 1) void k_is_valid_v5(Scen
                     return;
                 }
                 if (sv) q.ent[n_ent + __builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u))] =
-                            (unsigned)lane | ((unsigned)m << 6) | (pcode << 12) | ((unsigned)(p0 + k) << 16);
+                            (unsigned)lane | ((unsigned)m << 6) | (pcode << 12) | ((unsigned)(p0 + k) << 16) | (T > 1 ? (unsigned)hf << kEntHalfBit : 0u);
                 n_ent += __popcll(mask);
                 present |= 1u << pcode;
 #ifdef MOPA_V5_KO_DRAIN
                 if (n_ent > h.v5_ent_cap - 64) n_ent = 0;
 #endif
-                if (n_ent > h.v5_ent_cap - 64) {           // buffer (almost) full: evaluate what is there
-                    v5_drain<WANT_MD>(h, v, q, s_tab, slab_tile, lane, n_ent, present, mpr_ring, mpr_head, &mpr_count, tile * 64);
+                if (n_ent > h.v5_ent_cap - 64) {           // buffer (almost) full: evaluate what is there (pair drain: of both halves, maybe)
+                    v5_drain<WANT_MD, T>(h, v, q, s_tab, slab_tile, lane, n_ent, present, mpr_ring, mpr_head, &mpr_count, tile * 64);
                     n_ent = 0;
                     present = 0u;
                 }
@@ -1166,13 +1224,26 @@ __global__ __launch_bounds__(kBlock, TR::kBaked ? 2 : 1) void k_is_valid_v5(Scen
                 for (int k = 0; k < pn; k++) pass_b_pair(k);
             }
         }
+        } while (T > 1 && ++hf < T);       // (the halves)
 #ifndef MOPA_V5_KO_DRAIN
-        if (n_ent > 0) v5_drain<WANT_MD>(h, v, q, s_tab, slab_tile, lane, n_ent, present, mpr_ring, mpr_head, &mpr_count, tile * 64);
+        if (n_ent > 0) v5_drain<WANT_MD, T>(h, v, q, s_tab, slab_tile, lane, n_ent, present, mpr_ring, mpr_head, &mpr_count, tile * 64);
 #endif
         wave_sync();
-        if (act) {
-            valid[s] = ((*q.bad >> lane) & 1ull) ? 0 : 1;
-            if (WANT_MD) min_dist[s] = f64_unsortable(q.md[lane]);
+        if constexpr (T == 1) {
+            if (act) {
+                valid[s] = ((*q.bad >> lane) & 1ull) ? 0 : 1;
+                if (WANT_MD) min_dist[s] = f64_unsortable(q.md[lane]);
+            }
+        } else {
+#pragma unroll
+            for (int ho = 0; ho < T; ho++) {        // (a second half that was skipped: a single pull, or it lies beyond N)
+                const long long so = (tile + ho) * 64 + lane;
+                if (so < N && !(ho > 0 && single)) {
+                    const int hf = ho;
+                    valid[so] = ((q.bad[hf] >> lane) & 1ull) ? 0 : 1;
+                    if (WANT_MD) min_dist[so] = f64_unsortable(q.md[64 * hf + lane]);
+                }
+            }
         }
         if (GATE && mesh_list) {     // states with a mesh pair within reach: appended to the second pass's work list
             const bool f = act && need_mesh;

@@ -34,6 +34,9 @@ OUT = os.path.join(ROOT, "mopa_rl_amd", "csrc", "mopa_valid_v5_baked.inc")
 # (env, traits name): the headline scene.  A scene is added here only once its baked kernel has been measured no slower
 # than the generic one (tools/scene_bench.py).
 SCENES = [("SawyerPushObstacle-v0", "K1Baked_SawyerPushObstacle")]
+# tiles per narrow-phase drain (TR::kTilesPerDrain; scenes not named: 1).  2 only where the pair drain has been measured faster
+# than 1 on the bench batch (DESIGN.md "Pair drain").
+TILES_PER_DRAIN = {"SawyerPushObstacle-v0": 2}
 
 
 def fnv1a64(chunks) -> int:
@@ -349,6 +352,8 @@ def bake(env: str, name: str, index: int) -> str:
          f"// contact threshold {thr!r}, pair pruning and cull radii from the scene's meta; {nmg} moving geoms, {n5} table entries",
          f"struct {name} {{",
          "    static constexpr bool kBaked = true;",
+         "    // consecutive 64-state tiles a wave walks and culls before ONE narrow-phase drain evaluates their entries together",
+         f"    static constexpr int kTilesPerDrain = {TILES_PER_DRAIN.get(env, 1)};",
          f"    static constexpr unsigned long long kFingerprint = 0x{fp:016x}ull;",
          f"    static constexpr int nmg = {nmg};",
          f"    static constexpr int padr[nmg] = {ints(padr)};",

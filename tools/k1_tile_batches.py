@@ -8,7 +8,7 @@ against the owner's bounding radius; planes: the plane test); verdict-only early
 an entry whose state an earlier class has already made invalid is dropped at compaction.  Tiles are 64 states of one kind, drawn
 with tests/conftest.sample_states.  A batch costs the same for 3 lanes as for 64, so batches per tile is the figure to watch.
 
-    python tools/k1_tile_batches.py [--tiles 16] [--resident head,right_l2] [--axis-extents] [--defer-small 0,4,8,16]
+    python tools/k1_tile_batches.py [--tiles 16] [--resident head,right_l2] [--axis-extents] [--defer-small 0,4,8,16] [--tiles-per-drain 1,2,3,4]
 
 --axis-extents: a capsule / cylinder owner is tested against a static partner's AABB with its per-axis reach r + hl |a_i| (a: the
 owner's axis) instead of its bounding radius (DESIGN.md "Axis extents in the baked pass A").
@@ -17,6 +17,9 @@ not the cylinder / convex class) is not evaluated in its tile when it has <= K l
 across tiles (tiles of one kind in sequence = one wave) and are evaluated 64 rows at a time, one routine execution per class present
 among the 64.  Deferred entries do not make their state invalid in the tile, so later classes lose that early-out.  Reported per
 tile: in-tile batches, deferred rows, the share of tiles that need the gather-only batch, and the routine executions of the ring.
+--tiles-per-drain G[,G...]: with the resident pair in the walk, G consecutive tiles of a kind share one drain (DESIGN.md "Pair drain"):
+the entries of all G wait in the buffer and each class is compacted and evaluated once over them.  The entries are the same ones;
+reported per TILE: entries evaluated, batches, lane utilisation.  (--tiles should be a multiple of every G.)
 """
 import argparse
 import collections
@@ -47,6 +50,7 @@ def main():
     ap.add_argument("--resident", default="head,right_l2", help="bodies of the pair taken out of the entry pipeline")
     ap.add_argument("--axis-extents", action="store_true", help="static cull of capsule / cylinder owners with r + hl |a_i| per axis")
     ap.add_argument("--defer-small", default="", help="comma list of K: class remainders of <= K live entries wait in a per-wave ring")
+    ap.add_argument("--tiles-per-drain", default="", help="comma list of G: G consecutive tiles share one drain")
     a = ap.parse_args()
     pi = planner_inputs(a.env)
     m = pi.model
@@ -186,6 +190,10 @@ def main():
         for K in [int(x) for x in a.defer_small.split(",") if x]:
             b, r, g, e = defer_stats([sv[64 * t: 64 * t + 64] for t in range(a.tiles)], K)
             print(f"{kind:10s} defer <= {K:2d}: in-tile batches {b:5.2f}, deferred rows {r:5.2f}, gather-only batch in {g:4.2f} of the tiles, ring executions {e:4.2f} per tile")
+        for G in [int(x) for x in a.tiles_per_drain.split(",") if x]:
+            # (tile_stats takes any number of states: a group of G tiles is one drain)
+            st = np.array([tile_stats(sv[64 * G * g: 64 * G * (g + 1)], res) for g in range(a.tiles // G)]).mean(axis=0)
+            print(f"{kind:10s} {G} tile(s) per drain: evaluated {st[1] / G:6.1f}, batches {st[2] / G:5.2f} per tile, lane util {st[1] / (64 * st[2]):4.2f}")
         n_res = sum(1 for s in sv if any(k == res for k, _, _ in s))
         print(f"{kind:10s} the pair survives the cull in {n_res / len(sv):.2f} of the states, violates in "
               f"{sum(1 for s in sv if any(k == res and hit for k, _, hit in s)) / len(sv):.3f}")
