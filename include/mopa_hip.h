@@ -581,6 +581,36 @@ int mopa_geom_manifolds_batch(int32_t device, int64_t M, const int32_t *types_de
 int mopa_geom_manifolds_host(int64_t M, const int32_t *types, const double *recs, const double *mesh_verts /*nullable*/, int32_t nvert,
                              double point_cutoff, int32_t max_points /*P*/, double *normal_dist, int32_t *npoint, double *points);
 
+/* Proximity report: HOW FAR from collision a state is and which pairs are nearest, inside a band the caller gives (DESIGN.md
+ * section 4, "Proximity report").  State i as in mopa_is_valid_batch.  Per non-ignored candidate pair p the band-limited distance
+ * d_p: the bits of the contact report for shapes in overlap; for disjoint shapes the separation distance where the pair function
+ * is one in closed form (plane-X, sphere-X, capsule-capsule, capsule-box, plane-mesh) and otherwise (box-box, cylinder pairs,
+ * convex-mesh) MuJoCo's margin rule: the portal refinement on the shapes inflated by band / 2 each, band taken off its depth --
+ * never more than 1e-6 above the true distance, below it by a shortfall that grows with band (measured per class in DESIGN.md).
+ * Pairs with d_p > band are out of band.  Outputs per state:
+ *   clearance[i]  min(band, min_p d_p): band when no pair is in band
+ *   count[i]      the number of pairs in band, even above max_pairs (K)
+ *   pair[i,:], dist[i,:]  the K nearest pairs (index into the pair list of the MopaSceneDesc) and their d_p, ascending by
+ *                 (d_p, p); unused slots hold pair = -1, dist = MOPA_FAR
+ * band must be finite and >= 0 and K >= 1 (MOPA_ERR_INVALID_ARG).  A glued scene and a scene created with pair_cull_radius (proven
+ * down to its contact_threshold only) return MOPA_ERR_UNSUPPORTED; per-wave distance arrays beyond LDS MOPA_ERR_LIMIT; N == 0 is a
+ * no-op.  One launch of its own (a wave per state, a broad phase widened by band), asynchronous on `stream`, deterministic: no
+ * atomics decide order or content.  The validity, contact and motion entry points are untouched by it. */
+int mopa_proximity_batch(MopaScene *scene, const double *q_active_dev /*[N,na]*/, const double *qpos_env_dev /*[E,nq]*/, int64_t N,
+                         int64_t samples_per_env, double band, int32_t max_pairs /*K*/, double *clearance_dev /*[N]*/,
+                         int32_t *count_dev /*[N]*/, int32_t *pair_dev /*[N,K]*/, double *dist_dev /*[N,K]*/, void *stream);
+/* the same for one state (host pointers, synchronous) */
+int mopa_proximity_state(MopaScene *scene, const double *qpos_host /*[nq]*/, double band, int32_t max_pairs /*K*/,
+                         double *clearance /*[1]*/, int32_t *count /*[1]*/, int32_t *pair /*[K]*/, double *dist /*[K]*/);
+/* Pair level: M posed pairs, one lane each; types / recs as mopa_geom_frames_batch takes them (either order: the value does not
+ * depend on it), out [M] = d if d <= band, else MOPA_FAR.  A mesh (type 7) reads the hull mesh_verts_dev [nvert,3] in the mesh
+ * frame (nullable with nvert = 0: mesh pairs then report MOPA_FAR). */
+int mopa_geom_sep_batch(int32_t device, int64_t M, const int32_t *types_dev, const double *recs_dev, const double *mesh_verts_dev /*nullable*/,
+                        int32_t nvert, double band, double *out_dev, void *stream);
+/* The host compile of the same functions -- the sequential form the kernels match bit for bit; no GPU, no HIP call. */
+int mopa_geom_sep_host(int64_t M, const int32_t *types, const double *recs, const double *mesh_verts /*nullable*/, int32_t nvert,
+                       double band, double *out);
+
 /* ======================================================================================================
  * (BASELINE configs 3-5) batched KINEMATIC env.step for the three Sawyer obstacle envs --
  * the "env-steps/sec" half of the metric.  Restates what the reference envs compute around the physics:

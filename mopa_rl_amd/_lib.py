@@ -34,6 +34,7 @@ EXPORTED_SYMBOLS = [
     "mopa_planner_status", "mopa_debug_fk", "mopa_debug_pair_dist", "mopa_contacts_batch", "mopa_contacts_state",
     "mopa_contact_frames_batch", "mopa_contact_frames_state", "mopa_geom_frames_batch", "mopa_geom_frames_host",
     "mopa_contact_manifolds_batch", "mopa_contact_manifolds_state", "mopa_geom_manifolds_batch", "mopa_geom_manifolds_host",
+    "mopa_proximity_batch", "mopa_proximity_state", "mopa_geom_sep_batch", "mopa_geom_sep_host",
     "mopa_motion_report_batch", "mopa_motion_report",
     "mopa_env_create", "mopa_env_destroy", "mopa_env_obs_dim", "mopa_env_action_dim", "mopa_env_step_batch", "mopa_env_exec_batch", "mopa_env_desired_batch",
     "mopa_env_attach_dynamics", "mopa_env_attach_contacts", "mopa_env_set_contact_stats", "mopa_rollout_stage", "mopa_rollout_pool_pick", "mopa_rollout_step_size", "mopa_reuse_batch", "mopa_replay_append", "mopa_replay_sample", "mopa_ct_desc_size", "mopa_env_contact_arena", "mopa_env_dyn_dofs", "mopa_env_dyn_qvel_width", "mopa_env_dyn_forward_batch", "mopa_env_dyn_substeps_batch", "mopa_env_step_dyn_batch",
@@ -251,6 +252,10 @@ def lib() -> C.CDLL:
     L.mopa_contact_manifolds_state.argtypes = [vp, _dp, C.c_double, C.c_double, C.c_int32, C.c_int32, _ip, _ip, _dp, _dp, _ip, _dp, _dp]
     L.mopa_geom_manifolds_batch.argtypes = [C.c_int32, C.c_int64, vp, vp, C.c_double, C.c_int32, vp, vp, vp, vp]
     L.mopa_geom_manifolds_host.argtypes = [C.c_int64, _ip, _dp, _dp, C.c_int32, C.c_double, C.c_int32, _dp, _ip, _dp]
+    L.mopa_proximity_batch.argtypes = [vp, vp, vp, C.c_int64, C.c_int64, C.c_double, C.c_int32, vp, vp, vp, vp, vp]
+    L.mopa_proximity_state.argtypes = [vp, _dp, C.c_double, C.c_int32, _dp, _ip, _ip, _dp]
+    L.mopa_geom_sep_batch.argtypes = [C.c_int32, C.c_int64, vp, vp, vp, C.c_int32, C.c_double, vp, vp]
+    L.mopa_geom_sep_host.argtypes = [C.c_int64, _ip, _dp, _dp, C.c_int32, C.c_double, _dp]
     L.mopa_motion_report_batch.argtypes = [vp, vp, vp, vp, C.c_int64, C.c_int64, vp, vp, vp, vp, vp, vp, C.c_int32, vp, vp, vp, vp]
     L.mopa_motion_report.argtypes = [vp, _dp, _dp, _ip, _ip, _ip, _dp, _dp, _dp, C.c_int32, _ip, _ip, _dp]
     L.mopa_env_create.argtypes = [C.POINTER(MopaEnvDesc), C.POINTER(vp)]
@@ -362,6 +367,19 @@ def geom_manifolds_host(types, recs, mesh_verts=None, point_cutoff: float = 0.0,
     check(lib().mopa_geom_manifolds_host(len(t), tp, rp, vp_, len(v), float(point_cutoff), P, nd.ctypes.data_as(_dp), npoint.ctypes.data_as(_ip),
                                          pts.ctypes.data_as(_dp)))
     return nd, npoint, pts
+
+
+def geom_sep_host(types, recs, band: float, mesh_verts=None) -> np.ndarray:
+    """mopa_geom_sep_host: M posed pairs as `geom_frames_host` takes them -> [M] band-limited signed distances by the host compile
+    of the kernels' geom_sep (no GPU): d where d <= band, MOPA_FAR otherwise ("Proximity report")."""
+    t, tp = _i(np.asarray(types).reshape(-1, 2))
+    r, rp = _d(np.asarray(recs, dtype=np.float64).reshape(-1, 30))
+    if len(t) != len(r):
+        raise MopaError(f"{len(t)} type pairs for {len(r)} record pairs")
+    out = np.zeros(len(t))
+    v, vp_ = _d(np.asarray(mesh_verts, dtype=np.float64).reshape(-1, 3)) if mesh_verts is not None else (np.zeros((0, 3)), None)
+    check(lib().mopa_geom_sep_host(len(t), tp, rp, vp_, len(v), float(band), out.ctypes.data_as(_dp)))
+    return out
 
 
 def model_struct(m, keep: list, pair_geom=None) -> MopaModel:
@@ -758,6 +776,33 @@ class Scene:
             return [(name(g[p, 0]), name(g[p, 1]), float(d), normal[k].copy(), pos[k].copy()) for k, (p, d) in enumerate(zip(pair[:n], dist[:n]))]
         n, pair, dist = self.contacts_state_raw(qpos, cutoff, K)
         return [(name(g[p, 0]), name(g[p, 1]), float(d)) for p, d in zip(pair[:n], dist[:n])]
+
+    def proximity_state_raw(self, qpos, band: float, max_pairs: int = 8):
+        """(clearance, count, pair [K] int32, dist [K]) of one state: the single-state form of `BatchPlanner.proximity`"""
+        if self.glue is not None:
+            raise NotImplementedError("the proximity report of a glued scene")
+        sc = self.contact_scene()
+        q, qp = _d(qpos)
+        if q.shape != (self.nq,):
+            raise MopaError(f"state has dimension {q.shape}, expected nq={self.nq}")
+        K = int(max_pairs)
+        cl, cnt = C.c_double(0.0), C.c_int32(0)
+        pair = np.full(max(K, 1), -1, dtype=np.int32)
+        dist = np.full(max(K, 1), MOPA_FAR)
+        check(lib().mopa_proximity_state(sc._h, qp, float(band), K, C.byref(cl), C.byref(cnt), pair.ctypes.data_as(_ip), dist.ctypes.data_as(_dp)))
+        return float(cl.value), int(cnt.value), pair, dist
+
+    def proximity_state(self, qpos, band: float, max_pairs: int = 8):
+        """How far from collision one state is, and which pairs are nearest: -> (clearance, [(geom1_name, geom2_name, dist), ...]),
+        clearance = min(band, the smallest pair distance), the list the at most max_pairs nearest non-ignored candidate pairs with
+        dist <= band, nearest first.  Distances of disjoint box-box, cylinder and mesh pairs are conservative -- never more than 1e-6
+        above the true distance, below it by a shortfall that grows with band ("Proximity report")."""
+        cl, n, pair, dist = self.proximity_state_raw(qpos, band, max_pairs)
+        m = self.model
+        g = np.asarray(m.pair_geom).reshape(-1, 2)
+        name = lambda k: m.all_geom_names[int(m.geom_mjid[int(k)])]
+        k = min(n, len(pair))
+        return cl, [(name(g[p, 0]), name(g[p, 1]), float(d)) for p, d in zip(pair[:k], dist[:k])]
 
     def motion_report_raw(self, qpos_a, qpos_b, max_contacts: int = 0):
         """(valid, n_states, first_bad, last_valid_t, last_valid_q [na], first_bad_q [na], blockers) of one segment: the

@@ -120,6 +120,22 @@ class ContactReport:
         return [(m.all_geom_names[int(a)], m.all_geom_names[int(b)], float(x)) for (a, b), x in zip(ids, d)]
 
 
+class ProximityReport:
+    """`BatchPlanner.proximity`: per state `clearance` [N] float64 (min(band, the smallest pair distance): band when no pair is in
+    band), `count` [N] int32 (the pairs with dist <= band, not capped) and the K nearest of them, ascending by (dist, pair index):
+    `pair` [N, K] int32 indices into `model.pair_geom` (-1 in unused slots), `dist` [N, K] float64 (MOPA_FAR in unused slots)."""
+
+    def __init__(self, clearance, count, pair, dist, model):
+        self.clearance, self.count, self.pair, self.dist, self.model = clearance, count, pair, dist, model
+
+    def __iter__(self):
+        return iter((self.clearance, self.count, self.pair, self.dist))
+
+    def geoms(self):
+        """[N, K, 2] int64 numpy array of MuJoCo geom ids (`ContactReport.geoms`), -1 in unused slots"""
+        return pair_geom_ids(self.model, self.pair.cpu().numpy())
+
+
 class MotionReport:
     """`BatchPlanner.motion_report`: per segment `valid` [N] uint8 (the byte `check_motion` writes), `n_states` [N] int32 (c =
     max(validSegmentCount, 1): the states s_1 .. s_c that were due, s_c = qb), `first_bad` [N] int32 (the smallest k with s_k
@@ -156,6 +172,27 @@ def geom_frames(types, recs, stream=None):
     out = torch.empty(M, 7, dtype=torch.float64, device=recs.device)
     dev = recs.device.index if recs.device.index is not None else torch.cuda.current_device()
     _lib.check(_lib.lib().mopa_geom_frames_batch(int(dev), M, _ptr(types), _ptr(recs), _ptr(out), _stream_handle(stream)))
+    return out
+
+
+def geom_sep(types, recs, band: float, mesh_verts=None, stream=None):
+    """mopa_geom_sep_batch: M posed pairs, one lane each, as `geom_frames` takes them -> [M] band-limited signed distances, the
+    bits of `_lib.geom_sep_host`; mesh_verts [n, 3] (float64, on the GPU): the hull of every geom of type 7"""
+    torch = _torch()
+    _check_f64(recs, "recs")
+    if types.dtype != torch.int32 or not types.is_cuda or not types.is_contiguous() or types.dim() != 2 or types.shape[1] != 2:
+        raise _lib.MopaError("types must be a contiguous int32 GPU tensor [M, 2]")
+    M = types.shape[0]
+    if recs.numel() != M * 30:
+        raise _lib.MopaError(f"recs must have shape [{M}, 2, 15], got {tuple(recs.shape)}")
+    nvert = 0
+    if mesh_verts is not None:
+        _check_f64(mesh_verts, "mesh_verts", 3)
+        nvert = mesh_verts.shape[0]
+    out = torch.empty(M, dtype=torch.float64, device=recs.device)
+    dev = recs.device.index if recs.device.index is not None else torch.cuda.current_device()
+    _lib.check(_lib.lib().mopa_geom_sep_batch(int(dev), M, _ptr(types), _ptr(recs), _ptr(mesh_verts) if nvert else None, nvert, float(band), _ptr(out),
+                                              _stream_handle(stream)))
     return out
 
 
@@ -307,6 +344,38 @@ class BatchPlanner:
                                                   float(self.scene.contact_threshold if cutoff is None else cutoff), K,
                                                   _ptr(count), _ptr(pair), _ptr(dist), _stream_handle(stream)))
         return ContactReport(count, pair, dist, self.scene.model)
+
+    def proximity(self, q_active, qpos_env, samples_per_env: Optional[int] = None, band: float = 0.05, max_pairs: int = 8,
+                  stream=None) -> ProximityReport:
+        """How far from collision every state of a batch is, and which pairs are nearest (states as in `is_valid`): the signed
+        distance of every non-ignored candidate pair at or below `band` (>= 0, metres); `clearance` saturates at band, `count`
+        is not capped by `max_pairs`, the nearest pairs are kept.  A pair in overlap carries the contact report's bits; disjoint
+        box-box, cylinder and mesh pairs get MuJoCo's margin rule, a conservative distance: never more than 1e-6 above the true
+        one, below it by a shortfall that grows with band ("Proximity report").  One launch of its own on the scene with the full pair list
+        (`Scene.contact_scene`); a glued scene raises."""
+        if self.scene.glue is not None:
+            raise NotImplementedError("the proximity report of a glued scene")
+        torch = _torch()
+        _check_f64(q_active, "q_active", self.na)
+        _check_f64(qpos_env, "qpos_env", self.nq)
+        N = q_active.shape[0]
+        K = int(max_pairs)
+        spe = int(samples_per_env) if samples_per_env is not None else max(1, N // max(1, qpos_env.shape[0]))
+        if N and (N + spe - 1) // spe > qpos_env.shape[0]:
+            raise _lib.MopaError("qpos_env has fewer rows than ceil(N / samples_per_env)")
+        sc = self.scene.contact_scene()
+        dev = q_active.device
+        clearance = torch.empty(N, dtype=torch.float64, device=dev)
+        count = torch.empty(N, dtype=torch.int32, device=dev)
+        pair = torch.empty(N, max(K, 1), dtype=torch.int32, device=dev)
+        dist = torch.empty(N, max(K, 1), dtype=torch.float64, device=dev)
+        _lib.check(_lib.lib().mopa_proximity_batch(sc.handle, _ptr(q_active), _ptr(qpos_env), N, spe, float(band), K, _ptr(clearance), _ptr(count),
+                                                   _ptr(pair), _ptr(dist), _stream_handle(stream)))
+        return ProximityReport(clearance, count, pair, dist, self.scene.model)
+
+    def clearance(self, q_active, qpos_env, samples_per_env: Optional[int] = None, band: float = 0.05, stream=None):
+        """`proximity(...).clearance` alone: [N] float64, min(band, the smallest pair distance) of every state"""
+        return self.proximity(q_active, qpos_env, samples_per_env, band=band, max_pairs=1, stream=stream).clearance
 
     def glue_attach(self, rows, stream=None):
         """glued scene (`Scene.glued`): rows [E, nq] -> their attached rows, copies whose free-joint slots of the carried body hold

@@ -650,12 +650,19 @@ MOPA_HD double origin_tri_dist2(V3 x0, V3 B, V3 C) {
     return dist;
 }
 // true + depth on intersection
-template <bool MESH = false, int G = 1>
-MOPA_HD bool mpr_penetration(const double *g1, int t1, const double *g2, int t2, double &depth, const double *aux = nullptr) {
+// INFL = true (the proximity report, mopa_sep.hpp): the same refinement on the Minkowski difference inflated by `infl`, support
+// support_md(dir) + infl * dir (dir is unit at every call); INFL = false compiles to the code it was before the parameter existed.
+template <bool MESH = false, int G = 1, bool INFL = false>
+MOPA_HD V3 mpr_support(const double *g1, int t1, const double *g2, int t2, V3 dir, const double *aux, double infl) {
+    const V3 s = support_md<MESH, G>(g1, t1, g2, t2, dir, aux);
+    return INFL ? addscl3(s, dir, infl) : s;
+}
+template <bool MESH = false, int G = 1, bool INFL = false>
+MOPA_HD bool mpr_penetration(const double *g1, int t1, const double *g2, int t2, double &depth, const double *aux = nullptr, double infl = 0.0) {
     V3 v0 = sub3(ld3(g1 + GO_POS), ld3(g2 + GO_POS));
     if (vec_eq0(v0)) v0.x += kCcdEps * 10.0;
     V3 dir = normalize3(neg3(v0));
-    V3 v1 = support_md<MESH, G>(g1, t1, g2, t2, dir, aux);
+    V3 v1 = mpr_support<MESH, G, INFL>(g1, t1, g2, t2, dir, aux, infl);
     double dot = dot3(v1, dir);
     if (is_zero(dot) || dot < 0.0) return false;
     dir = cross3(v0, v1);
@@ -665,7 +672,7 @@ MOPA_HD bool mpr_penetration(const double *g1, int t1, const double *g2, int t2,
         return true;
     }
     dir = normalize3(dir);
-    V3 v2 = support_md<MESH, G>(g1, t1, g2, t2, dir, aux);
+    V3 v2 = mpr_support<MESH, G, INFL>(g1, t1, g2, t2, dir, aux, infl);
     dot = dot3(v2, dir);
     if (is_zero(dot) || dot < 0.0) return false;
     dir = normalize3(cross3(sub3(v1, v0), sub3(v2, v0)));
@@ -678,7 +685,7 @@ MOPA_HD bool mpr_penetration(const double *g1, int t1, const double *g2, int t2,
     int it = 0;
     for (;;) {
         if (++it > kMprPortalMaxIt) return false;
-        v3 = support_md<MESH, G>(g1, t1, g2, t2, dir, aux);
+        v3 = mpr_support<MESH, G, INFL>(g1, t1, g2, t2, dir, aux, infl);
         dot = dot3(v3, dir);
         if (is_zero(dot) || dot < 0.0) return false;
         bool cont = false;
@@ -697,7 +704,7 @@ MOPA_HD bool mpr_penetration(const double *g1, int t1, const double *g2, int t2,
         dir = portal_dir(v1, v2, v3);
         dot = dot3(dir, v1);
         if (is_zero(dot) || dot > 0.0) break;
-        v4 = support_md<MESH, G>(g1, t1, g2, t2, dir, aux);
+        v4 = mpr_support<MESH, G, INFL>(g1, t1, g2, t2, dir, aux, infl);
         dot = dot3(v4, dir);
         if (!(is_zero(dot) || dot > 0.0) || portal_reach_tol(v1, v2, v3, v4, dir)) return false;
         expand_portal(v0, v1, v2, v3, v4);
@@ -705,7 +712,7 @@ MOPA_HD bool mpr_penetration(const double *g1, int t1, const double *g2, int t2,
     int iterations = 0;
     for (;;) {
         dir = portal_dir(v1, v2, v3);
-        v4 = support_md<MESH, G>(g1, t1, g2, t2, dir, aux);
+        v4 = mpr_support<MESH, G, INFL>(g1, t1, g2, t2, dir, aux, infl);
         if (portal_reach_tol(v1, v2, v3, v4, dir) || iterations > kMprMaxIt) {
             depth = sqrt(origin_tri_dist2(v1, v2, v3));
             return true;

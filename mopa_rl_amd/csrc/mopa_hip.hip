@@ -32,6 +32,7 @@
 #include "mopa_device.hpp"
 #include "mopa_frames.hpp"
 #include "mopa_manifold.hpp"
+#include "mopa_sep.hpp"
 #include "mopa_fk.hpp"
 #include "mopa_host.hpp"
 
@@ -51,6 +52,7 @@ static void contacts_register_lds();        // defined with the contact report (
 static void motion_report_register_lds();   // defined with the motion report (mopa_motion_report.inc)
 static void contact_frames_register_lds();  // defined with the contact frames (mopa_contact_frames.inc)
 static void contact_manifolds_register_lds();  // defined with the contact manifolds (mopa_contact_manifold.inc)
+static void proximity_register_lds();       // defined with the proximity report (mopa_proximity.inc)
 static void k9_register_lds();              // defined with K9 path simplification (mopa_k9.inc)
 static void star_register_lds();            // defined with K3b RRT* (mopa_rrtstar.inc)
 static void k1_register_lds();              // defined with the K1 kernel table (mopa_valid_launch.inc)
@@ -831,6 +833,7 @@ static int scene_create(const MopaSceneDesc *desc, int glue_a, int glue_b, MopaS
     motion_report_register_lds();
     contact_frames_register_lds();
     contact_manifolds_register_lds();
+    proximity_register_lds();
     k9_register_lds();
     star_register_lds();
     *out = S;
@@ -976,6 +979,8 @@ extern "C" const char *mopa_planner_status(const MopaScene *S) { return S ? S->s
 // contact frames behind it: mopa_contact_frames_batch / _state, pair level mopa_geom_frames_batch / _host
 #include "mopa_contact_frames.inc"
 #include "mopa_contact_manifold.inc"
+// proximity report: k_proximity_rows, mopa_proximity_batch / _state, pair level mopa_geom_sep_batch / _host
+#include "mopa_proximity.inc"
 // K2 motion report: k_motion_report / k_motion_report_reduce, mopa_motion_report_batch / mopa_motion_report
 #include "mopa_motion_report.inc"
 

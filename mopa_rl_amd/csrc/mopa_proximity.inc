@@ -1,0 +1,205 @@
+// mopa_proximity.inc -- batched proximity report: how far from collision a state is, and which pairs are nearest, inside a band.
+// What a user of a collision-checked planner asks besides the verdict; the reference's maximize_min_clearance objective reads it.
+//
+// One launch, modelled on k_contact_rows (DESIGN.md section 4, "Proximity report"): persistent waves pull states from a counter, one
+// state per pull, and EVERY state gets a wave -- there is no stage-1 gate, a separated state has a clearance too.  Per state: the
+// wave-per-state validity routine's wave_load_state / wave_fk, a MARGIN broad phase (pair_culled_band: every bound of pair_culled
+// widened by the band, so no pair at distance <= band is dropped), geom_sep (mopa_sep.hpp) for the survivors, then the selection.
+// Every distance lands in a per-wave LDS array indexed by the pair's position in the MopaSceneDesc pair list (kFar = out of band);
+// the count is a ballot over it, the K nearest come out of min(K, count) rounds of a wave-wide minimum over (distance, pair index)
+// -- ties to the lower index, no atomics, one writer per output word: two runs write the same bytes.
+
+// pair_culled with every bound widened by `band`
+MOPA_D bool pair_culled_band(const SceneHdr &h, const LdsView &v, int g1, int g2, const double *A, const double *B, double band) {
+    const int *I = v.ints;
+    const double *D = v.dbl;
+    const double rba = D[h.o_g_rbound + g1], rbb = D[h.o_g_rbound + g2];
+    const V3 diff = sub3(ld3(B + GO_POS), ld3(A + GO_POS));
+    if (I[h.o_g_type + g1] == G_PLANE) return dot3(diff, col3(A + GO_MAT, 2)) > rbb + band;
+    const double rs = rba + rbb + band;
+    if (dot3(diff, diff) > rs * rs) return true;
+    const bool s1 = I[h.o_g_slot + g1] < 0, s2 = I[h.o_g_slot + g2] < 0;
+    if (s1 == s2) return false;
+    return aabb_cull(ld3((s1 ? A : B) + GO_POS), D + h.o_g_aabb + 3 * (s1 ? g1 : g2), ld3((s1 ? B : A) + GO_POS), (s1 ? rbb : rba) + band);
+}
+
+template <bool MESH>
+__global__ __launch_bounds__(kBlock) void k_proximity_rows(SceneHdr h, const double *__restrict__ g_dbl, const int32_t *__restrict__ g_int,
+                                                           const int32_t *__restrict__ pair_model /*[h.npair] device pair -> index in the desc's pair list*/,
+                                                           int npair_model, const double *__restrict__ q_active, const double *__restrict__ qpos_env,
+                                                           long long N, long long samples_per_env, double band, int K,
+                                                           unsigned long long *__restrict__ ctr, double *__restrict__ clearance,
+                                                           int32_t *__restrict__ count, int32_t *__restrict__ pair, double *__restrict__ dist,
+                                                           int pd_off /*byte offset of the per-wave distance arrays in LDS*/) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    LdsView v = make_view(h, smem);
+    stage_scene(h, g_dbl, g_int, const_cast<double *>(v.dbl), const_cast<int *>(v.ints));
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    double *pd = reinterpret_cast<double *>(smem + pd_off) + wave * npair_model;   // [npair_model] distance by pair index, kFar = out of band
+    const int *I = v.ints;
+    const unsigned long long lt = (1ull << lane) - 1ull;
+    for (;;) {
+        unsigned long long t = 0ull;
+        if (lane == 0) t = atomicAdd(ctr, 1ull);
+        const unsigned t_lo = __builtin_amdgcn_readfirstlane((unsigned)t), t_hi = __builtin_amdgcn_readfirstlane((unsigned)(t >> 32));
+        const long long s = (long long)(((unsigned long long)t_hi << 32) | t_lo);
+        if (s >= N) break;
+        wave_load_state(h, v, lane, q_active + s * h.na, qpos_env + (s / samples_per_env) * h.nq);
+        wave_fk(h, v, lane);
+        for (int i = lane; i < npair_model; i += 64) pd[i] = kFar;
+        // margin broad phase + ballot compaction (order-preserving: the worklist stays sorted by narrow-phase class)
+        int wl_count = 0;
+        for (int base = 0; base < h.npair; base += 64) {
+            const int p = base + lane;
+            bool surv = false;
+            if (p < h.npair) {
+                const int pk = I[h.o_pairs + p];
+                const int g1 = pk & 0xff, g2 = (pk >> 8) & 0xff;
+                surv = !pair_culled_band(h, v, g1, g2, geom_rec(h, v, g1), geom_rec(h, v, g2), band);
+            }
+            const unsigned long long mask = __ballot(surv);
+            if (surv) v.wl[wl_count + __popcll(mask & lt)] = (unsigned short)p;
+            wl_count += __popcll(mask);
+        }
+        wave_sync();
+        for (int base = 0; base < wl_count; base += 64) {
+            const int i = base + lane;
+            if (i < wl_count) {
+                const int p = v.wl[i];
+                const int pk = I[h.o_pairs + p];
+                const int g1 = pk & 0xff, g2 = (pk >> 8) & 0xff, code = (pk >> 16) & 0xff;
+                pd[pair_model[p]] = geom_sep<MESH>(code, geom_rec(h, v, g1), I[h.o_g_type + g1], geom_rec(h, v, g2), I[h.o_g_type + g2], band, v.dbl);
+            }
+        }
+        wave_sync();
+        int cnt = 0;
+        for (int base = 0; base < npair_model; base += 64) {
+            const int p = base + lane;
+            const double d = (p < npair_model) ? pd[p] : kFar;
+            cnt += __popcll(__ballot(d <= band && d < kFar));
+        }
+        // the K nearest, ascending by (distance, pair index): one wave-wide minimum per record
+        const int nrec = cnt < K ? cnt : K;
+        for (int r = 0; r < nrec; r++) {
+            double bd = kFar;
+            int bi = 0x7fffffff;
+            for (int p = lane; p < npair_model; p += 64) {
+                const double d = pd[p];
+                if (d < bd) { bd = d; bi = p; }      // (ascending p within a lane: the first minimum is the lowest index)
+            }
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) {
+                const double od = __shfl_xor(bd, off, 64);
+                const int oi = __shfl_xor(bi, off, 64);
+                if (od < bd || (od == bd && oi < bi)) { bd = od; bi = oi; }
+            }
+            if (lane == 0) {
+                pair[s * K + r] = bi;
+                dist[s * K + r] = bd;
+                if (r == 0) clearance[s] = bd;
+            }
+            if (bi < npair_model && (bi & 63) == lane) pd[bi] = kFar;      // (cnt counted it: bi names an entry below kFar)
+            wave_sync();
+        }
+        for (int i = nrec + lane; i < K; i += 64) {
+            pair[s * K + i] = -1;
+            dist[s * K + i] = kFar;
+        }
+        if (lane == 0) {
+            count[s] = cnt;
+            if (cnt == 0) clearance[s] = band;
+        }
+        wave_sync();   // pd / worklist / geom slab are about to be reused
+    }
+    tile_ctr_release(ctr, lane);
+}
+
+// pair level: one lane per posed pair; a mesh (type 7) as the second geom reads the hull at mesh_verts
+__global__ __launch_bounds__(256) void k_geom_sep(long long M, const int32_t *__restrict__ types /*[M,2]*/, const double *__restrict__ recs /*[M,2,15]*/,
+                                                  const double *__restrict__ mesh_verts /*[nvert,3] or null*/, int nvert, double band,
+                                                  double *__restrict__ out /*[M]*/) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= M) return;
+    out[i] = geom_sep_rec(types[2 * i], recs + i * 30, types[2 * i + 1], recs + i * 30 + 15, mesh_verts, nvert, band);
+}
+
+static void proximity_register_lds() {
+    for (const void *k : {(const void *)k_proximity_rows<false>, (const void *)k_proximity_rows<true>})
+        (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLdsBytes);
+}
+
+extern "C" int mopa_proximity_batch(MopaScene *S, const double *q_active, const double *qpos_env, int64_t N, int64_t samples_per_env, double band,
+                                    int32_t K, double *clearance, int32_t *count, int32_t *pair, double *dist, void *stream) {
+    if (!S || !clearance || !count || !pair || !dist || (N > 0 && (!q_active || !qpos_env))) return fail(MOPA_ERR_INVALID_ARG, "null argument");
+    MOPA_REFUSE_GLUED(S, "the proximity report (mopa_proximity_batch)");
+    if (N < 0 || samples_per_env <= 0) return fail(MOPA_ERR_INVALID_ARG, "N < 0 or samples_per_env <= 0");
+    if (!std::isfinite(band) || !(band >= 0.0)) return fail(MOPA_ERR_INVALID_ARG, "band must be finite and >= 0");
+    if (K < 1) return fail(MOPA_ERR_INVALID_ARG, "max_pairs must be >= 1");
+    if (S->pruned)
+        return fail(MOPA_ERR_UNSUPPORTED, "a scene with pair_cull_radius is proven down to its contact_threshold only: the proximity report needs the full scene");
+    if (N == 0) return MOPA_OK;
+    ON_DEVICE(S->device);
+    hipStream_t st = (hipStream_t)stream;
+    const int pd_off = (S->lds_bytes + 15) & ~15;
+    const size_t lds = (size_t)pd_off + (size_t)kWavesPerBlock * S->npair_model * sizeof(double);
+    if (lds > (size_t)kMaxLdsBytes) return fail(MOPA_ERR_LIMIT, "proximity report: the per-wave distance arrays do not fit LDS");
+    StreamScratch &sc = scratch_for(S, st);
+    if (!sc.ct_ctr.p) {      // the contact report's counter: zeroed once, synchronously; the kernel puts it back to zero (tile_ctr_release)
+        HIP_TRY(grow(S, sc.ct_ctr, 64));
+        HIP_TRY(hipMemset(sc.ct_ctr.p, 0, 64));
+        HIP_TRY(hipStreamSynchronize(nullptr));
+    }
+    const int64_t blocks = std::max<int64_t>(1, std::min<int64_t>((N + kWavesPerBlock - 1) / kWavesPerBlock, (int64_t)S->n_cu * 2));
+    hipLaunchKernelGGL(S->hdr.has_mesh ? k_proximity_rows<true> : k_proximity_rows<false>, dim3((unsigned)blocks), dim3(kBlock), lds, st, S->hdr, S->d_dbl, S->d_int,
+                       (const int32_t *)S->d_pair_model, S->npair_model, q_active, qpos_env, (long long)N, (long long)samples_per_env, band, (int)K,
+                       sc.ct_ctr.as<unsigned long long>(), clearance, count, pair, dist, pd_off);
+    HIP_TRY(hipGetLastError());
+    return MOPA_OK;
+}
+
+extern "C" int mopa_proximity_state(MopaScene *S, const double *qpos_host, double band, int32_t K, double *clearance, int32_t *count, int32_t *pair,
+                                    double *dist) {
+    if (!S || !qpos_host || !clearance || !count || !pair || !dist) return fail(MOPA_ERR_INVALID_ARG, "null argument");
+    MOPA_REFUSE_GLUED(S, "the proximity report (mopa_proximity_state)");
+    if (K < 1) return fail(MOPA_ERR_INVALID_ARG, "max_pairs must be >= 1");
+    ON_DEVICE(S->device);
+    int rc = upload_state(S, qpos_host);
+    if (rc) return rc;
+    void *buf = nullptr;
+    const size_t off_dist = 0, off_clear = (size_t)K * sizeof(double), off_pair = off_clear + sizeof(double), off_count = off_pair + (size_t)K * sizeof(int32_t);
+    HIP_TRY(hipMalloc(&buf, off_count + sizeof(int32_t)));
+    unsigned char *b = static_cast<unsigned char *>(buf);
+    rc = mopa_proximity_batch(S, S->d_q + S->nq, S->d_q, 1, 1, band, K, reinterpret_cast<double *>(b + off_clear), reinterpret_cast<int32_t *>(b + off_count),
+                              reinterpret_cast<int32_t *>(b + off_pair), reinterpret_cast<double *>(b + off_dist), nullptr);
+    hipError_t e = hipSuccess;
+    if (rc == MOPA_OK) {
+        e = hipMemcpy(dist, b + off_dist, (size_t)K * sizeof(double), hipMemcpyDeviceToHost);
+        if (e == hipSuccess) e = hipMemcpy(clearance, b + off_clear, sizeof(double), hipMemcpyDeviceToHost);
+        if (e == hipSuccess) e = hipMemcpy(pair, b + off_pair, (size_t)K * sizeof(int32_t), hipMemcpyDeviceToHost);
+        if (e == hipSuccess) e = hipMemcpy(count, b + off_count, sizeof(int32_t), hipMemcpyDeviceToHost);
+    }
+    (void)hipFree(buf);
+    if (rc != MOPA_OK) return rc;
+    HIP_TRY(e);
+    return MOPA_OK;
+}
+
+extern "C" int mopa_geom_sep_batch(int32_t device, int64_t M, const int32_t *types, const double *recs, const double *mesh_verts, int32_t nvert, double band,
+                                   double *out, void *stream) {
+    if (M < 0 || (M > 0 && (!types || !recs || !out)) || nvert < 0 || (nvert > 0 && !mesh_verts)) return fail(MOPA_ERR_INVALID_ARG, "null argument / negative count");
+    if (!std::isfinite(band) || !(band >= 0.0)) return fail(MOPA_ERR_INVALID_ARG, "band must be finite and >= 0");
+    if (device < 0 || device >= mopa_device_count()) return fail(MOPA_ERR_INVALID_ARG, "device ordinal out of range");
+    if (M == 0) return MOPA_OK;
+    ON_DEVICE(device);
+    hipLaunchKernelGGL(k_geom_sep, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (long long)M, types, recs, mesh_verts, (int)nvert, band, out);
+    HIP_TRY(hipGetLastError());
+    return MOPA_OK;
+}
+
+// The host compile of the same functions: the sequential form the kernels must match bit for bit.  No GPU, no HIP call.
+extern "C" int mopa_geom_sep_host(int64_t M, const int32_t *types, const double *recs, const double *mesh_verts, int32_t nvert, double band, double *out) {
+    if (M < 0 || (M > 0 && (!types || !recs || !out)) || nvert < 0 || (nvert > 0 && !mesh_verts)) return fail(MOPA_ERR_INVALID_ARG, "null argument / negative count");
+    if (!std::isfinite(band) || !(band >= 0.0)) return fail(MOPA_ERR_INVALID_ARG, "band must be finite and >= 0");
+    for (int64_t i = 0; i < M; i++) out[i] = geom_sep_rec(types[2 * i], recs + i * 30, types[2 * i + 1], recs + i * 30 + 15, mesh_verts, nvert, band);
+    return MOPA_OK;
+}

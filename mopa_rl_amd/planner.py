@@ -209,6 +209,14 @@ class PyKinematicPlanner:
             return self._scene.contacts_state(np.asarray(state_vec, dtype=np.float64), manifold=True, max_points=max_points, point_cutoff=point_cutoff)
         return self._scene.contacts_state(np.asarray(state_vec, dtype=np.float64), frames=frames)
 
+    def proximity(self, state_vec, band: float, max_pairs: int = 8):
+        """how far from collision `state_vec` is and which pairs are nearest: (clearance, [(geom1_name, geom2_name, dist), ...]),
+        clearance saturating at `band`, the pairs with dist <= band nearest first (`Scene.proximity_state`).  With glue_bodies it
+        raises: the proximity report is not built for a glued scene"""
+        if self.glue_bodies:
+            raise NotImplementedError("proximity() with glue_bodies: the proximity report is not built for a glued scene")
+        return self._scene.proximity_state(np.asarray(state_vec, dtype=np.float64), band, max_pairs)
+
     def motion_report(self, start_vec, goal_vec, max_contacts: int = 0) -> dict:
         """where the straight line from `start_vec` to `goal_vec` (full qpos vectors; the passive entries are start_vec's) is
         blocked -- OMPL's checkMotion(s1, s2, lastValid): `valid`, `n_states`, `first_bad`, `last_valid_t`, `last_valid_q`,
