@@ -611,6 +611,39 @@ int mopa_geom_sep_batch(int32_t device, int64_t M, const int32_t *types_dev, con
 int mopa_geom_sep_host(int64_t M, const int32_t *types, const double *recs, const double *mesh_verts /*nullable*/, int32_t nvert,
                        double band, double *out);
 
+/* Clearance report: HOW NEAR a motion comes to collision, where along it and to which pair -- OMPL's
+ * MinimaxObjective::motionCost(s1, s2) under the maximize_min_clearance state cost ("Clearance report").
+ * Segments and env rows as in mopa_check_motion_batch; segment i has c = max(validSegmentCount, 1) states s_k, k = 1 .. c, s_c = qb
+ * (its bits), the states mopa_motion_report_batch walks; qa is not evaluated.  Per state d_k, p_k = what mopa_proximity_batch
+ * writes to clearance and pair[.,0] for s_k at this band (d_k saturates at band; p_k = -1 when no pair is in band).  Per segment:
+ *   clearance[i]      min_k d_k
+ *   n_states[i]       c
+ *   n_near[i]         the number of k with a pair in band
+ *   k_min[i]          the smallest k with d_k == clearance and a pair in band; 0 when n_near == 0
+ *   t_min[i]          (double)k_min / (double)c; 0.0 when k_min == 0, 1.0 when k_min == c
+ *   pair_min[i]       p_{k_min} (index into the pair list of the MopaSceneDesc); -1 when k_min == 0
+ *   end_clearance[i]  d_c
+ *   q_min[i,:]        s_{k_min}; qb's bits when k_min == 0 (NULL: not written)
+ * One form at every batch size: the segments are expanded into their states (mopa_check_motion_batch's large-batch pipeline), a
+ * wave per state takes the minimum, a lane per segment reduces in order.  It reads the state count back once per chunk: `stream` is
+ * synchronised in the MIDDLE of the call, behind the count and the scan, to size the launches that follow.  The per-state kernel, the
+ * reduction and the row copy are still in flight when the call returns: the outputs are complete once `stream` has run them, as
+ * with every other asynchronous entry point.  Deterministic: every output word has one writer.
+ * Argument rules of mopa_proximity_batch: band finite and >= 0, N >= 0, samples_per_env > 0, no NULL among the required buffers
+ * (MOPA_ERR_INVALID_ARG); a glued scene and a scene created with pair_cull_radius return MOPA_ERR_UNSUPPORTED; all of them before
+ * any launch; N == 0 returns MOPA_OK.  It needs the scene's own LDS only: a scene whose per-wave distance arrays
+ * mopa_proximity_batch refuses with MOPA_ERR_LIMIT is served here. */
+int mopa_motion_clearance_batch(MopaScene *scene, const double *qa_dev /*[N,na]*/, const double *qb_dev /*[N,na]*/,
+                                const double *qpos_env_dev /*[E,nq]*/, int64_t N, int64_t samples_per_env, double band,
+                                double *clearance_dev /*[N]*/, int32_t *n_states_dev /*[N]*/, int32_t *n_near_dev /*[N]*/,
+                                int32_t *k_min_dev /*[N]*/, double *t_min_dev /*[N]*/, int32_t *pair_min_dev /*[N]*/,
+                                double *end_clearance_dev /*[N]*/, double *q_min_dev /*[N,na] or NULL*/, void *stream);
+/* the same for one segment (host pointers, synchronous): from the active entries of qpos_a to those of qpos_b; the passive
+ * entries come from qpos_a.  q_min holds active coordinates. */
+int mopa_motion_clearance(MopaScene *scene, const double *qpos_a_host /*[nq]*/, const double *qpos_b_host /*[nq]*/, double band,
+                          double *clearance_out, int32_t *n_states_out, int32_t *n_near_out, int32_t *k_min_out, double *t_min_out,
+                          int32_t *pair_min_out, double *end_clearance_out, double *q_min_out /*[na] or NULL*/);
+
 /* ======================================================================================================
  * (BASELINE configs 3-5) batched KINEMATIC env.step for the three Sawyer obstacle envs --
  * the "env-steps/sec" half of the metric.  Restates what the reference envs compute around the physics:

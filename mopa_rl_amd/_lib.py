@@ -35,7 +35,7 @@ EXPORTED_SYMBOLS = [
     "mopa_contact_frames_batch", "mopa_contact_frames_state", "mopa_geom_frames_batch", "mopa_geom_frames_host",
     "mopa_contact_manifolds_batch", "mopa_contact_manifolds_state", "mopa_geom_manifolds_batch", "mopa_geom_manifolds_host",
     "mopa_proximity_batch", "mopa_proximity_state", "mopa_geom_sep_batch", "mopa_geom_sep_host",
-    "mopa_motion_report_batch", "mopa_motion_report",
+    "mopa_motion_report_batch", "mopa_motion_report", "mopa_motion_clearance_batch", "mopa_motion_clearance",
     "mopa_env_create", "mopa_env_destroy", "mopa_env_obs_dim", "mopa_env_action_dim", "mopa_env_step_batch", "mopa_env_exec_batch", "mopa_env_desired_batch",
     "mopa_env_attach_dynamics", "mopa_env_attach_contacts", "mopa_env_set_contact_stats", "mopa_rollout_stage", "mopa_rollout_pool_pick", "mopa_rollout_step_size", "mopa_reuse_batch", "mopa_replay_append", "mopa_replay_sample", "mopa_ct_desc_size", "mopa_env_contact_arena", "mopa_env_dyn_dofs", "mopa_env_dyn_qvel_width", "mopa_env_dyn_forward_batch", "mopa_env_dyn_substeps_batch", "mopa_env_step_dyn_batch",
     "mopa_pusher_dyn_desc_size", "mopa_env_attach_pusher_dynamics", "mopa_env_set_pusher_stats", "mopa_env_pusher_substeps_batch",
@@ -258,6 +258,8 @@ def lib() -> C.CDLL:
     L.mopa_geom_sep_host.argtypes = [C.c_int64, _ip, _dp, _dp, C.c_int32, C.c_double, _dp]
     L.mopa_motion_report_batch.argtypes = [vp, vp, vp, vp, C.c_int64, C.c_int64, vp, vp, vp, vp, vp, vp, C.c_int32, vp, vp, vp, vp]
     L.mopa_motion_report.argtypes = [vp, _dp, _dp, _ip, _ip, _ip, _dp, _dp, _dp, C.c_int32, _ip, _ip, _dp]
+    L.mopa_motion_clearance_batch.argtypes = [vp, vp, vp, vp, C.c_int64, C.c_int64, C.c_double, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.mopa_motion_clearance.argtypes = [vp, _dp, _dp, C.c_double, _dp, _ip, _ip, _ip, _dp, _ip, _dp, _dp]
     L.mopa_env_create.argtypes = [C.POINTER(MopaEnvDesc), C.POINTER(vp)]
     L.mopa_env_destroy.argtypes = [vp]
     L.mopa_env_destroy.restype = None
@@ -597,6 +599,11 @@ class Scene:
             self._glued[key] = Scene(mdl, pas, ign, thr, range_=rng, resolution=res, seed=seed, device=dev, prune_pairs=self._prune_pairs, glue=key)
         return self._glued[key]
 
+    @property
+    def device_ordinal(self) -> int:
+        """the device ordinal this scene was created with; -1: the device that was current at creation"""
+        return self._ctor[7]
+
     def full(self) -> "Scene":
         """the sibling scene with the FULL candidate-pair list (created on first use): where states outside the pruning proof's
         box -- a joint beyond its range + guard band -- are evaluated"""
@@ -854,6 +861,39 @@ class Scene:
             out["blockers"] = [(name(g[p, 0]), name(g[p, 1]), float(d)) for p, d in zip(pair[:k], dist[:k])]
             out["n_blockers"] = cnt
         return out
+
+    def motion_clearance_raw(self, qpos_a, qpos_b, band: float):
+        """(clearance, n_states, n_near, k_min, t_min, pair_min, end_clearance, q_min [na]) of one segment: the single-segment
+        form of `BatchPlanner.motion_clearance` (mopa_motion_clearance) from the active entries of qpos_a to those of qpos_b, the
+        passive entries taken from qpos_a; pair_min is an index into `model.pair_geom` (-1: nothing within the band)"""
+        if self.glue is not None:
+            raise NotImplementedError("the clearance report of a glued scene")
+        sc = self.contact_scene()
+        a, ap = _d(qpos_a)
+        b, bp = _d(qpos_b)
+        if a.shape != (self.nq,) or b.shape != (self.nq,):
+            raise MopaError(f"states have dimensions {a.shape} / {b.shape}, expected nq={self.nq}")
+        cl, t, ec = C.c_double(0.0), C.c_double(0.0), C.c_double(0.0)
+        n, near, k, pair = C.c_int32(0), C.c_int32(0), C.c_int32(0), C.c_int32(-1)
+        q_min = np.zeros(self.na)
+        check(lib().mopa_motion_clearance(sc._h, ap, bp, float(band), C.byref(cl), C.byref(n), C.byref(near), C.byref(k), C.byref(t), C.byref(pair),
+                                          C.byref(ec), q_min.ctypes.data_as(_dp)))
+        return float(cl.value), int(n.value), int(near.value), int(k.value), float(t.value), int(pair.value), float(ec.value), q_min
+
+    def motion_clearance_state(self, qpos_a, qpos_b, band: float):
+        """How near the straight line from qpos_a to qpos_b comes to collision, where, and to which pair: OMPL's
+        MinimaxObjective::motionCost under the clearance state cost, over the states s_k, k = 1 .. n_states, `motion_report_state`
+        walks (qpos_a is not evaluated).  -> dict: `clearance` (the smallest state clearance, saturating at band), `n_states`,
+        `n_near` (states with a pair within the band), `k_min` (the first state that attains the clearance, 0: nothing within the
+        band), `t_min` (k_min / n_states), `pair` ((geom1_name, geom2_name) of the nearest pair there, None when k_min == 0),
+        `pair_min` (its index into `model.pair_geom`, -1), `end_clearance` (that of qpos_b) and `q_min` (active coordinates [na] of
+        s_k_min; qpos_b's when k_min == 0).  DESIGN.md section 4, "Clearance report"."""
+        cl, n, near, k, t, pair, ec, q_min = self.motion_clearance_raw(qpos_a, qpos_b, band)
+        m = self.model
+        g = np.asarray(m.pair_geom).reshape(-1, 2)
+        name = lambda j: m.all_geom_names[int(m.geom_mjid[int(j)])]
+        return {"clearance": cl, "n_states": n, "n_near": near, "k_min": k, "t_min": t, "pair_min": pair,
+                "pair": (name(g[pair, 0]), name(g[pair, 1])) if pair >= 0 else None, "end_clearance": ec, "q_min": q_min}
 
     def debug_pair_dist(self, qpos):
         q, qp = _d(qpos)

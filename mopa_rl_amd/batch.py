@@ -5,7 +5,9 @@ pointers to libmopa_hip.so through the C ABI (include/mopa_hip.h).
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
+import math
 import os
 
 import numpy as np
@@ -147,6 +149,41 @@ class MotionReport:
     def __init__(self, valid, n_states, first_bad, last_valid_t, last_valid_q=None, first_bad_q=None, blockers=None):
         self.valid, self.n_states, self.first_bad, self.last_valid_t = valid, n_states, first_bad, last_valid_t
         self.last_valid_q, self.first_bad_q, self.blockers = last_valid_q, first_bad_q, blockers
+
+
+class MotionClearance:
+    """`BatchPlanner.motion_clearance`: per segment, over the states s_1 .. s_c `MotionReport` walks (s_c = qb; qa is not
+    evaluated), `clearance` [N] float64 (the smallest state clearance, each saturating at band), `n_states` [N] int32 (c),
+    `n_near` [N] int32 (states with a pair within the band), `k_min` [N] int32 (the smallest k whose state attains the clearance
+    with a pair in band; 0: nothing within the band), `t_min` [N] float64 (k_min / c), `pair_min` [N] int32 (the nearest pair of
+    s_k_min, index into `model.pair_geom`; -1 when k_min == 0), `end_clearance` [N] float64 (that of qb) and with states=True
+    `q_min` [N, na] float64 (s_k_min; qb's bits when k_min == 0), None otherwise.  As `PathClearance.segments` it also carries
+    `path_index` / `seg_index` [N] int64: segment i is seg_index[i] -> seg_index[i] + 1 of path path_index[i]."""
+
+    def __init__(self, clearance, n_states, n_near, k_min, t_min, pair_min, end_clearance, q_min, model, path_index=None, seg_index=None):
+        self.clearance, self.n_states, self.n_near, self.k_min, self.t_min = clearance, n_states, n_near, k_min, t_min
+        self.pair_min, self.end_clearance, self.q_min, self.model = pair_min, end_clearance, q_min, model
+        self.path_index, self.seg_index = path_index, seg_index
+
+    def geoms(self):
+        """[N, 2] int64 numpy array of MuJoCo geom ids of `pair_min` (`ContactReport.geoms`), -1 where nothing is within the band"""
+        return pair_geom_ids(self.model, self.pair_min.cpu().numpy())
+
+
+class PathClearance:
+    """`BatchPlanner.path_clearance`: per path `clearance` [E] float64 (min of vertex 0's state clearance and the segments'
+    clearances; NaN for an unsolved query, path_len == 0), `seg_min` [E] int32 (the first segment that attains it; -1 when vertex
+    0 does, which includes "nothing within the band"), `k_min` / `pair_min` [E] int32 (that segment's; 0 and vertex 0's pair when
+    seg_min == -1), `mean_vertex_clearance` [E] float64 (the mean of the band-saturated clearances of the path's vertices, OMPL's
+    PathGeometric::clearance(); NaN when path_len == 0) and `segments`, the `MotionClearance` of all segments of all paths."""
+
+    def __init__(self, clearance, seg_min, k_min, pair_min, mean_vertex_clearance, segments):
+        self.clearance, self.seg_min, self.k_min, self.pair_min = clearance, seg_min, k_min, pair_min
+        self.mean_vertex_clearance, self.segments = mean_vertex_clearance, segments
+
+    def geoms(self):
+        """[E, 2] int64 numpy array of MuJoCo geom ids of `pair_min`, -1 where there is none"""
+        return pair_geom_ids(self.segments.model, self.pair_min.cpu().numpy())
 
 
 def pair_geom_ids(model, pair) -> np.ndarray:
@@ -459,6 +496,113 @@ class BatchPlanner:
                                                       _ptr(count), _ptr(pair), _ptr(dist), sh))
         blockers = ContactReport(count, pair, dist, self.scene.model) if K else None
         return MotionReport(valid, n_states, first_bad, t, lvq, fbq if states else None, blockers)
+
+    def motion_clearance(self, qa, qb, qpos_env, samples_per_env: Optional[int] = None, band: float = 0.05, states: bool = False,
+                         stream=None) -> MotionClearance:
+        """How near every segment qa[i] -> qb[i] comes to collision, where along it and to which pair (mopa_motion_clearance_batch;
+        segments and env rows as in `check_motion`): OMPL's MinimaxObjective::motionCost under the clearance state cost, over the
+        states `motion_report` walks, each state's clearance and nearest pair being the bits of `proximity(..., max_pairs=1)` --
+        see `MotionClearance`.  states=True adds the [N, na] rows q_min.  Runs on the scene with the full pair list
+        (`Scene.contact_scene`) and synchronises the stream once in the middle of the call (the state count is read back), as the
+        large-batch `check_motion` does -- the last kernels are still in flight when it returns; N == 0 gives an empty report
+        without a call; a glued scene raises."""
+        if self.scene.glue is not None:
+            raise NotImplementedError("the clearance report of a glued scene")
+        torch = _torch()
+        _check_f64(qa, "qa", self.na)
+        _check_f64(qb, "qb", self.na)
+        _check_f64(qpos_env, "qpos_env", self.nq)
+        N = qa.shape[0]
+        if qb.shape[0] != N:
+            raise _lib.MopaError("qa and qb must hold the same number of segments")
+        spe = int(samples_per_env) if samples_per_env is not None else max(1, N // max(1, qpos_env.shape[0]))
+        if N and (spe <= 0 or (N + spe - 1) // spe > qpos_env.shape[0]):
+            raise _lib.MopaError("qpos_env has fewer rows than ceil(N / samples_per_env)")
+        if not (math.isfinite(float(band)) and float(band) >= 0.0):
+            raise _lib.MopaError("band must be finite and >= 0")
+        sc = self.scene.contact_scene()
+        dev = qa.device
+        f64 = lambda *shape: torch.empty(*shape, dtype=torch.float64, device=dev)
+        i32 = lambda: torch.empty(N, dtype=torch.int32, device=dev)
+        clearance, t_min, end_clearance = f64(N), f64(N), f64(N)
+        n_states, n_near, k_min, pair_min = i32(), i32(), i32(), i32()
+        q_min = f64(N, self.na) if states else None
+        if N == 0:      # (empty tensors have no address to pass: an empty report, no call)
+            return MotionClearance(clearance, n_states, n_near, k_min, t_min, pair_min, end_clearance, q_min, self.scene.model)
+        _lib.check(_lib.lib().mopa_motion_clearance_batch(sc.handle, _ptr(qa), _ptr(qb), _ptr(qpos_env), N, spe, float(band), _ptr(clearance),
+                                                          _ptr(n_states), _ptr(n_near), _ptr(k_min), _ptr(t_min), _ptr(pair_min), _ptr(end_clearance),
+                                                          _ptr(q_min) if states else None, _stream_handle(stream)))
+        return MotionClearance(clearance, n_states, n_near, k_min, t_min, pair_min, end_clearance, q_min, self.scene.model)
+
+    def path_clearance(self, path, path_len, band: float = 0.05, stream=None) -> PathClearance:
+        """The clearance of E planner paths (path [E, max_path, nq], path_len [E] int32, as `plan` returns them): the path cost of
+        the minimax clearance objective with vertex 0 counted, where along the path it is attained and to which pair, and the mean
+        clearance of the vertices -- see `PathClearance` and DESIGN.md section 4, "Clearance report".  The env row of a path is its
+        row 0; the rows of an unsolved query (path_len == 0) are not read.  Torch plumbing around `motion_clearance` (all segments
+        of all paths in one call) and `proximity` (the vertices 0 of the solved queries); the reductions are deterministic.
+        Cost besides the pipeline's own read-back: `path_len` is copied to the host once (E int32, one more synchronisation of the
+        stream) to lay out the segment list, and the mean is summed left to right by one small launch per column up to the
+        longest path."""
+        if self.scene.glue is not None:
+            raise NotImplementedError("the clearance report of a glued scene")
+        torch = _torch()
+        if path.dtype != torch.float64 or not path.is_cuda or not path.is_contiguous() or path.dim() != 3 or path.shape[2] != self.nq:
+            raise _lib.MopaError("path must be a contiguous float64 GPU tensor [E, max_path, nq]")
+        if path_len.dtype != torch.int32 or not path_len.is_cuda or not path_len.is_contiguous() or path_len.shape != (path.shape[0],):
+            raise _lib.MopaError("path_len must be a contiguous int32 GPU tensor [E]")
+        E, P = path.shape[0], path.shape[1]
+        if P < 1:
+            raise _lib.MopaError("path must hold at least one row per query")
+        dev = path.device
+        ctx = torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext()
+        with ctx:
+            hl = path_len.cpu().numpy().astype(np.int64)                   # the read-back
+            if ((hl < 0) | (hl > P)).any():
+                raise _lib.MopaError("path_len must lie in 0 .. max_path")
+            nseg = np.maximum(hl - 1, 0)
+            start = np.cumsum(nseg) - nseg
+            to_dev = lambda a: torch.as_tensor(a, dtype=torch.long, device=dev)
+            pe = to_dev(np.repeat(np.arange(E), nseg))                     # (path, j) of every segment, path by path, j ascending
+            pj = to_dev(np.arange(int(nseg.sum())) - np.repeat(start, nseg))
+            solved = to_dev(np.nonzero(hl >= 1)[0])
+            act = to_dev(np.asarray(self.scene.active_idx))
+            L = path_len.long()
+            jj = torch.arange(P - 1, device=dev)
+            pa = path[:, :, act]                                           # [E, P, na]
+            seg = self.motion_clearance(pa[pe, pj].contiguous(), pa[pe, pj + 1].contiguous(), path[pe, 0].contiguous(), samples_per_env=1,
+                                        band=band, stream=stream)
+            seg.path_index, seg.seg_index = pe, pj
+            v0 = torch.full((E,), float("nan"), dtype=torch.float64, device=dev)
+            p0 = torch.full((E,), -1, dtype=torch.int32, device=dev)
+            if len(solved):
+                v = self.proximity(pa[solved, 0].contiguous(), path[solved, 0].contiguous(), samples_per_env=1, band=band, max_pairs=1, stream=stream)
+                v0[solved], p0[solved] = v.clearance, v.pair[:, 0]
+            segc = torch.full((E, P - 1), float("inf"), dtype=torch.float64, device=dev)
+            segk = torch.zeros(E, P - 1, dtype=torch.int32, device=dev)
+            segp = torch.full((E, P - 1), -1, dtype=torch.int32, device=dev)
+            ende = torch.zeros(E, P - 1, dtype=torch.float64, device=dev)
+            segc[pe, pj], segk[pe, pj], segp[pe, pj], ende[pe, pj] = seg.clearance, seg.k_min, seg.pair_min, seg.end_clearance
+            clearance = torch.cat([v0[:, None], segc], dim=1).min(dim=1).values
+            # the first segment that attains the minimum (not torch.min's index, whose tie rule is not specified)
+            first = torch.where(segc == clearance[:, None], jj[None, :], P).min(dim=1).values if P > 1 else torch.full((E,), P, device=dev)
+            at_v0 = (v0 == clearance) | (first >= P)
+            seg_min = torch.where(at_v0, -1, first)
+            g = seg_min.clamp(min=0)[:, None]
+            zero = torch.zeros(E, dtype=torch.int32, device=dev)
+            k_min = torch.where(at_v0, zero, segk.gather(1, g)[:, 0] if P > 1 else zero)
+            pair_min = torch.where(at_v0, p0, segp.gather(1, g)[:, 0] if P > 1 else p0)
+            acc = v0.clone()                                               # left to right: v_0, then the end state of segment 0, 1, ...
+            for j in range(int(nseg.max()) if E else 0):                   # (the longest path's segments)
+                acc = torch.where(L - 1 > j, acc + ende[:, j], acc)
+            mean = acc / L.double()
+            none = L <= 0                                                  # an unsolved query: NaN, -1, 0, -1, NaN
+            nan = torch.full((E,), float("nan"), dtype=torch.float64, device=dev)
+            clearance = torch.where(none, nan, clearance)
+            mean = torch.where(none, nan, mean)
+            seg_min = torch.where(none, -1, seg_min).int()
+            k_min = torch.where(none, zero, k_min)
+            pair_min = torch.where(none, torch.full_like(p0, -1), pair_min)
+        return PathClearance(clearance, seg_min, k_min, pair_min, mean, seg)
 
     def plan(self, start, goal, max_iters: int = 2000, max_nodes: int = 1024, max_path: int = 256, seed: int = 0,
              env_id_base: int = 0, stream=None, env_ids=None, seeds=None, max_workgroups: int = 0, exclusive: bool = False,

@@ -9,6 +9,7 @@
 //        routine the planner kernels call.  Scene constants (~10 KB) are staged once per workgroup in LDS.
 //   K2 k_check_motion  one wave per segment (OMPL DiscreteMotionValidator semantics)
 //      k_motion_report (mopa_motion_report.inc) the same walk in ascending order: where a segment is blocked, and by which pairs
+//      k_clearance_states (mopa_motion_clearance.inc) one wave per expanded state: how near a segment comes, where, and to which pair
 //   K3 k_rrt_connect   (mopa_planner.inc) one wave per env
 //   K4 k_env_step      (mopa_env.inc) one lane per env, kinematic env.step
 //   FP64 VALU bound, no MFMA (there is no dense contraction on this path).
@@ -53,6 +54,7 @@ static void motion_report_register_lds();   // defined with the motion report (m
 static void contact_frames_register_lds();  // defined with the contact frames (mopa_contact_frames.inc)
 static void contact_manifolds_register_lds();  // defined with the contact manifolds (mopa_contact_manifold.inc)
 static void proximity_register_lds();       // defined with the proximity report (mopa_proximity.inc)
+static void motion_clearance_register_lds();   // defined with the clearance report (mopa_motion_clearance.inc)
 static void k9_register_lds();              // defined with K9 path simplification (mopa_k9.inc)
 static void star_register_lds();            // defined with K3b RRT* (mopa_rrtstar.inc)
 static void k1_register_lds();              // defined with the K1 kernel table (mopa_valid_launch.inc)
@@ -115,6 +117,7 @@ struct StreamScratch {
     size_t slab_waves = 0, slab_tiles = 0;   // what `slab` is sized for: waves, and slab regions per wave (tiles per drain)
     DevBuf mv_cnt, mv_off, mv_env, mv_q, mv_valid, mv_scan;   // expanded motion validation (mopa_motion.inc)
     DevBuf mr_fbq;                                            // motion report: first_bad_q when the caller keeps no rows but asks for blockers
+    DevBuf mc_d, mc_p;                                        // clearance report (mopa_motion_clearance.inc): per expanded state its clearance and nearest pair
     DevBuf plan_q, plan_p, plan_ctr;                          // planner: both trees of every env, env counter (mopa_planner.inc)
     DevBuf race_rec, race_word;                               // K3 race (mopa_race.inc): the members' records, one race word per query
     DevBuf ip_walk;                                           // straight-line pre-check: walk states + verdicts (mopa_paths.inc)
@@ -834,6 +837,7 @@ static int scene_create(const MopaSceneDesc *desc, int glue_a, int glue_b, MopaS
     contact_frames_register_lds();
     contact_manifolds_register_lds();
     proximity_register_lds();
+    motion_clearance_register_lds();
     k9_register_lds();
     star_register_lds();
     *out = S;
@@ -853,7 +857,7 @@ extern "C" void mopa_scene_destroy(MopaScene *S) {
         if (q) (void)hipFree(q);
     for (auto &kv : S->scratch) {
         StreamScratch &sc = kv.second;
-        for (DevBuf *b : {&sc.slab, &sc.mpr, &sc.cen, &sc.mesh_list, &sc.mesh_rows, &sc.mv_cnt, &sc.mv_off, &sc.mv_env, &sc.mv_q, &sc.mv_valid, &sc.mv_scan, &sc.mr_fbq, &sc.plan_q,
+        for (DevBuf *b : {&sc.slab, &sc.mpr, &sc.cen, &sc.mesh_list, &sc.mesh_rows, &sc.mv_cnt, &sc.mv_off, &sc.mv_env, &sc.mv_q, &sc.mv_valid, &sc.mv_scan, &sc.mr_fbq, &sc.mc_d, &sc.mc_p, &sc.plan_q,
                           &sc.plan_p, &sc.plan_ctr, &sc.pb_small, &sc.pb_rows, &sc.pb_act, &sc.ip_walk, &sc.ct_valid, &sc.ct_md, &sc.ct_ctr, &sc.star_tree, &sc.star_k, &sc.race_rec, &sc.race_word, &sc.glue_rows})
             if (b->p) (void)hipFree(b->p);
     }
@@ -983,6 +987,8 @@ extern "C" const char *mopa_planner_status(const MopaScene *S) { return S ? S->s
 #include "mopa_proximity.inc"
 // K2 motion report: k_motion_report / k_motion_report_reduce, mopa_motion_report_batch / mopa_motion_report
 #include "mopa_motion_report.inc"
+// K2 clearance report: k_clearance_states / k_motion_clearance_reduce, mopa_motion_clearance_batch / mopa_motion_clearance
+#include "mopa_motion_clearance.inc"
 
 // The planner entry points are defined in mopa_planner.inc (K3).
 #include "mopa_planner.inc"

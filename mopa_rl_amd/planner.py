@@ -105,6 +105,7 @@ class PyKinematicPlanner:
         #: the scene plan() and isValidState() run on: with glue_bodies the glued sibling (closed with `_scene`)
         self._query_scene = self._scene.glued(*self.glue_bodies) if self.glue_bodies else self._scene
         self._plan_count = 0
+        self._batch = None          # the BatchPlanner of `_scene`, made on first use (path_clearance)
         #: RRT*: the cost (L1 length) of the last plan()'s path, +inf when it found none
         self.last_cost = float("inf")
 
@@ -162,7 +163,7 @@ class PyKinematicPlanner:
         seed = self.seed if seed is None else seed
         import torch
         from .batch import BatchPlanner, k9_entry, k9_passes
-        ordinal = self._scene._ctor[7]          # the scene's device (-1: the current one, where it was created)
+        ordinal = self._scene.device_ordinal    # the scene's device (-1: the current one, where it was created)
         dev = torch.device("cuda", ordinal if ordinal >= 0 else torch.cuda.current_device())
         plen = torch.tensor([len(path)], dtype=torch.int32, device=dev)
         flags = (self.vertex_simplify, self.path_shortcut, self.path_smooth)
@@ -226,3 +227,37 @@ class PyKinematicPlanner:
         if self.glue_bodies:
             raise NotImplementedError("motion_report() with glue_bodies: the motion report is not built for a glued scene")
         return self._scene.motion_report_state(np.asarray(start_vec, dtype=np.float64), np.asarray(goal_vec, dtype=np.float64), max_contacts=max_contacts)
+
+    def motion_clearance(self, start_vec, goal_vec, band: float) -> dict:
+        """how near the straight line from `start_vec` to `goal_vec` (full qpos vectors; the passive entries are start_vec's) comes
+        to collision -- OMPL's MinimaxObjective::motionCost under the clearance state cost: `clearance`, `n_states`, `n_near`,
+        `k_min`, `t_min`, `pair` as (geom1_name, geom2_name), `pair_min`, `end_clearance`, `q_min` (`Scene.motion_clearance_state`).
+        With glue_bodies it raises: the clearance report is not built for a glued scene"""
+        if self.glue_bodies:
+            raise NotImplementedError("motion_clearance() with glue_bodies: the clearance report is not built for a glued scene")
+        return self._scene.motion_clearance_state(np.asarray(start_vec, dtype=np.float64), np.asarray(goal_vec, dtype=np.float64), band)
+
+    def path_clearance(self, traj, band: float) -> dict:
+        """the clearance of a path as `plan` returns it (a list of full qpos vectors): `clearance` (the smallest state clearance
+        along it, vertex 0 included, saturating at band), `seg_min` (the first segment that attains it; -1: vertex 0 does, or
+        nothing is within the band), `k_min`, `pair` as (geom1_name, geom2_name) or None, `pair_min`, `mean_vertex_clearance`
+        (`BatchPlanner.path_clearance`).  With glue_bodies it raises: the clearance report is not built for a glued scene"""
+        if self.glue_bodies:
+            raise NotImplementedError("path_clearance() with glue_bodies: the clearance report is not built for a glued scene")
+        import torch
+        from .batch import BatchPlanner
+        rows = np.ascontiguousarray(np.asarray(traj, dtype=np.float64).reshape(-1, self._scene.nq))
+        ordinal = self._scene.device_ordinal
+        dev = torch.device("cuda", ordinal if ordinal >= 0 else torch.cuda.current_device())
+        path = torch.from_numpy(rows[None] if len(rows) else np.zeros((1, 1, self._scene.nq))).to(dev).contiguous()
+        plen = torch.tensor([len(rows)], dtype=torch.int32, device=dev)
+        if self._batch is None:
+            self._batch = BatchPlanner(self._scene)
+        r = self._batch.path_clearance(path, plen, band=band)
+        m = self._model
+        pair = int(r.pair_min[0])
+        g = np.asarray(m.pair_geom).reshape(-1, 2)
+        name = lambda j: m.all_geom_names[int(m.geom_mjid[int(j)])]
+        return {"clearance": float(r.clearance[0]), "seg_min": int(r.seg_min[0]), "k_min": int(r.k_min[0]), "pair_min": pair,
+                "pair": (name(g[pair, 0]), name(g[pair, 1])) if pair >= 0 else None,
+                "mean_vertex_clearance": float(r.mean_vertex_clearance[0])}
