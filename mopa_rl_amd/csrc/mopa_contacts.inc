@@ -6,8 +6,9 @@
 //      cutoff < 0 (the broad phase culls at zero margin: it only ever drops separated pairs).
 //   2. k_contact_rows (here): persistent waves pull chunks of states from a counter; rows of states without a record are filled with
 //      the "unused" pattern, every other state gets one wave: the FK and pair sweep of the wave-per-state validity routine
-//      (wave_load_state / wave_fk / pair_culled / geom_dist -- what k_is_valid, k_debug_state and plan_state_valid_impl are made of)
-//      with NO verdict early-out and NO deep-overlap shortcut, so a distance carries the bits mopa_debug_pair_dist reports.
+//      (wave_load_state / wave_fk / wave_broad_phase over pair_culled / geom_dist -- what k_is_valid, k_debug_state and
+//      plan_state_valid_impl are made of) with NO verdict early-out and NO deep-overlap shortcut (wave_each_survivor), so a
+//      distance carries the bits mopa_debug_pair_dist reports.
 // Order: every distance lands in a per-wave LDS array indexed by the pair's position in the MopaSceneDesc pair list; the wave then
 // emits records in that order with a ballot and a prefix popcount -- ascending pair index and "the lowest K are kept" without atomics,
 // so two runs write the same bytes.
@@ -28,11 +29,7 @@ __global__ __launch_bounds__(kBlock) void k_contact_rows(SceneHdr h, const doubl
     const int *I = v.ints;
     const unsigned long long lt = (1ull << lane) - 1ull;
     for (;;) {
-        unsigned long long t = 0ull;
-        if (lane == 0) t = atomicAdd(ctr, 1ull);
-        // (the chunk index is wave-uniform: through readfirstlane it and every address formed from it stay in scalar registers)
-        const unsigned t_lo = __builtin_amdgcn_readfirstlane((unsigned)t), t_hi = __builtin_amdgcn_readfirstlane((unsigned)(t >> 32));
-        const long long s0 = (long long)(((unsigned long long)t_hi << 32) | t_lo) * chunk;
+        const long long s0 = wave_pull64(ctr, lane) * chunk;
         if (s0 >= N) break;
         const int n = (int)((N - s0 < (long long)chunk) ? (N - s0) : (long long)chunk);
         const bool kept = lane < n && min_dist[s0 + lane] <= cutoff;
@@ -53,31 +50,11 @@ __global__ __launch_bounds__(kBlock) void k_contact_rows(SceneHdr h, const doubl
             wave_load_state(h, v, lane, q_active + s * h.na, qpos_env + (s / samples_per_env) * h.nq);
             wave_fk(h, v, lane);
             for (int i = lane; i < npair_model; i += 64) pd[i] = kFar;
-            // broad phase + ballot compaction (order-preserving: the worklist stays sorted by narrow-phase class)
-            int wl_count = 0;
-            for (int base = 0; base < h.npair; base += 64) {
-                const int p = base + lane;
-                bool surv = false;
-                if (p < h.npair) {
-                    const int pk = I[h.o_pairs + p];
-                    const int g1 = pk & 0xff, g2 = (pk >> 8) & 0xff;
-                    surv = !pair_culled(h, v, g1, g2, geom_rec(h, v, g1), geom_rec(h, v, g2));
-                }
-                const unsigned long long mask = __ballot(surv);
-                if (surv) v.wl[wl_count + __popcll(mask & lt)] = (unsigned short)p;
-                wl_count += __popcll(mask);
-            }
-            wave_sync();
+            const int wl_count = wave_broad_phase(h, v, lane, CullZeroMargin{});
             // narrow phase over every survivor, full refinement
-            for (int base = 0; base < wl_count; base += 64) {
-                const int i = base + lane;
-                if (i < wl_count) {
-                    const int p = v.wl[i];
-                    const int pk = I[h.o_pairs + p];
-                    const int g1 = pk & 0xff, g2 = (pk >> 8) & 0xff, code = (pk >> 16) & 0xff;
-                    pd[pair_model[p]] = geom_dist<MESH>(code, geom_rec(h, v, g1), I[h.o_g_type + g1], geom_rec(h, v, g2), I[h.o_g_type + g2], v.dbl);
-                }
-            }
+            wave_each_survivor(h, v, lane, wl_count, [&](int p, int g1, int g2, int code) {
+                pd[pair_model[p]] = geom_dist<MESH>(code, geom_rec(h, v, g1), I[h.o_g_type + g1], geom_rec(h, v, g2), I[h.o_g_type + g2], v.dbl);
+            });
             wave_sync();
             // records in pair-index order; the count runs on past K
             int cnt = 0;
@@ -93,10 +70,7 @@ __global__ __launch_bounds__(kBlock) void k_contact_rows(SceneHdr h, const doubl
                 }
                 cnt += __popcll(mask);
             }
-            for (int i = cnt + lane; i < K; i += 64) {
-                pair[s * K + i] = -1;
-                dist[s * K + i] = kFar;
-            }
+            row_fill_unused(pair, dist, s, K, cnt, lane);
             if (lane == 0) count[s] = cnt;
             wave_sync();   // pd / worklist / geom slab are about to be reused
         }
@@ -127,13 +101,10 @@ extern "C" int mopa_contacts_batch(MopaScene *S, const double *q_active, const d
     StreamScratch &sc = scratch_for(S, st);
     HIP_TRY(grow(S, sc.ct_valid, (size_t)N));
     HIP_TRY(grow(S, sc.ct_md, (size_t)N * sizeof(double)));
-    if (!sc.ct_ctr.p) {      // zeroed once, synchronously; the kernel puts it back to zero (tile_ctr_release)
-        HIP_TRY(grow(S, sc.ct_ctr, 64));
-        HIP_TRY(hipMemset(sc.ct_ctr.p, 0, 64));
-        HIP_TRY(hipStreamSynchronize(nullptr));      // (a device memset may return before it has run: `st` need not wait for the null stream)
-    }
+    int rc = ensure_report_ctr(S, sc);
+    if (rc != MOPA_OK) return rc;
     // stage 1: deepest penetration of every state
-    const int rc = launch_is_valid(S, q_active, qpos_env, N, samples_per_env, nullptr, sc.ct_valid.as<uint8_t>(), sc.ct_md.as<double>(), stream);
+    rc = launch_is_valid(S, q_active, qpos_env, N, samples_per_env, nullptr, sc.ct_valid.as<uint8_t>(), sc.ct_md.as<double>(), stream);
     if (rc != MOPA_OK) return rc;
     // stage 2: persistent waves (189 / 191 VGPRs: two waves per SIMD, i.e. two workgroups per CU are resident); small batches are
     // handed out state by state, large ones in chunks of up to 64

@@ -139,6 +139,7 @@ struct K1Policy {
     int v2_lds_bytes = 0;
     int v5_lds_bytes = 0;        // verdict-only instantiations of k_is_valid_v5 (hdr.v5_ent_cap entries per wave)
     int v5_lds_bytes_md = 0, v5_ent_cap_md = 0;   // depth-reporting instantiations
+    int64_t motion_chunk = 1;    // K2, expanded motion (mopa_motion.inc: motion_for_chunks): segments per chunk of the pipeline
 };
 
 struct MopaScene {
@@ -204,6 +205,15 @@ static hipError_t grow(MopaScene *S, DevBuf &b, size_t bytes) {
     b.cap = want;
     return hipSuccess;
 }
+// The work counter of the report kernels (k_contact_rows, k_proximity_rows, k_clearance_states; one per stream, shared: calls on a
+// stream are ordered): zeroed once, synchronously; the kernels put it back to zero themselves (tile_ctr_release).
+static int ensure_report_ctr(MopaScene *S, StreamScratch &sc) {
+    if (sc.ct_ctr.p) return MOPA_OK;
+    HIP_TRY(grow(S, sc.ct_ctr, 64));
+    HIP_TRY(hipMemset(sc.ct_ctr.p, 0, 64));
+    HIP_TRY(hipStreamSynchronize(nullptr));      // (a device memset may return before it has run: the call's stream need not wait for the null stream)
+    return MOPA_OK;
+}
 
 // Zero a few 8-byte words on a stream.  A kernel, not hipMemsetAsync: these launches are also captured into HIP graphs
 // (rollout.py, cfg.use_graphs), and small memset nodes proved unreliable there.
@@ -244,6 +254,31 @@ MOPA_D void tile_ctr_release(unsigned long long *ctr, int lane) {
         }
     }
 }
+// ... and the pull of its next work item, 64 bits.  The index is wave-uniform: through readfirstlane it and every address formed
+// from it stay in scalar registers.
+MOPA_D long long wave_pull64(unsigned long long *ctr, int lane) {
+    unsigned long long t = 0ull;
+    if (lane == 0) t = atomicAdd(ctr, 1ull);
+    const unsigned t_lo = __builtin_amdgcn_readfirstlane((unsigned)t), t_hi = __builtin_amdgcn_readfirstlane((unsigned)(t >> 32));
+    return (long long)(((unsigned long long)t_hi << 32) | t_lo);
+}
+// wave-wide minimum under the (distance, index) order -- a strictly smaller distance, or an equal one with a lower index; every
+// lane ends with the winner.  The one selection rule of the proximity and clearance reports.
+MOPA_D void wave_argmin(double &bd, int &bi) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const double od = __shfl_xor(bd, off, 64);
+        const int oi = __shfl_xor(bi, off, 64);
+        if (od < bd || (od == bd && oi < bi)) { bd = od; bi = oi; }
+    }
+}
+// the rest of report row s ([K] entries of `pair` and `dist`) from entry `from` on is unused: pair -1, distance kFar
+MOPA_D void row_fill_unused(int32_t *__restrict__ pair, double *__restrict__ dist, long long s, int K, int from, int lane) {
+    for (int i = from + lane; i < K; i += 64) {
+        pair[s * K + i] = -1;
+        dist[s * K + i] = kFar;
+    }
+}
 
 struct LdsView {
     const double *dbl;   // shared scene doubles
@@ -276,6 +311,12 @@ MOPA_D LdsView make_view(const SceneHdr &h, unsigned char *smem) {
     v.wl = reinterpret_cast<unsigned short *>(v.sc + 2 * h.nmj);
     return v;
 }
+// the scene tables read where they are, in global memory, by kernels that stage nothing: no per-wave slab
+MOPA_D LdsView global_view(const double *g_dbl, const int32_t *g_int) {
+    LdsView v;
+    v.dbl = g_dbl; v.ints = g_int; v.grec = nullptr; v.qbuf = nullptr; v.sc = nullptr; v.wl = nullptr;
+    return v;
+}
 
 // posed record of geom g: moving geoms live in the wave slab, static ones in the shared blob
 MOPA_D const double *geom_rec(const SceneHdr &h, const LdsView &v, int g) {
@@ -296,6 +337,27 @@ MOPA_D bool pair_culled(const SceneHdr &h, const LdsView &v, int g1, int g2, con
     const int gs = s1 ? g1 : g2, gm = s1 ? g2 : g1;
     return aabb_cull(ld3((s1 ? A : B) + GO_POS), D + h.o_g_aabb + 3 * gs, ld3((s1 ? B : A) + GO_POS), D[h.o_g_rbound + gm]);
 }
+// pair_culled with every bound widened by `band`: no pair at distance <= band is dropped
+MOPA_D bool pair_culled_band(const SceneHdr &h, const LdsView &v, int g1, int g2, const double *A, const double *B, double band) {
+    const int *I = v.ints;
+    const double *D = v.dbl;
+    const double rba = D[h.o_g_rbound + g1], rbb = D[h.o_g_rbound + g2];
+    const V3 diff = sub3(ld3(B + GO_POS), ld3(A + GO_POS));
+    if (I[h.o_g_type + g1] == G_PLANE) return dot3(diff, col3(A + GO_MAT, 2)) > rbb + band;
+    const double rs = rba + rbb + band;
+    if (dot3(diff, diff) > rs * rs) return true;
+    const bool s1 = I[h.o_g_slot + g1] < 0, s2 = I[h.o_g_slot + g2] < 0;
+    if (s1 == s2) return false;
+    return aabb_cull(ld3((s1 ? A : B) + GO_POS), D + h.o_g_aabb + 3 * (s1 ? g1 : g2), ld3((s1 ? B : A) + GO_POS), (s1 ? rbb : rba) + band);
+}
+// the two as cull callables of wave_broad_phase (by value: nothing but the band to carry)
+struct CullZeroMargin {
+    MOPA_D bool operator()(const SceneHdr &h, const LdsView &v, int g1, int g2, const double *A, const double *B) const { return pair_culled(h, v, g1, g2, A, B); }
+};
+struct CullBand {
+    double band;
+    MOPA_D bool operator()(const SceneHdr &h, const LdsView &v, int g1, int g2, const double *A, const double *B) const { return pair_culled_band(h, v, g1, g2, A, B, band); }
+};
 
 // Forward kinematics for the state whose joint values are in v.qbuf.
 // Lane l < nmg walks the ancestor chain of moving geom l (same operation order
@@ -363,13 +425,12 @@ MOPA_D void wave_fk(const SceneHdr &h, const LdsView &v, int lane) {
     wave_sync();
 }
 
-// Collision sweep for the posed state.  Returns the wave-uniform verdict.
-// WANT_MD: also produce the minimum distance over broad-phase survivors
-// (disables the early-out so the minimum is complete).
-template <bool WANT_MD, bool MESH = false>
-MOPA_D bool wave_collide(const SceneHdr &h, const LdsView &v, int lane, double &min_dist) {
+// The per-state pair sweep, first half: broad phase over the scene's candidate pairs of the posed state + ballot compaction of the
+// survivors into v.wl (order-preserving => the worklist stays sorted by pair type, i.e. by narrow-phase class).
+// cull(h, v, g1, g2, A, B): true drops the pair (CullZeroMargin, or CullBand at a report's band).  Returns the number of survivors.
+template <class Cull>
+MOPA_D int wave_broad_phase(const SceneHdr &h, const LdsView &v, int lane, Cull cull) {
     const int *I = v.ints;
-    // 1. broad phase + ballot compaction (order-preserving => worklist stays sorted by pair type)
     int wl_count = 0;
     for (int base = 0; base < h.npair; base += 64) {
         int p = base + lane;
@@ -378,7 +439,7 @@ MOPA_D bool wave_collide(const SceneHdr &h, const LdsView &v, int lane, double &
             int pk = I[h.o_pairs + p];
             int g1 = pk & 0xff, g2 = (pk >> 8) & 0xff;
             const double *A = geom_rec(h, v, g1), *B = geom_rec(h, v, g2);
-            surv = !pair_culled(h, v, g1, g2, A, B);
+            surv = !cull(h, v, g1, g2, A, B);
         }
         unsigned long long mask = __ballot(surv);
         if (surv) {
@@ -388,6 +449,31 @@ MOPA_D bool wave_collide(const SceneHdr &h, const LdsView &v, int lane, double &
         wl_count += __popcll(mask);
     }
     wave_sync();
+    return wl_count;
+}
+// ... second half, as the reports run it (every survivor, no early-out): a lane per survivor, f(p, g1, g2, code) with p the device
+// pair index, g1 / g2 its geoms and code its narrow-phase class
+template <class F>
+MOPA_D void wave_each_survivor(const SceneHdr &h, const LdsView &v, int lane, int wl_count, F f) {
+    const int *I = v.ints;
+    for (int base = 0; base < wl_count; base += 64) {
+        const int i = base + lane;
+        if (i < wl_count) {
+            const int p = v.wl[i];
+            const int pk = I[h.o_pairs + p];
+            f(p, pk & 0xff, (pk >> 8) & 0xff, (pk >> 16) & 0xff);
+        }
+    }
+}
+
+// Collision sweep for the posed state.  Returns the wave-uniform verdict.
+// WANT_MD: also produce the minimum distance over broad-phase survivors
+// (disables the early-out so the minimum is complete).
+template <bool WANT_MD, bool MESH = false>
+MOPA_D bool wave_collide(const SceneHdr &h, const LdsView &v, int lane, double &min_dist) {
+    const int *I = v.ints;
+    // 1. broad phase
+    const int wl_count = wave_broad_phase(h, v, lane, CullZeroMargin{});
     // 2. narrow phase over the survivors
     bool bad = false;
     double md = 0.0;   // deepest penetration: min(0, min over pairs)

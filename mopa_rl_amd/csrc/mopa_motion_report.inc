@@ -14,11 +14,11 @@
 //   small batches  k_motion_report, one wave per segment, k ASCENDING with a stop at the first invalid state.  k_check_motion tests the
 //                  end state first, which is right for the verdict and useless for "first blocked": a segment whose end state alone
 //                  is invalid costs c passes here and one there, which is why this is an entry point of its own.
-//   large batches  k_motion_count -> k_motion_scan_blocks -> k_motion_expand -> launch_is_valid, all unchanged, then
-//                  k_motion_report_reduce in place of k_motion_reduce and k_motion_report_rows.  k_motion_expand stores state k of a
-//                  segment at slot o + (c - k), so first_bad = c - (largest j with vstate[o + j] == 0); both rows are copied out of the
-//                  expanded state buffer: first_bad_q from slot j = c - first_bad, last_valid_q from slot j + 1 (qa when
-//                  first_bad == 1).  The 31-bit chunking loop of motion_expanded applies, and so does its one 8-byte read-back per
+//   large batches  the expanded-motion pipeline check_motion runs (mopa_motion.inc: motion_expand_chunk under motion_for_chunks) and
+//                  launch_is_valid, then k_motion_report_reduce in place of k_motion_reduce and k_motion_report_rows.  k_motion_expand
+//                  stores state k of a segment at slot o + (c - k), so first_bad = c - (largest j with vstate[o + j] == 0); both rows
+//                  are copied out of the expanded state buffer: first_bad_q from slot j = c - first_bad, last_valid_q from slot j + 1
+//                  (qa when first_bad == 1).  The pipeline's 31-bit chunking applies, and so does its one 4-byte read-back per
 //                  chunk: this form synchronises the stream before it returns.
 // Every output word has one writer and is a plain vector store; no atomics, so two runs write the same bytes.
 // Blockers (max_contacts = K >= 1): mopa_contacts_batch over the rows first_bad_q at the scene's contact_threshold -- no narrow-phase
@@ -80,8 +80,8 @@ __global__ __launch_bounds__(256) void k_motion_report_reduce(const int *__restr
                                                               int32_t *__restrict__ first_bad, double *__restrict__ last_valid_t) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= N) return;
-    const int c = cnt[i], o = off[i] + bsum[i >> 8];
-    int jmax = -1;                                   // state k sits at slot c - k: the first bad k is the LAST bad slot
+    const int c = cnt[i], o = motion_slot0(off, bsum, i);
+    int jmax = -1;                                  // state k sits at slot c - k: the first bad k is the LAST bad slot
     for (int j = 0; j < c; j++)
         if (!vstate[o + j]) jmax = j;
     const int bad = jmax < 0 ? 0 : c - jmax;
@@ -101,67 +101,34 @@ __global__ __launch_bounds__(256) void k_motion_report_rows(int na, const int *_
     const long long i = e / na;
     const int a = (int)(e - i * na);
     const int c = cnt[i], bad = first_bad[i];
-    const size_t o = (size_t)(off[i] + bsum[i >> 8]);
-    const int j = bad ? c - bad : 0;                 // slot 0 holds s_c = qb
+    const size_t o = (size_t)motion_slot0(off, bsum, i);
+    const int j = bad ? c - bad : 0;                // slot 0 holds s_c = qb
     if (first_bad_q) first_bad_q[e] = q_states[(o + j) * na + a];
     if (last_valid_q) last_valid_q[e] = (bad == 0) ? q_states[o * na + a] : (bad == 1) ? qa[e] : q_states[(o + j + 1) * na + a];
 }
 
-// one chunk of segments: motion_expanded_chunk's pipeline with the ordered reduction at its end
-static int motion_report_expanded_chunk(MopaScene *S, StreamScratch &sc, const double *qa, const double *qb, const double *qpos_env, int64_t N,
-                                        int64_t samples_per_env, int64_t first, uint8_t *valid, int32_t *n_states, int32_t *first_bad,
-                                        double *last_valid_t, double *last_valid_q, double *first_bad_q, hipStream_t st) {
-    HIP_TRY(grow(S, sc.mv_cnt, sizeof(int32_t) * (size_t)N));
-    HIP_TRY(grow(S, sc.mv_off, sizeof(int32_t) * (size_t)N));
-    int32_t *cnt = sc.mv_cnt.as<int32_t>(), *off = sc.mv_off.as<int32_t>();
-    const unsigned nb = (unsigned)((N + 255) / 256);
-    HIP_TRY(grow(S, sc.mv_scan, sizeof(int32_t) * ((size_t)nb + 1)));
-    int32_t *bsum = sc.mv_scan.as<int32_t>();
-    hipLaunchKernelGGL(k_motion_count, dim3(nb), dim3(256), 0, st, S->hdr, S->d_dbl, S->d_int, qa, qb, (long long)N, cnt, off, bsum);
-    hipLaunchKernelGGL(k_motion_scan_blocks, dim3(1), dim3(1024), 0, st, bsum, (int)nb);
-    int32_t total = 0;
-    HIP_TRY(hipMemcpyAsync(&total, bsum + nb, 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    const int64_t T = total;
-    if (T <= 0 || T > 0x7fffffffLL) return fail(MOPA_ERR_LIMIT, "motion report: state count of a chunk does not fit 31 bits");
-    const size_t cap = (size_t)T + (size_t)T / 4 + 64;
-    if ((size_t)T * S->na * sizeof(double) > sc.mv_q.cap) {
-        HIP_TRY(grow(S, sc.mv_q, sizeof(double) * cap * S->na));
-        HIP_TRY(grow(S, sc.mv_env, sizeof(int32_t) * cap));
-        HIP_TRY(grow(S, sc.mv_valid, cap));
-    }
-    hipLaunchKernelGGL(k_motion_expand, dim3(nb), dim3(256), 0, st, S->hdr, S->d_dbl, S->d_int, qa, qb, (long long)N,
-                       (long long)samples_per_env, (long long)first, cnt, off, bsum, sc.mv_q.as<double>(), sc.mv_env.as<int32_t>());
-    int rc = launch_is_valid(S, sc.mv_q.as<double>(), qpos_env, T, 1, sc.mv_env.as<int32_t>(), sc.mv_valid.as<uint8_t>(), nullptr, st);
-    if (rc != MOPA_OK) return rc;
-    hipLaunchKernelGGL(k_motion_report_reduce, dim3(nb), dim3(256), 0, st, cnt, off, bsum, sc.mv_valid.as<uint8_t>(), (long long)N, valid,
-                       n_states, first_bad, last_valid_t);
-    if (last_valid_q || first_bad_q) {
-        const unsigned nbr = (unsigned)((N * S->na + 255) / 256);
-        hipLaunchKernelGGL(k_motion_report_rows, dim3(nbr), dim3(256), 0, st, S->na, cnt, off, bsum, first_bad, sc.mv_q.as<double>(), qa,
-                           (long long)N, last_valid_q, first_bad_q);
-    }
-    HIP_TRY(hipGetLastError());
-    return MOPA_OK;
-}
-
+// large batches: the expanded-motion pipeline (mopa_motion.inc) and launch_is_valid, then the ordered reduction and the rows
 static int motion_report_expanded(MopaScene *S, const double *qa, const double *qb, const double *qpos_env, int64_t N, int64_t samples_per_env,
                                   uint8_t *valid, int32_t *n_states, int32_t *first_bad, double *last_valid_t, double *last_valid_q,
                                   double *first_bad_q, hipStream_t st) {
-    // (the chunk size of motion_expanded: every 32-bit offset of the count -> scan -> expand pipeline stays in range)
-    const double res = S->hdr.resolution;
-    const int64_t per_seg = (int64_t)std::ceil(1.0 / res) + 2;
-    const int64_t chunk = std::max<int64_t>(1, 0x7fffffffLL / per_seg);
     StreamScratch &sc = scratch_for(S, st);
     const size_t na = (size_t)S->na;
-    for (int64_t first = 0; first < N; first += chunk) {
-        const int64_t n = std::min(chunk, N - first);
-        int rc = motion_report_expanded_chunk(S, sc, qa + first * na, qb + first * na, qpos_env, n, samples_per_env, first, valid + first,
-                                              n_states + first, first_bad + first, last_valid_t + first,
-                                              last_valid_q ? last_valid_q + first * na : nullptr, first_bad_q ? first_bad_q + first * na : nullptr, st);
+    return motion_for_chunks(S, N, [&](int64_t first, int64_t n) {
+        MotionExpanded x;
+        int rc = motion_expand_chunk(S, sc, "motion report", qa + first * na, qb + first * na, n, samples_per_env, first, st, x);
         if (rc != MOPA_OK) return rc;
-    }
-    return MOPA_OK;
+        rc = launch_is_valid(S, x.q, qpos_env, x.T, 1, x.env, sc.mv_valid.as<uint8_t>(), nullptr, st);
+        if (rc != MOPA_OK) return rc;
+        hipLaunchKernelGGL(k_motion_report_reduce, dim3(x.nb), dim3(256), 0, st, x.cnt, x.off, x.bsum, sc.mv_valid.as<uint8_t>(), (long long)n,
+                           valid + first, n_states + first, first_bad + first, last_valid_t + first);
+        if (last_valid_q || first_bad_q) {
+            const unsigned nbr = (unsigned)((n * S->na + 255) / 256);
+            hipLaunchKernelGGL(k_motion_report_rows, dim3(nbr), dim3(256), 0, st, S->na, x.cnt, x.off, x.bsum, first_bad + first, x.q, qa + first * na,
+                               (long long)n, last_valid_q ? last_valid_q + first * na : nullptr, first_bad_q ? first_bad_q + first * na : nullptr);
+        }
+        HIP_TRY(hipGetLastError());
+        return (int)MOPA_OK;
+    });
 }
 
 static void motion_report_register_lds() {

@@ -1,27 +1,14 @@
 // mopa_proximity.inc -- batched proximity report: how far from collision a state is, and which pairs are nearest, inside a band.
 // What a user of a collision-checked planner asks besides the verdict; the reference's maximize_min_clearance objective reads it.
 //
-// One launch, modelled on k_contact_rows (DESIGN.md section 4, "Proximity report"): persistent waves pull states from a counter, one
+// One launch (DESIGN.md section 4, "Proximity report"): persistent waves pull states from the reports' counter (wave_pull64), one
 // state per pull, and EVERY state gets a wave -- there is no stage-1 gate, a separated state has a clearance too.  Per state: the
-// wave-per-state validity routine's wave_load_state / wave_fk, a MARGIN broad phase (pair_culled_band: every bound of pair_culled
-// widened by the band, so no pair at distance <= band is dropped), geom_sep (mopa_sep.hpp) for the survivors, then the selection.
+// wave-per-state validity routine's wave_load_state / wave_fk, the shared pair sweep (wave_broad_phase / wave_each_survivor,
+// mopa_hip.hip) with a MARGIN cull (pair_culled_band: every bound of pair_culled widened by the band, so no pair at distance
+// <= band is dropped) and geom_sep (mopa_sep.hpp) for the survivors, then the selection.
 // Every distance lands in a per-wave LDS array indexed by the pair's position in the MopaSceneDesc pair list (kFar = out of band);
 // the count is a ballot over it, the K nearest come out of min(K, count) rounds of a wave-wide minimum over (distance, pair index)
-// -- ties to the lower index, no atomics, one writer per output word: two runs write the same bytes.
-
-// pair_culled with every bound widened by `band`
-MOPA_D bool pair_culled_band(const SceneHdr &h, const LdsView &v, int g1, int g2, const double *A, const double *B, double band) {
-    const int *I = v.ints;
-    const double *D = v.dbl;
-    const double rba = D[h.o_g_rbound + g1], rbb = D[h.o_g_rbound + g2];
-    const V3 diff = sub3(ld3(B + GO_POS), ld3(A + GO_POS));
-    if (I[h.o_g_type + g1] == G_PLANE) return dot3(diff, col3(A + GO_MAT, 2)) > rbb + band;
-    const double rs = rba + rbb + band;
-    if (dot3(diff, diff) > rs * rs) return true;
-    const bool s1 = I[h.o_g_slot + g1] < 0, s2 = I[h.o_g_slot + g2] < 0;
-    if (s1 == s2) return false;
-    return aabb_cull(ld3((s1 ? A : B) + GO_POS), D + h.o_g_aabb + 3 * (s1 ? g1 : g2), ld3((s1 ? B : A) + GO_POS), (s1 ? rbb : rba) + band);
-}
+// (wave_argmin) -- ties to the lower index, no atomics, one writer per output word: two runs write the same bytes.
 
 template <bool MESH>
 __global__ __launch_bounds__(kBlock) void k_proximity_rows(SceneHdr h, const double *__restrict__ g_dbl, const int32_t *__restrict__ g_int,
@@ -37,40 +24,17 @@ __global__ __launch_bounds__(kBlock) void k_proximity_rows(SceneHdr h, const dou
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     double *pd = reinterpret_cast<double *>(smem + pd_off) + wave * npair_model;   // [npair_model] distance by pair index, kFar = out of band
     const int *I = v.ints;
-    const unsigned long long lt = (1ull << lane) - 1ull;
     for (;;) {
-        unsigned long long t = 0ull;
-        if (lane == 0) t = atomicAdd(ctr, 1ull);
-        const unsigned t_lo = __builtin_amdgcn_readfirstlane((unsigned)t), t_hi = __builtin_amdgcn_readfirstlane((unsigned)(t >> 32));
-        const long long s = (long long)(((unsigned long long)t_hi << 32) | t_lo);
+        const long long s = wave_pull64(ctr, lane);
         if (s >= N) break;
         wave_load_state(h, v, lane, q_active + s * h.na, qpos_env + (s / samples_per_env) * h.nq);
         wave_fk(h, v, lane);
         for (int i = lane; i < npair_model; i += 64) pd[i] = kFar;
-        // margin broad phase + ballot compaction (order-preserving: the worklist stays sorted by narrow-phase class)
-        int wl_count = 0;
-        for (int base = 0; base < h.npair; base += 64) {
-            const int p = base + lane;
-            bool surv = false;
-            if (p < h.npair) {
-                const int pk = I[h.o_pairs + p];
-                const int g1 = pk & 0xff, g2 = (pk >> 8) & 0xff;
-                surv = !pair_culled_band(h, v, g1, g2, geom_rec(h, v, g1), geom_rec(h, v, g2), band);
-            }
-            const unsigned long long mask = __ballot(surv);
-            if (surv) v.wl[wl_count + __popcll(mask & lt)] = (unsigned short)p;
-            wl_count += __popcll(mask);
-        }
-        wave_sync();
-        for (int base = 0; base < wl_count; base += 64) {
-            const int i = base + lane;
-            if (i < wl_count) {
-                const int p = v.wl[i];
-                const int pk = I[h.o_pairs + p];
-                const int g1 = pk & 0xff, g2 = (pk >> 8) & 0xff, code = (pk >> 16) & 0xff;
-                pd[pair_model[p]] = geom_sep<MESH>(code, geom_rec(h, v, g1), I[h.o_g_type + g1], geom_rec(h, v, g2), I[h.o_g_type + g2], band, v.dbl);
-            }
-        }
+        // margin broad phase
+        const int wl_count = wave_broad_phase(h, v, lane, CullBand{band});
+        wave_each_survivor(h, v, lane, wl_count, [&](int p, int g1, int g2, int code) {
+            pd[pair_model[p]] = geom_sep<MESH>(code, geom_rec(h, v, g1), I[h.o_g_type + g1], geom_rec(h, v, g2), I[h.o_g_type + g2], band, v.dbl);
+        });
         wave_sync();
         int cnt = 0;
         for (int base = 0; base < npair_model; base += 64) {
@@ -87,12 +51,7 @@ __global__ __launch_bounds__(kBlock) void k_proximity_rows(SceneHdr h, const dou
                 const double d = pd[p];
                 if (d < bd) { bd = d; bi = p; }      // (ascending p within a lane: the first minimum is the lowest index)
             }
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) {
-                const double od = __shfl_xor(bd, off, 64);
-                const int oi = __shfl_xor(bi, off, 64);
-                if (od < bd || (od == bd && oi < bi)) { bd = od; bi = oi; }
-            }
+            wave_argmin(bd, bi);
             if (lane == 0) {
                 pair[s * K + r] = bi;
                 dist[s * K + r] = bd;
@@ -101,10 +60,7 @@ __global__ __launch_bounds__(kBlock) void k_proximity_rows(SceneHdr h, const dou
             if (bi < npair_model && (bi & 63) == lane) pd[bi] = kFar;      // (cnt counted it: bi names an entry below kFar)
             wave_sync();
         }
-        for (int i = nrec + lane; i < K; i += 64) {
-            pair[s * K + i] = -1;
-            dist[s * K + i] = kFar;
-        }
+        row_fill_unused(pair, dist, s, K, nrec, lane);
         if (lane == 0) {
             count[s] = cnt;
             if (cnt == 0) clearance[s] = band;
@@ -144,11 +100,8 @@ extern "C" int mopa_proximity_batch(MopaScene *S, const double *q_active, const 
     const size_t lds = (size_t)pd_off + (size_t)kWavesPerBlock * S->npair_model * sizeof(double);
     if (lds > (size_t)kMaxLdsBytes) return fail(MOPA_ERR_LIMIT, "proximity report: the per-wave distance arrays do not fit LDS");
     StreamScratch &sc = scratch_for(S, st);
-    if (!sc.ct_ctr.p) {      // the contact report's counter: zeroed once, synchronously; the kernel puts it back to zero (tile_ctr_release)
-        HIP_TRY(grow(S, sc.ct_ctr, 64));
-        HIP_TRY(hipMemset(sc.ct_ctr.p, 0, 64));
-        HIP_TRY(hipStreamSynchronize(nullptr));
-    }
+    const int rc = ensure_report_ctr(S, sc);
+    if (rc != MOPA_OK) return rc;
     const int64_t blocks = std::max<int64_t>(1, std::min<int64_t>((N + kWavesPerBlock - 1) / kWavesPerBlock, (int64_t)S->n_cu * 2));
     hipLaunchKernelGGL(S->hdr.has_mesh ? k_proximity_rows<true> : k_proximity_rows<false>, dim3((unsigned)blocks), dim3(kBlock), lds, st, S->hdr, S->d_dbl, S->d_int,
                        (const int32_t *)S->d_pair_model, S->npair_model, q_active, qpos_env, (long long)N, (long long)samples_per_env, band, (int)K,

@@ -788,6 +788,13 @@ int SceneBuild::k1_policy() {
     const bool v5_fits2 = P.v5_lds_bytes <= 80 * 1024, v2_fits2 = P.v2_lds_bytes <= 80 * 1024;
     P.use_v5 = gen != Gen::V2 && P.use_v2 && max_pnum <= 64 && std::max(P.v5_lds_bytes, P.v5_lds_bytes_md) <= kMaxLdsBytes && reach <= kV5MaxReach &&
                (v5_fits2 || !v2_fits2 || gen == Gen::V5);
+    // K2, expanded motion: a segment expands into at most ceil(1 / resolution) states (a joint cannot move further than its extent),
+    // so chunks of INT32_MAX / that many segments keep every 32-bit offset of the count -> scan -> expand pipeline in range.
+    // MOPA_MOTION_CHUNK (segments, clamped to 1 .. that default) is a test knob, not a tuning one: it makes a batch of a few
+    // thousand segments take several chunks, so the tests reach the arithmetic on a chunk's first segment.
+    const int64_t per_seg = (int64_t)std::ceil(1.0 / h.resolution) + 2;
+    P.motion_chunk = std::max<int64_t>(1, 0x7fffffffLL / per_seg);
+    if (const char *em = std::getenv("MOPA_MOTION_CHUNK")) P.motion_chunk = std::max<int64_t>(1, std::min<int64_t>(P.motion_chunk, atoll(em)));
     return MOPA_OK;
 }
 
