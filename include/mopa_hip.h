@@ -71,7 +71,22 @@ enum { MOPA_GEOM_PLANE = 0, MOPA_GEOM_SPHERE = 2, MOPA_GEOM_CAPSULE = 3, MOPA_GE
 enum { MOPA_JNT_FREE = 0, MOPA_JNT_BALL = 1, MOPA_JNT_SLIDE = 2, MOPA_JNT_HINGE = 3 };
 
 /* Flat compiled model (host pointers; copied by mopa_scene_create).
- * Same arrays as mopa_rl_amd.mjcf.CompiledModel. */
+ * Same arrays as mopa_rl_amd.mjcf.CompiledModel.
+ *
+ * Preconditions -- what MuJoCo's compiler emits; every entry point that compiles a scene (mopa_scene_create, _create_glued,
+ * mopa_scene_k1_export, _export_glued) checks them before anything indexes with these values and refuses a model that breaks one:
+ *   - body 0 is the world; 0 <= body_parent[b] < b for b >= 1                                    (MOPA_ERR_INVALID_ARG)
+ *   - the bodies are in depth-first order: body_parent[b] is body b - 1 or one of its ancestors  (MOPA_ERR_UNSUPPORTED; a breadth-
+ *     first numbering of a branching tree is refused, not compiled: the pose save slots of the FK program are numbered by depth)
+ *   - body_jntnum[b] >= 0, and the joints body_jntadr[b] .. + body_jntnum[b] lie in [0, njnt)     (MOPA_ERR_INVALID_ARG)
+ *   - jnt_type is one of MOPA_JNT_*; jnt_qposadr[j] and the slots behind it (7 of a free joint, 4 of a ball joint, 1 otherwise) lie
+ *     in [0, nq)                                                                                  (MOPA_ERR_INVALID_ARG)
+ *   - 0 <= geom_body[g] < nbody; the geoms are in body order; a mesh geom's geom_dataid names a mesh whose vertices lie in
+ *     [0, nmeshvert)                                                                              (MOPA_ERR_INVALID_ARG / _UNSUPPORTED)
+ *   - a candidate pair names two different geoms in [0, ngeom), at least one of them on a body that a joint moves
+ *                                                                                                 (MOPA_ERR_INVALID_ARG)
+ * Capacities (MOPA_ERR_LIMIT): 255 collidable geoms, 64 of them moving, 65535 candidate pairs.  Unit quaternions and unit joint axes are
+ * the caller's responsibility. */
 typedef struct MopaModel {
     int32_t nq, nbody, njnt, ngeom, npair;
     const int32_t *body_parent;   /* [nbody]            */

@@ -717,6 +717,7 @@ extern "C" int mopa_scene_hdr_offset(const char *field) {
     MOPA_HDR_FIELD(o_mb_parent) MOPA_HDR_FIELD(o_chain_adr) MOPA_HDR_FIELD(o_chain_len) MOPA_HDR_FIELD(o_chain_items) MOPA_HDR_FIELD(o_g_mb)
     MOPA_HDR_FIELD(o_mb_load) MOPA_HDR_FIELD(o_mb_save) MOPA_HDR_FIELD(pfk_maxlen) MOPA_HDR_FIELD(n_gp) MOPA_HDR_FIELD(npair) MOPA_HDR_FIELD(o_pairs)
     MOPA_HDR_FIELD(o_g_rec) MOPA_HDR_FIELD(o_g_type) MOPA_HDR_FIELD(o_g_aabb)
+    MOPA_HDR_FIELD(n_pas_g) MOPA_HDR_FIELD(n_pas_lv) MOPA_HDR_FIELD(v5_ent_cap) MOPA_HDR_FIELD(o_act_so2) MOPA_HDR_FIELD(o_mj_type) MOPA_HDR_FIELD(o_mj_qsrc) MOPA_HDR_FIELD(nmj)
 #undef MOPA_HDR_FIELD
     return -1;
 }

@@ -90,6 +90,35 @@ int SceneBuild::check_model() {
     // depending on the cull, and MuJoCo's own contact list (dist < margin) would have to be reproduced.  The reference
     // passes negative thresholds (config/sawyer.py:98-100, config/pusher.py:79-81); 0 keeps "any penetration".
     if (desc->contact_threshold > 0.0) return fail(MOPA_ERR_UNSUPPORTED, "contact_threshold > 0 is not supported (the broad phase culls at zero margin)");
+    // The structure every later step indexes with (the preconditions of MopaModel, include/mopa_hip.h).  MuJoCo's compiler emits
+    // nothing else; a model built by hand is refused here instead of read out of bounds there.
+    if (m.njnt < 0 || m.npair < 0 || m.nmesh < 0 || m.nmeshvert < 0) return fail(MOPA_ERR_INVALID_ARG, "negative count in the model");
+    for (int b = 1; b < m.nbody; b++) {
+        const int p = m.body_parent[b];
+        if (p < 0 || p >= b) return fail(MOPA_ERR_INVALID_ARG, "body_parent[" + std::to_string(b) + "] out of range (a body's parent must come before it)");
+        // depth-first order: the parent is the previous body or one of its ancestors.  The save slots of the DFS program (dfs_program)
+        // are numbered by depth, which parks a pose under a slot that is still needed when siblings' subtrees interleave.
+        int a = b - 1;
+        while (a > p) a = m.body_parent[a];
+        if (a != p) return fail(MOPA_ERR_UNSUPPORTED, "bodies are not in depth-first order (body " + std::to_string(b) + ")");
+    }
+    for (int b = 0; b < m.nbody; b++) {
+        const int n = m.body_jntnum[b], a = m.body_jntadr[b];
+        if (n < 0 || (n > 0 && (a < 0 || a > m.njnt - n))) return fail(MOPA_ERR_INVALID_ARG, "body_jntadr + body_jntnum out of range (body " + std::to_string(b) + ")");
+    }
+    for (int j = 0; j < m.njnt; j++) {
+        const int t = m.jnt_type[j];
+        if (t != J_FREE && t != J_BALL && t != J_SLIDE && t != J_HINGE) return fail(MOPA_ERR_INVALID_ARG, "unknown joint type " + std::to_string(t));
+        const int w = (t == J_FREE) ? 7 : (t == J_BALL ? 4 : 1);
+        if (m.jnt_qposadr[j] < 0 || m.jnt_qposadr[j] > m.nq - w) return fail(MOPA_ERR_INVALID_ARG, "jnt_qposadr out of range (joint " + std::to_string(j) + ")");
+    }
+    for (int g = 0; g < m.ngeom; g++)   // (a mesh geom's geom_dataid: static_frames, with the hull it names)
+        if (m.geom_body[g] < 0 || m.geom_body[g] >= m.nbody) return fail(MOPA_ERR_INVALID_ARG, "geom_body out of range (geom " + std::to_string(g) + ")");
+    for (int p = 0; p < m.npair; p++) {
+        const int g1 = m.pair_geom[2 * p], g2 = m.pair_geom[2 * p + 1];
+        if (g1 < 0 || g1 >= m.ngeom || g2 < 0 || g2 >= m.ngeom) return fail(MOPA_ERR_INVALID_ARG, "pair_geom out of range");
+        if (g1 == g2) return fail(MOPA_ERR_INVALID_ARG, "pair_geom names one geom twice (pair " + std::to_string(p) + ")");
+    }
     par.assign(m.body_parent, m.body_parent + m.nbody);
     in_glue.assign(m.nbody, 0);
     if (glued()) {
@@ -348,7 +377,9 @@ int SceneBuild::geoms_and_pairs() {
     // pairs: drop ignored (mujoco_ompl_interface.cpp:950-960), sort by narrow-phase cost class
     for (int p = 0; p < m.npair; p++) {
         int g1 = m.pair_geom[2 * p], g2 = m.pair_geom[2 * p + 1];
-        if (g1 < 0 || g1 >= m.ngeom || g2 < 0 || g2 >= m.ngeom) { return fail(MOPA_ERR_INVALID_ARG, "pair_geom out of range"); }
+        // (in range and distinct: check_model)  Every pair list belongs to a moving geom, the later of the two: a pair of two static
+        // geoms has no owner -- and no state changes its distance, so it is no candidate of MuJoCo's either
+        if (g_slot[g1] < 0 && g_slot[g2] < 0) { return fail(MOPA_ERR_INVALID_ARG, "candidate pair of two static geoms (pair " + std::to_string(p) + ")"); }
         int a = m.geom_mjid[g1], b = m.geom_mjid[g2];
         int lo = std::min(a, b), hi = std::max(a, b);
         bool ignored = false;

@@ -1,0 +1,444 @@
+"""Random and directed kinematic scenes for the scene compiler and the scene-level kernels (helpers of test_random_scenes_host /
+test_random_scenes_gpu): models that are none of the shipped ones, built in memory (no fixture files), with the planner inputs the
+sequential forms read (contacts_ref, proximity_ref, motion_report_ref, motion_clearance_ref work on them unchanged).
+
+A scene is what MuJoCo's compiler would emit: bodies in depth-first order, geoms in body order, candidate pairs after MuJoCo's
+filters (no pair on one body or in one weld group, none between a body and its parent unless that parent is welded to the world,
+none of two static geoms) with type1 <= type2, unit quaternions and axes, at least one active hinge or slide.  `random_scene(seed)`
+draws everything from numpy.random.default_rng(seed); the directed constructors (DIRECTED) fix the tree so that the compiler takes
+one particular decision (mopa_scene_build.inc: save slots, tile poses, packed FK chains, entry caps, centre placement, the
+conditions of the third-generation kernel)."""
+import functools
+import types
+
+import numpy as np
+
+from mopa_rl_amd import mjcf
+from mopa_rl_amd.mjcf import GEOM_BOX, GEOM_CAPSULE, GEOM_CYLINDER, GEOM_MESH, GEOM_PLANE, GEOM_SPHERE, JNT_FREE, JNT_HINGE, JNT_SLIDE
+
+CONTACT_THRESHOLD = -0.002
+PRIMS = (GEOM_SPHERE, GEOM_CAPSULE, GEOM_CYLINDER, GEOM_BOX)
+HOST_SEEDS = range(48)
+GPU_SEEDS = range(24)
+
+
+def _rquat(rng):
+    q = rng.normal(size=4)
+    return q / np.linalg.norm(q)
+
+
+def _unit(rng):
+    v = rng.normal(size=3)
+    return v / np.linalg.norm(v)
+
+
+def node(parent, joints=(JNT_HINGE,), ngeom=1, passive=False, unlimited=False, geoms=None):
+    """one body of the moving tree: parent = index of an earlier node, -1 = the world; joints = their types ((): welded to the parent);
+    passive: every joint of the body is passive (a tuple: per joint); unlimited: its first hinge has no range (SO2); geoms: explicit [(type, size)]"""
+    return dict(parent=parent, joints=tuple(joints), ngeom=ngeom, passive=passive, unlimited=unlimited, geoms=geoms)
+
+
+class _Model:
+    """accumulates bodies (in the order given: the caller keeps it depth-first), joints and geoms"""
+
+    def __init__(self, rng, scale, gscale):
+        self.rng, self.scale, self.gscale = rng, scale, gscale
+        self.bp, self.bpos, self.bquat, self.bja, self.bjn = [0], [np.zeros(3)], [np.array([1.0, 0, 0, 0])], [-1], [0]
+        self.jt, self.jq, self.jb, self.jax, self.jpos, self.jref, self.jlim, self.jrng = [], [], [], [], [], [], [], []
+        self.gt, self.gb, self.gs, self.gp, self.gq, self.gmesh = [], [], [], [], [], []
+        self.nq = 0
+        self.passive = []
+
+    def body(self, parent, joints, pos=None, quat=None, passive=False, unlimited=False):
+        rng = self.rng
+        b = len(self.bp)
+        self.bp.append(parent)
+        self.bpos.append(_unit(rng) * rng.uniform(0.5, 1.2) * self.scale if pos is None else np.asarray(pos, dtype=float))
+        self.bquat.append(_rquat(rng) if quat is None else np.asarray(quat, dtype=float))
+        self.bja.append(len(self.jt) if joints else -1)
+        self.bjn.append(len(joints))
+        for k, t in enumerate(joints):
+            self.jt.append(t); self.jq.append(self.nq); self.jb.append(b)
+            self.jax.append(_unit(rng))
+            self.jpos.append(rng.uniform(-0.05, 0.05, 3) if rng.random() < 0.5 else np.zeros(3))      # anchors at and away from the origin
+            if t == JNT_FREE:
+                self.jref.append(0.0); self.jlim.append(0); self.jrng.append([0.0, 0.0])
+                self.passive += list(range(self.nq, self.nq + 7))
+                self.nq += 7
+                continue
+            self.jref.append(float(rng.uniform(-0.2, 0.2)) if rng.random() < 0.3 else 0.0)
+            free_hinge = t == JNT_HINGE and ((unlimited and k == 0) or (not unlimited and rng.random() < 0.12))
+            self.jlim.append(0 if free_hinge else 1)
+            self.jrng.append([0.0, 0.0] if free_hinge else [-rng.uniform(0.3, 2.5), rng.uniform(0.3, 2.5)] if t == JNT_HINGE
+                             else [-rng.uniform(0.02, 0.2), rng.uniform(0.02, 0.2)])
+            if passive[k] if isinstance(passive, tuple) else passive:
+                self.passive.append(self.nq)
+            self.nq += 1
+        return b
+
+    def prim(self, t=None):
+        rng, s = self.rng, self.gscale
+        t = int(rng.choice(PRIMS)) if t is None else t
+        size = {GEOM_SPHERE: [rng.uniform(.03, .08) * s, 0, 0], GEOM_CAPSULE: [rng.uniform(.02, .05) * s, rng.uniform(.03, .15) * s, 0],
+                GEOM_CYLINDER: [rng.uniform(.02, .06) * s, rng.uniform(.01, .12) * s, 0], GEOM_BOX: list(rng.uniform(.02, .1, 3) * s)}[t]
+        return t, size
+
+    def geom(self, b, t=None, size=None, pos=None, quat=None, mesh=-1):
+        if size is None:
+            t, size = self.prim(t)
+        self.gt.append(t); self.gb.append(b); self.gs.append(np.asarray(size, dtype=float))
+        self.gp.append(self.rng.uniform(-.05, .05, 3) if pos is None else np.asarray(pos, dtype=float))
+        self.gq.append(_rquat(self.rng) if quat is None else np.asarray(quat, dtype=float))
+        self.gmesh.append(mesh)
+
+
+def _finish(M, name, rng, pair_keep=1.0, extra_pairs=(), mesh_vert=None, n_ignored=3, qpos0_free=None, all_pairs_of=()):
+    """-> (CompiledModel, pi): the candidate pairs after MuJoCo's filters, geom_mjid with gaps, a few ignored pairs, the planner inputs"""
+    nb, ng = len(M.bp), len(M.gt)
+    assert all(M.gb[g] <= M.gb[g + 1] for g in range(ng - 1)), "geoms in body order"
+    bp = np.array(M.bp, dtype=np.int32)
+    static = np.ones(nb, dtype=bool)
+    weld = np.zeros(nb, dtype=np.int64)
+    for b in range(1, nb):
+        static[b] = M.bjn[b] == 0 and static[bp[b]]
+        weld[b] = b if M.bjn[b] else weld[bp[b]]
+    wpar = {int(w): int(weld[bp[w]]) for w in set(weld.tolist()) if w}
+    pairs = []
+    for a in range(ng):
+        for b in range(a + 1, ng):
+            ba, bb = M.gb[a], M.gb[b]
+            wa, wb = int(weld[ba]), int(weld[bb])
+            if wa == wb or (static[ba] and static[bb]) or (M.gt[a] == M.gt[b] and M.gt[a] in (GEOM_PLANE, GEOM_MESH)):
+                continue
+            if (wa and wpar[wa] == wb and wb) or (wb and wpar[wb] == wa and wa):     # parent and child, the parent not welded to the world
+                continue
+            if pair_keep < 1.0 and a not in all_pairs_of and b not in all_pairs_of and rng.random() >= pair_keep:
+                continue
+            pairs.append((a, b) if M.gt[a] <= M.gt[b] else (b, a))
+    pairs += [tuple(p) for p in extra_pairs]
+    # MuJoCo's ids of the collidable geoms among all geoms: strictly increasing, with non-collidable geoms in between
+    mjid = np.cumsum(1 + (rng.random(ng) < 0.3).astype(np.int64)) - 1 + int(rng.integers(0, 3)) if ng else np.zeros(0, dtype=np.int64)
+    n_all = int(mjid[-1]) + 1 if ng else 0
+    all_body = np.zeros(n_all, dtype=np.int32)
+    if ng:
+        all_body[mjid] = M.gb
+    qpos0 = np.zeros(M.nq)
+    for j, t in enumerate(M.jt):
+        a = M.jq[j]
+        if t == JNT_FREE:
+            qpos0[a:a + 3] = rng.uniform(-.35, .35, 3) if qpos0_free is None else qpos0_free
+            qpos0[a + 3:a + 7] = _rquat(rng)
+        else:
+            qpos0[a] = M.jref[j]
+    nmesh = 0 if mesh_vert is None else 1
+    m = mjcf.CompiledModel(
+        name=name, nq=M.nq, body_names=[f"b{i}" for i in range(nb)], body_parent=bp, body_pos=np.array(M.bpos, dtype=float).reshape(-1, 3),
+        body_quat=np.array(M.bquat, dtype=float).reshape(-1, 4), body_jntadr=np.array(M.bja, dtype=np.int32),
+        body_jntnum=np.array(M.bjn, dtype=np.int32), body_weldid=weld.astype(np.int32),
+        jnt_names=[f"j{i}" for i in range(len(M.jt))], jnt_type=np.array(M.jt, dtype=np.int32), jnt_qposadr=np.array(M.jq, dtype=np.int32),
+        jnt_body=np.array(M.jb, dtype=np.int32), jnt_axis=np.array(M.jax, dtype=float).reshape(-1, 3),
+        jnt_pos=np.array(M.jpos, dtype=float).reshape(-1, 3), jnt_ref=np.array(M.jref, dtype=float), jnt_limited=np.array(M.jlim, dtype=np.int32),
+        jnt_range=np.array(M.jrng, dtype=float).reshape(-1, 2), qpos0=qpos0,
+        all_geom_names=[f"g{i}" for i in range(n_all)], all_geom_body=all_body,
+        geom_mjid=mjid.astype(np.int32), geom_type=np.array(M.gt, dtype=np.int32), geom_body=np.array(M.gb, dtype=np.int32),
+        geom_size=np.array(M.gs, dtype=float).reshape(-1, 3), geom_pos=np.array(M.gp, dtype=float).reshape(-1, 3),
+        geom_quat=np.array(M.gq, dtype=float).reshape(-1, 4), geom_contype=np.ones(ng, dtype=np.int32), geom_conaffinity=np.ones(ng, dtype=np.int32),
+        geom_margin=np.zeros(ng), geom_mesh=["can" if d >= 0 else "" for d in M.gmesh], pair_geom=np.array(pairs, dtype=np.int32).reshape(-1, 2),
+        site_names=[], site_body=np.zeros(0, dtype=np.int32), site_pos=np.zeros((0, 3)), site_quat=np.zeros((0, 4)),
+        geom_dataid=np.array(M.gmesh, dtype=np.int32) if nmesh else np.zeros(0, dtype=np.int32),
+        mesh_vertadr=np.zeros(nmesh, dtype=np.int32), mesh_vertnum=np.full(nmesh, 0 if mesh_vert is None else len(mesh_vert), dtype=np.int32),
+        mesh_vert=np.zeros((0, 3)) if mesh_vert is None else np.array(mesh_vert, dtype=float))
+    passive = sorted(M.passive)
+    hs = [j for j, t in enumerate(M.jt) if t != JNT_FREE]
+    if hs and all(M.jq[j] in passive for j in hs):          # at least one active hinge or slide
+        passive.remove(M.jq[hs[0]])
+    ignored = []
+    if len(pairs) > 8 and n_ignored:
+        for p in rng.choice(len(pairs), size=n_ignored, replace=False):
+            a, b = int(mjid[pairs[p][0]]), int(mjid[pairs[p][1]])
+            ignored.append((min(a, b), max(a, b)))
+    return m, planner_inputs(m, passive, ignored)
+
+
+def planner_inputs(m, passive, ignored, range_=0.1):
+    """the `pi` of mopa_rl_amd.scene.planner_inputs for a model that belongs to no environment"""
+    active = [a for a in range(m.nq) if a not in set(passive)]
+    jid = [int(np.nonzero(np.asarray(m.jnt_qposadr) == a)[0][0]) for a in active]
+    lim = np.asarray(m.jnt_limited)[jid].astype(bool) if jid else np.zeros(0, dtype=bool)
+    lo = np.where(lim, np.asarray(m.jnt_range, dtype=float).reshape(-1, 2)[jid, 0], -3.14) if jid else np.zeros(0)
+    hi = np.where(lim, np.asarray(m.jnt_range, dtype=float).reshape(-1, 2)[jid, 1], 3.14) if jid else np.zeros(0)
+    spec = types.SimpleNamespace(env=m.name, contact_threshold=CONTACT_THRESHOLD, range=float(range_))
+    return types.SimpleNamespace(model=m, spec=spec, ref_joint_pos_indexes=active, passive_joint_idx=list(passive), ignored_contacts=list(ignored),
+                                 non_limited_idx=np.where(~lim)[0], jnt_minimum=lo, jnt_maximum=hi, is_jnt_limited=lim)
+
+
+def _statics(M, rng, n_static, plane=True, tilt=False, plane_z=-0.45):
+    """world geoms first, then the static bodies (each a child of the world or of the static body before it)"""
+    world = [i for i in range(n_static) if rng.random() < 0.5]
+    if plane and not tilt:
+        M.geom(0, GEOM_PLANE, [0, 0, 0], pos=[0, 0, plane_z], quat=[1, 0, 0, 0])
+    for _ in world:
+        M.geom(0, pos=rng.uniform(-.45, .45, 3))
+    last = 0
+    if plane and tilt:          # the plane on a rotated static body
+        ang = rng.uniform(-0.3, 0.3)
+        last = M.body(0, (), pos=[0, 0, plane_z], quat=[np.cos(ang / 2), np.sin(ang / 2), 0, 0])
+        M.geom(last, GEOM_PLANE, [0, 0, 0], pos=[0, 0, 0], quat=[1, 0, 0, 0])
+    for _ in range(n_static - len(world)):
+        par = last if (last and rng.random() < 0.3) else 0
+        last = M.body(par, (), pos=rng.uniform(-.45, .45, 3))
+        for _ in range(int(rng.integers(1, 3))):
+            M.geom(last)
+
+
+def _tree(M, nodes):
+    ids = []
+    for n in nodes:
+        b = M.body(0 if n["parent"] < 0 else ids[n["parent"]], n["joints"], passive=n["passive"], unlimited=n["unlimited"])
+        ids.append(b)
+        if n["geoms"] is not None:
+            for t, size in n["geoms"]:
+                M.geom(b, t, size)
+        else:
+            for _ in range(n["ngeom"]):
+                M.geom(b)
+    return ids
+
+
+def _random_nodes(rng, n_bodies, branch, slide, multi_joint, passive_frac):
+    """a random tree in depth-first order: each new body hangs on the previous one or, with probability `branch`, on one of its ancestors"""
+    nodes = []
+    for k in range(n_bodies):
+        parent = k - 1
+        while parent >= 0 and rng.random() < branch:
+            parent = nodes[parent]["parent"]
+        joints = [JNT_SLIDE if rng.random() < slide else JNT_HINGE]
+        if rng.random() < multi_joint:
+            joints.append(JNT_HINGE)
+        if k and rng.random() < 0.12:
+            joints = []                                     # a jointless body inside the moving tree
+        nodes.append(node(parent, joints, ngeom=int(rng.integers(0, 3)), passive=tuple(bool(rng.random() < passive_frac) for _ in joints)))
+    if not any(n["ngeom"] for n in nodes):
+        nodes[-1]["ngeom"] = 1
+    return nodes
+
+
+def build(name, seed, nodes, n_static=5, n_free=1, plane=True, tilt=False, scale=0.25, gscale=0.75, free_geoms=1, mesh_vert=None, **finish):
+    rng = np.random.default_rng(seed)
+    M = _Model(rng, scale, gscale)
+    _statics(M, rng, n_static, plane, tilt)
+    _tree(M, nodes)
+    for f in range(n_free):
+        b = M.body(0, (JNT_FREE,))
+        if mesh_vert is not None:
+            M.geom(b, GEOM_MESH, [0, 0, 0], pos=[0, 0, 0], quat=[1, 0, 0, 0], mesh=0)
+        else:
+            for _ in range(free_geoms):
+                M.geom(b)
+    return _finish(M, name, rng, mesh_vert=mesh_vert, **finish)
+
+
+def random_scene(seed, **shape):
+    """(CompiledModel, pi) drawn from numpy.random.default_rng(seed); `shape` overrides what the seed would draw"""
+    rng = np.random.default_rng([seed, 1])
+    s = dict(n_bodies=int(rng.integers(3, 13)), branch=float(rng.uniform(0.0, 0.6)), slide=0.3, multi_joint=0.2, passive_frac=0.25,
+             n_static=int(rng.integers(1, 8)), n_free=int(rng.integers(0, 3)), tilt=bool(rng.random() < 0.3))
+    s.update(shape)
+    nodes = _random_nodes(rng, s["n_bodies"], s["branch"], s["slide"], s["multi_joint"], s["passive_frac"])
+    return build(f"random{seed}", seed, nodes, n_static=s["n_static"], n_free=s["n_free"], tilt=s["tilt"])
+
+
+# ---------------- directed scenes: one per decision of the compiler ----------------
+def _chain(n, first=-1, **kw):
+    return [node(first if k == 0 else k - 1, **kw) for k in range(n)]
+
+
+def serial():
+    """a chain without branches: no save slot"""
+    nodes = _chain(5)
+    nodes[2] = node(1, (JNT_SLIDE,))
+    return build("serial", 101, nodes, n_free=0)
+
+
+def deep_branches():
+    """branch points at three depths: three save slots"""
+    par = [-1, 0, 1, 2, 3, 2, 1, 6, 0, 8]
+    nodes = [node(p, (JNT_SLIDE,) if k == 4 else (JNT_HINGE,)) for k, p in enumerate(par)]
+    return build("deep_branches", 102, nodes, n_static=3)
+
+
+def long_chain():
+    """18 moving bodies in one chain: longer than the packed FK chains hold"""
+    nodes = _chain(18, geoms=None)
+    for k, n in enumerate(nodes):
+        n["passive"] = k % 3 == 2
+    return build("long_chain", 202, nodes, n_static=4, scale=0.2, gscale=0.4)
+
+
+def wide():
+    """11 active coordinates, one of them SO2: beyond the 8-entry act_ref / act_hinge tables"""
+    par = [-1, 0, 1, 2, 2, 1, 5, 0, 7, 8, 8]
+    nodes = [node(p, (JNT_SLIDE,) if k in (3, 9) else (JNT_HINGE,), unlimited=(k == 6)) for k, p in enumerate(par)]
+    return build("wide", 104, nodes, n_static=4, scale=0.2)
+
+
+def tile_posed():
+    """5 passive bodies (4 of the tree in 3 levels and a free body): one has an active child, one is a leaf"""
+    nodes = [node(-1, passive=True), node(0, (JNT_SLIDE,), passive=True), node(1, passive=True), node(1), node(3), node(4, (JNT_SLIDE,)),
+             node(0, passive=True), node(0), node(7)]
+    return build("tile_posed", 203, nodes, n_static=4, n_free=1)
+
+
+def no_tile_poses():
+    """3 passive bodies, below the minimum of the tile-posed path"""
+    nodes = [node(-1, passive=True), node(0, passive=True), node(1), node(2), node(0)]
+    return build("no_tile_poses", 106, nodes, n_static=3, n_free=1)
+
+
+def full():
+    """exactly 64 moving geoms, the limit"""
+    nodes = [node(p, ngeom=8) for p in (-1, 0, 1, 1, 0, 4, 4)] + [node(-1, ngeom=7)]
+    return build("full", 107, nodes, n_static=3, n_free=1, gscale=0.5, scale=0.3, pair_keep=0.25)
+
+
+def crowded_owner():
+    """one moving geom with more than 64 partners: the third generation is off, the second is used"""
+    rng = np.random.default_rng(108)
+    M = _Model(rng, 0.25, 1.0)
+    M.geom(0, GEOM_PLANE, [0, 0, 0], pos=[0, 0, -0.3], quat=[1, 0, 0, 0])
+    for _ in range(70):
+        M.geom(0, GEOM_SPHERE, [0.02, 0, 0], pos=rng.uniform(-.6, .6, 3))
+    _tree(M, [node(-1), node(0), node(1, (JNT_SLIDE,)), node(0)])
+    return _finish(M, "crowded_owner", rng, pair_keep=0.1, all_pairs_of=(len(M.gt) - 1,))
+
+
+def far():
+    """a static geom 40 m away: reach > 32, the FP32 broad phase is off"""
+    rng = np.random.default_rng(109)
+    M = _Model(rng, 0.25, 1.0)
+    _statics(M, rng, 3)
+    b = M.body(0, (), pos=[40.0, 0, 0])
+    M.geom(b)
+    _tree(M, _random_nodes(rng, 6, 0.3, 0.3, 0.2, 0.2))
+    return _finish(M, "far", rng)
+
+
+def slab_centres():
+    """36 moving geoms: the FP32 centre table of a tile leaves the LDS for the slab, the entry buffer keeps its 1024 entries"""
+    nodes = [node(p, ngeom=5) for p in (-1, 0, 1, 1, 0, 4, 4)]
+    return build("slab_centres", 111, nodes, n_static=8, n_free=1, gscale=0.5, scale=0.3, pair_keep=0.55)
+
+
+def small_entry_cap():
+    """50 moving geoms and over a thousand pairs: the entry buffer is cut below 1024 (centres in the slab)"""
+    nodes = [node(p, ngeom=7) for p in (-1, 0, 1, 1, 0, 4, 4)]
+    return build("small_entry_cap", 111, nodes, n_static=8, n_free=1, gscale=0.5, scale=0.3, pair_keep=0.85)
+
+
+@functools.lru_cache(maxsize=None)
+def _can_hull():
+    from mopa_rl_amd.scene import load_scene
+    m = load_scene("sawyer_lift_obstacle")
+    return m.mesh_vert[m.mesh_vertadr[0]:m.mesh_vertadr[0] + m.mesh_vertnum[0]].copy()
+
+
+def mesh():
+    """two free bodies carrying the Lift scene's can hull: one near the plane, one next to the tree's first body"""
+    rng = np.random.default_rng([112, 1])
+    m, pi = build("mesh", 112, _random_nodes(rng, 6, 0.4, 0.3, 0.2, 0.2), n_static=4, n_free=2, mesh_vert=_can_hull(), qpos0_free=(0.1, 0.1, -0.36))
+    root = int(np.nonzero(m.body_jntnum)[0][0])                # the tree's first body, a child of the world
+    a = int(m.jnt_qposadr[np.nonzero(m.jnt_type == JNT_FREE)[0][1]])
+    m.qpos0[a:a + 3] = m.body_pos[root] + [0.1, 0.0, 0.0]
+    return m, pi
+
+
+def no_moving_geoms():
+    """joints, but every collidable geom is static: nmg == 0, and with it no candidate pair"""
+    nodes = _chain(3, ngeom=0)
+    return build("no_moving_geoms", 113, nodes, n_static=3, n_free=0)
+
+
+def no_pairs():
+    """moving geoms, no candidate pair"""
+    m, pi = build("no_pairs", 114, _chain(3), n_static=2, n_free=0, pair_keep=0.0)
+    return m, pi
+
+
+def one_active():
+    """a single active coordinate"""
+    nodes = [node(-1), node(0, passive=True), node(1, (JNT_SLIDE,), passive=True)]
+    return build("one_active", 115, nodes, n_static=3, n_free=1)
+
+
+def same_body_pair():
+    """one candidate pair on a single moving body (MuJoCo emits none; the C ABI takes it)"""
+    rng = np.random.default_rng(116)
+    M = _Model(rng, 0.25, 1.0)
+    _statics(M, rng, 3)
+    ids = _tree(M, [node(-1), node(0, ngeom=0), node(1)])
+    at = len(M.gt) - 1                                   # the two geoms of the middle body, a constant 0.3 m apart
+    for x in (-0.15, 0.15):
+        t, size = M.prim()
+        M.gt.insert(at, t); M.gb.insert(at, ids[1]); M.gs.insert(at, np.asarray(size, dtype=float)); M.gp.insert(at, np.array([x, 0.0, 0.0]))
+        M.gq.insert(at, _rquat(rng)); M.gmesh.insert(at, -1)
+    g = [i for i, b in enumerate(M.gb) if b == ids[1]]
+    pair = (g[0], g[1]) if M.gt[g[0]] <= M.gt[g[1]] else (g[1], g[0])
+    return _finish(M, "same_body_pair", rng, extra_pairs=[pair], n_ignored=0)
+
+
+DIRECTED = {f.__name__: f for f in (serial, deep_branches, long_chain, wide, tile_posed, no_tile_poses, full, crowded_owner, far, slab_centres,
+                                    small_entry_cap, mesh, no_moving_geoms, no_pairs, one_active, same_body_pair)}
+
+
+@functools.lru_cache(maxsize=None)
+def scene(key):
+    """the scene of a seed (int) or of a directed constructor (its name), built once per process; read-only"""
+    return random_scene(key) if isinstance(key, int) else DIRECTED[key]()
+
+
+# ---------------- states ----------------
+def env_rows(pi, n_rows, seed):
+    """[n_rows, nq] env rows that all differ: the passive hinges / slides inside their ranges, the free bodies moved and turned"""
+    m = pi.model
+    rng = np.random.default_rng([seed, 2])
+    rows = np.repeat(np.asarray(m.qpos0, dtype=float)[None], n_rows, axis=0)
+    active = set(pi.ref_joint_pos_indexes)
+    for j, t in enumerate(m.jnt_type):
+        a = int(m.jnt_qposadr[j])
+        if t == JNT_FREE:
+            rows[:, a:a + 3] += rng.normal(0.0, 0.06, (n_rows, 3))
+            q = rng.normal(size=(n_rows, 4))
+            rows[:, a + 3:a + 7] = q / np.linalg.norm(q, axis=1, keepdims=True)
+        elif a not in active:
+            lo, hi = m.jnt_range[j] if m.jnt_limited[j] else (-3.14, 3.14)
+            rows[:, a] = rng.uniform(lo, hi, n_rows)
+    return rows
+
+
+def sample(pi, n, seed):
+    """[n, na] uniform joint samples"""
+    return np.random.default_rng([seed, 3]).uniform(pi.jnt_minimum, pi.jnt_maximum, size=(n, len(pi.jnt_minimum)))
+
+
+def segments(pi, n, seed, span=0.08):
+    """(qa, qb) [n, na]: short segments (up to `span` of a coordinate's extent: a dozen states), a quarter of them long, some of zero
+    length, and on an SO2 coordinate some across the +-pi seam"""
+    rng = np.random.default_rng([seed, 4])
+    lo, hi = pi.jnt_minimum, pi.jnt_maximum
+    qa = rng.uniform(lo, hi, size=(n, len(lo)))
+    step = rng.uniform(-span, span, size=qa.shape) * (hi - lo)
+    step[n // 2::4] *= 5.0
+    step[::9] = 0.0
+    qb = np.clip(qa + step, lo, hi)
+    for c in pi.non_limited_idx:
+        k = np.arange(3, n, 7)
+        qa[k, c] = rng.uniform(2.9, 3.14, len(k))
+        qb[k, c] = rng.uniform(-3.14, -2.9, len(k))
+        qa[k[::2]], qb[k[::2]] = qb[k[::2]].copy(), qa[k[::2]].copy()
+    return qa, qb
+
+
+def full_state(pi, qa, row):
+    q = np.array(row, dtype=np.float64, copy=True)
+    q[pi.ref_joint_pos_indexes] = qa
+    return q
