@@ -333,6 +333,14 @@ def _d(a):
     return a, a.ctypes.data_as(_dp)
 
 
+def _pair_names(model, pair, dist, n):
+    """the first min(n, len(pair)) records of a report row as (geom1_name, geom2_name, dist), `pair` indexing `model.pair_geom`"""
+    g = np.asarray(model.pair_geom).reshape(-1, 2)
+    name = lambda k: model.all_geom_names[int(model.geom_mjid[int(k)])]
+    k = min(int(n), len(pair))
+    return [(name(g[p, 0]), name(g[p, 1]), float(d)) for p, d in zip(pair[:k], dist[:k])]
+
+
 def _i(a):
     a = np.ascontiguousarray(a, dtype=np.int32)
     return a, a.ctypes.data_as(_ip)
@@ -630,10 +638,20 @@ class Scene:
         return ((q < self.guard_lo) | (q > self.guard_hi)).any(axis=1)
 
     # ---- single-state forms (host pointers) ----
-    def is_valid_state(self, qpos, want_min_dist: bool = False):
+    def _state(self, qpos):
+        """(array, pointer) of one full qpos, shape (nq,)"""
         q, qp = _d(qpos)
         if q.shape != (self.nq,):
             raise MopaError(f"state has dimension {q.shape}, expected nq={self.nq}")
+        return q, qp
+
+    @staticmethod
+    def _record_bufs(K: int):
+        """(count, pair [max(K, 1)] int32, dist [max(K, 1)]) a report row is written into, preset to the unused patterns"""
+        return C.c_int32(0), np.full(max(K, 1), -1, dtype=np.int32), np.full(max(K, 1), MOPA_FAR)
+
+    def is_valid_state(self, qpos, want_min_dist: bool = False):
+        q, qp = self._state(qpos)
         if self.npair_pruned and bool(self.outside_guard(q)[0]):
             return self.full().is_valid_state(q, want_min_dist)
         v = C.c_int32(0)
@@ -708,13 +726,9 @@ class Scene:
     def contacts_state_raw(self, qpos, cutoff: Optional[float] = None, max_contacts: int = 64):
         """(count, pair [K] int32, dist [K]) of one state: the single-state form of `BatchPlanner.contacts`"""
         sc = self.contact_scene()
-        q, qp = _d(qpos)
-        if q.shape != (self.nq,):
-            raise MopaError(f"state has dimension {q.shape}, expected nq={self.nq}")
+        q, qp = self._state(qpos)
         K = int(max_contacts)
-        cnt = C.c_int32(0)
-        pair = np.full(max(K, 1), -1, dtype=np.int32)
-        dist = np.full(max(K, 1), MOPA_FAR)
+        cnt, pair, dist = self._record_bufs(K)
         check(lib().mopa_contacts_state(sc._h, qp, float(self.contact_threshold if cutoff is None else cutoff), K, C.byref(cnt),
                                         pair.ctypes.data_as(_ip), dist.ctypes.data_as(_dp)))
         return int(cnt.value), pair, dist
@@ -723,13 +737,9 @@ class Scene:
         """(count, pair [K] int32, dist [K], normal [K, 3], pos [K, 3]) of one state: `contacts_state_raw` with the contact
         frame of every record (mopa_contact_frames_state); unused slots of normal / pos hold 0.0"""
         sc = self.contact_scene()
-        q, qp = _d(qpos)
-        if q.shape != (self.nq,):
-            raise MopaError(f"state has dimension {q.shape}, expected nq={self.nq}")
+        q, qp = self._state(qpos)
         K = int(max_contacts)
-        cnt = C.c_int32(0)
-        pair = np.full(max(K, 1), -1, dtype=np.int32)
-        dist = np.full(max(K, 1), MOPA_FAR)
+        cnt, pair, dist = self._record_bufs(K)
         normal = np.zeros((max(K, 1), 3))
         pos = np.zeros((max(K, 1), 3))
         check(lib().mopa_contact_frames_state(sc._h, qp, float(self.contact_threshold if cutoff is None else cutoff), K, C.byref(cnt),
@@ -741,14 +751,10 @@ class Scene:
         state: `contacts_state_raw` with the contact manifold of every record (mopa_contact_manifolds_state); unused slots hold
         normal / npoint / point_pos 0, point_dist MOPA_FAR"""
         sc = self.contact_scene()
-        q, qp = _d(qpos)
-        if q.shape != (self.nq,):
-            raise MopaError(f"state has dimension {q.shape}, expected nq={self.nq}")
+        q, qp = self._state(qpos)
         K, P = int(max_contacts), int(max_points)
         k1, p1 = max(K, 1), max(P, 1)
-        cnt = C.c_int32(0)
-        pair = np.full(k1, -1, dtype=np.int32)
-        dist = np.full(k1, MOPA_FAR)
+        cnt, pair, dist = self._record_bufs(K)
         normal = np.zeros((k1, 3))
         npoint = np.zeros(k1, dtype=np.int32)
         pdist = np.full((k1, p1), MOPA_FAR)
@@ -771,31 +777,25 @@ class Scene:
         "Contact manifolds"; PARITY UNPINNED)."""
         m = self.model
         K = max(1, len(m.pair_geom))
-        g = np.asarray(m.pair_geom).reshape(-1, 2)
-        name = lambda k: m.all_geom_names[int(m.geom_mjid[int(k)])]
         if manifold:
             n, pair, dist, normal, npoint, pdist, ppos = self.contact_manifolds_state_raw(qpos, cutoff, K, max_points, point_cutoff)
-            return [(name(g[p, 0]), name(g[p, 1]), float(d), normal[k].copy(),
-                     [(ppos[k, j].copy(), float(pdist[k, j])) for j in range(min(int(npoint[k]), pdist.shape[1]))])
-                    for k, (p, d) in enumerate(zip(pair[:n], dist[:n]))]
+            return [rec + (normal[k].copy(), [(ppos[k, j].copy(), float(pdist[k, j])) for j in range(min(int(npoint[k]), pdist.shape[1]))])
+                    for k, rec in enumerate(_pair_names(m, pair, dist, n))]
         if frames:
             n, pair, dist, normal, pos = self.contact_frames_state_raw(qpos, cutoff, K)
-            return [(name(g[p, 0]), name(g[p, 1]), float(d), normal[k].copy(), pos[k].copy()) for k, (p, d) in enumerate(zip(pair[:n], dist[:n]))]
+            return [rec + (normal[k].copy(), pos[k].copy()) for k, rec in enumerate(_pair_names(m, pair, dist, n))]
         n, pair, dist = self.contacts_state_raw(qpos, cutoff, K)
-        return [(name(g[p, 0]), name(g[p, 1]), float(d)) for p, d in zip(pair[:n], dist[:n])]
+        return _pair_names(m, pair, dist, n)
 
     def proximity_state_raw(self, qpos, band: float, max_pairs: int = 8):
         """(clearance, count, pair [K] int32, dist [K]) of one state: the single-state form of `BatchPlanner.proximity`"""
         if self.glue is not None:
             raise NotImplementedError("the proximity report of a glued scene")
         sc = self.contact_scene()
-        q, qp = _d(qpos)
-        if q.shape != (self.nq,):
-            raise MopaError(f"state has dimension {q.shape}, expected nq={self.nq}")
+        q, qp = self._state(qpos)
         K = int(max_pairs)
-        cl, cnt = C.c_double(0.0), C.c_int32(0)
-        pair = np.full(max(K, 1), -1, dtype=np.int32)
-        dist = np.full(max(K, 1), MOPA_FAR)
+        cl = C.c_double(0.0)
+        cnt, pair, dist = self._record_bufs(K)
         check(lib().mopa_proximity_state(sc._h, qp, float(band), K, C.byref(cl), C.byref(cnt), pair.ctypes.data_as(_ip), dist.ctypes.data_as(_dp)))
         return float(cl.value), int(cnt.value), pair, dist
 
@@ -805,11 +805,7 @@ class Scene:
         dist <= band, nearest first.  Distances of disjoint box-box, cylinder and mesh pairs are conservative -- never more than 1e-6
         above the true distance, below it by a shortfall that grows with band ("Proximity report")."""
         cl, n, pair, dist = self.proximity_state_raw(qpos, band, max_pairs)
-        m = self.model
-        g = np.asarray(m.pair_geom).reshape(-1, 2)
-        name = lambda k: m.all_geom_names[int(m.geom_mjid[int(k)])]
-        k = min(n, len(pair))
-        return cl, [(name(g[p, 0]), name(g[p, 1]), float(d)) for p, d in zip(pair[:k], dist[:k])]
+        return cl, _pair_names(self.model, pair, dist, n)
 
     def motion_report_raw(self, qpos_a, qpos_b, max_contacts: int = 0):
         """(valid, n_states, first_bad, last_valid_t, last_valid_q [na], first_bad_q [na], blockers) of one segment: the
@@ -817,17 +813,12 @@ class Scene:
         qpos_b, the passive entries taken from qpos_a.  blockers: None with max_contacts = 0, else (count, pair [K] int32,
         dist [K]) of the state first_bad_q at the contact threshold, pair indices into `model.pair_geom` -- in the same call on a
         scene that holds the whole pair list, else through the sibling `contact_scene()` (the same bytes)."""
-        a, ap = _d(qpos_a)
-        b, bp = _d(qpos_b)
-        if a.shape != (self.nq,) or b.shape != (self.nq,):
-            raise MopaError(f"states have dimensions {a.shape} / {b.shape}, expected nq={self.nq}")
+        (a, ap), (b, bp) = self._state(qpos_a), self._state(qpos_b)
         K = int(max_contacts)
         chained = K != 0 and self.contact_scene() is self
         v, n, fb, t = C.c_int32(0), C.c_int32(0), C.c_int32(0), C.c_double(0.0)
         lvq, fbq = np.zeros(self.na), np.zeros(self.na)
-        cnt = C.c_int32(0)
-        pair = np.full(max(K, 1), -1, dtype=np.int32)
-        dist = np.full(max(K, 1), MOPA_FAR)
+        cnt, pair, dist = self._record_bufs(K)
         if K < 0:
             raise MopaError("max_contacts must be >= 0")
         check(lib().mopa_motion_report(self._h, ap, bp, C.byref(v), C.byref(n), C.byref(fb), C.byref(t), lvq.ctypes.data_as(_dp), fbq.ctypes.data_as(_dp),
@@ -850,15 +841,11 @@ class Scene:
         and `blockers`: None with max_contacts = 0, else the pairs that make s_first_bad invalid as (geom1_name, geom2_name,
         dist), at most max_contacts of them in `model.pair_geom` order (the style of `contacts_state`), and `n_blockers`, their
         uncapped number.  DESIGN.md section 4, "Motion report"."""
-        m = self.model
         valid, n, fb, t, lvq, fbq, blk = self.motion_report_raw(qpos_a, qpos_b, max_contacts)
         out = {"valid": valid, "n_states": n, "first_bad": fb, "last_valid_t": t, "last_valid_q": lvq, "first_bad_q": fbq, "blockers": None}
         if blk is not None:
-            g = np.asarray(m.pair_geom).reshape(-1, 2)
-            name = lambda k: m.all_geom_names[int(m.geom_mjid[int(k)])]
             cnt, pair, dist = blk
-            k = min(cnt, len(pair))
-            out["blockers"] = [(name(g[p, 0]), name(g[p, 1]), float(d)) for p, d in zip(pair[:k], dist[:k])]
+            out["blockers"] = _pair_names(self.model, pair, dist, cnt)
             out["n_blockers"] = cnt
         return out
 
@@ -869,10 +856,7 @@ class Scene:
         if self.glue is not None:
             raise NotImplementedError("the clearance report of a glued scene")
         sc = self.contact_scene()
-        a, ap = _d(qpos_a)
-        b, bp = _d(qpos_b)
-        if a.shape != (self.nq,) or b.shape != (self.nq,):
-            raise MopaError(f"states have dimensions {a.shape} / {b.shape}, expected nq={self.nq}")
+        (a, ap), (b, bp) = self._state(qpos_a), self._state(qpos_b)
         cl, t, ec = C.c_double(0.0), C.c_double(0.0), C.c_double(0.0)
         n, near, k, pair = C.c_int32(0), C.c_int32(0), C.c_int32(0), C.c_int32(-1)
         q_min = np.zeros(self.na)
@@ -889,11 +873,8 @@ class Scene:
         `pair_min` (its index into `model.pair_geom`, -1), `end_clearance` (that of qpos_b) and `q_min` (active coordinates [na] of
         s_k_min; qpos_b's when k_min == 0).  DESIGN.md section 4, "Clearance report"."""
         cl, n, near, k, t, pair, ec, q_min = self.motion_clearance_raw(qpos_a, qpos_b, band)
-        m = self.model
-        g = np.asarray(m.pair_geom).reshape(-1, 2)
-        name = lambda j: m.all_geom_names[int(m.geom_mjid[int(j)])]
         return {"clearance": cl, "n_states": n, "n_near": near, "k_min": k, "t_min": t, "pair_min": pair,
-                "pair": (name(g[pair, 0]), name(g[pair, 1])) if pair >= 0 else None, "end_clearance": ec, "q_min": q_min}
+                "pair": _pair_names(self.model, [pair], [cl], 1)[0][:2] if pair >= 0 else None, "end_clearance": ec, "q_min": q_min}
 
     def debug_pair_dist(self, qpos):
         q, qp = _d(qpos)

@@ -195,10 +195,9 @@ def pair_geom_ids(model, pair) -> np.ndarray:
     return out
 
 
-def geom_frames(types, recs, stream=None):
-    """mopa_geom_frames_batch: M posed primitive pairs, one lane each -- types [M, 2] int32 (MuJoCo geom type codes, either
-    order), recs [M, 2, 15] float64 (pos[3] mat[9] size[3] per geom), both contiguous on the GPU -> [M, 7] = dist, normal[3],
-    pos[3]; the bits of `_lib.geom_frames_host`.  Meshes are not served at this level."""
+def _pair_batch(types, recs):
+    """The argument rule of the pair-level entry points: types [M, 2] int32 and recs [M, 2, 15] float64, both contiguous on
+    the GPU -> (M, the device ordinal of recs)"""
     torch = _torch()
     _check_f64(recs, "recs")
     if types.dtype != torch.int32 or not types.is_cuda or not types.is_contiguous() or types.dim() != 2 or types.shape[1] != 2:
@@ -206,9 +205,17 @@ def geom_frames(types, recs, stream=None):
     M = types.shape[0]
     if recs.numel() != M * 30:
         raise _lib.MopaError(f"recs must have shape [{M}, 2, 15], got {tuple(recs.shape)}")
+    return M, int(recs.device.index if recs.device.index is not None else torch.cuda.current_device())
+
+
+def geom_frames(types, recs, stream=None):
+    """mopa_geom_frames_batch: M posed primitive pairs, one lane each -- types [M, 2] int32 (MuJoCo geom type codes, either
+    order), recs [M, 2, 15] float64 (pos[3] mat[9] size[3] per geom), both contiguous on the GPU -> [M, 7] = dist, normal[3],
+    pos[3]; the bits of `_lib.geom_frames_host`.  Meshes are not served at this level."""
+    torch = _torch()
+    M, dev = _pair_batch(types, recs)
     out = torch.empty(M, 7, dtype=torch.float64, device=recs.device)
-    dev = recs.device.index if recs.device.index is not None else torch.cuda.current_device()
-    _lib.check(_lib.lib().mopa_geom_frames_batch(int(dev), M, _ptr(types), _ptr(recs), _ptr(out), _stream_handle(stream)))
+    _lib.check(_lib.lib().mopa_geom_frames_batch(dev, M, _ptr(types), _ptr(recs), _ptr(out), _stream_handle(stream)))
     return out
 
 
@@ -216,19 +223,13 @@ def geom_sep(types, recs, band: float, mesh_verts=None, stream=None):
     """mopa_geom_sep_batch: M posed pairs, one lane each, as `geom_frames` takes them -> [M] band-limited signed distances, the
     bits of `_lib.geom_sep_host`; mesh_verts [n, 3] (float64, on the GPU): the hull of every geom of type 7"""
     torch = _torch()
-    _check_f64(recs, "recs")
-    if types.dtype != torch.int32 or not types.is_cuda or not types.is_contiguous() or types.dim() != 2 or types.shape[1] != 2:
-        raise _lib.MopaError("types must be a contiguous int32 GPU tensor [M, 2]")
-    M = types.shape[0]
-    if recs.numel() != M * 30:
-        raise _lib.MopaError(f"recs must have shape [{M}, 2, 15], got {tuple(recs.shape)}")
+    M, dev = _pair_batch(types, recs)
     nvert = 0
     if mesh_verts is not None:
         _check_f64(mesh_verts, "mesh_verts", 3)
         nvert = mesh_verts.shape[0]
     out = torch.empty(M, dtype=torch.float64, device=recs.device)
-    dev = recs.device.index if recs.device.index is not None else torch.cuda.current_device()
-    _lib.check(_lib.lib().mopa_geom_sep_batch(int(dev), M, _ptr(types), _ptr(recs), _ptr(mesh_verts) if nvert else None, nvert, float(band), _ptr(out),
+    _lib.check(_lib.lib().mopa_geom_sep_batch(dev, M, _ptr(types), _ptr(recs), _ptr(mesh_verts) if nvert else None, nvert, float(band), _ptr(out),
                                               _stream_handle(stream)))
     return out
 
@@ -238,17 +239,12 @@ def geom_manifolds(types, recs, point_cutoff: float = 0.0, max_points: int = 4, 
     normal[3], dist; npoint [M] int32; points [M, P, 4] = pos[3], dist_i): the bits of `_lib.geom_manifolds_host`.  Meshes are
     not served at this level."""
     torch = _torch()
-    _check_f64(recs, "recs")
-    if types.dtype != torch.int32 or not types.is_cuda or not types.is_contiguous() or types.dim() != 2 or types.shape[1] != 2:
-        raise _lib.MopaError("types must be a contiguous int32 GPU tensor [M, 2]")
-    M, P = types.shape[0], int(max_points)
-    if recs.numel() != M * 30:
-        raise _lib.MopaError(f"recs must have shape [{M}, 2, 15], got {tuple(recs.shape)}")
+    M, dev = _pair_batch(types, recs)
+    P = int(max_points)
     nd = torch.empty(M, 4, dtype=torch.float64, device=recs.device)
     npoint = torch.empty(M, dtype=torch.int32, device=recs.device)
     pts = torch.empty(M, max(P, 1), 4, dtype=torch.float64, device=recs.device)
-    dev = recs.device.index if recs.device.index is not None else torch.cuda.current_device()
-    _lib.check(_lib.lib().mopa_geom_manifolds_batch(int(dev), M, _ptr(types), _ptr(recs), float(point_cutoff), P, _ptr(nd), _ptr(npoint), _ptr(pts),
+    _lib.check(_lib.lib().mopa_geom_manifolds_batch(dev, M, _ptr(types), _ptr(recs), float(point_cutoff), P, _ptr(nd), _ptr(npoint), _ptr(pts),
                                                     _stream_handle(stream)))
     return nd, npoint, pts
 
@@ -275,6 +271,27 @@ class BatchPlanner:
         self.na = scene.na
         self.nq = scene.nq
 
+    def _state_batch(self, q_active, qpos_env, samples_per_env, name="q_active"):
+        """The one argument rule of a batch of states: q_active [N, na] and qpos_env [rows, nq] contiguous float64 on the GPU,
+        samples_per_env >= 1 (None: N // rows) with ceil(N / samples_per_env) <= rows -> (N, samples_per_env)"""
+        _check_f64(q_active, name, self.na)
+        _check_f64(qpos_env, "qpos_env", self.nq)
+        N, rows = q_active.shape[0], qpos_env.shape[0]
+        spe = int(samples_per_env) if samples_per_env is not None else max(1, N // max(1, rows))
+        if spe <= 0:
+            raise _lib.MopaError("samples_per_env must be >= 1")
+        if (N + spe - 1) // spe > rows:
+            raise _lib.MopaError("qpos_env has fewer rows than ceil(N / samples_per_env)")
+        return N, spe
+
+    def _segment_batch(self, qa, qb, qpos_env, samples_per_env):
+        """... and of a batch of segments qa[i] -> qb[i]: `_state_batch` of qa, and qb as long as qa"""
+        N, spe = self._state_batch(qa, qpos_env, samples_per_env, "qa")
+        _check_f64(qb, "qb", self.na)
+        if qb.shape[0] != N:
+            raise _lib.MopaError("qa and qb must hold the same number of segments")
+        return N, spe
+
     # valid[i] for state i = qpos_env[i // samples_per_env] with active entries <- q_active[i]
     def is_valid(self, q_active, qpos_env, samples_per_env: Optional[int] = None, want_min_dist: bool = False,
                  out=None, stream=None, guard: bool = False, n_dev=None):
@@ -284,12 +301,7 @@ class BatchPlanner:
         (a device-side range test, one host read of the count; off on the hot paths, whose states are sampled / clipped inside
         the ranges -- `Scene.is_valid_state`, the reference's isValidState, always guards)."""
         torch = _torch()
-        _check_f64(q_active, "q_active", self.na)
-        _check_f64(qpos_env, "qpos_env", self.nq)
-        N = q_active.shape[0]
-        spe = int(samples_per_env) if samples_per_env is not None else max(1, N // max(1, qpos_env.shape[0]))
-        if N and (N + spe - 1) // spe > qpos_env.shape[0]:
-            raise _lib.MopaError("qpos_env has fewer rows than ceil(N / samples_per_env)")
+        N, spe = self._state_batch(q_active, qpos_env, samples_per_env)
         valid = out if out is not None else torch.empty(N, dtype=torch.uint8, device=q_active.device)
         md = torch.empty(N, dtype=torch.float64, device=q_active.device) if want_min_dist else None
         if n_dev is not None:
@@ -342,45 +354,30 @@ class BatchPlanner:
         DESIGN.md section 4, "Contact manifolds", PARITY UNPINNED).  With both switches on the report runs once per switch and
         writes the same bytes both times."""
         torch = _torch()
-        _check_f64(q_active, "q_active", self.na)
-        _check_f64(qpos_env, "qpos_env", self.nq)
-        N = q_active.shape[0]
-        K = int(max_contacts)
-        spe = int(samples_per_env) if samples_per_env is not None else max(1, N // max(1, qpos_env.shape[0]))
-        if N and (N + spe - 1) // spe > qpos_env.shape[0]:
-            raise _lib.MopaError("qpos_env has fewer rows than ceil(N / samples_per_env)")
-        sc = self.scene.contact_scene()
+        N, spe = self._state_batch(q_active, qpos_env, samples_per_env)
+        K, P = int(max_contacts), int(max_points)
+        k1, p1 = max(K, 1), max(P, 1)
+        h = self.scene.contact_scene().handle
         dev = q_active.device
+        f64 = lambda *shape: torch.empty(N, k1, *shape, dtype=torch.float64, device=dev)
         count = torch.empty(N, dtype=torch.int32, device=dev)
-        pair = torch.empty(N, max(K, 1), dtype=torch.int32, device=dev)
-        dist = torch.empty(N, max(K, 1), dtype=torch.float64, device=dev)
+        pair = torch.empty(N, k1, dtype=torch.int32, device=dev)
+        dist = f64()
+        normal = f64(3) if (frames or manifold) else None
+        pos = f64(3) if frames else None
+        npoint = torch.empty(N, k1, dtype=torch.int32, device=dev) if manifold else None
+        pdist, ppos = (f64(p1), f64(p1, 3)) if manifold else (None, None)
+        cut = float(self.scene.contact_threshold if cutoff is None else cutoff)
+        states = (h, _ptr(q_active), _ptr(qpos_env), N, spe)
+        rows = (_ptr(count), _ptr(pair), _ptr(dist))
+        sh = _stream_handle(stream)
+        if frames:      # (the frames call first: both write the same normal bits, the manifold's stay)
+            _lib.check(_lib.lib().mopa_contact_frames_batch(*states, cut, K, *rows, _ptr(normal), _ptr(pos), sh))
         if manifold:
-            P = int(max_points)
-            normal = torch.empty(N, max(K, 1), 3, dtype=torch.float64, device=dev)
-            npoint = torch.empty(N, max(K, 1), dtype=torch.int32, device=dev)
-            pdist = torch.empty(N, max(K, 1), max(P, 1), dtype=torch.float64, device=dev)
-            ppos = torch.empty(N, max(K, 1), max(P, 1), 3, dtype=torch.float64, device=dev)
-            cut = float(self.scene.contact_threshold if cutoff is None else cutoff)
-            pos = None
-            if frames:      # (the frames call first: both write the same normal bits, the manifold's stay)
-                pos = torch.empty(N, max(K, 1), 3, dtype=torch.float64, device=dev)
-                _lib.check(_lib.lib().mopa_contact_frames_batch(sc.handle, _ptr(q_active), _ptr(qpos_env), N, spe, cut, K, _ptr(count), _ptr(pair), _ptr(dist),
-                                                                _ptr(normal), _ptr(pos), _stream_handle(stream)))
-            _lib.check(_lib.lib().mopa_contact_manifolds_batch(sc.handle, _ptr(q_active), _ptr(qpos_env), N, spe, cut, float(point_cutoff), K, P, _ptr(count),
-                                                               _ptr(pair), _ptr(dist), _ptr(normal), _ptr(npoint), _ptr(pdist), _ptr(ppos),
-                                                               _stream_handle(stream)))
-            return ContactReport(count, pair, dist, self.scene.model, normal, pos, npoint, pdist, ppos)
-        if frames:
-            normal = torch.empty(N, max(K, 1), 3, dtype=torch.float64, device=dev)
-            pos = torch.empty(N, max(K, 1), 3, dtype=torch.float64, device=dev)
-            _lib.check(_lib.lib().mopa_contact_frames_batch(sc.handle, _ptr(q_active), _ptr(qpos_env), N, spe,
-                                                            float(self.scene.contact_threshold if cutoff is None else cutoff), K,
-                                                            _ptr(count), _ptr(pair), _ptr(dist), _ptr(normal), _ptr(pos), _stream_handle(stream)))
-            return ContactReport(count, pair, dist, self.scene.model, normal, pos)
-        _lib.check(_lib.lib().mopa_contacts_batch(sc.handle, _ptr(q_active), _ptr(qpos_env), N, spe,
-                                                  float(self.scene.contact_threshold if cutoff is None else cutoff), K,
-                                                  _ptr(count), _ptr(pair), _ptr(dist), _stream_handle(stream)))
-        return ContactReport(count, pair, dist, self.scene.model)
+            _lib.check(_lib.lib().mopa_contact_manifolds_batch(*states, cut, float(point_cutoff), K, P, *rows, _ptr(normal), _ptr(npoint), _ptr(pdist), _ptr(ppos), sh))
+        if not (frames or manifold):
+            _lib.check(_lib.lib().mopa_contacts_batch(*states, cut, K, *rows, sh))
+        return ContactReport(count, pair, dist, self.scene.model, normal, pos, npoint, pdist, ppos)
 
     def proximity(self, q_active, qpos_env, samples_per_env: Optional[int] = None, band: float = 0.05, max_pairs: int = 8,
                   stream=None) -> ProximityReport:
@@ -393,13 +390,8 @@ class BatchPlanner:
         if self.scene.glue is not None:
             raise NotImplementedError("the proximity report of a glued scene")
         torch = _torch()
-        _check_f64(q_active, "q_active", self.na)
-        _check_f64(qpos_env, "qpos_env", self.nq)
-        N = q_active.shape[0]
+        N, spe = self._state_batch(q_active, qpos_env, samples_per_env)
         K = int(max_pairs)
-        spe = int(samples_per_env) if samples_per_env is not None else max(1, N // max(1, qpos_env.shape[0]))
-        if N and (N + spe - 1) // spe > qpos_env.shape[0]:
-            raise _lib.MopaError("qpos_env has fewer rows than ceil(N / samples_per_env)")
         sc = self.scene.contact_scene()
         dev = q_active.device
         clearance = torch.empty(N, dtype=torch.float64, device=dev)
@@ -440,11 +432,7 @@ class BatchPlanner:
 
     def check_motion(self, qa, qb, qpos_env, samples_per_env: Optional[int] = None, stream=None):
         torch = _torch()
-        _check_f64(qa, "qa", self.na)
-        _check_f64(qb, "qb", self.na)
-        _check_f64(qpos_env, "qpos_env", self.nq)
-        N = qa.shape[0]
-        spe = int(samples_per_env) if samples_per_env is not None else max(1, N // max(1, qpos_env.shape[0]))
+        N, spe = self._segment_batch(qa, qb, qpos_env, samples_per_env)
         valid = torch.empty(N, dtype=torch.uint8, device=qa.device)
         _lib.check(_lib.lib().mopa_check_motion_batch(self.scene.handle, _ptr(qa), _ptr(qb), _ptr(qpos_env), N, spe,
                                                       _ptr(valid), _stream_handle(stream)))
@@ -460,17 +448,10 @@ class BatchPlanner:
         scene that holds the whole pair list, else on `Scene.contact_scene()` behind it.  The large-batch form
         (`Scene.motion_kernel`) synchronises the stream once per call, as `check_motion`'s does."""
         torch = _torch()
-        _check_f64(qa, "qa", self.na)
-        _check_f64(qb, "qb", self.na)
-        _check_f64(qpos_env, "qpos_env", self.nq)
-        N, K = qa.shape[0], int(max_contacts)
-        if qb.shape[0] != N:
-            raise _lib.MopaError("qa and qb must hold the same number of segments")
+        N, spe = self._segment_batch(qa, qb, qpos_env, samples_per_env)
+        K = int(max_contacts)
         if K < 0:
             raise _lib.MopaError("max_contacts must be >= 0")
-        spe = int(samples_per_env) if samples_per_env is not None else max(1, N // max(1, qpos_env.shape[0]))
-        if N and (N + spe - 1) // spe > qpos_env.shape[0]:
-            raise _lib.MopaError("qpos_env has fewer rows than ceil(N / samples_per_env)")
         dev = qa.device
         valid = torch.empty(N, dtype=torch.uint8, device=dev)
         n_states = torch.empty(N, dtype=torch.int32, device=dev)
@@ -509,15 +490,7 @@ class BatchPlanner:
         if self.scene.glue is not None:
             raise NotImplementedError("the clearance report of a glued scene")
         torch = _torch()
-        _check_f64(qa, "qa", self.na)
-        _check_f64(qb, "qb", self.na)
-        _check_f64(qpos_env, "qpos_env", self.nq)
-        N = qa.shape[0]
-        if qb.shape[0] != N:
-            raise _lib.MopaError("qa and qb must hold the same number of segments")
-        spe = int(samples_per_env) if samples_per_env is not None else max(1, N // max(1, qpos_env.shape[0]))
-        if N and (spe <= 0 or (N + spe - 1) // spe > qpos_env.shape[0]):
-            raise _lib.MopaError("qpos_env has fewer rows than ceil(N / samples_per_env)")
+        N, spe = self._segment_batch(qa, qb, qpos_env, samples_per_env)
         if not (math.isfinite(float(band)) and float(band) >= 0.0):
             raise _lib.MopaError("band must be finite and >= 0")
         sc = self.scene.contact_scene()

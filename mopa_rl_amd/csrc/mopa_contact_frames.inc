@@ -57,9 +57,41 @@ __global__ __launch_bounds__(256) void k_geom_frames(long long M, const int32_t 
     geom_frame_pair<false>(types[2 * i], recs + i * 30, types[2 * i + 1], recs + i * 30 + 15, nullptr, out + i * 7);
 }
 
-static void contact_frames_register_lds() {
-    for (const void *k : {(const void *)k_contact_frames<false>, (const void *)k_contact_frames<true>})
-        (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLdsBytes);
+static const LdsKernels kContactFramesLds({(const void *)k_contact_frames<false>, (const void *)k_contact_frames<true>});
+
+// The launch of a kernel behind k_contact_rows (k_contact_frames, k_contact_manifolds): a wave per state, the scene's own LDS;
+// `args`: the kernel's arguments from q_active on.
+template <class Kern, class... Args>
+static int contact_tail_launch(MopaScene *S, const char *what, Kern kern, int64_t N, void *stream, Args... args) {
+    ON_DEVICE(S->device);
+    if (S->lds_bytes > kMaxLdsBytes) return fail(MOPA_ERR_LIMIT, std::string(what) + ": the scene does not fit LDS");
+    hipLaunchKernelGGL(kern, dim3(grid_for(S, N)), dim3(kBlock), S->lds_bytes, (hipStream_t)stream, S->hdr, S->d_dbl, S->d_int, (const int32_t *)S->d_pair_slot,
+                       S->npair_model, args...);
+    HIP_TRY(hipGetLastError());
+    return MOPA_OK;
+}
+
+// The pair-level entry points (mopa_geom_{frames,sep,manifolds}_{batch,host}): M posed pairs as types [M,2] and recs [M,2,15], `outs_ok`:
+// every output buffer is there; a hull as nvert vertices at mesh_verts (none: 0, null).
+static int pair_batch_rule(int64_t M, const int32_t *types, const double *recs, bool outs_ok, const double *mesh_verts = nullptr, int32_t nvert = 0) {
+    if (M < 0 || (M > 0 && (!types || !recs || !outs_ok)) || nvert < 0 || (nvert > 0 && !mesh_verts)) return fail(MOPA_ERR_INVALID_ARG, "null argument / negative count");
+    return MOPA_OK;
+}
+// ... the device rule of a _batch form and its launch: one lane per pair, 256 lanes per workgroup; `args`: the kernel's arguments behind M
+template <class Kern, class... Args>
+static int pair_launch(int32_t device, Kern kern, int64_t M, void *stream, Args... args) {
+    if (device < 0 || device >= mopa_device_count()) return fail(MOPA_ERR_INVALID_ARG, "device ordinal out of range");
+    if (M == 0) return MOPA_OK;
+    ON_DEVICE(device);
+    hipLaunchKernelGGL(kern, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (long long)M, args...);
+    HIP_TRY(hipGetLastError());
+    return MOPA_OK;
+}
+// ... and in the _host forms a mesh as the second geom: rm = its record r2 with the size slots replaced by where the hull lives
+// (offset 0 of mesh_verts, nvert vertices)
+static void pair_mesh_rec(const double *r2, int32_t nvert, double *rm /*[15]*/) {
+    std::memcpy(rm, r2, 15 * sizeof(double));
+    rm[GO_SIZE] = 0.0; rm[GO_SIZE + 1] = (double)nvert; rm[GO_SIZE + 2] = 0.0;
 }
 
 extern "C" int mopa_contact_frames_batch(MopaScene *S, const double *q_active, const double *qpos_env, int64_t N, int64_t samples_per_env,
@@ -69,13 +101,8 @@ extern "C" int mopa_contact_frames_batch(MopaScene *S, const double *q_active, c
     // (argument rules and status codes: mopa_contacts_batch's)
     const int rc = mopa_contacts_batch(S, q_active, qpos_env, N, samples_per_env, cutoff, K, count, pair, dist, stream);
     if (rc != MOPA_OK || N == 0) return rc;
-    ON_DEVICE(S->device);
-    if (S->lds_bytes > kMaxLdsBytes) return fail(MOPA_ERR_LIMIT, "contact frames: the scene does not fit LDS");
-    hipLaunchKernelGGL(S->hdr.has_mesh ? k_contact_frames<true> : k_contact_frames<false>, dim3(grid_for(S, N)), dim3(kBlock), S->lds_bytes, (hipStream_t)stream,
-                       S->hdr, S->d_dbl, S->d_int, (const int32_t *)S->d_pair_slot, S->npair_model, q_active, qpos_env, (long long)N, (long long)samples_per_env,
-                       (int)K, (const int32_t *)count, (const int32_t *)pair, normal, pos);
-    HIP_TRY(hipGetLastError());
-    return MOPA_OK;
+    return contact_tail_launch(S, "contact frames", S->hdr.has_mesh ? k_contact_frames<true> : k_contact_frames<false>, N, stream, q_active, qpos_env, (long long)N,
+                               (long long)samples_per_env, (int)K, (const int32_t *)count, (const int32_t *)pair, normal, pos);
 }
 
 extern "C" int mopa_contact_frames_state(MopaScene *S, const double *qpos_host, double cutoff, int32_t K, int32_t *count, int32_t *pair, double *dist,
@@ -86,49 +113,31 @@ extern "C" int mopa_contact_frames_state(MopaScene *S, const double *qpos_host, 
     ON_DEVICE(S->device);
     int rc = upload_state(S, qpos_host);
     if (rc) return rc;
-    void *buf = nullptr;
-    const size_t nK = (size_t)K;
-    const size_t off_dist = 0, off_normal = nK * sizeof(double), off_pos = off_normal + 3 * nK * sizeof(double), off_pair = off_pos + 3 * nK * sizeof(double),
-                 off_count = off_pair + nK * sizeof(int32_t);
-    HIP_TRY(hipMalloc(&buf, off_count + sizeof(int32_t)));
-    unsigned char *b = static_cast<unsigned char *>(buf);
-    rc = mopa_contact_frames_batch(S, S->d_q + S->nq, S->d_q, 1, 1, cutoff, K, reinterpret_cast<int32_t *>(b + off_count), reinterpret_cast<int32_t *>(b + off_pair),
-                                   reinterpret_cast<double *>(b + off_dist), reinterpret_cast<double *>(b + off_normal), reinterpret_cast<double *>(b + off_pos), nullptr);
-    hipError_t e = hipSuccess;
-    if (rc == MOPA_OK) {
-        e = hipMemcpy(dist, b + off_dist, nK * sizeof(double), hipMemcpyDeviceToHost);
-        if (e == hipSuccess) e = hipMemcpy(normal, b + off_normal, 3 * nK * sizeof(double), hipMemcpyDeviceToHost);
-        if (e == hipSuccess) e = hipMemcpy(pos, b + off_pos, 3 * nK * sizeof(double), hipMemcpyDeviceToHost);
-        if (e == hipSuccess) e = hipMemcpy(pair, b + off_pair, nK * sizeof(int32_t), hipMemcpyDeviceToHost);
-        if (e == hipSuccess) e = hipMemcpy(count, b + off_count, sizeof(int32_t), hipMemcpyDeviceToHost);
-    }
-    (void)hipFree(buf);
+    Staging g;
+    const auto f_dist = g.dbl(K), f_normal = g.dbl(3 * (size_t)K), f_pos = g.dbl(3 * (size_t)K);
+    const auto f_pair = g.i32(K), f_count = g.i32(1);
+    HIP_TRY(g.alloc());
+    rc = mopa_contact_frames_batch(S, S->d_q + S->nq, S->d_q, 1, 1, cutoff, K, g.dev(f_count), g.dev(f_pair), g.dev(f_dist), g.dev(f_normal), g.dev(f_pos), nullptr);
     if (rc != MOPA_OK) return rc;
-    HIP_TRY(e);
+    HIP_TRY(g.fetch());
+    g.out(f_dist, dist); g.out(f_normal, normal); g.out(f_pos, pos); g.out(f_pair, pair); g.out(f_count, count);
     return MOPA_OK;
 }
 
 extern "C" int mopa_geom_frames_batch(int32_t device, int64_t M, const int32_t *types, const double *recs, double *out, void *stream) {
-    if (M < 0 || (M > 0 && (!types || !recs || !out))) return fail(MOPA_ERR_INVALID_ARG, "null argument / negative count");
-    if (device < 0 || device >= mopa_device_count()) return fail(MOPA_ERR_INVALID_ARG, "device ordinal out of range");
-    if (M == 0) return MOPA_OK;
-    ON_DEVICE(device);
-    hipLaunchKernelGGL(k_geom_frames, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (long long)M, types, recs, out);
-    HIP_TRY(hipGetLastError());
-    return MOPA_OK;
+    if (const int rc = pair_batch_rule(M, types, recs, out != nullptr)) return rc;
+    return pair_launch(device, k_geom_frames, M, stream, types, recs, out);
 }
 
 // The host compile of the same functions: the sequential form the kernels must match bit for bit.  No GPU, no HIP call.
 extern "C" int mopa_geom_frames_host(int64_t M, const int32_t *types, const double *recs, const double *mesh_verts, int32_t nvert, double *out) {
-    if (M < 0 || (M > 0 && (!types || !recs || !out)) || nvert < 0 || (nvert > 0 && !mesh_verts)) return fail(MOPA_ERR_INVALID_ARG, "null argument / negative count");
+    if (const int rc = pair_batch_rule(M, types, recs, out != nullptr, mesh_verts, nvert)) return rc;
     for (int64_t i = 0; i < M; i++) {
         const int t1 = types[2 * i], t2 = types[2 * i + 1];
         const double *r1 = recs + i * 30, *r2 = r1 + 15;
         if (t2 == G_MESH && nvert > 0) {
-            // a mesh as the second geom: its record's size slots are replaced by where the hull lives (offset 0 of mesh_verts, nvert vertices)
             double rm[15];
-            std::memcpy(rm, r2, sizeof(rm));
-            rm[GO_SIZE] = 0.0; rm[GO_SIZE + 1] = (double)nvert; rm[GO_SIZE + 2] = 0.0;
+            pair_mesh_rec(r2, nvert, rm);
             geom_frame_pair<true>(t1, r1, t2, rm, mesh_verts, out + i * 7);
         } else {
             geom_frame_pair<false>(t1, r1, t2, r2, nullptr, out + i * 7);

@@ -74,10 +74,7 @@ __global__ __launch_bounds__(256) void k_geom_manifolds(long long M, const int32
     npoint[i] = np;
 }
 
-static void contact_manifolds_register_lds() {
-    for (const void *k : {(const void *)k_contact_manifolds<false>, (const void *)k_contact_manifolds<true>})
-        (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLdsBytes);
-}
+static const LdsKernels kContactManifoldsLds({(const void *)k_contact_manifolds<false>, (const void *)k_contact_manifolds<true>});
 
 static int manifold_args_ok(int32_t P, double point_cutoff) {
     if (P < 1 || P > kManifoldMax) return fail(MOPA_ERR_INVALID_ARG, "max_points must be 1 .. 8");
@@ -96,13 +93,9 @@ extern "C" int mopa_contact_manifolds_batch(MopaScene *S, const double *q_active
     // (argument rules and status codes: mopa_contacts_batch's)
     rc = mopa_contacts_batch(S, q_active, qpos_env, N, samples_per_env, cutoff, K, count, pair, dist, stream);
     if (rc != MOPA_OK || N == 0) return rc;
-    ON_DEVICE(S->device);
-    if (S->lds_bytes > kMaxLdsBytes) return fail(MOPA_ERR_LIMIT, "contact manifolds: the scene does not fit LDS");
-    hipLaunchKernelGGL(S->hdr.has_mesh ? k_contact_manifolds<true> : k_contact_manifolds<false>, dim3(grid_for(S, N)), dim3(kBlock), S->lds_bytes,
-                       (hipStream_t)stream, S->hdr, S->d_dbl, S->d_int, (const int32_t *)S->d_pair_slot, S->npair_model, q_active, qpos_env, (long long)N,
-                       (long long)samples_per_env, (int)K, (int)P, point_cutoff, (const int32_t *)count, (const int32_t *)pair, normal, npoint, point_dist, point_pos);
-    HIP_TRY(hipGetLastError());
-    return MOPA_OK;
+    return contact_tail_launch(S, "contact manifolds", S->hdr.has_mesh ? k_contact_manifolds<true> : k_contact_manifolds<false>, N, stream, q_active, qpos_env,
+                               (long long)N, (long long)samples_per_env, (int)K, (int)P, point_cutoff, (const int32_t *)count, (const int32_t *)pair, normal, npoint,
+                               point_dist, point_pos);
 }
 
 extern "C" int mopa_contact_manifolds_state(MopaScene *S, const double *qpos_host, double cutoff, double point_cutoff, int32_t K, int32_t P, int32_t *count,
@@ -115,53 +108,32 @@ extern "C" int mopa_contact_manifolds_state(MopaScene *S, const double *qpos_hos
     ON_DEVICE(S->device);
     rc = upload_state(S, qpos_host);
     if (rc) return rc;
-    void *buf = nullptr;
-    const size_t nK = (size_t)K, nP = (size_t)P, D = sizeof(double);
-    // doubles first (dist, normal, point_dist, point_pos), then the int32 arrays (pair, npoint, count)
-    const size_t off_dist = 0, off_normal = nK * D, off_pd = off_normal + 3 * nK * D, off_pp = off_pd + nK * nP * D, off_pair = off_pp + 3 * nK * nP * D,
-                 off_np = off_pair + nK * sizeof(int32_t), off_count = off_np + nK * sizeof(int32_t);
-    HIP_TRY(hipMalloc(&buf, off_count + sizeof(int32_t)));
-    unsigned char *b = static_cast<unsigned char *>(buf);
-    rc = mopa_contact_manifolds_batch(S, S->d_q + S->nq, S->d_q, 1, 1, cutoff, point_cutoff, K, P, reinterpret_cast<int32_t *>(b + off_count),
-                                      reinterpret_cast<int32_t *>(b + off_pair), reinterpret_cast<double *>(b + off_dist), reinterpret_cast<double *>(b + off_normal),
-                                      reinterpret_cast<int32_t *>(b + off_np), reinterpret_cast<double *>(b + off_pd), reinterpret_cast<double *>(b + off_pp), nullptr);
-    hipError_t e = hipSuccess;
-    if (rc == MOPA_OK) {
-        e = hipMemcpy(dist, b + off_dist, nK * D, hipMemcpyDeviceToHost);
-        if (e == hipSuccess) e = hipMemcpy(normal, b + off_normal, 3 * nK * D, hipMemcpyDeviceToHost);
-        if (e == hipSuccess) e = hipMemcpy(point_dist, b + off_pd, nK * nP * D, hipMemcpyDeviceToHost);
-        if (e == hipSuccess) e = hipMemcpy(point_pos, b + off_pp, 3 * nK * nP * D, hipMemcpyDeviceToHost);
-        if (e == hipSuccess) e = hipMemcpy(pair, b + off_pair, nK * sizeof(int32_t), hipMemcpyDeviceToHost);
-        if (e == hipSuccess) e = hipMemcpy(npoint, b + off_np, nK * sizeof(int32_t), hipMemcpyDeviceToHost);
-        if (e == hipSuccess) e = hipMemcpy(count, b + off_count, sizeof(int32_t), hipMemcpyDeviceToHost);
-    }
-    (void)hipFree(buf);
+    const size_t nK = (size_t)K, nP = (size_t)P;
+    Staging g;
+    const auto f_dist = g.dbl(nK), f_normal = g.dbl(3 * nK), f_pd = g.dbl(nK * nP), f_pp = g.dbl(3 * nK * nP);
+    const auto f_pair = g.i32(nK), f_np = g.i32(nK), f_count = g.i32(1);
+    HIP_TRY(g.alloc());
+    rc = mopa_contact_manifolds_batch(S, S->d_q + S->nq, S->d_q, 1, 1, cutoff, point_cutoff, K, P, g.dev(f_count), g.dev(f_pair), g.dev(f_dist), g.dev(f_normal),
+                                      g.dev(f_np), g.dev(f_pd), g.dev(f_pp), nullptr);
     if (rc != MOPA_OK) return rc;
-    HIP_TRY(e);
+    HIP_TRY(g.fetch());
+    g.out(f_dist, dist); g.out(f_normal, normal); g.out(f_pd, point_dist); g.out(f_pp, point_pos);
+    g.out(f_pair, pair); g.out(f_np, npoint); g.out(f_count, count);
     return MOPA_OK;
 }
 
 extern "C" int mopa_geom_manifolds_batch(int32_t device, int64_t M, const int32_t *types, const double *recs, double point_cutoff, int32_t P, double *normal_dist,
                                          int32_t *npoint, double *points, void *stream) {
-    if (M < 0 || (M > 0 && (!types || !recs || !normal_dist || !npoint || !points))) return fail(MOPA_ERR_INVALID_ARG, "null argument / negative count");
-    const int rc = manifold_args_ok(P, point_cutoff);
-    if (rc != MOPA_OK) return rc;
-    if (device < 0 || device >= mopa_device_count()) return fail(MOPA_ERR_INVALID_ARG, "device ordinal out of range");
-    if (M == 0) return MOPA_OK;
-    ON_DEVICE(device);
-    hipLaunchKernelGGL(k_geom_manifolds, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (long long)M, types, recs, point_cutoff, (int)P,
-                       normal_dist, npoint, points);
-    HIP_TRY(hipGetLastError());
-    return MOPA_OK;
+    if (const int rc = pair_batch_rule(M, types, recs, normal_dist && npoint && points)) return rc;
+    if (const int rc = manifold_args_ok(P, point_cutoff)) return rc;
+    return pair_launch(device, k_geom_manifolds, M, stream, types, recs, point_cutoff, (int)P, normal_dist, npoint, points);
 }
 
 // The host compile of the same functions: the sequential form the kernels must match bit for bit.  No GPU, no HIP call.
 extern "C" int mopa_geom_manifolds_host(int64_t M, const int32_t *types, const double *recs, const double *mesh_verts, int32_t nvert, double point_cutoff, int32_t P,
                                         double *normal_dist, int32_t *npoint, double *points) {
-    if (M < 0 || (M > 0 && (!types || !recs || !normal_dist || !npoint || !points)) || nvert < 0 || (nvert > 0 && !mesh_verts))
-        return fail(MOPA_ERR_INVALID_ARG, "null argument / negative count");
-    const int rc = manifold_args_ok(P, point_cutoff);
-    if (rc != MOPA_OK) return rc;
+    if (const int rc = pair_batch_rule(M, types, recs, normal_dist && npoint && points, mesh_verts, nvert)) return rc;
+    if (const int rc = manifold_args_ok(P, point_cutoff)) return rc;
     for (int64_t i = 0; i < M; i++) {
         const int t1 = types[2 * i], t2 = types[2 * i + 1];
         const double *r1 = recs + i * 30, *r2 = r1 + 15;
@@ -169,8 +141,7 @@ extern "C" int mopa_geom_manifolds_host(int64_t M, const int32_t *types, const d
         if (t2 == G_MESH && nvert > 0) {
             // a mesh as the second geom: its record's size slots are replaced by where the hull lives, as in mopa_geom_frames_host
             double rm[15];
-            std::memcpy(rm, r2, sizeof(rm));
-            rm[GO_SIZE] = 0.0; rm[GO_SIZE + 1] = (double)nvert; rm[GO_SIZE + 2] = 0.0;
+            pair_mesh_rec(r2, nvert, rm);
             geom_manifold_pair<true>(t1, r1, t2, rm, mesh_verts, point_cutoff, P, normal_dist + i * 4, &np, points + i * P * 4);
         } else {
             geom_manifold_pair<false>(t1, r1, t2, r2, nullptr, point_cutoff, P, normal_dist + i * 4, &np, points + i * P * 4);

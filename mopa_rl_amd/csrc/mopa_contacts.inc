@@ -78,38 +78,33 @@ __global__ __launch_bounds__(kBlock) void k_contact_rows(SceneHdr h, const doubl
     tile_ctr_release(ctr, lane);
 }
 
-static void contacts_register_lds() {
-    for (const void *k : {(const void *)k_contact_rows<false>, (const void *)k_contact_rows<true>})
-        (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLdsBytes);
-}
+static const LdsKernels kContactsLds({(const void *)k_contact_rows<false>, (const void *)k_contact_rows<true>});
 
 extern "C" int mopa_contacts_batch(MopaScene *S, const double *q_active, const double *qpos_env, int64_t N, int64_t samples_per_env,
                                    double cutoff, int32_t K, int32_t *count, int32_t *pair, double *dist, void *stream) {
     if (!S || !count || !pair || !dist || (N > 0 && (!q_active || !qpos_env))) return fail(MOPA_ERR_INVALID_ARG, "null argument");
     MOPA_REFUSE_GLUED(S, "the contact report (mopa_contacts_batch)");
-    if (N < 0 || samples_per_env <= 0) return fail(MOPA_ERR_INVALID_ARG, "N < 0 or samples_per_env <= 0");
+    if (const int rc = state_batch_rule(N, samples_per_env)) return rc;
     if (!std::isfinite(cutoff) || !(cutoff < 0.0)) return fail(MOPA_ERR_INVALID_ARG, "cutoff must be finite and < 0 (the broad phase culls at zero margin)");
     if (K < 1) return fail(MOPA_ERR_INVALID_ARG, "max_contacts must be >= 1");
-    if (S->pruned && cutoff > S->hdr.thr)
-        return fail(MOPA_ERR_UNSUPPORTED, "a scene with pair_cull_radius is proven down to its contact_threshold only: cutoff > contact_threshold needs the full scene");
+    if (S->pruned && cutoff > S->hdr.thr) return refuse_pruned("cutoff > contact_threshold needs");
     if (N == 0) return MOPA_OK;
     ON_DEVICE(S->device);
     hipStream_t st = (hipStream_t)stream;
-    const int pd_off = (S->lds_bytes + 15) & ~15;
-    const size_t lds = (size_t)pd_off + (size_t)kWavesPerBlock * S->npair_model * sizeof(double);
-    if (lds > (size_t)kMaxLdsBytes) return fail(MOPA_ERR_LIMIT, "contact report: the per-wave distance arrays do not fit LDS");
+    int pd_off;
+    size_t lds;
+    int rc = pair_dist_lds(S, "contact report", &pd_off, &lds);
+    if (rc != MOPA_OK) return rc;
     StreamScratch &sc = scratch_for(S, st);
     HIP_TRY(grow(S, sc.ct_valid, (size_t)N));
     HIP_TRY(grow(S, sc.ct_md, (size_t)N * sizeof(double)));
-    int rc = ensure_report_ctr(S, sc);
+    rc = ensure_report_ctr(S, sc);
     if (rc != MOPA_OK) return rc;
     // stage 1: deepest penetration of every state
     rc = launch_is_valid(S, q_active, qpos_env, N, samples_per_env, nullptr, sc.ct_valid.as<uint8_t>(), sc.ct_md.as<double>(), stream);
     if (rc != MOPA_OK) return rc;
-    // stage 2: persistent waves (189 / 191 VGPRs: two waves per SIMD, i.e. two workgroups per CU are resident); small batches are
-    // handed out state by state, large ones in chunks of up to 64
-    const int64_t max_blocks = (int64_t)S->n_cu * 2;
-    const int64_t blocks = std::max<int64_t>(1, std::min<int64_t>((N + kWavesPerBlock - 1) / kWavesPerBlock, max_blocks));
+    // stage 2: persistent waves (189 / 191 VGPRs); small batches are handed out state by state, large ones in chunks of up to 64
+    const int64_t blocks = report_blocks(S, N);
     const int chunk = (int)std::max<int64_t>(1, std::min<int64_t>(64, N / (blocks * kWavesPerBlock * 8)));
     hipLaunchKernelGGL(S->hdr.has_mesh ? k_contact_rows<true> : k_contact_rows<false>, dim3((unsigned)blocks), dim3(kBlock), lds, st, S->hdr, S->d_dbl, S->d_int,
                        (const int32_t *)S->d_pair_model, S->npair_model, q_active, qpos_env, (long long)N, (long long)samples_per_env,
@@ -125,20 +120,13 @@ extern "C" int mopa_contacts_state(MopaScene *S, const double *qpos_host, double
     ON_DEVICE(S->device);
     int rc = upload_state(S, qpos_host);
     if (rc) return rc;
-    void *buf = nullptr;
-    const size_t off_dist = 0, off_pair = (size_t)K * sizeof(double), off_count = off_pair + (size_t)K * sizeof(int32_t);
-    HIP_TRY(hipMalloc(&buf, off_count + sizeof(int32_t)));
-    unsigned char *b = static_cast<unsigned char *>(buf);
-    rc = mopa_contacts_batch(S, S->d_q + S->nq, S->d_q, 1, 1, cutoff, K, reinterpret_cast<int32_t *>(b + off_count), reinterpret_cast<int32_t *>(b + off_pair),
-                             reinterpret_cast<double *>(b + off_dist), nullptr);
-    hipError_t e = hipSuccess;
-    if (rc == MOPA_OK) {
-        e = hipMemcpy(dist, b + off_dist, (size_t)K * sizeof(double), hipMemcpyDeviceToHost);
-        if (e == hipSuccess) e = hipMemcpy(pair, b + off_pair, (size_t)K * sizeof(int32_t), hipMemcpyDeviceToHost);
-        if (e == hipSuccess) e = hipMemcpy(count, b + off_count, sizeof(int32_t), hipMemcpyDeviceToHost);
-    }
-    (void)hipFree(buf);
+    Staging g;
+    const auto f_dist = g.dbl(K);
+    const auto f_pair = g.i32(K), f_count = g.i32(1);
+    HIP_TRY(g.alloc());
+    rc = mopa_contacts_batch(S, S->d_q + S->nq, S->d_q, 1, 1, cutoff, K, g.dev(f_count), g.dev(f_pair), g.dev(f_dist), nullptr);
     if (rc != MOPA_OK) return rc;
-    HIP_TRY(e);
+    HIP_TRY(g.fetch());
+    g.out(f_dist, dist); g.out(f_pair, pair); g.out(f_count, count);
     return MOPA_OK;
 }

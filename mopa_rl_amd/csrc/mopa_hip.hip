@@ -48,16 +48,15 @@ int mopa_fail(int code, const std::string &msg) {
     return code;
 }
 constexpr double kV5MaxReach = 32.0;        // metres: beyond this the FP32 broad phase is not used (see mopa_scene_create)
-static void plan_register_lds();            // defined with K3 (mopa_planner.inc)
-static void contacts_register_lds();        // defined with the contact report (mopa_contacts.inc)
-static void motion_report_register_lds();   // defined with the motion report (mopa_motion_report.inc)
-static void contact_frames_register_lds();  // defined with the contact frames (mopa_contact_frames.inc)
-static void contact_manifolds_register_lds();  // defined with the contact manifolds (mopa_contact_manifold.inc)
-static void proximity_register_lds();       // defined with the proximity report (mopa_proximity.inc)
-static void motion_clearance_register_lds();   // defined with the clearance report (mopa_motion_clearance.inc)
-static void k9_register_lds();              // defined with K9 path simplification (mopa_k9.inc)
-static void star_register_lds();            // defined with K3b RRT* (mopa_rrtstar.inc)
-static void k1_register_lds();              // defined with the K1 kernel table (mopa_valid_launch.inc)
+// The kernels that take more dynamic LDS than the default allows: every file that defines some adds them with a file-scope
+// `static const LdsKernels` object, next to the kernels; scene_create walks the list (null entries: holes of a kernel table).
+static std::vector<const void *> &lds_kernels() {
+    static std::vector<const void *> list;
+    return list;
+}
+struct LdsKernels {
+    LdsKernels(const std::vector<const void *> &ks) { lds_kernels().insert(lds_kernels().end(), ks.begin(), ks.end()); }
+};
 
 extern "C" const char *mopa_last_error(void) { return g_err.c_str(); }
 extern "C" const char *mopa_version(void) { return "mopa_hip 0.1.0 (gfx950)"; }
@@ -668,6 +667,7 @@ __global__ __launch_bounds__(kBlock) void k_debug_state(SceneHdr h, const double
         out_dist[p] = d;
     }
 }
+static const LdsKernels kHipLds({(const void *)k_check_motion, (const void *)k_debug_state<false>, (const void *)k_debug_state<true>});
 
 #include "mopa_valid_v2.inc"
 #include "mopa_valid_v5.inc"
@@ -915,18 +915,8 @@ static int scene_create(const MopaSceneDesc *desc, int glue_a, int glue_b, MopaS
     // allow the dynamic LDS size
     // the attribute is per function, not per scene: register the device maximum once so scenes of different sizes can
     // coexist in one process in any creation order (each launch still passes its own, checked, size)
-    for (const void *k : {(const void *)k_check_motion, (const void *)k_debug_state<false>, (const void *)k_debug_state<true>})
-        (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLdsBytes);
-    k1_register_lds();
-    plan_register_lds();
-    contacts_register_lds();
-    motion_report_register_lds();
-    contact_frames_register_lds();
-    contact_manifolds_register_lds();
-    proximity_register_lds();
-    motion_clearance_register_lds();
-    k9_register_lds();
-    star_register_lds();
+    for (const void *k : lds_kernels())
+        if (k) (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLdsBytes);
     *out = S;
     return MOPA_OK;
 }
@@ -968,6 +958,28 @@ static int grid_for(const MopaScene *S, int64_t N) {
     int64_t cap = (int64_t)S->n_cu * 8;
     return (int)std::max<int64_t>(1, std::min(blocks, cap));
 }
+// ... and of the persistent report kernels (k_contact_rows, k_proximity_rows, k_clearance_states: two waves per SIMD, i.e. two
+// workgroups per CU are resident), which pull their n work items from a counter
+static int64_t report_blocks(const MopaScene *S, int64_t n) {
+    return std::max<int64_t>(1, std::min<int64_t>((n + kWavesPerBlock - 1) / kWavesPerBlock, (int64_t)S->n_cu * 2));
+}
+// The reports' shared argument rules.  A batch of states or segments:
+static int state_batch_rule(int64_t N, int64_t samples_per_env) {
+    if (N < 0 || samples_per_env <= 0) return fail(MOPA_ERR_INVALID_ARG, "N < 0 or samples_per_env <= 0");
+    return MOPA_OK;
+}
+// a scene created with pair_cull_radius serves a report only where its pair list is proven (`needs`: what is asked beyond that)
+static int refuse_pruned(const char *needs) {
+    return fail(MOPA_ERR_UNSUPPORTED, std::string("a scene with pair_cull_radius is proven down to its contact_threshold only: ") + needs + " the full scene");
+}
+// the per-wave distance arrays of k_contact_rows / k_proximity_rows ([npair_model] doubles each) behind the scene's LDS: their
+// byte offset and the launch's LDS size
+static int pair_dist_lds(const MopaScene *S, const char *what, int *pd_off, size_t *lds) {
+    *pd_off = (S->lds_bytes + 15) & ~15;
+    *lds = (size_t)*pd_off + (size_t)kWavesPerBlock * S->npair_model * sizeof(double);
+    if (*lds > (size_t)kMaxLdsBytes) return fail(MOPA_ERR_LIMIT, std::string(what) + ": the per-wave distance arrays do not fit LDS");
+    return MOPA_OK;
+}
 
 // glue_bodies: k_glue_attach / k_glue_rows, mopa_glue_attach_batch / mopa_glue_rows_batch / mopa_scene_glue, MOPA_REFUSE_GLUED
 #include "mopa_glue.inc"
@@ -980,7 +992,7 @@ static int grid_for(const MopaScene *S, int64_t N) {
 extern "C" int mopa_check_motion_batch(MopaScene *S, const double *qa, const double *qb, const double *qpos_env, int64_t N,
                                        int64_t samples_per_env, uint8_t *valid, void *stream) {
     if (!S || !valid || (N > 0 && (!qa || !qb || !qpos_env))) return fail(MOPA_ERR_INVALID_ARG, "null argument");
-    if (N < 0 || samples_per_env <= 0) return fail(MOPA_ERR_INVALID_ARG, "N < 0 or samples_per_env <= 0");
+    if (const int rc = state_batch_rule(N, samples_per_env)) return rc;
     if (N == 0) return MOPA_OK;
     ON_DEVICE(S->device);
     hipStream_t st = (hipStream_t)stream;
@@ -999,11 +1011,17 @@ extern "C" int mopa_check_motion_batch(MopaScene *S, const double *qa, const dou
     return MOPA_OK;
 }
 
+// the active entries of a full qpos
+static std::vector<double> active_of(const MopaScene *S, const double *qpos_host) {
+    std::vector<double> act(S->na);
+    for (int a = 0; a < S->na; a++) act[a] = qpos_host[S->active_idx[a]];
+    return act;
+}
 // split a full qpos into (active vector, env row) on the scene's scratch
 static int upload_state(MopaScene *S, const double *qpos_host) {
-    std::vector<double> buf(S->nq + S->na);
-    std::memcpy(buf.data(), qpos_host, sizeof(double) * S->nq);
-    for (int a = 0; a < S->na; a++) buf[S->nq + a] = qpos_host[S->active_idx[a]];
+    std::vector<double> buf(qpos_host, qpos_host + S->nq);
+    const std::vector<double> act = active_of(S, qpos_host);
+    buf.insert(buf.end(), act.begin(), act.end());
     HIP_TRY(hipMemcpy(S->d_q, buf.data(), sizeof(double) * buf.size(), hipMemcpyHostToDevice));
     return MOPA_OK;
 }

@@ -579,9 +579,7 @@ MOPA_K9_KERNEL(k_smooth_paths, 2)
 typedef void (*K9Kernel)(SceneHdr, const double *, const int32_t *, K9Args);
 static const K9Kernel kK9Kernels[3] = {k_simplify_paths, k_shortcut_paths, k_smooth_paths};
 
-static void k9_register_lds() {
-    for (K9Kernel k : kK9Kernels) (void)hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLdsBytes);
-}
+static const LdsKernels kK9Lds({(const void *)k_simplify_paths, (const void *)k_shortcut_paths, (const void *)k_smooth_paths});
 
 // one wave's LDS behind the header copy, and the whole workgroup's
 static int k9_wave_bytes(int level, const MopaScene *S, int max_path) {

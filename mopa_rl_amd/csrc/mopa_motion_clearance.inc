@@ -104,10 +104,7 @@ __global__ __launch_bounds__(256) void k_motion_clearance_rows(int na, const int
     q_min[e] = q_states[(o + j) * na + a];
 }
 
-static void motion_clearance_register_lds() {
-    for (const void *k : {(const void *)k_clearance_states<false>, (const void *)k_clearance_states<true>})
-        (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLdsBytes);
-}
+static const LdsKernels kMotionClearanceLds({(const void *)k_clearance_states<false>, (const void *)k_clearance_states<true>});
 
 extern "C" int mopa_motion_clearance_batch(MopaScene *S, const double *qa, const double *qb, const double *qpos_env, int64_t N, int64_t samples_per_env,
                                            double band, double *clearance, int32_t *n_states, int32_t *n_near, int32_t *k_min, double *t_min,
@@ -115,10 +112,9 @@ extern "C" int mopa_motion_clearance_batch(MopaScene *S, const double *qa, const
     if (!S || !clearance || !n_states || !n_near || !k_min || !t_min || !pair_min || !end_clearance || (N > 0 && (!qa || !qb || !qpos_env)))
         return fail(MOPA_ERR_INVALID_ARG, "null argument");
     MOPA_REFUSE_GLUED(S, "the clearance report (mopa_motion_clearance_batch)");
-    if (N < 0 || samples_per_env <= 0) return fail(MOPA_ERR_INVALID_ARG, "N < 0 or samples_per_env <= 0");
-    if (!std::isfinite(band) || !(band >= 0.0)) return fail(MOPA_ERR_INVALID_ARG, "band must be finite and >= 0");
-    if (S->pruned)
-        return fail(MOPA_ERR_UNSUPPORTED, "a scene with pair_cull_radius is proven down to its contact_threshold only: the proximity report needs the full scene");
+    if (const int rc = state_batch_rule(N, samples_per_env)) return rc;
+    if (const int rc = band_rule(band)) return rc;
+    if (S->pruned) return refuse_pruned("the proximity report needs");
     if (N == 0) return MOPA_OK;
     ON_DEVICE(S->device);
     hipStream_t st = (hipStream_t)stream;
@@ -137,8 +133,7 @@ extern "C" int mopa_motion_clearance_batch(MopaScene *S, const double *qa, const
             HIP_TRY(grow(S, sc.mc_d, sizeof(double) * cap));
             HIP_TRY(grow(S, sc.mc_p, sizeof(int32_t) * cap));
         }
-        const int64_t blocks = std::max<int64_t>(1, std::min<int64_t>((x.T + kWavesPerBlock - 1) / kWavesPerBlock, (int64_t)S->n_cu * 2));
-        hipLaunchKernelGGL(S->hdr.has_mesh ? k_clearance_states<true> : k_clearance_states<false>, dim3((unsigned)blocks), dim3(kBlock), (size_t)S->lds_bytes, st,
+        hipLaunchKernelGGL(S->hdr.has_mesh ? k_clearance_states<true> : k_clearance_states<false>, dim3((unsigned)report_blocks(S, x.T)), dim3(kBlock), (size_t)S->lds_bytes, st,
                            S->hdr, S->d_dbl, S->d_int, (const int32_t *)S->d_pair_model, (const double *)x.q, qpos_env, (const int32_t *)x.env, (long long)x.T,
                            band, sc.ct_ctr.as<unsigned long long>(), sc.mc_d.as<double>(), sc.mc_p.as<int32_t>());
         hipLaunchKernelGGL(k_motion_clearance_reduce, dim3(x.nb), dim3(256), 0, st, x.cnt, x.off, x.bsum, (const double *)sc.mc_d.as<double>(),
@@ -165,37 +160,17 @@ extern "C" int mopa_motion_clearance(MopaScene *S, const double *qpos_a, const d
     int rc = upload_state(S, qpos_a);       // S->d_q: the env row, then a's active entries
     if (rc) return rc;
     const size_t na = (size_t)S->na;
-    // doubles: qb | q_min | clearance, t_min, end_clearance; int32: n_states, n_near, k_min, pair_min
-    const size_t n_dbl = 2 * na + 3, n_i32 = 4;
-    std::vector<double> hb(na);
-    for (size_t a = 0; a < na; a++) hb[a] = qpos_b[S->active_idx[a]];
-    void *buf = nullptr;
-    HIP_TRY(hipMalloc(&buf, n_dbl * sizeof(double) + n_i32 * sizeof(int32_t)));
-    double *d = static_cast<double *>(buf);
-    int32_t *w = reinterpret_cast<int32_t *>(d + n_dbl);
-    hipError_t e = hipMemcpy(d, hb.data(), na * sizeof(double), hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        rc = mopa_motion_clearance_batch(S, S->d_q + S->nq, d, S->d_q, 1, 1, band, d + 2 * na, w, w + 1, w + 2, d + 2 * na + 1, w + 3, d + 2 * na + 2,
-                                         d + na, nullptr);
-        std::vector<double> hd(n_dbl);
-        int32_t hw[4] = {0, 0, 0, 0};
-        if (rc == MOPA_OK) {
-            e = hipMemcpy(hd.data(), d, n_dbl * sizeof(double), hipMemcpyDeviceToHost);      // (synchronises with the null stream's launches)
-            if (e == hipSuccess) e = hipMemcpy(hw, w, n_i32 * sizeof(int32_t), hipMemcpyDeviceToHost);
-        }
-        if (rc == MOPA_OK && e == hipSuccess) {
-            *clearance_out = hd[2 * na];
-            *t_min_out = hd[2 * na + 1];
-            *end_clearance_out = hd[2 * na + 2];
-            *n_states_out = hw[0];
-            *n_near_out = hw[1];
-            *k_min_out = hw[2];
-            *pair_min_out = hw[3];
-            if (q_min_out) std::memcpy(q_min_out, &hd[na], na * sizeof(double));
-        }
-    }
-    (void)hipFree(buf);
+    Staging g;
+    const auto f_qb = g.dbl(na), f_qmin = g.dbl(na), f_clear = g.dbl(1), f_t = g.dbl(1), f_end = g.dbl(1);
+    const auto f_n = g.i32(1), f_near = g.i32(1), f_k = g.i32(1), f_pair = g.i32(1);
+    HIP_TRY(g.alloc());
+    HIP_TRY(g.seed(f_qb, active_of(S, qpos_b).data()));
+    rc = mopa_motion_clearance_batch(S, S->d_q + S->nq, g.dev(f_qb), S->d_q, 1, 1, band, g.dev(f_clear), g.dev(f_n), g.dev(f_near), g.dev(f_k), g.dev(f_t),
+                                     g.dev(f_pair), g.dev(f_end), g.dev(f_qmin), nullptr);
     if (rc != MOPA_OK) return rc;
-    HIP_TRY(e);
+    HIP_TRY(g.fetch());
+    g.out(f_clear, clearance_out); g.out(f_t, t_min_out); g.out(f_end, end_clearance_out);
+    g.out(f_n, n_states_out); g.out(f_near, n_near_out); g.out(f_k, k_min_out); g.out(f_pair, pair_min_out);
+    g.out(f_qmin, q_min_out);
     return MOPA_OK;
 }

@@ -131,16 +131,14 @@ static int motion_report_expanded(MopaScene *S, const double *qa, const double *
     });
 }
 
-static void motion_report_register_lds() {
-    (void)hipFuncSetAttribute((const void *)k_motion_report, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLdsBytes);
-}
+static const LdsKernels kMotionReportLds({(const void *)k_motion_report});
 
 extern "C" int mopa_motion_report_batch(MopaScene *S, const double *qa, const double *qb, const double *qpos_env, int64_t N, int64_t samples_per_env,
                                         uint8_t *valid, int32_t *n_states, int32_t *first_bad, double *last_valid_t, double *last_valid_q,
                                         double *first_bad_q, int32_t K, int32_t *block_count, int32_t *block_pair, double *block_dist, void *stream) {
     if (!S) return fail(MOPA_ERR_INVALID_ARG, "null argument");
     if (N > 0 && (!qa || !qb || !qpos_env || !valid || !n_states || !first_bad || !last_valid_t)) return fail(MOPA_ERR_INVALID_ARG, "null argument");
-    if (N < 0 || samples_per_env <= 0) return fail(MOPA_ERR_INVALID_ARG, "N < 0 or samples_per_env <= 0");
+    if (const int rc = state_batch_rule(N, samples_per_env)) return rc;
     const bool blockers = K != 0 || block_count || block_pair || block_dist;
     if (blockers && K < 1) return fail(MOPA_ERR_INVALID_ARG, "max_contacts must be >= 1 (0 with null blocker buffers: no blockers)");
     if (blockers && N > 0 && (!block_count || !block_pair || !block_dist)) return fail(MOPA_ERR_INVALID_ARG, "null blocker buffer with max_contacts >= 1");
@@ -186,43 +184,21 @@ extern "C" int mopa_motion_report(MopaScene *S, const double *qpos_a, const doub
     int rc = upload_state(S, qpos_a);       // S->d_q: the env row, then a's active entries
     if (rc) return rc;
     const size_t na = (size_t)S->na, Kb = blockers ? (size_t)K : 0;
-    // doubles: qb | last_valid_q | first_bad_q | t | dist[K]; int32: n_states, first_bad, count, pair[K]; then the verdict byte
-    const size_t n_dbl = 3 * na + 1 + Kb, n_i32 = 3 + Kb;
-    std::vector<double> hb(na);
-    for (size_t a = 0; a < na; a++) hb[a] = qpos_b[S->active_idx[a]];
-    void *buf = nullptr;
-    HIP_TRY(hipMalloc(&buf, n_dbl * sizeof(double) + n_i32 * sizeof(int32_t) + 8));
-    double *d = static_cast<double *>(buf);
-    int32_t *w = reinterpret_cast<int32_t *>(d + n_dbl);
-    uint8_t *vb = reinterpret_cast<uint8_t *>(w + n_i32);
-    hipError_t e = hipMemcpy(d, hb.data(), na * sizeof(double), hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        rc = mopa_motion_report_batch(S, S->d_q + S->nq, d, S->d_q, 1, 1, vb, w, w + 1, d + 3 * na, d + na, d + 2 * na, K, blockers ? w + 2 : nullptr,
-                                      blockers ? w + 3 : nullptr, blockers ? d + 3 * na + 1 : nullptr, nullptr);
-        std::vector<double> hd(n_dbl);
-        std::vector<int32_t> hw(n_i32);
-        uint8_t hv = 0;
-        if (rc == MOPA_OK) {
-            e = hipMemcpy(hd.data(), d, n_dbl * sizeof(double), hipMemcpyDeviceToHost);      // (synchronises with the null stream's launches)
-            if (e == hipSuccess) e = hipMemcpy(hw.data(), w, n_i32 * sizeof(int32_t), hipMemcpyDeviceToHost);
-            if (e == hipSuccess) e = hipMemcpy(&hv, vb, 1, hipMemcpyDeviceToHost);
-        }
-        if (rc == MOPA_OK && e == hipSuccess) {
-            *valid_out = hv;
-            *n_states_out = hw[0];
-            *first_bad_out = hw[1];
-            *last_valid_t_out = hd[3 * na];
-            if (last_valid_q_out) std::memcpy(last_valid_q_out, &hd[na], na * sizeof(double));
-            if (first_bad_q_out) std::memcpy(first_bad_q_out, &hd[2 * na], na * sizeof(double));
-            if (blockers) {
-                *block_count = hw[2];
-                std::memcpy(block_pair, &hw[3], Kb * sizeof(int32_t));
-                std::memcpy(block_dist, &hd[3 * na + 1], Kb * sizeof(double));
-            }
-        }
-    }
-    (void)hipFree(buf);
+    Staging g;
+    const auto f_qb = g.dbl(na), f_lvq = g.dbl(na), f_fbq = g.dbl(na), f_t = g.dbl(1), f_dist = g.dbl(Kb);
+    const auto f_n = g.i32(1), f_bad = g.i32(1), f_count = g.i32(1), f_pair = g.i32(Kb);
+    const auto f_valid = g.u8(1);
+    HIP_TRY(g.alloc());
+    HIP_TRY(g.seed(f_qb, active_of(S, qpos_b).data()));
+    rc = mopa_motion_report_batch(S, S->d_q + S->nq, g.dev(f_qb), S->d_q, 1, 1, g.dev(f_valid), g.dev(f_n), g.dev(f_bad), g.dev(f_t), g.dev(f_lvq), g.dev(f_fbq), K,
+                                  blockers ? g.dev(f_count) : nullptr, blockers ? g.dev(f_pair) : nullptr, blockers ? g.dev(f_dist) : nullptr, nullptr);
     if (rc != MOPA_OK) return rc;
-    HIP_TRY(e);
+    HIP_TRY(g.fetch());
+    *valid_out = *g.host(f_valid);
+    g.out(f_n, n_states_out); g.out(f_bad, first_bad_out); g.out(f_t, last_valid_t_out);
+    g.out(f_lvq, last_valid_q_out); g.out(f_fbq, first_bad_q_out);
+    if (blockers) {
+        g.out(f_count, block_count); g.out(f_pair, block_pair); g.out(f_dist, block_dist);
+    }
     return MOPA_OK;
 }

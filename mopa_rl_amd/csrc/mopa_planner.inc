@@ -713,11 +713,5 @@ extern "C" int mopa_plan(MopaScene *S, const double *start_host, const double *g
 // K3 race: RaceArgs, k_race_pick, mopa_plan_race_batch / mopa_plan_race
 #include "mopa_race.inc"
 
-static void plan_register_more();   // kernels defined after this file (mopa_pullback.inc)
-static void plan_register_lds() {
-    (void)hipFuncSetAttribute((const void *)k_rrt_connect<K3W2>, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLdsBytes);
-    (void)hipFuncSetAttribute((const void *)k_rrt_connect<K3W1>, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLdsBytes);
-    (void)hipFuncSetAttribute((const void *)k_rrt_connect<K3WG>, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLdsBytes);
-    (void)hipFuncSetAttribute((const void *)k_rrt_connect<K3Race>, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLdsBytes);
-    plan_register_more();
-}
+static const LdsKernels kPlanLds({(const void *)k_rrt_connect<K3W2>, (const void *)k_rrt_connect<K3W1>, (const void *)k_rrt_connect<K3WG>,
+                                  (const void *)k_rrt_connect<K3Race>});

@@ -79,31 +79,33 @@ __global__ __launch_bounds__(256) void k_geom_sep(long long M, const int32_t *__
     out[i] = geom_sep_rec(types[2 * i], recs + i * 30, types[2 * i + 1], recs + i * 30 + 15, mesh_verts, nvert, band);
 }
 
-static void proximity_register_lds() {
-    for (const void *k : {(const void *)k_proximity_rows<false>, (const void *)k_proximity_rows<true>})
-        (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLdsBytes);
+static const LdsKernels kProximityLds({(const void *)k_proximity_rows<false>, (const void *)k_proximity_rows<true>});
+
+// the band of the proximity and clearance reports and of geom_sep
+static int band_rule(double band) {
+    if (!std::isfinite(band) || !(band >= 0.0)) return fail(MOPA_ERR_INVALID_ARG, "band must be finite and >= 0");
+    return MOPA_OK;
 }
 
 extern "C" int mopa_proximity_batch(MopaScene *S, const double *q_active, const double *qpos_env, int64_t N, int64_t samples_per_env, double band,
                                     int32_t K, double *clearance, int32_t *count, int32_t *pair, double *dist, void *stream) {
     if (!S || !clearance || !count || !pair || !dist || (N > 0 && (!q_active || !qpos_env))) return fail(MOPA_ERR_INVALID_ARG, "null argument");
     MOPA_REFUSE_GLUED(S, "the proximity report (mopa_proximity_batch)");
-    if (N < 0 || samples_per_env <= 0) return fail(MOPA_ERR_INVALID_ARG, "N < 0 or samples_per_env <= 0");
-    if (!std::isfinite(band) || !(band >= 0.0)) return fail(MOPA_ERR_INVALID_ARG, "band must be finite and >= 0");
+    if (const int rc = state_batch_rule(N, samples_per_env)) return rc;
+    if (const int rc = band_rule(band)) return rc;
     if (K < 1) return fail(MOPA_ERR_INVALID_ARG, "max_pairs must be >= 1");
-    if (S->pruned)
-        return fail(MOPA_ERR_UNSUPPORTED, "a scene with pair_cull_radius is proven down to its contact_threshold only: the proximity report needs the full scene");
+    if (S->pruned) return refuse_pruned("the proximity report needs");
     if (N == 0) return MOPA_OK;
     ON_DEVICE(S->device);
     hipStream_t st = (hipStream_t)stream;
-    const int pd_off = (S->lds_bytes + 15) & ~15;
-    const size_t lds = (size_t)pd_off + (size_t)kWavesPerBlock * S->npair_model * sizeof(double);
-    if (lds > (size_t)kMaxLdsBytes) return fail(MOPA_ERR_LIMIT, "proximity report: the per-wave distance arrays do not fit LDS");
-    StreamScratch &sc = scratch_for(S, st);
-    const int rc = ensure_report_ctr(S, sc);
+    int pd_off;
+    size_t lds;
+    int rc = pair_dist_lds(S, "proximity report", &pd_off, &lds);
     if (rc != MOPA_OK) return rc;
-    const int64_t blocks = std::max<int64_t>(1, std::min<int64_t>((N + kWavesPerBlock - 1) / kWavesPerBlock, (int64_t)S->n_cu * 2));
-    hipLaunchKernelGGL(S->hdr.has_mesh ? k_proximity_rows<true> : k_proximity_rows<false>, dim3((unsigned)blocks), dim3(kBlock), lds, st, S->hdr, S->d_dbl, S->d_int,
+    StreamScratch &sc = scratch_for(S, st);
+    rc = ensure_report_ctr(S, sc);
+    if (rc != MOPA_OK) return rc;
+    hipLaunchKernelGGL(S->hdr.has_mesh ? k_proximity_rows<true> : k_proximity_rows<false>, dim3((unsigned)report_blocks(S, N)), dim3(kBlock), lds, st, S->hdr, S->d_dbl, S->d_int,
                        (const int32_t *)S->d_pair_model, S->npair_model, q_active, qpos_env, (long long)N, (long long)samples_per_env, band, (int)K,
                        sc.ct_ctr.as<unsigned long long>(), clearance, count, pair, dist, pd_off);
     HIP_TRY(hipGetLastError());
@@ -118,41 +120,28 @@ extern "C" int mopa_proximity_state(MopaScene *S, const double *qpos_host, doubl
     ON_DEVICE(S->device);
     int rc = upload_state(S, qpos_host);
     if (rc) return rc;
-    void *buf = nullptr;
-    const size_t off_dist = 0, off_clear = (size_t)K * sizeof(double), off_pair = off_clear + sizeof(double), off_count = off_pair + (size_t)K * sizeof(int32_t);
-    HIP_TRY(hipMalloc(&buf, off_count + sizeof(int32_t)));
-    unsigned char *b = static_cast<unsigned char *>(buf);
-    rc = mopa_proximity_batch(S, S->d_q + S->nq, S->d_q, 1, 1, band, K, reinterpret_cast<double *>(b + off_clear), reinterpret_cast<int32_t *>(b + off_count),
-                              reinterpret_cast<int32_t *>(b + off_pair), reinterpret_cast<double *>(b + off_dist), nullptr);
-    hipError_t e = hipSuccess;
-    if (rc == MOPA_OK) {
-        e = hipMemcpy(dist, b + off_dist, (size_t)K * sizeof(double), hipMemcpyDeviceToHost);
-        if (e == hipSuccess) e = hipMemcpy(clearance, b + off_clear, sizeof(double), hipMemcpyDeviceToHost);
-        if (e == hipSuccess) e = hipMemcpy(pair, b + off_pair, (size_t)K * sizeof(int32_t), hipMemcpyDeviceToHost);
-        if (e == hipSuccess) e = hipMemcpy(count, b + off_count, sizeof(int32_t), hipMemcpyDeviceToHost);
-    }
-    (void)hipFree(buf);
+    Staging g;
+    const auto f_dist = g.dbl(K), f_clear = g.dbl(1);
+    const auto f_pair = g.i32(K), f_count = g.i32(1);
+    HIP_TRY(g.alloc());
+    rc = mopa_proximity_batch(S, S->d_q + S->nq, S->d_q, 1, 1, band, K, g.dev(f_clear), g.dev(f_count), g.dev(f_pair), g.dev(f_dist), nullptr);
     if (rc != MOPA_OK) return rc;
-    HIP_TRY(e);
+    HIP_TRY(g.fetch());
+    g.out(f_dist, dist); g.out(f_clear, clearance); g.out(f_pair, pair); g.out(f_count, count);
     return MOPA_OK;
 }
 
 extern "C" int mopa_geom_sep_batch(int32_t device, int64_t M, const int32_t *types, const double *recs, const double *mesh_verts, int32_t nvert, double band,
                                    double *out, void *stream) {
-    if (M < 0 || (M > 0 && (!types || !recs || !out)) || nvert < 0 || (nvert > 0 && !mesh_verts)) return fail(MOPA_ERR_INVALID_ARG, "null argument / negative count");
-    if (!std::isfinite(band) || !(band >= 0.0)) return fail(MOPA_ERR_INVALID_ARG, "band must be finite and >= 0");
-    if (device < 0 || device >= mopa_device_count()) return fail(MOPA_ERR_INVALID_ARG, "device ordinal out of range");
-    if (M == 0) return MOPA_OK;
-    ON_DEVICE(device);
-    hipLaunchKernelGGL(k_geom_sep, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (long long)M, types, recs, mesh_verts, (int)nvert, band, out);
-    HIP_TRY(hipGetLastError());
-    return MOPA_OK;
+    if (const int rc = pair_batch_rule(M, types, recs, out != nullptr, mesh_verts, nvert)) return rc;
+    if (const int rc = band_rule(band)) return rc;
+    return pair_launch(device, k_geom_sep, M, stream, types, recs, mesh_verts, (int)nvert, band, out);
 }
 
 // The host compile of the same functions: the sequential form the kernels must match bit for bit.  No GPU, no HIP call.
 extern "C" int mopa_geom_sep_host(int64_t M, const int32_t *types, const double *recs, const double *mesh_verts, int32_t nvert, double band, double *out) {
-    if (M < 0 || (M > 0 && (!types || !recs || !out)) || nvert < 0 || (nvert > 0 && !mesh_verts)) return fail(MOPA_ERR_INVALID_ARG, "null argument / negative count");
-    if (!std::isfinite(band) || !(band >= 0.0)) return fail(MOPA_ERR_INVALID_ARG, "band must be finite and >= 0");
+    if (const int rc = pair_batch_rule(M, types, recs, out != nullptr, mesh_verts, nvert)) return rc;
+    if (const int rc = band_rule(band)) return rc;
     for (int64_t i = 0; i < M; i++) out[i] = geom_sep_rec(types[2 * i], recs + i * 30, types[2 * i + 1], recs + i * 30 + 15, mesh_verts, nvert, band);
     return MOPA_OK;
 }

@@ -300,6 +300,4 @@ extern "C" int mopa_pullback_batch(MopaScene *S, const double *cur, double *targ
     return MOPA_OK;
 }
 
-static void plan_register_more() {
-    (void)hipFuncSetAttribute((const void *)k_pullback, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLdsBytes);
-}
+static const LdsKernels kPullbackLds({(const void *)k_pullback});

@@ -300,9 +300,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(2, 2))) 
     }
 }
 
-static void star_register_lds() {
-    (void)hipFuncSetAttribute((const void *)k_rrt_star, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLdsBytes);
-}
+static const LdsKernels kStarLds({(const void *)k_rrt_star});
 
 extern "C" int mopa_star_params_size(void) { return (int)sizeof(MopaStarParams); }
 

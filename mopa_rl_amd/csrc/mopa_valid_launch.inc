@@ -16,7 +16,7 @@ static int64_t k1_motion_expand_min(const MopaScene *S) { return S->k1.v2_forced
 
 // ---------------------------------------------------------------------------
 // the K1 instantiations: every one the library launches is in one of these tables (plus MOPA_K1_BAKED_SCENES), and
-// k1_register_lds walks their whole domain
+// k1_kernels walks their whole domain for the LDS list (mopa_hip.hip: LdsKernels)
 // ---------------------------------------------------------------------------
 using K1FnV1 = decltype(&k_is_valid<false, false>);
 using K1FnV2 = decltype(&k_is_valid_v2<false, false>);
@@ -74,18 +74,20 @@ static int k1_baked_pair_words(int baked, bool want_md) {
 // allow the dynamic LDS size
 // the attribute is per function, not per scene: register the device maximum once so scenes of different sizes can
 // coexist in one process in any creation order (each launch still passes its own, checked, size)
-static void k1_register_lds() {
-    auto reg = [](const void *k) { if (k) (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLdsBytes); };
+static std::vector<const void *> k1_kernels() {
+    std::vector<const void *> ks;
     for (int md = 0; md < 2; md++)
         for (int mesh = 0; mesh < 2; mesh++) {
-            reg((const void *)k1_kernel_v1(md, mesh));
-            reg((const void *)k1_kernel_v2(md, mesh));
+            ks.push_back((const void *)k1_kernel_v1(md, mesh));
+            ks.push_back((const void *)k1_kernel_v2(md, mesh));
         }
     for (int md = 0; md < 2; md++)
         for (int cen_lds = 0; cen_lds < 2; cen_lds++)
             for (int gate = 0; gate < 2; gate++)
-                for (int baked = 0; baked <= kK1BakedScenes; baked++) reg((const void *)k1_kernel_v5(md, cen_lds, gate, baked));
+                for (int baked = 0; baked <= kK1BakedScenes; baked++) ks.push_back((const void *)k1_kernel_v5(md, cen_lds, gate, baked));      // (null: no such instantiation)
+    return ks;
 }
+static const LdsKernels kK1Lds(k1_kernels());
 
 // ---------------------------------------------------------------------------
 // the plan of one validity batch
@@ -235,7 +237,7 @@ static int launch_is_valid(MopaScene *S, const double *q_active, const double *q
                            const int *env_idx, uint8_t *valid, double *min_dist, void *stream, const long long *n_dev = nullptr,
                            bool attach = false) {
     if (!S || !valid || (N > 0 && (!q_active || !qpos_env))) return fail(MOPA_ERR_INVALID_ARG, "null argument");
-    if (N < 0 || samples_per_env <= 0) return fail(MOPA_ERR_INVALID_ARG, "N < 0 or samples_per_env <= 0");
+    if (const int rc = state_batch_rule(N, samples_per_env)) return rc;
     if (N == 0) return MOPA_OK;
     ON_DEVICE(S->device);
     hipStream_t st = (hipStream_t)stream;
