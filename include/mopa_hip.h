@@ -73,8 +73,10 @@ enum { MOPA_JNT_FREE = 0, MOPA_JNT_BALL = 1, MOPA_JNT_SLIDE = 2, MOPA_JNT_HINGE 
 /* Flat compiled model (host pointers; copied by mopa_scene_create).
  * Same arrays as mopa_rl_amd.mjcf.CompiledModel.
  *
- * Preconditions -- what MuJoCo's compiler emits; every entry point that compiles a scene (mopa_scene_create, _create_glued,
- * mopa_scene_k1_export, _export_glued) checks them before anything indexes with these values and refuses a model that breaks one:
+ * Preconditions -- what MuJoCo's compiler emits; every entry point that compiles a model (mopa_scene_create, _create_glued,
+ * mopa_scene_k1_export, _export_glued; mopa_env_create, mopa_ik_create and their host halves mopa_env_tables_host, mopa_ik_tables_host,
+ * mopa_dyn_tables_host: the body, joint and geom_body rules) checks them before anything indexes with these values and refuses a
+ * model that breaks one:
  *   - body 0 is the world; 0 <= body_parent[b] < b for b >= 1                                    (MOPA_ERR_INVALID_ARG)
  *   - the bodies are in depth-first order: body_parent[b] is body b - 1 or one of its ancestors  (MOPA_ERR_UNSUPPORTED; a breadth-
  *     first numbering of a branching tree is refused, not compiled: the pose save slots of the FK program are numbered by depth)
@@ -824,6 +826,14 @@ typedef struct MopaDynDesc {
     const MopaObjDesc *obj;           /* NULL: stage A (only the robot moves) */
 } MopaDynDesc;
 int mopa_env_attach_dynamics(MopaEnv *env, const MopaDynDesc *desc);
+/* The dofs are listed parents first (MOPA_ERR_INVALID_ARG) and in depth-first order, as the bodies of a MopaModel are (MOPA_ERR_UNSUPPORTED).
+ * A failed attach leaves the env as it was.
+ *
+ * The host halves of mopa_env_create and of mopa_env_create + mopa_env_attach_dynamics alone, no device needed: the status code the
+ * creation would refuse the description with, and for an accepted one the FNV-1a fingerprint of the tables it would upload (header,
+ * double table, int table / header, dof records, object table), the walk's body count and its pose save slots.  Outputs may be NULL. */
+int mopa_env_tables_host(const MopaEnvDesc *desc, uint64_t *fingerprint, int32_t *nb, int32_t *n_save);
+int mopa_dyn_tables_host(const MopaEnvDesc *env_desc, const MopaDynDesc *desc, uint64_t *fingerprint, int32_t *n_save);
 /* (stage C) contacts of the arm, of the manipulated object (Push: cube, Lift: can, Assembly: furniture; a
  * free rigid body) and between the two, two-way coupled behind ONE soft-constraint solve per sub-step.  Replaces, inside
  * `sim.step()` of the reference's `_do_simulation` loop (env/sawyer/sawyer_push_obstacle.py:186-203, sawyer_lift_obstacle.py:
@@ -1108,6 +1118,8 @@ typedef struct MopaIkDesc {
 typedef struct MopaIk MopaIk;
 
 int mopa_ik_create(const MopaIkDesc *desc, MopaIk **out);
+/* its host half alone (see mopa_env_tables_host): status, fingerprint of the tables, bodies on the site's chain */
+int mopa_ik_tables_host(const MopaIkDesc *desc, uint64_t *fingerprint, int32_t *nb);
 void mopa_ik_destroy(MopaIk *ik);
 /* E independent IK problems; qpos rows are updated in place (IKResult.qpos); err_norm / steps / success as IKResult.
  * target_quat_dev NULL = position target only (rot_weight ignored). */

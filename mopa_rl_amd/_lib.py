@@ -42,6 +42,7 @@ EXPORTED_SYMBOLS = [
     "mopa_env_step_pusher_batch", "mopa_env_set_contact_force",
     "mopa_ik_create", "mopa_ik_destroy", "mopa_ik_solve_batch", "mopa_ik_site_pose_batch", "mopa_ik_targets_batch",
     "mopa_ik_targets_pos_batch", "mopa_ik_displacement_pos_batch",
+    "mopa_env_tables_host", "mopa_ik_tables_host", "mopa_dyn_tables_host",
     "mopa_paths_unwrap_batch", "mopa_paths_unwrap_seam_batch", "mopa_paths_walk_batch", "mopa_paths_assemble_batch", "mopa_interpolate_batch",
 ]
 
@@ -293,6 +294,11 @@ def lib() -> C.CDLL:
     L.mopa_env_step_pusher_batch.argtypes = [vp, C.c_int64, vp, vp, vp, vp, vp, vp, vp, C.c_int32, vp, vp, vp, vp, vp, vp]
     L.mopa_env_set_contact_force.argtypes = [vp, vp, vp, vp, vp, C.c_int32]
     L.mopa_ik_create.argtypes = [C.POINTER(MopaIkDesc), C.POINTER(vp)]
+    # host halves of env / IK / dynamics creation (no device): status code, fingerprint of the tables, table counts
+    u64p = C.POINTER(C.c_uint64)
+    L.mopa_env_tables_host.argtypes = [C.POINTER(MopaEnvDesc), u64p, _ip, _ip]
+    L.mopa_ik_tables_host.argtypes = [C.POINTER(MopaIkDesc), u64p, _ip]
+    L.mopa_dyn_tables_host.argtypes = [C.POINTER(MopaEnvDesc), C.POINTER(MopaDynDesc), u64p, _ip]
     L.mopa_ik_destroy.argtypes = [vp]
     L.mopa_ik_destroy.restype = None
     L.mopa_ik_solve_batch.argtypes = [vp, C.c_int64, vp, vp, vp, C.c_double, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double,

@@ -1380,28 +1380,37 @@ extern "C" int mopa_env_attach_contacts(MopaEnv *env, const MopaCtDesc *d) {
     }
     DeviceGuard guard(env->device);
     if (!guard.ok()) return fail(MOPA_ERR_HIP, "hipSetDevice failed");
-    const size_t nb = (ft.size() + pr.size()) * sizeof(double);
-    double *tab = nullptr;
-    HIP_TRY(hipMalloc((void **)&tab, nb));
+    // everything is allocated and uploaded into locals; env changes only once nothing can fail any more
     std::vector<double> all(ft);
     all.insert(all.end(), pr.begin(), pr.end());
-    if (hipMemcpy(tab, all.data(), nb, hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(tab); return fail(MOPA_ERR_HIP, "upload of the contact tables failed"); }
+    double *tab = nullptr;
+    CtHdr *nh = nullptr;
+    DynHdr dyn = env->dyn;
+    dyn.nv = nd + (smooth_only ? 0 : 6);
+    auto drop = [&](const char *what) {
+        if (tab) (void)hipFree(tab);
+        if (nh) (void)hipFree(nh);
+        return fail(MOPA_ERR_HIP, what);
+    };
+    if (upload_array(all.data(), all.size(), &tab) != hipSuccess) return drop("upload of the contact tables failed");
+    if (!env->d_cthdr && hipMalloc((void **)&nh, sizeof(CtHdr)) != hipSuccess) return drop("allocation of the contact header failed");
+    if (hipMemcpy(nh ? nh : env->d_cthdr, &ch, sizeof(CtHdr), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(env->d_dynhdr, &dyn, sizeof(DynHdr), hipMemcpyHostToDevice) != hipSuccess)
+        return drop("upload of the contact / dynamics headers failed");
     if (env->d_ct) {
         std::lock_guard<std::mutex> lock(env->mu);
         env->retired.push_back(env->d_ct);
     }
     env->d_ct = tab;
     env->ct_ft_off = 0; env->ct_pr_off = ft.size();
-    if (!env->d_cthdr) HIP_TRY(hipMalloc((void **)&env->d_cthdr, sizeof(CtHdr)));
-    HIP_TRY(hipMemcpy(env->d_cthdr, &ch, sizeof(CtHdr), hipMemcpyHostToDevice));
+    if (nh) env->d_cthdr = nh;
     env->ct_lds = lds;
     env->ct_on = true;
     env->ct_solver = d->solver;
     env->ct_arena = ch.arena;
     env->ct_maxcon = d->maxcon;
     env->cf = CfOut{nullptr, nullptr, nullptr, nullptr, 0};
-    env->dyn.nv = nd + (smooth_only ? 0 : 6);
-    HIP_TRY(hipMemcpy(env->d_dynhdr, &env->dyn, sizeof(DynHdr), hipMemcpyHostToDevice));
+    env->dyn = dyn;
     for (const void *k : {(const void *)k_env_dyn_ct<0>, (const void *)k_env_dyn_ct<1>, (const void *)k_env_dyn_ct<2>})
         (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLdsBytes);
     return MOPA_OK;

@@ -887,16 +887,24 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 }
 #undef DLW
 
-extern "C" int mopa_env_attach_dynamics(MopaEnv *env, const MopaDynDesc *d) {
-    if (!env || !d) return fail(MOPA_ERR_INVALID_ARG, "null argument");
+// What attach_dynamics compiles: the header, the per-dof records, the penalty object's [feature points | collider records] (empty:
+// no object), the LDS bytes of a launch.
+struct DynTables {
+    DynHdr hdr{};
+    std::vector<double> rec, orec;
+    size_t lds = 0;
+};
+// Host half of attach_dynamics, over the env's header and the host copy of its int table (actuator / joint addresses).  No device.
+static int dyn_build_host(const EnvHdr &h, const std::vector<int32_t> &hi, const MopaDynDesc *d, DynTables &T) {
+    if (!d) return fail(MOPA_ERR_INVALID_ARG, "null argument");
     if (d->nd <= 0 || d->nd > kDynMax) return fail(MOPA_ERR_LIMIT, "the dynamics kernel keeps 1 .. 9 dofs per env");
     if (!(d->timestep > 0.0) || d->nsub <= 0) return fail(MOPA_ERR_INVALID_ARG, "timestep / nsub must be positive");
-    const EnvHdr &h = env->hdr;
-    DynHdr dh{};
+    DynHdr &dh = T.hdr;
+    dh = DynHdr{};
     dh.nd = d->nd; dh.nsub = d->nsub; dh.nv = d->nd;
     dh.gx = d->gravity[0]; dh.gy = d->gravity[1]; dh.gz = d->gravity[2]; dh.h = d->timestep;
-    std::vector<double> rec((size_t)kDynRec * d->nd, 0.0);
-    std::vector<int32_t> hi(env_host_ints(env));
+    std::vector<double> &rec = T.rec, &orec = T.orec;
+    rec.assign((size_t)kDynRec * d->nd, 0.0);
     for (int i = 0; i < d->nd; i++) {
         if (d->parent[i] >= i || d->parent[i] < -1) return fail(MOPA_ERR_INVALID_ARG, "dynamic bodies must list parents before children");
         if (d->jtype[i] != J_SLIDE && d->jtype[i] != J_HINGE) return fail(MOPA_ERR_UNSUPPORTED, "hinge / slide dofs only");
@@ -929,22 +937,9 @@ extern "C" int mopa_env_attach_dynamics(MopaEnv *env, const MopaDynDesc *d) {
     }
     for (int j = 0; j < h.n_arm; j++) if (dh.arm_dof[j] < 0) return fail(MOPA_ERR_INVALID_ARG, "an arm joint is not among the dynamic dofs");
     for (int j = 0; j < h.n_grip; j++) if (dh.grip_dof[j] < 0) return fail(MOPA_ERR_INVALID_ARG, "a gripper joint is not among the dynamic dofs");
-    // DFS save-slot program over the dynamic tree (same scheme as the FK walks)
-    {
-        std::vector<char> need_save(d->nd, 0);
-        for (int k = 0; k < d->nd; k++)
-            if (d->parent[k] >= 0 && d->parent[k] != k - 1) need_save[d->parent[k]] = 1;
-        std::vector<int> depth(d->nd, 0), save_of(d->nd, -1);
-        int n_save = 0;
-        for (int k = 0; k < d->nd; k++) {
-            const int pk = d->parent[k];
-            depth[k] = (pk >= 0) ? depth[pk] + (need_save[pk] ? 1 : 0) : 0;
-            if (need_save[k]) { save_of[k] = depth[k]; n_save = std::max(n_save, depth[k] + 1); }
-            dh.load[k] = (pk < 0) ? -2 : (pk == k - 1 ? -1 : save_of[pk]);
-            dh.save[k] = save_of[k];
-        }
-        dh.n_save = n_save;
-    }
+    if (const int k = parents_depth_first(d->parent, d->nd); k >= 0)
+        return fail(MOPA_ERR_UNSUPPORTED, "bodies are not in depth-first order (body " + std::to_string(k) + ")");
+    dh.n_save = save_slot_program(d->parent, d->nd, dh.load, dh.save);
     // workgroup form: bodies round-robin over the waves that own bodies (three with the object on, four without);
     // rows of M by descending length to the least loaded wave (row i has depth(i) + 1 entries)
     {
@@ -964,9 +959,8 @@ extern "C" int mopa_env_attach_dynamics(MopaEnv *env, const MopaDynDesc *d) {
             load[w] += len[i];
         }
     }
-    const size_t lds = (size_t)(DL_SAVE + kDynSaveStride * dh.n_save) * 64 * sizeof(double);
-    if (lds > (size_t)kMaxLdsBytes) return fail(MOPA_ERR_LIMIT, "dynamic tree too branchy for the LDS layout");
-    std::vector<double> orec;
+    T.lds = (size_t)(DL_SAVE + kDynSaveStride * dh.n_save) * 64 * sizeof(double);
+    if (T.lds > (size_t)kMaxLdsBytes) return fail(MOPA_ERR_LIMIT, "dynamic tree too branchy for the LDS layout");
     if (d->obj) {
         const MopaObjDesc &o = *d->obj;
         if (o.nfeat != kObjFeat || o.ncol < 0) return fail(MOPA_ERR_INVALID_ARG, "a box object comes with its 26 feature points (8 vertices, 12 edge midpoints, 6 face centres)");
@@ -1002,32 +996,62 @@ extern "C" int mopa_env_attach_dynamics(MopaEnv *env, const MopaDynDesc *d) {
             orec.insert(orec.end(), r, r + kObjRec);
         }
     }
+    return MOPA_OK;
+}
+
+extern "C" int mopa_env_attach_dynamics(MopaEnv *env, const MopaDynDesc *d) {
+    if (!env || !d) return fail(MOPA_ERR_INVALID_ARG, "null argument");
+    DynTables T;
+    if (const int rc = dyn_build_host(env->hdr, env->h_int, d, T)) return rc;
     DeviceGuard guard(env->device);
     if (!guard.ok()) return fail(MOPA_ERR_HIP, "hipSetDevice failed");
-    if (!orec.empty()) {
-        double *od = nullptr;
-        HIP_TRY(hipMalloc((void **)&od, orec.size() * sizeof(double)));
-        if (hipMemcpy(od, orec.data(), orec.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) {
-            (void)hipFree(od);
-            return fail(MOPA_ERR_HIP, "upload of the object table failed");
-        }
-        if (env->d_obj) env->retired.push_back(env->d_obj);
-        env->d_obj = od;
+    // everything is allocated and uploaded into locals; env changes only once nothing can fail any more
+    double *od = nullptr, *dd = nullptr;
+    DynHdr *nh = nullptr;
+    auto drop = [&](const char *what) {
+        for (void *q : {(void *)od, (void *)dd, (void *)nh})
+            if (q) (void)hipFree(q);
+        return fail(MOPA_ERR_HIP, what);
+    };
+    if (!T.orec.empty() && upload_array(T.orec.data(), T.orec.size(), &od) != hipSuccess) return drop("upload of the object table failed");
+    if (upload_array(T.rec.data(), T.rec.size(), &dd) != hipSuccess) return drop("upload of the dynamics table failed");
+    if (!env->d_dynhdr && hipMalloc((void **)&nh, sizeof(DynHdr)) != hipSuccess) return drop("allocation of the dynamics header failed");
+    if (hipMemcpy(nh ? nh : env->d_dynhdr, &T.hdr, sizeof(DynHdr), hipMemcpyHostToDevice) != hipSuccess) return drop("upload of the dynamics header failed");
+    {
+        std::lock_guard<std::mutex> lock(env->mu);
+        if (od && env->d_obj) env->retired.push_back(env->d_obj);
+        if (env->d_dyn) env->retired.push_back(env->d_dyn);
     }
-    double *dd = nullptr;
-    HIP_TRY(hipMalloc((void **)&dd, rec.size() * sizeof(double)));
-    if (hipMemcpy(dd, rec.data(), rec.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) {
-        (void)hipFree(dd);
-        return fail(MOPA_ERR_HIP, "upload of the dynamics table failed");
-    }
-    if (env->d_dyn) env->retired.push_back(env->d_dyn);
+    if (od) env->d_obj = od;
     env->d_dyn = dd;
-    env->dyn = dh;
-    if (!env->d_dynhdr) HIP_TRY(hipMalloc((void **)&env->d_dynhdr, sizeof(DynHdr)));
-    HIP_TRY(hipMemcpy(env->d_dynhdr, &dh, sizeof(DynHdr), hipMemcpyHostToDevice));
-    env->dyn_lds = lds;
+    if (nh) env->d_dynhdr = nh;
+    env->dyn = T.hdr;
+    env->dyn_lds = T.lds;
     for (const void *k : {(const void *)k_env_dyn, (const void *)k_env_dyn4})
         (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLdsBytes);
+    return MOPA_OK;
+}
+
+// The host halves of mopa_env_create + mopa_env_attach_dynamics alone: status, and for accepted descriptions the fingerprint of what
+// attach_dynamics would upload (header, dof records, object table) with the dynamic tree's save-slot count.  DynHdr ends in padding:
+// its fields are contiguous up to rows4 (asserted), and the hash stops there.
+static_assert(offsetof(DynHdr, gx) == offsetof(DynHdr, grip_dof) + 4 * sizeof(int) && offsetof(DynHdr, obj_on) == offsetof(DynHdr, h) + sizeof(double) &&
+                  offsetof(DynHdr, o_mass) == offsetof(DynHdr, co_first) + (kDynMax + 2) * sizeof(int) &&
+                  offsetof(DynHdr, o_every) == offsetof(DynHdr, o_margin) + sizeof(double) && offsetof(DynHdr, own4) == offsetof(DynHdr, o_every) + sizeof(int) &&
+                  offsetof(DynHdr, rows4) == offsetof(DynHdr, own4) + 4 * sizeof(unsigned),
+              "DynHdr has padding between its fields: mopa_dyn_tables_host would hash indeterminate bytes");
+extern "C" int mopa_dyn_tables_host(const MopaEnvDesc *env_desc, const MopaDynDesc *d, uint64_t *fingerprint, int32_t *n_save) {
+    MopaEnv S;
+    BlobPacker B;
+    if (const int rc = env_build_host(env_desc, S, B)) return rc;
+    DynTables T;
+    if (const int rc = dyn_build_host(S.hdr, S.h_int, d, T)) return rc;
+    Fnv f;
+    f.add(&T.hdr, offsetof(DynHdr, rows4) + sizeof(T.hdr.rows4));
+    f.add(T.rec);
+    f.add(T.orec);
+    if (fingerprint) *fingerprint = f.f;
+    if (n_save) *n_save = T.hdr.n_save;
     return MOPA_OK;
 }
 

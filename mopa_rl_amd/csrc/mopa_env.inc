@@ -596,9 +596,10 @@ __global__ __launch_bounds__(256) void k_env_desired(EnvHdr h, const double *__r
     desired[i] = d;
 }
 
-extern "C" int mopa_env_create(const MopaEnvDesc *desc, MopaEnv **out) {
-    if (!desc || !out) return fail(MOPA_ERR_INVALID_ARG, "null argument");
-    *out = nullptr;
+// Host half of env creation: every argument check, the model's structure, then the compile -- the header into S.hdr, the tables into B,
+// the int table's host copy into S.h_int.  No device.
+static int env_build_host(const MopaEnvDesc *desc, MopaEnv &S, BlobPacker &B) {
+    if (!desc) return fail(MOPA_ERR_INVALID_ARG, "null argument");
     const MopaModel &m = desc->model;
     if (m.nq <= 0 || m.nbody <= 0) return fail(MOPA_ERR_INVALID_ARG, "empty model");
     const int kind = desc->kind;
@@ -631,14 +632,7 @@ extern "C" int mopa_env_create(const MopaEnvDesc *desc, MopaEnv **out) {
         if (desc->act_qpos_idx[j] < 0 || desc->act_qpos_idx[j] >= m.nq) return fail(MOPA_ERR_INVALID_ARG, "act_qpos_idx out of range");
     for (int j = 0; j < desc->n_grip; j++)
         if (desc->grip_qpos_idx[j] < 0 || desc->grip_qpos_idx[j] >= m.nq) return fail(MOPA_ERR_INVALID_ARG, "grip_qpos_idx out of range");
-
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(MOPA_ERR_HIP, "no HIP device available (this library has no CPU fallback)");
-    auto *S = new MopaEnv();
-    if (desc->device >= 0) {
-        if (desc->device >= ndev) { delete S; return fail(MOPA_ERR_INVALID_ARG, "device ordinal out of range"); }
-        S->device = desc->device;
-    } else if (hipGetDevice(&S->device) != hipSuccess) { delete S; return fail(MOPA_ERR_HIP, "hipGetDevice failed"); }
+    if (const int rc = check_model_structure(m)) return rc;
 
     // closure of the frame bodies, in id (= DFS preorder) order
     std::vector<char> needed(m.nbody, 0);
@@ -649,29 +643,23 @@ extern "C" int mopa_env_create(const MopaEnvDesc *desc, MopaEnv **out) {
         if (needed[b]) { k_of[b] = (int)body_of.size(); body_of.push_back(b); }
     const int nb = (int)body_of.size();
 
-    std::vector<int32_t> bi(8 * (size_t)nb, 0), j_type, j_qadr;
+    std::vector<int32_t> bi(8 * (size_t)nb, 0), j_type, j_qadr, parent_k(nb);
     std::vector<double> bd(16 * (size_t)nb, 0.0), j_axis, j_pos, j_ref;
-    std::vector<int> parent_k(nb);
     for (int k = 0; k < nb; k++) {
         const int b = body_of[k];
         parent_k[k] = m.body_parent[b] > 0 ? k_of[m.body_parent[b]] : -1;
-        double *d = &bd[16 * (size_t)k];
-        std::memcpy(d, m.body_pos + 3 * b, 24);
-        std::memcpy(d + 3, m.body_quat + 4 * b, 32);
+        fill_body_record(m, b, &bd[16 * (size_t)k]);
         int32_t *r = &bi[8 * (size_t)k];
         r[0] = m.body_jntnum[b];
         r[1] = (int)j_type.size();
         r[4] = -1;
         for (int j = m.body_jntadr[b]; j < m.body_jntadr[b] + m.body_jntnum[b]; j++) {
             const int t = m.jnt_type[j];
-            if (t == J_BALL) { delete S; return fail(MOPA_ERR_UNSUPPORTED, "ball joints are not supported"); }
-            if (t == J_FREE && m.body_jntnum[b] != 1) { delete S; return fail(MOPA_ERR_UNSUPPORTED, "free joint combined with other joints"); }
+            if (t == J_BALL) return fail(MOPA_ERR_UNSUPPORTED, "ball joints are not supported");
+            if (t == J_FREE && m.body_jntnum[b] != 1) return fail(MOPA_ERR_UNSUPPORTED, "free joint combined with other joints");
             if (j == m.body_jntadr[b]) {
                 r[4] = t;
                 r[5] = m.jnt_qposadr[j];
-                std::memcpy(d + 7, m.jnt_axis + 3 * j, 24);
-                std::memcpy(d + 10, m.jnt_pos + 3 * j, 24);
-                d[13] = (t == J_FREE) ? 0.0 : m.jnt_ref[j];
             }
             j_type.push_back(t);
             j_qadr.push_back(m.jnt_qposadr[j]);
@@ -680,32 +668,12 @@ extern "C" int mopa_env_create(const MopaEnvDesc *desc, MopaEnv **out) {
             j_ref.push_back(t == J_FREE ? 0.0 : m.jnt_ref[j]);
         }
     }
-    // DFS save-slot program (same scheme as the validity kernel)
-    int n_save = 0;
-    {
-        std::vector<char> need_save(nb, 0);
-        for (int k = 0; k < nb; k++)
-            if (parent_k[k] >= 0 && parent_k[k] != k - 1) need_save[parent_k[k]] = 1;
-        std::vector<int> depth(nb, 0), save_of(nb, -1);
-        for (int k = 0; k < nb; k++) {
-            const int pk = parent_k[k];
-            depth[k] = (pk >= 0) ? depth[pk] + (need_save[pk] ? 1 : 0) : 0;
-            if (need_save[k]) { save_of[k] = depth[k]; n_save = std::max(n_save, depth[k] + 1); }
-            bi[8 * (size_t)k + 2] = (pk < 0) ? -2 : (pk == k - 1 ? -1 : save_of[pk]);
-            bi[8 * (size_t)k + 3] = save_of[k];
-        }
-    }
-    if (((size_t)n_save * 7 + (size_t)(kind == MOPA_ENV_LIFT ? desc->n_touch : 0) * 12) * 64 * sizeof(double) > 62 * 1024) {
-        delete S;
+    const int n_save = save_slot_program(parent_k.data(), nb, bi.data() + 2, bi.data() + 3, 8);      // (EnvBodyI.load, .save)
+    if (((size_t)n_save * 7 + (size_t)n_touch * 12) * 64 * sizeof(double) > 62 * 1024)
         return fail(MOPA_ERR_LIMIT, "kinematic tree too branchy for the LDS save slots");
-    }
 
     // pack the blobs
-    std::vector<double> D;
-    std::vector<int32_t> I;
-    auto add_d = [&](const double *p, size_t n) { int o = (int)D.size(); D.insert(D.end(), p, p + n); while (D.size() & 1) D.push_back(0.0); return o; };
-    auto add_i = [&](const int32_t *p, size_t n) { int o = (int)I.size(); I.insert(I.end(), p, p + n); while (I.size() & 7) I.push_back(0); return o; };
-    EnvHdr &h = S->hdr;
+    EnvHdr &h = S.hdr;
     h.kind = kind;
     h.nq = m.nq; h.n_arm = desc->n_arm; h.n_grip = desc->n_grip; h.n_act = desc->n_act; h.nb = nb; h.n_save = n_save;
     h.n_frames = nf; h.n_touch = n_touch; h.n_touch_left = desc->n_touch_left;
@@ -715,30 +683,30 @@ extern "C" int mopa_env_create(const MopaEnvDesc *desc, MopaEnv **out) {
     for (int f = 0; f < kEnvMaxFrames; f++) h.frame_k[f] = f < nf ? k_of[desc->frame_body[f]] : -1;
     for (int f = 0; f < 2; f++) h.quat_k[f] = k_of[desc->quat_body[f]];
     for (int g = 0; g < kEnvMaxTouch; g++) h.touch_k[g] = g < n_touch ? k_of[m.geom_body[desc->touch_geom[g]]] : -1;
-    h.o_bi = add_i(bi.data(), bi.size());
-    h.o_bd = add_d(bd.data(), bd.size());
-    h.o_j_type = add_i(j_type.data(), j_type.size());
-    h.o_j_qadr = add_i(j_qadr.data(), j_qadr.size());
-    h.o_j_axis = add_d(j_axis.data(), j_axis.size());
-    h.o_j_pos = add_d(j_pos.data(), j_pos.size());
-    h.o_j_ref = add_d(j_ref.data(), j_ref.size());
-    h.o_arm = add_i(desc->arm_qpos_idx, desc->n_arm);
-    h.o_grip = add_i(desc->grip_qpos_idx, desc->n_grip);
-    h.o_act = add_i(desc->act_qpos_idx, desc->n_act);
-    h.o_act_lo = add_d(desc->act_ctrl_lo, desc->n_act);
-    h.o_act_hi = add_d(desc->act_ctrl_hi, desc->n_act);
-    h.o_lim = add_i(desc->qpos_limited, m.nq);
-    h.o_lo = add_d(desc->qpos_min, m.nq);
-    h.o_hi = add_d(desc->qpos_max, m.nq);
-    h.o_off = add_d(desc->frame_off, 3 * (size_t)nf);
-    h.o_tg = (int)D.size();
+    h.o_bi = B.add_i(bi);
+    h.o_bd = B.add_d(bd);
+    h.o_j_type = B.add_i(j_type);
+    h.o_j_qadr = B.add_i(j_qadr);
+    h.o_j_axis = B.add_d(j_axis);
+    h.o_j_pos = B.add_d(j_pos);
+    h.o_j_ref = B.add_d(j_ref);
+    h.o_arm = B.add_i(desc->arm_qpos_idx, desc->n_arm);
+    h.o_grip = B.add_i(desc->grip_qpos_idx, desc->n_grip);
+    h.o_act = B.add_i(desc->act_qpos_idx, desc->n_act);
+    h.o_act_lo = B.add_d(desc->act_ctrl_lo, desc->n_act);
+    h.o_act_hi = B.add_d(desc->act_ctrl_hi, desc->n_act);
+    h.o_lim = B.add_i(desc->qpos_limited, m.nq);
+    h.o_lo = B.add_d(desc->qpos_min, m.nq);
+    h.o_hi = B.add_d(desc->qpos_max, m.nq);
+    h.o_off = B.add_d(desc->frame_off, 3 * (size_t)nf);
+    h.o_tg = (int)B.D.size();
     if (n_touch > 0) {
         // touch geom records: local pos[3] quat[4] size[3] type rbound; the mesh's size slots = (vertex offset in this blob, count)
         const int cg0 = desc->touch_geom[0], mid = m.geom_dataid[cg0];
         const double *V = m.mesh_vert + 3 * (size_t)m.mesh_vertadr[mid];
         const int nv = m.mesh_vertnum[mid];
         std::vector<double> tg((size_t)kTgStride * n_touch, 0.0);
-        const int o_verts = (int)D.size() + (int)tg.size();
+        const int o_verts = (int)B.D.size() + (int)tg.size();
         for (int g = 0; g < n_touch; g++) {
             const int cg = desc->touch_geom[g];
             double *r = &tg[(size_t)kTgStride * g];
@@ -755,28 +723,47 @@ extern "C" int mopa_env_create(const MopaEnvDesc *desc, MopaEnv **out) {
                 r[11] = rbound_of(G_BOX, m.geom_size + 3 * cg);
             }
         }
-        add_d(tg.data(), tg.size());
-        if ((int)D.size() != o_verts) { delete S; return fail(MOPA_ERR_INVALID_ARG, "internal: touch table misaligned"); }
-        add_d(V, 3 * (size_t)nv);
+        B.add_d(tg);
+        if ((int)B.D.size() != o_verts) return fail(MOPA_ERR_INVALID_ARG, "internal: touch table misaligned");
+        B.add_d(V, 3 * (size_t)nv);
     }
     h.max_episode_steps = desc->max_episode_steps;
     h.ac_scale = desc->ac_scale; h.distance_threshold = desc->distance_threshold; h.success_reward = desc->success_reward;
-
-    DeviceGuard guard(S->device);
-    if (!guard.ok()) { delete S; return fail(MOPA_ERR_HIP, "hipSetDevice failed"); }
-    if (hipMalloc((void **)&S->d_dbl, D.size() * sizeof(double)) != hipSuccess ||
-        hipMalloc((void **)&S->d_int, I.size() * sizeof(int32_t)) != hipSuccess ||
-        hipMemcpy(S->d_dbl, D.data(), D.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(S->d_int, I.data(), I.size() * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess) {
-        delete S;
-        return fail(MOPA_ERR_HIP, "device allocation / upload of the env tables failed");
-    }
-    S->h_int = I;
-    *out = S;
+    S.h_int = B.I;
     return MOPA_OK;
 }
 
-static const std::vector<int32_t> &env_host_ints(const MopaEnv *env) { return env->h_int; }
+extern "C" int mopa_env_create(const MopaEnvDesc *desc, MopaEnv **out) {
+    if (!desc || !out) return fail(MOPA_ERR_INVALID_ARG, "null argument");
+    *out = nullptr;
+    auto S = std::make_unique<MopaEnv>();
+    BlobPacker B;
+    if (const int rc = env_build_host(desc, *S, B)) return rc;
+    if (const int rc = pick_device(desc->device, &S->device, "no HIP device available (this library has no CPU fallback)")) return rc;
+    DeviceGuard guard(S->device);
+    if (!guard.ok()) return fail(MOPA_ERR_HIP, "hipSetDevice failed");
+    if (upload_tables(B.D, B.I, &S->d_dbl, &S->d_int) != hipSuccess) return fail(MOPA_ERR_HIP, "device allocation / upload of the env tables failed");
+    *out = S.release();
+    return MOPA_OK;
+}
+
+// The host half alone: status, and for an accepted description the fingerprint of what mopa_env_create would upload (header, double
+// table, int table) with the walk's body and save-slot counts.
+static_assert(sizeof(EnvHdr) == offsetof(EnvHdr, ac_scale) + 3 * sizeof(double) && offsetof(EnvHdr, ac_scale) == offsetof(EnvHdr, max_episode_steps) + sizeof(int),
+              "EnvHdr has padding: mopa_env_tables_host would hash indeterminate bytes");
+extern "C" int mopa_env_tables_host(const MopaEnvDesc *desc, uint64_t *fingerprint, int32_t *nb, int32_t *n_save) {
+    MopaEnv S;
+    BlobPacker B;
+    if (const int rc = env_build_host(desc, S, B)) return rc;
+    Fnv f;
+    f.add(&S.hdr, sizeof(EnvHdr));
+    f.add(B.D);
+    f.add(B.I);
+    if (fingerprint) *fingerprint = f.f;
+    if (nb) *nb = S.hdr.nb;
+    if (n_save) *n_save = S.hdr.n_save;
+    return MOPA_OK;
+}
 
 extern "C" void mopa_env_destroy(MopaEnv *env) { delete env; }
 extern "C" int mopa_env_obs_dim(const MopaEnv *env) { return env ? env->hdr.obs_dim : -1; }

@@ -19,6 +19,7 @@
 #include "mopa_device.hpp"
 #include "mopa_fk.hpp"
 #include "mopa_host.hpp"
+#include "mopa_model_host.hpp"
 
 using namespace mopa;
 

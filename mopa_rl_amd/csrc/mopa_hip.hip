@@ -36,6 +36,7 @@
 #include "mopa_sep.hpp"
 #include "mopa_fk.hpp"
 #include "mopa_host.hpp"
+#include "mopa_model_host.hpp"
 
 using namespace mopa;
 
@@ -885,12 +886,7 @@ static int scene_create(const MopaSceneDesc *desc, int glue_a, int glue_b, MopaS
     const SceneHdr &h = S->hdr;
 
     // --- device upload ---
-    int ndev = mopa_device_count();
-    if (ndev <= 0) { delete S; return fail(MOPA_ERR_HIP, "no HIP device visible: libmopa_hip has no CPU fallback"); }
-    if (desc->device >= 0) {
-        if (desc->device >= ndev) { delete S; return fail(MOPA_ERR_INVALID_ARG, "device ordinal out of range"); }
-        S->device = desc->device;
-    } else if (hipGetDevice(&S->device) != hipSuccess) { delete S; return fail(MOPA_ERR_HIP, "hipGetDevice failed"); }
+    if (const int rc = pick_device(desc->device, &S->device, "no HIP device visible: libmopa_hip has no CPU fallback")) { delete S; return rc; }
     DeviceGuard guard(S->device);      // the caller's current device is restored on every exit path
     if (!guard.ok()) { delete S; return fail(MOPA_ERR_HIP, "cannot switch to the requested HIP device"); }
     hipDeviceProp_t prop;

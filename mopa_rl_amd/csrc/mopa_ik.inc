@@ -443,34 +443,27 @@ __global__ __launch_bounds__(64) void k_ik_displacement_pos(IkHdr h, const doubl
     }
 }
 
-extern "C" int mopa_ik_create(const MopaIkDesc *desc, MopaIk **out) {
-    if (!desc || !out) return fail(MOPA_ERR_INVALID_ARG, "null argument");
-    *out = nullptr;
+// Host half of IK creation: every argument check, the model's structure, then the compile -- the header into S.hdr, the tables into B.
+// No device.
+static int ik_build_host(const MopaIkDesc *desc, MopaIk &S, BlobPacker &B) {
+    if (!desc) return fail(MOPA_ERR_INVALID_ARG, "null argument");
     const MopaModel &m = desc->model;
     if (m.nq <= 0 || m.nbody <= 0) return fail(MOPA_ERR_INVALID_ARG, "empty model");
     if (desc->n_joints <= 0 || desc->n_joints > kIkMaxJ) return fail(MOPA_ERR_LIMIT, "IK supports 1..8 movable joints");
     if (desc->site_body <= 0 || desc->site_body >= m.nbody) return fail(MOPA_ERR_INVALID_ARG, "site_body out of range");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(MOPA_ERR_HIP, "no HIP device available (this library has no CPU fallback)");
-    auto *S = new MopaIk();
-    if (desc->device >= 0) {
-        if (desc->device >= ndev) { delete S; return fail(MOPA_ERR_INVALID_ARG, "device ordinal out of range"); }
-        S->device = desc->device;
-    } else if (hipGetDevice(&S->device) != hipSuccess) { delete S; return fail(MOPA_ERR_HIP, "hipGetDevice failed"); }
+    if (const int rc = check_model_structure(m)) return rc;
 
     // ancestor chain of the site's body, root first (a chain: no branching, no save slots needed -- kept general)
     std::vector<int> body_of;
     for (int b = desc->site_body; b > 0; b = m.body_parent[b]) body_of.push_back(b);
     std::reverse(body_of.begin(), body_of.end());
     const int nb = (int)body_of.size();
-    std::vector<int> k_of(m.nbody, -1);
-    for (int k = 0; k < nb; k++) k_of[body_of[k]] = k;
 
     std::vector<int32_t> col_of_joint(m.njnt, -1), col_type(kIkMaxJ, J_HINGE), col_adr(kIkMaxJ, 0);
     for (int c = 0; c < desc->n_joints; c++) {
         const int j = desc->joint_ids[c];
-        if (j < 0 || j >= m.njnt) { delete S; return fail(MOPA_ERR_INVALID_ARG, "joint id out of range"); }
-        if (m.jnt_type[j] != J_HINGE && m.jnt_type[j] != J_SLIDE) { delete S; return fail(MOPA_ERR_UNSUPPORTED, "IK joints must be hinge or slide"); }
+        if (j < 0 || j >= m.njnt) return fail(MOPA_ERR_INVALID_ARG, "joint id out of range");
+        if (m.jnt_type[j] != J_HINGE && m.jnt_type[j] != J_SLIDE) return fail(MOPA_ERR_UNSUPPORTED, "IK joints must be hinge or slide");
         col_of_joint[j] = c;
         col_type[c] = m.jnt_type[j];
         col_adr[c] = m.jnt_qposadr[j];
@@ -479,61 +472,71 @@ extern "C" int mopa_ik_create(const MopaIkDesc *desc, MopaIk **out) {
     std::vector<double> bd(16 * (size_t)nb, 0.0);
     for (int k = 0; k < nb; k++) {
         const int b = body_of[k];
-        double *d = &bd[16 * (size_t)k];
-        std::memcpy(d, m.body_pos + 3 * b, 24);
-        std::memcpy(d + 3, m.body_quat + 4 * b, 32);
-        int32_t *r = &bi[8 * (size_t)k];
         const int jn = m.body_jntnum[b];
-        if (jn > 1) { delete S; return fail(MOPA_ERR_UNSUPPORTED, "IK: bodies on the site's chain may carry at most one joint"); }
+        if (jn > 1) return fail(MOPA_ERR_UNSUPPORTED, "IK: bodies on the site's chain may carry at most one joint");
+        fill_body_record(m, b, &bd[16 * (size_t)k]);
+        int32_t *r = &bi[8 * (size_t)k];
         r[0] = jn;
         r[1] = (k == 0) ? -2 : -1;   // a chain: the parent is always the previous body
         r[2] = -1;
         r[3] = -1; r[5] = -1;
         if (jn == 1) {
             const int j = m.body_jntadr[b];
-            if (m.jnt_type[j] == J_BALL) { delete S; return fail(MOPA_ERR_UNSUPPORTED, "ball joints are not supported"); }
+            if (m.jnt_type[j] == J_BALL) return fail(MOPA_ERR_UNSUPPORTED, "ball joints are not supported");
             r[3] = m.jnt_type[j];
             r[4] = m.jnt_qposadr[j];
             r[5] = col_of_joint[j];
-            std::memcpy(d + 7, m.jnt_axis + 3 * j, 24);
-            std::memcpy(d + 10, m.jnt_pos + 3 * j, 24);
-            d[13] = (m.jnt_type[j] == J_FREE) ? 0.0 : m.jnt_ref[j];
         }
     }
-    std::vector<double> D;
-    std::vector<int32_t> I;
-    auto add_d = [&](const double *p, size_t n) { int o = (int)D.size(); D.insert(D.end(), p, p + n); while (D.size() & 1) D.push_back(0.0); return o; };
-    auto add_i = [&](const int32_t *p, size_t n) { int o = (int)I.size(); I.insert(I.end(), p, p + n); while (I.size() & 7) I.push_back(0); return o; };
-    IkHdr &h = S->hdr;
+    IkHdr &h = S.hdr;
     h.nq = m.nq; h.nb = nb; h.n_save = 0; h.n_joints = desc->n_joints; h.site_k = nb - 1;
-    h.o_bi = add_i(bi.data(), bi.size());
-    h.o_bd = add_d(bd.data(), bd.size());
-    h.o_col_type = add_i(col_type.data(), col_type.size());
-    h.o_col_adr = add_i(col_adr.data(), col_adr.size());
+    h.o_bi = B.add_i(bi);
+    h.o_bd = B.add_d(bd);
+    h.o_col_type = B.add_i(col_type);
+    h.o_col_adr = B.add_i(col_adr);
     {
         int n_pre = 0;
         while (n_pre < nb - 1 && m.body_jntnum[body_of[n_pre]] == 0) n_pre++;      // (never the site's own body: its frame closes the walk)
         h.n_pre = (desc->n_joints > 0 && !std::getenv("MOPA_IK_NO_PREFIX")) ? n_pre : 0;
     }
-    h.o_off = add_d(desc->site_off, 3);
+    h.o_off = B.add_d(desc->site_off, 3);
     {
         const double *sq = desc->site_quat;
         const bool ident = (sq[0] == 0.0 && sq[1] == 0.0 && sq[2] == 0.0 && sq[3] == 0.0) || (sq[0] == 1.0 && sq[1] == 0.0 && sq[2] == 0.0 && sq[3] == 0.0);
         double sm[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
         if (!ident) quat2mat(sm, Q4{sq[0], sq[1], sq[2], sq[3]});
-        h.o_smat = add_d(sm, 9);
+        h.o_smat = B.add_d(sm, 9);
         h.has_smat = ident ? 0 : 1;
     }
-    DeviceGuard guard0(S->device);
-    if (!guard0.ok()) { delete S; return fail(MOPA_ERR_HIP, "hipSetDevice failed"); }
-    if (hipMalloc((void **)&S->d_dbl, D.size() * sizeof(double)) != hipSuccess ||
-        hipMalloc((void **)&S->d_int, I.size() * sizeof(int32_t)) != hipSuccess ||
-        hipMemcpy(S->d_dbl, D.data(), D.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(S->d_int, I.data(), I.size() * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess) {
-        delete S;
-        return fail(MOPA_ERR_HIP, "device allocation / upload of the IK tables failed");
-    }
-    *out = S;
+    return MOPA_OK;
+}
+
+extern "C" int mopa_ik_create(const MopaIkDesc *desc, MopaIk **out) {
+    if (!desc || !out) return fail(MOPA_ERR_INVALID_ARG, "null argument");
+    *out = nullptr;
+    auto S = std::make_unique<MopaIk>();
+    BlobPacker B;
+    if (const int rc = ik_build_host(desc, *S, B)) return rc;
+    if (const int rc = pick_device(desc->device, &S->device, "no HIP device available (this library has no CPU fallback)")) return rc;
+    DeviceGuard guard(S->device);
+    if (!guard.ok()) return fail(MOPA_ERR_HIP, "hipSetDevice failed");
+    if (upload_tables(B.D, B.I, &S->d_dbl, &S->d_int) != hipSuccess) return fail(MOPA_ERR_HIP, "device allocation / upload of the IK tables failed");
+    *out = S.release();
+    return MOPA_OK;
+}
+
+// The host half alone: status, and for an accepted description the fingerprint of what mopa_ik_create would upload (header -- all
+// ints, no padding --, double table, int table) with the chain's body count.
+extern "C" int mopa_ik_tables_host(const MopaIkDesc *desc, uint64_t *fingerprint, int32_t *nb) {
+    MopaIk S;
+    BlobPacker B;
+    if (const int rc = ik_build_host(desc, S, B)) return rc;
+    Fnv f;
+    f.add(&S.hdr, sizeof(IkHdr));
+    f.add(B.D);
+    f.add(B.I);
+    if (fingerprint) *fingerprint = f.f;
+    if (nb) *nb = S.hdr.nb;
     return MOPA_OK;
 }
 

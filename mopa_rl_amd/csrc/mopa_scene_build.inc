@@ -90,30 +90,7 @@ int SceneBuild::check_model() {
     // depending on the cull, and MuJoCo's own contact list (dist < margin) would have to be reproduced.  The reference
     // passes negative thresholds (config/sawyer.py:98-100, config/pusher.py:79-81); 0 keeps "any penetration".
     if (desc->contact_threshold > 0.0) return fail(MOPA_ERR_UNSUPPORTED, "contact_threshold > 0 is not supported (the broad phase culls at zero margin)");
-    // The structure every later step indexes with (the preconditions of MopaModel, include/mopa_hip.h).  MuJoCo's compiler emits
-    // nothing else; a model built by hand is refused here instead of read out of bounds there.
-    if (m.njnt < 0 || m.npair < 0 || m.nmesh < 0 || m.nmeshvert < 0) return fail(MOPA_ERR_INVALID_ARG, "negative count in the model");
-    for (int b = 1; b < m.nbody; b++) {
-        const int p = m.body_parent[b];
-        if (p < 0 || p >= b) return fail(MOPA_ERR_INVALID_ARG, "body_parent[" + std::to_string(b) + "] out of range (a body's parent must come before it)");
-        // depth-first order: the parent is the previous body or one of its ancestors.  The save slots of the DFS program (dfs_program)
-        // are numbered by depth, which parks a pose under a slot that is still needed when siblings' subtrees interleave.
-        int a = b - 1;
-        while (a > p) a = m.body_parent[a];
-        if (a != p) return fail(MOPA_ERR_UNSUPPORTED, "bodies are not in depth-first order (body " + std::to_string(b) + ")");
-    }
-    for (int b = 0; b < m.nbody; b++) {
-        const int n = m.body_jntnum[b], a = m.body_jntadr[b];
-        if (n < 0 || (n > 0 && (a < 0 || a > m.njnt - n))) return fail(MOPA_ERR_INVALID_ARG, "body_jntadr + body_jntnum out of range (body " + std::to_string(b) + ")");
-    }
-    for (int j = 0; j < m.njnt; j++) {
-        const int t = m.jnt_type[j];
-        if (t != J_FREE && t != J_BALL && t != J_SLIDE && t != J_HINGE) return fail(MOPA_ERR_INVALID_ARG, "unknown joint type " + std::to_string(t));
-        const int w = (t == J_FREE) ? 7 : (t == J_BALL ? 4 : 1);
-        if (m.jnt_qposadr[j] < 0 || m.jnt_qposadr[j] > m.nq - w) return fail(MOPA_ERR_INVALID_ARG, "jnt_qposadr out of range (joint " + std::to_string(j) + ")");
-    }
-    for (int g = 0; g < m.ngeom; g++)   // (a mesh geom's geom_dataid: static_frames, with the hull it names)
-        if (m.geom_body[g] < 0 || m.geom_body[g] >= m.nbody) return fail(MOPA_ERR_INVALID_ARG, "geom_body out of range (geom " + std::to_string(g) + ")");
+    if (const int rc = check_model_structure(m)) return rc;
     for (int p = 0; p < m.npair; p++) {
         const int g1 = m.pair_geom[2 * p], g2 = m.pair_geom[2 * p + 1];
         if (g1 < 0 || g1 >= m.ngeom || g2 < 0 || g2 >= m.ngeom) return fail(MOPA_ERR_INVALID_ARG, "pair_geom out of range");
@@ -406,35 +383,18 @@ int SceneBuild::geoms_and_pairs() {
 // 5. second-generation kernel: DFS program over the moving bodies, save slots
 int SceneBuild::dfs_program() {
     // --- second-generation kernel: DFS program over the moving bodies + per-geom pair lists ---
-    mb_load.assign(nmb, -1);
-    mb_save.assign(nmb, -1);
+    mb_load.resize(nmb);
+    mb_save.resize(nmb);
     mb_mgadr.assign(nmb, 0);
     mb_mgnum.assign(nmb, 0);
-    n_save = 0;
-    {
-        std::vector<char> need_save(nmb, 0);
-        for (int k = 0; k < nmb; k++) {
-            int pk = mb_parent[k];
-            if (pk >= 0 && pk != k - 1) need_save[pk] = 1;
-        }
-        std::vector<int> save_depth(nmb, 0);   // number of saved proper ancestors
-        for (int k = 0; k < nmb; k++) {
-            int pk = mb_parent[k];
-            save_depth[k] = (pk >= 0) ? save_depth[pk] + (need_save[pk] ? 1 : 0) : 0;
-            if (need_save[k]) { mb_save[k] = save_depth[k]; n_save = std::max(n_save, save_depth[k] + 1); }
-            if (pk < 0) mb_load[k] = -2;
-            else if (pk == k - 1) mb_load[k] = -1;
-            else mb_load[k] = mb_save[pk];
-        }
-        if (glued() && mb_save[mb_of_body[glue_a]] >= 0) {
-            // The save slots above are numbered by depth, which is right for a tree in depth-first body order.  The carried body comes
-            // long after body_a's own subtree, and whatever was parked at body_a's depth in between has overwritten its slot: body_a gets a
-            // slot of its own.
-            const int ka = mb_of_body[glue_a];
-            mb_save[ka] = n_save++;
-            for (int k = 0; k < nmb; k++)
-                if (mb_parent[k] == ka && mb_load[k] >= 0) mb_load[k] = mb_save[ka];
-        }
+    n_save = save_slot_program(mb_parent.data(), nmb, mb_load.data(), mb_save.data());
+    if (glued() && mb_save[mb_of_body[glue_a]] >= 0) {
+        // The save slots are numbered by depth, which is right for a tree in depth-first body order.  The carried body comes long after
+        // body_a's own subtree, and whatever was parked at body_a's depth in between has overwritten its slot: body_a gets a slot of its own.
+        const int ka = mb_of_body[glue_a];
+        mb_save[ka] = n_save++;
+        for (int k = 0; k < nmb; k++)
+            if (mb_parent[k] == ka && mb_load[k] >= 0) mb_load[k] = mb_save[ka];
     }
     // moving geoms are in geom-id order == body order, so each body's geoms are a contiguous slot range
     for (int mslot = 0; mslot < nmg; mslot++) {
@@ -862,18 +822,14 @@ static int scene_build_host(const MopaSceneDesc *desc, MopaScene *S, int glue_a 
 static_assert(offsetof(SceneHdr, thr) == offsetof(SceneHdr, wave_bytes) + sizeof(int) && sizeof(SceneHdr) == offsetof(SceneHdr, nn_eps) + sizeof(double),
               "SceneHdr has padding: k1_fingerprint would hash indeterminate bytes");
 static uint64_t k1_fingerprint(const MopaScene *S) {
-    uint64_t f = 0xcbf29ce484222325ull;
-    auto add = [&f](const void *p, size_t n) {
-        const unsigned char *b = static_cast<const unsigned char *>(p);
-        for (size_t i = 0; i < n; i++) f = (f ^ b[i]) * 0x100000001b3ull;
-    };
-    add(S->h_dbl.data(), S->h_dbl.size() * sizeof(double));
-    add(S->h_int.data(), S->h_int.size() * sizeof(int32_t));
-    add(S->h_gp_tab.data(), S->h_gp_tab.size() * sizeof(int32_t));
+    Fnv f;
+    f.add(S->h_dbl);
+    f.add(S->h_int);
+    f.add(S->h_gp_tab);
     SceneHdr h = S->hdr;
     h.range = 0.0; h.resolution = 0.0; h.nn_eps = 0.0;
-    add(&h, sizeof(SceneHdr));
-    return f;
+    f.add(&h, sizeof(SceneHdr));
+    return f.f;
 }
 // baked scene of this fingerprint (its index in MOPA_K1_BAKED_SCENES, from 1), 0 = none
 static int k1_baked_index(uint64_t fp) {

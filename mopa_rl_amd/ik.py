@@ -23,22 +23,30 @@ from .batch import _ptr, _stream_handle, _torch
 IKResult = collections.namedtuple("IKResult", ["qpos", "err_norm", "steps", "success"])
 
 
+def ik_desc(model, site: str, joint_names: Sequence[str], device: int = -1):
+    """(MopaIkDesc, keep) of a site and its movable joints on a CompiledModel; `keep` owns the arrays the description points into.
+    Needs no device."""
+    si = model.site_name2id(site)
+    keep = []
+    d = _lib.MopaIkDesc()
+    d.model = _lib.model_struct(model, keep)
+    ji, jp = _lib._i(np.array([model.joint_name2id(j) for j in joint_names], dtype=np.int32))
+    keep.append(ji)
+    d.n_joints, d.joint_ids = len(ji), jp
+    d.site_body, d.device = int(model.site_body[si]), int(device)
+    d.site_off = (C.c_double * 3)(*np.asarray(model.site_pos[si], dtype=np.float64))
+    d.site_quat = (C.c_double * 4)(*np.asarray(model.site_quat[si], dtype=np.float64))
+    return d, keep
+
+
 class BatchIK:
     def __init__(self, model, site: str, joint_names: Sequence[str], device: int = -1):
         L = _lib.lib()
         self.model = model
-        si = model.site_name2id(site)
-        self.site_body = int(model.site_body[si])
-        self.site_off = np.asarray(model.site_pos[si], dtype=np.float64)
-        self.joint_ids = np.array([model.joint_name2id(j) for j in joint_names], dtype=np.int32)
-        keep = []
-        d = _lib.MopaIkDesc()
-        d.model = _lib.model_struct(model, keep)
-        ji, jp = _lib._i(self.joint_ids)
-        keep.append(ji)
-        d.n_joints, d.joint_ids = len(ji), jp
-        d.site_body, d.site_off, d.device = self.site_body, (C.c_double * 3)(*self.site_off), int(device)
-        d.site_quat = (C.c_double * 4)(*np.asarray(model.site_quat[si], dtype=np.float64))
+        d, keep = ik_desc(model, site, joint_names, device)
+        self.site_body = int(d.site_body)
+        self.site_off = np.array(d.site_off, dtype=np.float64)
+        self.joint_ids = keep[-1]       # (ik_desc keeps the joint id array last)
         h = C.c_void_p()
         _lib.check(L.mopa_ik_create(C.byref(d), C.byref(h)))
         self._h = h

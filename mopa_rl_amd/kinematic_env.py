@@ -190,6 +190,73 @@ def push_env_facts(model) -> EnvFacts:
     return env_facts("SawyerPushObstacle-v0", model)
 
 
+def _packers(keep: list):
+    """(ip, dp): int32 / float64 array -> ctypes pointer, the array kept alive in `keep`."""
+    def ip(a):
+        a, p = _lib._i(a); keep.append(a); return p
+
+    def dp(a):
+        a, p = _lib._d(a); keep.append(a); return p
+
+    return ip, dp
+
+
+def env_desc(model, facts: EnvFacts, ac_scale: float, distance_threshold: float = 0.06, success_reward: float = 150.0,
+             max_episode_steps: int = 250, device: int = -1):
+    """(MopaEnvDesc, keep) of an env's facts on a CompiledModel; `keep` owns the arrays the description points into.  Needs no device."""
+    f = facts
+    keep = []
+    ip, dp = _packers(keep)
+    desc = _lib.MopaEnvDesc()
+    desc.model = _lib.model_struct(model, keep)
+    desc.kind = f.kind
+    desc.n_arm, desc.arm_qpos_idx = len(f.arm_qpos_idx), ip(f.arm_qpos_idx)
+    desc.n_grip, desc.grip_qpos_idx = len(f.grip_qpos_idx), ip(f.grip_qpos_idx)
+    desc.n_act, desc.act_qpos_idx, desc.act_ctrl_lo, desc.act_ctrl_hi = len(f.act_qpos_idx), ip(f.act_qpos_idx), dp(f.act_lo), dp(f.act_hi)
+    desc.n_frames, desc.frame_body, desc.frame_off = len(f.frame_body), ip(f.frame_body), dp(f.frame_off)
+    desc.n_quats, desc.quat_body = len(f.quat_body), ip(f.quat_body)
+    desc.n_touch, desc.touch_geom, desc.n_touch_left = len(f.touch_geom), ip(f.touch_geom), int(f.n_touch_left)
+    desc.qpos_min, desc.qpos_max, desc.qpos_limited = dp(f.qpos_min), dp(f.qpos_max), ip(f.qpos_limited)
+    desc.ac_scale = float(ac_scale)
+    desc.distance_threshold = float(distance_threshold)
+    desc.success_reward = float(success_reward)
+    desc.max_episode_steps = int(max_episode_steps)
+    desc.device = int(device)
+    return desc, keep
+
+
+def dyn_desc(dyn_facts, obj_facts=None):
+    """(MopaDynDesc, keep) of dynamics.dyn_facts [+ the penalty object of dynamics.obj_facts].  Needs no device."""
+    df, of = dyn_facts, obj_facts
+    keep = []
+    ip, dp = _packers(keep)
+    dd = _lib.MopaDynDesc()
+    dd.nd = df.nd
+    dd.parent, dd.jtype, dd.qadr = ip(df.parent), ip(df.jtype), ip(df.qadr)
+    dd.rel_pos, dd.rel_quat, dd.axis, dd.jpos, dd.qref = dp(df.rel_pos), dp(df.rel_quat), dp(df.axis), dp(df.jpos), dp(df.qref)
+    dd.mass, dd.ipos, dd.inertia = dp(df.mass), dp(df.ipos), dp(df.inertia)
+    dd.damping, dd.armature = dp(df.damping), dp(df.armature)
+    dd.limited, dd.lo, dd.hi = ip(df.limited), dp(df.lo), dp(df.hi)
+    dd.actuated, dd.kp, dd.force_lo, dd.force_hi, dd.gravcomp = ip(df.actuated), dp(df.kp), dp(df.force_lo), dp(df.force_hi), ip(df.gravcomp)
+    dd.gravity = (C.c_double * 3)(*[float(x) for x in df.gravity])
+    dd.timestep, dd.nsub = float(df.timestep), int(df.nsub)
+    if of is not None:
+        od = _lib.MopaObjDesc()
+        od.qadr, od.mass, od.damping, od.rbound = int(of.qadr), float(of.mass), float(of.damping), float(of.rbound)
+        od.inertia = (C.c_double * 3)(*[float(x) for x in of.inertia])
+        od.half = (C.c_double * 3)(*[float(x) for x in of.half])
+        od.nfeat, od.feat = len(of.feat), dp(of.feat)
+        od.ncol, od.co_body, od.co_type = len(of.co_body), ip(of.co_body), ip(of.co_type)
+        od.co_size, od.co_pos, od.co_mat, od.co_mu, od.co_rbound = dp(of.co_size), dp(of.co_pos), dp(of.co_mat), dp(of.co_mu), dp(of.co_rbound)
+        od.kn, od.dn, od.eps_v, od.ct_max = float(of.kn), float(of.dn), float(of.eps_v), float(of.ct_max)
+        od.inv_mass = float(of.inv_mass)
+        od.inv_inertia = (C.c_double * 3)(*[float(x) for x in of.inv_inertia])
+        od.precull_every, od.precull_margin = int(of.precull_every), float(of.precull_margin)
+        keep.append(od)
+        dd.obj = C.pointer(od)
+    return dd, keep
+
+
 class BatchKinematicEnv:
     """E envs of one of the three Sawyer obstacle tasks -- or of PusherObstacle-v0 (KIND_PUSHER: four hinges, joint0 unlimited) --
     stepped kinematically on one GPU."""
@@ -223,29 +290,9 @@ class BatchKinematicEnv:
         self.max_episode_steps = int(max_episode_steps)
         self.ac_scale = float(self.spec.ac_scale if ac_scale is None else ac_scale)
         L = _lib.lib()
-        keep = []
-        desc = _lib.MopaEnvDesc()
-        desc.model = _lib.model_struct(self.model, keep)
-
-        def ip(a):
-            a, p = _lib._i(a); keep.append(a); return p
-
-        def dp(a):
-            a, p = _lib._d(a); keep.append(a); return p
-
-        desc.kind = f.kind
-        desc.n_arm, desc.arm_qpos_idx = self.n_arm, ip(f.arm_qpos_idx)
-        desc.n_grip, desc.grip_qpos_idx = len(f.grip_qpos_idx), ip(f.grip_qpos_idx)
-        desc.n_act, desc.act_qpos_idx, desc.act_ctrl_lo, desc.act_ctrl_hi = len(f.act_qpos_idx), ip(f.act_qpos_idx), dp(f.act_lo), dp(f.act_hi)
-        desc.n_frames, desc.frame_body, desc.frame_off = len(f.frame_body), ip(f.frame_body), dp(f.frame_off)
-        desc.n_quats, desc.quat_body = len(f.quat_body), ip(f.quat_body)
-        desc.n_touch, desc.touch_geom, desc.n_touch_left = len(f.touch_geom), ip(f.touch_geom), int(f.n_touch_left)
-        desc.qpos_min, desc.qpos_max, desc.qpos_limited = dp(f.qpos_min), dp(f.qpos_max), ip(f.qpos_limited)
-        desc.ac_scale = self.ac_scale
-        desc.distance_threshold = float(distance_threshold)
-        desc.success_reward = float(success_reward)
-        desc.max_episode_steps = self.max_episode_steps
-        desc.device = self.device.index if self.device.index is not None else -1
+        desc, keep = env_desc(self.model, f, ac_scale=self.ac_scale, distance_threshold=distance_threshold, success_reward=success_reward,
+                              max_episode_steps=self.max_episode_steps, device=self.device.index if self.device.index is not None else -1)
+        ip, dp = _packers(keep)
         h = C.c_void_p()
         _lib.check(L.mopa_env_create(C.byref(desc), C.byref(h)))
         self._h = h
@@ -282,16 +329,6 @@ class BatchKinematicEnv:
         elif self.dynamics:
             from .dynamics import dyn_facts
             self.dyn = df = dyn_facts(self.model, f, frame_dt=frame_dt)
-            dd = _lib.MopaDynDesc()
-            dd.nd = df.nd
-            dd.parent, dd.jtype, dd.qadr = ip(df.parent), ip(df.jtype), ip(df.qadr)
-            dd.rel_pos, dd.rel_quat, dd.axis, dd.jpos, dd.qref = dp(df.rel_pos), dp(df.rel_quat), dp(df.axis), dp(df.jpos), dp(df.qref)
-            dd.mass, dd.ipos, dd.inertia = dp(df.mass), dp(df.ipos), dp(df.inertia)
-            dd.damping, dd.armature = dp(df.damping), dp(df.armature)
-            dd.limited, dd.lo, dd.hi = ip(df.limited), dp(df.lo), dp(df.hi)
-            dd.actuated, dd.kp, dd.force_lo, dd.force_hi, dd.gravcomp = ip(df.actuated), dp(df.kp), dp(df.force_lo), dp(df.force_hi), ip(df.gravcomp)
-            dd.gravity = (C.c_double * 3)(*[float(x) for x in df.gravity])
-            dd.timestep, dd.nsub = float(df.timestep), int(df.nsub)
             self.obj = None
             self.ct = None
             if contacts == "penalty":
@@ -300,23 +337,12 @@ class BatchKinematicEnv:
                     raise _lib.MopaError("contacts='penalty': the penalty-contact object model is built for the Push cube only")
                 from .dynamics import obj_facts
                 self.obj = of = obj_facts(self.model, df)
-                od = _lib.MopaObjDesc()
-                od.qadr, od.mass, od.damping, od.rbound = int(of.qadr), float(of.mass), float(of.damping), float(of.rbound)
-                od.inertia = (C.c_double * 3)(*[float(x) for x in of.inertia])
-                od.half = (C.c_double * 3)(*[float(x) for x in of.half])
-                od.nfeat, od.feat = len(of.feat), dp(of.feat)
-                od.ncol, od.co_body, od.co_type = len(of.co_body), ip(of.co_body), ip(of.co_type)
-                od.co_size, od.co_pos, od.co_mat, od.co_mu, od.co_rbound = dp(of.co_size), dp(of.co_pos), dp(of.co_mat), dp(of.co_mu), dp(of.co_rbound)
-                od.kn, od.dn, od.eps_v, od.ct_max = float(of.kn), float(of.dn), float(of.eps_v), float(of.ct_max)
-                od.inv_mass = float(of.inv_mass)
-                od.inv_inertia = (C.c_double * 3)(*[float(x) for x in of.inv_inertia])
-                od.precull_every, od.precull_margin = int(of.precull_every), float(of.precull_margin)
-                keep.append(od)
-                dd.obj = C.pointer(od)
             elif contacts:
                 # stage C: contacts of arm and object behind the constraint solver, all three envs
                 from .dynamics import contact_facts
                 self.ct = contact_facts(self.model, df, OBJECT_BODY[f.kind], qpos_ref=self.init_qpos_row, **(contact_options or {}))
+            dd, dkeep = dyn_desc(df, self.obj)
+            keep.append(dkeep)
             _lib.check(L.mopa_env_attach_dynamics(self._h, C.byref(dd)))
             assert L.mopa_env_dyn_dofs(self._h) == df.nd
             if dyn_lanes not in (1, 16):
