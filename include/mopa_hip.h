@@ -409,6 +409,38 @@ int mopa_plan_star(MopaScene *scene, const double *start_host, const double *goa
 int mopa_plan_star_k(int32_t na, int64_t n, double rewire_factor);
 int mopa_star_params_size(void);
 
+/* K3b under the maximize-min-clearance objective, band-limited: RRT* that optimises the quantity mopa_path_clearance_batch measures.
+ * Same shape as mopa_plan_star_batch (one wave per query, asynchronous on `stream`, no read-back, MopaStarParams unchanged); the
+ * definition is the sequential form tests/star_clearance_ref.py ("K3b under the clearance objective").
+ *   band:         finite, >= 0 and above the scene's contact_threshold; every clearance saturates at it.
+ *   motion value: mc(a -> b) = mopa_motion_clearance_batch's `clearance` of the segment on the passive entries of start[e]; a motion
+ *                 is valid iff mc > contact_threshold, which is mopa_check_motion_batch's verdict.
+ *   key:          a chain's cost is the pair (C, L): C = min(the clearance of the start state, the values of its edges), L = its L1
+ *                 length; (C1, L1) is better than (C2, L2) iff C1 > C2 or (C1 == C2 and L1 < L2).  LEXICOGRAPHIC ON PURPOSE: OMPL's
+ *                 pure minimax cost ties wherever nothing is in band and never rewires there.  Where no evaluated motion is in band
+ *                 the planner is mopa_plan_star_batch bit for bit.
+ *   parent:       exact branch and bound over the neighbours' bounds (C[i], L[i] + dist), best first, starting from the nearest node;
+ *   rewire:       pre-tested on the bound, then evaluated from the new state to the neighbour (no value is reused across directions).
+ *   node set:     draws, nearest, steering, the full-tree rule, k(n) and the goal rules are mopa_plan_star_batch's, so for equal seed,
+ *                 ids and parameters status (up to max_path), nodes, goal nodes and first goal iteration equal that planner's.
+ *   results:      the chain of the goal node with the best key (the earliest among equals); clearance[e] = its C, which is the bits
+ *                 of mopa_path_clearance_batch on the returned rows (vertex 0 counted), length[e] = its L.  Unless status[e] = 0:
+ *                 path_len[e] = 0, clearance[e] = -inf, length[e] = +inf.
+ *   info_dev:     nullable, [E,11]: columns 0-7 as mopa_plan_star_batch with column 2 counting motion evaluations (motions, never
+ *                 states; an evaluation may stop at the first state at or below the threshold), 8 = evaluations of the parent walk,
+ *                 9 = evaluations of the rewire step, 10 = rewires that strictly raised C.
+ * Refused before any launch: everything mopa_plan_star_batch refuses; band negative, NaN or infinite, band <= contact_threshold
+ * (MOPA_ERR_INVALID_ARG); a glued scene, a scene created with pair_cull_radius (MOPA_ERR_UNSUPPORTED); LDS (MOPA_ERR_LIMIT).
+ * E == 0 returns MOPA_OK without a launch. */
+int mopa_plan_star_clearance_batch(MopaScene *scene, const double *start_dev /*[E,nq]*/, const double *goal_dev /*[E,nq]*/, int64_t E,
+                                   const MopaStarParams *params, double band, double *path_dev /*[E,max_path,nq]*/,
+                                   int32_t *path_len_dev /*[E]*/, int32_t *status_dev /*[E]*/, double *clearance_dev /*[E]*/,
+                                   double *length_dev /*[E] nullable*/, int64_t *info_dev /*[E,11] nullable*/, void *stream);
+/* the single-query host form (host pointers, stream id = env_id_base, synchronous) */
+int mopa_plan_star_clearance(MopaScene *scene, const double *start_host, const double *goal_host, const MopaStarParams *params, double band,
+                             double *path_host /*[max_path,nq]*/, int32_t *path_len_out, int32_t *status_out, double *clearance_out,
+                             double *length_out /*nullable*/, int64_t *info_out /*[11] nullable*/);
+
 /* K3 race: E RRT-Connect queries, each run by `portfolio` = K members that share start, goal, env row and stream id and differ in
  * their seed only; asynchronous on `stream`, no read-back.  The result of a query is that of ONE member, chosen by a rule that does
  * not depend on timing (DESIGN.md "K3 race"; the sequential form is tests/race_ref.py):

@@ -30,6 +30,7 @@ EXPORTED_SYMBOLS = [
     "mopa_scene_k1_baked", "mopa_scene_k1_drain_plan", "mopa_scene_k1_export", "mopa_scene_hdr_offset", "mopa_k1_baked_fk_host", "mopa_k1_baked_fk_sparse_host", "mopa_k1_baked_fk_pose_host", "mopa_k1_baked_resident_host", "mopa_k1_baked_static_host",
     "mopa_is_valid_batch", "mopa_is_valid_batch_counted", "mopa_check_motion_batch", "mopa_plan_batch", "mopa_simplify_paths_batch", "mopa_simplify_paths_max_path", "mopa_shortcut_paths_batch", "mopa_shortcut_paths_max_path", "mopa_smooth_paths_batch", "mopa_smooth_paths_max_path",
     "mopa_plan_star_batch", "mopa_plan_star", "mopa_plan_star_k", "mopa_star_params_size",
+    "mopa_plan_star_clearance_batch", "mopa_plan_star_clearance",
     "mopa_plan_race_batch", "mopa_plan_race", "mopa_race_params_size", "mopa_pullback_batch", "mopa_is_valid_state", "mopa_plan",
     "mopa_planner_status", "mopa_debug_fk", "mopa_debug_pair_dist", "mopa_contacts_batch", "mopa_contacts_state",
     "mopa_contact_frames_batch", "mopa_contact_frames_state", "mopa_geom_frames_batch", "mopa_geom_frames_host",
@@ -178,6 +179,7 @@ class MopaRaceParams(C.Structure):
 RACE_INFO_COLS = 3          # members cut, checks spent by all members, the winner's iterations (-1: none)
 RACE_SEED_STEP = 0x9E3779B97F4A7C15     # member m of a query runs the seed (seed + m * RACE_SEED_STEP) mod 2^64
 STAR_INFO_COLS = 8          # iterations run, nodes, motion checks, rewires, goal nodes, first goal iteration, descendant updates, full-tree iterations
+STAR_CLEARANCE_INFO_COLS = 11   # ... with motion evaluations in column 2, then parent-walk evaluations, rewire evaluations, rewires that raised the clearance
 STAR_REWIRE_FACTOR = 1.1    # OMPL's default
 STAR_GOAL_BIAS = 0.05       # OMPL's default
 
@@ -230,6 +232,9 @@ def lib() -> C.CDLL:
     L.mopa_plan_star.argtypes = [vp, _dp, _dp, C.POINTER(MopaStarParams), _dp, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                  C.POINTER(C.c_double), C.POINTER(C.c_int64)]
     L.mopa_plan_star_k.argtypes = [C.c_int32, C.c_int64, C.c_double]
+    L.mopa_plan_star_clearance_batch.argtypes = [vp, vp, vp, C.c_int64, C.POINTER(MopaStarParams), C.c_double, vp, vp, vp, vp, vp, vp, vp]
+    L.mopa_plan_star_clearance.argtypes = [vp, _dp, _dp, C.POINTER(MopaStarParams), C.c_double, _dp, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                           C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64)]
     L.mopa_star_params_size.argtypes = []
     L.mopa_plan_race_batch.argtypes = [vp, vp, vp, C.c_int64, C.POINTER(MopaRaceParams), vp, vp, vp, vp, vp, vp, vp, vp]
     L.mopa_plan_race.argtypes = [vp, _dp, _dp, C.POINTER(MopaRaceParams), _dp, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
@@ -691,6 +696,24 @@ class Scene:
         check(lib().mopa_plan_star(self._h, sp, gp, C.byref(prm), path.ctypes.data_as(_dp), C.byref(plen), C.byref(st), C.byref(cost),
                                    info.ctypes.data_as(C.POINTER(C.c_int64))))
         return st.value, path[:plen.value].copy(), cost.value, info
+
+    def plan_star_clearance(self, start, goal, band: float, max_iters: int, max_nodes: Optional[int] = None, max_path: int = 512,
+                            seed: Optional[int] = None, env_id: int = 0, goal_bias: float = STAR_GOAL_BIAS, goal_threshold: float = 0.0,
+                            rewire_factor: float = STAR_REWIRE_FACTOR):
+        """one RRT* query under the maximize-min-clearance objective at `band` (DESIGN.md "K3b under the clearance objective"):
+        -> (status, path rows, clearance, length, info [11] int64); clearance = -inf and length = +inf unless status is 0"""
+        s, sp = _d(start)
+        g, gp = _d(goal)
+        nodes = int(max_iters) + 1 if max_nodes is None else int(max_nodes)
+        prm = MopaStarParams(int(max_iters), max(nodes, 2), int(max_path), int(self.seed if seed is None else seed) & 0xFFFFFFFFFFFFFFFF,
+                             int(env_id), None, None, float(goal_bias), float(goal_threshold), float(rewire_factor), 0)
+        path = np.zeros((max_path, self.nq))
+        info = np.zeros(STAR_CLEARANCE_INFO_COLS, dtype=np.int64)
+        plen, st, clr, length = C.c_int32(0), C.c_int32(0), C.c_double(0.0), C.c_double(0.0)
+        sc = self if self.glue is not None else self.contact_scene()        # the full pair list, as the clearance report; glue: refused
+        check(lib().mopa_plan_star_clearance(sc._h, sp, gp, C.byref(prm), float(band), path.ctypes.data_as(_dp), C.byref(plen), C.byref(st),
+                                             C.byref(clr), C.byref(length), info.ctypes.data_as(C.POINTER(C.c_int64))))
+        return st.value, path[:plen.value].copy(), clr.value, length.value, info
 
     def plan_race(self, start, goal, portfolio: int, max_iters: int, max_nodes: int = 4096, max_path: int = 512, seed: Optional[int] = None,
                   env_id: int = 0, no_abort: bool = False):

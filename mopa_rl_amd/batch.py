@@ -679,6 +679,51 @@ class BatchPlanner:
         self._k9_behind(path, plen, status, seed, env_id_base, env_ids, seeds, vertex_simplify, simplify_passes, path_shortcut, path_smooth, stream)
         return (path, plen, status, cost, info) if want_info else (path, plen, status, cost)
 
+    def plan_star_clearance(self, start, goal, band: float, max_iters: int = 2000, max_nodes: Optional[int] = None, max_path: int = 256,
+                            seed: int = 0, env_id_base: int = 0, stream=None, env_ids=None, seeds=None, max_workgroups: int = 0,
+                            goal_bias: float = _lib.STAR_GOAL_BIAS, goal_threshold: float = 0.0,
+                            rewire_factor: float = _lib.STAR_REWIRE_FACTOR, want_info: bool = False):
+        """E independent RRT* queries under the maximize-min-clearance objective, band-limited ("K3b under the
+        clearance objective"): the planner that optimises what `path_clearance` measures.  Returns (path [E, max_path, nq], path_len
+        [E], status [E], clearance [E], length [E]) and with `want_info` a sixth element, an int64 [E, 11] tensor: `plan_star`'s
+        eight columns with motion evaluations in column 2, then the evaluations of the parent walk, those of the rewire step, and the
+        rewires that strictly raised a clearance.  A chain's cost is the pair (clearance, larger is better; then L1 length, smaller
+        is better): `clearance` is the bits of `path_clearance(path, path_len, band).clearance`, `length` the chain's L1 length;
+        -inf and +inf unless status is 0.  `band`: finite, >= 0 and above the scene's contact threshold.  For equal seeds, ids and
+        parameters the tree holds the nodes `plan_star` grows; where no evaluated motion is in band the result is `plan_star`'s.
+        Every other keyword is `plan_star`'s.  Runs on the scene with the full pair list (`Scene.contact_scene`), as the clearance
+        report does; a glued scene raises.  The K9 switches are not offered: a simplifier behind this planner would change the
+        clearance it reports -- call `simplify_paths` and `path_clearance` on the result instead."""
+        torch = _torch()
+        _check_f64(start, "start", self.nq)
+        _check_f64(goal, "goal", self.nq)
+        E = start.shape[0]
+        dev = start.device
+        for t, name in ((env_ids, "env_ids"), (seeds, "seeds")):
+            if t is not None and (t.dtype != torch.int64 or not t.is_cuda or not t.is_contiguous() or tuple(t.shape) != (E,)):
+                raise _lib.MopaError(f"{name} must be a contiguous int64 GPU tensor of shape [E]")
+        nodes = int(max_iters) + 1 if max_nodes is None else int(max_nodes)
+
+        def alloc():
+            return (torch.zeros(E, max_path, self.nq, dtype=torch.float64, device=dev), torch.zeros(E, dtype=torch.int32, device=dev),
+                    torch.zeros(E, dtype=torch.int32, device=dev), torch.zeros(E, dtype=torch.float64, device=dev),
+                    torch.zeros(E, dtype=torch.float64, device=dev),
+                    torch.zeros(E, _lib.STAR_CLEARANCE_INFO_COLS, dtype=torch.int64, device=dev) if want_info else None)
+        if stream is not None:
+            with torch.cuda.stream(stream):
+                path, plen, status, clearance, length, info = alloc()
+        else:
+            path, plen, status, clearance, length, info = alloc()
+        prm = _lib.MopaStarParams(int(max_iters), max(nodes, 2), int(max_path), int(seed) & 0xFFFFFFFFFFFFFFFF, int(env_id_base),
+                                  _ptr(env_ids) if env_ids is not None else None, _ptr(seeds) if seeds is not None else None,
+                                  float(goal_bias), float(goal_threshold), float(rewire_factor), int(max_workgroups))
+        # the scene with the full pair list, as the clearance report runs on (a glued scene goes to the library as it is, which refuses it)
+        sc = self.scene if self.scene.glue is not None else self.scene.contact_scene()
+        _lib.check(_lib.lib().mopa_plan_star_clearance_batch(sc.handle, _ptr(start), _ptr(goal), E, C.byref(prm), float(band), _ptr(path),
+                                                             _ptr(plen), _ptr(status), _ptr(clearance), _ptr(length),
+                                                             _ptr(info) if info is not None else None, _stream_handle(stream)))
+        return (path, plen, status, clearance, length, info) if want_info else (path, plen, status, clearance, length)
+
     def plan_race(self, start, goal, portfolio: int = 4, max_iters: int = 2000, max_nodes: int = 1024, max_path: int = 256, seed: int = 0,
                   env_id_base: int = 0, env_ids=None, seeds=None, stream=None, max_workgroups: int = 0, no_abort: bool = False,
                   want_info: bool = False, vertex_simplify: bool = False, simplify_passes: int = 3, path_shortcut: bool = False,

@@ -1100,5 +1100,7 @@ extern "C" const char *mopa_planner_status(const MopaScene *S) { return S ? S->s
 #include "mopa_k9.inc"
 // K3b: RRT*, the reference's other planner algorithm (k_rrt_star, mopa_plan_star_batch); the K9 kernels' shape
 #include "mopa_rrtstar.inc"
+// ... under the maximize-min-clearance objective (k_rrt_star_clear, mopa_plan_star_clearance_batch): a kernel of its own next to it
+#include "mopa_rrtstar_clear.inc"
 #include "mopa_ik.inc"
 #include "mopa_paths.inc"

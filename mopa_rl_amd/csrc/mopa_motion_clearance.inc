@@ -26,6 +26,30 @@
 // survivors it evaluates -- a strictly smaller distance, or an equal one with a lower index -- and the wave reduces with
 // wave_argmin, the reduction k_proximity_rows selects its first record with: the same order by construction.  LDS is the
 // scene's own (S->lds_bytes).
+// One state of that sweep, for k_clearance_states and for RRT* under the clearance objective (mopa_rrtstar_clear.inc): the active
+// vector `q_active` on the env row `row` -> on every lane d = min(band, the smallest pair distance) and p = the nearest pair in
+// band, -1 when there is none.  The caller synchronises the wave before the worklist / geom slab are reused.
+template <bool MESH>
+MOPA_D void wave_state_clearance(const SceneHdr &h, const LdsView &v, int lane, const double *q_active, const double *row,
+                                 const int32_t *__restrict__ pair_model, double band, double &d_out, int &p_out) {
+    const int *I = v.ints;
+    wave_load_state(h, v, lane, q_active, row);
+    wave_fk(h, v, lane);
+    // margin broad phase
+    const int wl_count = wave_broad_phase(h, v, lane, CullBand{band});
+    double bd = kFar;
+    int bi = 0x7fffffff;
+    wave_each_survivor(h, v, lane, wl_count, [&](int p, int g1, int g2, int code) {
+        const double d = geom_sep<MESH>(code, geom_rec(h, v, g1), I[h.o_g_type + g1], geom_rec(h, v, g2), I[h.o_g_type + g2], band, v.dbl);
+        const int pm = pair_model[p];
+        if (d < bd || (d == bd && pm < bi)) { bd = d; bi = pm; }
+    });
+    wave_argmin(bd, bi);
+    const bool near = bd <= band && bd < kFar;      // (k_proximity_rows' count rule)
+    d_out = near ? bd : band;
+    p_out = near ? bi : -1;
+}
+
 template <bool MESH>
 __global__ __launch_bounds__(kBlock) void k_clearance_states(SceneHdr h, const double *__restrict__ g_dbl, const int32_t *__restrict__ g_int,
                                                              const int32_t *__restrict__ pair_model /*[h.npair] device pair -> index in the desc's pair list*/,
@@ -37,26 +61,15 @@ __global__ __launch_bounds__(kBlock) void k_clearance_states(SceneHdr h, const d
     LdsView v = make_view(h, smem);
     stage_scene(h, g_dbl, g_int, const_cast<double *>(v.dbl), const_cast<int *>(v.ints));
     const int lane = threadIdx.x & 63;
-    const int *I = v.ints;
     for (;;) {
         const long long s = wave_pull64(ctr, lane);
         if (s >= T) break;
-        wave_load_state(h, v, lane, q_states + s * h.na, qpos_env + (long long)env_of_state[s] * h.nq);
-        wave_fk(h, v, lane);
-        // margin broad phase
-        const int wl_count = wave_broad_phase(h, v, lane, CullBand{band});
-        double bd = kFar;
-        int bi = 0x7fffffff;
-        wave_each_survivor(h, v, lane, wl_count, [&](int p, int g1, int g2, int code) {
-            const double d = geom_sep<MESH>(code, geom_rec(h, v, g1), I[h.o_g_type + g1], geom_rec(h, v, g2), I[h.o_g_type + g2], band, v.dbl);
-            const int pm = pair_model[p];
-            if (d < bd || (d == bd && pm < bi)) { bd = d; bi = pm; }
-        });
-        wave_argmin(bd, bi);
+        double d;
+        int p;
+        wave_state_clearance<MESH>(h, v, lane, q_states + s * h.na, qpos_env + (long long)env_of_state[s] * h.nq, pair_model, band, d, p);
         if (lane == 0) {
-            const bool near = bd <= band && bd < kFar;      // (k_proximity_rows' count rule)
-            d_state[s] = near ? bd : band;
-            p_state[s] = near ? bi : -1;
+            d_state[s] = d;
+            p_state[s] = p;
         }
         wave_sync();   // worklist / geom slab are about to be reused
     }

@@ -41,7 +41,8 @@ static int star_list_bytes(int na) { return (8 * 5 * na + 15) & ~15; }
 static int star_lds_bytes(const MopaScene *S) {
     return ((S->lds_bytes + 15) & ~15) + (((int)sizeof(SceneHdr) + 15) & ~15) + kWavesPerBlock * star_list_bytes(S->na);
 }
-static long long star_tree_bytes(int na, int max_nodes) { return ((long long)max_nodes * (8 * na + 24 + 12) + 15) & ~15ll; }
+static int star_node_bytes(int na) { return 8 * na + 24 + 12; }       // one node of k_rrt_star's slab
+static long long star_tree_bytes(int max_nodes, int node_bytes) { return ((long long)max_nodes * node_bytes + 15) & ~15ll; }
 
 // reads of the tree at a wave-uniform index: what this wave's vector stores wrote must come back through the vector memory path
 MOPA_D double star_ld(const double *p) { return *reinterpret_cast<const volatile double *>(p); }
@@ -312,11 +313,9 @@ extern "C" int mopa_plan_star_k(int32_t na, int64_t n, double rewire_factor) {
     return k > 2147483647.0 ? 2147483647 : (int)k;
 }
 
-extern "C" int mopa_plan_star_batch(MopaScene *S, const double *start, const double *goal, int64_t E, const MopaStarParams *params, double *path,
-                                    int32_t *path_len, int32_t *status, double *cost, int64_t *info, void *stream) {
-    if (!S || !params || (E > 0 && (!start || !goal || !path || !path_len || !status))) return fail(MOPA_ERR_INVALID_ARG, "null argument");
-    const MopaStarParams &p = *params;
-    MOPA_REFUSE_GLUED(S, "RRT* (mopa_plan_star)");
+// What every RRT* entry refuses before a launch (`what`: the entry, `node_bytes`: one node of its tree slab), in this order.
+static int star_rules(MopaScene *S, const MopaStarParams &p, int64_t E, const char *what, int node_bytes) {
+    if (S->glue_b >= 0) return fail(MOPA_ERR_UNSUPPORTED, std::string(what) + " is not built for a glued scene (glue_bodies)");
     if (E < 0 || p.max_iters < 0 || p.max_nodes < 2 || p.max_path < 2 || !(p.goal_bias >= 0.0 && p.goal_bias <= 1.0) || !(p.goal_threshold >= 0.0) ||
         !(p.rewire_factor > 0.0) || !std::isfinite(p.rewire_factor))
         return fail(MOPA_ERR_INVALID_ARG, "bad RRT* parameters (E < 0, max_iters < 0, max_nodes < 2, max_path < 2, goal_bias outside [0, 1], "
@@ -324,17 +323,22 @@ extern "C" int mopa_plan_star_batch(MopaScene *S, const double *start, const dou
     if (mopa_plan_star_k(S->na, p.max_nodes, p.rewire_factor) > kStarMaxK)
         return fail(MOPA_ERR_UNSUPPORTED, "RRT*: k(max_nodes) = " + std::to_string(mopa_plan_star_k(S->na, p.max_nodes, p.rewire_factor)) +
                                               " neighbours, the kernel holds one per lane (64)");
-    const long long tree_bytes = star_tree_bytes(S->na, p.max_nodes);
-    if (tree_bytes * kWavesPerBlock > kStarMaxTreeBytes)
+    if (star_tree_bytes(p.max_nodes, node_bytes) * kWavesPerBlock > kStarMaxTreeBytes)
         return fail(MOPA_ERR_UNSUPPORTED, "RRT*: the trees of one workgroup (max_nodes = " + std::to_string(p.max_nodes) + ") do not fit the scratch");
     if (star_lds_bytes(S) > kMaxLdsBytes) return fail(MOPA_ERR_LIMIT, "RRT* LDS does not fit");
-    if (E == 0) return MOPA_OK;
-    ON_DEVICE(S->device);
-    // persistent workgroups: two per CU are resident (two waves per SIMD); max_workgroups > 0 caps them; fewer where the trees ask for it
-    int64_t nblk = std::min<int64_t>((E + kWavesPerBlock - 1) / kWavesPerBlock, (int64_t)S->n_cu * 2);
+    return MOPA_OK;
+}
+
+// The launch of an accepted call with E > 0, on the scene's device: the number of persistent workgroups (`per_cu` resident per CU),
+// the tree slabs and the table k(n) in the stream's scratch, and the kernel arguments all RRT* kernels share (cost / info: the caller's).
+static int star_stage(MopaScene *S, const MopaStarParams &p, const double *start, const double *goal, int64_t E, double *path, int32_t *path_len,
+                      int32_t *status, int node_bytes, int per_cu, hipStream_t stream, StarArgs &a, int64_t &nblk) {
+    const long long tree_bytes = star_tree_bytes(p.max_nodes, node_bytes);
+    // persistent workgroups: `per_cu` per CU are resident; max_workgroups > 0 caps them; fewer where the trees ask for it
+    nblk = std::min<int64_t>((E + kWavesPerBlock - 1) / kWavesPerBlock, (int64_t)S->n_cu * per_cu);
     if (p.max_workgroups > 0) nblk = std::min<int64_t>(nblk, p.max_workgroups);
     nblk = std::max<int64_t>(1, std::min<int64_t>(nblk, kStarMaxTreeBytes / (tree_bytes * kWavesPerBlock)));
-    StreamScratch &sc = scratch_for(S, (hipStream_t)stream);
+    StreamScratch &sc = scratch_for(S, stream);
     HIP_TRY(grow(S, sc.star_tree, (size_t)nblk * kWavesPerBlock * (size_t)tree_bytes));
     // the table k(n), n = 1 .. max_nodes: a prefix of every longer table of the same rewire_factor, so it is uploaded when it grows
     // or the factor changes (synchronously, into a buffer of its own: launches in flight keep reading the one they were given)
@@ -353,9 +357,7 @@ extern "C" int mopa_plan_star_batch(MopaScene *S, const double *start, const dou
         sc.star_k_n = cnt;
         sc.star_k_rf = p.rewire_factor;
     }
-    StarArgs a;
-    a.start = start; a.goal = goal; a.E = (long long)E; a.path = path; a.path_len = path_len; a.status = status; a.cost = cost;
-    a.info = reinterpret_cast<long long *>(info);
+    a.start = start; a.goal = goal; a.E = (long long)E; a.path = path; a.path_len = path_len; a.status = status; a.cost = nullptr; a.info = nullptr;
     a.max_iters = p.max_iters; a.max_nodes = p.max_nodes; a.max_path = p.max_path; a.seed = p.seed; a.env_id_base = p.env_id_base;
     a.env_ids = reinterpret_cast<const unsigned long long *>(p.env_ids_dev); a.seeds = reinterpret_cast<const unsigned long long *>(p.seeds_dev);
     a.goal_bias = p.goal_bias; a.goal_threshold = p.goal_threshold;
@@ -363,6 +365,22 @@ extern "C" int mopa_plan_star_batch(MopaScene *S, const double *start, const dou
     a.hdr_lds_off = (S->lds_bytes + 15) & ~15;
     a.list_lds_off = a.hdr_lds_off + (((int)sizeof(SceneHdr) + 15) & ~15);
     a.list_bytes = star_list_bytes(S->na);
+    return MOPA_OK;
+}
+
+extern "C" int mopa_plan_star_batch(MopaScene *S, const double *start, const double *goal, int64_t E, const MopaStarParams *params, double *path,
+                                    int32_t *path_len, int32_t *status, double *cost, int64_t *info, void *stream) {
+    if (!S || !params || (E > 0 && (!start || !goal || !path || !path_len || !status))) return fail(MOPA_ERR_INVALID_ARG, "null argument");
+    const int node_bytes = star_node_bytes(S->na);
+    if (const int rc = star_rules(S, *params, E, "RRT* (mopa_plan_star)", node_bytes)) return rc;
+    if (E == 0) return MOPA_OK;
+    ON_DEVICE(S->device);
+    StarArgs a;
+    int64_t nblk;
+    // two workgroups per CU are resident (two waves per SIMD)
+    if (const int rc = star_stage(S, *params, start, goal, E, path, path_len, status, node_bytes, 2, (hipStream_t)stream, a, nblk)) return rc;
+    a.cost = cost;
+    a.info = reinterpret_cast<long long *>(info);
     hipLaunchKernelGGL(k_rrt_star, dim3((unsigned)nblk), dim3(kBlock), star_lds_bytes(S), (hipStream_t)stream, S->hdr, S->d_dbl, S->d_int, a);
     HIP_TRY(hipGetLastError());
     return MOPA_OK;

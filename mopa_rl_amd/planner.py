@@ -17,7 +17,14 @@ Differences that cannot be hidden (DESIGN.md "Semantics"):
     has the name ``b"rrt_star"`` here.  With it ``opt`` must be ``""`` or
     ``path_length`` (the only objective built), ``threshold`` is the goal
     threshold, the goal bias is OMPL's default 0.05 whatever ``goal_bias``
-    says, and every ``plan`` spends its whole iteration budget;
+    says, and every ``plan`` spends its whole iteration budget.  The
+    maximize-min-clearance objective needs a band, for which the 14
+    constructor arguments have no slot: it is chosen after construction
+    with the attributes ``objective = "maximize_min_clearance"`` and
+    ``clearance_band`` ("K3b under the clearance
+    objective"; a stated deviation from OMPL: the cost is the pair
+    (clearance, then L1 length)), and ``plan`` then leaves the clearance
+    in ``last_cost`` and the length in ``last_length``;
   * ``opt``, ``num_actions``, ``goal_bias``, ``simplified_duration`` are
     accepted and ignored exactly as the reference ignores them
     (KinematicPlanner.cpp:42-61); ``is_simplified=True`` is rejected
@@ -98,6 +105,10 @@ class PyKinematicPlanner:
         self.path_smooth = False
         #: K3 race: with rrt_connect, plan() runs `portfolio` seeded members per query and returns the winner's path (DESIGN.md "K3 race")
         self.portfolio = 1
+        #: K3b: with rrt_star, "path_length" or "maximize_min_clearance" (band-limited: `clearance_band`, finite, >= 0 and above the
+        #: contact threshold, has to be set too).  plan() then optimises the pair (clearance, then L1 length): DESIGN.md section 4
+        self.objective = "path_length"
+        self.clearance_band = None
         self._check_glue_combination()
         self._model = load_scene(self.xml_filename)
         self._scene = _lib.Scene(self._model, self.passive_joint_idx, self.ignored_contacts, self.contact_threshold,
@@ -105,9 +116,12 @@ class PyKinematicPlanner:
         #: the scene plan() and isValidState() run on: with glue_bodies the glued sibling (closed with `_scene`)
         self._query_scene = self._scene.glued(*self.glue_bodies) if self.glue_bodies else self._scene
         self._plan_count = 0
+        self._status_scene = self._query_scene      # the scene the last plan() ran on: getPlannerStatus() reads it
         self._batch = None          # the BatchPlanner of `_scene`, made on first use (path_clearance)
-        #: RRT*: the cost (L1 length) of the last plan()'s path, +inf when it found none
+        #: RRT*: the cost of the last plan()'s path: its L1 length, +inf when it found none; under the clearance objective its
+        #: clearance, -inf when it found none, and `last_length` holds the L1 length
         self.last_cost = float("inf")
+        self.last_length = float("inf")
 
     # -- reference API -----------------------------------------------------
     def isValidState(self, state_vec) -> bool:
@@ -119,10 +133,19 @@ class PyKinematicPlanner:
         max_iters = max(1, int(round(float(timelimit) * ITERS_PER_SECOND)))
         # every plan() call of one planner object draws a fresh sample stream
         k9_seed = self.seed
+        self._status_scene = self._query_scene
         self._check_glue_combination()
         if int(self.portfolio) > 1 and self.algo == "rrt_star":
             raise NotImplementedError("portfolio > 1 is built for rrt_connect only (RRT* always spends its whole budget: nothing to race)")
-        if self.algo == "rrt_star":
+        if self.objective not in ("path_length", "maximize_min_clearance"):
+            raise ValueError(f"objective={self.objective!r}: 'path_length' or 'maximize_min_clearance'")
+        if self.objective == "maximize_min_clearance":
+            self._check_clearance_combination()
+            self._status_scene = self._scene.contact_scene()       # the scene with the full pair list, as the clearance report runs on
+            status, path, self.last_cost, self.last_length, _ = self._status_scene.plan_star_clearance(
+                start, goal, float(self.clearance_band), max_iters=max_iters, max_nodes=max_iters + 1, max_path=MAX_PATH, seed=self.seed,
+                env_id=self._plan_count, goal_bias=_lib.STAR_GOAL_BIAS, goal_threshold=self.threshold)
+        elif self.algo == "rrt_star":
             # goal bias: OMPL's default 0.05, not the constructor's `goal_bias` -- the reference never forwards that argument to
             # the planner it builds (KinematicPlanner.cpp:42-120); the goal threshold is the constructor's `threshold`
             status, path, self.last_cost, _ = self._scene.plan_star(start, goal, max_iters=max_iters, max_nodes=max_iters + 1, max_path=MAX_PATH,
@@ -157,6 +180,19 @@ class PyKinematicPlanner:
         if on:
             raise NotImplementedError(f"glue_bodies with {' / '.join(on)}: path simplification (K9) is not built for a glued scene")
 
+    def _check_clearance_combination(self) -> None:
+        """objective = "maximize_min_clearance" is built for plain rrt_star with a band"""
+        if self.glue_bodies:
+            raise NotImplementedError("objective='maximize_min_clearance' with glue_bodies: RRT* is not built for a glued scene")
+        if self.algo != "rrt_star":
+            raise NotImplementedError(f"objective='maximize_min_clearance' with algo={self.algo!r}: the clearance objective is built for rrt_star only")
+        on = [n for n in ("vertex_simplify", "path_shortcut", "path_smooth") if getattr(self, n)]
+        if on:
+            raise NotImplementedError(f"objective='maximize_min_clearance' with {' / '.join(on)}: a simplifier behind this planner would change "
+                                      "the clearance it reports; simplify the returned path and call path_clearance instead")
+        if self.clearance_band is None:
+            raise ValueError("objective='maximize_min_clearance' needs clearance_band (finite, >= 0, above the contact threshold)")
+
     def _simplify(self, path: np.ndarray, stream_id: int, seed=None) -> np.ndarray:
         """K9 over one solved path: the draws come from the sample stream (seed, stream_id) the plan itself used (a race: the
         winner's seed)"""
@@ -182,7 +218,7 @@ class PyKinematicPlanner:
         return rows[0, :int(plen[0])].cpu().numpy()
 
     def getPlannerStatus(self) -> bytes:
-        return self._query_scene.planner_status()
+        return self._status_scene.planner_status()
 
     # -- extras used by the batched host code --------------------------------
     @property

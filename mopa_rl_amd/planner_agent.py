@@ -20,7 +20,8 @@ def action_size(ac_space) -> int:
 class PlannerAgent:
     def __init__(self, config, ac_space, non_limited_idx=None, passive_joint_idx=[], ignored_contacts=[],
                  planner_type=None, goal_bias=0.05, is_simplified=False, simplified_duration=0.1, range_=None,
-                 vertex_simplify=False, path_shortcut=False, path_smooth=False, portfolio=1):
+                 vertex_simplify=False, path_shortcut=False, path_smooth=False, portfolio=1,
+                 star_objective=None, clearance_band=None):
         self._config = config
         self._is_simplified, self._simplified_duration = is_simplified, simplified_duration
         self.planner = SamplingBasedPlanner(config, config._xml_path, action_size(ac_space), non_limited_idx,
@@ -29,7 +30,8 @@ class PlannerAgent:
                                             goal_bias=goal_bias, is_simplified=is_simplified,
                                             simplified_duration=simplified_duration, range_=range_,
                                             vertex_simplify=vertex_simplify, path_shortcut=path_shortcut,
-                                            path_smooth=path_smooth, portfolio=portfolio)
+                                            path_smooth=path_smooth, portfolio=portfolio, star_objective=star_objective,
+                                            clearance_band=clearance_band)
 
     def isValidState(self, state):
         return self.planner.isValidState(state)

@@ -30,7 +30,7 @@ class SamplingBasedPlanner:
     def __init__(self, config, xml_path, num_actions, non_limited_idx, planner_type=None, passive_joint_idx=[],
                  glue_bodies=[], ignored_contacts=[], contact_threshold=0.0, goal_bias=0.05, is_simplified=False,
                  simplified_duration=0.1, range_=None, vertex_simplify=False, path_shortcut=False, path_smooth=False,
-                 portfolio=1):
+                 portfolio=1, star_objective=None, clearance_band=None):
         self.config = config
         self.non_limited_idx = non_limited_idx
         # planner_type: "rrt_connect", or "rrt_star" for RRT* (K3b; what the reference's configs call "rrt", a name that keeps raising here)
@@ -49,6 +49,11 @@ class SamplingBasedPlanner:
         self.planner.path_smooth = bool(path_smooth)
         # K3 race (not in the reference's argument list): rrt_connect runs `portfolio` seeded members per query and returns the winner's rows
         self.planner.portfolio = int(portfolio)
+        # K3b under the clearance objective (not in the reference's argument list): "maximize_min_clearance" with a band; plan() raises
+        # where the combination is not built (PyKinematicPlanner.objective)
+        if star_objective is not None:
+            self.planner.objective = str(star_objective)
+        self.planner.clearance_band = clearance_band
 
     # ------------------------------------------------------------------
     def convert_nonlimited(self, state):
