@@ -925,6 +925,9 @@ int mopa_env_contact_arena(const MopaEnv *env);   /* the arena (doubles per env)
 int mopa_env_set_contact_stats(MopaEnv *env, int32_t *stats_dev);
 int mopa_env_dyn_dofs(const MopaEnv *env);      /* nd, or -1 without dynamics */
 int mopa_env_dyn_qvel_width(const MopaEnv *env); /* nd (+ 6 with an object), or -1 */
+/* waves that share 64 envs in a servo-dynamics launch of this env: 4 (the workgroup form), or 1 -- a tree in which two bodies park
+ * their pose in one save slot (parent = -1 0 1 1 0 4 4), or MOPA_DYN_KERNEL=wave in the environment; -1 without dynamics */
+int mopa_env_dyn_waves(const MopaEnv *env);
 /* mj_forward at (qpos, qvel): bias [E,nd] <- qfrc_bias (what the env reads as gravity compensation before its next
  * sub-step; call after a reset / set_state with qvel = 0); M (optional) <- packed lower triangle of the joint-space
  * inertia [E, nd (nd + 1) / 2]; mask (optional): envs with bit 1 set are skipped. */
@@ -1140,7 +1143,8 @@ int mopa_env_desired_batch(MopaEnv *env, int64_t E, const double *qpos_dev /*[E,
 typedef struct MopaIkDesc {
     MopaModel model;              /* body / joint arrays */
     int32_t n_joints;             /* movable joints, 1..8 */
-    const int32_t *joint_ids;     /* [n_joints] model joint ids (hinge / slide, one per body) */
+    const int32_t *joint_ids;     /* [n_joints] model joint ids (hinge / slide, one per body), each at most once: a repeated id is
+                                     refused with MOPA_ERR_INVALID_ARG (one of its two columns would stay zero) */
     int32_t site_body;            /* body carrying the site */
     double site_off[3];           /* site position in that body's frame */
     double site_quat[4];          /* site orientation in that body's frame, wxyz (all zero = identity) */

@@ -38,7 +38,7 @@ EXPORTED_SYMBOLS = [
     "mopa_proximity_batch", "mopa_proximity_state", "mopa_geom_sep_batch", "mopa_geom_sep_host",
     "mopa_motion_report_batch", "mopa_motion_report", "mopa_motion_clearance_batch", "mopa_motion_clearance",
     "mopa_env_create", "mopa_env_destroy", "mopa_env_obs_dim", "mopa_env_action_dim", "mopa_env_step_batch", "mopa_env_exec_batch", "mopa_env_desired_batch",
-    "mopa_env_attach_dynamics", "mopa_env_attach_contacts", "mopa_env_set_contact_stats", "mopa_rollout_stage", "mopa_rollout_pool_pick", "mopa_rollout_step_size", "mopa_reuse_batch", "mopa_replay_append", "mopa_replay_sample", "mopa_ct_desc_size", "mopa_env_contact_arena", "mopa_env_dyn_dofs", "mopa_env_dyn_qvel_width", "mopa_env_dyn_forward_batch", "mopa_env_dyn_substeps_batch", "mopa_env_step_dyn_batch",
+    "mopa_env_attach_dynamics", "mopa_env_attach_contacts", "mopa_env_set_contact_stats", "mopa_rollout_stage", "mopa_rollout_pool_pick", "mopa_rollout_step_size", "mopa_reuse_batch", "mopa_replay_append", "mopa_replay_sample", "mopa_ct_desc_size", "mopa_env_contact_arena", "mopa_env_dyn_dofs", "mopa_env_dyn_qvel_width", "mopa_env_dyn_waves", "mopa_env_dyn_forward_batch", "mopa_env_dyn_substeps_batch", "mopa_env_step_dyn_batch",
     "mopa_pusher_dyn_desc_size", "mopa_env_attach_pusher_dynamics", "mopa_env_set_pusher_stats", "mopa_env_pusher_substeps_batch",
     "mopa_env_step_pusher_batch", "mopa_env_set_contact_force",
     "mopa_ik_create", "mopa_ik_destroy", "mopa_ik_solve_batch", "mopa_ik_site_pose_batch", "mopa_ik_targets_batch",
@@ -289,6 +289,7 @@ def lib() -> C.CDLL:
     L.mopa_env_contact_arena.restype = C.c_int
     L.mopa_env_dyn_dofs.argtypes = [vp]
     L.mopa_env_dyn_qvel_width.argtypes = [vp]
+    L.mopa_env_dyn_waves.argtypes = [vp]
     L.mopa_env_dyn_forward_batch.argtypes = [vp, C.c_int64, vp, vp, vp, vp, vp, vp]
     L.mopa_env_dyn_substeps_batch.argtypes = [vp, C.c_int64, vp, vp, vp, vp, C.c_int32, vp]
     L.mopa_env_step_dyn_batch.argtypes = [vp, C.c_int64, vp, vp, vp, vp, vp, vp, vp, C.c_int32, vp, vp, vp, vp, vp, vp]

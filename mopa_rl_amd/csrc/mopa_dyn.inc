@@ -893,6 +893,7 @@ struct DynTables {
     DynHdr hdr{};
     std::vector<double> rec, orec;
     size_t lds = 0;
+    bool slot_shared = false;      // a save slot has more than one writer (slots are numbered by saved-ancestor depth)
 };
 // Host half of attach_dynamics, over the env's header and the host copy of its int table (actuator / joint addresses).  No device.
 static int dyn_build_host(const EnvHdr &h, const std::vector<int32_t> &hi, const MopaDynDesc *d, DynTables &T) {
@@ -940,6 +941,17 @@ static int dyn_build_host(const EnvHdr &h, const std::vector<int32_t> &hi, const
     if (const int k = parents_depth_first(d->parent, d->nd); k >= 0)
         return fail(MOPA_ERR_UNSUPPORTED, "bodies are not in depth-first order (body " + std::to_string(k) + ")");
     dh.n_save = save_slot_program(d->parent, d->nd, dh.load, dh.save);
+    // A slot with two writers (parent = -1 0 1 1 0 4 4: bodies 1 and 4 both park in slot 1) is safe in a walk that one wave makes.  The
+    // workgroup form's four waves each make the whole walk on the SAME columns with no barrier inside it: a wave that is two bodies
+    // ahead would overwrite the slot before a slower one has reloaded it.  Such a tree is launched in the single-wave form.
+    {
+        unsigned written = 0u;
+        for (int i = 0; i < d->nd; i++)
+            if (dh.save[i] >= 0) {
+                if (written & (1u << dh.save[i])) T.slot_shared = true;
+                written |= 1u << dh.save[i];
+            }
+    }
     // workgroup form: bodies round-robin over the waves that own bodies (three with the object on, four without);
     // rows of M by descending length to the least loaded wave (row i has depth(i) + 1 entries)
     {
@@ -1027,6 +1039,7 @@ extern "C" int mopa_env_attach_dynamics(MopaEnv *env, const MopaDynDesc *d) {
     if (nh) env->d_dynhdr = nh;
     env->dyn = T.hdr;
     env->dyn_lds = T.lds;
+    env->dyn_slot_shared = T.slot_shared;
     for (const void *k : {(const void *)k_env_dyn, (const void *)k_env_dyn4})
         (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLdsBytes);
     return MOPA_OK;
@@ -1057,6 +1070,13 @@ extern "C" int mopa_dyn_tables_host(const MopaEnvDesc *env_desc, const MopaDynDe
 
 extern "C" int mopa_env_dyn_dofs(const MopaEnv *env) { return (env && env->d_dyn) ? env->dyn.nd : -1; }
 extern "C" int mopa_env_dyn_qvel_width(const MopaEnv *env) { return (env && env->d_dyn) ? env->dyn.nv : -1; }
+// The form a servo-dynamics launch of this env takes: the workgroup form (four waves share 64 envs) unless the tree has a save slot with
+// two writers or MOPA_DYN_KERNEL=wave pins the single-wave form (A/B runs, tests).
+static bool dyn_workgroup_form(const MopaEnv *env) {
+    const char *force = getenv("MOPA_DYN_KERNEL");
+    return !env->dyn_slot_shared && !(force && std::strcmp(force, "wave") == 0);
+}
+extern "C" int mopa_env_dyn_waves(const MopaEnv *env) { return (env && env->d_dyn) ? (dyn_workgroup_form(env) ? 4 : 1) : -1; }
 
 static int env_ct_launch(MopaEnv *env, int64_t E, int mode, int n_steps, double *qpos, double *qvel, double *bias_lag, double *prev_state,
                          uint8_t *has_prev, const double *action, int is_planner, const uint8_t *move_mask, const double *ctrl, hipStream_t st);
@@ -1066,9 +1086,8 @@ static int env_dyn_launch(MopaEnv *env, int64_t E, int mode, int n_steps, double
     if (env->ct_on && mode != 2)      // stage C: the sub-steps run in the contact kernel (mopa_contact.inc); mj_forward stays here
         return env_ct_launch(env, E, mode, n_steps, qpos, qvel, bias_lag, prev_state, has_prev, action, is_planner, move_mask, ctrl, st);
     const unsigned blocks = (unsigned)((E + 63) / 64);
-    // MOPA_DYN_KERNEL=wave pins the single-wave form (one wave per 64 envs) for A/B runs and tests; default: the workgroup form
-    const char *force = getenv("MOPA_DYN_KERNEL");
-    const bool wg = !(force && std::strcmp(force, "wave") == 0);
+    // default: the workgroup form; the single-wave form (one wave per 64 envs) for a tree with a shared save slot, or pinned
+    const bool wg = dyn_workgroup_form(env);
     auto kern = wg ? k_env_dyn4 : k_env_dyn;
     hipLaunchKernelGGL(kern, dim3(blocks), dim3(wg ? 256 : 64), env->dyn_lds, st, env->hdr, env->d_dynhdr, env->d_dbl, env->d_int, env->d_dyn, env->d_obj,
                        (long long)E, mode, n_steps, qpos, qvel, bias_lag, prev_state, has_prev, action, is_planner, move_mask, ctrl, M_out);

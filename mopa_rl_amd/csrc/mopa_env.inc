@@ -63,6 +63,7 @@ struct MopaEnv {
     DynHdr dyn{};
     DynHdr *d_dynhdr = nullptr;       // the same header in device memory (the kernel reads it through scalar loads)
     size_t dyn_lds = 0;
+    bool dyn_slot_shared = false;     // two bodies of the dynamic tree park their pose in one save slot: launched in the single-wave form
     // stage C (mopa_contact.inc): [shape | feature | pair] tables, header, LDS bytes of a 4-env workgroup, optional counters
     double *d_ct = nullptr;
     size_t ct_ft_off = 0, ct_pr_off = 0;

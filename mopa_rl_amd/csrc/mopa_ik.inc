@@ -464,6 +464,8 @@ static int ik_build_host(const MopaIkDesc *desc, MopaIk &S, BlobPacker &B) {
         const int j = desc->joint_ids[c];
         if (j < 0 || j >= m.njnt) return fail(MOPA_ERR_INVALID_ARG, "joint id out of range");
         if (m.jnt_type[j] != J_HINGE && m.jnt_type[j] != J_SLIDE) return fail(MOPA_ERR_UNSUPPORTED, "IK joints must be hinge or slide");
+        // (a joint has one column: listed twice, the first of its columns would stay zero and the solve would differ from the checker's)
+        if (col_of_joint[j] >= 0) return fail(MOPA_ERR_INVALID_ARG, "IK: joint id " + std::to_string(j) + " is listed twice");
         col_of_joint[j] = c;
         col_type[c] = m.jnt_type[j];
         col_adr[c] = m.jnt_qposadr[j];
