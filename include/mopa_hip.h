@@ -659,6 +659,22 @@ int mopa_geom_sep_batch(int32_t device, int64_t M, const int32_t *types_dev, con
 /* The host compile of the same functions -- the sequential form the kernels match bit for bit; no GPU, no HIP call. */
 int mopa_geom_sep_host(int64_t M, const int32_t *types, const double *recs, const double *mesh_verts /*nullable*/, int32_t nvert,
                        double band, double *out);
+/* Exact route (opt-in; DESIGN.md section 4, "Proximity report", paragraph "Exact route").  The four entry points above with ONE
+ * change: a disjoint pair of the inflated classes (box-box, cylinder pairs, convex-mesh) gets its separation distance from GJK on
+ * the shapes as they are (gjk_distance, mopa_gjk.hpp) instead of the margin rule: true <= d <= true + 1e-6, the same bits at every
+ * band that reports the pair and in either order of the pair.  Overlaps, the closed-form classes, band == 0, the culls, the
+ * selection, the argument rules, the status codes and the messages are those of the entry point without `_exact`. */
+int mopa_proximity_exact_batch(MopaScene *scene, const double *q_active_dev /*[N,na]*/, const double *qpos_env_dev /*[E,nq]*/, int64_t N,
+                               int64_t samples_per_env, double band, int32_t max_pairs /*K*/, double *clearance_dev /*[N]*/,
+                               int32_t *count_dev /*[N]*/, int32_t *pair_dev /*[N,K]*/, double *dist_dev /*[N,K]*/, void *stream);
+int mopa_proximity_exact_state(MopaScene *scene, const double *qpos_host /*[nq]*/, double band, int32_t max_pairs /*K*/,
+                               double *clearance /*[1]*/, int32_t *count /*[1]*/, int32_t *pair /*[K]*/, double *dist /*[K]*/);
+int mopa_geom_sep_exact_batch(int32_t device, int64_t M, const int32_t *types_dev, const double *recs_dev,
+                              const double *mesh_verts_dev /*nullable*/, int32_t nvert, double band, double *out_dev, void *stream);
+/* iters_out [M] (nullable): the exact route's number of support evaluations for pair i; 0 where the route was not taken (overlap,
+ * closed form, band == 0, culled); negative where the iteration cap ended it (the value is then a lower bound of the distance). */
+int mopa_geom_sep_exact_host(int64_t M, const int32_t *types, const double *recs, const double *mesh_verts /*nullable*/, int32_t nvert,
+                             double band, double *out, int32_t *iters_out /*[M] or NULL*/);
 
 /* Clearance report: HOW NEAR a motion comes to collision, where along it and to which pair -- OMPL's
  * MinimaxObjective::motionCost(s1, s2) under the maximize_min_clearance state cost ("Clearance report").
@@ -692,6 +708,15 @@ int mopa_motion_clearance_batch(MopaScene *scene, const double *qa_dev /*[N,na]*
 int mopa_motion_clearance(MopaScene *scene, const double *qpos_a_host /*[nq]*/, const double *qpos_b_host /*[nq]*/, double band,
                           double *clearance_out, int32_t *n_states_out, int32_t *n_near_out, int32_t *k_min_out, double *t_min_out,
                           int32_t *pair_min_out, double *end_clearance_out, double *q_min_out /*[na] or NULL*/);
+/* The same two with the per-state distances of mopa_proximity_exact_batch (the exact route above); everything else unchanged. */
+int mopa_motion_clearance_exact_batch(MopaScene *scene, const double *qa_dev /*[N,na]*/, const double *qb_dev /*[N,na]*/,
+                                      const double *qpos_env_dev /*[E,nq]*/, int64_t N, int64_t samples_per_env, double band,
+                                      double *clearance_dev /*[N]*/, int32_t *n_states_dev /*[N]*/, int32_t *n_near_dev /*[N]*/,
+                                      int32_t *k_min_dev /*[N]*/, double *t_min_dev /*[N]*/, int32_t *pair_min_dev /*[N]*/,
+                                      double *end_clearance_dev /*[N]*/, double *q_min_dev /*[N,na] or NULL*/, void *stream);
+int mopa_motion_clearance_exact(MopaScene *scene, const double *qpos_a_host /*[nq]*/, const double *qpos_b_host /*[nq]*/, double band,
+                                double *clearance_out, int32_t *n_states_out, int32_t *n_near_out, int32_t *k_min_out, double *t_min_out,
+                                int32_t *pair_min_out, double *end_clearance_out, double *q_min_out /*[na] or NULL*/);
 
 /* ======================================================================================================
  * (BASELINE configs 3-5) batched KINEMATIC env.step for the three Sawyer obstacle envs --

@@ -36,6 +36,8 @@ EXPORTED_SYMBOLS = [
     "mopa_contact_frames_batch", "mopa_contact_frames_state", "mopa_geom_frames_batch", "mopa_geom_frames_host",
     "mopa_contact_manifolds_batch", "mopa_contact_manifolds_state", "mopa_geom_manifolds_batch", "mopa_geom_manifolds_host",
     "mopa_proximity_batch", "mopa_proximity_state", "mopa_geom_sep_batch", "mopa_geom_sep_host",
+    "mopa_proximity_exact_batch", "mopa_proximity_exact_state", "mopa_geom_sep_exact_batch", "mopa_geom_sep_exact_host",
+    "mopa_motion_clearance_exact_batch", "mopa_motion_clearance_exact",
     "mopa_motion_report_batch", "mopa_motion_report", "mopa_motion_clearance_batch", "mopa_motion_clearance",
     "mopa_env_create", "mopa_env_destroy", "mopa_env_obs_dim", "mopa_env_action_dim", "mopa_env_step_batch", "mopa_env_exec_batch", "mopa_env_desired_batch",
     "mopa_env_attach_dynamics", "mopa_env_attach_contacts", "mopa_env_set_contact_stats", "mopa_rollout_stage", "mopa_rollout_pool_pick", "mopa_rollout_step_size", "mopa_reuse_batch", "mopa_replay_append", "mopa_replay_sample", "mopa_ct_desc_size", "mopa_env_contact_arena", "mopa_env_dyn_dofs", "mopa_env_dyn_qvel_width", "mopa_env_dyn_waves", "mopa_env_dyn_forward_batch", "mopa_env_dyn_substeps_batch", "mopa_env_step_dyn_batch",
@@ -262,10 +264,16 @@ def lib() -> C.CDLL:
     L.mopa_proximity_state.argtypes = [vp, _dp, C.c_double, C.c_int32, _dp, _ip, _ip, _dp]
     L.mopa_geom_sep_batch.argtypes = [C.c_int32, C.c_int64, vp, vp, vp, C.c_int32, C.c_double, vp, vp]
     L.mopa_geom_sep_host.argtypes = [C.c_int64, _ip, _dp, _dp, C.c_int32, C.c_double, _dp]
+    L.mopa_proximity_exact_batch.argtypes = L.mopa_proximity_batch.argtypes
+    L.mopa_proximity_exact_state.argtypes = L.mopa_proximity_state.argtypes
+    L.mopa_geom_sep_exact_batch.argtypes = L.mopa_geom_sep_batch.argtypes
+    L.mopa_geom_sep_exact_host.argtypes = [C.c_int64, _ip, _dp, _dp, C.c_int32, C.c_double, _dp, _ip]
     L.mopa_motion_report_batch.argtypes = [vp, vp, vp, vp, C.c_int64, C.c_int64, vp, vp, vp, vp, vp, vp, C.c_int32, vp, vp, vp, vp]
     L.mopa_motion_report.argtypes = [vp, _dp, _dp, _ip, _ip, _ip, _dp, _dp, _dp, C.c_int32, _ip, _ip, _dp]
     L.mopa_motion_clearance_batch.argtypes = [vp, vp, vp, vp, C.c_int64, C.c_int64, C.c_double, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.mopa_motion_clearance.argtypes = [vp, _dp, _dp, C.c_double, _dp, _ip, _ip, _ip, _dp, _ip, _dp, _dp]
+    L.mopa_motion_clearance_exact_batch.argtypes = L.mopa_motion_clearance_batch.argtypes
+    L.mopa_motion_clearance_exact.argtypes = L.mopa_motion_clearance.argtypes
     L.mopa_env_create.argtypes = [C.POINTER(MopaEnvDesc), C.POINTER(vp)]
     L.mopa_env_destroy.argtypes = [vp]
     L.mopa_env_destroy.restype = None
@@ -391,15 +399,24 @@ def geom_manifolds_host(types, recs, mesh_verts=None, point_cutoff: float = 0.0,
     return nd, npoint, pts
 
 
-def geom_sep_host(types, recs, band: float, mesh_verts=None) -> np.ndarray:
+def geom_sep_host(types, recs, band: float, mesh_verts=None, exact: bool = False, return_iters: bool = False):
     """mopa_geom_sep_host: M posed pairs as `geom_frames_host` takes them -> [M] band-limited signed distances by the host compile
-    of the kernels' geom_sep (no GPU): d where d <= band, MOPA_FAR otherwise ("Proximity report")."""
+    of the kernels' geom_sep (no GPU): d where d <= band, MOPA_FAR otherwise ("Proximity report").
+    exact=True (mopa_geom_sep_exact_host): disjoint box-box, cylinder and mesh pairs get the GJK distance, at most 1e-6 above the
+    true one, instead of the margin rule's.  return_iters=True (with exact=True): -> (out, iters [M] int32), the exact route's
+    number of support evaluations per pair, 0 where it was not taken, negative where its iteration cap ended it."""
+    if return_iters and not exact:
+        raise MopaError("return_iters needs exact=True")
     t, tp = _i(np.asarray(types).reshape(-1, 2))
     r, rp = _d(np.asarray(recs, dtype=np.float64).reshape(-1, 30))
     if len(t) != len(r):
         raise MopaError(f"{len(t)} type pairs for {len(r)} record pairs")
     out = np.zeros(len(t))
     v, vp_ = _d(np.asarray(mesh_verts, dtype=np.float64).reshape(-1, 3)) if mesh_verts is not None else (np.zeros((0, 3)), None)
+    if exact:
+        iters = np.zeros(len(t), dtype=np.int32)
+        check(lib().mopa_geom_sep_exact_host(len(t), tp, rp, vp_, len(v), float(band), out.ctypes.data_as(_dp), iters.ctypes.data_as(_ip)))
+        return (out, iters) if return_iters else out
     check(lib().mopa_geom_sep_host(len(t), tp, rp, vp_, len(v), float(band), out.ctypes.data_as(_dp)))
     return out
 
@@ -702,7 +719,9 @@ class Scene:
                             seed: Optional[int] = None, env_id: int = 0, goal_bias: float = STAR_GOAL_BIAS, goal_threshold: float = 0.0,
                             rewire_factor: float = STAR_REWIRE_FACTOR):
         """one RRT* query under the maximize-min-clearance objective at `band` (DESIGN.md "K3b under the clearance objective"):
-        -> (status, path rows, clearance, length, info [11] int64); clearance = -inf and length = +inf unless status is 0"""
+        -> (status, path rows, clearance, length, info [11] int64); clearance = -inf and length = +inf unless status is 0.
+        The planner stays on the inflated (margin-rule) distances: the exact clearance of the returned path is never lower than
+        `clearance`, up to kGjkTol = 1e-6; equality of bits with the clearance report holds with exact=False only."""
         s, sp = _d(start)
         g, gp = _d(goal)
         nodes = int(max_iters) + 1 if max_nodes is None else int(max_nodes)
@@ -817,8 +836,9 @@ class Scene:
         n, pair, dist = self.contacts_state_raw(qpos, cutoff, K)
         return _pair_names(m, pair, dist, n)
 
-    def proximity_state_raw(self, qpos, band: float, max_pairs: int = 8):
-        """(clearance, count, pair [K] int32, dist [K]) of one state: the single-state form of `BatchPlanner.proximity`"""
+    def proximity_state_raw(self, qpos, band: float, max_pairs: int = 8, exact: bool = False):
+        """(clearance, count, pair [K] int32, dist [K]) of one state: the single-state form of `BatchPlanner.proximity`
+        (exact=True: mopa_proximity_exact_state)"""
         if self.glue is not None:
             raise NotImplementedError("the proximity report of a glued scene")
         sc = self.contact_scene()
@@ -826,15 +846,17 @@ class Scene:
         K = int(max_pairs)
         cl = C.c_double(0.0)
         cnt, pair, dist = self._record_bufs(K)
-        check(lib().mopa_proximity_state(sc._h, qp, float(band), K, C.byref(cl), C.byref(cnt), pair.ctypes.data_as(_ip), dist.ctypes.data_as(_dp)))
+        fn = lib().mopa_proximity_exact_state if exact else lib().mopa_proximity_state
+        check(fn(sc._h, qp, float(band), K, C.byref(cl), C.byref(cnt), pair.ctypes.data_as(_ip), dist.ctypes.data_as(_dp)))
         return float(cl.value), int(cnt.value), pair, dist
 
-    def proximity_state(self, qpos, band: float, max_pairs: int = 8):
+    def proximity_state(self, qpos, band: float, max_pairs: int = 8, exact: bool = False):
         """How far from collision one state is, and which pairs are nearest: -> (clearance, [(geom1_name, geom2_name, dist), ...]),
         clearance = min(band, the smallest pair distance), the list the at most max_pairs nearest non-ignored candidate pairs with
         dist <= band, nearest first.  Distances of disjoint box-box, cylinder and mesh pairs are conservative -- never more than 1e-6
-        above the true distance, below it by a shortfall that grows with band ("Proximity report")."""
-        cl, n, pair, dist = self.proximity_state_raw(qpos, band, max_pairs)
+        above the true distance, below it by a shortfall that grows with band ("Proximity report").
+        exact=True: those pairs get their GJK distance instead, true <= d <= true + 1e-6 whatever the band ("Exact route")."""
+        cl, n, pair, dist = self.proximity_state_raw(qpos, band, max_pairs, exact)
         return cl, _pair_names(self.model, pair, dist, n)
 
     def motion_report_raw(self, qpos_a, qpos_b, max_contacts: int = 0):
@@ -879,10 +901,11 @@ class Scene:
             out["n_blockers"] = cnt
         return out
 
-    def motion_clearance_raw(self, qpos_a, qpos_b, band: float):
+    def motion_clearance_raw(self, qpos_a, qpos_b, band: float, exact: bool = False):
         """(clearance, n_states, n_near, k_min, t_min, pair_min, end_clearance, q_min [na]) of one segment: the single-segment
         form of `BatchPlanner.motion_clearance` (mopa_motion_clearance) from the active entries of qpos_a to those of qpos_b, the
-        passive entries taken from qpos_a; pair_min is an index into `model.pair_geom` (-1: nothing within the band)"""
+        passive entries taken from qpos_a; pair_min is an index into `model.pair_geom` (-1: nothing within the band).
+        exact=True: mopa_motion_clearance_exact, the per-state distances of `proximity(exact=True)`."""
         if self.glue is not None:
             raise NotImplementedError("the clearance report of a glued scene")
         sc = self.contact_scene()
@@ -890,19 +913,21 @@ class Scene:
         cl, t, ec = C.c_double(0.0), C.c_double(0.0), C.c_double(0.0)
         n, near, k, pair = C.c_int32(0), C.c_int32(0), C.c_int32(0), C.c_int32(-1)
         q_min = np.zeros(self.na)
-        check(lib().mopa_motion_clearance(sc._h, ap, bp, float(band), C.byref(cl), C.byref(n), C.byref(near), C.byref(k), C.byref(t), C.byref(pair),
-                                          C.byref(ec), q_min.ctypes.data_as(_dp)))
+        fn = lib().mopa_motion_clearance_exact if exact else lib().mopa_motion_clearance
+        check(fn(sc._h, ap, bp, float(band), C.byref(cl), C.byref(n), C.byref(near), C.byref(k), C.byref(t), C.byref(pair), C.byref(ec),
+                 q_min.ctypes.data_as(_dp)))
         return float(cl.value), int(n.value), int(near.value), int(k.value), float(t.value), int(pair.value), float(ec.value), q_min
 
-    def motion_clearance_state(self, qpos_a, qpos_b, band: float):
+    def motion_clearance_state(self, qpos_a, qpos_b, band: float, exact: bool = False):
         """How near the straight line from qpos_a to qpos_b comes to collision, where, and to which pair: OMPL's
         MinimaxObjective::motionCost under the clearance state cost, over the states s_k, k = 1 .. n_states, `motion_report_state`
         walks (qpos_a is not evaluated).  -> dict: `clearance` (the smallest state clearance, saturating at band), `n_states`,
         `n_near` (states with a pair within the band), `k_min` (the first state that attains the clearance, 0: nothing within the
         band), `t_min` (k_min / n_states), `pair` ((geom1_name, geom2_name) of the nearest pair there, None when k_min == 0),
         `pair_min` (its index into `model.pair_geom`, -1), `end_clearance` (that of qpos_b) and `q_min` (active coordinates [na] of
-        s_k_min; qpos_b's when k_min == 0).  DESIGN.md section 4, "Clearance report"."""
-        cl, n, near, k, t, pair, ec, q_min = self.motion_clearance_raw(qpos_a, qpos_b, band)
+        s_k_min; qpos_b's when k_min == 0).  exact=True: the state clearances of `proximity_state(exact=True)`.  DESIGN.md section 4,
+        "Clearance report"."""
+        cl, n, near, k, t, pair, ec, q_min = self.motion_clearance_raw(qpos_a, qpos_b, band, exact)
         return {"clearance": cl, "n_states": n, "n_near": near, "k_min": k, "t_min": t, "pair_min": pair,
                 "pair": _pair_names(self.model, [pair], [cl], 1)[0][:2] if pair >= 0 else None, "end_clearance": ec, "q_min": q_min}
 

@@ -219,9 +219,11 @@ def geom_frames(types, recs, stream=None):
     return out
 
 
-def geom_sep(types, recs, band: float, mesh_verts=None, stream=None):
+def geom_sep(types, recs, band: float, mesh_verts=None, stream=None, exact: bool = False):
     """mopa_geom_sep_batch: M posed pairs, one lane each, as `geom_frames` takes them -> [M] band-limited signed distances, the
-    bits of `_lib.geom_sep_host`; mesh_verts [n, 3] (float64, on the GPU): the hull of every geom of type 7"""
+    bits of `_lib.geom_sep_host`; mesh_verts [n, 3] (float64, on the GPU): the hull of every geom of type 7.
+    exact=True (mopa_geom_sep_exact_batch): the bits of `_lib.geom_sep_host(..., exact=True)`, the GJK distance of disjoint box-box,
+    cylinder and mesh pairs"""
     torch = _torch()
     M, dev = _pair_batch(types, recs)
     nvert = 0
@@ -229,8 +231,8 @@ def geom_sep(types, recs, band: float, mesh_verts=None, stream=None):
         _check_f64(mesh_verts, "mesh_verts", 3)
         nvert = mesh_verts.shape[0]
     out = torch.empty(M, dtype=torch.float64, device=recs.device)
-    _lib.check(_lib.lib().mopa_geom_sep_batch(dev, M, _ptr(types), _ptr(recs), _ptr(mesh_verts) if nvert else None, nvert, float(band), _ptr(out),
-                                              _stream_handle(stream)))
+    fn = _lib.lib().mopa_geom_sep_exact_batch if exact else _lib.lib().mopa_geom_sep_batch
+    _lib.check(fn(dev, M, _ptr(types), _ptr(recs), _ptr(mesh_verts) if nvert else None, nvert, float(band), _ptr(out), _stream_handle(stream)))
     return out
 
 
@@ -380,13 +382,15 @@ class BatchPlanner:
         return ContactReport(count, pair, dist, self.scene.model, normal, pos, npoint, pdist, ppos)
 
     def proximity(self, q_active, qpos_env, samples_per_env: Optional[int] = None, band: float = 0.05, max_pairs: int = 8,
-                  stream=None) -> ProximityReport:
+                  stream=None, exact: bool = False) -> ProximityReport:
         """How far from collision every state of a batch is, and which pairs are nearest (states as in `is_valid`): the signed
         distance of every non-ignored candidate pair at or below `band` (>= 0, metres); `clearance` saturates at band, `count`
         is not capped by `max_pairs`, the nearest pairs are kept.  A pair in overlap carries the contact report's bits; disjoint
         box-box, cylinder and mesh pairs get MuJoCo's margin rule, a conservative distance: never more than 1e-6 above the true
-        one, below it by a shortfall that grows with band ("Proximity report").  One launch of its own on the scene with the full pair list
-        (`Scene.contact_scene`); a glued scene raises."""
+        one, below it by a shortfall that grows with band ("Proximity report").  exact=True
+        (mopa_proximity_exact_batch): those pairs get their GJK distance instead -- true <= d <= true + 1e-6, the same bits at
+        every band that reports the pair; everything else is unchanged ("Exact route").  One launch of its own on the scene with the
+        full pair list (`Scene.contact_scene`); a glued scene raises."""
         if self.scene.glue is not None:
             raise NotImplementedError("the proximity report of a glued scene")
         torch = _torch()
@@ -398,13 +402,14 @@ class BatchPlanner:
         count = torch.empty(N, dtype=torch.int32, device=dev)
         pair = torch.empty(N, max(K, 1), dtype=torch.int32, device=dev)
         dist = torch.empty(N, max(K, 1), dtype=torch.float64, device=dev)
-        _lib.check(_lib.lib().mopa_proximity_batch(sc.handle, _ptr(q_active), _ptr(qpos_env), N, spe, float(band), K, _ptr(clearance), _ptr(count),
-                                                   _ptr(pair), _ptr(dist), _stream_handle(stream)))
+        fn = _lib.lib().mopa_proximity_exact_batch if exact else _lib.lib().mopa_proximity_batch
+        _lib.check(fn(sc.handle, _ptr(q_active), _ptr(qpos_env), N, spe, float(band), K, _ptr(clearance), _ptr(count), _ptr(pair), _ptr(dist),
+                      _stream_handle(stream)))
         return ProximityReport(clearance, count, pair, dist, self.scene.model)
 
-    def clearance(self, q_active, qpos_env, samples_per_env: Optional[int] = None, band: float = 0.05, stream=None):
+    def clearance(self, q_active, qpos_env, samples_per_env: Optional[int] = None, band: float = 0.05, stream=None, exact: bool = False):
         """`proximity(...).clearance` alone: [N] float64, min(band, the smallest pair distance) of every state"""
-        return self.proximity(q_active, qpos_env, samples_per_env, band=band, max_pairs=1, stream=stream).clearance
+        return self.proximity(q_active, qpos_env, samples_per_env, band=band, max_pairs=1, stream=stream, exact=exact).clearance
 
     def glue_attach(self, rows, stream=None):
         """glued scene (`Scene.glued`): rows [E, nq] -> their attached rows, copies whose free-joint slots of the carried body hold
@@ -479,11 +484,12 @@ class BatchPlanner:
         return MotionReport(valid, n_states, first_bad, t, lvq, fbq if states else None, blockers)
 
     def motion_clearance(self, qa, qb, qpos_env, samples_per_env: Optional[int] = None, band: float = 0.05, states: bool = False,
-                         stream=None) -> MotionClearance:
+                         stream=None, exact: bool = False) -> MotionClearance:
         """How near every segment qa[i] -> qb[i] comes to collision, where along it and to which pair (mopa_motion_clearance_batch;
         segments and env rows as in `check_motion`): OMPL's MinimaxObjective::motionCost under the clearance state cost, over the
         states `motion_report` walks, each state's clearance and nearest pair being the bits of `proximity(..., max_pairs=1)` --
-        see `MotionClearance`.  states=True adds the [N, na] rows q_min.  Runs on the scene with the full pair list
+        see `MotionClearance`.  states=True adds the [N, na] rows q_min.  exact=True (mopa_motion_clearance_exact_batch): the bits of
+        `proximity(..., max_pairs=1, exact=True)` per state.  Runs on the scene with the full pair list
         (`Scene.contact_scene`) and synchronises the stream once in the middle of the call (the state count is read back), as the
         large-batch `check_motion` does -- the last kernels are still in flight when it returns; N == 0 gives an empty report
         without a call; a glued scene raises."""
@@ -502,12 +508,12 @@ class BatchPlanner:
         q_min = f64(N, self.na) if states else None
         if N == 0:      # (empty tensors have no address to pass: an empty report, no call)
             return MotionClearance(clearance, n_states, n_near, k_min, t_min, pair_min, end_clearance, q_min, self.scene.model)
-        _lib.check(_lib.lib().mopa_motion_clearance_batch(sc.handle, _ptr(qa), _ptr(qb), _ptr(qpos_env), N, spe, float(band), _ptr(clearance),
-                                                          _ptr(n_states), _ptr(n_near), _ptr(k_min), _ptr(t_min), _ptr(pair_min), _ptr(end_clearance),
-                                                          _ptr(q_min) if states else None, _stream_handle(stream)))
+        fn = _lib.lib().mopa_motion_clearance_exact_batch if exact else _lib.lib().mopa_motion_clearance_batch
+        _lib.check(fn(sc.handle, _ptr(qa), _ptr(qb), _ptr(qpos_env), N, spe, float(band), _ptr(clearance), _ptr(n_states), _ptr(n_near), _ptr(k_min),
+                      _ptr(t_min), _ptr(pair_min), _ptr(end_clearance), _ptr(q_min) if states else None, _stream_handle(stream)))
         return MotionClearance(clearance, n_states, n_near, k_min, t_min, pair_min, end_clearance, q_min, self.scene.model)
 
-    def path_clearance(self, path, path_len, band: float = 0.05, stream=None) -> PathClearance:
+    def path_clearance(self, path, path_len, band: float = 0.05, stream=None, exact: bool = False) -> PathClearance:
         """The clearance of E planner paths (path [E, max_path, nq], path_len [E] int32, as `plan` returns them): the path cost of
         the minimax clearance objective with vertex 0 counted, where along the path it is attained and to which pair, and the mean
         clearance of the vertices -- see `PathClearance` and DESIGN.md section 4, "Clearance report".  The env row of a path is its
@@ -515,7 +521,7 @@ class BatchPlanner:
         of all paths in one call) and `proximity` (the vertices 0 of the solved queries); the reductions are deterministic.
         Cost besides the pipeline's own read-back: `path_len` is copied to the host once (E int32, one more synchronisation of the
         stream) to lay out the segment list, and the mean is summed left to right by one small launch per column up to the
-        longest path."""
+        longest path.  exact=True: both calls with exact=True."""
         if self.scene.glue is not None:
             raise NotImplementedError("the clearance report of a glued scene")
         torch = _torch()
@@ -543,12 +549,13 @@ class BatchPlanner:
             jj = torch.arange(P - 1, device=dev)
             pa = path[:, :, act]                                           # [E, P, na]
             seg = self.motion_clearance(pa[pe, pj].contiguous(), pa[pe, pj + 1].contiguous(), path[pe, 0].contiguous(), samples_per_env=1,
-                                        band=band, stream=stream)
+                                        band=band, stream=stream, exact=exact)
             seg.path_index, seg.seg_index = pe, pj
             v0 = torch.full((E,), float("nan"), dtype=torch.float64, device=dev)
             p0 = torch.full((E,), -1, dtype=torch.int32, device=dev)
             if len(solved):
-                v = self.proximity(pa[solved, 0].contiguous(), path[solved, 0].contiguous(), samples_per_env=1, band=band, max_pairs=1, stream=stream)
+                v = self.proximity(pa[solved, 0].contiguous(), path[solved, 0].contiguous(), samples_per_env=1, band=band, max_pairs=1, stream=stream,
+                                   exact=exact)
                 v0[solved], p0[solved] = v.clearance, v.pair[:, 0]
             segc = torch.full((E, P - 1), float("inf"), dtype=torch.float64, device=dev)
             segk = torch.zeros(E, P - 1, dtype=torch.int32, device=dev)
@@ -693,7 +700,9 @@ class BatchPlanner:
         parameters the tree holds the nodes `plan_star` grows; where no evaluated motion is in band the result is `plan_star`'s.
         Every other keyword is `plan_star`'s.  Runs on the scene with the full pair list (`Scene.contact_scene`), as the clearance
         report does; a glued scene raises.  The K9 switches are not offered: a simplifier behind this planner would change the
-        clearance it reports -- call `simplify_paths` and `path_clearance` on the result instead."""
+        clearance it reports -- call `simplify_paths` and `path_clearance` on the result instead.
+        The planner stays on the inflated (margin-rule) distances: `path_clearance(path, path_len, band, exact=True)`
+        of a returned path is never lower than `clearance`, up to kGjkTol = 1e-6; equality of bits holds with exact=False only."""
         torch = _torch()
         _check_f64(start, "start", self.nq)
         _check_f64(goal, "goal", self.nq)

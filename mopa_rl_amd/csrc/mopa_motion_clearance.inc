@@ -29,7 +29,8 @@
 // One state of that sweep, for k_clearance_states and for RRT* under the clearance objective (mopa_rrtstar_clear.inc): the active
 // vector `q_active` on the env row `row` -> on every lane d = min(band, the smallest pair distance) and p = the nearest pair in
 // band, -1 when there is none.  The caller synchronises the wave before the worklist / geom slab are reused.
-template <bool MESH>
+// EXACT = true: geom_sep's exact route (gjk_distance) in the lambda; nothing else changes.
+template <bool MESH, bool EXACT = false>
 MOPA_D void wave_state_clearance(const SceneHdr &h, const LdsView &v, int lane, const double *q_active, const double *row,
                                  const int32_t *__restrict__ pair_model, double band, double &d_out, int &p_out) {
     const int *I = v.ints;
@@ -40,7 +41,7 @@ MOPA_D void wave_state_clearance(const SceneHdr &h, const LdsView &v, int lane, 
     double bd = kFar;
     int bi = 0x7fffffff;
     wave_each_survivor(h, v, lane, wl_count, [&](int p, int g1, int g2, int code) {
-        const double d = geom_sep<MESH>(code, geom_rec(h, v, g1), I[h.o_g_type + g1], geom_rec(h, v, g2), I[h.o_g_type + g2], band, v.dbl);
+        const double d = geom_sep<MESH, 1, EXACT>(code, geom_rec(h, v, g1), I[h.o_g_type + g1], geom_rec(h, v, g2), I[h.o_g_type + g2], band, v.dbl);
         const int pm = pair_model[p];
         if (d < bd || (d == bd && pm < bi)) { bd = d; bi = pm; }
     });
@@ -50,7 +51,7 @@ MOPA_D void wave_state_clearance(const SceneHdr &h, const LdsView &v, int lane, 
     p_out = near ? bi : -1;
 }
 
-template <bool MESH>
+template <bool MESH, bool EXACT = false>
 __global__ __launch_bounds__(kBlock) void k_clearance_states(SceneHdr h, const double *__restrict__ g_dbl, const int32_t *__restrict__ g_int,
                                                              const int32_t *__restrict__ pair_model /*[h.npair] device pair -> index in the desc's pair list*/,
                                                              const double *__restrict__ q_states /*[T,na]*/, const double *__restrict__ qpos_env,
@@ -66,7 +67,7 @@ __global__ __launch_bounds__(kBlock) void k_clearance_states(SceneHdr h, const d
         if (s >= T) break;
         double d;
         int p;
-        wave_state_clearance<MESH>(h, v, lane, q_states + s * h.na, qpos_env + (long long)env_of_state[s] * h.nq, pair_model, band, d, p);
+        wave_state_clearance<MESH, EXACT>(h, v, lane, q_states + s * h.na, qpos_env + (long long)env_of_state[s] * h.nq, pair_model, band, d, p);
         if (lane == 0) {
             d_state[s] = d;
             p_state[s] = p;
@@ -117,11 +118,12 @@ __global__ __launch_bounds__(256) void k_motion_clearance_rows(int na, const int
     q_min[e] = q_states[(o + j) * na + a];
 }
 
-static const LdsKernels kMotionClearanceLds({(const void *)k_clearance_states<false>, (const void *)k_clearance_states<true>});
+static const LdsKernels kMotionClearanceLds({(const void *)k_clearance_states<false>, (const void *)k_clearance_states<true>,
+                                              (const void *)k_clearance_states<false, true>, (const void *)k_clearance_states<true, true>});
 
-extern "C" int mopa_motion_clearance_batch(MopaScene *S, const double *qa, const double *qb, const double *qpos_env, int64_t N, int64_t samples_per_env,
-                                           double band, double *clearance, int32_t *n_states, int32_t *n_near, int32_t *k_min, double *t_min,
-                                           int32_t *pair_min, double *end_clearance, double *q_min, void *stream) {
+static int motion_clearance_batch(bool exact, MopaScene *S, const double *qa, const double *qb, const double *qpos_env, int64_t N, int64_t samples_per_env,
+                                  double band, double *clearance, int32_t *n_states, int32_t *n_near, int32_t *k_min, double *t_min,
+                                  int32_t *pair_min, double *end_clearance, double *q_min, void *stream) {
     if (!S || !clearance || !n_states || !n_near || !k_min || !t_min || !pair_min || !end_clearance || (N > 0 && (!qa || !qb || !qpos_env)))
         return fail(MOPA_ERR_INVALID_ARG, "null argument");
     MOPA_REFUSE_GLUED(S, "the clearance report (mopa_motion_clearance_batch)");
@@ -136,6 +138,8 @@ extern "C" int mopa_motion_clearance_batch(MopaScene *S, const double *qa, const
     const int rc0 = ensure_report_ctr(S, sc);
     if (rc0 != MOPA_OK) return rc0;
     const size_t na = (size_t)S->na;
+    const auto kern = exact ? (S->hdr.has_mesh ? k_clearance_states<true, true> : k_clearance_states<false, true>)
+                            : (S->hdr.has_mesh ? k_clearance_states<true> : k_clearance_states<false>);
     // the expanded-motion pipeline (mopa_motion.inc), then per chunk: a wave per expanded state, a lane per segment, the row
     return motion_for_chunks(S, N, [&](int64_t first, int64_t n) {
         MotionExpanded x;
@@ -146,7 +150,7 @@ extern "C" int mopa_motion_clearance_batch(MopaScene *S, const double *qa, const
             HIP_TRY(grow(S, sc.mc_d, sizeof(double) * cap));
             HIP_TRY(grow(S, sc.mc_p, sizeof(int32_t) * cap));
         }
-        hipLaunchKernelGGL(S->hdr.has_mesh ? k_clearance_states<true> : k_clearance_states<false>, dim3((unsigned)report_blocks(S, x.T)), dim3(kBlock), (size_t)S->lds_bytes, st,
+        hipLaunchKernelGGL(kern, dim3((unsigned)report_blocks(S, x.T)), dim3(kBlock), (size_t)S->lds_bytes, st,
                            S->hdr, S->d_dbl, S->d_int, (const int32_t *)S->d_pair_model, (const double *)x.q, qpos_env, (const int32_t *)x.env, (long long)x.T,
                            band, sc.ct_ctr.as<unsigned long long>(), sc.mc_d.as<double>(), sc.mc_p.as<int32_t>());
         hipLaunchKernelGGL(k_motion_clearance_reduce, dim3(x.nb), dim3(256), 0, st, x.cnt, x.off, x.bsum, (const double *)sc.mc_d.as<double>(),
@@ -161,11 +165,23 @@ extern "C" int mopa_motion_clearance_batch(MopaScene *S, const double *qa, const
         return (int)MOPA_OK;
     });
 }
+extern "C" int mopa_motion_clearance_batch(MopaScene *S, const double *qa, const double *qb, const double *qpos_env, int64_t N, int64_t samples_per_env,
+                                           double band, double *clearance, int32_t *n_states, int32_t *n_near, int32_t *k_min, double *t_min,
+                                           int32_t *pair_min, double *end_clearance, double *q_min, void *stream) {
+    return motion_clearance_batch(false, S, qa, qb, qpos_env, N, samples_per_env, band, clearance, n_states, n_near, k_min, t_min, pair_min, end_clearance,
+                                  q_min, stream);
+}
+extern "C" int mopa_motion_clearance_exact_batch(MopaScene *S, const double *qa, const double *qb, const double *qpos_env, int64_t N, int64_t samples_per_env,
+                                                 double band, double *clearance, int32_t *n_states, int32_t *n_near, int32_t *k_min, double *t_min,
+                                                 int32_t *pair_min, double *end_clearance, double *q_min, void *stream) {
+    return motion_clearance_batch(true, S, qa, qb, qpos_env, N, samples_per_env, band, clearance, n_states, n_near, k_min, t_min, pair_min, end_clearance,
+                                  q_min, stream);
+}
 
 // one segment, host pointers, synchronous: the active entries of qpos_a -> those of qpos_b, the passive entries from qpos_a
-extern "C" int mopa_motion_clearance(MopaScene *S, const double *qpos_a, const double *qpos_b, double band, double *clearance_out,
-                                     int32_t *n_states_out, int32_t *n_near_out, int32_t *k_min_out, double *t_min_out, int32_t *pair_min_out,
-                                     double *end_clearance_out, double *q_min_out) {
+static int motion_clearance_one(bool exact, MopaScene *S, const double *qpos_a, const double *qpos_b, double band, double *clearance_out,
+                                int32_t *n_states_out, int32_t *n_near_out, int32_t *k_min_out, double *t_min_out, int32_t *pair_min_out,
+                                double *end_clearance_out, double *q_min_out) {
     if (!S || !qpos_a || !qpos_b || !clearance_out || !n_states_out || !n_near_out || !k_min_out || !t_min_out || !pair_min_out || !end_clearance_out)
         return fail(MOPA_ERR_INVALID_ARG, "null argument");
     MOPA_REFUSE_GLUED(S, "the clearance report (mopa_motion_clearance)");
@@ -178,12 +194,24 @@ extern "C" int mopa_motion_clearance(MopaScene *S, const double *qpos_a, const d
     const auto f_n = g.i32(1), f_near = g.i32(1), f_k = g.i32(1), f_pair = g.i32(1);
     HIP_TRY(g.alloc());
     HIP_TRY(g.seed(f_qb, active_of(S, qpos_b).data()));
-    rc = mopa_motion_clearance_batch(S, S->d_q + S->nq, g.dev(f_qb), S->d_q, 1, 1, band, g.dev(f_clear), g.dev(f_n), g.dev(f_near), g.dev(f_k), g.dev(f_t),
-                                     g.dev(f_pair), g.dev(f_end), g.dev(f_qmin), nullptr);
+    rc = motion_clearance_batch(exact, S, S->d_q + S->nq, g.dev(f_qb), S->d_q, 1, 1, band, g.dev(f_clear), g.dev(f_n), g.dev(f_near), g.dev(f_k), g.dev(f_t),
+                                g.dev(f_pair), g.dev(f_end), g.dev(f_qmin), nullptr);
     if (rc != MOPA_OK) return rc;
     HIP_TRY(g.fetch());
     g.out(f_clear, clearance_out); g.out(f_t, t_min_out); g.out(f_end, end_clearance_out);
     g.out(f_n, n_states_out); g.out(f_near, n_near_out); g.out(f_k, k_min_out); g.out(f_pair, pair_min_out);
     g.out(f_qmin, q_min_out);
     return MOPA_OK;
+}
+extern "C" int mopa_motion_clearance(MopaScene *S, const double *qpos_a, const double *qpos_b, double band, double *clearance_out,
+                                     int32_t *n_states_out, int32_t *n_near_out, int32_t *k_min_out, double *t_min_out, int32_t *pair_min_out,
+                                     double *end_clearance_out, double *q_min_out) {
+    return motion_clearance_one(false, S, qpos_a, qpos_b, band, clearance_out, n_states_out, n_near_out, k_min_out, t_min_out, pair_min_out,
+                                end_clearance_out, q_min_out);
+}
+extern "C" int mopa_motion_clearance_exact(MopaScene *S, const double *qpos_a, const double *qpos_b, double band, double *clearance_out,
+                                           int32_t *n_states_out, int32_t *n_near_out, int32_t *k_min_out, double *t_min_out, int32_t *pair_min_out,
+                                           double *end_clearance_out, double *q_min_out) {
+    return motion_clearance_one(true, S, qpos_a, qpos_b, band, clearance_out, n_states_out, n_near_out, k_min_out, t_min_out, pair_min_out,
+                                end_clearance_out, q_min_out);
 }

@@ -24,7 +24,11 @@ Differences that cannot be hidden (DESIGN.md "Semantics"):
     ``clearance_band`` ("K3b under the clearance
     objective"; a stated deviation from OMPL: the cost is the pair
     (clearance, then L1 length)), and ``plan`` then leaves the clearance
-    in ``last_cost`` and the length in ``last_length``;
+    in ``last_cost`` and the length in ``last_length``.  The planner stays
+    on the inflated (margin-rule) distances: ``path_clearance(rows,
+    exact=True)`` of a returned path is never lower than the planner's
+    clearance, up to kGjkTol = 1e-6; equality of bits holds with
+    ``exact=False`` only;
   * ``opt``, ``num_actions``, ``goal_bias``, ``simplified_duration`` are
     accepted and ignored exactly as the reference ignores them
     (KinematicPlanner.cpp:42-61); ``is_simplified=True`` is rejected
@@ -246,13 +250,14 @@ class PyKinematicPlanner:
             return self._scene.contacts_state(np.asarray(state_vec, dtype=np.float64), manifold=True, max_points=max_points, point_cutoff=point_cutoff)
         return self._scene.contacts_state(np.asarray(state_vec, dtype=np.float64), frames=frames)
 
-    def proximity(self, state_vec, band: float, max_pairs: int = 8):
+    def proximity(self, state_vec, band: float, max_pairs: int = 8, exact: bool = False):
         """how far from collision `state_vec` is and which pairs are nearest: (clearance, [(geom1_name, geom2_name, dist), ...]),
-        clearance saturating at `band`, the pairs with dist <= band nearest first (`Scene.proximity_state`).  With glue_bodies it
+        clearance saturating at `band`, the pairs with dist <= band nearest first (`Scene.proximity_state`); exact=True: GJK distances
+        for disjoint box-box, cylinder and mesh pairs instead of the margin rule's.  With glue_bodies it
         raises: the proximity report is not built for a glued scene"""
         if self.glue_bodies:
             raise NotImplementedError("proximity() with glue_bodies: the proximity report is not built for a glued scene")
-        return self._scene.proximity_state(np.asarray(state_vec, dtype=np.float64), band, max_pairs)
+        return self._scene.proximity_state(np.asarray(state_vec, dtype=np.float64), band, max_pairs, exact=exact)
 
     def motion_report(self, start_vec, goal_vec, max_contacts: int = 0) -> dict:
         """where the straight line from `start_vec` to `goal_vec` (full qpos vectors; the passive entries are start_vec's) is
@@ -264,20 +269,22 @@ class PyKinematicPlanner:
             raise NotImplementedError("motion_report() with glue_bodies: the motion report is not built for a glued scene")
         return self._scene.motion_report_state(np.asarray(start_vec, dtype=np.float64), np.asarray(goal_vec, dtype=np.float64), max_contacts=max_contacts)
 
-    def motion_clearance(self, start_vec, goal_vec, band: float) -> dict:
+    def motion_clearance(self, start_vec, goal_vec, band: float, exact: bool = False) -> dict:
         """how near the straight line from `start_vec` to `goal_vec` (full qpos vectors; the passive entries are start_vec's) comes
         to collision -- OMPL's MinimaxObjective::motionCost under the clearance state cost: `clearance`, `n_states`, `n_near`,
-        `k_min`, `t_min`, `pair` as (geom1_name, geom2_name), `pair_min`, `end_clearance`, `q_min` (`Scene.motion_clearance_state`).
-        With glue_bodies it raises: the clearance report is not built for a glued scene"""
+        `k_min`, `t_min`, `pair` as (geom1_name, geom2_name), `pair_min`, `end_clearance`, `q_min` (`Scene.motion_clearance_state`);
+        exact=True: over the state clearances of `proximity(..., exact=True)`.  With glue_bodies it raises: the clearance report is not built for a glued scene"""
         if self.glue_bodies:
             raise NotImplementedError("motion_clearance() with glue_bodies: the clearance report is not built for a glued scene")
-        return self._scene.motion_clearance_state(np.asarray(start_vec, dtype=np.float64), np.asarray(goal_vec, dtype=np.float64), band)
+        return self._scene.motion_clearance_state(np.asarray(start_vec, dtype=np.float64), np.asarray(goal_vec, dtype=np.float64), band,
+                                                  exact=exact)
 
-    def path_clearance(self, traj, band: float) -> dict:
+    def path_clearance(self, traj, band: float, exact: bool = False) -> dict:
         """the clearance of a path as `plan` returns it (a list of full qpos vectors): `clearance` (the smallest state clearance
         along it, vertex 0 included, saturating at band), `seg_min` (the first segment that attains it; -1: vertex 0 does, or
         nothing is within the band), `k_min`, `pair` as (geom1_name, geom2_name) or None, `pair_min`, `mean_vertex_clearance`
-        (`BatchPlanner.path_clearance`).  With glue_bodies it raises: the clearance report is not built for a glued scene"""
+        (`BatchPlanner.path_clearance`); exact=True: with the exact route's distances -- for a path planned under
+        objective = "maximize_min_clearance" never lower than the planner's clearance, up to 1e-6.  With glue_bodies it raises: the clearance report is not built for a glued scene"""
         if self.glue_bodies:
             raise NotImplementedError("path_clearance() with glue_bodies: the clearance report is not built for a glued scene")
         import torch
@@ -289,7 +296,7 @@ class PyKinematicPlanner:
         plen = torch.tensor([len(rows)], dtype=torch.int32, device=dev)
         if self._batch is None:
             self._batch = BatchPlanner(self._scene)
-        r = self._batch.path_clearance(path, plen, band=band)
+        r = self._batch.path_clearance(path, plen, band=band, exact=exact)
         m = self._model
         pair = int(r.pair_min[0])
         g = np.asarray(m.pair_geom).reshape(-1, 2)

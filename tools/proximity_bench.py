@@ -9,6 +9,12 @@ ms per call (median [min .. max]) and each form's ratio to is_valid.  The figure
 state a wave of its own and runs no verdict early-out, and its cost grows with the band through the margin broad phase.
 
     python tools/proximity_bench.py --out profiles/r31/proximity_bench.txt
+
+--exact adds an `exact` column: proximity(band, exact=True) at the bands above 0 joins the same alternated rounds, and each is reported
+with its ratio to proximity(band) without the keyword (GJK on the shapes as they are against the inflated portal refinement).  Without the
+flag the forms, the rounds and the output are what they were.
+
+    python tools/proximity_bench.py --exact --out profiles/r39/proximity_bench.txt
 """
 from __future__ import annotations
 
@@ -40,6 +46,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--reps", type=int, default=5, help="calls per timed window")
     ap.add_argument("--max-pairs", type=int, default=8)
+    ap.add_argument("--exact", action="store_true", help="add proximity(band, exact=True) to the rounds and its ratio to the inflated route")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     sys.path.insert(0, os.path.dirname(HERE))
@@ -67,6 +74,9 @@ def main():
     forms = [("is_valid", lambda: bp.is_valid(q, rows, samples_per_env=S)),
              ("contacts(cutoff=threshold)", lambda: bp.contacts(q, rows, samples_per_env=S, max_contacts=args.max_pairs))]
     forms += [(f"proximity(band={b})", lambda b=b: bp.proximity(q, rows, samples_per_env=S, band=b, max_pairs=args.max_pairs)) for b in BANDS]
+    exact_bands = [b for b in BANDS if b > 0] if args.exact else []
+    forms += [(f"proximity(band={b}, exact)", lambda b=b: bp.proximity(q, rows, samples_per_env=S, band=b, max_pairs=args.max_pairs, exact=True))
+              for b in exact_bands]
     for _, fn in forms:
         fn()
     torch.cuda.synchronize()
@@ -85,10 +95,21 @@ def main():
              f"{args.rounds} alternated rounds of {args.reps} calls per window (device events, one synchronise per window); ms per call: median [min .. max]", ""]
     for name, _ in forms:
         lines.append(f"    {name:30s}{med(times[name])}    x {np.median(times[name]) / base:.2f} of is_valid")
+    for b in exact_bands:
+        r = np.array(times[f"proximity(band={b}, exact)"]) / np.array(times[f"proximity(band={b})"])
+        lines.append(f"    exact / inflated at band {b}: x {np.median(times[f'proximity(band={b}, exact)']) / np.median(times[f'proximity(band={b})']):.3f}"
+                     f"  (per round {r.min():.3f} .. {r.max():.3f})")
     lines.append("")
     for b in BANDS:
         c = reps[b].count
         lines.append(f"    band {b}: pairs in band per state: mean {c.double().mean().item():.2f}, max {int(c.max())};  states with none: {(c == 0).double().mean().item() * 100:.1f} %")
+    for b in exact_bands:
+        ex = bp.proximity(q, rows, samples_per_env=S, band=b, max_pairs=args.max_pairs, exact=True)
+        torch.cuda.synchronize()
+        assert torch.equal(valid, ex.clearance > pi.spec.contact_threshold), "the exact report's clearance disagrees with is_valid"
+        gain = ex.clearance - reps[b].clearance
+        lines.append(f"    band {b}, exact: pairs in band per state: mean {ex.count.double().mean().item():.2f};  clearance above the inflated one: "
+                     f"mean {gain.mean().item():.2e}, max {gain.max().item():.2e}, min {gain.min().item():.2e}")
     text = "\n".join(lines) + "\n"
     print(text)
     if args.out:
