@@ -420,6 +420,18 @@ def sample(pi, n, seed):
     return np.random.default_rng([seed, 3]).uniform(pi.jnt_minimum, pi.jnt_maximum, size=(n, len(pi.jnt_minimum)))
 
 
+#: the states of the exact-route tests (test_random_scenes_host shows that they reach the route, test_random_scenes_gpu runs them):
+#: the first 65 of `sample(pi, ., 7)` on the five rows of `env_rows(pi, 5, 7)`, 13 per row
+N_EXACT, EXACT_SPE = 65, 13
+#: the report scenes and the two that the compiler places differently: 64 moving geoms, centres in the slab
+EXACT_KEYS = [0, 3, 7, 15, "tile_posed", "mesh", "deep_branches", "wide", "full", "slab_centres"]
+
+
+def exact_states(pi):
+    """(qa [65, na], rows [5, nq], samples_per_env)"""
+    return sample(pi, N_EXACT, 7), env_rows(pi, (N_EXACT + EXACT_SPE - 1) // EXACT_SPE, 7), EXACT_SPE
+
+
 def segments(pi, n, seed, span=0.08):
     """(qa, qb) [n, na]: short segments (up to `span` of a coordinate's extent: a dozen states), a quarter of them long, some of zero
     length, and on an SO2 coordinate some across the +-pi seam"""

@@ -1,7 +1,8 @@
 """The scene-level kernels off the four shipped scenes: on random body trees and on one directed scene per decision of the scene
 compiler (random_scenes.py) the FK, the per-pair distances, the verdicts of all three K1 generations, K2, the four reports and
 RRT-Connect are bit-identical to the CPU oracle or to the existing sequential forms, as on the shipped scenes: every comparison is on
-bits, no tolerance is involved.  229 states = three full tiles and a tail of 37, 50 per env row: five rows with different passive
+bits, no tolerance is involved.  The proximity and clearance reports also run with exact=True (the GJK route) against the sequential
+forms under the exact host pair table, on random_scenes.EXACT_KEYS.  229 states = three full tiles and a tail of 37, 50 per env row: five rows with different passive
 values and free-body poses, tiles that span two rows.  No test here provokes a fault."""
 import functools
 
@@ -10,6 +11,7 @@ import pytest
 
 import motion_clearance_ref as MC
 import motion_report_ref as MR
+import proximity_exact_ref as X
 import proximity_ref as P
 import random_scenes as RS
 from contacts_ref import FAR, ignored_mask, oracle_pair_dists, report_from_dists
@@ -256,6 +258,87 @@ def _motion_refs(key):
     assert 0 < rep["valid"].sum() < N_REP, (key, int(rep["valid"].sum()))        # blocked and free segments
     return {"report": rep, "blockers": MR.blockers(w.pi, w.orc, rep, rows, 2, REP_SPE),
             "clearance": MC.motion_clearance(w.pi, w.orc, qa, qb, rows, 0.01, REP_SPE)}
+
+
+# ---------------- the exact route of the proximity and clearance reports ----------------
+# (test_random_scenes_host::test_the_exact_route_is_reached: on every one of these scenes the states below hold separated pairs that
+# gjk_distance answers for)
+@functools.lru_cache(maxsize=None)
+def _exact_refs(key):
+    """the sequential forms under the exact host pair table: proximity tables per band on RS.exact_states, the clearance report of the
+    64 report segments per band, and paths of 0 .. 3 vertices made of those segments with their path report"""
+    w = _WORLDS[key]
+    pi = w.pi
+    qs, srows, spe = RS.exact_states(pi)
+    gpos, gmat = P.poses(pi, w.orc, qs, srows, spe)
+    qa, qb, rows = _report_inputs(key)
+    E = 24
+    hp = np.zeros((E, 3, w.m.nq))
+    for e in range(E):
+        for j, q in enumerate((qa[e], qb[e], qa[e + 1])):
+            hp[e, j] = RS.full_state(pi, q, rows[e // REP_SPE])
+    hl = (np.arange(E) % 4).astype(np.int32)
+    out = {"states": (qs, srows, spe), "paths": (hp, hl), "D": {}, "clearance": {}, "path": {}}
+    for band in X.BANDS:
+        out["D"][band] = X.pair_dists(pi, gpos, gmat, band)
+        with X.exact_host():
+            out["clearance"][band] = MC.motion_clearance(pi, w.orc, qa, qb, rows, band, REP_SPE)
+            out["path"][band] = MC.path_clearance(pi, w.orc, hp, hl, band)
+    # the exact table matters on these inputs
+    assert (_bits(out["D"][0.05]) != _bits(P.pair_dists(pi, gpos, gmat, 0.05))).any(), key
+    return out
+
+
+@pytest.mark.parametrize("world", RS.EXACT_KEYS, indirect=True, ids=_ids(RS.EXACT_KEYS))
+def test_exact_proximity_and_path_clearance(world):
+    import torch
+    from mopa_rl_amd.batch import BatchPlanner
+    w = world
+    ref = _exact_refs(w.key)
+    qs, srows, spe = ref["states"]
+    hp, hl = ref["paths"]
+    sc = w.scene()
+    try:
+        bp = BatchPlanner(sc)
+        tq, tr, tp, tl = _cuda(qs), _cuda(srows), _cuda(hp), _cuda(hl)
+        for band in X.BANDS:
+            for K in (1, 4):
+                want = P.select(ref["D"][band], band, K)
+                rep = bp.proximity(tq, tr, samples_per_env=spe, band=band, max_pairs=K, exact=True)
+                torch.cuda.synchronize()
+                for name, g, o in zip(("clearance", "count", "pair", "dist"), (rep.clearance, rep.count, rep.pair, rep.dist), want):
+                    g = g.cpu().numpy()
+                    assert g.dtype == o.dtype and g.shape == o.shape and g.tobytes() == o.tobytes(), f"{w.key} band {band} K {K}: exact proximity {name} differs in {(g != o).sum()} words"
+            got = bp.path_clearance(tp, tl, band=band, exact=True)
+            torch.cuda.synchronize()
+            for k in ("clearance", "seg_min", "k_min", "pair_min", "mean_vertex_clearance"):
+                g, o = getattr(got, k).cpu().numpy(), ref["path"][band][k]
+                assert g.dtype == o.dtype and g.tobytes() == o.tobytes(), (w.key, band, k, g, o)
+    finally:
+        sc.close()
+
+
+@pytest.mark.parametrize("kernel", [None, "v5"])        # the wave-per-segment form / the expanded one, as in test_motion_report_and_clearance
+@pytest.mark.parametrize("world", RS.EXACT_KEYS, indirect=True, ids=_ids(RS.EXACT_KEYS))
+def test_exact_motion_clearance(world, kernel):
+    import torch
+    from mopa_rl_amd.batch import BatchPlanner
+    w = world
+    qa, qb, rows = _report_inputs(w.key)
+    ref = _exact_refs(w.key)
+    sc = w.scene(kernel)
+    try:
+        assert sc.motion_kernel(N_REP) == ("k_motion_expand" if kernel else "k_check_motion")
+        bp = BatchPlanner(sc)
+        ta, tb, tr = _cuda(qa), _cuda(qb), _cuda(rows)
+        for band in X.BANDS:
+            cl = bp.motion_clearance(ta, tb, tr, samples_per_env=REP_SPE, band=band, states=True, exact=True)
+            torch.cuda.synchronize()
+            for k in MC.OUTPUTS:
+                g, o = getattr(cl, k).cpu().numpy(), ref["clearance"][band][k]
+                assert g.dtype == o.dtype and g.shape == o.shape and g.tobytes() == o.tobytes(), f"{w.key} {kernel} band {band}: exact clearance {k} differs at {np.nonzero(np.atleast_2d((g != o).T).any(axis=0))[0][:8]}"
+    finally:
+        sc.close()
 
 
 # ---------------- RRT-Connect ----------------

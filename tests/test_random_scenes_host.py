@@ -1,7 +1,8 @@
 """The scene compiler and the oracle off the four shipped scenes, host side (no GPU): on random body trees and on one directed scene
 per decision of the compiler (random_scenes.py) the oracle's FK equals an independent composition, every scene compiles into a save-slot
 program in which no body continues from another body's pose, the set reaches the compiler states it is meant to reach (asserted), the
-oracle's verdicts are mixed and every pair class decides some state; and malformed models -- the ones that used to crash the compiler
+oracle's verdicts are mixed and every pair class decides some state, the states of the exact-route GPU tests hold separated pairs that
+gjk_distance answers for; and malformed models -- the ones that used to crash the compiler
 included -- are refused with a status and a message by the export and by the create entry points, in this process."""
 import copy
 import functools
@@ -219,6 +220,38 @@ def test_state_mix_and_deciding_pair_classes(oracle_mod):
     for c in PRIMITIVE_CLASSES + ["plane-mesh"]:
         assert deciding.get(c, 0) >= 1, c
     assert any(c.endswith("-mesh") and not c.startswith("plane") for c in deciding)
+
+
+# ---------------- the states of the exact-route tests reach the route ----------------
+def test_the_exact_route_is_reached(oracle_mod):
+    """sequential form alone: per scene of RS.EXACT_KEYS the separated pairs of an inflated class (box-box, cylinder-*, *-mesh) that the
+    exact table reports inside the 5 cm band over RS.exact_states -- the pairs gjk_distance answers for -- and, at 1 cm, likewise.  A scene
+    without one is listed: at most a quarter of the scenes, and none of the scenes that are there for a reason."""
+    import proximity_exact_ref as X
+    import proximity_ref as P
+    none, tilted = [], []
+    for key in RS.EXACT_KEYS:
+        m, pi, args = _args(key)
+        orc = oracle_mod.OracleScene(*args)
+        qa, rows, spe = RS.exact_states(pi)
+        assert len(qa) == RS.N_EXACT
+        gpos, gmat = P.poses(pi, orc, qa, rows, spe)
+        infl = X.inflated_pairs(m)
+        n = {}
+        for band in X.BANDS:
+            De, Di = X.pair_dists(pi, gpos, gmat, band), P.pair_dists(pi, gpos, gmat, band)
+            n[band] = int(((De > 0) & (De <= band))[:, infl].sum())
+            # the exact table is not the inflated one wherever such a pair is counted, and is the inflated one on every other class
+            assert n[band] == 0 or (De.view(np.uint64) != Di.view(np.uint64))[:, infl].any(), (key, band)
+            assert np.array_equal(De[:, ~infl].view(np.uint64), Di[:, ~infl].view(np.uint64)), (key, band)
+        print(key, "separated pairs of an inflated class in band:", n, "of", int(infl.sum()), "such pairs x", len(qa), "states")
+        if n[0.05] == 0:
+            none.append(key)
+        elif any(t == 0 and m.geom_body[g] != 0 for g, t in enumerate(m.geom_type)):
+            tilted.append(key)
+    print("scenes without such a pair:", none, "; tilted-plane scenes with one:", tilted)
+    assert len(none) <= len(RS.EXACT_KEYS) // 4, none
+    assert not {"mesh", "full", "slab_centres"} & set(none) and tilted, (none, tilted)
 
 
 # ---------------- malformed models are refused, by the export and by scene creation ----------------
