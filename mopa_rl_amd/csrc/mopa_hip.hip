@@ -295,6 +295,18 @@ MOPA_D void stage_scene(const SceneHdr &h, const double *g_dbl, const int32_t *g
     __syncthreads();
 }
 
+// What k_is_valid_v5 reads out of LDS on a baked scene, in the places stage_scene puts it (so LdsView and the header's offsets serve
+// unchanged): the walk and pass A run on literals, which leaves the geom records and types, the moving geoms' geom ids (v5_flush,
+// v5_load_rec2) and word 7 of every pair-table entry (pass A's broadcast, v5_flush).  Everything else in the blobs stays uncopied --
+// about a third of stage_scene's bytes on Push, before a workgroup's first tile.  Ends with __syncthreads(), as stage_scene does.
+MOPA_D void stage_scene_k1_baked(const SceneHdr &h, const double *g_dbl, const int32_t *g_int, const int32_t *g_tab, double *s_dbl, int *s_int, int *s_tab) {
+    for (int i = threadIdx.x; i < h.ng * kGeomStride; i += blockDim.x) s_dbl[h.o_g_rec + i] = g_dbl[h.o_g_rec + i];
+    for (int i = threadIdx.x; i < h.ng; i += blockDim.x) s_int[h.o_g_type + i] = g_int[h.o_g_type + i];
+    for (int i = threadIdx.x; i < h.nmg; i += blockDim.x) s_int[h.o_mg_geom + i] = g_int[h.o_mg_geom + i];
+    for (int i = threadIdx.x; i < h.n_gp; i += blockDim.x) s_tab[8 * i + 7] = g_tab[8 * i + 7];
+    __syncthreads();
+}
+
 MOPA_D LdsView make_view(const SceneHdr &h, unsigned char *smem) {
     LdsView v;
     double *s_dbl = reinterpret_cast<double *>(smem);

@@ -228,6 +228,22 @@ extern "C" int mopa_scene_motion_kernel(const MopaScene *S, int64_t N, char *out
     return MOPA_OK;
 }
 
+// MOPA_V5_TIMELINE (the diagnostic build of tools/k1_wave_timeline.py): the rows of the last lane-per-state launch, [waves][kTlRow]
+// words, copied out once the device is idle; returns the number of rows (mopa_valid_v5.inc has the row's layout)
+#ifdef MOPA_V5_TIMELINE
+constexpr size_t kK1TimelineWords = kTlRow;
+static unsigned long long *g_k1_timeline = nullptr;
+static long long g_k1_timeline_rows = 0;
+extern "C" long long mopa_k1_timeline_read(unsigned long long *out, long long cap_rows) {
+    if (!out || !g_k1_timeline || hipDeviceSynchronize() != hipSuccess) return -1;
+    const long long n = std::min(cap_rows, g_k1_timeline_rows);
+    if (n > 0 && hipMemcpy(out, g_k1_timeline, (size_t)n * kTlRow * 8, hipMemcpyDeviceToHost) != hipSuccess) return -1;
+    return n;
+}
+#else
+constexpr size_t kK1TimelineWords = 0;
+#endif
+
 // state validity of N states; env row of state i = env_idx ? env_idx[i] : i / samples_per_env
 // n_dev (nullable): the number of states is only known on the device (*n_dev <= N, N then sizes the launch): served by the
 // lane-per-state kernel, which reads it when it starts -- no host read-back between the producer of the states and this launch
@@ -262,7 +278,7 @@ static int launch_is_valid(MopaScene *S, const double *q_active, const double *q
         // (a pair-drain plan keeps one slab region per tile of a drain: on Push 2 x 57 KB per wave, 235 MB per stream at 2048 waves)
         const size_t want = std::max(std::max(p.waves, sc.slab_waves), (size_t)S->n_cu * 2 * kWavesPerBlock);
         const size_t tiles = std::max((size_t)p.tiles_per_drain, sc.slab_tiles);
-        HIP_TRY(grow(S, sc.slab, (want * tiles * (size_t)(S->hdr.nmg + S->hdr.n_save) * kSlabStride + 16) * sizeof(double)));
+        HIP_TRY(grow(S, sc.slab, (want * tiles * (size_t)(S->hdr.nmg + S->hdr.n_save) * kSlabStride + 16 + want * kK1TimelineWords) * sizeof(double)));
         HIP_TRY(grow(S, sc.mpr, want * (size_t)kMprCapV5 * kMprRow * sizeof(double)));
         HIP_TRY(grow(S, sc.cen, want * (size_t)S->hdr.nmg * 3 * 64 * sizeof(float)));
         sc.slab_waves = want;
@@ -284,6 +300,12 @@ static int launch_is_valid(MopaScene *S, const double *q_active, const double *q
     double *d_tail = d_slab + (size_t)p.blocks * kWavesPerBlock * p.tiles_per_drain * (S->hdr.nmg + S->hdr.n_save) * kSlabStride;
     unsigned long long *d_prof = (unsigned long long *)d_tail;
     (void)zero_async(d_prof, 6 * 8, st);
+#endif
+#ifdef MOPA_V5_TIMELINE
+    // the waves' timeline rows live right behind the slabs of this launch's waves (where k_is_valid_v5 looks for them)
+    g_k1_timeline = reinterpret_cast<unsigned long long *>(d_slab + (size_t)p.blocks * kWavesPerBlock * p.tiles_per_drain * (S->hdr.nmg + S->hdr.n_save) * kSlabStride);
+    g_k1_timeline_rows = p.v5 ? (long long)p.waves : 0;
+    HIP_TRY(zero_async(g_k1_timeline, p.waves * (size_t)kTlRow * 8, st));
 #endif
     long long *mesh_list = nullptr;
     unsigned long long *rows_cnt = nullptr;

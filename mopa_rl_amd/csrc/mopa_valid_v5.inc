@@ -452,8 +452,9 @@ MOPA_HD void k1_fk_body(K1FkRegs<TR> &r, const double *qact, const double *sn, c
 }
 // SPARSE: marked bodies take their sparse form; returns the lane's guard flag (the caller re-runs the dense walk, SPARSE = false,
 // when it is set; the dense walk returns false)
-template <class TR, bool SPARSE = false, class Sink, int... B>
-MOPA_HD bool k1_fk_baked(const double *qa_row, const double *env_row, Sink &sink, std::integer_sequence<int, B...>) {
+// QP: pointer to the input rows (const double *; the kernel's cold walk passes its laundered rows typed as global memory)
+template <class TR, bool SPARSE = false, class QP, class Sink, int... B>
+MOPA_HD bool k1_fk_baked(QP qa_row, QP env_row, Sink &sink, std::integer_sequence<int, B...>) {
     static_assert(TR::na <= 8 && TR::n_pq >= 1 && TR::n_save >= 1, "baked walk: at most 8 active values; array sizes padded to 1");
     static_assert(TR::n_res <= kResMax, "baked walk: at most kResMax resident pairs");
     double qact[TR::na], pv[TR::n_pq], sn[TR::na], cs[TR::na];
@@ -482,14 +483,26 @@ MOPA_HD bool k1_fk_baked(const double *qa_row, const double *env_row, Sink &sink
 // MPR ring read, exactly as the generic walk writes them)
 // COLD: the dense walk behind the sparse one's guard.  Each geom's slab address passes through an empty asm: in that rarely run
 // block the compiler otherwise forms all the rows' addresses up front and spills VGPRs to hold them.
+// The slab pointer is typed as global memory: an empty asm hides where a pointer came from, and through a generic pointer every pose
+// store is a FLAT instruction -- issued to the LDS queue as well, counted in lgkmcnt, and every LDS wait behind one becomes
+// lgkmcnt(0).  The type survives the asm, so the 98 stores of a walk are global_store and pass A's first centre read waits for LDS only.
+#ifdef MOPA_V5_FLAT_SLAB      // knock-out (tools/k1_knock.sh flatslab): generic pointers, as before
+typedef double k1_gdouble;
+typedef const double k1_gcdouble;
+#else
+typedef __attribute__((address_space(1))) double k1_gdouble;
+typedef const __attribute__((address_space(1))) double k1_gcdouble;
+#endif
 template <bool COLD>
 struct V5FkSinkT {
-    double *slab;   // this lane's place in the wave's slab
+    k1_gdouble *slab;   // this lane's place in the wave's slab
     float *cen;     // this lane's place in the centre table
     MOPA_D void operator()(int m, V3 gp, Q4 gq) {
-        double *sp = slab + (size_t)m * kSlabStride;
+        k1_gdouble *sp = slab + (size_t)m * kSlabStride;
         if constexpr (COLD) asm volatile("" : "+v"(sp));
-        pose7_st<64>(sp, gp, gq);
+        // (pose7_st<64>, through the typed pointer)
+        sp[0] = gp.x; sp[64] = gp.y; sp[2 * 64] = gp.z;
+        sp[3 * 64] = gq.w; sp[4 * 64] = gq.x; sp[5 * 64] = gq.y; sp[6 * 64] = gq.z;
         float *cp = cen + (size_t)m * 3 * 64;
         cp[0] = (float)gp.x; cp[64] = (float)gp.y; cp[128] = (float)gp.z;
     }
@@ -696,6 +709,43 @@ MOPA_D void v5_drain(const SceneHdr &h, const LdsView &v, const V5Lds &q, const 
     }
 }
 
+// MOPA_V5_TIMELINE: the diagnostic build of tools/k1_wave_timeline.py (never the production library).  Every wave stamps the constant
+// 100 MHz clock (s_memrealtime) where its life changes phase, into its own row of kTlRow words behind the launch's pose slabs (lane 0,
+// plain vector stores; launch_is_valid sizes and zeroes the rows, mopa_k1_timeline_read copies them out).  Row: [0] kernel entry,
+// [1] staged, [2] pulls (the one that found no tile included), [3] the last pull that got a tile, [4] the pull that found none = in
+// front of the final portal flush, [5] behind that flush, [6] exit, [7] rows in that flush, [8] tiles, [9] HW_ID, [10 ..] every pull.
+constexpr int kTlRow = 64, kTlPulls = kTlRow - 10;
+#ifdef MOPA_V5_TIMELINE
+#define V5_TL_DECL const unsigned long long tl_t0 = __builtin_amdgcn_s_memrealtime();
+#define V5_TL_STAGED const unsigned long long tl_t1 = __builtin_amdgcn_s_memrealtime();
+#define V5_TL_ROW(tail_, w_)                                                                                  \
+    unsigned long long *const tl_row = reinterpret_cast<unsigned long long *>(tail_) + (w_) * (size_t)kTlRow; \
+    unsigned tl_pulls = 0u, tl_tiles = 0u;                                                                    \
+    if (lane == 0) { tl_row[0] = tl_t0; tl_row[1] = tl_t1; tl_row[9] = (unsigned long long)__builtin_amdgcn_s_getreg(4 | (31 << 11)) | ((unsigned long long)__builtin_amdgcn_s_getreg(20 | (3 << 11)) << 32); }   /* HW_ID | XCC_ID << 32 */
+#define V5_TL_PULL(fin_)                                                                  \
+    {                                                                                     \
+        const unsigned long long tl_t = __builtin_amdgcn_s_memrealtime();                 \
+        if (lane == 0) {                                                                  \
+            if (tl_pulls < (unsigned)kTlPulls) tl_row[10 + tl_pulls] = tl_t;              \
+            tl_row[(fin_) ? 4 : 3] = tl_t;                                                \
+        }                                                                                 \
+        tl_pulls++;                                                                       \
+    }
+#define V5_TL_TILE tl_tiles++;
+#define V5_TL_MPR0(fin_, n_) if ((fin_) && lane == 0) tl_row[7] = (unsigned long long)(n_);
+#define V5_TL_MPR1(fin_) if ((fin_) && lane == 0) tl_row[5] = __builtin_amdgcn_s_memrealtime();
+#define V5_TL_EXIT if (lane == 0) { tl_row[2] = tl_pulls; tl_row[8] = tl_tiles; tl_row[6] = __builtin_amdgcn_s_memrealtime(); }
+#else
+#define V5_TL_DECL
+#define V5_TL_STAGED
+#define V5_TL_ROW(tail_, w_)
+#define V5_TL_PULL(fin_)
+#define V5_TL_TILE
+#define V5_TL_MPR0(fin_, n_)
+#define V5_TL_MPR1(fin_)
+#define V5_TL_EXIT
+#endif
+
 // CEN_LDS: the FP32 centre table of the tile lives in LDS (3 x 256 B per moving geom and wave).  Scenes with many moving
 // geoms (Assembly 34, Lift 19) then get one workgroup per CU; with CEN_LDS = false the table of each wave lives in global
 // memory instead (same FP32 values => the same survivors; 26 KB per wave for Assembly, a fifth of its pose slab, and the
@@ -726,13 +776,23 @@ __global__ __launch_bounds__(kBlock, TR::kBaked ? 2 : 1) void k_is_valid_v5(Scen
         if (nd < N) N = nd;
         if (nd < n_small) N = 0;
     }
+    V5_TL_DECL
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     double *s_dbl = reinterpret_cast<double *>(smem);
     int *s_int = reinterpret_cast<int *>(s_dbl + h.n_dbl);
     int *s_tab = s_int + ((h.n_int + 3) & ~3);                       // [n_gp][8] FP32 pair table
     constexpr int kTail = GATE ? 3 : 1;     // per geom after the entries: group counts [, first entry, count]
-    for (int i = threadIdx.x; i < 8 * h.n_gp + kTail * h.nmg; i += blockDim.x) s_tab[i] = g_tab[i];
-    stage_scene(h, g_dbl, g_int, s_dbl, s_int);                      // ends with __syncthreads()
+    // (MOPA_V5_FULL_STAGING: the knock-out of the baked scenes' lean staging, tools/k1_knock.sh fullstage)
+#ifndef MOPA_V5_FULL_STAGING
+    if constexpr (TR::kBaked) {
+        stage_scene_k1_baked(h, g_dbl, g_int, g_tab, s_dbl, s_int, s_tab);   // ends with __syncthreads()
+    } else
+#endif
+    {
+        for (int i = threadIdx.x; i < 8 * h.n_gp + kTail * h.nmg; i += blockDim.x) s_tab[i] = g_tab[i];
+        stage_scene(h, g_dbl, g_int, s_dbl, s_int);                      // ends with __syncthreads()
+    }
+    V5_TL_STAGED
     LdsView v;
     v.dbl = s_dbl; v.ints = s_int; v.grec = nullptr; v.qbuf = nullptr; v.sc = nullptr; v.wl = nullptr;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -764,6 +824,7 @@ __global__ __launch_bounds__(kBlock, TR::kBaked ? 2 : 1) void k_is_valid_v5(Scen
     float *gcen = CEN_LDS ? nullptr : cen_all + ((size_t)blockIdx.x * kWavesPerBlock + wave) * (size_t)h.nmg * 3 * 64 + lane;
     int mpr_head = 0, mpr_count = 0;      // deferred cylinder pairs of this wave (persist across tiles)
     const long long n_tiles = (N + 63) >> 6;
+    V5_TL_ROW(slab_all + (size_t)gridDim.x * kWavesPerBlock * (size_t)(T * nslab) * kSlabStride, (size_t)blockIdx.x * kWavesPerBlock + wave)
     // tile counter [0] + count of waves that have run out of tiles [1]: zero between launches -- the last wave to leave resets both
     // (tile_ctr_release), so no launch has to zero them first
     for (;;) {
@@ -782,6 +843,7 @@ __global__ __launch_bounds__(kBlock, TR::kBaked ? 2 : 1) void k_is_valid_v5(Scen
             }
         }
         const bool fin = tile >= n_tiles;      // (pair drain: decided on the first tile of the pair)
+        V5_TL_PULL(fin)
         if (!fin) {
         int n_ent;                 // survivor entries in the buffer and the pair classes among them: zeroed by the first half, and
         unsigned present;          // by every drain
@@ -794,6 +856,7 @@ __global__ __launch_bounds__(kBlock, TR::kBaked ? 2 : 1) void k_is_valid_v5(Scen
 #pragma unroll 1
         do {
         if (T > 1 && hf > 0 && (single || tile + hf >= n_tiles)) break;       // no second tile (a single pull; an odd tile count or a device-side count that ends in the pair)
+        V5_TL_TILE
         s = (tile + hf) * 64 + lane;
         act = s < N;
         if (!act) s = N - 1;
@@ -814,7 +877,8 @@ __global__ __launch_bounds__(kBlock, TR::kBaked ? 2 : 1) void k_is_valid_v5(Scen
             //  straight-line walk are hoisted out of the tile loop and held in VGPR pairs for the whole kernel)
             double *fk_slab = T > 1 ? slab + (size_t)hf * (size_t)nslab * kSlabStride : slab;
             asm volatile("" : "+v"(fk_slab));
-            V5FkSink sink{fk_slab, q.cen + lane, {}, 3 * TR::nmg};
+            k1_gdouble *const fk_slab_g = (k1_gdouble *)fk_slab;      // (the asm erased what the kernel argument said: global memory)
+            V5FkSink sink{fk_slab_g, q.cen + lane, {}, 3 * TR::nmg};
             // the sparse walk; a guard flag anywhere in the wave (rare: an exact zero in a stored pose, an input beyond 2^20 or not
             // finite): the dense walk for the tile, over everything the sparse one stored
             if constexpr (k1_sparse_on<TR>) {
@@ -824,8 +888,8 @@ __global__ __launch_bounds__(kBlock, TR::kBaked ? 2 : 1) void k_is_valid_v5(Scen
                     //  inputs, sines, the first bodies -- has to stay in registers for it)
                     const double *qa_cold = qa_row, *env_cold = env_row;
                     asm volatile("" : "+v"(qa_cold), "+v"(env_cold) : : "memory");
-                    V5FkSinkT<true> cold{fk_slab, q.cen + lane, {}, 3 * TR::nmg};
-                    k1_fk_baked<TR>(qa_cold, env_cold, cold, std::make_integer_sequence<int, TR::nmb>{});
+                    V5FkSinkT<true> cold{fk_slab_g, q.cen + lane, {}, 3 * TR::nmg};
+                    k1_fk_baked<TR>((k1_gcdouble *)qa_cold, (k1_gcdouble *)env_cold, cold, std::make_integer_sequence<int, TR::nmb>{});
 #pragma unroll
                     for (int r = 0; r < kResMax; r++) sink.res_d[r] = cold.res_d[r];
                 }
@@ -1258,6 +1322,7 @@ __global__ __launch_bounds__(kBlock, TR::kBaked ? 2 : 1) void k_is_valid_v5(Scen
         wave_sync();
         }
         // deferred cylinder pairs: full batches now, whatever is left when the wave runs out of tiles
+        V5_TL_MPR0(fin, mpr_count)
         while (mpr_count >= 64 || (fin && mpr_count > 0)) {
             const int nb = mpr_count < 64 ? mpr_count : 64;
             __threadfence_block();
@@ -1265,14 +1330,16 @@ __global__ __launch_bounds__(kBlock, TR::kBaked ? 2 : 1) void k_is_valid_v5(Scen
             mpr_head = (mpr_head + nb) & (kMprCapV5 - 1);
             mpr_count -= nb;
         }
+        V5_TL_MPR1(fin)
         if (fin) break;
     }
     tile_ctr_release(tile_ctr, lane);
+    V5_TL_EXIT
 }
 
 // The mesh pairs the gate of k_is_valid_v5 found within reach, as complete records (rows: geom 1 record[15], geom 2 record[15], state
-// index, types | pair class << 16): the pair routine on G = 16 lanes per row (they share the exhaustive vertex searches of the hull's
-// support function: mesh_support_local<G>, 7 of the can's 106 vertices per lane), 4 rows per wave and round; the verdict / depth is folded straight into the first pass's outputs
+// index, types | pair class << 16): the pair routine on G lanes per row (MOPA_MESH_ROWS_G, 8 as shipped; they share the exhaustive
+// vertex searches of the hull's support function: mesh_support_local<G>, 14 of the can's 106 vertices per lane), 64 / G = 8 rows per wave and round; the verdict / depth is folded straight into the first pass's outputs
 // (same stream, after it).  The hull vertices are staged in LDS.  Same routine on the same records as the state-list pass => the same bits.
 #ifndef MOPA_MESH_ROWS_G
 #define MOPA_MESH_ROWS_G 8

@@ -12,7 +12,8 @@ cd /tmp && export TMPDIR=/tmp
 BENCH="python $R/bench.py --no-cpu --no-plan --no-env --no-rollout --steps 5 --warmup 2"
 run() {  # name, rocprof args...
   name=$1; shift
-  rocprofv3 "$@" --output-format csv -d $WORK/$name -o $name -- $BENCH > $OUT/${name}_bench.log 2>&1
+  # (a pass that fails or outruns its limit ends the script: nothing more is started on a GPU that may have faulted)
+  timeout -k 10 ${PASS_TIMEOUT:-300} rocprofv3 "$@" --output-format csv -d $WORK/$name -o $name -- $BENCH > $OUT/${name}_bench.log 2>&1 || { echo "pass $name failed"; tail -5 $OUT/${name}_bench.log; exit 1; }
   for f in $(find $WORK/$name -name "*.csv"); do
     sz=$(stat -c %s $f)
     if [ $sz -lt 400000 ]; then cp $f $OUT/$(basename $f); else
