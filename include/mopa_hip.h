@@ -675,6 +675,34 @@ int mopa_geom_sep_exact_batch(int32_t device, int64_t M, const int32_t *types_de
  * closed form, band == 0, culled); negative where the iteration cap ended it (the value is then a lower bound of the distance). */
 int mopa_geom_sep_exact_host(int64_t M, const int32_t *types, const double *recs, const double *mesh_verts /*nullable*/, int32_t nvert,
                              double band, double *out, int32_t *iters_out /*[M] or NULL*/);
+/* Witness points (opt-in; DESIGN.md section 4, "Proximity report", paragraph "Witness points"): the exact route's report with, for
+ * every record, WHERE on the two shapes the distance is attained and in which direction.  mopa_proximity_exact_batch, then one
+ * more launch behind it that reads the rows it wrote; clearance / count / pair / dist are its bytes.  Per record (slot < min(count,
+ * K)) of pair (g1, g2) as the MopaSceneDesc lists it, world frame:
+ *   p1[i,k,:], p2[i,k,:]  a point of g1 and a point of g2 with |p2 - p1| = dist for separated shapes (to 1e-6 for the GJK classes:
+ *                 both are convex combinations of support points); for shapes in overlap the contact frame's two witness points,
+ *                 pos -/+ (dist / 2) normal
+ *   normal[i,k,:]  the unit vector from p1 towards p2 (separated) / the contact frame's normal (overlap): from g1 towards g2
+ * Unused slots hold 0.0.  Argument rules, refusals and status codes are mopa_proximity_exact_batch's (a glued or pruned scene:
+ * MOPA_ERR_UNSUPPORTED), a NULL among the three new buffers MOPA_ERR_INVALID_ARG; every refusal precedes the first launch; N == 0
+ * is a no-op.  Deterministic: every output word has one writer. */
+int mopa_proximity_witness_batch(MopaScene *scene, const double *q_active_dev /*[N,na]*/, const double *qpos_env_dev /*[E,nq]*/, int64_t N,
+                                 int64_t samples_per_env, double band, int32_t max_pairs /*K*/, double *clearance_dev /*[N]*/,
+                                 int32_t *count_dev /*[N]*/, int32_t *pair_dev /*[N,K]*/, double *dist_dev /*[N,K]*/,
+                                 double *normal_dev /*[N,K,3]*/, double *p1_dev /*[N,K,3]*/, double *p2_dev /*[N,K,3]*/, void *stream);
+/* the same for one state (host pointers, synchronous) */
+int mopa_proximity_witness_state(MopaScene *scene, const double *qpos_host /*[nq]*/, double band, int32_t max_pairs /*K*/,
+                                 double *clearance /*[1]*/, int32_t *count /*[1]*/, int32_t *pair /*[K]*/, double *dist /*[K]*/,
+                                 double *normal /*[K,3]*/, double *p1 /*[K,3]*/, double *p2 /*[K,3]*/);
+/* Pair level: types / recs / mesh_verts / band as mopa_geom_sep_exact_batch takes them; out [M,10] = d, n[3], p1[3], p2[3], d the
+ * bits of mopa_geom_sep_exact_batch, p1 on the FIRST geom given: the other order returns p1 / p2 exchanged and n negated.
+ * d == MOPA_FAR: the nine others are 0.0. */
+int mopa_geom_witness_batch(int32_t device, int64_t M, const int32_t *types_dev, const double *recs_dev,
+                            const double *mesh_verts_dev /*nullable*/, int32_t nvert, double band, double *out_dev /*[M,10]*/, void *stream);
+/* The host compile of the same functions -- the sequential form the kernels match bit for bit; no GPU, no HIP call.  iters_out as
+ * mopa_geom_sep_exact_host's. */
+int mopa_geom_witness_host(int64_t M, const int32_t *types, const double *recs, const double *mesh_verts /*nullable*/, int32_t nvert,
+                           double band, double *out /*[M,10]*/, int32_t *iters_out /*[M] or NULL*/);
 
 /* Clearance report: HOW NEAR a motion comes to collision, where along it and to which pair -- OMPL's
  * MinimaxObjective::motionCost(s1, s2) under the maximize_min_clearance state cost ("Clearance report").

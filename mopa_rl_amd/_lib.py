@@ -37,6 +37,7 @@ EXPORTED_SYMBOLS = [
     "mopa_contact_manifolds_batch", "mopa_contact_manifolds_state", "mopa_geom_manifolds_batch", "mopa_geom_manifolds_host",
     "mopa_proximity_batch", "mopa_proximity_state", "mopa_geom_sep_batch", "mopa_geom_sep_host",
     "mopa_proximity_exact_batch", "mopa_proximity_exact_state", "mopa_geom_sep_exact_batch", "mopa_geom_sep_exact_host",
+    "mopa_proximity_witness_batch", "mopa_proximity_witness_state", "mopa_geom_witness_batch", "mopa_geom_witness_host",
     "mopa_motion_clearance_exact_batch", "mopa_motion_clearance_exact",
     "mopa_motion_report_batch", "mopa_motion_report", "mopa_motion_clearance_batch", "mopa_motion_clearance",
     "mopa_env_create", "mopa_env_destroy", "mopa_env_obs_dim", "mopa_env_action_dim", "mopa_env_step_batch", "mopa_env_exec_batch", "mopa_env_desired_batch",
@@ -268,6 +269,10 @@ def lib() -> C.CDLL:
     L.mopa_proximity_exact_state.argtypes = L.mopa_proximity_state.argtypes
     L.mopa_geom_sep_exact_batch.argtypes = L.mopa_geom_sep_batch.argtypes
     L.mopa_geom_sep_exact_host.argtypes = [C.c_int64, _ip, _dp, _dp, C.c_int32, C.c_double, _dp, _ip]
+    L.mopa_proximity_witness_batch.argtypes = L.mopa_proximity_batch.argtypes[:-1] + [vp, vp, vp, vp]
+    L.mopa_proximity_witness_state.argtypes = L.mopa_proximity_state.argtypes + [_dp, _dp, _dp]
+    L.mopa_geom_witness_batch.argtypes = L.mopa_geom_sep_batch.argtypes
+    L.mopa_geom_witness_host.argtypes = L.mopa_geom_sep_exact_host.argtypes
     L.mopa_motion_report_batch.argtypes = [vp, vp, vp, vp, C.c_int64, C.c_int64, vp, vp, vp, vp, vp, vp, C.c_int32, vp, vp, vp, vp]
     L.mopa_motion_report.argtypes = [vp, _dp, _dp, _ip, _ip, _ip, _dp, _dp, _dp, C.c_int32, _ip, _ip, _dp]
     L.mopa_motion_clearance_batch.argtypes = [vp, vp, vp, vp, C.c_int64, C.c_int64, C.c_double, vp, vp, vp, vp, vp, vp, vp, vp, vp]
@@ -419,6 +424,24 @@ def geom_sep_host(types, recs, band: float, mesh_verts=None, exact: bool = False
         return (out, iters) if return_iters else out
     check(lib().mopa_geom_sep_host(len(t), tp, rp, vp_, len(v), float(band), out.ctypes.data_as(_dp)))
     return out
+
+
+def geom_witness_host(types, recs, band: float, mesh_verts=None, return_iters: bool = False):
+    """mopa_geom_witness_host: M posed pairs as `geom_frames_host` takes them -> [M, 10] = d, n[3], p1[3], p2[3] by the host compile
+    of the kernels' geom_witness (no GPU): d the bits of `geom_sep_host(..., exact=True)`; p1 a point of the first geom given, p2 of
+    the second, with |p2 - p1| = d where the shapes are apart (to 1e-6 for box-box, cylinder and mesh pairs) and the contact
+    frame's witness points pos -/+ (d / 2) n where they overlap; n the unit vector from the first geom towards the second.  The nine
+    are 0.0 where d is MOPA_FAR ("Witness points").  return_iters=True: -> (out, iters [M] int32) as
+    `geom_sep_host` returns them."""
+    t, tp = _i(np.asarray(types).reshape(-1, 2))
+    r, rp = _d(np.asarray(recs, dtype=np.float64).reshape(-1, 30))
+    if len(t) != len(r):
+        raise MopaError(f"{len(t)} type pairs for {len(r)} record pairs")
+    out = np.zeros((len(t), 10))
+    iters = np.zeros(len(t), dtype=np.int32)
+    v, vp_ = _d(np.asarray(mesh_verts, dtype=np.float64).reshape(-1, 3)) if mesh_verts is not None else (np.zeros((0, 3)), None)
+    check(lib().mopa_geom_witness_host(len(t), tp, rp, vp_, len(v), float(band), out.ctypes.data_as(_dp), iters.ctypes.data_as(_ip)))
+    return (out, iters) if return_iters else out
 
 
 def model_struct(m, keep: list, pair_geom=None) -> MopaModel:
@@ -836,9 +859,12 @@ class Scene:
         n, pair, dist = self.contacts_state_raw(qpos, cutoff, K)
         return _pair_names(m, pair, dist, n)
 
-    def proximity_state_raw(self, qpos, band: float, max_pairs: int = 8, exact: bool = False):
+    def proximity_state_raw(self, qpos, band: float, max_pairs: int = 8, exact: bool = False, witness: bool = False):
         """(clearance, count, pair [K] int32, dist [K]) of one state: the single-state form of `BatchPlanner.proximity`
-        (exact=True: mopa_proximity_exact_state)"""
+        (exact=True: mopa_proximity_exact_state).  witness=True (needs exact=True; mopa_proximity_witness_state): three more
+        entries normal, p1, p2 [K, 3], 0.0 in unused slots"""
+        if witness and not exact:
+            raise ValueError("witness=True needs exact=True: the inflated route's distance is not attained by two points of the shapes")
         if self.glue is not None:
             raise NotImplementedError("the proximity report of a glued scene")
         sc = self.contact_scene()
@@ -846,16 +872,27 @@ class Scene:
         K = int(max_pairs)
         cl = C.c_double(0.0)
         cnt, pair, dist = self._record_bufs(K)
+        if witness:
+            normal, p1, p2 = (np.zeros((max(K, 1), 3)) for _ in range(3))
+            check(lib().mopa_proximity_witness_state(sc._h, qp, float(band), K, C.byref(cl), C.byref(cnt), pair.ctypes.data_as(_ip), dist.ctypes.data_as(_dp),
+                                                     normal.ctypes.data_as(_dp), p1.ctypes.data_as(_dp), p2.ctypes.data_as(_dp)))
+            return float(cl.value), int(cnt.value), pair, dist, normal, p1, p2
         fn = lib().mopa_proximity_exact_state if exact else lib().mopa_proximity_state
         check(fn(sc._h, qp, float(band), K, C.byref(cl), C.byref(cnt), pair.ctypes.data_as(_ip), dist.ctypes.data_as(_dp)))
         return float(cl.value), int(cnt.value), pair, dist
 
-    def proximity_state(self, qpos, band: float, max_pairs: int = 8, exact: bool = False):
+    def proximity_state(self, qpos, band: float, max_pairs: int = 8, exact: bool = False, witness: bool = False):
         """How far from collision one state is, and which pairs are nearest: -> (clearance, [(geom1_name, geom2_name, dist), ...]),
         clearance = min(band, the smallest pair distance), the list the at most max_pairs nearest non-ignored candidate pairs with
         dist <= band, nearest first.  Distances of disjoint box-box, cylinder and mesh pairs are conservative -- never more than 1e-6
         above the true distance, below it by a shortfall that grows with band ("Proximity report").
-        exact=True: those pairs get their GJK distance instead, true <= d <= true + 1e-6 whatever the band ("Exact route")."""
+        exact=True: those pairs get their GJK distance instead, true <= d <= true + 1e-6 whatever the band ("Exact route").
+        witness=True (needs exact=True): (geom1_name, geom2_name, dist, normal, p1, p2) -- `p1` [3] a point of geom1 and `p2` [3] a
+        point of geom2 at that distance from each other, `normal` [3] the unit vector from p1 towards p2; for a pair in overlap the
+        contact frame's normal and its two witness points ("Witness points")."""
+        if witness:
+            cl, n, pair, dist, normal, p1, p2 = self.proximity_state_raw(qpos, band, max_pairs, exact, True)
+            return cl, [rec + (normal[k].copy(), p1[k].copy(), p2[k].copy()) for k, rec in enumerate(_pair_names(self.model, pair, dist, n))]
         cl, n, pair, dist = self.proximity_state_raw(qpos, band, max_pairs, exact)
         return cl, _pair_names(self.model, pair, dist, n)
 

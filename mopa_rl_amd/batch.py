@@ -125,10 +125,14 @@ class ContactReport:
 class ProximityReport:
     """`BatchPlanner.proximity`: per state `clearance` [N] float64 (min(band, the smallest pair distance): band when no pair is in
     band), `count` [N] int32 (the pairs with dist <= band, not capped) and the K nearest of them, ascending by (dist, pair index):
-    `pair` [N, K] int32 indices into `model.pair_geom` (-1 in unused slots), `dist` [N, K] float64 (MOPA_FAR in unused slots)."""
+    `pair` [N, K] int32 indices into `model.pair_geom` (-1 in unused slots), `dist` [N, K] float64 (MOPA_FAR in unused slots).
+    With witness=True also `p1` / `p2` [N, K, 3] float64 (world frame: a point of the pair's first geom and one of its second, at
+    `dist` from each other; the contact frame's two witness points for a pair in overlap) and `normal` [N, K, 3] (the unit vector
+    from p1 towards p2), 0.0 in unused slots; None otherwise."""
 
-    def __init__(self, clearance, count, pair, dist, model):
+    def __init__(self, clearance, count, pair, dist, model, normal=None, p1=None, p2=None):
         self.clearance, self.count, self.pair, self.dist, self.model = clearance, count, pair, dist, model
+        self.normal, self.p1, self.p2 = normal, p1, p2
 
     def __iter__(self):
         return iter((self.clearance, self.count, self.pair, self.dist))
@@ -233,6 +237,22 @@ def geom_sep(types, recs, band: float, mesh_verts=None, stream=None, exact: bool
     out = torch.empty(M, dtype=torch.float64, device=recs.device)
     fn = _lib.lib().mopa_geom_sep_exact_batch if exact else _lib.lib().mopa_geom_sep_batch
     _lib.check(fn(dev, M, _ptr(types), _ptr(recs), _ptr(mesh_verts) if nvert else None, nvert, float(band), _ptr(out), _stream_handle(stream)))
+    return out
+
+
+def geom_witness(types, recs, band: float, mesh_verts=None, stream=None):
+    """mopa_geom_witness_batch: M posed pairs, one lane each, as `geom_sep` takes them -> [M, 10] = d, n[3], p1[3], p2[3]: the
+    exact route's distance with the pair's two closest points and the unit vector between them, the bits of
+    `_lib.geom_witness_host`"""
+    torch = _torch()
+    M, dev = _pair_batch(types, recs)
+    nvert = 0
+    if mesh_verts is not None:
+        _check_f64(mesh_verts, "mesh_verts", 3)
+        nvert = mesh_verts.shape[0]
+    out = torch.empty(M, 10, dtype=torch.float64, device=recs.device)
+    _lib.check(_lib.lib().mopa_geom_witness_batch(dev, M, _ptr(types), _ptr(recs), _ptr(mesh_verts) if nvert else None, nvert, float(band), _ptr(out),
+                                                  _stream_handle(stream)))
     return out
 
 
@@ -382,7 +402,7 @@ class BatchPlanner:
         return ContactReport(count, pair, dist, self.scene.model, normal, pos, npoint, pdist, ppos)
 
     def proximity(self, q_active, qpos_env, samples_per_env: Optional[int] = None, band: float = 0.05, max_pairs: int = 8,
-                  stream=None, exact: bool = False) -> ProximityReport:
+                  stream=None, exact: bool = False, witness: bool = False) -> ProximityReport:
         """How far from collision every state of a batch is, and which pairs are nearest (states as in `is_valid`): the signed
         distance of every non-ignored candidate pair at or below `band` (>= 0, metres); `clearance` saturates at band, `count`
         is not capped by `max_pairs`, the nearest pairs are kept.  A pair in overlap carries the contact report's bits; disjoint
@@ -390,7 +410,13 @@ class BatchPlanner:
         one, below it by a shortfall that grows with band ("Proximity report").  exact=True
         (mopa_proximity_exact_batch): those pairs get their GJK distance instead -- true <= d <= true + 1e-6, the same bits at
         every band that reports the pair; everything else is unchanged ("Exact route").  One launch of its own on the scene with the
-        full pair list (`Scene.contact_scene`); a glued scene raises."""
+        full pair list (`Scene.contact_scene`); a glued scene raises.
+        witness=True (needs exact=True; mopa_proximity_witness_batch): the report also carries `.normal`, `.p1` and `.p2`, where on
+        the two shapes each reported distance is attained and in which direction (one more launch behind the report; clearance /
+        count / pair / dist are the same bytes; "Witness points").  The inflated route's distance is not attained by any two
+        points of the shapes, so witness=True with exact=False raises ValueError."""
+        if witness and not exact:
+            raise ValueError("witness=True needs exact=True: the inflated route's distance is not attained by two points of the shapes")
         if self.scene.glue is not None:
             raise NotImplementedError("the proximity report of a glued scene")
         torch = _torch()
@@ -402,6 +428,11 @@ class BatchPlanner:
         count = torch.empty(N, dtype=torch.int32, device=dev)
         pair = torch.empty(N, max(K, 1), dtype=torch.int32, device=dev)
         dist = torch.empty(N, max(K, 1), dtype=torch.float64, device=dev)
+        if witness:
+            normal, p1, p2 = (torch.empty(N, max(K, 1), 3, dtype=torch.float64, device=dev) for _ in range(3))
+            _lib.check(_lib.lib().mopa_proximity_witness_batch(sc.handle, _ptr(q_active), _ptr(qpos_env), N, spe, float(band), K, _ptr(clearance), _ptr(count),
+                                                               _ptr(pair), _ptr(dist), _ptr(normal), _ptr(p1), _ptr(p2), _stream_handle(stream)))
+            return ProximityReport(clearance, count, pair, dist, self.scene.model, normal, p1, p2)
         fn = _lib.lib().mopa_proximity_exact_batch if exact else _lib.lib().mopa_proximity_batch
         _lib.check(fn(sc.handle, _ptr(q_active), _ptr(qpos_env), N, spe, float(band), K, _ptr(clearance), _ptr(count), _ptr(pair), _ptr(dist),
                       _stream_handle(stream)))

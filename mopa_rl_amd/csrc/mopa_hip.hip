@@ -34,6 +34,7 @@
 #include "mopa_frames.hpp"
 #include "mopa_manifold.hpp"
 #include "mopa_sep.hpp"
+#include "mopa_witness.hpp"
 #include "mopa_fk.hpp"
 #include "mopa_host.hpp"
 #include "mopa_model_host.hpp"
@@ -1098,6 +1099,8 @@ extern "C" const char *mopa_planner_status(const MopaScene *S) { return S ? S->s
 #include "mopa_contact_manifold.inc"
 // proximity report: k_proximity_rows, mopa_proximity_batch / _state, pair level mopa_geom_sep_batch / _host
 #include "mopa_proximity.inc"
+// witness points behind its exact route: k_proximity_witness, mopa_proximity_witness_batch / _state, pair level mopa_geom_witness_batch / _host
+#include "mopa_proximity_witness.inc"
 // K2 motion report: k_motion_report / k_motion_report_reduce, mopa_motion_report_batch / mopa_motion_report
 #include "mopa_motion_report.inc"
 // K2 clearance report: k_clearance_states / k_motion_clearance_reduce, mopa_motion_clearance_batch / mopa_motion_clearance

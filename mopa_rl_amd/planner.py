@@ -250,13 +250,18 @@ class PyKinematicPlanner:
             return self._scene.contacts_state(np.asarray(state_vec, dtype=np.float64), manifold=True, max_points=max_points, point_cutoff=point_cutoff)
         return self._scene.contacts_state(np.asarray(state_vec, dtype=np.float64), frames=frames)
 
-    def proximity(self, state_vec, band: float, max_pairs: int = 8, exact: bool = False):
+    def proximity(self, state_vec, band: float, max_pairs: int = 8, exact: bool = False, witness: bool = False):
         """how far from collision `state_vec` is and which pairs are nearest: (clearance, [(geom1_name, geom2_name, dist), ...]),
         clearance saturating at `band`, the pairs with dist <= band nearest first (`Scene.proximity_state`); exact=True: GJK distances
-        for disjoint box-box, cylinder and mesh pairs instead of the margin rule's.  With glue_bodies it
-        raises: the proximity report is not built for a glued scene"""
+        for disjoint box-box, cylinder and mesh pairs instead of the margin rule's; witness=True (needs exact=True): the entries
+        become (geom1_name, geom2_name, dist, normal, p1, p2), the pair's two closest points and the unit vector from the first to
+        the second.  With glue_bodies it raises: the proximity report is not built for a glued scene"""
+        if witness and not exact:
+            raise ValueError("witness=True needs exact=True: the inflated route's distance is not attained by two points of the shapes")
         if self.glue_bodies:
             raise NotImplementedError("proximity() with glue_bodies: the proximity report is not built for a glued scene")
+        if witness:
+            return self._scene.proximity_state(np.asarray(state_vec, dtype=np.float64), band, max_pairs, exact=exact, witness=True)
         return self._scene.proximity_state(np.asarray(state_vec, dtype=np.float64), band, max_pairs, exact=exact)
 
     def motion_report(self, start_vec, goal_vec, max_contacts: int = 0) -> dict:

@@ -15,6 +15,11 @@ with its ratio to proximity(band) without the keyword (GJK on the shapes as they
 flag the forms, the rounds and the output are what they were.
 
     python tools/proximity_bench.py --exact --out profiles/r39/proximity_bench.txt
+
+--witness (implies --exact) adds a `witness` column: proximity(band, exact=True, witness=True) at the bands above 0 joins the same
+alternated rounds, and each is reported with its ratio to proximity(band, exact=True) -- the cost of the tail kernel behind the report.
+
+    python tools/proximity_bench.py --witness --out profiles/r42/proximity_bench.txt
 """
 from __future__ import annotations
 
@@ -47,8 +52,10 @@ def main():
     ap.add_argument("--reps", type=int, default=5, help="calls per timed window")
     ap.add_argument("--max-pairs", type=int, default=8)
     ap.add_argument("--exact", action="store_true", help="add proximity(band, exact=True) to the rounds and its ratio to the inflated route")
+    ap.add_argument("--witness", action="store_true", help="add proximity(band, exact=True, witness=True) and its ratio to exact=True alone (implies --exact)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    args.exact = args.exact or args.witness
     sys.path.insert(0, os.path.dirname(HERE))
     import torch
     from mopa_rl_amd import _lib
@@ -77,6 +84,9 @@ def main():
     exact_bands = [b for b in BANDS if b > 0] if args.exact else []
     forms += [(f"proximity(band={b}, exact)", lambda b=b: bp.proximity(q, rows, samples_per_env=S, band=b, max_pairs=args.max_pairs, exact=True))
               for b in exact_bands]
+    witness_bands = exact_bands if args.witness else []
+    forms += [(f"proximity(band={b}, witness)", lambda b=b: bp.proximity(q, rows, samples_per_env=S, band=b, max_pairs=args.max_pairs, exact=True, witness=True))
+              for b in witness_bands]
     for _, fn in forms:
         fn()
     torch.cuda.synchronize()
@@ -99,6 +109,10 @@ def main():
         r = np.array(times[f"proximity(band={b}, exact)"]) / np.array(times[f"proximity(band={b})"])
         lines.append(f"    exact / inflated at band {b}: x {np.median(times[f'proximity(band={b}, exact)']) / np.median(times[f'proximity(band={b})']):.3f}"
                      f"  (per round {r.min():.3f} .. {r.max():.3f})")
+    for b in witness_bands:
+        r = np.array(times[f"proximity(band={b}, witness)"]) / np.array(times[f"proximity(band={b}, exact)"])
+        lines.append(f"    witness / exact at band {b}: x {np.median(times[f'proximity(band={b}, witness)']) / np.median(times[f'proximity(band={b}, exact)']):.3f}"
+                     f"  (per round {r.min():.3f} .. {r.max():.3f})")
     lines.append("")
     for b in BANDS:
         c = reps[b].count
@@ -110,6 +124,15 @@ def main():
         gain = ex.clearance - reps[b].clearance
         lines.append(f"    band {b}, exact: pairs in band per state: mean {ex.count.double().mean().item():.2f};  clearance above the inflated one: "
                      f"mean {gain.mean().item():.2e}, max {gain.max().item():.2e}, min {gain.min().item():.2e}")
+    for b in witness_bands:
+        ex = bp.proximity(q, rows, samples_per_env=S, band=b, max_pairs=args.max_pairs, exact=True)
+        wt = bp.proximity(q, rows, samples_per_env=S, band=b, max_pairs=args.max_pairs, exact=True, witness=True)
+        torch.cuda.synchronize()
+        assert all(torch.equal(a, c) for a, c in zip(ex, wt)), "witness=True changed the report's rows"
+        used = wt.dist < 1.0e9
+        sep = used & (wt.dist > 0)
+        err = ((wt.p2 - wt.p1).norm(dim=2) - wt.dist)[sep].abs().max().item() if bool(sep.any()) else 0.0
+        lines.append(f"    band {b}, witness: records {int(used.sum())}, of them separated {int(sep.sum())};  largest | |p2 - p1| - dist | over those: {err:.2e}")
     text = "\n".join(lines) + "\n"
     print(text)
     if args.out:
